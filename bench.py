@@ -19,7 +19,8 @@ carries the normalisers.  `--scaling weak` gives every rank its own set of the g
     python bench.py                                   # cfg4, 1 GPU
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Beside `value` (inputs resident in HBM) the line carries `roofline` (dominant kernel, HIP events on the library's stream),
+A plain run sets up, warms up, times the steps and prints the line (`--dump-outputs DIR`: the last timed step's tables as .npy).  With
+`--full`, beside `value` (inputs resident in HBM) the line carries `roofline` (dominant kernel, HIP events on the library's stream),
 `from_gaf_text` (the same workload from GAF text on disk -> tables, PCIe + device tokenizer included), `pao_hard` (a
 synthetic variant whose first filter keeps all ten strains: the LP regime BASELINE.md section 2 flags) and
 `cpu_baseline`: the plain-C oracle on all host cores, one species per worker thread like profile.rs:3297-3319, on a bounded
@@ -176,6 +177,27 @@ def _mem_available_gb():
     return None
 
 
+def host_threads_of(world=1):
+    """Host threads for one of `world` ranks: the CPUs this process may use (affinity mask, cgroup CPU quota) shared by the ranks,
+    at most OMP_NUM_THREADS when that is set.  os.cpu_count() counts the whole machine, which may be many times what a job is given."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    n = max(1, n // max(world, 1))
+    try:
+        n = min(n, int(os.environ["OMP_NUM_THREADS"]))
+    except (KeyError, ValueError):
+        pass
+    return max(1, n)
+
+
 def _cgroup_limit_gb():
     for fn in ("/sys/fs/cgroup/memory.max", "/sys/fs/cgroup/memory/memory.limit_in_bytes"):
         try:
@@ -261,7 +283,7 @@ def cpu_leg_child(args):
         spec = workload_spec(args.workload, args.species, args.haps, args.reads, args.genome_len)
         cfg = StepConfig(fr=0.5) if spec.get("long_reads") else StepConfig()
         cfgd = dict(fr=cfg.fr, fc=cfg.fc, sr=cfg.sr)
-        cores = args.cpu_cores or (os.cpu_count() or 1)
+        cores = args.cpu_cores or host_threads_of()
         t_g = time.perf_counter()
         ns = native_set(spec, threads=min(cores, 64))
         n_chunks = synth.N_CHUNKS if spec["reads"] <= CPU_SAMPLE_READS else max(1, (synth.N_CHUNKS * CPU_SAMPLE_READS) // spec["reads"])
@@ -680,6 +702,44 @@ def file_seam_leg(local_rank, species, gaf_path, td, threads, out, n_reads, fr=0
     return res
 
 
+def dump_outputs(path, out):
+    """--dump-outputs DIR: what the last timed step returned to its caller, (species_rows, strain_rows, stats), as float64 .npy files.
+    A species is given by its taxid, a strain by the digits of its assembly name (both are numbers in every synthetic set).  Every value
+    is finite: an absent one (an Option that is None, the objective of an LP that was not solved) is 0.0 beside a flag that says so,
+    as in the slab the ranks exchange (pipeline.rows_to_array).  The rows keep the order of the tables."""
+    import re
+    species_rows, strain_rows, stats = out
+    num = lambda name: float(int(re.sub(r"\D", "", name)))
+
+    def strain_row(r):
+        opt = r[4:]
+        return (num(r[0]), num(r[1]), r[2], r[3], float(sum(1 << i for i, v in enumerate(opt) if v is not None))) + tuple(0.0 if v is None else v for v in opt)
+    obj = np.array(stats["obj"], dtype=np.float64).reshape(-1, 2)
+    obj_set = np.isfinite(obj)
+    arrays = {
+        # species_taxid, predicted_abundance, predicted_coverage
+        "species_table": np.array([(num(r[0]), r[1], r[2]) for r in species_rows], dtype=np.float64).reshape(-1, 3),
+        # species_taxid, strain, predicted_coverage, predicted_abundance, option bits (bit i: value i is present), then the six values in
+        # order (0.0 when absent): path_base_cov, unique_trio_fraction, uniq_trio_cov_mean, first_sol, strain_cov_diff, total_cov_diff
+        "strain_table": np.array([strain_row(r) for r in strain_rows], dtype=np.float64).reshape(-1, 11),
+        # per species of this rank's shard: the two LP solves' objectives (0.0 where lp_objective_set is 0: no solve) and iterations, LP
+        # rows, candidate columns, row patterns
+        "lp_objective": np.where(obj_set, obj, 0.0),
+        "lp_objective_set": obj_set.astype(np.float64),
+        "lp_iterations": np.array(stats["iters"], dtype=np.float64).reshape(-1, 2),
+        "lp_rows": np.array(stats["n_rows"], dtype=np.float64),
+        "lp_candidates": np.array(stats["n_cand"], dtype=np.float64),
+        "lp_patterns": np.array(stats["n_patterns"], dtype=np.float64),
+    }
+    bad = [name for name, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise ValueError("--dump-outputs: non-finite values in %s" % ", ".join(bad))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
 def run_many_dbs(args, spec, local_rank):
     """A workload of more path steps than one resident db addresses (32-bit positions: BASELINE configs[4] at its size, 1 000 species x 50
     strains = 1.1e10 path steps) on ONE GPU: the species are cut into contiguous groups under the limit, every group is a db on a ctx of its
@@ -691,7 +751,7 @@ def run_many_dbs(args, spec, local_rank):
     import torch
     cfg = StepConfig(fr=0.5) if spec.get("long_reads") else StepConfig()
     n_species, n_haps, n_reads, genome_len = spec["species"], spec["haps"], spec["reads"], spec["genome_len"]
-    host_threads = max(1, min(64, os.cpu_count() or 1))
+    host_threads = min(64, host_threads_of())
     torch.cuda.set_device(local_rank)
     t_gen = time.perf_counter()
     ns = native_set(spec, threads=host_threads)
@@ -745,22 +805,26 @@ def run_many_dbs(args, spec, local_rank):
         return tot
     run(2)
     barrier()
-    for e in engs:
-        e.timing_enable(True); e.timing_reset()
-    # the per-kernel clocks (kernel table, roofline) come from warm-up steps in which the dbs are stepped ONE AFTER THE OTHER: side by side, a
-    # kernel's events also span the other dbs' kernels it shares the GPU with, and the table would add up to several times the step
     n_warm = max(args.warmup, 1)
-    barrier()
-    t_ser = time.perf_counter()
-    out = run(n_warm, serial=True)[-1]
-    barrier()
-    ms_serial = (time.perf_counter() - t_ser) / n_warm * 1e3
-    warm = timings()
-    cov_kernel = "coverage_fast_kernel" if "coverage_fast_kernel" in warm else ("coverage_long_kernel" if "coverage_long_kernel" in warm else "coverage_step_kernel")
-    top2 = [k for k, _ in sorted(warm.items(), key=lambda kv: -kv[1][1])[:6]]
-    for e in engs:
-        e.timing_enable(False)
-    run(1)
+    if args.full:
+        for e in engs:
+            e.timing_enable(True); e.timing_reset()
+        # the per-kernel clocks (kernel table, roofline) come from warm-up steps in which the dbs are stepped ONE AFTER THE OTHER: side by side, a
+        # kernel's events also span the other dbs' kernels it shares the GPU with, and the table would add up to several times the step
+        barrier()
+        t_ser = time.perf_counter()
+        out = run(n_warm, serial=True)[-1]
+        barrier()
+        ms_serial = (time.perf_counter() - t_ser) / n_warm * 1e3
+        warm = timings()
+        cov_kernel = "coverage_fast_kernel" if "coverage_fast_kernel" in warm else ("coverage_long_kernel" if "coverage_long_kernel" in warm else "coverage_step_kernel")
+        top2 = [k for k, _ in sorted(warm.items(), key=lambda kv: -kv[1][1])[:6]]
+        for e in engs:
+            e.timing_enable(False)
+        run(1)
+    else:
+        # a plain run: the warm-up steps go through the path that is timed below (the dbs side by side), without per-kernel clocks
+        run(n_warm)
     import gc
     gc.collect(); gc.freeze()
     barrier()
@@ -768,6 +832,32 @@ def run_many_dbs(args, spec, local_rank):
     out = run(args.steps)[-1]
     barrier()
     dt = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs else None
+    species_rows, strain_rows, stats = out
+    ms_per_step = dt / args.steps * 1e3
+    if not args.full:
+        line = {
+            "metric": "PAO wall-time (s) + Mreads/s: packed reads + DBs (graphs and their unique-trio index) resident in HBM -> abundance tables",
+            "value": n_reads / (dt / args.steps) / 1e6, "unit": "Mreads/s", "n_gpus": 1, "steps": args.steps, "warmup": n_warm,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "int64+f64", "data": "synthetic",
+            "config": {"workload": "%s: %d species x %d strains, %d %s, genome %d bp, seed %d, generator %s"
+                                   % (spec["name"], n_species, n_haps, n_reads, "long reads N(15000, 3000^2) bp" if spec.get("long_reads") else "short reads (150 bp)",
+                                      genome_len, spec["seed"], GENERATOR),
+                       "baseline_config": spec["label"][:60], "dbs_on_the_gpu": K, "species_per_db": [b - a for a, b in groups],
+                       "gsteps_per_s": sum(T_l) / (dt / args.steps) / 1e9, "strains_total": n_species * n_haps, "reads_total": n_reads,
+                       "parallelism": "species-shard x1 (%d dbs side by side)" % K, "pao_wall_s": ms_per_step / 1e3,
+                       "n_species_rows": len(species_rows), "n_strain_rows": len(strain_rows), "upload_ms_once": upload_ms,
+                       "synthetic_set_generated_in_s": gen_s, "sample_nodes": 0, "host_threads": host_threads},
+            "result": {"n_species_rows": len(species_rows), "n_strain_rows": len(strain_rows),
+                       "top_strains": [(r[0], r[1], round(r[2], 4), round(r[3], 6)) for r in strain_rows[:3]]},
+            "full": False,
+        }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
+        print(json.dumps(line), flush=True)
+        for e in engs:
+            e.close()
+        return
     tm = warm
     run(1, cfg)
     barrier()
@@ -831,6 +921,9 @@ def run_many_dbs(args, spec, local_rank):
         "result": {"n_species_rows": len(species_rows), "n_strain_rows": len(strain_rows),
                    "top_strains": [(r[0], r[1], round(r[2], 4), round(r[3], 6)) for r in strain_rows[:3]]},
     }
+    line["full"] = True
+    if dumped is not None:
+        line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
     detail = {"line": line, "abundance_l1": l1, "kernels_ms_per_step_all": {k: v[1] / n_warm for k, v in sorted(warm.items(), key=lambda kv: -kv[1][1])},
               "reads_per_db": R_l, "steps_per_db": T_l, "host": {"cores": os.cpu_count(), "mem_available_gb": _mem_available_gb()}}
     dpath = args.detail_file or os.path.join(ROOT, "gpurun_out", "bench_detail_%s_n1.json" % spec["name"])
@@ -844,6 +937,58 @@ def run_many_dbs(args, spec, local_rank):
     print(json.dumps(line), flush=True)
     for e in engs:
         e.close()
+
+
+def plain_line(args, spec, world, rank, eng, dt, out, dumped, total_reads, T_res, S_loc, n_species, n_haps, ns, ranks_seen, backend, setup):
+    """The end of a run without --full: the ranks' slowest timed region makes `value`, rank 0 prints the line, the ranks close."""
+    import torch
+    dt_min = dt_max = dt
+    if world > 1:
+        import torch.distributed as dist
+        t = torch.tensor([dt, -dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt_max, dt_min = float(t[0].item()), -float(t[1].item())
+        dt = dt_max
+    if rank == 0:
+        species_rows, strain_rows, stats = out
+        ms_per_step = dt / args.steps * 1e3
+        line = {
+            "metric": "PAO wall-time (s) + Mreads/s: packed reads + DB (graphs and their unique-trio index) resident in HBM -> abundance tables; "
+                      "the metric's own GAF -> abundance quantity is value_gaf_to_tables (files -> tables, never `value`)",
+            "value": total_reads / (dt / args.steps) / 1e6, "unit": "Mreads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": "int64+f64", "data": "synthetic",
+            "config": dict({"workload": "%s: %d species x %s strains, %d %s, genome %d bp, seed %d, generator %s"
+                                        % (spec["name"], n_species, n_haps, spec["reads"], "long reads N(15000, 3000^2) bp" if spec.get("long_reads") else "short reads (150 bp)",
+                                           spec["genome_len"], spec["seed"], GENERATOR),
+                            "gsteps_per_s": T_res * world / (dt / args.steps) / 1e9,
+                            "baseline_config": spec["label"][:60], "set": "per GPU" if args.scaling == "weak" else "one set cut over the ranks",
+                            "species_per_gpu": S_loc,
+                            "strains_total": (int(ns.n_haps.sum()) if spec.get("refdb") else n_species * n_haps * (world if args.scaling == "weak" else 1)),
+                            "reads_total": total_reads, "parallelism": "species-shard x%d" % world,
+                            "rccl_ranks": ranks_seen if backend == "nccl" else None, "ranks_seen": ranks_seen,
+                            "exchange": "none" if world == 1 else ("one rccl all_reduce per step" if backend == "nccl" else backend + " all_reduce (dry run)"),
+                            "pao_wall_s": ms_per_step / 1e3,
+                            "value_times": "resident step over a resident DB (graphs + the DB's unique-trio index, SURVEY 8f-2): bin -> species decision -> coverage -> filters -> LPs -> tables",
+                            "ms_per_step_ranks_min_max": [dt_min / args.steps * 1e3, dt_max / args.steps * 1e3],
+                            "lp_rows_total": int(sum(stats["n_rows"])), "n_species_rows": len(species_rows), "n_strain_rows": len(strain_rows),
+                            "sample_nodes": 0}, **setup),
+            "result": {"n_species_rows": len(species_rows), "n_strain_rows": len(strain_rows),
+                       "top_strains": [(r[0], r[1], round(r[2], 4), round(r[3], 6)) for r in strain_rows[:3]]},
+            "full": False,
+        }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
+        print(json.dumps(line), flush=True)
+    if os.environ.get("PANTAX_BENCH_RSS"):     # tools/strong_dry_run.sh: what a rank needs of the host
+        import resource
+        print("rank %d: peak host RSS %.1f GB" % (rank, resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1048576.0), file=sys.stderr, flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+    eng.close()
+    if world > 1:
+        dist.destroy_process_group()
 
 
 def launch_ranks(n):
@@ -899,7 +1044,13 @@ def main():
     ap.add_argument("--genome-len", type=int, default=None)
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="strong (default): ONE set of the given size cut over the ranks; weak: one such set per rank")
-    ap.add_argument("--cpu-cores", type=int, default=0, help="worker threads of the CPU baseline (0 = all host cores)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, every side measurement and check: CPU baseline, index-rebuild steps, from-GAF-text and file-seam "
+                         "legs, pao_hard, abundance L1 against the oracle, per-kernel table and roofline, detail file (the --no-* options below pick "
+                         "among them).  Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the tables the last timed step returned as DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--cpu-cores", type=int, default=0, help="worker threads of the CPU baseline (0 = every CPU this process may use)")
     ap.add_argument("--highs-rows", default="2000,5000,10000", help="row samples of the HiGHS legs ('' = none)")
     ap.add_argument("--highs-time-limit", type=float, default=25.0)
     ap.add_argument("--highs-full-time-limit", type=float, default=120.0, help="time limit of HiGHS on the FULL LP of one species (0 = skip)")
@@ -918,6 +1069,10 @@ def main():
         sys.exit(cpu_leg_child(args))
     if args.seam_child:
         sys.exit(seam_child(args.seam_child))
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:       # a plain run: the side legs are all off
+        args.no_cpu_baseline = args.no_gaf = args.no_seam = args.no_hard = args.no_l1 = True
     # ---- `python3 bench.py --gpus N` without a launcher around it: this process -- which has touched neither torch nor the GPU --
     # starts the N ranks as a CHILD (never an exec) and relays rank 0's line and the exit code
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
@@ -984,7 +1139,7 @@ def main():
 
     # ---- deterministic synthetic input (seed = 20260501 + cfg index).  strong: ONE set; this rank generates its
     # slice of the reads (chunks of the generator) and, later, the graphs of the species it owns.  weak: one set per rank.
-    host_threads = max(1, min(64, (os.cpu_count() or 1) // max(world, 1)))
+    host_threads = min(64, host_threads_of(world))
     strong = args.scaling == "strong"
     t_gen = time.perf_counter()
     ns = native_set(spec, threads=host_threads, seed_shift=0 if strong else 1000 * rank)
@@ -1086,8 +1241,9 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
-    eng.timing_enable(True)
-    eng.timing_reset()
+    if args.full:           # the per-kernel clocks (kernel table, roofline) run with --full only
+        eng.timing_enable(True)
+        eng.timing_reset()
     n_warm_timed = 0
     if args.warmup:
         # the very first step also allocates: its launches are not representative
@@ -1099,15 +1255,16 @@ def main():
         eng.timing_reset()
         n_warm_timed = args.warmup - 1
         out = run_steps(n_warm_timed)[-1]
-    warm = eng.timing_get() if args.warmup else {}
-    # the two largest of the warm-up table are bracketed in the timed steps; the dominant kernel is the one with the larger
-    # average THERE
-    cov_kernel = "coverage_fast_kernel" if (not warm or "coverage_fast_kernel" in warm) else ("coverage_long_kernel" if "coverage_long_kernel" in warm else "coverage_step_kernel")   # short reads / long reads
-    # the six largest of the warm-up table are bracketed in the timed steps as well (a dozen event records per step)
-    top2 = [k for k, _ in sorted(warm.items(), key=lambda kv: -kv[1][1])[:6]] if warm else [cov_kernel]
-    # ... and the coverage kernel always (the histogram is the path's named kernel)
-    eng.timing_filter("|".join(top2 + [k for k in [cov_kernel] if k not in top2]))
-    eng.timing_reset()
+    if args.full:
+        warm = eng.timing_get() if args.warmup else {}
+        # the two largest of the warm-up table are bracketed in the timed steps; the dominant kernel is the one with the larger
+        # average THERE
+        cov_kernel = "coverage_fast_kernel" if (not warm or "coverage_fast_kernel" in warm) else ("coverage_long_kernel" if "coverage_long_kernel" in warm else "coverage_step_kernel")   # short reads / long reads
+        # the six largest of the warm-up table are bracketed in the timed steps as well (a dozen event records per step)
+        top2 = [k for k, _ in sorted(warm.items(), key=lambda kv: -kv[1][1])[:6]] if warm else [cov_kernel]
+        # ... and the coverage kernel always (the histogram is the path's named kernel)
+        eng.timing_filter("|".join(top2 + [k for k in [cov_kernel] if k not in top2]))
+        eng.timing_reset()
     barrier()
     # K steps back to back; with N > 1 the all-reduce of step i is in flight while step i+1 computes (every step's tables
     # are complete before the closing barrier)
@@ -1118,6 +1275,11 @@ def main():
     dt = time.perf_counter() - t0
     if os.environ.get("PANTAX_PIPE_TRACE"):
         print("[bench] timed region: %.2f ms of steps + %.2f ms in the closing barrier" % (t_steps * 1e3, (dt - t_steps) * 1e3), file=sys.stderr)
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs and rank == 0 else None
+    if not args.full:
+        return plain_line(args, spec, world, rank, eng, dt, out, dumped, total_reads, T_res, S_loc, n_species, n_haps, ns, ranks_seen, backend,
+                          dict(synthetic_set_generated_in_s=gen_s, upload_ms_once=upload_ms, index_first_build_ms=index_first_build_ms,
+                               step_path_primed_ms_once=prime_ms, ingest_route_ms=(ingest_route or {}).get("ms"), host_threads=host_threads))
     cpu_child_alive = False                         # the child's HiGHS legs wait (it sleeps on a file between its oracle leg and them) ...
     timings = eng.timing_get()
     eng.timing_enable(False)
@@ -1425,6 +1587,9 @@ def main():
                                            "pcie_floor_s": (moved_gb / h2d) if h2d else None}
         if cpu is not None:
             line["cpu_baseline"] = cpu
+        line["full"] = True
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
         line["kernels_ms_per_step"] = {k: round(v[1] / max(n_warm_timed, 1), 3) for k, v in sorted(warm.items(), key=lambda kv: -kv[1][1])[:14]}
         line["result"] = {"n_species_rows": len(species_rows), "n_strain_rows": len(strain_rows),
                           "top_strains": [(r[0], r[1], round(r[2], 4), round(r[3], 6)) for r in strain_rows[:3]]}

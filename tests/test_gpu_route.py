@@ -191,7 +191,7 @@ def test_bench_over_two_gpus_gives_the_one_gpu_tables():
     from tests.conftest import ROOT
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (RCCL refuses two ranks on one device)")
-    common = ["--workload", "cfg3", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-gaf", "--no-hard"]
+    common = ["--workload", "cfg3", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-gaf", "--no-hard"]
     lines = []
     for n in (1, 2):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n)] + common, capture_output=True, text=True, timeout=900, cwd=ROOT)
