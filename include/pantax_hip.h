@@ -196,6 +196,27 @@ int pantax_hip_abundance_filter(uint32_t n_species, const uint64_t *hap_off, con
                                 double *sum_all_out, double *sum_pass_out,
                                 double *species_sum_all_out /*[S] or NULL*/, double *species_sum_pass_out /*[S] or NULL*/);
 
+/* ---- per-read strain assignment (the --read-strains report; not a stage of the reference): which candidate strain of its species
+ * every read supports.  N(r) = the distinct nodes of the walk of read r; C(r) = the candidates of r's species whose walk visits every
+ * node of N(r) (node-set containment: order and orientation ignored, the node-level model of the LP, profile.rs:1333-1342).  The
+ * assigned strain is the argmax of the weight over C(r), ties to the smallest species-local haplotype index; posterior = w_assigned /
+ * the sum of w over C(r), summed in f64 in ascending haplotype index.  The file seam takes the rows of strain_abundance.txt as the
+ * candidates (the a15 filter, pantax_hip_abundance_filter's pass_out) and their unrounded predicted_coverage as the weights.
+ * Requires pantax_hip_bin_reads of `reads` against `db` (else PANTAX_HIP_E_STATE).  Outputs are host arrays of R entries in file order;
+ * ONLY the entries of reads binned to a species of `db` are written (every other entry keeps what the caller put there, so a caller
+ * can loop over groups of species):
+ *   counted reads (the coverage pass uses them): hap_out = species-local haplotype index of the assigned strain, n_out = |C(r)|,
+ *     post_out = posterior; C(r) empty: 0xFFFFFFFF, 0, 0.0;
+ *   reads dropped by their flags (null field, duplicate-id rule) and reads of a species without candidates: 0xFFFFFFFF, -1, 0.0. */
+typedef struct {
+    uint32_t n_species;         /* must equal the db's */
+    const uint64_t *cand_off;   /* [S+1] species s owns candidates [cand_off[s], cand_off[s+1]) */
+    const uint32_t *cand_hap;   /* [C] species-local haplotype index (any order, no repeats) */
+    const double *cand_w;       /* [C] weight of the candidate */
+} pantax_hip_read_strain_set;
+int pantax_hip_read_strains(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
+                            uint32_t *hap_out /*[R]*/, int32_t *n_out /*[R]*/, double *post_out /*[R]*/);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -375,6 +396,13 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
     double minimization_min_cov;    /* types.rs:72 (main.rs:150 sets 0; no CLI flag).  It only shifts the indicator rows z_i >= (x_i - this) / (2 max), and the
                                      * indicators are bound by nothing but sum z <= npaths (profile.rs:1374-1378): INERT at any value.  Mirrored for
                                      * completeness of the struct; negative or non-finite values are refused. */
+    /* --read-strains: path of the per-read strain report (pantax_hip_read_strains over every group of species; NULL or "None" = off).
+     * TSV without header, one row per GAF record in the order and count of the -R report (the two files join by position):
+     * read_id, species_taxid (both as in the -R report), genome_ID, strain_taxid (the genomes_info.txt join of the strain table),
+     * n_compatible, posterior (shortest round-trip digits).  No strain: "U U 0 0" when no candidate contains the read's nodes,
+     * "U U - 0" when the read is not counted in a species or its species has no candidates.  Written only by a run that performs the
+     * strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
+    const char *read_strain_file;
 } pantax_hip_profiling_config;
 
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in

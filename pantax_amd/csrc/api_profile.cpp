@@ -78,6 +78,12 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
     const bool use_comm = W > 1 || (cfg->world_size == 1 && cfg->allreduce_sum != nullptr);
     const bool sharded = use_comm && cfg->alltoallv != nullptr;
     if (sharded && W > 64) return fail(ctx, PANTAX_HIP_E_LIMIT, "profile: the sharded ingest routes reads to at most 64 ranks (world_size %d)", W);
+    // --read-strains: the rows of a species live on the rank that owns it, the rows of the file on the rank of its byte range -- not joined here
+    const std::string rs_path = opt(cfg->read_strain_file);
+    const bool want_rs = !rs_path.empty() && rs_path != "None";
+    if (want_rs && (W > 1 || sharded))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-read strain report (read_strain_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
+                    sharded ? ", sharded" : "");
     auto allreduce = [&](double *buf, uint64_t n) -> int {
         if (!use_comm) return 0;
         const int rc = cfg->allreduce_sum(cfg->comm_user, buf, n);
@@ -117,7 +123,9 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
         PTX_TRY(allreduce(d, 3));
         full_path = d[0] != 0.0; strain_only = d[1] != 0.0; strain_done = d[2] != 0.0;
     }
-    if (!full_path && !strain_only) return 0;   // profile.rs:3419-3427: outputs already present
+    auto rs_skipped = [&]() { if (want_rs) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", rs_path.c_str()); };
+    if (!full_path && !strain_only) { rs_skipped(); return 0; }   // profile.rs:3419-3427: outputs already present
+    const bool rs_run = want_rs && cfg->strain && !(full_path && strain_done);   // this call runs a strain step and writes the report
     mkdir(out_dir.c_str(), 0777);
 
     // PANTAX_HIP_TRACE=1: wall time of each phase on stderr (the reference logs its phases through env_logger)
@@ -210,7 +218,7 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
         // two reads do share an id (host_cols below).  A plain run on distinct ids needs the species COUNTERS and the first rows only.
         // (no locus-grouped copy yet: the species decision needs the counters only -- the plain columns are binned in file order --, and the copy is
         // built while the first graphs travel, on an otherwise idle device; round 5 built it here, 27 ms behind the last byte of the GAF at 1e8 reads)
-        PTX_TRY(gaf_tokenize_device(ctx, mf.data + text_begin, text_end - text_begin, hr, reads.rd, mf.fd, text_begin, /*group=*/false, /*want_id_spans=*/want_report,
+        PTX_TRY(gaf_tokenize_device(ctx, mf.data + text_begin, text_end - text_begin, hr, reads.rd, mf.fd, text_begin, /*group=*/false, /*want_id_spans=*/want_report || rs_run,
                                     /*want_host_columns=*/false));
         R = reads.rd->R;
         lap("ranges + GAF tokenise");
@@ -239,7 +247,7 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
         return 0;
     };
     int local_rc = ingest();
-    if (local_rc == 0 && (want_report || sharded || strain_only)) local_rc = host_cols();
+    if (local_rc == 0 && (want_report || sharded || strain_only || rs_run)) local_rc = host_cols();
     // the read lengths of the first (up to 1000) binned rows of the FILE decide the equal-length branch (profile.rs:312-319): they are among the
     // first rows the binning pass hands back with its counters, unless those hold fewer than 1000 binned rows of a longer file
     std::vector<uint32_t> head;
@@ -367,7 +375,7 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
         out.close();
         if (!ok || !out) local_rc = fail(ctx, PANTAX_HIP_E_IO, "cannot join the parts of %s", report.c_str());
     }
-    if (full_path && (!cfg->strain || strain_done)) return agree(local_rc);
+    if (full_path && (!cfg->strain || strain_done)) { rs_skipped(); return agree(local_rc); }
 
     lap("species table / report");
     // ---- a4: load_species_range (profile.rs:553-656)
@@ -391,7 +399,7 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
         if (!ds.empty() && !ds.count(row.species)) continue;
         any_after_ds = true;
     }
-    if (!any_after_ds) return agree(local_rc);   // reference: warn + exit(0) (profile.rs:595-598); the same decision on every rank
+    if (!any_after_ds) { rs_skipped(); return agree(local_rc); }   // reference: warn + exit(0) (profile.rs:595-598); the same decision on every rank
     for (auto &row : sp_profile) {
         if (!(row.abundance > cfg->min_species_abundance)) continue;                 // :602
         auto it = range_idx.find(row.species);
@@ -523,6 +531,11 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
     std::vector<pantax_hip_solve_info> info;
     std::vector<uint64_t> hap_off(1, 0);
     std::vector<std::string> hap_names;
+    // --read-strains, file order: global haplotype index (into hap_names) of the assigned strain or ~0, |C(r)| or -1 (not counted), posterior
+    std::vector<uint64_t> rs_hap;
+    std::vector<int32_t> rs_n;
+    std::vector<double> rs_post;
+    if (rs_run) { rs_hap.assign(R, ~0ull); rs_n.assign(R, -1); rs_post.assign(R, 0.0); }
     // which rank takes which selected species: longest-processing-time packing on (reads binned to the species + its graph
     // nodes), heaviest first onto the least loaded rank; every rank computes the same table from the same inputs
     std::vector<int> owner(Ss, 0);
@@ -794,6 +807,39 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
                                         cfg->sample_test ? 500 : cfg->sample_nodes, cfg->solver_semantics};
             PTX_TRY(pantax_hip_strain_profile(ctx, sdb.db, &sc, nullptr, cov.data() + k0, met.data() + hap_off[k0], info.data() + k0));
             lap("strain step");
+            if (rs_run) {
+                // the candidates are this group's rows of strain_abundance.txt: the a15 filter is row-local, so the group decides it in its own turn
+                std::vector<uint8_t> rep_g(Sg);
+                for (uint32_t k = k0; k < k1; ++k) rep_g[k - k0] = (info[k].status1 == 0 && info[k].status2 == 0) ? 1 : 0;
+                std::vector<uint8_t> pass_g(hap_names.size() ? hap_names.size() : 1, 0);
+                PTX_TRY(pantax_hip_abundance_filter(Sg, hap_off.data() + k0, met.data(), rep_g.data(), cfg->single_cov_diff, cfg->min_cov, pass_g.data(),
+                                                    nullptr, nullptr, nullptr, nullptr));
+                std::vector<uint64_t> c_off(Sg + 1, 0);
+                std::vector<uint32_t> c_hap;
+                std::vector<double> c_w;
+                for (uint32_t k = k0; k < k1; ++k) {
+                    for (uint64_t h = hap_off[k]; h < hap_off[k + 1]; ++h)
+                        if (pass_g[h]) { c_hap.push_back((uint32_t)(h - hap_off[k])); c_w.push_back(met[h].second_sol); }
+                    c_off[k - k0 + 1] = c_hap.size();
+                }
+                const pantax_hip_read_strain_set cs{Sg, c_off.data(), c_hap.data(), c_w.data()};
+                constexpr int32_t UNTOUCHED = -3;   // entries of reads outside this group's species keep it
+                std::vector<uint32_t> t_hap(R, 0u);
+                std::vector<int32_t> t_n(R, UNTOUCHED), g_sp(R, -1);
+                std::vector<double> t_post(R, 0.0);
+                PTX_TRY(pantax_hip_read_strains(ctx, sdb.db, sreads_rd, &cs, t_hap.data(), t_n.data(), t_post.data()));
+                if (R) {   // the group-local species of every read (the slot records of this group's binning pass)
+                    PTX_TRY(species_ensure(ctx, sreads_rd));
+                    PTX_TRY(download(ctx, g_sp.data(), sreads_rd->d_species.p, R));
+                    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                }
+                for (uint64_t r = 0; r < R; ++r) {
+                    if (t_n[r] == UNTOUCHED) continue;
+                    rs_n[r] = t_n[r]; rs_post[r] = t_post[r];
+                    rs_hap[r] = t_n[r] > 0 && g_sp[r] >= 0 ? hap_off[k0 + (uint32_t)g_sp[r]] + t_hap[r] : ~0ull;
+                }
+                lap("  read strains");
+            }
             if (cfg->image_cache == 2) {   // leave images behind for the next run
                 for (uint32_t k = k0; k < k1; ++k)
                     if (src[use[k]].kind != 1) {
@@ -924,6 +970,28 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
     f << header;
     for (auto &r : final_rows) f << r.line << '\n';
     lap("tables");
+    if (rs_run) {
+        // one row per GAF record, in the -R report's order (read_id and species_taxid are its columns 1 and 3)
+        std::unordered_map<std::string, size_t> first_genome;   // the first genomes_info.txt row of every haplotype (the strain table's left join)
+        for (size_t i = genomes.size(); i-- > 0;) first_genome[genomes[i].hap_id] = i;
+        std::ofstream rf(rs_path);
+        if (!rf) return fail(ctx, PANTAX_HIP_E_IO, "cannot write %s", rs_path.c_str());
+        for (uint64_t r = 0; r < R; ++r) {
+            rf.write(mf.data + text_begin + hr.id_span[r].first, hr.id_span[r].second);
+            rf << '\t' << (sp_idx[r] >= 0 ? ranges[sp_idx[r]].species : std::string("U")) << '\t';
+            if (rs_n[r] < 0) rf << "U\tU\t-\t0\n";
+            else if (rs_n[r] == 0 || rs_hap[r] == ~0ull) rf << "U\tU\t0\t0\n";
+            else {
+                auto it = first_genome.find(hap_names[rs_hap[r]]);
+                if (it != first_genome.end()) rf << genomes[it->second].genome_id << '\t' << genomes[it->second].strain_taxid;
+                else rf << '\t';
+                rf << '\t' << rs_n[r] << '\t' << fmt_f64(rs_post[r]) << '\n';
+            }
+        }
+        rf.close();
+        if (!rf) return fail(ctx, PANTAX_HIP_E_IO, "cannot write %s", rs_path.c_str());
+        lap("read strains report");
+    }
     return 0;
 }
 

@@ -16,6 +16,8 @@ static void usage() {
             "  --min_cov N  --min_depth N  --sample N (default 500000)  --sample_test  --ds a,b,c  --smode 0|1  --no-filter\n"
             "  --solver gurobi|highs|cplex|cbc|glpk   whose second-solve semantics to reproduce (the LP optimum is the same; default gurobi)\n"
             "  --force  -R <reads_classification.tsv>  --range-file F  --species-len-file F  --reads-binning-file F\n"
+            "  --read-strains F   per-read strain report: one row per GAF record (the -R order) with read_id, species_taxid, genome_ID,\n"
+            "                     strain_taxid, n_compatible, posterior of the reported strain that contains the read's nodes (one rank only)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -85,6 +87,7 @@ int main(int argc, char **argv) {
         else if (a == "--range-file") c.range_file = next();
         else if (a == "--species-len-file") c.species_len_file = next();
         else if (a == "--reads-binning-file") c.reads_binning_file = next();
+        else if (a == "--read-strains") c.read_strain_file = next();
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

@@ -143,6 +143,7 @@ struct CtxConfig {
     std::string mask;                // "walk": membership masks from the path walk
     std::string row_sort;            // "radix" / "nodes"
     std::string objective;           // "nodes": the LP objective summed over the nodes
+    std::string read_strain_route;   // "walk": the per-read strain masks of every species from its candidates' walks (stage_read_strain.hip), not from the node -> haplotype words
     bool cov_general = false;        // every group through the kernel of the longer walks (coverage_fast_kernel<.., LONG>; cov_long=step: coverage_step_kernel)
     std::string cov_long;            // "step": round 5's coverage_step_kernel for the groups that hold steps of walks of more than 64 steps
     int covl_shape = -1;             // shape of the long-walk kernel: <U><groups per workgroup / 8><window / 1024><back / 256> (default 2234)
@@ -494,6 +495,7 @@ struct Reads {
     bool g_flags_valid = false;
     bool species_valid = false;      // d_species (file order) reflects the last binning pass; species_ensure() gathers it from the slots
     bool binned = false;
+    uint64_t binned_db = 0;          // Db::uid of the db the last binning pass ran against (its species indices are in the slot records)
     bool grouped = true;             // false: columns only (a slice that will be routed away, stage_route.hip; the file seam until its graphs travel): no locus-grouped copy, no coverage pass
     uint64_t layout_id = 0;          // a new number for every locus-grouped copy built (build_step_read)
     uint64_t long_sums_db = 0;       // Db::uid of the db whose binning pass filled d_long_sum / d_long_len0 (0: nobody: walk_sum_kernel does it)
@@ -662,6 +664,10 @@ int trio_visits_build(Ctx *ctx, Db *db); // end of db upload: the visit table (a
 int trio_runs_build(Ctx *ctx, Db *db);   // end of db upload, after trio_visits_build: the node-block run table of those species
 int node_haps_build(Ctx *ctx, Db *db);   // end of db upload: node -> haplotypes (the LP's membership masks built by node)
 bool use_node_haps(const Ctx *ctx, const Db *db);
+// stage_read_strain.hip (pantax_hip_read_strains): candidates of every species sorted by haplotype, [S+1] offsets; host arrays of R entries in
+// file order, only the entries of reads binned to a species of db are written
+int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, uint32_t *hap_out,
+                        int32_t *n_out, double *post_out);
 struct HostReads;
 // stage_gaf.hip: text -> host columns (+ walks unless `resident` is given, which then owns the packed reads in HBM)
 int gaf_tokenize_device(Ctx *ctx, const char *text, uint64_t size, HostReads &out, Reads *resident = nullptr, int fd = -1, uint64_t file_base = 0, bool group = true,

@@ -474,6 +474,7 @@ int bin_reads_launch(Ctx *ctx, const Db *db, Reads *rd, unsigned long long *d_co
     int S = (int)db->S;
     PTX_HIP(ctx, hipMemsetAsync(d_counters, 0, bin_counter_words(S) * sizeof(unsigned long long), ctx->stream));
     rd->species_valid = false;
+    rd->binned_db = db->uid;
     if (rd->R == 0) { rd->binned = true; return 0; }
     unsigned long long *d_final = d_counters;
     d_counters = d_counters + bin_result_words(S);   // replicas

@@ -1,0 +1,293 @@
+// stage_read_strain.hip -- per-read strain assignment (pantax_hip_read_strains, the --read-strains report): which candidate strain of its
+// species every read supports.  Not a stage of the reference; it answers, on data the strain step leaves in HBM, what a user of
+// the tables would otherwise re-derive on the host from the graph files.
+//
+// Contract (DESIGN.md "Per-read strain assignment"):
+//   N(r) = the distinct nodes of the walk of read r (order and orientation ignored: the node-level model of the LP, profile.rs:1333-1342);
+//   C(r) = the candidates of r's species whose walk visits every node of N(r);
+//   assigned strain = argmax of the weight over C(r), ties to the smallest species-local haplotype index;
+//   posterior = w_assigned / sum of w over C(r), summed in f64 in ascending haplotype index;  n = |C(r)|.
+// Only reads the coverage pass counts (slot species >= 0) are assigned; reads binned to a species of the db but dropped (flags,
+// duplicate-id rule) and reads of species without candidates come out as "not counted" (n = -1).
+//
+// Membership of a node in the candidates' walks, as one mask per node:
+//   route 1 -- species of <= 64 haplotypes whose node -> haplotype words were built at upload (Db::d_node_haps, node_haps_build):
+//              mask(v) = node_haps[v] & cand_bits[s], bit = haplotype index; no array of its own.
+//   route 2 -- every other species (more than 64 haplotypes: node_haps is zero there; no node -> haplotype words; option
+//              read_strain_route=walk): a compact arena of W_s = ceil(K_s / 64) words per node over the species' K_s candidates only
+//              (bit = candidate index, candidates sorted by haplotype), built by read_strain_mask_kernel in one pass over the
+//              candidates' walks (64-bit atomic ORs: the result does not depend on their order).
+// read_strain_kernel walks the locus-grouped stream of the coverage pass (build_step_read, stage_cov.hip): a wave per 64-step group,
+// a lane per step.  The AND of the masks over a walk's steps is a segmented scan over the lanes on the DPP path; walks of <= 64 steps
+// never straddle a group, so the lane of the last step holds the walk's AND and decides there.  Walks of more than 64 steps (long
+// reads) AND their per-group partials into a per-slot word set to all ones first (64-bit atomic AND), and read_strain_long_kernel
+// decides them.  read_strain_gather_kernel brings the per-slot results into file order through Reads::d_slot_of.
+//
+// Algorithmic bytes of read_strain_kernel (T' padded steps, R' slots):
+//   4T' (node ids) + 1T' (step codes) + 8T' (mask words, route 1) + 16R' (read records) + 8R' (slot records) + 16R' (results)
+#include <algorithm>
+#include <cmath>
+#include "common.hpp"
+#include "primitives.hpp"
+#include "wave.hpp"
+
+namespace ptx {
+
+namespace {
+
+constexpr uint32_t RS_NO_SLOT = 0xFFFFFFFFu;
+// step codes of the grouped stream (stage_cov.hip: STEP_PAD, STEP_START)
+constexpr uint32_t RS_STEP_PAD = 0xFFu, RS_STEP_START = 0x40u;
+constexpr uint64_t RS_TILE = 4096;   // walk positions per tile of the mask pass (one wave)
+
+struct RsSpecies {
+    unsigned long long cand_bits;   // route 1: bit j = haplotype j is a candidate
+    uint64_t mask_base;             // route 2: first word of the species' node masks in the arena
+    uint32_t node_base;             // first global node index of the species
+    uint32_t route;                 // 0: no candidates, 1: node -> haplotype words, 2: compact masks
+    uint32_t nw;                    // mask words per node (route 1: 1)
+    uint32_t bit_base;              // first entry of the species in bit_w / bit_hap
+};
+struct RsTile { uint64_t p0, p1, word0; uint32_t nw, k; };   // walk positions [p0, p1) of candidate k; its words start at word0 (+ local node * nw)
+struct RsResult { uint32_t hap; int32_t n; double post; };
+
+// slot of the step held by `lane` (all 64 lanes): group_first_slot owns the group's first step, every later walk start advances it
+__device__ __forceinline__ uint32_t rs_slot_in_group(uint32_t group_first_slot, uint32_t code, int lane) {
+    const unsigned long long starts = __builtin_amdgcn_ballot_w64((code != RS_STEP_PAD) & ((code & RS_STEP_START) != 0u)) & ~1ull;
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(starts >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)starts, 0u));
+    return group_first_slot + below + (uint32_t)((starts >> lane) & 1ull);
+}
+
+// DPP move whose invalid / masked-off lanes read all ones (the identity of AND)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_ones(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)v, CTRL, ROW_MASK, 0xF, false); }
+
+// inclusive AND over lanes [seg, lane] (seg <= lane: the first lane of my walk in this wave); all 64 lanes active.  The steps of
+// wave_incl_scan_dpp: row_shr 1/2/4/8 inside the 16-lane rows, then the row results travel by row_bcast:15 and row_bcast:31; a lane
+// takes a value only from a source lane of its own walk.
+__device__ __forceinline__ unsigned long long seg_and(unsigned long long m, int lane, int seg) {
+    uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
+#define RS_STEP(CTRL, RM, SRC)                                                  \
+    {                                                                           \
+        const uint32_t tl = dpp_ones<CTRL, RM>(lo), th = dpp_ones<CTRL, RM>(hi); \
+        if ((SRC) >= seg) { lo &= tl; hi &= th; }                               \
+    }
+    RS_STEP(0x111, 0xF, lane - 1)
+    RS_STEP(0x112, 0xF, lane - 2)
+    RS_STEP(0x114, 0xF, lane - 4)
+    RS_STEP(0x118, 0xF, lane - 8)
+    RS_STEP(0x142, 0xA, (lane & ~15) - 1)   // rows 1 and 3 <- lanes 15 and 47
+    RS_STEP(0x143, 0xC, 31)                 // rows 2 and 3 <- lane 31
+#undef RS_STEP
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+// the candidates of one mask word, ascending: count, sum (f64, in order), argmax (first of equal weights)
+__device__ __forceinline__ void rs_take(unsigned long long m, uint32_t w, const double *__restrict__ bit_w, uint32_t bit_base, double &best,
+                                        uint32_t &besti, double &sum, int &n) {
+    while (m) {
+        const uint32_t idx = w * 64u + (uint32_t)__builtin_ctzll(m);
+        m &= m - 1ull;
+        const double x = bit_w[bit_base + idx];
+        ++n;
+        sum += x;
+        if (x > best) { best = x; besti = idx; }
+    }
+}
+__device__ __forceinline__ RsResult rs_finish(const RsSpecies &st, const uint32_t *__restrict__ bit_hap, double best, uint32_t besti, double sum, int n) {
+    RsResult o;
+    if (st.route == 0) { o.hap = 0xFFFFFFFFu; o.n = -1; o.post = 0.0; }
+    else if (n == 0) { o.hap = 0xFFFFFFFFu; o.n = 0; o.post = 0.0; }
+    else { o.hap = bit_hap[st.bit_base + besti]; o.n = n; o.post = best / sum; }
+    return o;
+}
+
+// route 2: a wave per tile of one candidate's walk; bit k of the candidate's word on every node the stretch visits
+__global__ void __launch_bounds__(256) read_strain_mask_kernel(uint32_t n_tiles, const RsTile *__restrict__ tiles, const uint32_t *__restrict__ path_nodes,
+                                                               unsigned long long *__restrict__ mask) {
+    const int lane = threadIdx.x & 63;
+    for (uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * 4) {
+        const RsTile tl = tiles[t];
+        const unsigned long long bit = 1ull << (tl.k & 63u);
+        const uint64_t wb = tl.word0 + (tl.k >> 6);
+        for (uint64_t p = tl.p0 + (uint64_t)lane; p < tl.p1; p += 64) atomicOr(&mask[wb + (uint64_t)path_nodes[p] * tl.nw], bit);
+    }
+}
+
+__global__ void __launch_bounds__(256) read_strain_kernel(uint32_t n_groups, uint32_t n_slots, const uint32_t *__restrict__ group_slot,
+                                                          const uint8_t *__restrict__ step_code, const uint32_t *__restrict__ g_node_id,
+                                                          const uint4 *__restrict__ read_rec, const uint2 *__restrict__ slot_rec,
+                                                          const RsSpecies *__restrict__ tab, const unsigned long long *__restrict__ node_haps,
+                                                          const unsigned long long *__restrict__ mask, const double *__restrict__ bit_w,
+                                                          const uint32_t *__restrict__ bit_hap, unsigned long long *__restrict__ long_acc, uint32_t long_nw,
+                                                          RsResult *__restrict__ res) {
+    const int lane = threadIdx.x & 63;
+    for (uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6); g < n_groups; g += gridDim.x * 4) {
+        const uint32_t gs = group_slot[g];                                   // (wave-uniform) NO_SLOT: a group of pads only
+        if (gs == RS_NO_SLOT) continue;
+        const uint64_t t = (uint64_t)g * 64u + (uint64_t)lane;
+        const uint32_t code = step_code[t];
+        const uint32_t slot = rs_slot_in_group(gs, code, lane);
+        const bool live = code != RS_STEP_PAD && slot < n_slots;
+        uint4 rr = make_uint4(0u, 0u, 0u, 0u);
+        uint2 sr = make_uint2(0xFFFFFFFFu, 0u);
+        if (live) { rr = read_rec[slot]; sr = slot_rec[slot]; }
+        const bool counted = live && (int32_t)sr.x >= 0;
+        RsSpecies st{0ull, 0ull, 0u, 0u, 0u, 0u};
+        if (counted) st = tab[sr.x];
+        const uint32_t i = live ? (uint32_t)t - rr.x : 0u;                  // position in the walk (T_pad < 2^32)
+        const bool last = live && i + 1u == rr.y;
+        const bool is_long = rr.y > 64u;
+        const int seg = lane - (int)min(i, (uint32_t)lane);                 // first lane of my walk in this wave
+        const bool tail = live && (last || lane == 63);                      // last step of my walk in this wave
+        const uint32_t nw = st.route ? st.nw : 0u;
+        const uint32_t nw_max = wave_reduce(nw, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
+        const uint32_t v = counted ? g_node_id[t] + sr.y : 0u;               // global node index
+        const uint64_t mrow = st.mask_base + (uint64_t)(v - st.node_base) * nw;
+        double best = -INFINITY, sum = 0.0;
+        uint32_t besti = 0;
+        int n = 0;
+        for (uint32_t w = 0; w < nw_max; ++w) {                              // (wave-uniform trip count: seg_and wants every lane)
+            unsigned long long m = ~0ull;
+            if (w < nw) m = st.route == 1u ? (node_haps[v] & st.cand_bits) : mask[mrow + w];
+            m = seg_and(m, lane, seg);
+            if (tail && w < nw) {
+                if (is_long) atomicAnd(&long_acc[(uint64_t)slot * long_nw + w], m);
+                else if (last) rs_take(m, w, bit_w, st.bit_base, best, besti, sum, n);
+            }
+        }
+        if (last && counted && !is_long) res[slot] = rs_finish(st, bit_hap, best, besti, sum, n);
+    }
+}
+
+// walks of more than 64 steps: the AND of their per-group partials -> the decision
+__global__ void __launch_bounds__(256) read_strain_long_kernel(uint32_t n_slots, const uint4 *__restrict__ read_rec, const uint2 *__restrict__ slot_rec,
+                                                               const RsSpecies *__restrict__ tab, const unsigned long long *__restrict__ long_acc,
+                                                               uint32_t long_nw, const double *__restrict__ bit_w, const uint32_t *__restrict__ bit_hap,
+                                                               RsResult *__restrict__ res) {
+    for (uint32_t s = blockIdx.x * 256 + threadIdx.x; s < n_slots; s += gridDim.x * 256) {
+        if (read_rec[s].y <= 64u) continue;
+        const int32_t sp = (int32_t)slot_rec[s].x;
+        if (sp < 0) continue;
+        const RsSpecies st = tab[sp];
+        double best = -INFINITY, sum = 0.0;
+        uint32_t besti = 0;
+        int n = 0;
+        if (st.route)
+            for (uint32_t w = 0; w < st.nw; ++w) rs_take(long_acc[(uint64_t)s * long_nw + w], w, bit_w, st.bit_base, best, besti, sum, n);
+        res[s] = rs_finish(st, bit_hap, best, besti, sum, n);
+    }
+}
+
+// file order: reads binned to a species of the db (counted: their slot's result; dropped: "not counted"); every other entry is left alone
+__global__ void __launch_bounds__(256) read_strain_gather_kernel(uint64_t R, const uint32_t *__restrict__ slot_of, const uint2 *__restrict__ slot_rec,
+                                                                 const RsResult *__restrict__ res, uint32_t *__restrict__ hap_out, int32_t *__restrict__ n_out,
+                                                                 double *__restrict__ post_out) {
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < R; r += (uint64_t)gridDim.x * 256) {
+        const uint32_t s = slot_of[r];
+        if (s == RS_NO_SLOT) continue;
+        const int32_t x = (int32_t)slot_rec[s].x;
+        if (x == -1) continue;                                                // "U" against this db
+        if (x < -1) { hap_out[r] = 0xFFFFFFFFu; n_out[r] = -1; post_out[r] = 0.0; continue; }
+        const RsResult o = res[s];
+        hap_out[r] = o.hap; n_out[r] = o.n; post_out[r] = o.post;
+    }
+}
+
+}  // namespace
+
+int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, uint32_t *hap_out,
+                        int32_t *n_out, double *post_out) {
+    const uint32_t S = db->S;
+    const uint64_t H = db->H, C = cand_off[S];
+    const bool by_node = db->nh_built && ctx->cfg.read_strain_route != "walk";
+    std::vector<RsSpecies> tab(S ? S : 1);
+    std::vector<double> bit_w(H + C + 1, 0.0);
+    std::vector<uint32_t> bit_hap(H + C + 1, 0u);
+    std::vector<RsTile> tiles;
+    uint64_t arena = 0;
+    uint32_t long_nw = 1;
+    for (uint32_t s = 0; s < S; ++s) {
+        RsSpecies &st = tab[s];
+        st = RsSpecies{0ull, 0ull, (uint32_t)db->h_node_off[s], 0u, 0u, 0u};
+        const uint64_t K = cand_off[s + 1] - cand_off[s], nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
+        if (K == 0) continue;
+        if (by_node && nh <= 64) {
+            st.route = 1; st.nw = 1; st.bit_base = (uint32_t)db->h_hap_off[s];
+            for (uint64_t c = cand_off[s]; c < cand_off[s + 1]; ++c) {
+                st.cand_bits |= 1ull << cand_hap[c];
+                bit_w[st.bit_base + cand_hap[c]] = cand_w[c];
+                bit_hap[st.bit_base + cand_hap[c]] = cand_hap[c];
+            }
+        } else {
+            st.route = 2; st.nw = (uint32_t)((K + 63) / 64); st.bit_base = (uint32_t)(H + cand_off[s]); st.mask_base = arena;
+            arena += (db->h_node_off[s + 1] - db->h_node_off[s]) * st.nw;
+            for (uint64_t k = 0; k < K; ++k) {
+                const uint64_t c = cand_off[s] + k, h = db->h_hap_off[s] + cand_hap[c];
+                bit_w[st.bit_base + k] = cand_w[c];
+                bit_hap[st.bit_base + k] = cand_hap[c];
+                for (uint64_t p = db->h_path_off[h]; p < db->h_path_off[h + 1]; p += RS_TILE)
+                    tiles.push_back(RsTile{p, std::min(p + RS_TILE, db->h_path_off[h + 1]), st.mask_base, st.nw, (uint32_t)k});
+            }
+        }
+        long_nw = std::max(long_nw, st.nw);
+    }
+    if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "read_strains: %llu haplotypes + candidates exceed 32-bit positions", (unsigned long long)(H + C));
+    DevBuf<RsSpecies> d_tab;
+    DevBuf<double> d_bit_w;
+    DevBuf<uint32_t> d_bit_hap;
+    DevBuf<RsTile> d_tiles;
+    DevBuf<unsigned long long> d_mask, d_long;
+    DevBuf<RsResult> d_res;
+    PTX_TRY(upload(ctx, d_tab, tab.data(), tab.size()));
+    PTX_TRY(upload(ctx, d_bit_w, bit_w.data(), bit_w.size()));
+    PTX_TRY(upload(ctx, d_bit_hap, bit_hap.data(), bit_hap.size()));
+    PTX_HIP(ctx, d_mask.alloc(arena ? arena : 1));
+    if (!tiles.empty()) {
+        PTX_TRY(upload(ctx, d_tiles, tiles.data(), tiles.size()));
+        PTX_TRY(zero_fill(ctx, d_mask.p, arena * sizeof(unsigned long long)));
+        KTimer tm(ctx, "read_strain_mask_kernel");
+        hipLaunchKernelGGL(read_strain_mask_kernel, dim3(grid_for(tiles.size(), 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, (uint32_t)tiles.size(), d_tiles.p,
+                           db->d_path_nodes.p, d_mask.p);
+    }
+    const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
+    PTX_HIP(ctx, d_res.alloc(n_slots ? n_slots : 1));
+    const bool any_long = rd->n_long != 0;
+    PTX_HIP(ctx, d_long.alloc(any_long ? (size_t)n_slots * long_nw : 1));
+    if (any_long) PTX_HIP(ctx, hipMemsetAsync(d_long.p, 0xFF, (size_t)n_slots * long_nw * sizeof(unsigned long long), ctx->stream));
+    if (n_slots && n_groups) {
+        KTimer tm(ctx, "read_strain_kernel");
+        hipLaunchKernelGGL(read_strain_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->d_g_group_slot.p,
+                           rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p,
+                           by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, d_mask.p, d_bit_w.p, d_bit_hap.p,
+                           d_long.p, long_nw, d_res.p);
+    }
+    if (n_slots && any_long) {
+        KTimer tm(ctx, "read_strain_long_kernel");
+        hipLaunchKernelGGL(read_strain_long_kernel, dim3(grid_for(n_slots, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, n_slots, rd->d_g_read_rec.p,
+                           rd->d_g_slot_rec.p, d_tab.p, d_long.p, long_nw, d_bit_w.p, d_bit_hap.p, d_res.p);
+    }
+    const uint64_t R = rd->R;
+    if (R) {
+        // the caller's arrays travel up first: entries of reads outside this db's species keep what the caller put there
+        DevBuf<uint32_t> d_hap;
+        DevBuf<int32_t> d_n;
+        DevBuf<double> d_post;
+        PTX_TRY(upload(ctx, d_hap, hap_out, R));
+        PTX_TRY(upload(ctx, d_n, n_out, R));
+        PTX_TRY(upload(ctx, d_post, post_out, R));
+        {
+            KTimer tm(ctx, "read_strain_gather_kernel");
+            hipLaunchKernelGGL(read_strain_gather_kernel, dim3(grid_for(R, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, R, rd->d_slot_of.p, rd->d_g_slot_rec.p,
+                               d_res.p, d_hap.p, d_n.p, d_post.p);
+        }
+        PTX_TRY(download(ctx, hap_out, d_hap.p, R));
+        PTX_TRY(download(ctx, n_out, d_n.p, R));
+        PTX_TRY(download(ctx, post_out, d_post.p, R));
+    }
+    PTX_HIP(ctx, hipGetLastError());
+    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host arrays are filled, the temporaries are released on return
+    return 0;
+}
+
+}  // namespace ptx

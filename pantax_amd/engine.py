@@ -293,6 +293,28 @@ class Engine:
         self._check(rc)
         return passed[: self.H], s_all, s_pass
 
+    def read_strains(self, cand_off, cand_hap, cand_w, fill=None):
+        """Per-read strain assignment (pantax_hip_read_strains) of the resident reads, binned against the resident db.
+        cand_off [S+1], cand_hap (species-local haplotype indices), cand_w (weights) -> (hap uint32, n int32, posterior float64), [R] each in file
+        order.  Only reads binned to a species of the db are written; every other entry keeps its value from `fill` ((hap, n, post) arrays),
+        by default (0xFFFFFFFF, -2, 0.0)."""
+        if self.R is None:
+            raise ValueError("read_strains: the number of reads is not known on the host (load_reads_from_gaf(columns=True))")
+        co = as_c(cand_off, np.uint64)
+        ch = as_c(cand_hap, np.uint32)
+        cw = as_c(cand_w, np.float64)
+        if len(co) != self.S + 1 or len(ch) != int(co[-1]) or len(cw) != len(ch):
+            raise ValueError("read_strains: cand_off needs S + 1 entries and cand_hap / cand_w cand_off[-1] each")
+        if fill is None:
+            hap = np.full(self.R, 0xFFFFFFFF, dtype=np.uint32)
+            n = np.full(self.R, -2, dtype=np.int32)
+            post = np.zeros(self.R)
+        else:
+            hap, n, post = as_c(fill[0], np.uint32).copy(), as_c(fill[1], np.int32).copy(), as_c(fill[2], np.float64).copy()
+        cs = _ffi.ReadStrainSet(self.S, co.ctypes.data, ch.ctypes.data if len(ch) else None, cw.ctypes.data if len(cw) else None)
+        self._check(self.lib.pantax_hip_read_strains(self.ctx, self.db, self.reads, C.byref(cs), p(hap), p(n), p(post)))
+        return hap, n, post
+
     def trio_nodes_info(self, fetch=True):
         n = C.c_uint64(0)
         self._check(self.lib.pantax_hip_trio_index(self.ctx, self.db, C.byref(n)))
@@ -446,10 +468,11 @@ class Engine:
                 min_species_abundance=1e-4, min_cov=0, min_depth=0, shift=False, filtered=True, full=True, force=False,
                 mode=2, sample_nodes=0, designated_species=None, zip="serialize", out_binning_file=None,
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
-                allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0):
+                allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
-        (host buffers) and switches on the sharded ingest."""
+        (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
+        (--read-strains; one rank only)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -460,7 +483,7 @@ class Engine:
             filtered=int(filtered), full=int(full), force=int(force), mode=mode, sample_nodes=sample_nodes,
             designated_species=enc(designated_species), zip=enc(zip), rank=int(rank), world_size=int(world_size),
             image_cache=int(image_cache), sample_test=int(sample_test), solver_semantics=int(solver_semantics),
-            minimization_min_cov=float(minimization_min_cov))
+            minimization_min_cov=float(minimization_min_cov), read_strain_file=enc(read_strain_file))
         cb = None
         if allreduce is not None:   # allreduce(np.ndarray float64) sums it in place over the ranks
             def _cb(_user, buf, n):
