@@ -448,6 +448,13 @@ void pantax_hip_graph_free(pantax_hip_graph *g);
  * values; exemplar rows README.md:343, :354).  Host only.  Returns the length, or < 0. */
 int pantax_hip_format_f64(double v, char *buf, size_t cap);
 
+/* The per-species node statistics of the strain step collected last on this db (pantax_hip_strain_profile, pantax_hip_profile_step,
+ * pantax_hip_profile_step_collect), as the device left them: max node abundance, nodes with abundance > 0, and the unrounded sum / count of the
+ * abundances above min_depth (frequencies_mean of a single-path species is their rounded quotient).  Host copies only; any output may be NULL.
+ * PANTAX_HIP_E_STATE before the first collected step, and while enqueued steps of the db are not yet collected. */
+int pantax_hip_strain_node_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, double *amax_out, uint32_t *nvalid_out, double *nzsum_out,
+                                 uint32_t *nzcnt_out);
+
 /* ---- measurement: HIP-event timings of kernels launched on the ctx stream ---------------- */
 int pantax_hip_timing_enable(pantax_hip_ctx *ctx, int on);
 int pantax_hip_timing_reset(pantax_hip_ctx *ctx);

@@ -153,6 +153,13 @@ int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const 
     db->cov_self_clean = db->cov_count_pending && ctx->cfg.cov_self_clean && db->U != 0;
     PTX_TRY(hap_trio_stats_launch(ctx, db, db->d_hap_nnz, db->d_hap_mean, skip_absent));                 // a9 statistics
     mark();
+    // ONE pass over the nodes where the step is eligible (node_rows_kernel, inside lad_prepare's row sort): the first filter reads the unique-trio statistics
+    // alone, so the LP columns are known before any node is looked at, and the statistics below are first needed by lad_pair_launch
+    lb.node_pass_fused = node_pass_fused_eligible(ctx, db, cfg);
+    lb.fused_min_depth = (double)cfg->min_depth;
+    lb.fused_active = ctx->cfg.no_absent_skip ? nullptr : skip_absent;
+    if (lb.node_pass_fused) lb.S = S;
+    else
     PTX_TRY(node_stats_launch(ctx, db, &lb, cfg->min_depth, skip_absent));                               // abundances + per-species stats
     if (db->cov_self_clean) { db->cov_arena_clean = true; db->cov_done = false; db->cov_self_clean = false; }   // (cov_done: the arena no longer holds a coverage result)
     mark();
@@ -205,6 +212,7 @@ int strain_finish(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const u
     StrainRaw r;
     PTX_TRY(fetch_arena_wait(ctx, db, lb, L, r, slot));                                         // the one host round trip
     if (after_wait) after_wait(after_wait_arg);
+    db->stats_slot = slot;
     lb.n_rows = r.counts[0]; lb.K = r.counts[1];
     lb.h_sp_pat_off.assign(r.sp_pat_off, r.sp_pat_off + S + 1);
 
@@ -325,6 +333,20 @@ int pantax_hip_strain_profile(pantax_hip_ctx *ctx, pantax_hip_db *db, const pant
     if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "strain_profile: %d enqueued step(s) of this db have not been collected", db->step_inflight);
     PTX_TRY(strain_enqueue(ctx, db, cfg, d_active, 0));
     return strain_finish(ctx, db, cfg, species_active, species_coverage, met, info_out, nullptr, nullptr, 0);
+}
+
+int pantax_hip_strain_node_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, double *amax_out, uint32_t *nvalid_out, double *nzsum_out, uint32_t *nzcnt_out) {
+    if (!ctx || !db) return PANTAX_HIP_E_INVALID;
+    PTX_ENTER(ctx);
+    if (db->stats_slot < 0 || db->h_arena[db->stats_slot].p == nullptr) return fail(ctx, PANTAX_HIP_E_STATE, "strain_node_stats: no strain step of this db has been collected");
+    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "strain_node_stats: %d enqueued step(s) of this db have not been collected (their download may reuse the slot)", db->step_inflight);
+    const ArenaLayout L(db->S, db->H);
+    const uint8_t *b = db->h_arena[db->stats_slot].p;   // (nothing in flight: no download is writing either slot)
+    if (amax_out) std::memcpy(amax_out, b + L.amax, sizeof(double) * db->S);
+    if (nvalid_out) std::memcpy(nvalid_out, b + L.nvalid, sizeof(uint32_t) * db->S);
+    if (nzsum_out) std::memcpy(nzsum_out, b + L.nzsum, sizeof(double) * db->S);
+    if (nzcnt_out) std::memcpy(nzcnt_out, b + L.nzcnt, sizeof(uint32_t) * db->S);
+    return 0;
 }
 
 int pantax_hip_pao_solve_batch(pantax_hip_ctx *ctx, const pantax_hip_species_batch *in, const pantax_hip_solution_batch *out) {

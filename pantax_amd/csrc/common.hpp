@@ -161,6 +161,7 @@ struct CtxConfig {
     int tv_u = 4, tv_rounds = 4, tf_u = 8, tf_rounds = 1, rows_u = 1, tb_slots = 256, trio_xcd = 3, cov_shape = -1, covf_shape = -1, cov_xcd = 0, group_bucket_bits = 0;
     uint32_t tv_ablate = 0, cov_ablate = 0, ssn_ablate = 0;
     bool trio_two_pass = false;      // every build through records + prefix + rows kernel, as a db's first build (tests, measurements)
+    std::string node_pass;           // "split": the resident step keeps node_cov_stats_kernel + ssn_hist_kernel where it would take the fused node_rows_kernel (tests compare, measurements)
     bool no_absent_skip = false;     // the statistics / histogram passes of the step read the species the species level dropped like the others (tests compare, measurements)
     bool ssn_debug = false, scan_no_huge = false, flag_rank_chained = false, ratio_kernel = false, mask_pass = false, trio_free_at_filter = false,
          trio_after_step = false;
@@ -252,6 +253,9 @@ struct LadBatch {
     DevBuf<double> d_c0;                // [S] sum of ab over the nodes with ab > 0 and no column (the row sort straight from the nodes sums it): the objective's part without rows
     bool rows_c0_valid = false;         // ... is there for the rows lad_prepare has just sorted
     bool masks_in_sort = false;         // the last lad_prepare formed the masks inside the row sort: d_mask holds nothing
+    bool node_pass_fused = false;       // this step's lad_prepare also forms abundances, covered bases and the node statistics inside the row sort (node_rows_kernel):
+    double fused_min_depth = 0.0;       //   d_ab and the db's d_cov hold nothing; strain_enqueue decides (node_pass_fused_eligible) and hands over min_depth and the
+    const uint8_t *fused_active = nullptr;   // species flags the coverage pass skipped by
     DevBuf<unsigned long long> d_ratio; // [H*2] at 2 * (hap_off[s] + k): sum cov, sum len of candidate k (exact integers)
     // species that can have more than 64 candidates (more than 64 haplotypes): LAD_WIDE_NW mask words per node in a side
     // array, d_mask then holds a 64-bit hash of those words (rows are grouped by it; the words of every pattern are
@@ -384,7 +388,7 @@ struct Db {
     bool trio_perm_valid = false;   // d_trio_perm holds the export order of the last build
     uint64_t U = 0;
     bool cov_prepared = false;       // coverage_prepare ran for the coming coverage_launch
-    bool cov_count_pending = false;  // d_cov of the last coverage pass is still to be counted from the bitmap (node_stats_launch does it)
+    bool cov_count_pending = false;  // d_cov of the last coverage pass is still to be counted from the bitmap (node_stats_launch does it, or the fused node pass, which needs no d_cov)
     // round 6: in the resident step the last readers of the coverage arena (hap_rows_pass_kernel<0>: trio_bases; node_cov_stats_kernel: bases, bit vector,
     // full-node flags) zero what they read, and the next coverage pass skips its zero fill.  cov_self_clean: this step's readers clean (set by
     // strain_enqueue); cov_arena_clean + its signature: the arena is all zero in exactly this layout (reset by whatever dirties it).
@@ -453,6 +457,7 @@ struct Db {
     PinBuf h_sp_out[2];              // [S f64 absolute][S u8 keep], per step in flight
     hipEvent_t ev_step[2] = {nullptr, nullptr};   // recorded behind the last download of the step that uses the slot
     pantax_hip_step_config step_cfg[2];
+    int stats_slot = -1;             // h_arena slot of the step collected last (pantax_hip_strain_node_stats), -1: none yet
     int step_enq = 0, step_col = 0, step_inflight = 0;   // slot of the next enqueue / the next collect; steps enqueued and not yet collected
     hipEvent_t ev_trio_free = nullptr;   // recorded behind the last reader of the unique-trio tables in a step: the next step's rebuild waits
     bool trio_free_valid = false;        // for this, not for the whole previous step (its row sort and LPs run beside the rebuild)

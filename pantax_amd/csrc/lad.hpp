@@ -10,6 +10,8 @@ int hap_trio_stats_launch(Ctx *ctx, const Db *db, DevBuf<uint32_t> &d_ntrio_nz /
                           const uint8_t *d_active = nullptr /* device [S] or null: species the coverage pass skipped are not read */);
 // node abundance + per-species stats
 int node_stats_launch(Ctx *ctx, const Db *db, LadBatch *lb, int64_t min_depth, const uint8_t *d_active = nullptr);
+// the resident step's fused node pass (node_rows_kernel in place of node_cov_stats_kernel + ssn_hist_kernel<true>): can THIS step take it?  Host-known only.
+bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg);
 // a11: species with more valid rows than sample_nodes keep the rows rand 0.9.2's choose_multiple(seed 42) would keep
 int row_sample_apply(Ctx *ctx, const Db *db, LadBatch *lb, int64_t sample_nodes);
 // a10: masks, ratios; then LP rows sorted and grouped into patterns

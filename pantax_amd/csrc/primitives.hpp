@@ -67,10 +67,24 @@ struct RowMaskSource {
     unsigned long long *ratio = nullptr;             // [2 H] at 2 (hap_off[s] + k): sum cov, sum len of column k
     uint32_t max_haps = 0;                           // most haplotypes of a species (<= 64)
 };
+// partial node statistics of a range of nodes: max a, sum and count of the a above min_depth, count of the a > 0 (profile.rs:1316-1319, :1193-1201, :1380-1385)
+struct NodePartial { double mx, zs; unsigned long long nv, zc; };
+// The resident step's ONE pass over the nodes (node_rows_kernel): with `haps` and this, the sort takes neither an abundance array nor covered-base
+// counts -- its histogram pass counts a node's covered bases from the coverage arena, forms a = bases / len in a register, and sums the per-species
+// statistics node_cov_stats_kernel would have written (`ab` and haps->cov are null then)
+struct NodeCovSource {
+    const unsigned long long *bases = nullptr;       // [V] aligned bases of every node (coverage arena)
+    const uint64_t *bit_off = nullptr;               // [V + 1] first bit of a node in the bit vector
+    const uint32_t *full = nullptr, *bitmap = nullptr;   // one flag per node "covered whole"; one bit per base
+    const uint8_t *active = nullptr;                 // [S] or null: species the coverage pass skipped (all zero: nothing is read)
+    double min_depth = 0.0;
+    double *amax = nullptr, *nzsum = nullptr;        // [S] outputs, as node_stats_final_kernel writes them
+    uint32_t *nvalid = nullptr, *nzcnt = nullptr;
+};
 size_t sample_sort_nodes_ws_elems(uint32_t S, uint64_t seg_bound, uint64_t V);
 int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const uint32_t *d_node_base, uint32_t S, uint64_t seg_bound, uint64_t V,
                       uint64_t *rows16, uint64_t *ksp, uint64_t *km, uint64_t *ka, int pack_shift, uint32_t *d_ws, uint32_t *d_n, const RowPatterns *pat = nullptr,
-                      const RowMaskSource *haps = nullptr);
+                      const RowMaskSource *haps = nullptr, const NodeCovSource *fused = nullptr);
 
 // helper: passes covering bits [lo,hi) of a word, least significant first, appended to out
 inline void add_passes(std::vector<SortPass> &out, int word, int lo, int hi) {

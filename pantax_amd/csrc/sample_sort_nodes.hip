@@ -74,6 +74,8 @@ struct Sn {
     const double *ab;            // [V] a_v (0 = no row)
     const uint64_t *mask;        // [V] membership mask (0 = no row); null: formed from the haplotype words (hp)
     RowMaskSource hp;
+    NodeCovSource fz;            // fz.bases != null: the fused node pass -- no `ab`, no hp.cov; a and the covered bases are formed from the coverage arena
+    NodePartial *npart;          // [S x G] fused: the statistics of the nodes a partition workgroup walked (a small segment: entry 0, from the sample kernel)
     uint32_t *ws;                // S x SN_WS_WORDS
     uint32_t *cntm;              // S x G x SN_NBUCKET: counts, then first slots
     uint16_t *ids;               // [V] bucket id of every staged row (same places as `stage`)
@@ -106,6 +108,55 @@ __device__ __forceinline__ uint64_t sn_node_mask(const Sn &sn, uint32_t s, uint6
     uint64_t m = 0;
     while (hm) { const int j = __ffsll((long long)hm) - 1; hm &= hm - 1; const int bit = sn.hp.hap_bit[h0 + j]; if (bit >= 0) m |= 1ull << bit; }
     return m;
+}
+
+// fused node pass: the abundance and the covered bases of ONE node from the coverage arena (what node_cov_stats_kernel writes to `ab` / `cov`), for the
+// few nodes the samplers look at
+template <bool FUSED>
+__device__ __forceinline__ double sn_node_ab(const Sn &sn, uint64_t v) {
+    if constexpr (!FUSED) return sn.ab[v];
+    return (double)(long long)sn.fz.bases[v] / (double)sn.hp.node_len[v];     // profile.rs:987-988
+}
+template <bool FUSED>
+__device__ __forceinline__ uint32_t sn_node_cov(const Sn &sn, uint64_t v) {
+    if constexpr (!FUSED) return sn.hp.cov[v];
+    const uint32_t l = sn.hp.node_len[v];
+    if ((sn.fz.full[v >> 5] >> (v & 31u)) & 1u) return l;                     // a step covered the whole node: a flag instead of marked bits
+    if (l == 0u) return 0u;
+    const uint64_t g0 = sn.fz.bit_off[v], g1 = g0 + l, w0 = g0 >> 5, w1 = (g1 - 1) >> 5;
+    const uint32_t m0 = 0xFFFFFFFFu << (g0 & 31), m1 = 0xFFFFFFFFu >> (31 - (uint32_t)((g1 - 1) & 31));
+    if (w0 == w1) return (uint32_t)__popc(sn.fz.bitmap[w0] & m0 & m1);
+    uint32_t c = (uint32_t)__popc(sn.fz.bitmap[w0] & m0) + (uint32_t)__popc(sn.fz.bitmap[w1] & m1);
+    for (uint64_t w = w0 + 1; w < w1; ++w) c += (uint32_t)__popc(sn.fz.bitmap[w]);
+    return c;
+}
+struct NodeAcc {                                                              // a thread's share of a NodePartial
+    double mx = -INFINITY, zs = 0.0;
+    unsigned long long nv = 0, zc = 0;
+    __device__ __forceinline__ void add(double ab, double min_depth) {
+        mx = fmax(mx, ab);
+        if (ab > 0.0) ++nv;
+        const double o = ab > min_depth ? ab : 0.0;                           // :2941-2944
+        if (o > 0.0) { zs += o; ++zc; }
+    }
+};
+// the workgroup's NodePartial in a fixed shape (every thread its nodes in order, a wave reduction, the waves in order): the same bits from run to run
+template <int NW>
+__device__ __forceinline__ void sn_block_partial(NodeAcc a, NodePartial *dst) {
+    __shared__ double s_mx[NW], s_zs[NW];
+    __shared__ unsigned long long s_nv[NW], s_zc[NW];
+    a.mx = wave_reduce(a.mx, [](double x, double y) { return fmax(x, y); });
+    a.zs = wave_reduce(a.zs, [](double x, double y) { return x + y; });
+    a.nv = wave_reduce(a.nv, [](unsigned long long x, unsigned long long y) { return x + y; });
+    a.zc = wave_reduce(a.zc, [](unsigned long long x, unsigned long long y) { return x + y; });
+    if ((threadIdx.x & 63) == 0) { const int q = threadIdx.x >> 6; s_mx[q] = a.mx; s_zs[q] = a.zs; s_nv[q] = a.nv; s_zc[q] = a.zc; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        NodePartial p{s_mx[0], s_zs[0], s_nv[0], s_zc[0]};
+        for (int q = 1; q < NW; ++q) { p.mx = fmax(p.mx, s_mx[q]); p.zs += s_zs[q]; p.nv += s_nv[q]; p.zc += s_zc[q]; }
+        *dst = p;
+    }
+    __syncthreads();
 }
 
 // sorted rank (0-based, among the SN_NSPLIT splitters) of tree node k, and back
@@ -205,6 +256,7 @@ __device__ __forceinline__ void wave_sort_bucket(const Sn &sn, uint32_t s, const
     }
 }
 
+template <bool FUSED>   // (compile time: the samplers of the two-kernel path keep the code they had)
 __global__ void __launch_bounds__(256) ssn_gather_kernel(Sn sn) {
     const uint32_t s = blockIdx.y, o = sn.node_base[s], n = sn.node_base[s + 1] - o;
     uint32_t *w = sn.w(s);
@@ -216,7 +268,7 @@ __global__ void __launch_bounds__(256) ssn_gather_kernel(Sn sn) {
     const bool dead = !sn.mask && sn.skip_empty && sn.hp.sp_p[s] <= 0;   // a segment without LP columns has no rows: nothing sampled, nothing sorted (round 6)
     if (dead) { if (i == 0) { w[SN_OFF_FLAGS] = small ? 1u : 0u; w[SN_OFF_FLAGS + 1] = 0; w[SN_OFF_FLAGS + 2] = 0; w[SN_OFF_FLAGS + 3] = 0; } return; }
     if (pos < n) {
-        const double av = sn.ab[o + pos];
+        const double av = sn_node_ab<FUSED>(sn, o + pos);
         const uint64_t mv = av > 0.0 ? sn_node_mask(sn, s, o + pos) : 0ull;
         if (av > 0.0 && mv != 0ull) { m = mv; a = (uint64_t)__double_as_longlong(av); }   // positive doubles order like their bit patterns
     }
@@ -224,12 +276,20 @@ __global__ void __launch_bounds__(256) ssn_gather_kernel(Sn sn) {
     if (i == 0) { w[SN_OFF_FLAGS] = small ? 1u : 0u; w[SN_OFF_FLAGS + 1] = 0; w[SN_OFF_FLAGS + 2] = 0; w[SN_OFF_FLAGS + 3] = 0; }
 }
 // One 1024-thread workgroup per segment sorts its 4096 samples in LDS; the splitters are the valid samples at even ranks.
+template <bool FUSED>
 __global__ void __launch_bounds__(1024) ssn_sample_kernel(Sn sn) {
     __shared__ uint64_t km[SN_SAMPLE], ka[SN_SAMPLE];
     __shared__ uint32_t s_nv;
     const uint32_t s = blockIdx.x, o = sn.node_base[s], n = sn.node_base[s + 1] - o;
     uint32_t *w = sn.w(s);
     if (n == 0) { if (threadIdx.x == 0) { sn.seg_n[s] = 0; if (sn.c0) sn.c0[s] = 0.0; } return; }
+    if constexpr (FUSED) {
+        if (n <= (uint32_t)SN_SAMPLE && (!sn.fz.active || sn.fz.active[s])) {   // (workgroup-uniform) the histogram pass returns early for a small segment:
+            NodeAcc acc;                                                        // its statistics are summed here, columns or not
+            for (uint32_t i = threadIdx.x; i < n; i += 1024) acc.add(sn_node_ab<true>(sn, o + i), sn.fz.min_depth);
+            sn_block_partial<16>(acc, sn.npart + (size_t)s * sn.G);
+        }
+    }
     if (!sn.mask && sn.skip_empty && sn.hp.sp_p[s] <= 0) {   // (see ssn_gather_kernel; the histogram pass writes the empty counts of a large segment)
         if (threadIdx.x == 0) { sn.seg_n[s] = 0; w[SN_OFF_FLAGS + 3] = 0; if (sn.c0) sn.c0[s] = 0.0; }
         return;
@@ -254,7 +314,7 @@ __global__ void __launch_bounds__(1024) ssn_sample_kernel(Sn sn) {
             __syncthreads();
             for (uint32_t i = threadIdx.x; i < n; i += 1024) {
                 uint64_t m = sn_node_mask(sn, s, o + i);
-                const unsigned long long c = sn.hp.cov[o + i], l = sn.hp.node_len[o + i];
+                const unsigned long long c = FUSED ? (m ? sn_node_cov<true>(sn, o + i) : 0u) : sn_node_cov<false>(sn, o + i), l = sn.hp.node_len[o + i];
                 while (m) { const int k = __ffsll((long long)m) - 1; m &= m - 1; if (c) atomicAdd(&s_r[2 * k], c); atomicAdd(&s_r[2 * k + 1], l); }
             }
             __syncthreads();
@@ -263,7 +323,7 @@ __global__ void __launch_bounds__(1024) ssn_sample_kernel(Sn sn) {
         if (sn.c0) {                                     // the segment's nodes without a column (fixed order: deterministic)
             __shared__ double s_c[16];
             double c = 0.0;
-            for (uint32_t i = threadIdx.x; i < n; i += 1024) { const double av = sn.ab[o + i]; if (av > 0.0 && sn_node_mask(sn, s, o + i) == 0ull) c += av; }
+            for (uint32_t i = threadIdx.x; i < n; i += 1024) { const double av = sn_node_ab<FUSED>(sn, o + i); if (av > 0.0 && sn_node_mask(sn, s, o + i) == 0ull) c += av; }
             c = wave_reduce(c, [](double x, double y) { return x + y; });
             if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
             __syncthreads();
@@ -447,6 +507,231 @@ __global__ void __launch_bounds__(256) ssn_hist_kernel(Sn sn) {
         __syncthreads();
         if ((int)threadIdx.x < 2 * p0 && s_acc[threadIdx.x]) atomicAdd(&sn.hp.ratio[2 * h0 + threadIdx.x], s_acc[threadIdx.x]);
     }
+}
+
+// The same pass for the resident step, FUSED with the node statistics (node_rows_kernel).  It has no abundance array and no covered-base counts to read:
+// it takes a node from `bases`, the bit vector, the full-node flags and the haplotype word to {covered bases, a, statistics, mask, column sums, bucket
+// id, staged row} in registers, which is node_cov_stats_kernel<false>'s work (stage_lad.hip) in front of this pass's own -- the 12 bytes a node that
+// kernel wrote and this one read back, and the second read of the lengths, are gone.
+// A kernel of its own, not a third instantiation of ssn_hist_kernel: one shared body changed the register allocation of ssn_hist_kernel<true>
+// (115 -> 127 VGPRs, node_pass=split 0.6 ms a step slower than the parent at cfg4), and the two-kernel path of the stage calls and fallbacks has to stay
+// what it was.  The price: from "haplotype word -> columns" down to the staging of the row, and the three epilogues (count matrix row, c0 partial,
+// column sums), this kernel and ssn_hist_kernel<true> are the SAME statements and have to be edited together.
+// A wave's item is 64 consecutive nodes: their first bit comes from ONE wave-uniform load of bit_off plus a DPP prefix sum of the lengths (no running
+// offset: a workgroup's tiles are not consecutive for a wave).  A tile is walked in two halves of four items -- the statistics kernel's depth: eight
+// items' lengths, bases, flag, haplotype and bit-vector words beside the sixteen column sums do not fit the registers of four waves per SIMD (153 VGPRs)
+// -- and a half's streams are all requested before its first dependent bit-vector load.  The covered bases of a node have ONE consumer here, the column
+// sums of path_cov_ratio: a node without a column (empty mask), or one a step covered whole (flag), does not fetch its bit-vector words at all.
+constexpr int SN_HALF = SN_ITEMS >= 8 ? SN_ITEMS / 2 : SN_ITEMS;
+static_assert(SN_ITEMS % SN_HALF == 0, "whole halves");
+__global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
+    __shared__ ulonglong2 tree[SN_NLEAF];
+    __shared__ uint32_t s_hist[SN_NBUCKET];
+    extern __shared__ unsigned long long s_dyn_tab[];             // [nbyte][256] columns of the haplotypes 8b .. 8b+7 set in a byte value
+    __shared__ int s_bit[64];
+    __shared__ unsigned long long s_acc[2 * 64];
+    const uint32_t s = blockIdx.y, g = blockIdx.x, o = sn.node_base[s], n = sn.node_base[s + 1] - o;
+    uint32_t *w = sn.w(s);
+    if (n == 0 || w[SN_OFF_FLAGS] != 0) return;                  // (a small segment: rows, column sums and statistics are the sample kernel's)
+    uint32_t t0, t1;
+    sn_tiles(sn, n, g, t0, t1);
+    // a species without LP columns (the species level dropped it, or no haplotype passed the first filter) has no rows: an empty histogram, nothing staged
+    if (sn.skip_empty && sn.hp.sp_p[s] <= 0) {                   // (workgroup-uniform)
+        uint32_t *row0 = sn.cntm + ((size_t)s * sn.G + g) * SN_NBUCKET;
+        for (int i = threadIdx.x; i < SN_NBUCKET; i += 256) row0[i] = 0u;
+        if (threadIdx.x == 0) { sn.stage_cnt[(size_t)s * sn.G + g] = 0u; if (sn.c0) sn.c0p[(size_t)s * sn.G + g] = 0.0; }
+        // a species that is PRESENT but has no column still reports its statistics (the single-path frequencies_mean, strain_finish) -- from lengths
+        // and bases alone; one the species level dropped has zeros (node_rows_final_kernel), as node_cov_stats_kernel writes them without reading
+        if (!sn.fz.active || sn.fz.active[s]) {
+            NodeAcc acc;
+            for (uint32_t t = t0; t < t1; ++t)
+#pragma unroll
+                for (int r = 0; r < SN_ITEMS; ++r) {
+                    const uint32_t i = t * SN_TILE + (uint32_t)r * 256u + threadIdx.x;
+                    if (i < n) acc.add((double)(long long)sn.fz.bases[o + i] / (double)sn.hp.node_len[o + i], sn.fz.min_depth);
+                }
+            sn_block_partial<4>(acc, sn.npart + (size_t)s * sn.G + g);
+        }
+        return;
+    }
+    const ulonglong2 *gt = reinterpret_cast<const ulonglong2 *>(w + SN_OFF_TREE);
+    __shared__ uint32_t s_nstage;
+    for (int i = threadIdx.x; i < SN_NBUCKET; i += 256) s_hist[i] = 0;
+    if (threadIdx.x == 0) s_nstage = 0;
+    if (t0 < t1) for (int i = threadIdx.x; i < SN_NLEAF; i += 256) tree[i] = gt[i];
+    const uint64_t h0 = sn.hp.hap_off[s], nh = sn.hp.hap_off[s + 1] - h0;
+    int p0 = sn.hp.sp_p[s];
+    if (p0 <= 0 || p0 > 64 || nh > 64) p0 = 0;                    // no columns
+    const int nbyte = p0 ? (int)((nh + 7) / 8) : 0;
+    if (threadIdx.x < 64) s_bit[threadIdx.x] = (p0 && threadIdx.x < nh) ? sn.hp.hap_bit[h0 + threadIdx.x] : -1;
+    if (threadIdx.x < 128) s_acc[threadIdx.x] = 0;
+    __syncthreads();
+    for (int b = 0; b < nbyte; ++b) {
+        unsigned long long e = 0ull;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { const int bit = s_bit[8 * b + i]; if (((threadIdx.x >> i) & 1u) && bit >= 0) e |= 1ull << bit; }
+        s_dyn_tab[b * 256 + threadIdx.x] = e;
+    }
+    __syncthreads();
+    unsigned long long c8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, l8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const uint32_t stage0 = o + t0 * SN_TILE;                    // (the staged rows: see ssn_hist_kernel)
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) << 6;
+    double cacc = 0.0;                                           // abundances of this thread's nodes with an empty mask
+    NodeAcc nacc;                                                // statistics of this thread's nodes
+    constexpr int HALF = SN_HALF;                                // items in flight together
+    for (uint32_t t = t0; t < t1; ++t) {
+#pragma unroll
+      for (int hb = 0; hb < SN_ITEMS; hb += HALF) {
+        const uint32_t base = t * SN_TILE + (uint32_t)hb * 256u + threadIdx.x;
+        double av[HALF];
+        uint64_t mv[HALF];
+        uint32_t cv[HALF], lv[HALF];
+        {
+            unsigned long long bs[HALF];
+            uint32_t fw[HALF];
+            uint64_t g0[HALF];
+#pragma unroll
+            for (int r = 0; r < HALF; ++r) {                     // the four streams of the half
+                const uint32_t i = base + (uint32_t)r * 256u;
+                const bool in = i < n;
+                lv[r] = in ? sn.hp.node_len[o + i] : 0u;
+                bs[r] = in ? sn.fz.bases[o + i] : 0ull;
+                fw[r] = in ? sn.fz.full[(o + i) >> 5] : 0u;
+                mv[r] = in ? sn.hp.node_haps[o + i] : 0ull;
+            }
+#pragma unroll
+            for (int r = 0; r < HALF; ++r) {                     // first bit of the wave's 64 nodes (wave-uniform), then of every node
+                const uint32_t i0 = t * SN_TILE + (uint32_t)(hb + r) * 256u + wave64;
+                g0[r] = i0 < n ? sn.fz.bit_off[o + i0] : 0ull;
+            }
+#pragma unroll
+            for (int r = 0; r < HALF; ++r) g0[r] += wave_incl_scan_dpp(lv[r]) - lv[r];   // (a species' bases fit 32 bits: checked at upload)
+            bool whole[HALF];
+#pragma unroll
+            for (int r = 0; r < HALF; ++r) {                     // haplotype word -> columns
+                const unsigned long long hm = mv[r];
+                unsigned long long m = 0ull;
+                for (int b = 0; b < nbyte; ++b) m |= s_dyn_tab[b * 256 + (int)((hm >> (8 * b)) & 255ull)];
+                mv[r] = m;
+                whole[r] = (fw[r] >> ((o + base + (uint32_t)r * 256u) & 31u)) & 1u;   // a step covered the whole node: a flag instead of marked bits
+            }
+            uint32_t bw0[HALF], bw1[HALF];                       // first and last bit-vector word of every node that has a consumer for its count: independent loads, issued together
+#pragma unroll
+            for (int r = 0; r < HALF; ++r) {
+                const bool count = lv[r] != 0u && mv[r] != 0ull && !whole[r];   // (l = 0 behind the segment's end)
+                bw0[r] = count ? sn.fz.bitmap[g0[r] >> 5] : 0u;
+                bw1[r] = count ? sn.fz.bitmap[(g0[r] + lv[r] - 1) >> 5] : 0u;
+            }
+#pragma unroll
+            for (int r = 0; r < HALF; ++r) {
+                const uint32_t i = base + (uint32_t)r * 256u;
+                uint32_t c = whole[r] ? lv[r] : 0u;
+                if (lv[r] != 0u && mv[r] != 0ull && !whole[r]) {
+                    const uint64_t g1 = g0[r] + lv[r], w0 = g0[r] >> 5, w1 = (g1 - 1) >> 5;
+                    const uint32_t m0 = 0xFFFFFFFFu << (g0[r] & 31), m1 = 0xFFFFFFFFu >> (31 - (uint32_t)((g1 - 1) & 31));
+                    c = w0 == w1 ? __popc(bw0[r] & m0 & m1) : __popc(bw0[r] & m0) + __popc(bw1[r] & m1);
+                    for (uint64_t ww = w0 + 1; ww < w1; ++ww) c += __popc(sn.fz.bitmap[ww]);   // nodes of more than 33 bases
+                }
+                cv[r] = c;
+                av[r] = 0.0;
+                if (i < n) {
+                    av[r] = (double)(long long)bs[r] / (double)lv[r];   // profile.rs:987-988, as node_cov_stats_kernel forms it
+                    nacc.add(av[r], sn.fz.min_depth);
+                }
+            }
+        }
+        // ---- from here to the end of the kernel: ssn_hist_kernel<true>'s statements (edit both)
+#pragma unroll
+        for (int r = 0; r < HALF; ++r) {
+            {                                                     // the columns' sums
+                const unsigned long long m = mv[r];
+                if (m) {
+                    const unsigned long long c = cv[r], l = lv[r];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (k < p0) { const bool on = (m >> k) & 1ull; c8[k] += on ? c : 0ull; l8[k] += on ? l : 0ull; }   // (block-uniform: the columns that exist)
+                    unsigned long long rest = m >> 8;
+                    while (rest) {
+                        const int k = __ffsll((long long)rest) - 1 + 8;
+                        rest &= rest - 1;
+                        if (c) atomicAdd(&s_acc[2 * k], c);
+                        atomicAdd(&s_acc[2 * k + 1], l);
+                    }
+                }
+            }
+            uint32_t id = SN_NO_ROW;
+            const uint64_t abits = (uint64_t)__double_as_longlong(av[r]);
+            if (av[r] > 0.0 && mv[r] == 0ull) cacc += av[r];
+            if (av[r] > 0.0 && mv[r] != 0ull) {                  // (nodes behind the segment's end were loaded as zeros)
+                const Key2 key{mv[r], abits};
+                uint32_t k = 1;
+#pragma unroll
+                for (int l = 0; l < SN_LEVELS; ++l) { const ulonglong2 nd = tree[k]; k = 2u * k + (less2(Key2{nd.x, nd.y}, key) ? 1u : 0u); }
+                const uint32_t lo = k - (uint32_t)SN_NLEAF;   // splitters less than the key
+                uint32_t eq = 0;
+                if (lo < (uint32_t)SN_NSPLIT) { const ulonglong2 nd = tree[tree_node(lo)]; eq = eq2(Key2{nd.x, nd.y}, key) ? 1u : 0u; }
+                id = 2u * lo + eq;
+                atomicAdd(&s_hist[id], 1u);
+            }
+            const bool travels = id != SN_NO_ROW && !(id & 1u);
+            const unsigned long long bal = __ballot(travels);
+            if (bal) {                                           // (wave-uniform)
+                uint32_t wbase = 0;
+                if (lane == 0) wbase = atomicAdd(&s_nstage, (uint32_t)__popcll(bal));
+                wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
+                if (travels) {
+                    const uint32_t pos = stage0 + wbase + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+                    sn.stage[pos] = make_ulonglong2(mv[r], abits);
+                    sn.ids[pos] = (uint16_t)id;
+                }
+            }
+        }
+      }
+    }
+    __syncthreads();
+    sn_block_partial<4>(nacc, sn.npart + (size_t)s * sn.G + g);
+    uint32_t *row = sn.cntm + ((size_t)s * sn.G + g) * SN_NBUCKET;
+    for (int i = threadIdx.x; i < SN_NBUCKET; i += 256) row[i] = s_hist[i];
+    if (threadIdx.x == 0) sn.stage_cnt[(size_t)s * sn.G + g] = s_nstage;
+    if (sn.c0) {                                                 // (block-uniform) fixed-shape sum: deterministic
+        __shared__ double s_c[4];
+        cacc = wave_reduce(cacc, [](double x, double y) { return x + y; });
+        if (lane == 0) s_c[threadIdx.x >> 6] = cacc;
+        __syncthreads();
+        if (threadIdx.x == 0) sn.c0p[(size_t)s * sn.G + g] = (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]);
+    }
+    if (p0 > 0 && sn.hp.ratio) {                                 // (block-uniform) exact integer sums: any order
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (k >= p0) break;
+            const unsigned long long cs = wave_reduce(c8[k], [](unsigned long long x, unsigned long long y) { return x + y; });
+            const unsigned long long ls = wave_reduce(l8[k], [](unsigned long long x, unsigned long long y) { return x + y; });
+            if (lane == 0) {
+                if (cs) atomicAdd(&s_acc[2 * k], cs);
+                if (ls) atomicAdd(&s_acc[2 * k + 1], ls);
+            }
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < 2 * p0 && s_acc[threadIdx.x]) atomicAdd(&sn.hp.ratio[2 * h0 + threadIdx.x], s_acc[threadIdx.x]);
+    }
+}
+
+// fused: a species' statistics from the partials of its partition workgroups, in workgroup order (one wave per species: lane l combines workgroups
+// l, l + 64, ..., then a fixed-shape wave reduction -- node_stats_final_kernel's shape over the (species, workgroup) layout)
+__global__ void __launch_bounds__(64) node_rows_final_kernel(Sn sn) {
+    const uint32_t s = blockIdx.x, n = sn.node_base[s + 1] - sn.node_base[s];
+    double mx = -INFINITY, zs = 0.0; unsigned long long nv = 0, zc = 0;
+    if (n != 0 && sn.fz.active && !sn.fz.active[s]) mx = 0.0;    // dropped by the species level: the zeros node_cov_stats_kernel writes without reading
+    else if (n != 0) {
+        const uint32_t nt = (n + SN_TILE - 1) / SN_TILE, ng = n <= (uint32_t)SN_SAMPLE ? 1u : (nt + sn.per - 1) / sn.per;   // (a small segment: the sample kernel's)
+        for (uint32_t g = threadIdx.x; g < ng; g += 64) { const NodePartial p = sn.npart[(size_t)s * sn.G + g]; mx = fmax(mx, p.mx); zs += p.zs; nv += p.nv; zc += p.zc; }
+    }
+    mx = wave_reduce(mx, [](double x, double y) { return fmax(x, y); });
+    zs = wave_reduce(zs, [](double x, double y) { return x + y; });
+    nv = wave_reduce(nv, [](unsigned long long x, unsigned long long y) { return x + y; });
+    zc = wave_reduce(zc, [](unsigned long long x, unsigned long long y) { return x + y; });
+    if (threadIdx.x == 0) { sn.fz.amax[s] = mx; sn.fz.nvalid[s] = (uint32_t)nv; sn.fz.nzsum[s] = zs; sn.fz.nzcnt[s] = (uint32_t)zc; }
 }
 
 // bucket starts of a segment; the count matrix becomes the first slot of every workgroup in every bucket
@@ -807,7 +1092,8 @@ void sn_geometry(uint32_t S, uint64_t seg_bound, uint32_t *G, uint32_t *per) {
 size_t sample_sort_nodes_ws_elems(uint32_t S, uint64_t seg_bound, uint64_t V) {
     uint32_t G, per;
     sn_geometry(S, seg_bound, &G, &per);
-    return (size_t)S * SN_WS_WORDS + (size_t)S * G * (SN_NBUCKET + 1 + 2) + (V + 1) / 2 + (2 + (size_t)SN_NWH) * (size_t)S + 20;
+    return (size_t)S * SN_WS_WORDS + (size_t)S * G * (SN_NBUCKET + 1 + 2) + (V + 1) / 2 + (2 + (size_t)SN_NWH) * (size_t)S + 20 +
+           (size_t)S * G * (sizeof(NodePartial) / 4) + 4;   // (the fused node pass's statistics partials)
 }
 
 // Nodes of segment s: [node_base[s], node_base[s + 1]) (device array, the host knows that no segment exceeds seg_bound <= SS_MAX_N
@@ -815,7 +1101,7 @@ size_t sample_sort_nodes_ws_elems(uint32_t S, uint64_t seg_bound, uint64_t V) {
 // (mask, a), in (ksp, km, ka) -- ksp null: species << pack_shift | mask in km; *d_n = the number of rows.  rows16: 4 V words of scratch.
 int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const uint32_t *d_node_base, uint32_t S, uint64_t seg_bound, uint64_t V,
                       uint64_t *rows16, uint64_t *ksp, uint64_t *km, uint64_t *ka, int pack_shift, uint32_t *d_ws, uint32_t *d_n, const RowPatterns *pat,
-                      const RowMaskSource *haps) {
+                      const RowMaskSource *haps, const NodeCovSource *fused) {
     if (S == 0 || V == 0) {
         PTX_HIP(ctx, hipMemsetAsync(d_n, 0, sizeof(uint32_t), ctx->stream));
         if (pat) { PTX_HIP(ctx, hipMemsetAsync(pat->d_K, 0, sizeof(uint32_t), ctx->stream)); PTX_HIP(ctx, hipMemsetAsync(pat->sp_pat_off, 0, (S + 1) * sizeof(uint32_t), ctx->stream));
@@ -828,6 +1114,10 @@ int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const ui
     sn.node_base = d_node_base; sn.ab = ab; sn.mask = haps ? nullptr : mask; sn.ws = d_ws;
     if (haps) { if (haps->max_haps > 64) return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: masks from haplotype words take species of at most 64 haplotypes"); sn.hp = *haps; }
     else if (!mask) return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: neither a mask array nor haplotype words");
+    if (fused && (!haps || !fused->bases || !fused->bit_off || !fused->full || !fused->bitmap || !fused->amax || !fused->nvalid || !fused->nzsum || !fused->nzcnt))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: the fused node pass takes haplotype words and the coverage arena");
+    if (!fused && !ab) return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: no abundance array");
+    if (fused) { sn.fz = *fused; sn.ab = nullptr; sn.hp.cov = nullptr; }
     sn_geometry(S, seg_bound, &sn.G, &sn.per);
     sn.ablate = ctx->cfg.ssn_ablate;
     sn.skip_empty = ctx->cfg.no_absent_skip ? 0u : 1u;
@@ -841,12 +1131,29 @@ int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const ui
     sn.seg_n = tail; sn.seg_out = tail + S;                       // [S], [S + 1]
     uint32_t *sub_k = tail + 2 * (size_t)S + 4;                   // [S][SN_NWH] patterns found by each wave of ssn_heads_kernel
     sn.ids = reinterpret_cast<uint16_t *>(sub_k + (size_t)SN_NWH * S);
+    uint32_t *pw = sub_k + (size_t)SN_NWH * S + (V + 1) / 2;     // [S x G] NodePartial, 8-byte aligned
+    pw += ((reinterpret_cast<uintptr_t>(pw) & 7u) ? 1 : 0);
+    sn.npart = reinterpret_cast<NodePartial *>(pw);
     sn.rows = reinterpret_cast<ulonglong2 *>(rows16);
     sn.stage = reinterpret_cast<ulonglong2 *>(rows16) + V;
     sn.ksp = ksp; sn.km = km; sn.ka = ka; sn.pack_shift = pack_shift;
     { KTimer t(ctx, "ssn_sample_kernel");
-      hipLaunchKernelGGL(ssn_gather_kernel, dim3(SN_SAMPLE / 256, S), dim3(256), 0, ctx->stream, sn);
-      hipLaunchKernelGGL(ssn_sample_kernel, dim3(S), dim3(1024), 0, ctx->stream, sn); }
+      if (fused) {
+          hipLaunchKernelGGL(ssn_gather_kernel<true>, dim3(SN_SAMPLE / 256, S), dim3(256), 0, ctx->stream, sn);
+          hipLaunchKernelGGL(ssn_sample_kernel<true>, dim3(S), dim3(1024), 0, ctx->stream, sn);
+      } else {
+          hipLaunchKernelGGL(ssn_gather_kernel<false>, dim3(SN_SAMPLE / 256, S), dim3(256), 0, ctx->stream, sn);
+          hipLaunchKernelGGL(ssn_sample_kernel<false>, dim3(S), dim3(1024), 0, ctx->stream, sn);
+      } }
+    if (fused) {
+        // The one pass over the nodes of the resident step.  With ssn_gather_kernel above it is the LAST reader of `bases`, the bit vector and the full-node
+        // flags: the side-stream zero fill of the coverage arena (coverage_arena_clean_async) is enqueued by strain_enqueue after lad_prepare has returned,
+        // i.e. behind this launch; the event the next step's index rebuild waits for (ev_trio_free) was recorded before the sort and concerns the trio
+        // tables only, which nothing here reads.
+        KTimer t(ctx, "node_rows_kernel");
+        hipLaunchKernelGGL(node_rows_kernel, dim3(sn.G, S), dim3(256), (size_t)((haps->max_haps + 7) / 8) * 256 * sizeof(unsigned long long), ctx->stream, sn);
+        hipLaunchKernelGGL(node_rows_final_kernel, dim3(S), dim3(64), 0, ctx->stream, sn);
+    } else
     { KTimer t(ctx, "ssn_hist_kernel");
       if (haps) hipLaunchKernelGGL(ssn_hist_kernel<true>, dim3(sn.G, S), dim3(256), (size_t)((haps->max_haps + 7) / 8) * 256 * sizeof(unsigned long long), ctx->stream, sn);
       else hipLaunchKernelGGL(ssn_hist_kernel<false>, dim3(sn.G, S), dim3(256), 0, ctx->stream, sn); }

@@ -1310,7 +1310,7 @@ int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio) {
     db->d_abort = reinterpret_cast<unsigned long long *>(base + off_abort);
     db->d_bitmap.view(base + off_bm, words);
     db->d_full.view(base + off_full, fwords);
-    PTX_HIP(ctx, db->d_cov.alloc(db->V));
+    // (d_cov is allocated by the pass that writes it -- popcount_kernel below, node_stats_launch: a resident step on the fused node pass has none)
     // the resident step's last readers left the arena zeroed (cov_arena_clean) unless its layout or place changed since: only the abort counter is reset
     const uint64_t sig = (uint64_t)(uintptr_t)base ^ ((uint64_t)total * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)off_bm << 1) ^ ((uint64_t)off_full << 2) ^ (uint64_t)off_trio;
     db->cov_arena_total = total;
@@ -1548,6 +1548,7 @@ int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool w
     lap("coverage kernels");
     db->cov_count_pending = defer_count && db->V != 0;   // the resident step: node_stats_launch counts the covered bases in its own pass
     if (db->V && !defer_count) {
+        PTX_HIP(ctx, db->d_cov.alloc(db->V));
         KTimer t(ctx, "popcount_kernel");
         if (db->L / db->V >= (uint64_t)ctx->cfg.ncs_prefix_min && !ctx->cfg.ncs_no_prefix)     // long nodes on average: counts from a per-stretch prefix in LDS
             hipLaunchKernelGGL(popcount_long_kernel, dim3(grid_for((db->V + 63) / 64, 4, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, db->V,

@@ -505,7 +505,6 @@ int hap_trio_stats_launch(Ctx *ctx, const Db *db, DevBuf<uint32_t> &d_nnz, DevBu
 constexpr int STAT_CHUNKS = 256;  // most workgroups per species; partials are combined in fixed order (deterministic)
 // chunks per species actually used: ~2048 workgroups in all (one species: 256 chunks; a hundred species: 20)
 static inline uint32_t stat_chunks(uint32_t S, uint32_t target = 2048u) { uint32_t c = target / (S ? S : 1u); return c < 1u ? 1u : (c > (uint32_t)STAT_CHUNKS ? (uint32_t)STAT_CHUNKS : c); }
-struct NodePartial { double mx, zs; unsigned long long nv, zc; };
 
 __global__ void __launch_bounds__(256) node_stats_kernel(const uint32_t *__restrict__ node_base, const uint32_t *__restrict__ node_len,
                                                          const unsigned long long *__restrict__ bases, double min_depth,
@@ -734,6 +733,7 @@ int node_stats_launch(Ctx *ctx, const Db *db, LadBatch *lb, int64_t min_depth, c
     PTX_HIP(ctx, lb->d_nzsum.alloc(S)); PTX_HIP(ctx, lb->d_nzcnt.alloc(S));
     PTX_HIP(ctx, lb->d_partial.alloc((size_t)S * STAT_CHUNKS * 4));
     const bool with_cov = db->cov_count_pending;                 // the resident step left the covered-base counts to this pass
+    if (with_cov) PTX_HIP(ctx, const_cast<Db *>(db)->d_cov.alloc(db->V));
     // the chunk table of this db (made once per variant): ~8192 workgroups in all for the fused kernel (it holds fewer workgroups per CU: shorter ones, so
     // that the last round is short), ~2048 for the plain one; every species at least one chunk and at most STAT_CHUNKS, in proportion to its nodes
     Db *dbm = const_cast<Db *>(db);
@@ -1304,6 +1304,45 @@ int node_haps_build(Ctx *ctx, Db *db) {
     return 0;
 }
 
+// Where the rows are sorted straight from the node arrays and every species has at most 64 haplotypes, the masks are formed INSIDE the sort's histogram
+// pass (ssn_hist_kernel<true>): no mask array, no pass of its own (PANTAX_MASK_PASS=1 keeps mask_nodes_kernel; so do the measurement modes that read the
+// array afterwards).  Everything here is known on the host before the step; *use_nodes_out: the rows go through sample_sort_nodes at all.
+static bool masks_in_sort_possible(const Ctx *ctx, const Db *db, bool *use_nodes_out, bool *ratio_by_node_out) {
+    const uint32_t S = db->S;
+    const uint64_t V = db->V;
+    uint64_t max_vs = 0, max_hs = 0;
+    for (uint32_t s_ = 0; s_ < S; ++s_) {
+        max_vs = std::max<uint64_t>(max_vs, db->h_node_off[s_ + 1] - db->h_node_off[s_]);
+        max_hs = std::max<uint64_t>(max_hs, db->h_hap_off[s_ + 1] - db->h_hap_off[s_]);
+    }
+    // Many species: the rows are sorted species by species straight from the node arrays (sample_sort_nodes.hip) -- no compaction pass in front, no limit
+    // on a species' size below 2^26 nodes (round 3's compaction + segmented sample sort, unreachable since round 4, was deleted in round 5)
+    bool use_nodes = V > SS_MAX_N && max_vs <= SSN_MAX_SEG && S <= 65535;
+    if (!ctx->cfg.row_sort.empty()) {   // measurements / tests: "radix" = the whole-batch sorts at any size; "nodes" = the batched sort wherever it can run
+        const char *ev = ctx->cfg.row_sort.c_str();
+        if (ev[0] == 'r') use_nodes = false;
+        if (ev[0] == 'n') use_nodes = max_vs <= SSN_MAX_SEG && S <= 65535 && V > 0;
+    }
+    // the path_cov_ratio sums ride on the by-node mask pass (PANTAX_RATIO=kernel: ratio_kernel for every species, as in round 3)
+    const bool ratio_by_node = use_node_haps(ctx, db) && V && !ctx->cfg.ratio_kernel;
+    const bool wide = max_hs > (uint64_t)LAD_MAXP;                // (= lb->n_wide != 0: the species lad_prepare lays the wide tables out for)
+    const bool mask_pass_env = ctx->cfg.mask_pass || ctx->cfg.objective == "nodes";
+    if (use_nodes_out) *use_nodes_out = use_nodes;
+    if (ratio_by_node_out) *ratio_by_node_out = ratio_by_node;
+    return use_nodes && ratio_by_node && !db->nh_walk_too && !wide && !mask_pass_env;
+}
+
+// The fused node pass serves the resident step (the coverage pass left its counts: cov_count_pending) whose masks are formed in the sort, without a11 (it
+// needs nvalid on the host and edits the abundances in front of the sort), without the self-cleaning readers, and not the long-node variant of the
+// statistics kernel (the reference-DB shape: its per-stretch prefix in LDS does not fit beside the histogram pass's tree and tables -- it stays on the
+// two kernels).  Nothing hands `cov` or `ab` out after a resident step, so no output asks for the split path.  Option node_pass=split: never.
+bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg) {
+    if (ctx->cfg.node_pass == "split" || !db->cov_count_pending || db->V == 0) return false;
+    if (cfg->sample_nodes != 0 || ctx->cfg.cov_self_clean || db->cov_self_clean) return false;
+    if (db->L / db->V >= (uint64_t)ctx->cfg.ncs_prefix_min && !ctx->cfg.ncs_no_prefix) return false;
+    return masks_in_sort_possible(ctx, db, nullptr, nullptr);
+}
+
 // All of it is enqueued without a host round trip: the row count n and the pattern count K stay on the
 // device (lb->d_counts = {n_rows, K, overflow}); buffers are sized by their host-known bounds (n <= V,
 // K <= k_cap).  cand_on_device: lb->d_hap_bit / d_p were written by first_filter_kernel; otherwise they are
@@ -1374,26 +1413,17 @@ int lad_prepare(Ctx *ctx, const Db *db, LadBatch *lb, bool cand_on_device, int p
     // d_ratio and d_counts live in the step's result arena, which the caller has just zeroed
     // rows: compact -> sort by (species, mask, a)
     Db *dbm = const_cast<Db *>(db);   // staging buffers live in the db so repeated steps do not hipMalloc
-    // Many species: the rows are sorted species by species straight from the node arrays (sample_sort_nodes.hip) -- no compaction pass in front, no limit
-    // on a species' size below 2^26 nodes (round 3's compaction + segmented sample sort, unreachable since round 4, was deleted in round 5)
     uint64_t max_vs = 0;
     for (uint32_t s_ = 0; s_ < S; ++s_) max_vs = std::max<uint64_t>(max_vs, db->h_node_off[s_ + 1] - db->h_node_off[s_]);
-    bool use_nodes = V > SS_MAX_N && max_vs <= SSN_MAX_SEG && S <= 65535;
-    if (!ctx->cfg.row_sort.empty()) {   // measurements / tests: "radix" = the whole-batch sorts at any size; "nodes" = the batched sort wherever it can run
-        const char *ev = ctx->cfg.row_sort.c_str();
-        if (ev[0] == 'r') use_nodes = false;
-        if (ev[0] == 'n') use_nodes = max_vs <= SSN_MAX_SEG && S <= 65535 && V > 0;
-    }
     const bool by_node = use_node_haps(ctx, db);
-    // the path_cov_ratio sums ride on the by-node mask pass (PANTAX_RATIO=kernel: ratio_kernel for every species, as in round 3)
-    const bool ratio_sep = ctx->cfg.ratio_kernel;
-    const bool ratio_by_node = by_node && V && !ratio_sep;
-    // ... and where the rows are sorted straight from the node arrays and every species has at most 64 haplotypes, the masks are formed INSIDE the
-    // sort's histogram pass (ssn_hist_kernel<true>): no mask array, no pass of its own (PANTAX_MASK_PASS=1 keeps mask_nodes_kernel; so do the
-    // measurement modes that read the array afterwards)
-    const bool mask_pass_env = ctx->cfg.mask_pass || ctx->cfg.objective == "nodes";
-    const bool masks_in_sort = use_nodes && ratio_by_node && !db->nh_walk_too && !wide && !mask_pass_env;
+    bool use_nodes = false, ratio_by_node = false;
+    const bool masks_in_sort = masks_in_sort_possible(ctx, db, &use_nodes, &ratio_by_node);
     lb->masks_in_sort = masks_in_sort;
+    // the fused node pass was decided before the step's first kernel (strain_enqueue): no abundance array and no covered-base counts exist, so every reader
+    // of them below (mask_nodes_kernel, ratio_kernel, row_emit_kernel, wide_pattern_kernel; objective_kernel in objective_launch) is excluded by this flag
+    const bool fused = lb->node_pass_fused;
+    if (fused && (!masks_in_sort || wide || !cand_on_device))
+        return fail(ctx, PANTAX_HIP_E_STATE, "lad_prepare: internal (the fused node pass without masks formed in the row sort)");
     if (!masks_in_sort) {
         KTimer t(ctx, by_node ? "mask_nodes_kernel" : "mask_kernel");   // the names rocprofv3 shows
         if (by_node && V)
@@ -1455,14 +1485,22 @@ int lad_prepare(Ctx *ctx, const Db *db, LadBatch *lb, bool cand_on_device, int p
         const RowPatterns pat{lb->d_pat_mask.p, lb->d_pat_start.p, lb->d_pat_species.p, lb->d_sp_pat_off.p, d_K, lb->d_c0.p};
         lb->rows_c0_valid = true;
         RowMaskSource hp;
+        NodeCovSource fz;
+        if (fused) {
+            fz.bases = (const unsigned long long *)db->d_bases.p; fz.bit_off = db->d_bit_off.p; fz.full = db->d_full.p; fz.bitmap = db->d_bitmap.p;
+            fz.active = lb->fused_active; fz.min_depth = lb->fused_min_depth;
+            fz.amax = lb->d_amax.p; fz.nzsum = lb->d_nzsum.p; fz.nvalid = lb->d_nvalid.p; fz.nzcnt = lb->d_nzcnt.p;
+        }
         if (masks_in_sort) {
             uint32_t mh = 0;
             for (uint32_t s_ = 0; s_ < S; ++s_) mh = std::max<uint32_t>(mh, (uint32_t)(db->h_hap_off[s_ + 1] - db->h_hap_off[s_]));
             hp.node_haps = (const unsigned long long *)db->d_node_haps.p; hp.hap_off = db->d_hap_off.p; hp.hap_bit = lb->d_hap_bit.p; hp.sp_p = lb->d_p.p;
             hp.cov = db->d_cov.p; hp.node_len = db->d_node_len.p; hp.ratio = lb->d_ratio.p; hp.max_haps = mh;
         }
-        PTX_TRY(sample_sort_nodes(ctx, lb->d_ab.p, lb->d_mask.p, db->d_node_base.p, S, max_vs, V, dbm->d_row16.p, pack_shift >= 0 ? (uint64_t *)nullptr : ka[0].p,
-                                  pack_shift >= 0 ? ka[0].p : ka[1].p, pack_shift >= 0 ? ka[1].p : ka[2].p, pack_shift, dbm->d_ss_ws.p, d_n, &pat, masks_in_sort ? &hp : nullptr));
+        PTX_TRY(sample_sort_nodes(ctx, fused ? (const double *)nullptr : lb->d_ab.p, lb->d_mask.p, db->d_node_base.p, S, max_vs, V, dbm->d_row16.p, pack_shift >= 0 ? (uint64_t *)nullptr : ka[0].p,
+                                  pack_shift >= 0 ? ka[0].p : ka[1].p, pack_shift >= 0 ? ka[1].p : ka[2].p, pack_shift, dbm->d_ss_ws.p, d_n, &pat, masks_in_sort ? &hp : nullptr,
+                                  fused ? &fz : nullptr));
+        if (fused) dbm->cov_count_pending = false;            // the covered bases were counted (and used) inside the sort
     } else if (use_sample) {   // few rows: sample sort (6 launches) instead of 10+ radix passes of 3 launches each
         PTX_HIP(ctx, dbm->d_ss_ws.alloc(sample_sort_ws_elems(V)));
         PTX_TRY(sample_sort3(ctx, A, B, V, dbm->d_ss_ws.p, d_n));
@@ -2722,6 +2760,7 @@ static int objective_launch(Ctx *ctx, const Db *db, LadBatch *lb, const uint8_t 
         PTX_HIP(ctx, hipGetLastError());
         return 0;
     }
+    if (lb->node_pass_fused) return fail(ctx, PANTAX_HIP_E_STATE, "objective: internal (the pass over the nodes after a fused node pass: no abundance array)");
     KTimer t(ctx, "objective_kernel");
     PTX_HIP(ctx, lb->d_partial.alloc((size_t)S * STAT_CHUNKS * 4));
     if (lb->d_obj_done.n < S) {

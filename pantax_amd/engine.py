@@ -572,6 +572,13 @@ class Engine:
         self._check(self.lib.pantax_hip_sort_rows(self.ctx, C.c_uint64(len(k[0])), p(k[0]), p(k[1]), p(k[2]), int(algo)))
         return k
 
+    def strain_node_stats(self):
+        """pantax_hip_strain_node_stats: per-species (amax, nvalid, nzsum, nzcnt) of the strain step collected last, unrounded"""
+        amax, nzsum = np.zeros(self.S), np.zeros(self.S)
+        nvalid, nzcnt = np.zeros(self.S, dtype=np.uint32), np.zeros(self.S, dtype=np.uint32)
+        self._check(self.lib.pantax_hip_strain_node_stats(self.ctx, self.db, p(amax), p(nvalid), p(nzsum), p(nzcnt)))
+        return amax, nvalid, nzsum, nzcnt
+
     def timing_enable(self, on=True):
         self._check(self.lib.pantax_hip_timing_enable(self.ctx, int(on)))
 
@@ -582,7 +589,7 @@ class Engine:
         self._check(self.lib.pantax_hip_timing_reset(self.ctx))
 
     def timing_get(self):
-        cap = 64
+        cap = 256    # (a resident step launches more than 64 differently named kernels once the index rebuild is in it: the table was cut short)
         names = (C.c_char_p * cap)()
         launches = (C.c_uint64 * cap)()
         ms = (C.c_double * cap)()
