@@ -228,7 +228,7 @@ int db_upload_arrays(Ctx *ctx, pantax_hip_db *db, const GraphPart *parts, const 
                     return fail(ctx, PANTAX_HIP_E_INVALID, "db_upload: species %u: the packed walks do not cover its path steps", s);
                 if (nb_tot + pk.n_blocks >= 0xFFFFFFFFull || pay_units + pk.payload_bytes / PK_UNIT >= 0xFFFFFFFFull)
                     return fail(ctx, PANTAX_HIP_E_LIMIT, "db_upload: more than 2^32 blocks of packed walks");
-                ut.push_back(UnpackSpecies{(uint32_t)nb_tot, (uint32_t)noff_tot, (uint32_t)pay_units, (uint32_t)db->h_path_off[db->h_hap_off[s]], (uint32_t)Ps});
+                ut.push_back(UnpackSpecies{(uint32_t)nb_tot, (uint32_t)noff_tot, (uint32_t)pay_units, (uint32_t)db->h_path_off[db->h_hap_off[s]], (uint32_t)Ps, (uint32_t)(pk.payload_bytes / PK_UNIT)});
                 s_first.push_back(pk.first_seg); s_off.push_back(pk.off_seg); s_pay.push_back(pk.payload_seg);
                 nb_tot += pk.n_blocks; noff_tot += pk.n_blocks + 1; pay_units += pk.payload_bytes / PK_UNIT;
             }

@@ -600,8 +600,15 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
         local_rc = unpack();   // carried by the {failure flag, sums} all-reduce below
         lap("route reads to owners");
     }
-    // everything a rank does on its own shard; a failure here must not leave the other ranks waiting in the exchange below
+    // everything a rank does on its own shard; a failure here must not leave the other ranks waiting in the exchange below.
+    // An image is a cache: one whose header passes but whose arrays fail the load-time checks on the device (a damaged block offset, a walk that
+    // leaves its graph) must end where a truncated one ends, in the graph files.  The checks run per group of species, behind the headers' choice of
+    // sources, so the shard is run again from the start without images (image_fault -> images_off); what it had collected is dropped first.
+    bool images_off = false, image_fault = false, reads_grouped = false;
+    std::string fault_images;   // the images of the group that failed (the check names a haplotype, not a file), for the warning
     auto shard = [&]() -> int {
+    graphs.assign(Ss, HostGraph()); loaded.assign(Ss, 1); use.clear(); Su = 0; met.clear(); info.clear(); hap_off.assign(1, 0); hap_names.clear();
+    if (rs_run) { rs_hap.assign(R, ~0ull); rs_n.assign(R, -1); rs_post.assign(R, 0.0); }
     // Where every selected species' graph comes from (optimize_otu's file choice, profile.rs:2888-2932), decided species by species on
     // a few dozen threads that read HEADERS only:
     //   image_cache >= 1 and a device-ready image <db>/species_graph_info/<otu>.hipdb that is not older than its source (SURVEY 8f-2,
@@ -629,7 +636,7 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
                 const std::string &otu = ranges[sel[i]].species;
                 const int64_t nvert = ranges[sel[i]].end - ranges[sel[i]].start + 1;
                 Source &sc = src[i];
-                if (cfg->image_cache >= 1) {
+                if (cfg->image_cache >= 1 && !images_off) {
                     const std::string img = image_of(otu);
                     if (is_file(img) && file_mtime(img) >= file_mtime(source_of(otu)) && sc.img.open(img).empty() && (int64_t)sc.img.V == nvert) { sc.kind = 1; continue; }
                 }
@@ -779,7 +786,7 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
         bool flags_set = false;
         std::unique_ptr<Loader> cur(new Loader(ctx)), next;
         PTX_TRY(start_load(groups[0], *cur));
-        if (!sharded) { PTX_TRY(reads_group(ctx, reads.rd)); lap("locus-grouped copy of the reads"); }   // (sharded: reads_from_routed grouped what arrived)
+        if (!sharded && !reads_grouped) { PTX_TRY(reads_group(ctx, reads.rd)); reads_grouped = true; lap("locus-grouped copy of the reads"); }   // (sharded: reads_from_routed grouped what arrived)
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             const uint32_t k0 = groups[gi].k0, k1 = groups[gi].k1, Sg = k1 - k0;
             cur->join();
@@ -787,7 +794,18 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
             if (ctx->cfg.trace) std::fprintf(stderr, "[db_upload]            %-28s %9.3f ms%s\n", "graph arrays -> HBM", cur->ms, piped ? " (loader thread, beside the group before)" : "");
             if (gi + 1 < groups.size()) { next.reset(new Loader(ctx)); PTX_TRY(start_load(groups[gi + 1], *next)); }
             DbHolder &sdb = cur->db;
-            PTX_TRY(db_upload_finish(ctx, sdb.db));
+            // (the load-time refusals alone -- a node of length 0, a walk outside its graph, both E_INVALID from the checks on the device: a HIP error, a
+            // limit or a failed allocation is reported as it is, never followed by a second pass over the same device)
+            if (const int rc_fin = db_upload_finish(ctx, sdb.db)) {
+                bool has_image = false;
+                for (const GraphPart &pt : groups[gi].gparts) has_image = has_image || pt.packed;
+                image_fault = has_image && rc_fin == PANTAX_HIP_E_INVALID;
+                uint32_t n_named = 0;
+                for (uint32_t k = k0; k < k1 && image_fault; ++k)
+                    if (src[use[k]].kind == 1 && ++n_named <= 8) fault_images += (fault_images.empty() ? "" : ", ") + src[use[k]].img.path;
+                if (n_named > 8) fault_images += ", ... (" + std::to_string(n_named) + " images in the group)";
+                return rc_fin;
+            }
             lap(Sg == Su ? "db upload" : "db upload (a group of the species)");
             // the same resident reads with the strain-level drop flags; species binned against the selected ranges
             // (reads of unselected species fall outside every range => "U" => skipped, as in the reference
@@ -853,7 +871,14 @@ static int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *
     }
     return 0;
     };   // shard
-    const int shard_rc = local_rc ? local_rc : shard();
+    int shard_rc = local_rc ? local_rc : shard();
+    if (shard_rc && image_fault) {
+        // said once per run, trace or not: the image stays where it is (image_cache 1 writes none), and every run pays this detour until it is removed
+        std::fprintf(stderr, "pantax-hip: warning: a graph image among [%s] failed its load-time checks (%s); the graph files are loaded instead. "
+                             "Remove the damaged image, or run once with image_cache 2 to write it afresh.\n", fault_images.c_str(), pantax_hip_last_error(ctx));
+        images_off = true; image_fault = false;
+        shard_rc = shard();
+    }
 
     // ---- a15: abundance_est (profile.rs:3091-3289)
     std::vector<GenomeRow> genomes;

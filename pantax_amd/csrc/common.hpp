@@ -569,7 +569,7 @@ struct GraphPart {
     PackedWalks pk;
 };
 // stage_db.hip: the packed walks / 16-bit lengths of the species that have them -> d_path_nodes / d_node_len (the others' stretches are left alone)
-struct UnpackSpecies { uint32_t blk_base, off_base, payload_base /* PK_UNIT bytes */, out_base, n_steps; };
+struct UnpackSpecies { uint32_t blk_base, off_base, payload_base /* PK_UNIT bytes */, out_base, n_steps, payload_units /* the species' own payload: no block may end behind it */; };
 int walks_unpack_launch(Ctx *ctx, const UnpackSpecies *d_table, uint32_t n_species, uint32_t n_blocks, const uint32_t *d_first, const uint32_t *d_off,
                         const uint8_t *d_payload, uint32_t *d_path_nodes, hipStream_t stream = nullptr /* null: ctx->stream (timed) */);
 struct WidenSpecies { uint64_t src_base /* u16 index */, dst_base; uint64_t n; };

@@ -98,6 +98,11 @@ std::string SpeciesImage::open(const std::string &p) {
     if (!pread_all(f.fd, path_off.data(), 8 * (H + 1), L.path_off)) return p + ": cannot read the walk offsets";
     if (path_off[0] != 0 || path_off[H] != P) return p + ": graph image offsets are inconsistent";
     for (uint64_t i = 0; i < H; ++i) if (path_off[i] > path_off[i + 1]) return p + ": graph image offsets are inconsistent";
+    // the two ends of the blocks' payload offsets (the header checksum does not cover the table): it starts at 0 and ends with the payload.  What lies
+    // between is checked where it is used, block by block (walks_unpack_kernel, stage_db.hip) -- no pass over the table here
+    uint32_t bo_first = 0, bo_last = 0;
+    if (!pread_all(f.fd, &bo_first, 4, L.blk_off) || !pread_all(f.fd, &bo_last, 4, L.blk_off + 4 * h.n_blocks)) return p + ": cannot read the block offsets";
+    if (bo_first != 0 || (uint64_t)bo_last * PK_UNIT != h.payload_bytes) return p + ": graph image block offsets do not span its payload";
     std::string names(h.name_bytes, '\0');
     if (h.name_bytes && !pread_all(f.fd, &names[0], h.name_bytes, L.names)) return p + ": cannot read the haplotype names";
     hap_names.clear();

@@ -119,8 +119,9 @@ __global__ void __launch_bounds__(256) walks_same_kernel(const uint64_t *__restr
 
 // ---- image format 4 (round 6): packed walks / 16-bit node lengths -> the arrays the kernels read ----
 // One WAVE per block of PK_BLOCK positions: its species by a binary search over the species' first blocks (wave-uniform loads), then four rounds
-// of 64 zigzag deltas -> a wave prefix sum on top of the block's first id and the rounds before.  A block whose width is not 1, 2 or 4 (a damaged
-// file) is written as 0xFFFFFFFF: the walk check that follows every upload reports it.
+// of 64 zigzag deltas -> a wave prefix sum on top of the block's first id and the rounds before.  A block whose width is not 1, 2 or 4 or whose
+// offsets leave its species' payload (a damaged file) is written as 0xFFFFFFFF without touching the payload: the walk check that follows every
+// upload reports it.
 __global__ void __launch_bounds__(256) walks_unpack_kernel(const UnpackSpecies *__restrict__ table, uint32_t n_species, uint32_t n_blocks, const uint32_t *__restrict__ first,
                                                            const uint32_t *__restrict__ off, const uint8_t *__restrict__ payload, uint32_t *__restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -133,9 +134,12 @@ __global__ void __launch_bounds__(256) walks_unpack_kernel(const UnpackSpecies *
     const uint32_t o0 = off[sp.off_base + b], o1 = off[sp.off_base + b + 1], w = o1 - o0;
     const uint64_t pos0 = (uint64_t)b * PK_BLOCK;
     const uint32_t n_in = (uint32_t)min((uint64_t)PK_BLOCK, (uint64_t)sp.n_steps - pos0);
-    const uint8_t *src = payload + ((uint64_t)sp.payload_base + o0) * PK_UNIT;
     uint32_t *dst = out + (uint64_t)sp.out_base + pos0;
-    const bool good = w == 1u || w == 2u || w == 4u;
+    // The offsets come straight from the file: a block is read only if it lies inside its own species' payload.  o1 <= payload_units alone would let a
+    // width of 1, 2 or 4 pass that wraps around 2^32 (o0 huge, o1 small): hence o0 < o1.  Written without short-circuit operators, so that every
+    // operand is fetched up front with the loads the kernel made before -- no scalar load of the bound behind the width test.
+    const bool good = ((w == 1u) | (w == 2u) | (w == 4u)) & (o0 < o1) & (o1 <= sp.payload_units);
+    const uint8_t *src = payload + ((uint64_t)sp.payload_base + (good ? o0 : 0u)) * PK_UNIT;   // (an offset that failed the test forms no address)
     uint32_t carry = first[gb];
 #pragma unroll
     for (uint32_t r = 0; r < PK_BLOCK / 64; ++r) {

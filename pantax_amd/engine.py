@@ -514,7 +514,9 @@ class Engine:
         self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
 
     def save_images(self, paths, hap_names):
-        """one device-ready image per species of the resident db (graph + unique-trio index)."""
+        """one device-ready image per species of the resident db: the graph alone (node lengths, walk offsets, packed walks,
+        haplotype names; format 4, db_image.cpp).  The arrays are downloaded from the device, so the files are the read-back of whatever route
+        uploaded the db."""
         ps = (C.c_char_p * self.S)(*[x.encode() for x in paths])
         hn = (C.c_char_p * max(self.H, 1))(*[x.encode() for x in hap_names])
         self._check(self.lib.pantax_hip_db_save_images(self.ctx, self.db, ps, hn))
