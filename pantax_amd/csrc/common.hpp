@@ -152,7 +152,8 @@ struct CtxConfig {
     bool cov_self_clean = false;     // resident step: the last readers of the coverage arena zero it instead of a zero fill in front of every coverage pass.  OFF: measured
                                      // slower (node_cov_stats_kernel 2.5 -> 6.9 ms with the stores among its loads against 1.5 ms of zero fill at 1e4 strains)
     bool walk_sum_in_bin = false;    // the walk sums of long reads inside the binning pass instead of by walk_sum_kernel.  OFF: measured -- the row of 16 lanes that streams a
-                                     // long walk in bin_slots_kernel adds 0.63 ms there at the cfg5 share where walk_sum_kernel takes 0.38 (cfg5 at full size: +2.7 against 2.9)
+                                     // long walk in bin_slots_kernel adds 0.63 ms there at the cfg5 share where walk_sum_kernel takes 0.38 (cfg5 at full size: +2.7 against 2.9);
+                                     // it needs the walks, so it keeps bin_slots_kernel (0.25 + 0.63 ms there) where the default binning pass is bin_mm_kernel (under 0.01 ms)
     int ncs_prefix_min = 48;         // average node length (bases) from which the node statistics count covered bases through the per-stretch prefix in LDS
     bool ncs_no_prefix = false;      // node statistics of long-node graphs through the per-lane word loop (round 5's kernel; tests compare, measurements)
     bool cov_arena_verify = false;   // tests: a coverage pass that skips its zero fill first checks that the arena IS zero (fails with PANTAX_HIP_E_STATE)
@@ -161,6 +162,8 @@ struct CtxConfig {
     int tv_u = 4, tv_rounds = 4, tf_u = 8, tf_rounds = 1, rows_u = 1, tb_slots = 256, trio_xcd = 3, cov_shape = -1, covf_shape = -1, cov_xcd = 0, group_bucket_bits = 0;
     uint32_t tv_ablate = 0, cov_ablate = 0, ssn_ablate = 0;
     bool trio_two_pass = false;      // every build through records + prefix + rows kernel, as a db's first build (tests, measurements)
+    std::string bin_route;           // "walk": the binning pass of resident reads finds a walk's smallest and largest id by reading the walk (bin_slots_kernel) where it would take
+                                     // them from the record filed at upload (bin_mm_kernel; "minmax" or empty) (tests compare, measurements)
     std::string node_pass;           // "split": the resident step keeps node_cov_stats_kernel + ssn_hist_kernel where it would take the fused node_rows_kernel (tests compare, measurements)
     bool no_absent_skip = false;     // the statistics / histogram passes of the step read the species the species level dropped like the others (tests compare, measurements)
     bool ssn_debug = false, scan_no_huge = false, flag_rank_chained = false, ratio_kernel = false, mask_pass = false, trio_free_at_filter = false,
@@ -492,6 +495,8 @@ struct Reads {
     uint32_t n_long = 0;             // walks of more than 64 steps
     DevBuf<uint2> d_g_slot_rec;      // [R'] {species of the slot's read (coding below), node base - first node id of that species}, written by the binning pass
     DevBuf<uint2> d_g_qm;            // [R'] {read length, MAPQ} in slot order (the binning pass runs over the slots)
+    DevBuf<uint2> d_g_mm;            // [R'] {smallest node id of the walk, largest} in slot order: with d_g_qm all the binning pass needs of a read (bin_mm_kernel); they depend
+                                     //      on the reads alone and are filed by the fill kernels of the upload, which hold every step of every walk anyway
     DevBuf<uint8_t> d_g_flag;        // [R'] drop flags in slot order, refreshed when the flags changed (g_flags_valid)
     uint32_t n_slots = 0;            // reads that own a slot (non-empty walk)
     DevBuf<uint2> d_g_items;         // [n_items] work items of the short-read coverage kernel: groups [x, y) whose reads start inside one block of 2048 node ids

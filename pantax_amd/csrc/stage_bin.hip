@@ -428,6 +428,103 @@ __global__ void __launch_bounds__(BIN_BLOCK) bin_slots_kernel(
     }
 }
 
+// The same pass from the walk's smallest and largest node id FILED AT UPLOAD (Reads::d_g_mm; group_fill_kernel and
+// group_fill_long_kernel): binning asks nothing else of a walk (rcls.rs:237-258), and the two ids depend on the reads alone, not on the
+// db, the options or the step.  Two coalesced 8-byte loads per slot (plus the flag byte), the search, one 8-byte store: no read record,
+// no walk, no chain of dependent loads, nothing to request ahead.  Slot records and counters as in bin_slots_kernel, bit for bit.
+template <bool SORTED, bool LDS_TAB>
+__global__ void __launch_bounds__(BIN_BLOCK) bin_mm_kernel(
+    uint32_t n_slots, const uint2 *__restrict__ g_mm, const uint2 *__restrict__ g_qm, const uint8_t *__restrict__ g_flag /* null: no drop flags */,
+    const uint32_t *__restrict__ rs, const uint32_t *__restrict__ re, const uint32_t *__restrict__ ridx, int S, uint2 *__restrict__ slot_rec,
+    const uint32_t *__restrict__ sp_first_id /* null: db without graphs */, const uint32_t *__restrict__ node_base,
+    unsigned long long *__restrict__ counters_rep) {
+    extern __shared__ unsigned long long s_dyn[];
+    unsigned long long *s_base = s_dyn;                                   // [S]
+    unsigned int *s_cnt = reinterpret_cast<unsigned int *>(s_dyn + (LDS_TAB ? S : 0));    // [3S]
+    uint32_t *s_rs = s_cnt + (LDS_TAB ? 3 * S : 0), *s_re = s_rs + (LDS_TAB ? S : 0), *s_ridx = s_re + (LDS_TAB ? S : 0);
+    uint32_t *s_first = s_ridx + (LDS_TAB ? S : 0), *s_nb = s_first + (LDS_TAB ? S : 0);
+    unsigned long long *__restrict__ counters = counters_rep + (size_t)(blockIdx.x % BIN_REPL) * 4 * S;
+    if (LDS_TAB) {
+        for (int i = threadIdx.x; i < S; i += BIN_BLOCK) {
+            s_base[i] = 0; s_cnt[i] = 0; s_cnt[S + i] = 0; s_cnt[2 * S + i] = 0;
+            s_rs[i] = rs[i]; s_re[i] = re[i]; s_ridx[i] = ridx[i];
+            s_first[i] = sp_first_id ? sp_first_id[i] : 0u;
+            s_nb[i] = sp_first_id ? node_base[i] : 0u;
+        }
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    // whole waves iterate together (lanes past n_slots stay in the loop, masked) so wave-level aggregation is legal
+    for (uint64_t base = (uint64_t)blockIdx.x * BIN_BLOCK + (threadIdx.x - lane); base < n_slots; base += (uint64_t)gridDim.x * BIN_BLOCK) {
+        const uint64_t r = base + lane;
+        int sp = -1;
+        uint32_t q = 0, m = 255u;
+        if (r < n_slots) {
+            const uint2 mm = g_mm[r], qm = g_qm[r];                       // {min id, max id} (a slot's walk holds at least one step), {read length, MAPQ}
+            const uint8_t fl = g_flag ? g_flag[r] : (uint8_t)0;
+            q = qm.x; m = qm.y;
+            sp = LDS_TAB ? find_species<SORTED>(mm.x, mm.y, s_rs, s_re, s_ridx, S) : find_species<SORTED>(mm.x, mm.y, rs, re, ridx, S);
+            uint2 rec = make_uint2(0xFFFFFFFFu, 0u);
+            if (sp >= 0) {
+                uint32_t first = 0, nb = 0;
+                if (LDS_TAB) { first = s_first[sp]; nb = s_nb[sp]; }
+                else if (sp_first_id) { first = sp_first_id[sp]; nb = node_base[sp]; }
+                rec.x = fl ? (uint32_t)(-sp - 2) : (uint32_t)sp;
+                rec.y = nb - first;
+            }
+            slot_rec[r] = rec;
+        }
+        const bool lm = sp >= 0 && m >= 3 && m <= 60, uq = sp >= 0 && m == 60;
+        if (sp < 0) q = 0;
+        const unsigned long long have = __ballot(sp >= 0);
+        if (have == 0) continue;
+        const int sp0 = __shfl(sp, __ffsll((long long)have) - 1);
+        const bool uniform = __all(sp < 0 || sp == sp0);
+        if (uniform) {
+            unsigned long long qs = q;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) qs += __shfl_down(qs, off);
+            const unsigned int c = __popcll(have), l = __popcll(__ballot(lm)), u = __popcll(__ballot(uq));
+            if (lane == 0) {
+                if (LDS_TAB) {
+                    atomicAdd(&s_cnt[sp0], c); atomicAdd(&s_base[sp0], qs);
+                    if (l) atomicAdd(&s_cnt[S + sp0], l);
+                    if (u) atomicAdd(&s_cnt[2 * S + sp0], u);
+                } else {
+                    atomicAdd(&counters[sp0], (unsigned long long)c); atomicAdd(&counters[S + sp0], qs);
+                    if (l) atomicAdd(&counters[2 * S + sp0], (unsigned long long)l);
+                    if (u) atomicAdd(&counters[3 * S + sp0], (unsigned long long)u);
+                }
+            }
+        } else if (sp >= 0) {
+            if (LDS_TAB) {
+                atomicAdd(&s_cnt[sp], 1u);
+                atomicAdd(&s_base[sp], (unsigned long long)q);
+                if (lm) atomicAdd(&s_cnt[S + sp], 1u);
+                if (uq) atomicAdd(&s_cnt[2 * S + sp], 1u);
+            } else {
+                atomicAdd(&counters[sp], 1ull);
+                atomicAdd(&counters[S + sp], (unsigned long long)q);
+                if (lm) atomicAdd(&counters[2 * S + sp], 1ull);
+                if (uq) atomicAdd(&counters[3 * S + sp], 1ull);
+            }
+        }
+    }
+    if (LDS_TAB) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < S; i += BIN_BLOCK) {
+            unsigned int c = s_cnt[i];
+            if (c) {
+                atomicAdd(&counters[i], (unsigned long long)c);
+                atomicAdd(&counters[S + i], s_base[i]);
+                unsigned int l = s_cnt[S + i], u = s_cnt[2 * S + i];
+                if (l) atomicAdd(&counters[2 * S + i], (unsigned long long)l);
+                if (u) atomicAdd(&counters[3 * S + i], (unsigned long long)u);
+            }
+        }
+    }
+}
+
 // drop flags in slot order (one scattered byte per read, once per change of the flags -- not per binning pass)
 __global__ void __launch_bounds__(256) flags_to_slots_kernel(uint64_t R, const uint8_t *__restrict__ flags, const uint32_t *__restrict__ slot_of,
                                                              uint8_t *__restrict__ g_flag) {
@@ -473,6 +570,9 @@ size_t bin_result_words(uint32_t S) { return (size_t)4 * S + BIN_PREFIX; }
 int bin_reads_launch(Ctx *ctx, const Db *db, Reads *rd, unsigned long long *d_counters) {
     int S = (int)db->S;
     PTX_HIP(ctx, hipMemsetAsync(d_counters, 0, bin_counter_words(S) * sizeof(unsigned long long), ctx->stream));
+    const std::string &route = ctx->cfg.bin_route;
+    if (!route.empty() && route != "minmax" && route != "walk") return fail(ctx, PANTAX_HIP_E_INVALID, "bin_reads: option bin_route is \"minmax\" or \"walk\", not \"%s\"", route.c_str());
+    const bool walk = route == "walk";
     rd->species_valid = false;
     rd->binned_db = db->uid;
     if (rd->R == 0) { rd->binned = true; return 0; }
@@ -492,12 +592,25 @@ int bin_reads_launch(Ctx *ctx, const Db *db, Reads *rd, unsigned long long *d_co
             }
             g_flag = rd->d_g_flag.p;
         }
-        if (rd->n_slots) {
+        // (option walk_sum_in_bin: walk sums of long walks on the way -- a db with graphs, reads that hold walks of more than 64 steps)
+        const bool sums = rd->n_long && db->d_node_len.p && db->d_sp_first_id.p && rd->d_long_sum.p && rd->d_long_len0.p && ctx->cfg.walk_sum_in_bin;
+        rd->long_sums_db = sums ? db->uid : 0;
+        const int grid = grid_for(rd->n_slots, BIN_BLOCK, ctx->n_cu * 8);
+        // {min id, max id} of every walk were filed at upload: bin_mm_kernel; the pass that reads the walks stays for the walk sums and for bin_route=walk
+        if (rd->n_slots && !walk && !sums) {
+            KTimer t(ctx, "bin_mm_kernel");
+#define BIN_ARGS rd->n_slots, rd->d_g_mm.p, rd->d_g_qm.p, g_flag, db->d_rng_start.p, db->d_rng_end.p, db->d_rng_idx.p, S, rd->d_g_slot_rec.p, db->d_sp_first_id.p, \
+                 db->d_node_base.p, d_counters
+            if (db->ranges_sorted_disjoint) {
+                if (lds) hipLaunchKernelGGL((bin_mm_kernel<true, true>), dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, BIN_ARGS);
+                else hipLaunchKernelGGL((bin_mm_kernel<true, false>), dim3(grid), dim3(BIN_BLOCK), 0, ctx->stream, BIN_ARGS);
+            } else {
+                if (lds) hipLaunchKernelGGL((bin_mm_kernel<false, true>), dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, BIN_ARGS);
+                else hipLaunchKernelGGL((bin_mm_kernel<false, false>), dim3(grid), dim3(BIN_BLOCK), 0, ctx->stream, BIN_ARGS);
+            }
+#undef BIN_ARGS
+        } else if (rd->n_slots) {
             KTimer t(ctx, "bin_slots_kernel");
-            const int grid = grid_for(rd->n_slots, BIN_BLOCK, ctx->n_cu * 8);
-            // (option walk_sum_in_bin: walk sums of long walks on the way -- a db with graphs, reads that hold walks of more than 64 steps)
-            const bool sums = rd->n_long && db->d_node_len.p && db->d_sp_first_id.p && rd->d_long_sum.p && rd->d_long_len0.p && ctx->cfg.walk_sum_in_bin;
-            rd->long_sums_db = sums ? db->uid : 0;
 #define BIN_ARGS rd->n_slots, rd->d_g_read_rec.p, rd->d_g_node_id.p, rd->d_g_qm.p, g_flag, db->d_rng_start.p, db->d_rng_end.p, db->d_rng_idx.p, S, \
                  rd->d_g_slot_rec.p, db->d_sp_first_id.p, db->d_node_base.p, d_counters, sums ? (const uint32_t *)db->d_node_len.p : (const uint32_t *)nullptr, \
                  rd->d_long_sum.p, rd->d_long_len0.p

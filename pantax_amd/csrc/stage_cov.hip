@@ -976,8 +976,9 @@ __global__ void __launch_bounds__(64) group_layout_kernel(uint32_t NB, int g, co
 __global__ void __launch_bounds__(256) group_fill_kernel(uint32_t n_slots, const uint32_t *__restrict__ node_id, int shift,
                                                          const uint32_t *__restrict__ base_s, const uint32_t *__restrict__ slot_rel, uint4 *__restrict__ g_read_rec,
                                                          uint32_t *__restrict__ g_node_id, uint32_t *__restrict__ g_group_slot,
-                                                         uint8_t *__restrict__ g_step_dup) {
+                                                         uint8_t *__restrict__ g_step_dup, uint2 *__restrict__ g_mm) {
     __shared__ uint32_t s_excl[4][65], s_b[4][64], s_sb[4][64];
+    __shared__ uint2 s_mm[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t n_waves = (n_slots + 63) / 64;
     for (uint32_t w = blockIdx.x * 4 + wave; w < n_waves; w += gridDim.x * 4) {
@@ -989,7 +990,7 @@ __global__ void __launch_bounds__(256) group_fill_kernel(uint32_t n_slots, const
             sb = base_s[node_id[b] >> shift] + slot_rel[slot];
             rec.x = sb;
             g_read_rec[slot] = rec;
-            if (k > 64) k = 0;                                       // laid out by group_fill_long_kernel, one workgroup per walk
+            if (k > 64) { k = 0; s_mm[wave][lane] = make_uint2(0xFFFFFFFFu, 0u); }   // laid out by group_fill_long_kernel, one workgroup per walk (min / max: its atomics)
             else if ((sb & 63u) == 0u) g_group_slot[sb >> 6] = slot; // a walk of <= 64 steps lies inside one 64-step group
         }
         const uint32_t incl = wave_incl_scan_dpp(k);
@@ -1012,32 +1013,42 @@ __global__ void __launch_bounds__(256) group_fill_kernel(uint32_t n_slots, const
             const uint32_t i = on ? f - s_excl[wave][o] : 0u;
             const uint32_t id = on ? node_id[s_b[wave][o] + i] : 0u;
             // first occurrence of my node among the i earlier steps of my walk: they sit in the lanes below, or in the round before
-            uint32_t dup = 0;
+            uint32_t dup = 0, mn = id, mx = id;                      // smallest / largest id of my walk up to my step: complete in the lane of its last step
             const uint32_t imax = wave_reduce(i, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
             for (uint32_t d = 1; d <= imax; ++d) {
                 const uint32_t cur = __shfl(id, (lane - (int)d) & 63), old = __shfl(prev_id, (lane - (int)d) & 63);
                 const uint32_t other = (int)d <= lane ? cur : old;
                 if (d <= i && other == id) dup = d;                   // the largest such distance = the first occurrence
+                const uint32_t mine = d <= i ? other : id;
+                mn = min(mn, mine); mx = max(mx, mine);
             }
             if (on) {
                 const uint32_t dst = s_sb[wave][o] + i;
                 g_node_id[dst] = id;
                 g_step_dup[dst] = (uint8_t)(dup | (i == 0 ? STEP_START : 0u));
+                if (i + 1 == s_excl[wave][o + 1] - s_excl[wave][o]) s_mm[wave][o] = make_uint2(mn, mx);   // the walk's last step (the owner of a flat step holds at least one)
             }
             prev_id = id;
         }
+        // {min id, max id} of the 64 walks, one coalesced store (a slot holds a walk of at least one step: every row of s_mm was written)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+        if (slot < n_slots) g_mm[slot] = s_mm[wave][lane];
         __builtin_amdgcn_wave_barrier();                             // the LDS rows are reused by this wave's next 64 slots
     }
 }
 
 // Walks of more than 64 steps: one workgroup copies the walk (coalesced) and decides for every step whether its node
 // occurred earlier in the walk -- an LDS hash of (node id -> smallest position) for walks of up to LONG_HASH/2 steps,
-// a plain scan of the earlier steps above that.
+// a plain scan of the earlier steps above that.  The copy loop, which every walk takes, also forms the walk's smallest and largest id
+// for the binning pass (group_fill_kernel, which runs first, left the neutral pair in the slot's place): one atomic pair per wave.
 constexpr uint32_t LONG_HASH = 8192;
 __global__ void __launch_bounds__(256) group_fill_long_kernel(uint64_t R, const uint32_t *__restrict__ step_off, const uint32_t *__restrict__ node_id,
                                                               int shift, const uint32_t *__restrict__ base_s, const uint32_t *__restrict__ slot_of,
                                                               const uint32_t *__restrict__ slot_rel, uint32_t *__restrict__ g_node_id,
-                                                              uint32_t *__restrict__ g_group_slot, uint8_t *__restrict__ g_step_dup) {
+                                                              uint32_t *__restrict__ g_group_slot, uint8_t *__restrict__ g_step_dup,
+                                                              uint2 *__restrict__ g_mm) {
     __shared__ uint32_t h_key[LONG_HASH], h_pos[LONG_HASH];
     constexpr uint32_t EMPTY = 0xFFFFFFFFu;
     for (uint64_t r = blockIdx.x; r < R; r += gridDim.x) {
@@ -1045,9 +1056,18 @@ __global__ void __launch_bounds__(256) group_fill_long_kernel(uint64_t R, const 
         if (k <= 64) continue;
         const uint32_t slot = slot_of[r];
         const uint32_t sb = base_s[node_id[b] >> shift] + slot_rel[slot];
+        uint32_t mn = 0xFFFFFFFFu, mx = 0;
         for (uint32_t i = threadIdx.x; i < k; i += 256) {
-            g_node_id[sb + i] = node_id[b + i];
+            const uint32_t id = node_id[b + i];
+            g_node_id[sb + i] = id;
+            mn = min(mn, id); mx = max(mx, id);
             if (((sb + i) & 63u) == 0u) g_group_slot[(sb + i) >> 6] = slot;   // every group this walk's steps begin
+        }
+        mn = wave_reduce(mn, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
+        mx = wave_reduce(mx, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
+        if ((threadIdx.x & 63) == 0) {
+            uint32_t *mm = reinterpret_cast<uint32_t *>(g_mm + slot);
+            atomicMin(mm, mn); atomicMax(mm + 1, mx);
         }
         if (k <= LONG_HASH / 2) {
             for (uint32_t i = threadIdx.x; i < LONG_HASH; i += 256) { h_key[i] = EMPTY; h_pos[i] = EMPTY; }
@@ -1104,6 +1124,7 @@ int build_step_read(Ctx *ctx, Reads *rd, uint32_t max_node_id) {
     PTX_HIP(ctx, rd->d_slot_of.alloc(rd->R ? rd->R : 1));
     PTX_HIP(ctx, rd->d_g_slot_rec.alloc(rd->R ? rd->R : 1));
     PTX_HIP(ctx, rd->d_g_qm.alloc(rd->R ? rd->R : 1));
+    PTX_HIP(ctx, rd->d_g_mm.alloc(rd->R ? rd->R : 1));
     if (rd->R == 0) return 0;
     if (rd->T == 0) {
         PTX_HIP(ctx, hipMemsetAsync(rd->d_slot_of.p, 0xFF, rd->R * sizeof(uint32_t), ctx->stream));
@@ -1153,11 +1174,11 @@ int build_step_read(Ctx *ctx, Reads *rd, uint32_t max_node_id) {
     PTX_TRY(byte_fill(ctx, rd->d_g_step_dup.p, 0xFF, rd->T_pad));                                            // STEP_PAD
     if (rd->n_slots)
         hipLaunchKernelGGL(group_fill_kernel, dim3(grid_for(rd->n_slots, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, rd->n_slots, rd->d_node_id.p, ushift,
-                           base_s, slot_rel.p, rd->d_g_read_rec.p, rd->d_g_node_id.p, rd->d_g_group_slot.p, rd->d_g_step_dup.p);
+                           base_s, slot_rel.p, rd->d_g_read_rec.p, rd->d_g_node_id.p, rd->d_g_group_slot.p, rd->d_g_step_dup.p, rd->d_g_mm.p);
     if (rd->n_long) {
         const uint32_t gridL = (uint32_t)std::min<uint64_t>(rd->R, (uint64_t)ctx->n_cu * 64);
         hipLaunchKernelGGL(group_fill_long_kernel, dim3(gridL), dim3(256), 0, ctx->stream, rd->R, rd->d_step_off.p, rd->d_node_id.p, ushift, base_s,
-                           rd->d_slot_of.p, slot_rel.p, rd->d_g_node_id.p, rd->d_g_group_slot.p, rd->d_g_step_dup.p);
+                           rd->d_slot_of.p, slot_rel.p, rd->d_g_node_id.p, rd->d_g_group_slot.p, rd->d_g_step_dup.p, rd->d_g_mm.p);
         PTX_HIP(ctx, rd->d_long_sum.alloc(rd->R));
         PTX_HIP(ctx, rd->d_long_len0.alloc(rd->R));
     }
