@@ -455,6 +455,11 @@ int pantax_hip_format_f64(double v, char *buf, size_t cap);
 int pantax_hip_strain_node_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, double *amax_out, uint32_t *nvalid_out, double *nzsum_out,
                                  uint32_t *nzcnt_out);
 
+/* The per-haplotype unique-trio statistics (a9) of the same step, under the same contract: the number of unique-trio windows with an abundance > 0
+ * and the unrounded mean of those that pass the z-score filter (0.0 where the standard deviation is 0), for every haplotype of the db -- those
+ * the first filter dropped included; zeros for the haplotypes of a species the step skipped.  [H] each; either output may be NULL. */
+int pantax_hip_strain_hap_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, uint32_t *nnz_out, double *mean_filtered_out);
+
 /* ---- measurement: HIP-event timings of kernels launched on the ctx stream ---------------- */
 int pantax_hip_timing_enable(pantax_hip_ctx *ctx, int on);
 int pantax_hip_timing_reset(pantax_hip_ctx *ctx);

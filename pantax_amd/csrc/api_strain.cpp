@@ -349,6 +349,18 @@ int pantax_hip_strain_node_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, double 
     return 0;
 }
 
+int pantax_hip_strain_hap_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, uint32_t *nnz_out, double *mean_filtered_out) {
+    if (!ctx || !db) return PANTAX_HIP_E_INVALID;
+    PTX_ENTER(ctx);
+    if (db->stats_slot < 0 || db->h_arena[db->stats_slot].p == nullptr) return fail(ctx, PANTAX_HIP_E_STATE, "strain_hap_stats: no strain step of this db has been collected");
+    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "strain_hap_stats: %d enqueued step(s) of this db have not been collected (their download may reuse the slot)", db->step_inflight);
+    const ArenaLayout L(db->S, db->H);
+    const uint8_t *b = db->h_arena[db->stats_slot].p;   // (nothing in flight: no download is writing either slot)
+    if (nnz_out) std::memcpy(nnz_out, b + L.nnz, sizeof(uint32_t) * db->H);
+    if (mean_filtered_out) std::memcpy(mean_filtered_out, b + L.meanf, sizeof(double) * db->H);
+    return 0;
+}
+
 int pantax_hip_pao_solve_batch(pantax_hip_ctx *ctx, const pantax_hip_species_batch *in, const pantax_hip_solution_batch *out) {
     if (!ctx || !in || !out || !in->node_off || !in->node_len || !in->node_abundance || !in->hap_off || !in->path_off || !in->path_nodes ||
         !in->cand_off || !in->cand_path_idx || !out->x || !out->status)

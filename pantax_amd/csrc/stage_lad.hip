@@ -192,26 +192,34 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
 // in fixed lane order.  A chunk's partials are then added in chunk order by one wave per species.  Every sum has a fixed order: same bits
 // on every run (the reference's own order is that of a hash set).  Three passes like zscore_filter (profile.rs:1028-1051): (sum, count)
 // of the non-zero abundances -> mean; squared deviations -> sd; (sum, count) of |z| < 3 -> the filtered mean.
+// ALL NON-ZERO ABUNDANCES OF A HAPLOTYPE EQUAL (x, x, ... c times): the reference's mean is c SEQUENTIAL additions of x over c (data.iter().sum()) --
+// whatever the order of the rows --, and whether that gives x back decides sd == 0 and with it the filtered mean (0.0 or x).  The sums here have
+// another shape (lanes, a DPP tree, chunks) and land on the other side for many (c, x).  So pass 0 also carries, per haplotype, the OR of the
+// values' bits and the OR of their complements (HapBits; exact, order-free, zero for "nothing"): no bit position is set in both exactly when all
+// values are equal, and then hap_combine_kernel forms the mean the reference's way.  Passes 1 and 2 follow from that mean.
 // ---------------------------------------------------------------------------------------------
 constexpr uint32_t HS_CHUNK_ROWS = 1024, HS_LDS_HAPS = 1024;
 constexpr int HS_SLAB = 16;   // haplotypes whose accumulators a lane keeps in registers at a time
 struct HapAcc { double a; uint32_t c, n; };   // sum, count of the pass, rows seen (pass 0)
+struct HapBits { unsigned long long any1, any0; };   // pass 0: OR of the non-zero values' bits, OR of their complements
 
 template <int PASS>
 __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restrict__ chunks, const uint64_t *__restrict__ hap_off, const uint16_t *__restrict__ row_hap,
                                                            unsigned long long *tb /* read, and -- clean != 0, pass 0 -- zeroed behind the read */, const trio_len_t *__restrict__ tlen,
                                                            const double *__restrict__ mean0, const double *__restrict__ sd, HapAcc *__restrict__ part,
+                                                           HapBits *__restrict__ pbits /* pass 0: beside the partials, same index */,
                                                            double *__restrict__ cx, uint16_t *__restrict__ chh, uint32_t *__restrict__ cn, uint32_t clean,
                                                            const uint8_t *__restrict__ active) {
     extern __shared__ HapAcc s_hap_acc[];
     __shared__ uint32_t s_qrow[128];
     __shared__ unsigned long long s_qtb[128];
+    __shared__ unsigned long long s_any[PASS == 0 ? 128 : 1];   // pass 0, up to 64 haplotypes on the slab route: [h] OR of the value bits, [64 + h] OR of their complements
     const uint4 ch = chunks[blockIdx.x];                       // {species, first row, end row, first partial}
     const uint32_t h0 = (uint32_t)hap_off[ch.x], Hs = (uint32_t)hap_off[ch.x + 1] - h0;
     const int lane = threadIdx.x;
     // a species the species level dropped: the coverage pass skipped its reads, its rows' abundances are all zero -- the partials of an empty chunk, nothing read
     if (active != nullptr && active[ch.x] == 0) {              // (chunk-uniform)
-        for (uint32_t h = (uint32_t)lane; h < Hs; h += 64) part[ch.w + h] = HapAcc{0.0, 0u, 0u};
+        for (uint32_t h = (uint32_t)lane; h < Hs; h += 64) { part[ch.w + h] = HapAcc{0.0, 0u, 0u}; if (PASS == 0) pbits[ch.w + h] = HapBits{0ull, 0ull}; }
         if (PASS == 0 && lane == 0) cn[blockIdx.x] = 0u;
         return;
     }
@@ -230,7 +238,9 @@ __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restri
     const bool in_reg = Hs <= 64u;
     const bool in_lds = !in_reg && Hs <= HS_LDS_HAPS;
     HapAcc *acc = in_lds ? s_hap_acc : part + ch.w;            // (more than 64 haplotypes: LDS; beyond HS_LDS_HAPS the chunk's own, zero-filled row of partials)
-    if (in_lds) for (uint32_t h = lane; h < Hs; h += 64) acc[h] = HapAcc{0.0, 0u, 0u};
+    HapBits *accb = in_lds ? reinterpret_cast<HapBits *>(s_hap_acc + Hs) : pbits + ch.w;   // (pass 0; the LDS holds 32 bytes per haplotype)
+    if (in_lds) for (uint32_t h = lane; h < Hs; h += 64) { acc[h] = HapAcc{0.0, 0u, 0u}; if (PASS == 0) accb[h] = HapBits{0ull, 0ull}; }
+    if (PASS == 0 && in_reg) { s_any[lane] = 0ull; s_any[64 + lane] = 0ull; }
     __syncthreads();
     double my_mean = 0.0, my_sd = 0.0;
     if (in_reg && PASS >= 1 && (uint32_t)lane < Hs) { my_mean = mean0[h0 + lane]; if (PASS == 2) my_sd = sd[h0 + lane]; }
@@ -306,6 +316,7 @@ __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restri
         // reductions at the end.  (-DHS_NO_TRANSPOSE: the slabs of 16 below, as up to 16 haplotypes.)
         double acc_t = 0.0;
         uint32_t cnt_t = 0;
+        unsigned long long any1_t = 0ull, any0_t = 0ull;
         auto sink_t = [&](uint32_t h, double val, bool flag) {
             unsigned long long todo = __ballot(flag);
             while (todo) {
@@ -313,7 +324,7 @@ __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restri
                 todo &= todo - 1ull;
                 const uint32_t he = (uint32_t)__builtin_amdgcn_readlane((int)h, e);
                 const double ve = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(val), e), __builtin_amdgcn_readlane(__double2loint(val), e));
-                if ((uint32_t)lane == he) { acc_t += ve; ++cnt_t; }
+                if ((uint32_t)lane == he) { acc_t += ve; ++cnt_t; if (PASS == 0) { any1_t |= (unsigned long long)__double_as_longlong(ve); any0_t |= ~(unsigned long long)__double_as_longlong(ve); } }
             }
         };
         if (PASS == 0) compact_rows([&](uint32_t h, double x, bool v) { sink_t(h, v ? x : 0.0, v); });
@@ -327,7 +338,7 @@ __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restri
                 pass_value(h, x, v, val, flag);
                 sink_t(h, val, flag);
             }
-        if ((uint32_t)lane < Hs) part[ch.w + (uint32_t)lane] = HapAcc{acc_t, cnt_t, 0u};
+        if ((uint32_t)lane < Hs) { part[ch.w + (uint32_t)lane] = HapAcc{acc_t, cnt_t, 0u}; if (PASS == 0) pbits[ch.w + (uint32_t)lane] = HapBits{any1_t, any0_t}; }
         if (PASS == 0 && lane == 0) cn[blockIdx.x] = n_c;
         return;
     }
@@ -348,7 +359,12 @@ __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restri
                     c_[k] += (m_ && flag) ? 1u : 0u;
                 }
             };
-            if (PASS == 0 && slab == 0) compact_rows([&](uint32_t h, double x, bool v) { sink_reg(h, v ? x : 0.0, v); });
+            // the value bits: an OR has no order, so the entries of a dense batch go straight to the haplotype's two LDS words (two LDS atomics per 64 entries --
+            // carried through the compare-and-select above they cost 32 more 64-bit registers a lane and 0.2 ms over the three passes at 1e4 strains)
+            if (PASS == 0 && slab == 0) compact_rows([&](uint32_t h, double x, bool v) {
+                sink_reg(h, v ? x : 0.0, v);
+                if (v) { const unsigned long long b_ = (unsigned long long)__double_as_longlong(x); atomicOr(&s_any[h], b_); atomicOr(&s_any[64u + h], ~b_); }
+            });
             else {
                 // the compacted stretch was written by this very wave, entry i by the lane that reads it back: ordering within the wave is all that is
                 // needed.  (Until round 6 a __threadfence() stood here: agent scope = write-back + invalidate of the XCD's L2 on gfx950, by every chunk's
@@ -373,7 +389,11 @@ __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restri
                 if (lane == 0 && hh < Hs) part[ch.w + hh] = HapAcc{v, c, 0u};
             }
         }
-        if (PASS == 0 && lane == 0) cn[blockIdx.x] = n_c;
+        if (PASS == 0) {
+            __syncthreads();                                       // (one wave: the LDS atomics of all lanes are done)
+            if ((uint32_t)lane < Hs) pbits[ch.w + (uint32_t)lane] = HapBits{s_any[lane], s_any[64 + lane]};
+            if (lane == 0) cn[blockIdx.x] = n_c;
+        }
         return;
     }
     auto sink_gen = [&](uint32_t h, double val, bool flag, bool valid) {
@@ -385,6 +405,12 @@ __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restri
             const double v = wave_reduce(mine ? val : 0.0, [](double a2, double b2) { return a2 + b2; });
             const uint32_t c = (uint32_t)__popcll(__ballot(mine && flag));
             if (lane == 0) { HapAcc t = acc[hh]; t.a += v; t.c += c; t.n += (uint32_t)__popcll(sel); acc[hh] = t; }
+            if (PASS == 0) {
+                const unsigned long long b_ = (unsigned long long)__double_as_longlong(val);
+                const unsigned long long o1 = wave_reduce((mine && flag) ? b_ : 0ull, [](unsigned long long x, unsigned long long y) { return x | y; });
+                const unsigned long long o0 = wave_reduce((mine && flag) ? ~b_ : 0ull, [](unsigned long long x, unsigned long long y) { return x | y; });
+                if (lane == 0) { HapBits t = accb[hh]; t.any1 |= o1; t.any0 |= o0; accb[hh] = t; }
+            }
             todo &= ~sel;
         }
     };
@@ -400,17 +426,18 @@ __global__ void __launch_bounds__(64) hap_rows_pass_kernel(const uint4 *__restri
             sink_gen(h, val, flag, v);
         }
     __syncthreads();
-    if (in_lds) for (uint32_t h = lane; h < Hs; h += 64) part[ch.w + h] = acc[h];
+    if (in_lds) for (uint32_t h = lane; h < Hs; h += 64) { part[ch.w + h] = acc[h]; if (PASS == 0) pbits[ch.w + h] = accb[h]; }
     if (PASS == 0 && lane == 0) cn[blockIdx.x] = n_c;
 }
 template <int PASS>
 __global__ void __launch_bounds__(256) hap_combine_kernel(const uint32_t *__restrict__ sp_chunk_off, const uint4 *__restrict__ chunks, const uint64_t *__restrict__ hap_off,
-                                                          const HapAcc *__restrict__ part, uint32_t *__restrict__ nnz, double *__restrict__ mean0, double *__restrict__ sd,
+                                                          const HapAcc *__restrict__ part, const HapBits *__restrict__ pbits, uint32_t *__restrict__ nnz, double *__restrict__ mean0, double *__restrict__ sd,
                                                           double *__restrict__ meanf) {
     // one workgroup per species; the chunks' partials of a haplotype are summed by `parts` threads (chunk c by thread c mod parts, in chunk order), the
     // parts then in part order: a fixed order of additions, whatever the launch (same bits every run)
     __shared__ double s_a[256];
     __shared__ unsigned long long s_c[256];
+    __shared__ unsigned long long s_o1[PASS == 0 ? 256 : 1], s_o0[PASS == 0 ? 256 : 1];
     const uint32_t s = blockIdx.x, c0 = sp_chunk_off[s], c1 = sp_chunk_off[s + 1];
     const uint32_t h0 = (uint32_t)hap_off[s], Hs = (uint32_t)hap_off[s + 1] - h0;
     uint32_t width = 256;                                  // threads side by side over the haplotypes: the power of two >= Hs, at most 256
@@ -419,13 +446,27 @@ __global__ void __launch_bounds__(256) hap_combine_kernel(const uint32_t *__rest
     for (uint32_t hb = 0; hb < Hs; hb += width) {
         const uint32_t h = hb + hl;
         double a = 0.0;
-        unsigned long long c = 0;
-        if (h < Hs) for (uint32_t k = c0 + pt; k < c1; k += parts) { const HapAcc p = part[chunks[k].w + h]; a += p.a; c += p.c; }
+        unsigned long long c = 0, o1 = 0, o0 = 0;
+        if (h < Hs) for (uint32_t k = c0 + pt; k < c1; k += parts) {
+            const HapAcc p = part[chunks[k].w + h]; a += p.a; c += p.c;
+            if (PASS == 0) { const HapBits b = pbits[chunks[k].w + h]; o1 |= b.any1; o0 |= b.any0; }
+        }
         s_a[threadIdx.x] = a; s_c[threadIdx.x] = c;
+        if (PASS == 0) { s_o1[threadIdx.x] = o1; s_o0[threadIdx.x] = o0; }
         __syncthreads();
         if (pt == 0 && h < Hs) {
             for (uint32_t q = 1; q < parts; ++q) { a += s_a[q * width + hl]; c += s_c[q * width + hl]; }
-            if (PASS == 0) { nnz[h0 + h] = (uint32_t)c; mean0[h0 + h] = c ? a / (double)c : 0.0; }              // profile.rs:1037
+            if (PASS == 0) {
+                for (uint32_t q = 1; q < parts; ++q) { o1 |= s_o1[q * width + hl]; o0 |= s_o0[q * width + hl]; }
+                // c <= the unique-trio windows of this haplotype, and the loop runs only where every one of its non-zero windows has the same abundance: one thread,
+                // c dependent additions (some 1e8 a second -- 1e5 equally covered windows hold the species' workgroup for a millisecond).  The order IS the result.
+                if (c > 1 && (o1 & o0) == 0ull) {                          // all c values are the same x: the reference's sum, c sequential additions
+                    const double x = __longlong_as_double((long long)o1);
+                    a = 0.0;
+                    for (unsigned long long i = 0; i < c; ++i) a += x;
+                }
+                nnz[h0 + h] = (uint32_t)c; mean0[h0 + h] = c ? a / (double)c : 0.0;                              // profile.rs:1037
+            }
             else if (PASS == 1) { const double n = (double)nnz[h0 + h]; sd[h0 + h] = n > 0 ? sqrt(a / n) : 0.0; }   // :1038-1041
             else meanf[h0 + h] = c ? a / (double)c : 0.0;                 // sd == 0 -> empty -> 0.0 (:1043-1045, :1143-1147)
         }
@@ -479,20 +520,22 @@ int hap_trio_stats_launch(Ctx *ctx, const Db *db, DevBuf<uint32_t> &d_nnz, DevBu
     Db *dbm = const_cast<Db *>(db);
     const uint32_t S = db->S, NC = db->n_stat_chunks;
     const uint64_t H = db->H;
-    PTX_HIP(ctx, dbm->d_hap_part.alloc(2 * (size_t)std::max<uint64_t>(db->n_stat_partials, 1) + 2 * H));   // the chunks' partials (16 B each), then mean and sd of pass 0 / 1
+    const size_t NP = (size_t)std::max<uint64_t>(db->n_stat_partials, 1);
+    PTX_HIP(ctx, dbm->d_hap_part.alloc(4 * NP + 2 * H));   // the chunks' partials (16 B each), pass 0's value bits beside them (16 B each), then mean and sd of pass 0 / 1
     HapAcc *part = reinterpret_cast<HapAcc *>(dbm->d_hap_part.p);
-    double *mean0 = dbm->d_hap_part.p + 2 * (size_t)std::max<uint64_t>(db->n_stat_partials, 1), *sd = mean0 + H;
-    const size_t lds = (size_t)db->stat_lds_haps * sizeof(HapAcc);
+    HapBits *pbits = reinterpret_cast<HapBits *>(dbm->d_hap_part.p + 2 * NP);
+    double *mean0 = dbm->d_hap_part.p + 4 * NP, *sd = mean0 + H;
+    const size_t lds_acc = (size_t)db->stat_lds_haps * sizeof(HapAcc), lds_bits = (size_t)db->stat_lds_haps * sizeof(HapBits);   // (the bits: pass 0 alone)
     // the compacted copy of the non-zero rows {value, owner}, chunk by chunk in place of the chunk's rows, and its length per chunk
     PTX_HIP(ctx, dbm->d_hs_x.alloc(std::max<uint64_t>(db->U, 1))); PTX_HIP(ctx, dbm->d_hs_h.alloc(std::max<uint64_t>(db->U, 1))); PTX_HIP(ctx, dbm->d_hs_n.alloc(std::max<uint32_t>(NC, 1)));
     KTimer t(ctx, "hap_rows_pass_kernel");
 #define HS_PASS(PP)                                                                                                                                            \
-    if (db->stat_global_rows) PTX_TRY(zero_fill(ctx, part, (size_t)std::max<uint64_t>(db->n_stat_partials, 1) * sizeof(HapAcc)));                            \
-    if (NC) hipLaunchKernelGGL(hap_rows_pass_kernel<PP>, dim3(NC), dim3(64), lds, ctx->stream, (const uint4 *)db->d_stat_chunks.p, (const uint64_t *)db->d_hap_off.p, \
+    if (db->stat_global_rows) { KTimer tz(ctx, "hap_partials_zero_fill"); PTX_TRY(zero_fill(ctx, part, NP * (sizeof(HapAcc) + (PP == 0 ? sizeof(HapBits) : 0)))); }   /* (the bits lie behind the partials) */ \
+    if (NC) hipLaunchKernelGGL(hap_rows_pass_kernel<PP>, dim3(NC), dim3(64), lds_acc + (PP == 0 ? lds_bits : 0), ctx->stream, (const uint4 *)db->d_stat_chunks.p, (const uint64_t *)db->d_hap_off.p, \
                                TRIO_HAP_PTR(db), (unsigned long long *)db->d_trio_bases.p, (const trio_len_t *)db->d_trio_len.p,          \
-                               (const double *)mean0, (const double *)sd, part, dbm->d_hs_x.p, dbm->d_hs_h.p, dbm->d_hs_n.p, db->cov_self_clean ? 1u : 0u, d_active);  \
+                               (const double *)mean0, (const double *)sd, part, pbits, dbm->d_hs_x.p, dbm->d_hs_h.p, dbm->d_hs_n.p, db->cov_self_clean ? 1u : 0u, d_active);  \
     hipLaunchKernelGGL(hap_combine_kernel<PP>, dim3(S), dim3(256), 0, ctx->stream, (const uint32_t *)db->d_sp_chunk_off.p, (const uint4 *)db->d_stat_chunks.p,  \
-                       (const uint64_t *)db->d_hap_off.p, (const HapAcc *)part, d_nnz.p, mean0, sd, d_mean.p);
+                       (const uint64_t *)db->d_hap_off.p, (const HapAcc *)part, (const HapBits *)pbits, d_nnz.p, mean0, sd, d_mean.p);
     HS_PASS(0) HS_PASS(1) HS_PASS(2)
 #undef HS_PASS
     PTX_HIP(ctx, hipGetLastError());

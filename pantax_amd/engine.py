@@ -581,6 +581,12 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_node_stats(self.ctx, self.db, p(amax), p(nvalid), p(nzsum), p(nzcnt)))
         return amax, nvalid, nzsum, nzcnt
 
+    def strain_hap_stats(self):
+        """pantax_hip_strain_hap_stats: per-haplotype (nnz, mean_filtered) of the strain step collected last, as the device left them"""
+        nnz, meanf = np.zeros(max(self.H, 1), dtype=np.uint32), np.zeros(max(self.H, 1))
+        self._check(self.lib.pantax_hip_strain_hap_stats(self.ctx, self.db, p(nnz), p(meanf)))
+        return nnz[: self.H], meanf[: self.H]
+
     def timing_enable(self, on=True):
         self._check(self.lib.pantax_hip_timing_enable(self.ctx, int(on)))
 
