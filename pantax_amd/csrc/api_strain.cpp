@@ -3,7 +3,7 @@
 // pantax_hip_pao_solve (X_opt signature, profile.rs:2690-2698).
 //
 // The whole strain step is enqueued on the ctx stream without waiting for the host: the two filter
-// decisions are taken by small device kernels (stage_lad.hip), row / pattern counts stay on the
+// decisions are taken by small device kernels (stage_hap_stats.hip, second_filter.hpp), row / pattern counts stay on the
 // device, and ONE download + synchronisation at the end brings back the raw per-haplotype and
 // per-species results.  The host then only redoes the reporting arithmetic (rounded fractions,
 // divergence, abundance constraint) on those values, using the decisions the device took.

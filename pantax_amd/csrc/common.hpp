@@ -257,7 +257,7 @@ struct LadBatch {
     bool rows_c0_valid = false;         // ... is there for the rows lad_prepare has just sorted
     bool masks_in_sort = false;         // the last lad_prepare formed the masks inside the row sort: d_mask holds nothing
     bool node_pass_fused = false;       // this step's lad_prepare also forms abundances, covered bases and the node statistics inside the row sort (node_rows_kernel):
-    double fused_min_depth = 0.0;       //   d_ab and the db's d_cov hold nothing; strain_enqueue decides (node_pass_fused_eligible) and hands over min_depth and the
+    double fused_min_depth = 0.0;       //   d_ab and the db's d_cov hold nothing; strain_enqueue decides (node_pass_fused_eligible, stage_lp_rows.hip: the row route) and hands over min_depth and the
     const uint8_t *fused_active = nullptr;   // species flags the coverage pass skipped by
     DevBuf<unsigned long long> d_ratio; // [H*2] at 2 * (hap_off[s] + k): sum cov, sum len of candidate k (exact integers)
     // species that can have more than 64 candidates (more than 64 haplotypes): LAD_WIDE_NW mask words per node in a side
@@ -350,7 +350,7 @@ struct Db {
     DevBuf<uint2> d_tiles;           // path tiles {hap, chunk} ordered (species, chunk, hap); one workgroup each
     uint64_t n_tiles = 0;
     DevBuf<uint2> d_emit_tile_sp;    // [ceil(V / 2048)] {species of the first node, of the last node} of every 2048-node tile of the row compaction
-    // node -> haplotypes (node_haps_build, stage_lad.hip; built once at upload): bit j of d_node_haps[v] = the walk of haplotype j of the
+    // node -> haplotypes (node_haps_build, stage_lp_rows.hip; built once at upload): bit j of d_node_haps[v] = the walk of haplotype j of the
     // node's species visits v; species of more than 64 haplotypes are left at zero (nh_walk_too: there are such species)
     DevBuf<uint64_t> d_node_haps;    // [V]
     bool nh_built = false, nh_walk_too = false;

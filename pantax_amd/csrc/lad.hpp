@@ -1,21 +1,36 @@
-// lad.hpp -- device-side pieces of the strain step (a9, a10, a12): per-hap trio statistics,
-// candidate-path masks + path_cov_ratio, LP row grouping and the batched exact LAD solver.
+// lad.hpp -- device-side pieces of the strain step (a9 - a13), one source file per stage: per-hap trio statistics and the first filter
+// (stage_hap_stats.hip), node statistics and a11 (stage_node_stats.hip), candidate-path masks + path_cov_ratio and the LP rows
+// (stage_lp_rows.hip), the batched exact LAD solver with the second filter (stage_lad.hip), the objectives (stage_objective.hip).
 #pragma once
 #include "common.hpp"
 
 namespace ptx {
 
 // a9: per-hap unique-trio statistics (zscore_filter profile.rs:1028-1051; :1114-1147)
-int hap_trio_stats_launch(Ctx *ctx, const Db *db, DevBuf<uint32_t> &d_ntrio_nz /*[H]*/, DevBuf<double> &d_mean /*[H]*/,
+int hap_trio_stats_launch(Ctx *ctx, Db *db, DevBuf<uint32_t> &d_ntrio_nz /*[H]*/, DevBuf<double> &d_mean /*[H]*/,
                           const uint8_t *d_active = nullptr /* device [S] or null: species the coverage pass skipped are not read */);
 // node abundance + per-species stats
-int node_stats_launch(Ctx *ctx, const Db *db, LadBatch *lb, int64_t min_depth, const uint8_t *d_active = nullptr);
+int node_stats_launch(Ctx *ctx, Db *db, LadBatch *lb, int64_t min_depth, const uint8_t *d_active = nullptr);
+// Which route the LP rows take: a pure function of the options and of the db's host-side tables (h_node_off, h_hap_off, the node -> haplotype state).
+// node_pass_fused_eligible (before the step's first kernel) and lad_prepare (later) both decide from it.
+struct RowRoute {
+    uint64_t max_vs;       // nodes of the largest species
+    uint32_t max_haps;     // haplotypes of the largest species
+    bool wide;             // some species has more than LAD_MAXP haplotypes
+    bool by_node;          // masks from the node -> haplotype words (mask_nodes_kernel), not from the path walk
+    bool use_nodes;        // the rows are sorted straight from the node arrays (sample_sort_nodes), no compaction
+    bool use_sample;       // the compacted rows fit the whole-batch sample sort (otherwise: radix)
+    bool ratio_by_node;    // the path_cov_ratio sums ride on the by-node mask pass
+    bool masks_in_sort;    // the masks are formed inside the node sort: no mask array, no pass of its own
+};
+RowRoute row_route(const Ctx *ctx, const Db *db);
+int row_pack_shift(const RowRoute &rt, uint32_t S, int pmax_bound);   // >= 0: two-word rows {species << shift | mask, a}; -1: three words
 // the resident step's fused node pass (node_rows_kernel in place of node_cov_stats_kernel + ssn_hist_kernel<true>): can THIS step take it?  Host-known only.
 bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg);
 // a11: species with more valid rows than sample_nodes keep the rows rand 0.9.2's choose_multiple(seed 42) would keep
 int row_sample_apply(Ctx *ctx, const Db *db, LadBatch *lb, int64_t sample_nodes);
 // a10: masks, ratios; then LP rows sorted and grouped into patterns
-int lad_prepare(Ctx *ctx, const Db *db, LadBatch *lb, bool cand_on_device, int pmax_bound);
+int lad_prepare(Ctx *ctx, Db *db, LadBatch *lb, bool cand_on_device, int pmax_bound);
 // a12: one workgroup per species (those with d_p[s] > 0 and need[s], when given); variables with fixed[s*64+k]
 // are pinned to 0.  Writes x, obj, status, iters for the solved species.  Nothing is read back.
 int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const uint8_t *d_need, const uint8_t *d_fixed, double *d_x,
@@ -23,6 +38,8 @@ int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const
 // the strain step's LP1 -> second filter -> LP2 (+ both objectives) as two launches
 struct FilterCfg;
 int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const FilterCfg &fc);
+// both objectives of the solved species (x2 / need2 null: one solution), from the sorted rows or from the nodes
+int objective_launch(Ctx *ctx, const Db *db, LadBatch *lb, const uint8_t *d_need2, const double *d_x1, const double *d_x2, double *d_obj1, double *d_obj2);
 // a9 / a13 decisions on the device (the host redoes only the reporting arithmetic at the end of the step)
 struct FilterCfg { double fr, fc, sr; int shift; };
 int first_filter_launch(Ctx *ctx, const Db *db, LadBatch *lb, const uint8_t *d_active, const FilterCfg &fc);

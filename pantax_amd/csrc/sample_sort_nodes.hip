@@ -98,7 +98,7 @@ struct Sn {
 };
 
 // mask == null: the membership mask of node v of segment (= species) s from its haplotype word -- bit k of the mask = some haplotype of
-// column k visits the node (what mask_nodes_kernel writes, stage_lad.hip); the plain loop, for the few nodes the samplers look at
+// column k visits the node (what mask_nodes_kernel writes, stage_lp_rows.hip); the plain loop, for the few nodes the samplers look at
 __device__ __forceinline__ uint64_t sn_node_mask(const Sn &sn, uint32_t s, uint64_t v) {
     if (sn.mask) return sn.mask[v];
     const int p = sn.hp.sp_p[s];
@@ -511,7 +511,7 @@ __global__ void __launch_bounds__(256) ssn_hist_kernel(Sn sn) {
 
 // The same pass for the resident step, FUSED with the node statistics (node_rows_kernel).  It has no abundance array and no covered-base counts to read:
 // it takes a node from `bases`, the bit vector, the full-node flags and the haplotype word to {covered bases, a, statistics, mask, column sums, bucket
-// id, staged row} in registers, which is node_cov_stats_kernel<false>'s work (stage_lad.hip) in front of this pass's own -- the 12 bytes a node that
+// id, staged row} in registers, which is node_cov_stats_kernel<false>'s work (stage_node_stats.hip) in front of this pass's own -- the 12 bytes a node that
 // kernel wrote and this one read back, and the second read of the lengths, are gone.
 // A kernel of its own, not a third instantiation of ssn_hist_kernel: one shared body changed the register allocation of ssn_hist_kernel<true>
 // (115 -> 127 VGPRs, node_pass=split 0.6 ms a step slower than the parent at cfg4), and the two-kernel path of the stage calls and fallbacks has to stay

@@ -1257,7 +1257,7 @@ __global__ void __launch_bounds__(256) popcount_kernel(uint64_t V, const uint64_
 // The same counts for graphs of LONG nodes (a single-genome species is a chain of 1024-bp chunks, build_eq1.rs:26-36: 32 words of the bit vector per
 // node): the per-thread loop above walks 64 different cache lines per iteration (11 ms at the reference-DB shape).  Here a wave takes 64 consecutive nodes,
 // reads the words of the whole stretch coalesced, keeps the number of set bits in front of every word in LDS (a DPP prefix sum per 64 words) and takes a
-// node's count as the difference of that prefix at its two ends -- node_cov_stats_kernel<.., LONGN>'s scheme (stage_lad.hip) for the stage call.
+// node's count as the difference of that prefix at its two ends -- node_cov_stats_kernel<.., LONGN>'s scheme (stage_node_stats.hip) for the stage call.
 constexpr uint32_t PCL_WORDS = 2304;   // words of one stretch the prefix holds; a longer stretch takes the per-lane loop
 __global__ void __launch_bounds__(256) popcount_long_kernel(uint64_t V, const uint64_t *__restrict__ bit_off, const uint32_t *__restrict__ full,
                                                             const uint32_t *__restrict__ bitmap, uint32_t *__restrict__ cov) {
