@@ -53,6 +53,9 @@ void pantax_hip_destroy(pantax_hip_ctx *ctx);
  * "gaf_piece_bytes", and the switches that force one of the in-tree HIP paths for tests and measurements (pantax_amd/csrc/common.hpp
  * CtxConfig lists them).  value NULL = the default.  PANTAX_HIP_E_INVALID for an unknown name or an unparsable value. */
 int pantax_hip_set_option(pantax_hip_ctx *ctx, const char *name, const char *value);
+/* Which LDS shape ("roomy" / "compact") the LAD solver takes under the ctx's option "lad_shape" for a batch of n_species LPs of at most max_columns
+ * columns on this ctx's device: the host rule the solver launches follow, for tests and logs.  NULL for a NULL ctx. */
+const char *pantax_hip_lad_shape_name(const pantax_hip_ctx *ctx, uint32_t n_species, int max_columns);
 const char *pantax_hip_last_error(const pantax_hip_ctx *ctx); /* ctx may be NULL: init errors */
 const char *pantax_hip_version(void);
 

@@ -14,7 +14,7 @@ _lib = None
 
 # every symbol include/pantax_hip.h declares
 SYMBOLS = [
-    "pantax_hip_init", "pantax_hip_destroy", "pantax_hip_last_error", "pantax_hip_version", "pantax_hip_set_option",
+    "pantax_hip_init", "pantax_hip_destroy", "pantax_hip_last_error", "pantax_hip_version", "pantax_hip_set_option", "pantax_hip_lad_shape_name",
     "pantax_hip_db_upload", "pantax_hip_db_upload_parts", "pantax_hip_db_free", "pantax_hip_reads_upload", "pantax_hip_reads_free",
     "pantax_hip_bin_reads", "pantax_hip_species_profile", "pantax_hip_db_reset", "pantax_hip_abundance_filter",
     "pantax_hip_trio_index", "pantax_hip_trio_get", "pantax_hip_node_coverage",
@@ -122,6 +122,8 @@ def load():
         _lib.pantax_hip_last_error.restype = C.c_char_p
         _lib.pantax_hip_last_error.argtypes = [C.c_void_p]
         _lib.pantax_hip_version.restype = C.c_char_p
+        _lib.pantax_hip_lad_shape_name.restype = C.c_char_p
+        _lib.pantax_hip_lad_shape_name.argtypes = [C.c_void_p, C.c_uint32, C.c_int]
         _lib.pantax_hip_destroy.restype = None
         _lib.pantax_hip_db_free.restype = None
         _lib.pantax_hip_reads_free.restype = None

@@ -165,6 +165,8 @@ struct CtxConfig {
     std::string bin_route;           // "walk": the binning pass of resident reads finds a walk's smallest and largest id by reading the walk (bin_slots_kernel) where it would take
                                      // them from the record filed at upload (bin_mm_kernel; "minmax" or empty) (tests compare, measurements)
     std::string node_pass;           // "split": the resident step keeps node_cov_stats_kernel + ssn_hist_kernel where it would take the fused node_rows_kernel (tests compare, measurements)
+    std::string lad_shape;           // LDS shape of the <= 16-column LAD solver: "" / "auto": compact when the batch has more species than the device has CUs, else roomy
+                                     // (lad_shape(), lad.hpp); "roomy" / "compact": that shape for every such launch (tests compare, measurements)
     bool no_absent_skip = false;     // the statistics / histogram passes of the step read the species the species level dropped like the others (tests compare, measurements)
     bool ssn_debug = false, scan_no_huge = false, flag_rank_chained = false, ratio_kernel = false, mask_pass = false, trio_free_at_filter = false,
          trio_after_step = false;

@@ -20,6 +20,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include "common.hpp"
+#include "lad.hpp"
 
 namespace ptx {
 
@@ -100,7 +101,7 @@ const OptDesc OPTIONS[] = {
     OPT("cov_general", O_BOOL, cov_general), OPT("cov_long", O_STR, cov_long), OPT("covl_shape", O_INT, covl_shape), OPT("cov_count", O_BOOL, cov_count), OPT("cov_self_clean", O_BOOL, cov_self_clean), OPT("cov_clean_async", O_INT, cov_clean_async), OPT("cov_arena_verify", O_BOOL, cov_arena_verify), OPT("ncs_no_prefix", O_BOOL, ncs_no_prefix), OPT("ncs_prefix_min", O_INT, ncs_prefix_min), OPT("walk_sum_in_bin", O_BOOL, walk_sum_in_bin), OPT("cov_item_groups", O_INT, cov_item_groups), OPT("tv_u", O_INT, tv_u), OPT("tv_rounds", O_INT, tv_rounds), OPT("tf_u", O_INT, tf_u), OPT("tf_rounds", O_INT, tf_rounds),
     OPT("rows_u", O_INT, rows_u), OPT("tb_slots", O_INT, tb_slots), OPT("trio_xcd", O_INT, trio_xcd), OPT("cov_shape", O_INT, cov_shape),
     OPT("covf_shape", O_INT, covf_shape), OPT("cov_xcd", O_INT, cov_xcd), OPT("group_bucket_bits", O_INT, group_bucket_bits), OPT("tv_ablate", O_U32, tv_ablate),
-    OPT("cov_ablate", O_U32, cov_ablate), OPT("ssn_ablate", O_U32, ssn_ablate), OPT("no_absent_skip", O_BOOL, no_absent_skip), OPT("node_pass", O_STR, node_pass), OPT("bin_route", O_STR, bin_route), OPT("ssn_debug", O_BOOL, ssn_debug),
+    OPT("cov_ablate", O_U32, cov_ablate), OPT("ssn_ablate", O_U32, ssn_ablate), OPT("no_absent_skip", O_BOOL, no_absent_skip), OPT("node_pass", O_STR, node_pass), OPT("bin_route", O_STR, bin_route), OPT("lad_shape", O_STR, lad_shape), OPT("ssn_debug", O_BOOL, ssn_debug),
     OPT("scan_no_huge", O_BOOL, scan_no_huge), OPT("flag_rank_chained", O_BOOL, flag_rank_chained), OPT("ratio_kernel", O_BOOL, ratio_kernel),
     OPT("mask_pass", O_BOOL, mask_pass), OPT("trio_free_at_filter", O_BOOL, trio_free_at_filter), OPT("trio_after_step", O_BOOL, trio_after_step),
 };
@@ -152,6 +153,11 @@ int pantax_hip_set_option(pantax_hip_ctx *ctx, const char *name, const char *val
     const int rc = ctx_set_option(ctx->cfg, name, value);
     if (rc == 0 && std::strcmp(name, "dev_cache_gb") == 0) dev_cache_set_max(ctx->cfg.dev_cache_gb < 0 ? -1 : (long long)ctx->cfg.dev_cache_gb << 30);
     return rc == 0 ? 0 : fail(ctx, rc, "set_option: unknown option or unparsable value: %s=%s", name, value ? value : "(default)");
+}
+
+const char *pantax_hip_lad_shape_name(const pantax_hip_ctx *ctx, uint32_t n_species, int max_columns) {
+    if (!ctx) return nullptr;
+    return lad_shape_name(lad_shape(ctx->cfg.lad_shape, n_species, ctx->n_cu, max_columns));
 }
 
 const char *pantax_hip_last_error(const pantax_hip_ctx *ctx) {

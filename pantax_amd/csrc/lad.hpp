@@ -27,6 +27,14 @@ RowRoute row_route(const Ctx *ctx, const Db *db);
 int row_pack_shift(const RowRoute &rt, uint32_t S, int pmax_bound);   // >= 0: two-word rows {species << shift | mask, a}; -1: three words
 // the resident step's fused node pass (node_rows_kernel in place of node_cov_stats_kernel + ssn_hist_kernel<true>): can THIS step take it?  Host-known only.
 bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg);
+// Which LDS shape the <= 16-column LAD solver launches with (stage_lad.hip: LadRoomy / LadCompact): a pure function of the option lad_shape ("" / "auto",
+// "roomy", "compact"), the number of solver workgroups of the launch (one per species), the device's CU count and the launch's column bound.
+//   auto: compact when the batch has more workgroups than the device has CUs -- they would queue for a CU one at a time under the roomy shape, while four
+//   compact ones share it; roomy otherwise (a single or a few large LPs: residency buys nothing, the finer row index does).  More than 16 columns: always
+//   roomy (the 17..64-column and the wide instances have one shape).  The results are the same bits under either shape.
+enum class LadShape { roomy, compact };
+LadShape lad_shape(const std::string &option, uint32_t n_workgroups, int n_cu, int pmax_bound);
+const char *lad_shape_name(LadShape s);
 // a11: species with more valid rows than sample_nodes keep the rows rand 0.9.2's choose_multiple(seed 42) would keep
 int row_sample_apply(Ctx *ctx, const Db *db, LadBatch *lb, int64_t sample_nodes);
 // a10: masks, ratios; then LP rows sorted and grouped into patterns

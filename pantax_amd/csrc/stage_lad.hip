@@ -109,7 +109,20 @@ __device__ __forceinline__ uint32_t ub_(bool coop, const RowIdx &r, uint32_t lo,
 // ---------------------------------------------------------------------------------------------
 constexpr int LAD_BLOCK = 256;
 constexpr int LAD_KWIDE = 16;    // patterns up to which a wave searches cooperatively / the line search runs wide rounds
-constexpr int LAD_KLDS = 256;    // patterns whose solver state fits the LDS arrays (72 B each); more go through global scratch
+constexpr int LAD_KLDS = 256;    // patterns whose solver state fits the roomy LDS arrays (72 B each); more go through global scratch
+
+// The LDS "shape" of a solver workgroup of the <= 16-column instance: how many samples the row index keeps (IDX_N), how many candidate
+// rows of a line search are cached (CACHE_N) and how many patterns keep their state in LDS (KLDS; a species with more takes the
+// global-scratch body).  The tables only speed one species' searches: the searches are exact at any index stride, the cache is a copy,
+// and the line search ends in the same exact weighted median with or without the wide rounds -- x, status and iterations are the
+// same bits under every shape.  What the shape decides is how many workgroups a CU holds (160 KiB of LDS):
+//   roomy   87 912 B, 142 VGPRs -> one workgroup a CU: a few large LPs, where nothing waits for a CU and the finer index pays
+//   compact 39 016 B, 120 VGPRs -> four a CU: more species than CUs, where co-resident workgroups hide each other's barriers and searches
+// WAVES is the kernel's waves-per-SIMD hint: without it the compact instance takes 130 VGPRs and three workgroups fit (cfg4, 1 000 species:
+// lad_pair_kernel 1.27 ms roomy, 1.06 compact without the hint, 0.76 with it).
+// lad_shape() (stage_lp_rows.hip) chooses on the host before the launch.  The 17..64-column and the wide instances have one shape.
+struct LadRoomy { static constexpr uint32_t IDX_N = 4096, CACHE_N = 2048; static constexpr int KLDS = LAD_KLDS, WAVES = 1; };
+struct LadCompact { static constexpr uint32_t IDX_N = 1024, CACHE_N = 1024; static constexpr int KLDS = 32, WAVES = 4; };
 enum { C_LB = 0, C_UB = 1, C_PAT = 2, C_FIXED = 3 };
 
 // -DLAD_PROFILE (tools/lad_phase_probe.sh builds such a library beside the product): thread 0 of every solver workgroup adds
@@ -211,24 +224,26 @@ __device__ __forceinline__ void crossed_range(bool COOP, const RowIdx &a, double
     }
 #define PAT_LOOP(k) for (uint32_t k = k0 + (COOP ? (uint32_t)(tid >> 6) : (uint32_t)tid); k < k1; k += (COOP ? LAD_BLOCK / 64 : LAD_BLOCK))
 // LDS of one solver workgroup
-template <int PS, int NW>
+template <int PS, int NW, class SH = LadRoomy>
 struct LadLds {
-    static constexpr uint32_t IDX_N = PS <= 16 ? 4096 : 2048;     // samples of the row index (the 64-column instance spends its LDS on W and G)
+    static_assert(PS <= 16 || SH::KLDS == LAD_KLDS, "only the 16-column instance has more than one shape");
+    static constexpr int KLDS = SH::KLDS;
+    static constexpr uint32_t IDX_N = PS <= 16 ? SH::IDX_N : 2048;     // samples of the row index (the 64-column instance spends its LDS on W and G)
     // cached candidate rows of a line search.  The 64-column instance has no LDS to spare, but its elimination scratch G is idle
     // between two basis updates: the cache of a line search lives there (8192 rows instead of 512: with a hundred patterns the
     // sample-only rounds leave a few thousand candidates, and the exact rounds then run in LDS instead of in memory)
     static constexpr bool CACHE_IN_G = NW == 1 && PS > 16;
-    static constexpr uint32_t CACHE_N = PS <= 16 ? 2048 : CACHE_IN_G ? PS * 2 * PS : 512;
+    static constexpr uint32_t CACHE_N = PS <= 16 ? SH::CACHE_N : CACHE_IN_G ? PS * 2 * PS : 512;
     LadShared<PS> sh;
     double W[NW == 1 ? PS * PS : 1];          // wide species: W and G in global scratch (LadArgs::wide_W / wide_G)
     double G[NW == 1 ? PS * 2 * PS : 1];
-    // per-pattern solver state (species with at most LAD_KLDS patterns, the usual case; else the global scratch arrays)
-    double L_s[LAD_KLDS], L_rho[LAD_KLDS], L_eps[LAD_KLDS];
-    uint64_t L_mask[LAD_KLDS];
-    uint32_t L_lo[LAD_KLDS], L_up[LAD_KLDS], L_lslo[LAD_KLDS], L_lshi[LAD_KLDS], L_lsmid[LAD_KLDS], L_start[LAD_KLDS + 1];
+    // per-pattern solver state (species with at most KLDS patterns, the usual case; else the global scratch arrays)
+    double L_s[KLDS], L_rho[KLDS], L_eps[KLDS];
+    uint64_t L_mask[KLDS];
+    uint32_t L_lo[KLDS], L_up[KLDS], L_lslo[KLDS], L_lshi[KLDS], L_lsmid[KLDS], L_start[KLDS + 1];
     double L_idx[IDX_N];      // top level of every row search: every (1 << shift)-th row of the species' sorted rows
     double L_cache[CACHE_IN_G ? 1 : CACHE_N];
-    uint32_t L_lsmid2[LAD_KLDS], L_coff[LAD_KLDS + 1], L_cn[LAD_KLDS], L_crow0[LAD_KLDS];
+    uint32_t L_lsmid2[KLDS], L_coff[KLDS + 1], L_cn[KLDS], L_crow0[KLDS];
     // wide rounds of the line search (species with at most LAD_KWIDE patterns): crossed-count bounds of every
     // pattern at 64 pivots, and the per-wave slope contributions at those pivots
     uint32_t W_cmin[LAD_KWIDE][64], W_cmax[LAD_KWIDE][64];
@@ -237,10 +252,10 @@ struct LadLds {
 
 // USEL is a compile-time constant so that every access to the pattern state is a plain LDS (or plain global)
 // instruction; a run-time choice between the two would turn them all into flat accesses.
-template <int PS, bool USEL, int NW>
-__device__ __forceinline__ void lad_solve_body(const LadArgs &A, LadLds<PS, NW> &m, const int s, const int p, const uint32_t k0, const uint32_t k1) {
+template <int PS, bool USEL, int NW, class SH>
+__device__ __forceinline__ void lad_solve_body(const LadArgs &A, LadLds<PS, NW, SH> &m, const int s, const int p, const uint32_t k0, const uint32_t k1) {
     static_assert(NW == 1 || !USEL, "wide species keep their pattern state in global scratch");
-    constexpr uint32_t IDX_N = LadLds<PS, NW>::IDX_N, CACHE_N = LadLds<PS, NW>::CACHE_N;
+    constexpr uint32_t IDX_N = LadLds<PS, NW, SH>::IDX_N, CACHE_N = LadLds<PS, NW, SH>::CACHE_N;
     // NW == 0 ("huge", more than LAD_WIDEP haplotypes): the number of mask words and with it the row length of W / G are
     // run-time values, and everything that is sized by the columns lives in global scratch -- any number of columns
     constexpr bool HUGE = NW == 0;
@@ -277,7 +292,7 @@ __device__ __forceinline__ void lad_solve_body(const LadArgs &A, LadLds<PS, NW> 
     };
     const uint64_t c0 = A.col_off[s];
     double *L_s = m.L_s, *L_rho = m.L_rho, *L_eps = m.L_eps, *L_idx = m.L_idx, *L_cache;
-    if constexpr (LadLds<PS, NW>::CACHE_IN_G) L_cache = m.G; else L_cache = m.L_cache;
+    if constexpr (LadLds<PS, NW, SH>::CACHE_IN_G) L_cache = m.G; else L_cache = m.L_cache;
     uint64_t *L_mask = m.L_mask;
     uint32_t *L_lo = m.L_lo, *L_up = m.L_up, *L_lslo = m.L_lslo, *L_lshi = m.L_lshi, *L_lsmid = m.L_lsmid, *L_start = m.L_start,
              *L_lsmid2 = m.L_lsmid2, *L_coff = m.L_coff, *L_cn = m.L_cn, *L_crow0 = m.L_crow0;
@@ -999,9 +1014,9 @@ __device__ __forceinline__ bool lad_instance_takes(const LadArgs &A, int s, int 
     if (p <= LAD_MAXP) return false;
     return (NW == 0) == (A.wide_nw[s] > (uint32_t)LAD_WIDE_NW);
 }
-template <int PS, int NW>
-__global__ void __launch_bounds__(LAD_BLOCK) lad_solve_kernel(LadArgs A) {
-    __shared__ LadLds<PS, NW> m;
+template <int PS, int NW, class SH = LadRoomy>
+__global__ void __launch_bounds__(LAD_BLOCK) __attribute__((amdgpu_waves_per_eu(SH::WAVES))) lad_solve_kernel(LadArgs A) {
+    __shared__ LadLds<PS, NW, SH> m;
     const int s = NW == 1 ? (int)blockIdx.x : (int)A.wide_list[blockIdx.x];
     const int p = A.sp_p[s];
     if (!lad_instance_takes<NW>(A, s, p)) return;
@@ -1009,36 +1024,45 @@ __global__ void __launch_bounds__(LAD_BLOCK) lad_solve_kernel(LadArgs A) {
     if (p <= 0) { if (threadIdx.x == 0) { A.status[s] = 0; A.iters[s] = 0; } return; }
     const uint32_t k0 = A.sp_pat_off[s], k1 = A.sp_pat_off[s + 1];
     if constexpr (NW == 1) {
-        if (k1 - k0 <= (uint32_t)LAD_KLDS) lad_solve_body<PS, true, 1>(A, m, s, p, k0, k1);
-        else lad_solve_body<PS, false, 1>(A, m, s, p, k0, k1);
-    } else lad_solve_body<PS, false, NW>(A, m, s, p, k0, k1);
+        if (k1 - k0 <= (uint32_t)SH::KLDS) lad_solve_body<PS, true, 1, SH>(A, m, s, p, k0, k1);
+        else lad_solve_body<PS, false, 1, SH>(A, m, s, p, k0, k1);
+    } else lad_solve_body<PS, false, NW, SH>(A, m, s, p, k0, k1);
 }
 
 // Both LP solves of the strain step in ONE launch: solve, take the second-filter decision of this species
 // (one thread), and solve again with the dropped columns pinned to zero -- only where a column was dropped;
 // elsewhere LP2 == LP1 (m.reset() + no new constraint, profile.rs:1482-1490).
-template <int PS, int NW>
-__global__ void __launch_bounds__(LAD_BLOCK) lad_pair_kernel(LadArgs A1, LadArgs A2, SecondFilterArgs F) {
-    __shared__ LadLds<PS, NW> m;
+template <int PS, int NW, class SH = LadRoomy>
+__global__ void __launch_bounds__(LAD_BLOCK) __attribute__((amdgpu_waves_per_eu(SH::WAVES))) lad_pair_kernel(LadArgs A1, LadArgs A2, SecondFilterArgs F) {
+    __shared__ LadLds<PS, NW, SH> m;
     const int s = NW == 1 ? (int)blockIdx.x : (int)A1.wide_list[blockIdx.x];
     const int p = A1.sp_p[s];
     if (!lad_instance_takes<NW>(A1, s, p)) return;
     const uint32_t k0 = A1.sp_pat_off[s], k1 = A1.sp_pat_off[s + 1];
-    const bool lds_state = NW == 1 && k1 - k0 <= (uint32_t)LAD_KLDS;
+    const bool lds_state = NW == 1 && k1 - k0 <= (uint32_t)SH::KLDS;
     if (p > 0) {
         if constexpr (NW == 1) {
-            if (lds_state) lad_solve_body<PS, true, 1>(A1, m, s, p, k0, k1);
-            else lad_solve_body<PS, false, 1>(A1, m, s, p, k0, k1);
-        } else lad_solve_body<PS, false, NW>(A1, m, s, p, k0, k1);
+            if (lds_state) lad_solve_body<PS, true, 1, SH>(A1, m, s, p, k0, k1);
+            else lad_solve_body<PS, false, 1, SH>(A1, m, s, p, k0, k1);
+        } else lad_solve_body<PS, false, NW, SH>(A1, m, s, p, k0, k1);
     } else if (threadIdx.x == 0) { A1.status[s] = 0; A1.iters[s] = 0; }
     __syncthreads();   // x1 / status1 of this species are visible to the workgroup
     if (threadIdx.x == 0) second_filter_species(F, (uint32_t)s);
     __syncthreads();
     if (p <= 0 || !F.need2[s]) return;
     if constexpr (NW == 1) {
-        if (lds_state) lad_solve_body<PS, true, 1>(A2, m, s, p, k0, k1);
-        else lad_solve_body<PS, false, 1>(A2, m, s, p, k0, k1);
-    } else lad_solve_body<PS, false, NW>(A2, m, s, p, k0, k1);
+        if (lds_state) lad_solve_body<PS, true, 1, SH>(A2, m, s, p, k0, k1);
+        else lad_solve_body<PS, false, 1, SH>(A2, m, s, p, k0, k1);
+    } else lad_solve_body<PS, false, NW, SH>(A2, m, s, p, k0, k1);
+}
+
+// the shape of this launch (lad_shape), or PANTAX_HIP_E_INVALID for an option value that names none
+static int lad_shape_checked(Ctx *ctx, uint32_t S, int pmax_bound, LadShape *out) {
+    const std::string &opt = ctx->cfg.lad_shape;
+    if (!opt.empty() && opt != "auto" && opt != "roomy" && opt != "compact")
+        return fail(ctx, PANTAX_HIP_E_INVALID, "lad solver: option lad_shape is \"auto\", \"roomy\" or \"compact\", not \"%s\"", opt.c_str());
+    *out = lad_shape(opt, S, ctx->n_cu, pmax_bound);
+    return 0;
 }
 
 static SecondFilterArgs second_filter_args(const Db *db, LadBatch *lb, const FilterCfg &fc, const double *d_x1, const int32_t *d_status1,
@@ -1096,6 +1120,8 @@ static int lad_prof_end(Ctx *ctx, uint32_t S, DevBuf<unsigned long long> &buf, c
 // the strain step's two solves + second filter + both objectives: two launches
 int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const FilterCfg &fc) {
     const uint32_t S = db->S;
+    LadShape shape;
+    PTX_TRY(lad_shape_checked(ctx, S, pmax_bound, &shape));
     LadArgs A1 = lad_args(db, lb, nullptr, nullptr, lb->d_x.p, lb->d_status.p, lb->d_iters.p);
     LadArgs A2 = lad_args(db, lb, nullptr, lb->d_fixed2.p, lb->d_x2.p, lb->d_status2.p, lb->d_iters2.p);
     SecondFilterArgs F = second_filter_args(db, lb, fc, lb->d_x.p, lb->d_status.p, lb->d_fixed2.p, lb->d_need2.p);
@@ -1105,7 +1131,8 @@ int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const 
 #endif
     {
         KTimer t(ctx, "lad_pair_kernel");
-        if (pmax_bound <= 16) hipLaunchKernelGGL((lad_pair_kernel<16, 1>), dim3(S), dim3(LAD_BLOCK), 0, ctx->stream, A1, A2, F);
+        if (shape == LadShape::compact) hipLaunchKernelGGL((lad_pair_kernel<16, 1, LadCompact>), dim3(S), dim3(LAD_BLOCK), 0, ctx->stream, A1, A2, F);
+        else if (pmax_bound <= 16) hipLaunchKernelGGL((lad_pair_kernel<16, 1>), dim3(S), dim3(LAD_BLOCK), 0, ctx->stream, A1, A2, F);
         else hipLaunchKernelGGL((lad_pair_kernel<LAD_MAXP, 1>), dim3(S), dim3(LAD_BLOCK), 0, ctx->stream, A1, A2, F);
         if (lb->n_wide > lb->n_huge) hipLaunchKernelGGL((lad_pair_kernel<LAD_WIDEP, LAD_WIDE_NW>), dim3(lb->n_wide), dim3(LAD_BLOCK), 0, ctx->stream, A1, A2, F);
         if (lb->n_huge) hipLaunchKernelGGL((lad_pair_kernel<1, 0>), dim3(lb->n_wide), dim3(LAD_BLOCK), 0, ctx->stream, A1, A2, F);
@@ -1120,6 +1147,8 @@ int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const 
 int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const uint8_t *d_need, const uint8_t *d_fixed, double *d_x,
                      double *d_obj, int32_t *d_status, int32_t *d_iters) {
     const uint32_t S = db->S;
+    LadShape shape;
+    PTX_TRY(lad_shape_checked(ctx, S, pmax_bound, &shape));
     LadArgs A = lad_args(db, lb, d_need, d_fixed, d_x, d_status, d_iters);
 #ifdef LAD_PROFILE
     DevBuf<unsigned long long> prof;
@@ -1127,7 +1156,8 @@ int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const
 #endif
     {
         KTimer t(ctx, "lad_solve_kernel");
-        if (pmax_bound <= 16) hipLaunchKernelGGL((lad_solve_kernel<16, 1>), dim3(S), dim3(LAD_BLOCK), 0, ctx->stream, A);
+        if (shape == LadShape::compact) hipLaunchKernelGGL((lad_solve_kernel<16, 1, LadCompact>), dim3(S), dim3(LAD_BLOCK), 0, ctx->stream, A);
+        else if (pmax_bound <= 16) hipLaunchKernelGGL((lad_solve_kernel<16, 1>), dim3(S), dim3(LAD_BLOCK), 0, ctx->stream, A);
         else hipLaunchKernelGGL((lad_solve_kernel<LAD_MAXP, 1>), dim3(S), dim3(LAD_BLOCK), 0, ctx->stream, A);
         if (lb->n_wide > lb->n_huge) hipLaunchKernelGGL((lad_solve_kernel<LAD_WIDEP, LAD_WIDE_NW>), dim3(lb->n_wide), dim3(LAD_BLOCK), 0, ctx->stream, A);
         if (lb->n_huge) hipLaunchKernelGGL((lad_solve_kernel<1, 0>), dim3(lb->n_wide), dim3(LAD_BLOCK), 0, ctx->stream, A);

@@ -537,6 +537,14 @@ int row_pack_shift(const RowRoute &rt, uint32_t S, int pmax_bound) {
     return (!rt.use_sample && sp_bits + pmax_bound <= 64 && !(rt.use_nodes && pmax_bound >= 64)) ? pmax_bound : -1;
 }
 
+// Which LDS shape the LAD solver launches with (lad.hpp).  Host-known before the launch; nothing is launched or allocated.
+LadShape lad_shape(const std::string &option, uint32_t n_workgroups, int n_cu, int pmax_bound) {
+    if (pmax_bound > 16 || option == "roomy") return LadShape::roomy;
+    if (option == "compact") return LadShape::compact;
+    return n_workgroups > (uint32_t)std::max(n_cu, 0) ? LadShape::compact : LadShape::roomy;
+}
+const char *lad_shape_name(LadShape s) { return s == LadShape::compact ? "compact" : "roomy"; }
+
 // The fused node pass serves the resident step (the coverage pass left its counts: cov_count_pending) whose masks are formed in the sort, without a11 (it
 // needs nvalid on the host and edits the abundances in front of the sort), without the self-cleaning readers, and not the long-node variant of the
 // statistics kernel (the reference-DB shape: its per-stretch prefix in LDS does not fit beside the histogram pass's tree and tables -- it stays on the

@@ -75,6 +75,11 @@ class Engine:
         environment only once, at init."""
         self._check(self.lib.pantax_hip_set_option(self.ctx, name.encode(), None if value is None else str(value).encode()))
 
+    def lad_shape_name(self, n_species, max_columns):
+        """pantax_hip_lad_shape_name: "roomy" or "compact", the LDS shape the LAD solver takes for a batch of n_species LPs of at most max_columns columns
+        under this ctx's option lad_shape."""
+        return self.lib.pantax_hip_lad_shape_name(self.ctx, int(n_species), int(max_columns)).decode()
+
     # ------------------------------------------------------------------ uploads
     def upload_db(self, species):
         """species: list of objects with node_len, path_off, path_nodes, range_start, range_end
