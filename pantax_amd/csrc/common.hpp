@@ -146,7 +146,7 @@ struct CtxConfig {
     std::string read_strain_route;   // "walk": the per-read strain masks of every species from its candidates' walks (stage_read_strain.hip), not from the node -> haplotype words
     bool cov_general = false;        // every group through the kernel of the longer walks (coverage_fast_kernel<.., LONG>; cov_long=step: coverage_step_kernel)
     std::string cov_long;            // "step": round 5's coverage_step_kernel for the groups that hold steps of walks of more than 64 steps
-    int covl_shape = -1;             // shape of the long-walk kernel: <U><groups per workgroup / 8><window / 1024><back / 256> (default 2234)
+    int covl_shape = -1;             // shape of the long-walk kernel: <U><groups per workgroup / 8><window / 1024><back / 256> (default 2834)
     bool cov_count = false;          // resident step: popcount_kernel as in the stage call
     int cov_clean_async = -1;        // resident step: the coverage arena's zero fill goes onto the side stream, beside the LPs (1; -1: arenas of 1 GiB and more); 0: in front of the coverage pass
     bool cov_self_clean = false;     // resident step: the last readers of the coverage arena zero it instead of a zero fill in front of every coverage pass.  OFF: measured
@@ -659,7 +659,10 @@ int coverage_arena_clean_async(Ctx *ctx, Db *db);   // resident step: the arena'
 int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio);   // optional, ahead of coverage_launch (needs the binning and db->U only)
 // defer_count: leave node_base_cov (popcount_kernel) to the node statistics pass that follows in the resident step (db->cov_count_pending)
 int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool with_trio, bool defer_count = false);
-// the locus-grouped copy of reads that were tokenised / uploaded as plain columns (round 6: the file seam bins the plain columns for the species
+// stage_cov_step.hip: round 5's kernel for the groups of longer walks (option cov_long=step), in the shape the pass's plan names (cov_plan.hpp)
+struct CovPlan;
+int coverage_step_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool trio, const CovPlan &plan);
+// stage_read_layout.hip: the locus-grouped copy of reads that were tokenised / uploaded as plain columns (round 6: the file seam bins the plain columns for the species
 // decision and builds the copy while the first graphs travel); no-op on grouped reads
 int reads_group(Ctx *ctx, Reads *rd);
 int trio_index_build(Ctx *ctx, Db *db, bool with_keys = true);

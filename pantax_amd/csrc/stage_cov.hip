@@ -35,137 +35,18 @@
 // Layout: node arrays of all resident species are concatenated; a node's coverage bitmap starts
 // at bit bit_off[v] of one global bit vector (1 bit per graph base instead of the reference's
 // 1 byte, profile.rs:776-781).
-#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include "common.hpp"
 #include "primitives.hpp"
 #include "wave.hpp"
+#include "cov_plan.hpp"
+#include "cov_device.hpp"
 // bools are combined with & and | on purpose in the coverage kernels (no short-circuit control flow: every operand is a plain comparison or a vote)
 #pragma clang diagnostic ignored "-Wbitwise-instead-of-logical"
 
 namespace ptx {
-
-constexpr int COV_BLOCK = 256;
-
-// The test-before-set must see other CUs' ORs to be worth anything: the ORs execute below the
-// per-CU L1 (which is never refreshed by them), so the probe is an agent-scope load (sc1: L1
-// bypass, served by L2).  A stale 0 only costs a redundant OR; bits never clear, so it is safe.
-__device__ __forceinline__ uint32_t bm_peek(const uint32_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// Bits [g0,g1) of the coverage bit vector are marked through the workgroup's LDS bit window (words
-// [bw0, bw0 + COV_BWIN) of the global vector); words outside the window take the global test-then-OR path.  The window is ORed into memory once per workgroup.
-constexpr uint32_t COV_BWIN = 2048;   // 32-bit words: 64 kbit of graph bases
-constexpr int COV_WIN = 2048;         // nodes in the LDS window of `bases` (a multiple of 64 nodes from a multiple of 64: the full-node flags flush as ballots);
-                                      // 2048 steps of 1e7 reads over 3.2e7 nodes span ~1000 nodes: 1024 overflowed on most chunks
-// the LDS windows of the coverage kernel live at file scope: helpers that received them as (generic) pointer arguments
-// made this compiler emit an illegal null check of the shared-memory aperture
-// One dynamic LDS block per workgroup: [WIN u32 `bases` window][COV_BWIN u32 bit window][WIN u8 full-node flags: a step covered the
-// whole node, its bits are not marked one by one (popcount_kernel takes the length)].  WIN is a launch parameter of the
-// short-read kernel (a multiple of 256 nodes) and COV_WIN in the general one; helpers address the block by offsets.
-extern __shared__ uint32_t s_cov[];
-#define S_WIN(i) s_cov[(i)]
-#define S_BM(bmo, i) s_cov[(bmo) + (i)]
-#define S_FULL(bmo, i) reinterpret_cast<uint8_t *>(s_cov + (bmo) + COV_BWIN)[(i)]
-__host__ __device__ constexpr size_t cov_lds_bytes(int win) { return (size_t)win * 4 + COV_BWIN * 4 + (size_t)win; }
-__device__ __forceinline__ void lds_or(uint32_t *__restrict__ bm, uint32_t bmo, uint64_t bw0, uint32_t bwn, uint64_t w, uint32_t m) {
-    const uint64_t off = w - bw0;     // unsigned wrap: words below the window are out of range too
-    if (off < bwn) {
-        if ((S_BM(bmo, off) & m) != m) atomicOr(&S_BM(bmo, off), m);
-    } else if ((bm_peek(&bm[w]) & m) != m) atomicOr(&bm[w], m);
-}
-__device__ __forceinline__ void mark_range(uint32_t *__restrict__ bm, uint32_t bmo, uint64_t bw0, uint32_t bwn, uint64_t g0, uint64_t g1) {
-    if (g1 <= g0) return;
-    uint64_t w0 = g0 >> 5, w1 = (g1 - 1) >> 5;
-    uint32_t m0 = 0xFFFFFFFFu << (g0 & 31);
-    uint32_t m1 = 0xFFFFFFFFu >> (31 - (uint32_t)((g1 - 1) & 31));
-    if (w0 == w1) lds_or(bm, bmo, bw0, bwn, w0, m0 & m1);
-    else {
-        lds_or(bm, bmo, bw0, bwn, w0, m0);
-        for (uint64_t w = w0 + 1; w < w1; ++w) lds_or(bm, bmo, bw0, bwn, w, 0xFFFFFFFFu);
-        lds_or(bm, bmo, bw0, bwn, w1, m1);
-    }
-}
-// the same for a range that lies inside the LDS bit window: 32-bit positions relative to the window, LDS only
-__device__ __forceinline__ void win_or(uint32_t bmo, uint32_t w, uint32_t m) { if ((S_BM(bmo, w) & m) != m) atomicOr(&S_BM(bmo, w), m); }
-__device__ __forceinline__ void mark_window(uint32_t bmo, uint32_t r0, uint32_t r1) {
-    if (r1 <= r0) return;
-    const uint32_t w0 = r0 >> 5, w1 = (r1 - 1) >> 5;
-    const uint32_t m0 = 0xFFFFFFFFu << (r0 & 31), m1 = 0xFFFFFFFFu >> (31 - ((r1 - 1) & 31));
-    if (w0 == w1) win_or(bmo, w0, m0 & m1);
-    else {
-        win_or(bmo, w0, m0);
-        for (uint32_t w = w0 + 1; w < w1; ++w) win_or(bmo, w, 0xFFFFFFFFu);
-        win_or(bmo, w1, m1);
-    }
-}
-
-// Step codes (g_step_dup): walks of <= 64 steps carry the distance back to the first occurrence of the step's node in
-// the walk (0 = none); longer walks carry STEP_LONG | (1 if the node occurred earlier in the walk).  Where the first
-// occurrence sits matters only through "is it step 0" (profile.rs:853-856 vs :860-862), i.e. id == id of step 0.
-constexpr uint32_t STEP_LONG = 0x80u;
-// ... and, both kinds, STEP_START on the first step of a walk; pad steps carry STEP_PAD.  The slots of the grouped copy follow
-// the stream (build_step_read lays the walks out in slot order), so a step's slot is not stored per step: group_slot[g] names
-// the read that owns the first step of the 64-step group g, and every later walk start in the group advances it by one.
-constexpr uint32_t STEP_START = 0x40u, STEP_PAD = 0xFFu, STEP_DIST = 0x3Fu;
-// ballots / votes of a bool WITHOUT the detour through an int predicate (__ballot(int) costs a v_cndmask + v_cmp per call: the kernel is bound by VALU issue)
-__device__ __forceinline__ unsigned long long ballot1(bool b) { return __builtin_amdgcn_ballot_w64(b); }
-__device__ __forceinline__ bool any1(bool b) { return __builtin_amdgcn_ballot_w64(b) != 0ull; }
-__device__ __forceinline__ bool none1(bool b) { return __builtin_amdgcn_ballot_w64(b) == 0ull; }
-__device__ __forceinline__ uint32_t slot_in_group(uint32_t group_first_slot, uint32_t code, int lane) {
-    const unsigned long long starts = ballot1((code != STEP_PAD) & ((code & STEP_START) != 0u)) & ~1ull;   // lane 0's walk is group_first_slot itself
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(starts >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)starts, 0u));   // starts in lower lanes
-    return group_first_slot + below + (uint32_t)((starts >> lane) & 1ull);
-}
-
-// read_nodes_len of position j (never the last position) of a long walk: the length aligned at the node's FIRST
-// occurrence in the read (profile.rs:879-882)
-__device__ __forceinline__ uint32_t rl_from_memory(uint32_t j, uint32_t b, const uint32_t *__restrict__ node_id, const uint8_t *__restrict__ step_dup,
-                                                   uint32_t delta, const uint4 *__restrict__ node_rec, uint32_t len0, uint32_t ps) {
-    const uint32_t idj = node_id[b + j];
-    if (j == 0 || ((step_dup[b + j] & 1u) && idj == node_id[b])) return len0 - ps;
-    return node_rec[idj + delta].z;
-}
-
-// -DCOV_ABLATE builds (never the product library: make OUT=../lib_prof EXTRA=-DCOV_ABLATE, loaded through PANTAX_HIP_LIB) read
-// PANTAX_COV_ABLATE: bit 0 no bit / flag marking, bit 1 no `bases`, bit 2 no unique-trio lookups -- wrong results, for timing only
-#ifdef COV_ABLATE
-#define ABL(bit) (ablate & (bit))
-#else
-#define ABL(bit) false
-#endif
-constexpr int COV_WIN_BACK = 128; // window starts (at least) this many nodes before the node of the chunk's first live step
-constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
-
-__device__ __forceinline__ void add_bases(unsigned long long *__restrict__ bases, uint32_t wlo, uint32_t win_n, uint32_t v, uint32_t aln) {
-    const uint32_t off = v - wlo;   // unsigned wrap puts nodes below the window out of range too
-    if (off < win_n && aln < (1u << 18)) atomicAdd(&S_WIN(off), aln);   // <= 8192 steps x 2^18 < 2^32
-    else atomicAdd(&bases[v], (unsigned long long)aln);
-}
-// The full-node flag of node v (v = NO_FULL: none) -- called by ALL 64 lanes of a wave.  Inside the LDS window: plain byte stores of the
-// same value (no atomic, nothing to lose).  Outside: the steps of a long walk are neighbouring nodes, so dozens of lanes would OR
-// into the SAME 32-bit word -- memory-side atomics on one address run one after the other (1.0 of the kernel's 2.6 ms at cfg5's share);
-// the lanes of one word combine their bits first (DPP reduction) and the first of them issues ONE atomic per distinct word.
-constexpr uint32_t NO_FULL = 0xFFFFFFFFu;
-__device__ __forceinline__ void mark_full_wave(uint32_t *__restrict__ full, uint32_t wlo, uint32_t win_n, uint32_t v) {
-    const uint32_t off = v - wlo;
-    const bool have = v != NO_FULL;
-    if (have && off < win_n) S_FULL(COV_WIN, off) = 1;
-    const bool out = have && off >= win_n;
-    unsigned long long todo = __ballot(out);
-    const uint32_t w = v >> 5, bit = 1u << (v & 31);
-    const int lane = threadIdx.x & 63;
-    while (todo) {                                 // (wave-uniform) one round per distinct word: two to four for a stretch of a walk
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t wl = (uint32_t)__builtin_amdgcn_readlane((int)w, leader);
-        const bool mine = out && w == wl;
-        const uint32_t orv = wave_reduce(mine ? bit : 0u, [](uint32_t x, uint32_t y) { return x | y; });
-        if (lane == leader) atomicOr(&full[wl], orv);   // no test-before-set: the probe is a dependent round trip, the OR is fire-and-forget
-        todo &= ~__ballot(mine);
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // The short-read kernel: every 64-step group whose walks all have <= 64 steps (no STEP_LONG code: all of a short-read
@@ -181,9 +62,6 @@ __device__ __forceinline__ void mark_full_wave(uint32_t *__restrict__ full, uint
 // Dirichlet-distributed sample -- 4096 steps span more nodes than the LDS windows hold, and every update outside them is a memory-side
 // atomic: 3.3 of the kernel's 10.6 ms at 1e4 strains.  By node block the windows cover the block whatever the depth, and a deeply
 // covered block is simply cut into more items.)
-constexpr uint32_t COV_ITEM_GROUPS = 128;     // (64 until the end of round 5: a block of 2048 ids holds ~80 groups at 1e8 reads, cut as 64 + 17; whole blocks as ONE item: 5.2 -> 5.0 ms)
-struct __attribute__((packed, aligned(4))) EntPair { uint32_t a, b, c, d; };     // two neighbouring lookup entries {smaller end, larger end}
-constexpr int COV_BLK_SHIFT = 11;
 //
 // LONG (round 6): the same select-only body for the groups that hold steps of walks of MORE than 64 steps (HiFi / ONT reads; round 5 sent them through
 // coverage_step_kernel, whose per-lane branches for wave-straddling walks -- dependent loads under an exec mask for the two neighbours across a wave
@@ -194,22 +72,6 @@ constexpr int COV_BLK_SHIFT = 11;
 //   * per slot {length of the walk's first node, sum of the node lengths before the last step} (walk_sum_kernel) and the id of the walk's first
 //     step: gathers with the read record / the node record, for every lane (the lanes of one walk share the address);
 // and every per-lane case is a select.  only_long != 0: groups without a step of a longer walk are the plain instantiation's.
-template <int WIN>
-__device__ __forceinline__ void mark_full_out_wave(uint32_t *__restrict__ full, bool out, uint32_t v) {
-    // the steps of a long walk are neighbouring nodes: dozens of lanes would OR into the SAME word, and memory-side atomics on one address run one
-    // after the other -- the lanes of a word combine their bits first and ONE of them issues the atomic (wave-uniform loop, called by all 64 lanes)
-    unsigned long long todo = ballot1(out);
-    const uint32_t w = v >> 5, bit = 1u << (v & 31);
-    const int lane = threadIdx.x & 63;
-    while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const uint32_t wl = (uint32_t)__builtin_amdgcn_readlane((int)w, leader);
-        const bool mine = out & (w == wl);
-        const uint32_t orv = wave_reduce(mine ? bit : 0u, [](uint32_t x, uint32_t y) { return x | y; });
-        if (lane == leader) atomicOr(&full[wl], orv);
-        todo &= ~ballot1(mine);
-    }
-}
 template <bool WITH_TRIO, int U, int PASSES, int WIN, bool LONG = false>
 __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
     const uint2 *__restrict__ items, const uint32_t *__restrict__ group_slot, const uint4 *__restrict__ read_rec, const uint2 *__restrict__ slot_rec,
@@ -545,277 +407,6 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
     }
 }
 
-// Steps arrive grouped by the locus of their read's first node (build_step_read below), so a workgroup's
-// chunk of consecutive steps lands in a narrow node window: `bases` is accumulated in an LDS
-// window of COV_WIN nodes (32-bit LDS atomics) and flushed with one 64-bit global atomic per touched
-// node -- the LDS-staged segmented reduction of the scatter.  Nodes outside the window (or oversized
-// lengths) fall back to the global atomic; the result is identical either way.
-//
-// The kernel is bound by instruction issue and by the latency of its chain of dependent gathers, so
-//   * the chain is three levels: {slot, node id, step code} (stream) -> {read record (16 B), slot record (8 B)} -> {node record}
-//     (-> a unique-trio entry where the node has any).  The slot record {species, node base - first id} is written by the
-//     binning pass; a binned walk lies inside its species' range and db_upload makes the range span exactly the graph, so a
-//     step places its node with ONE add and no range test; the node record carries the lookup head of the unique-trio index (first row, #rows)
-//     next to bit offset and length, and a 3-window takes the head of its middle node from the lane below:
-//     ONE divergent 16-byte gather per step.  Everything is in global node indices (the lookup entries too).
-//   * a step that covers its whole node (every interior step of a read: profile.rs:860-862 with :870-873) sets ONE flag for
-//     the node instead of marking its bits word by word (popcount_kernel then takes the node's length); only the partial
-//     ranges -- first and last step of a read -- are marked in the bit window, in 32-bit positions relative to the window.
-//   * every wave works on U groups of 64 steps at once: the loads of one level are issued for all U groups before the
-//     first of them is waited for (U x the memory-level parallelism per wave; registers permitting).
-// PASSES such rounds share one set of LDS windows (zeroing and flushing them is per workgroup).  Workgroups are handed to
-// the XCDs round-robin by the dispatcher; XCD_MAP makes every XCD walk ONE contiguous eighth of the stream, so neighbouring
-// chunks -- which share the node records and bitmap lines at their seam -- meet in the same L2.
-template <bool WITH_TRIO, int U, int PASSES>
-__global__ void __launch_bounds__(COV_BLOCK) coverage_step_kernel(
-    uint64_t T, const uint32_t *__restrict__ group_slot, const uint4 *__restrict__ read_rec, const uint2 *__restrict__ slot_rec,
-    const uint32_t *__restrict__ node_id, const uint8_t *__restrict__ step_dup, const uint8_t *__restrict__ active,
-    const uint4 *__restrict__ node_rec, unsigned long long *__restrict__ bases, uint32_t *__restrict__ bitmap, uint32_t *__restrict__ full,
-    const uint2 *__restrict__ trio_ent, unsigned long long *__restrict__ trio_bases, unsigned long long *__restrict__ n_abort,
-    const uint32_t *__restrict__ long_sum, const uint32_t *__restrict__ long_len0, uint32_t n_chunks, uint32_t xcd_map, uint32_t ablate,
-    uint32_t only_long /* 1: groups without a step of a longer walk belong to coverage_fast_kernel */) {
-    constexpr int CHUNK = COV_BLOCK * U * PASSES;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t chunk = blockIdx.x;
-    if (xcd_map) {   // blockIdx -> XCD is round-robin over 8: XCD x takes chunks [x * per, (x + 1) * per)
-        const uint32_t per = (n_chunks + 7) / 8;
-        chunk = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
-        if ((blockIdx.x >> 3) >= per || chunk >= n_chunks) return;
-    }
-    const uint64_t chunk_b = (uint64_t)chunk * CHUNK;
-    uint64_t chunk_e = chunk_b + CHUNK;
-    if (chunk_e > T) chunk_e = T;
-    for (int i = threadIdx.x; i < (int)(cov_lds_bytes(COV_WIN) / 4); i += COV_BLOCK) s_cov[i] = 0;
-    // window base: the node of the first live step among a few probes of the chunk.  Every thread computes it
-    // (workgroup-uniform addresses), so nobody waits on a broadcast and the probes overlap the first gathers.
-    uint32_t wlo = 0, win_n = 0;
-    uint64_t bw0 = 0, bit0 = 0;
-    uint32_t bwn = 0;
-#pragma unroll
-    for (int c = 0; c < CHUNK / COV_BLOCK; ++c) {
-        const uint64_t tc = chunk_b + (uint64_t)c * COV_BLOCK;
-        if (win_n == 0 && tc < chunk_e) {
-            const uint32_t slot = group_slot[tc >> 6];          // tc is a multiple of 64: the read that owns the group's first step
-            if (slot != NO_SLOT) {
-                const uint2 sr0 = slot_rec[slot];
-                if ((int)sr0.x >= 0 && !(active && !active[sr0.x])) {
-                    const uint32_t v0 = node_id[tc] + sr0.y;
-                    wlo = (v0 > (uint32_t)COV_WIN_BACK ? v0 - COV_WIN_BACK : 0u) & ~63u;
-                    win_n = COV_WIN;
-                    bw0 = nr_bit_off(node_rec[wlo]) >> 5;        // bit window starts at the window's first node
-                    bit0 = bw0 << 5;
-                    bwn = COV_BWIN;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // the stream loads of round r + 1 are requested at the top of round r, as in the short-read kernel (-DCOV_NO_PREFETCH: the round-4 loop)
-#ifndef COV_NO_PREFETCH
-    uint32_t n_id[U], n_dupc[U], n_gs[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint64_t t = chunk_b + (uint64_t)(wave * U + u) * 64 + lane;
-        const uint64_t tc = t < chunk_e ? t : chunk_b;              // (in range; dead lanes of a round are masked by `ok`)
-        n_id[u] = node_id[tc]; n_dupc[u] = step_dup[tc]; n_gs[u] = group_slot[tc >> 6];
-    }
-#endif
-#pragma unroll 1
-    for (int pass = 0; pass < PASSES; ++pass) {
-        const uint64_t wbase = chunk_b + (uint64_t)((pass * (COV_BLOCK / 64) + wave) * U) * 64;   // this wave's U x 64 consecutive steps
-        if (wbase >= chunk_e) break;
-        // ---- level 1: the stream
-        uint32_t slot[U], id[U], dupc[U], ti[U];
-        bool ok[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint64_t t = wbase + (uint64_t)u * 64 + lane;
-            ok[u] = t < chunk_e;                                     // whole groups: T_pad and the chunk size are multiples of 64
-            slot[u] = NO_SLOT; id[u] = 0; dupc[u] = STEP_PAD;
-            ti[u] = (uint32_t)t;                                     // T_pad < 2^32 (build_step_read)
-#ifndef COV_NO_PREFETCH
-            uint32_t gs_now = NO_SLOT;
-            if (ok[u]) { id[u] = n_id[u]; dupc[u] = n_dupc[u]; gs_now = n_gs[u]; }
-            {
-                const uint64_t tn = t + (uint64_t)COV_BLOCK * U;    // the same lane's step in the coming round
-                const uint64_t tc = (pass + 1 < PASSES && tn < chunk_e) ? tn : chunk_b;
-                n_id[u] = node_id[tc]; n_dupc[u] = step_dup[tc]; n_gs[u] = group_slot[tc >> 6];
-            }
-            const uint32_t gs = gs_now;
-#else
-            if (ok[u]) { id[u] = node_id[t]; dupc[u] = step_dup[t]; }
-            const uint32_t gs = ok[u] ? group_slot[t >> 6] : NO_SLOT;
-#endif
-            const uint32_t sl = slot_in_group(gs, dupc[u], lane);
-            ok[u] = ok[u] && dupc[u] != STEP_PAD;
-            if (only_long && !__any(ok[u] && (dupc[u] & STEP_LONG))) ok[u] = false;   // a short-read group: the other kernel's
-            if (ok[u]) slot[u] = sl;
-        }
-        // ---- level 2: per-read records
-        uint4 rr[U];
-        uint2 sr[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            rr[u] = make_uint4(0u, 0u, 0u, 0u); sr[u] = make_uint2(0xFFFFFFFFu, 0u);
-            if (ok[u]) { rr[u] = read_rec[slot[u]]; sr[u] = slot_rec[slot[u]]; }
-        }
-        // ---- level 3: the node record (issued before the species' `active` flag is known: a wasted gather at worst)
-        uint4 nr[U];
-        uint32_t v[U], act[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            ok[u] = ok[u] && (int)sr[u].x >= 0;                       // "U" / dropped rows
-            nr[u] = make_uint4(0u, 0u, 0u, 0u); v[u] = 0; act[u] = 1u;
-            if (ok[u]) {
-                v[u] = id[u] + sr[u].y;
-                nr[u] = node_rec[v[u]];
-                if (active) act[u] = active[sr[u].x];
-            }
-        }
-        // ---- shuffles, the trio lookup head and the first trio entry (level 4), for all groups
-        uint32_t v1[U], v2[U], len0[U], tlo[U], thi[U];
-        uint2 th[U];
-        uint2 e0[U], e1[U];   // the first TWO lookup entries of the head: with one, 95 % of the waves held a lane whose window was
-                              // the node's second entry (8 % of the visits meet a head of two or more) and paid another dependent gather
-        int dist[U];
-        bool cross[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (ok[u] && !act[u]) ok[u] = false;                      // unselected species
-            if (!ok[u]) { v[u] = 0; nr[u] = make_uint4(0u, 0u, 0u, 0u); }
-            const uint32_t b = rr[u].x;
-            const uint32_t i = ok[u] ? ti[u] - b : 0u;
-            dist[u] = ok[u] ? (int)min(i, (uint32_t)lane) : 0;        // earlier steps of my read held by lower lanes
-            cross[u] = ok[u] && (int)i > lane;                        // the walk began before this wave (more than 64 steps)
-            // neighbours one and two lanes down: DPP wave shifts (VALU), not LDS-crossbar shuffles
-            v1[u] = wave_shr1(v[u]); v2[u] = wave_shr1(v1[u]);
-            const uint32_t tf1 = wave_shr1(nr[u].w), ty1 = wave_shr1(nr[u].y);
-            th[u] = make_uint2(0u, 0u); tlo[u] = 0; thi[u] = 0; e0[u] = make_uint2(0u, 0u); e1[u] = make_uint2(0u, 0u);
-            if (WITH_TRIO && !ABL(4u) && ok[u] && i >= 2) {
-                if (lane < 1) v1[u] = node_id[b + i - 1] + sr[u].y;
-                if (lane < 2) v2[u] = node_id[b + i - 2] + sr[u].y;
-                // canonical window (min end, middle, max end); the lookup rows are filed under the MIDDLE node (the lane below), keyed by the two ends
-                tlo[u] = min(v[u], v2[u]); thi[u] = max(v[u], v2[u]);
-                uint32_t hy = ty1;
-                if (lane >= 1) th[u].x = tf1;
-                else { const uint4 r1 = node_rec[v1[u]]; th[u].x = r1.w; hy = r1.y; }   // wave border of a long walk
-                th[u].y = (nr_filter(hy) & nr_pair_bit(tlo[u], thi[u])) ? nr_rows(hy) : 0u;   // the pair filter: nothing is fetched for a window whose bit is clear
-                if (th[u].y) {
-                    const EntPair ep = *reinterpret_cast<const EntPair *>(trio_ent + th[u].x);   // two entries, one load (one entry of slack behind the last row)
-                    e0[u] = make_uint2(ep.a, ep.b); e1[u] = make_uint2(ep.c, ep.d);
-                }
-            }
-            // first node length: from the lane that holds step b, else (long walk) noted by walk_sum_kernel
-            const uint32_t nl_src = __shfl(nr[u].z, lane - dist[u]);
-            len0[u] = nr[u].z;
-            if (ok[u] && i > 0) len0[u] = !cross[u] ? nl_src : long_len0[slot[u]];
-        }
-        // ---- per group: aligned lengths, bitmap, bases, trio bases
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t b = rr[u].x, k = rr[u].y, ps = rr[u].z, pe = rr[u].w;
-            // positions, node lengths and aligned lengths are 32-bit quantities (the packed layout carries u32 columns and a
-            // walk cannot align 4 Gbp): only `target` needs a sign.
-            const uint32_t i = ok[u] ? ti[u] - b : 0u;
-            const uint64_t bo = nr_bit_off(nr[u]);
-            const uint32_t nl = nr[u].z;
-            const uint64_t rel = bo - bit0;                           // the node inside the LDS bit window: 32-bit relative positions
-            const bool in_win = rel < (uint64_t)bwn * 32 && nl <= (uint64_t)bwn * 32 - rel;   // (a node that starts below the window wraps to a huge rel)
-            bool live = ok[u];
-            uint32_t mfull = NO_FULL;                                 // the node this step covers whole (its flag is set below, by the whole wave)
-            const long long target = (long long)pe - (long long)ps;   // profile.rs:800
-            if (live && k == 1) {                                     // :811
-                if (target >= 0) {                                    // :821-827
-                    if (target && !ABL(2u)) add_bases(bases, wlo, win_n, v[u], (uint32_t)target);
-                    if (ps < pe && pe <= nl && !ABL(1u)) {            // :832
-                        if (ps == 0 && pe == nl) { if (!ABL(8u)) mfull = v[u]; }
-                        else if (ABL(16u)) {}
-                        else if (in_win) mark_window(COV_WIN, (uint32_t)rel + ps, (uint32_t)rel + pe);
-                        else mark_range(bitmap, COV_WIN, bw0, bwn, bo + ps, bo + pe);
-                    }
-                }
-                live = false;
-            }
-            if (live && ps > len0[u]) {                               // assert :854 -> whole read contributes nothing
-                if (i == 0) atomicAdd(n_abort, 1ull);
-                live = false;
-            }
-            // ---- `seen` before this step = sum of the aligned lengths of steps 0..i-1 of MY read: a plain wave prefix sum (DPP)
-            // minus its value at the lane that holds step 0 -- the steps of a read sit in consecutive lanes (mod 2^32 like the adds)
-            const uint32_t contrib = live ? (i == 0 ? nl - ps : nl) : 0u;
-            const int dst = dist[u];
-            const uint32_t pexcl = wave_incl_scan_dpp(contrib) - contrib;
-            const uint32_t seen_in_wave = pexcl - __shfl(pexcl, lane - dst);
-            // ---- first occurrence of this node in the read (:879): decided at upload time (step codes above)
-            const uint32_t id0 = __shfl(id[u], lane - dst);           // id of step 0 when the walk starts in this wave
-            uint32_t rl = 0;
-            if (live) {
-                int jf = -1;                                          // -1: first occurrence; 0: the node of step 0; 1: another earlier step
-                if (dupc[u] & STEP_LONG) { if (dupc[u] & 1u) jf = (id[u] == (cross[u] ? node_id[b] : id0)) ? 0 : 1; }
-                else if (dupc[u] & STEP_DIST) jf = (int)i - (int)(dupc[u] & STEP_DIST);
-                uint32_t aln, sidx;
-                if (i == 0) { aln = nl - ps; sidx = ps; }             // :853-856
-                else if (i == k - 1) {                                // :857-859
-                    uint32_t seen = seen_in_wave;
-                    if (cross[u]) seen = long_sum[slot[u]] - ps;      // all steps but the last, from walk_sum_kernel
-                    aln = target > (long long)seen ? (uint32_t)(target - (long long)seen) : 0u;   // max(target - seen, 0)
-                    sidx = 0;
-                } else { aln = nl; sidx = 0; }                        // :860-862
-                uint32_t hi = sidx + aln;
-                if (hi > nl) hi = nl;                                 // :871
-                if (ABL(1u)) {}
-                else if (sidx == 0 && hi == nl) { if (nl && !ABL(8u)) mfull = v[u]; }
-                else if (ABL(16u)) {}
-                else if (in_win) mark_window(COV_WIN, (uint32_t)rel + sidx, (uint32_t)rel + hi);
-                else mark_range(bitmap, COV_WIN, bw0, bwn, bo + sidx, bo + hi);
-                if (jf < 0) {
-                    rl = aln;
-                    if (aln && !ABL(2u)) add_bases(bases, wlo, win_n, v[u], aln);     // :881
-                } else rl = (jf == 0) ? (len0[u] - ps) : nl;
-            }
-            mark_full_wave(full, wlo, win_n, mfull);
-            if (WITH_TRIO) {                                          // :890-907
-                uint32_t rl1 = wave_shr1(rl), rl2 = wave_shr1(wave_shr1(rl));
-                if (live && i >= 2 && !ABL(4u)) {
-                    if (lane < 1) rl1 = rl_from_memory(i - 1, b, node_id, step_dup, sr[u].y, node_rec, len0[u], ps);
-                    if (lane < 2) rl2 = rl_from_memory(i - 2, b, node_id, step_dup, sr[u].y, node_rec, len0[u], ps);
-                    long long row = -1;                                      // a row IS its lookup entry: the index of the entry that matches
-                    if (th[u].y) {
-                        if (e0[u].x == tlo[u] && e0[u].y == thi[u]) row = (long long)th[u].x;
-                        else if (th[u].y > 1 && e1[u].x == tlo[u] && e1[u].y == thi[u]) row = (long long)th[u].x + 1;
-                        else
-                            for (uint32_t j = 2; j < th[u].y; ++j) {
-                                const uint2 e = trio_ent[th[u].x + j];
-                                if (e.x == tlo[u] && e.y == thi[u]) { row = (long long)th[u].x + j; break; }
-                            }
-                    }
-                    if (row >= 0) {
-                        const unsigned long long sum = (unsigned long long)rl2 + rl1 + rl;
-                        if (sum) atomicAdd(&trio_bases[row], sum);
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (win_n) {
-        for (int i = threadIdx.x; i < COV_WIN; i += COV_BLOCK) {
-            const uint32_t c = S_WIN(i);
-            if (c) atomicAdd(&bases[wlo + i], (unsigned long long)c);
-            // full-node flags: the window starts at a multiple of 64 nodes, so a wave's ballot is two whole words of the flag vector
-            const unsigned long long fb = __ballot(S_FULL(COV_WIN, i) != 0);
-            if (fb && (lane & 31) == 0) {
-                const uint32_t m = (uint32_t)(fb >> (lane & 32));
-                if (m) atomicOr(&full[(wlo + i) >> 5], m);
-            }
-        }
-    }
-    for (uint32_t i = threadIdx.x; i < bwn; i += COV_BLOCK) {
-        const uint32_t m = S_BM(COV_WIN, i);
-        if (m) atomicOr(&bitmap[bw0 + i], m);     // nothing waits for these (a probe first would be a dependent round trip per word)
-    }
-}
-
 // Walks of more than 64 steps: the last step needs `seen` = everything aligned before it (:857-859), which lives in
 // other waves.  One cheap pass over the steps of long walks adds the node lengths of all steps but the last into
 // long_sum[slot] (one atomic per wave and walk); launched only when the upload saw such walks.
@@ -883,352 +474,6 @@ __global__ void __launch_bounds__(256) walk_sum_kernel(uint64_t T, const uint32_
             if (tail && slot[u] != NO_SLOT && incl) atomicAdd(&long_sum[slot[u]], incl);
         }
     }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Resident layout of the packed reads: grouped by the locus of their first node and padded so that
-// a walk of <= 64 steps never straddles a 64-step boundary.  Key = first node id >> shift (ids are
-// globally ordered by species and position, sort_range.rs:25-33).  Counting sort of the reads into
-// slots (histogram -> scan -> scatter), then one thread per bucket lays its walks out (start moved to
-// the next multiple of 64 when the walk would straddle one; bucket sizes rounded up to 64), a scan of
-// the bucket sizes, and the fill.  Done once per upload: it depends on the reads only, not on the
-// binning.  Slot order inside a bucket is arbitrary; every output of the path is an order-independent
-// integer sum, so results stay bit-exact.  Reads with an empty walk own no slot (profile.rs:794-796).
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) group_count_kernel(uint64_t R, const uint32_t *__restrict__ step_off, const uint32_t *__restrict__ node_id,
-                                                          int shift, uint32_t *__restrict__ cnt_r) {
-    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < R; r += (uint64_t)gridDim.x * 256) {
-        const uint32_t b = step_off[r], k = step_off[r + 1] - b;
-        if (k) atomicAdd(&cnt_r[node_id[b] >> shift], 1u);
-    }
-}
-__global__ void __launch_bounds__(256) group_slot_kernel(uint64_t R, const uint32_t *__restrict__ step_off, const uint32_t *__restrict__ node_id,
-                                                         const uint32_t *__restrict__ pstart, const uint32_t *__restrict__ pend, const uint32_t *__restrict__ qlen,
-                                                         const uint8_t *__restrict__ mapq, int shift, const uint32_t *__restrict__ base_r, uint32_t *__restrict__ cur_r,
-                                                         uint32_t *__restrict__ slot_of, uint4 *__restrict__ g_read_rec, uint2 *__restrict__ g_qm,
-                                                         uint32_t *__restrict__ n_long) {
-    // The per-read columns are read HERE, in file order (coalesced), and leave as the slot's two records -- {first step of the walk in
-    // the source columns (group_fill_kernel replaces it by the walk's place in the grouped stream), #steps, pstart, pend} and {read
-    // length, MAPQ}: the fill pass then reads one coalesced record per slot.  (Round 3 kept {#steps, read} per slot and let the fill
-    // pass gather six columns at random: 46 GB fetched for 4 GB of payload at 1e8 reads.)
-    uint32_t mine = 0;
-    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < R; r += (uint64_t)gridDim.x * 256) {
-        const uint32_t b = step_off[r], k = step_off[r + 1] - b;
-        uint32_t slot = NO_SLOT;
-        if (k) {
-            const uint32_t key = node_id[b] >> shift;
-            slot = base_r[key] + atomicAdd(&cur_r[key], 1u);
-            g_read_rec[slot] = make_uint4(b, k, pstart[r], pend[r]);
-            g_qm[slot] = make_uint2(qlen[r], (uint32_t)mapq[r]);    // slot-order copies for the binning pass
-            mine += k > 64 ? 1u : 0u;
-        }
-        slot_of[r] = slot;
-    }
-    if (__any(mine != 0)) {
-        mine = wave_reduce(mine, [](uint32_t x, uint32_t y) { return x + y; });
-        if ((threadIdx.x & 63) == 0) atomicAdd(n_long, mine);
-    }
-}
-// One thread lays out a UNIT of 2^g consecutive buckets; only units are rounded up to 64 steps.  (Rounding every 32-node
-// bucket cost 32 pad steps per bucket on average: with ten reads per bucket -- 1e7 reads over 3.2e7 nodes -- the padded
-// stream was 1.45 x the walk steps, and the coverage kernel spends a lane on every pad.)
-// A thread lays out ONE unit (its reads one after the other: a walk of <= 64 steps never straddles a 64-step border).  A workgroup of 64 threads takes 64
-// consecutive units -- their reads are one stretch of slots --, loads the reads' step counts into LDS coalesced, lets every thread walk its unit there,
-// and writes the places back coalesced.  (The first version had every thread read its reads' 16-byte records from memory, far from its neighbours':
-// 10.7 GB of sector traffic for 1.6 GB of records at 1e8 reads, 4.8 ms.)  A stretch of more reads than the LDS holds takes the plain loop.
-constexpr uint32_t GL_UNITS = 64, GL_CAP = 24576;
-__global__ void __launch_bounds__(64) group_layout_kernel(uint32_t NB, int g, const uint32_t *__restrict__ base_r /*[NB+1]*/,
-                                                          const uint4 *__restrict__ g_read_rec, uint32_t *__restrict__ slot_rel,
-                                                          uint32_t *__restrict__ size_s) {
-    __shared__ uint32_t s_k[GL_CAP];
-    const uint32_t NU = (NB + (1u << g) - 1) >> g;
-    const uint32_t u0 = blockIdx.x * GL_UNITS, key = u0 + threadIdx.x;
-    const uint32_t kb = min(NB, u0 << g), ke = min(NB, (u0 + GL_UNITS) << g);
-    const uint32_t s_begin = base_r[kb], n_wg = base_r[ke] - s_begin;                    // (workgroup-uniform)
-    const bool staged = n_wg <= GL_CAP;
-    if (staged) {
-        for (uint32_t i = threadIdx.x; i < n_wg; i += GL_UNITS) s_k[i] = g_read_rec[s_begin + i].y;
-        __syncthreads();
-    }
-    if (key < NU) {
-        const uint32_t k0 = key << g, k1 = min(NB, (key + 1) << g);
-        uint32_t pos = 0;
-        for (uint32_t s = base_r[k0], e = base_r[k1]; s < e; ++s) {
-            const uint32_t k = staged ? s_k[s - s_begin] : g_read_rec[s].y;
-            if (k <= 64 && (pos & 63) + k > 64) pos = (pos + 63) & ~63u;
-            if (staged) s_k[s - s_begin] = pos; else slot_rel[s] = pos;
-            pos += k;
-        }
-        size_s[key] = (pos + 63) & ~63u;
-    }
-    if (staged) {
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < n_wg; i += GL_UNITS) slot_rel[s_begin + i] = s_k[i];
-    }
-}
-// In SLOT order, one WAVE per 64 consecutive slots: the lanes first file their slot's records (coalesced), then hand the steps
-// of the 64 walks out flat over the wave -- lane = step of the output stream, which the slots follow in order, so node ids and
-// step codes are written as dense runs and the short source walks are gathered.  (Thread per read in file order scattered
-// single dwords and bytes over the whole stream: 72 GB written for 4 GB of payload at 1e8 reads, 46 ms; thread per slot with
-// a private loop over its steps still re-read every walk k times for the first-occurrence codes: 41 ms.)  The code of a step
-// -- distance back to the first occurrence of its node in the walk -- comes from the lanes below (and, where a walk began in
-// the round before, from that round's ids).
-__global__ void __launch_bounds__(256) group_fill_kernel(uint32_t n_slots, const uint32_t *__restrict__ node_id, int shift,
-                                                         const uint32_t *__restrict__ base_s, const uint32_t *__restrict__ slot_rel, uint4 *__restrict__ g_read_rec,
-                                                         uint32_t *__restrict__ g_node_id, uint32_t *__restrict__ g_group_slot,
-                                                         uint8_t *__restrict__ g_step_dup, uint2 *__restrict__ g_mm) {
-    __shared__ uint32_t s_excl[4][65], s_b[4][64], s_sb[4][64];
-    __shared__ uint2 s_mm[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t n_waves = (n_slots + 63) / 64;
-    for (uint32_t w = blockIdx.x * 4 + wave; w < n_waves; w += gridDim.x * 4) {
-        const uint32_t slot = w * 64 + lane;
-        uint32_t b = 0, k = 0, sb = 0;
-        if (slot < n_slots) {
-            uint4 rec = g_read_rec[slot];                            // {first step in the source columns, #steps, pstart, pend}: group_slot_kernel
-            b = rec.x; k = rec.y;
-            sb = base_s[node_id[b] >> shift] + slot_rel[slot];
-            rec.x = sb;
-            g_read_rec[slot] = rec;
-            if (k > 64) { k = 0; s_mm[wave][lane] = make_uint2(0xFFFFFFFFu, 0u); }   // laid out by group_fill_long_kernel, one workgroup per walk (min / max: its atomics)
-            else if ((sb & 63u) == 0u) g_group_slot[sb >> 6] = slot; // a walk of <= 64 steps lies inside one 64-step group
-        }
-        const uint32_t incl = wave_incl_scan_dpp(k);
-        const uint32_t total = __shfl(incl, 63);
-        s_excl[wave][lane] = incl - k; s_b[wave][lane] = b; s_sb[wave][lane] = sb;
-        if (lane == 0) s_excl[wave][64] = total;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-        uint32_t prev_id = 0;
-        for (uint32_t f0 = 0; f0 < total; f0 += 64) {
-            const uint32_t f = f0 + (uint32_t)lane;
-            const bool on = f < total;
-            uint32_t o = 0;                                          // owner: the last slot whose first flat step is <= f (walks of 0 steps own none)
-            if (on) {
-                uint32_t lo = 0, hi = 63;
-                while (lo < hi) { const uint32_t mid = (lo + hi + 1) >> 1; if (s_excl[wave][mid] <= f) lo = mid; else hi = mid - 1; }
-                o = lo;
-            }
-            const uint32_t i = on ? f - s_excl[wave][o] : 0u;
-            const uint32_t id = on ? node_id[s_b[wave][o] + i] : 0u;
-            // first occurrence of my node among the i earlier steps of my walk: they sit in the lanes below, or in the round before
-            uint32_t dup = 0, mn = id, mx = id;                      // smallest / largest id of my walk up to my step: complete in the lane of its last step
-            const uint32_t imax = wave_reduce(i, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
-            for (uint32_t d = 1; d <= imax; ++d) {
-                const uint32_t cur = __shfl(id, (lane - (int)d) & 63), old = __shfl(prev_id, (lane - (int)d) & 63);
-                const uint32_t other = (int)d <= lane ? cur : old;
-                if (d <= i && other == id) dup = d;                   // the largest such distance = the first occurrence
-                const uint32_t mine = d <= i ? other : id;
-                mn = min(mn, mine); mx = max(mx, mine);
-            }
-            if (on) {
-                const uint32_t dst = s_sb[wave][o] + i;
-                g_node_id[dst] = id;
-                g_step_dup[dst] = (uint8_t)(dup | (i == 0 ? STEP_START : 0u));
-                if (i + 1 == s_excl[wave][o + 1] - s_excl[wave][o]) s_mm[wave][o] = make_uint2(mn, mx);   // the walk's last step (the owner of a flat step holds at least one)
-            }
-            prev_id = id;
-        }
-        // {min id, max id} of the 64 walks, one coalesced store (a slot holds a walk of at least one step: every row of s_mm was written)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-        if (slot < n_slots) g_mm[slot] = s_mm[wave][lane];
-        __builtin_amdgcn_wave_barrier();                             // the LDS rows are reused by this wave's next 64 slots
-    }
-}
-
-// Walks of more than 64 steps: one workgroup copies the walk (coalesced) and decides for every step whether its node
-// occurred earlier in the walk -- an LDS hash of (node id -> smallest position) for walks of up to LONG_HASH/2 steps,
-// a plain scan of the earlier steps above that.  The copy loop, which every walk takes, also forms the walk's smallest and largest id
-// for the binning pass (group_fill_kernel, which runs first, left the neutral pair in the slot's place): one atomic pair per wave.
-constexpr uint32_t LONG_HASH = 8192;
-__global__ void __launch_bounds__(256) group_fill_long_kernel(uint64_t R, const uint32_t *__restrict__ step_off, const uint32_t *__restrict__ node_id,
-                                                              int shift, const uint32_t *__restrict__ base_s, const uint32_t *__restrict__ slot_of,
-                                                              const uint32_t *__restrict__ slot_rel, uint32_t *__restrict__ g_node_id,
-                                                              uint32_t *__restrict__ g_group_slot, uint8_t *__restrict__ g_step_dup,
-                                                              uint2 *__restrict__ g_mm) {
-    __shared__ uint32_t h_key[LONG_HASH], h_pos[LONG_HASH];
-    constexpr uint32_t EMPTY = 0xFFFFFFFFu;
-    for (uint64_t r = blockIdx.x; r < R; r += gridDim.x) {
-        const uint32_t b = step_off[r], k = step_off[r + 1] - b;
-        if (k <= 64) continue;
-        const uint32_t slot = slot_of[r];
-        const uint32_t sb = base_s[node_id[b] >> shift] + slot_rel[slot];
-        uint32_t mn = 0xFFFFFFFFu, mx = 0;
-        for (uint32_t i = threadIdx.x; i < k; i += 256) {
-            const uint32_t id = node_id[b + i];
-            g_node_id[sb + i] = id;
-            mn = min(mn, id); mx = max(mx, id);
-            if (((sb + i) & 63u) == 0u) g_group_slot[(sb + i) >> 6] = slot;   // every group this walk's steps begin
-        }
-        mn = wave_reduce(mn, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
-        mx = wave_reduce(mx, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
-        if ((threadIdx.x & 63) == 0) {
-            uint32_t *mm = reinterpret_cast<uint32_t *>(g_mm + slot);
-            atomicMin(mm, mn); atomicMax(mm + 1, mx);
-        }
-        if (k <= LONG_HASH / 2) {
-            for (uint32_t i = threadIdx.x; i < LONG_HASH; i += 256) { h_key[i] = EMPTY; h_pos[i] = EMPTY; }
-            __syncthreads();
-            for (uint32_t i = threadIdx.x; i < k; i += 256) {
-                const uint32_t id = node_id[b + i];
-                uint32_t h = (id * 2654435761u) >> 19;             // 13 bits
-                for (;;) {
-                    const uint32_t old = atomicCAS(&h_key[h], EMPTY, id);
-                    if (old == EMPTY || old == id) { atomicMin(&h_pos[h], i); break; }
-                    h = (h + 1) & (LONG_HASH - 1);
-                }
-            }
-            __syncthreads();
-            for (uint32_t i = threadIdx.x; i < k; i += 256) {
-                const uint32_t id = node_id[b + i];
-                uint32_t h = (id * 2654435761u) >> 19;
-                while (h_key[h] != id) h = (h + 1) & (LONG_HASH - 1);
-                g_step_dup[sb + i] = (uint8_t)(STEP_LONG | (h_pos[h] < i ? 1u : 0u) | (i == 0 ? STEP_START : 0u));
-            }
-            __syncthreads();
-        } else {
-            for (uint32_t i = threadIdx.x; i < k; i += 256) {
-                const uint32_t id = node_id[b + i];
-                uint32_t dup = 0;
-                for (uint32_t j = 0; j < i; ++j) if (node_id[b + j] == id) { dup = 1; break; }
-                g_step_dup[sb + i] = (uint8_t)(STEP_LONG | dup | (i == 0 ? STEP_START : 0u));
-            }
-        }
-    }
-}
-
-// first group of every node block: the smallest group whose first step is the first step of a read that starts in the block (a group
-// that continues a longer walk, or holds only pads, starts no read)
-__global__ void __launch_bounds__(256) group_block_kernel(uint32_t n_groups, const uint32_t *__restrict__ group_slot, const uint32_t *__restrict__ g_node_id,
-                                                          const uint8_t *__restrict__ step_code, int bshift, uint32_t *__restrict__ first_g) {
-    for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n_groups; g += gridDim.x * 256) {
-        if (group_slot[g] == NO_SLOT) continue;
-        const uint32_t code = step_code[(uint64_t)g * 64];
-        if (code == STEP_PAD || !(code & STEP_START)) continue;
-        atomicMin(&first_g[g_node_id[(uint64_t)g * 64] >> bshift], g);
-    }
-}
-
-int build_step_read(Ctx *ctx, Reads *rd, uint32_t max_node_id) {
-    static std::atomic<uint64_t> next_layout{1};
-    rd->layout_id = next_layout.fetch_add(1);       // (what a db's list of work items is made for)
-    rd->T_pad = 0;
-    rd->n_long = 0;
-    rd->n_slots = 0;
-    rd->n_items = 0;
-    rd->g_flags_valid = false;
-    rd->species_valid = false;
-    PTX_HIP(ctx, rd->d_slot_of.alloc(rd->R ? rd->R : 1));
-    PTX_HIP(ctx, rd->d_g_slot_rec.alloc(rd->R ? rd->R : 1));
-    PTX_HIP(ctx, rd->d_g_qm.alloc(rd->R ? rd->R : 1));
-    PTX_HIP(ctx, rd->d_g_mm.alloc(rd->R ? rd->R : 1));
-    if (rd->R == 0) return 0;
-    if (rd->T == 0) {
-        PTX_HIP(ctx, hipMemsetAsync(rd->d_slot_of.p, 0xFF, rd->R * sizeof(uint32_t), ctx->stream));
-        return 0;
-    }
-    int shift = 5;
-    // buckets of 32 node ids up to 5e8 ids (round 4; 2^20 buckets before: 512-id buckets at 3e8 ids, whose reads are in no particular order --
-    // the coverage pass gathers node records along the stream, and neighbours in the stream should be neighbours in the graph)
-    int bucket_cap_bits = 24;
-    if (ctx->cfg.group_bucket_bits) bucket_cap_bits = std::max(10, std::min(26, ctx->cfg.group_bucket_bits));
-    while (((uint64_t)max_node_id >> shift) + 1 > (1ull << bucket_cap_bits)) ++shift;
-    const uint32_t NB = (uint32_t)(max_node_id >> shift) + 1;
-    DevBuf<uint32_t> cnt, scan_tmp, slot_rel;
-    PTX_HIP(ctx, cnt.alloc(4ull * (NB + 1) + 8));
-    uint32_t *cnt_r = cnt.p, *base_r = cnt_r + (NB + 1), *size_s = base_r + (NB + 1), *base_s = size_s + (NB + 1);
-    PTX_HIP(ctx, scan_tmp.alloc(scan_tmp_elems(NB + 1)));
-    PTX_HIP(ctx, slot_rel.alloc(rd->R));
-    PTX_HIP(ctx, rd->d_g_read_rec.alloc(rd->R));
-    PTX_TRY(zero_fill(ctx, cnt_r, (NB + 1) * sizeof(uint32_t)));
-    int gridR = grid_for(rd->R, 256, ctx->n_cu * 8);
-    hipLaunchKernelGGL(group_count_kernel, dim3(gridR), dim3(256), 0, ctx->stream, rd->R, rd->d_step_off.p, rd->d_node_id.p, shift, cnt_r);
-    PTX_TRY(exclusive_scan_u32(ctx, cnt_r, base_r, NB + 1, scan_tmp.p, nullptr));
-    PTX_TRY(zero_fill(ctx, cnt_r, (NB + 1) * sizeof(uint32_t)));   // reused as cursors
-    uint32_t *d_total = (uint32_t *)ctx->d_scalars.p, *d_n_long = d_total + 1;
-    PTX_HIP(ctx, hipMemsetAsync(d_n_long, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(group_slot_kernel, dim3(gridR), dim3(256), 0, ctx->stream, rd->R, rd->d_step_off.p, rd->d_node_id.p, rd->d_pstart.p, rd->d_pend.p,
-                       rd->d_qlen.p, rd->d_mapq.p, shift, base_r, cnt_r, rd->d_slot_of.p, rd->d_g_read_rec.p, rd->d_g_qm.p, d_n_long);
-    // layout units: 2^g buckets each, about 2048 walk steps per unit (the rounding of a unit to 64 steps then costs ~1.5 %)
-    int g = 0;
-    while (g < 12 && ((double)rd->T / (double)NB) * (double)(1u << g) < 2048.0) ++g;
-    const uint32_t NU = (NB + (1u << g) - 1) >> g;
-    hipLaunchKernelGGL(group_layout_kernel, dim3((NU + GL_UNITS - 1) / GL_UNITS), dim3(GL_UNITS), 0, ctx->stream, NB, g, base_r, rd->d_g_read_rec.p, slot_rel.p, size_s);
-    PTX_TRY(exclusive_scan_u32(ctx, size_s, base_s, NU, scan_tmp.p, d_total));
-    const int ushift = shift + g;   // unit of a read = its first node id >> ushift
-    uint32_t h_tot[2] = {0, 0}, h_slots = 0;
-    PTX_TRY(download(ctx, h_tot, d_total, 2));
-    PTX_TRY(download(ctx, &h_slots, base_r + NB, 1));   // reads that own a slot (non-empty walk)
-    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint32_t h_total = h_tot[0];
-    rd->n_long = h_tot[1];
-    rd->n_slots = h_slots;
-    if ((uint64_t)h_total < rd->T) return fail(ctx, PANTAX_HIP_E_LIMIT, "reads_upload: padded step stream exceeds 32-bit positions");
-    rd->T_pad = h_total;
-    PTX_HIP(ctx, rd->d_g_node_id.alloc(rd->T_pad)); PTX_HIP(ctx, rd->d_g_group_slot.alloc(rd->T_pad / 64 + 1)); PTX_HIP(ctx, rd->d_g_step_dup.alloc(rd->T_pad));
-    PTX_TRY(byte_fill(ctx, rd->d_g_node_id.p, 0, rd->T_pad * sizeof(uint32_t)));
-    PTX_TRY(byte_fill(ctx, rd->d_g_group_slot.p, 0xFF, (rd->T_pad / 64 + 1) * sizeof(uint32_t)));
-    PTX_TRY(byte_fill(ctx, rd->d_g_step_dup.p, 0xFF, rd->T_pad));                                            // STEP_PAD
-    if (rd->n_slots)
-        hipLaunchKernelGGL(group_fill_kernel, dim3(grid_for(rd->n_slots, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, rd->n_slots, rd->d_node_id.p, ushift,
-                           base_s, slot_rel.p, rd->d_g_read_rec.p, rd->d_g_node_id.p, rd->d_g_group_slot.p, rd->d_g_step_dup.p, rd->d_g_mm.p);
-    if (rd->n_long) {
-        const uint32_t gridL = (uint32_t)std::min<uint64_t>(rd->R, (uint64_t)ctx->n_cu * 64);
-        hipLaunchKernelGGL(group_fill_long_kernel, dim3(gridL), dim3(256), 0, ctx->stream, rd->R, rd->d_step_off.p, rd->d_node_id.p, ushift, base_s,
-                           rd->d_slot_of.p, slot_rel.p, rd->d_g_node_id.p, rd->d_g_group_slot.p, rd->d_g_step_dup.p, rd->d_g_mm.p);
-        PTX_HIP(ctx, rd->d_long_sum.alloc(rd->R));
-        PTX_HIP(ctx, rd->d_long_len0.alloc(rd->R));
-    }
-    PTX_HIP(ctx, hipGetLastError());
-    // work items of the short-read coverage kernel: the groups cut at the borders of 2048-id node blocks (the stream is in the order of
-    // the reads' first nodes, bucket by bucket), a block's groups cut into items of COV_ITEM_GROUPS
-    {
-        const uint32_t n_groups = (uint32_t)(rd->T_pad / 64);
-        const int bshift = std::max(COV_BLK_SHIFT, shift);
-        const uint32_t NBLK = (uint32_t)(max_node_id >> bshift) + 1;
-        DevBuf<uint32_t> first_g;
-        PTX_HIP(ctx, first_g.alloc(NBLK + 1));
-        PTX_HIP(ctx, hipMemsetAsync(first_g.p, 0xFF, ((size_t)NBLK + 1) * sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(group_block_kernel, dim3(grid_for(n_groups, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, n_groups, rd->d_g_group_slot.p, rd->d_g_node_id.p,
-                           rd->d_g_step_dup.p, bshift, first_g.p);
-        std::vector<uint32_t> fg((size_t)NBLK + 1);
-        PTX_TRY(download(ctx, fg.data(), first_g.p, (size_t)NBLK + 1));
-        PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        fg[NBLK] = n_groups;
-        bool monotone = true;
-        for (uint32_t b = NBLK; b-- > 0;) { if (fg[b] == 0xFFFFFFFFu) fg[b] = fg[b + 1]; else if (fg[b] > fg[b + 1]) monotone = false; }
-        fg[0] = 0;                                                  // groups in front of the first live one (pads) belong to the first block
-        std::vector<uint2> items;
-        rd->h_item_block.clear();
-        const uint32_t cap = ctx->cfg.cov_item_groups > 0 ? (uint32_t)ctx->cfg.cov_item_groups : COV_ITEM_GROUPS;
-        if (monotone)
-            for (uint32_t b = 0; b < NBLK; ++b)
-            {   // a block's groups in EQUAL items of at most `cap` groups (81 groups: 41 + 40, not 64 + 17 -- a workgroup zeroes and flushes its LDS windows once per item)
-                const uint32_t n = fg[b + 1] - fg[b];
-                if (!n) continue;
-                const uint32_t k = (n + cap - 1) / cap, per = (n + k - 1) / k;
-                for (uint32_t g = fg[b]; g < fg[b + 1]; g += per) { items.push_back(make_uint2(g, std::min(fg[b + 1], g + per))); rd->h_item_block.push_back(b); }
-            }
-        else   // cannot happen with the counting sort above; never silent: plain cuts of the stream
-            for (uint32_t g = 0; g < n_groups; g += COV_ITEM_GROUPS) items.push_back(make_uint2(g, std::min(n_groups, g + COV_ITEM_GROUPS)));
-        rd->n_items = (uint32_t)items.size();
-        rd->item_blk_shift = monotone ? bshift : 0;
-        PTX_TRY(upload(ctx, rd->d_g_items, items.data(), items.size()));
-    }
-    PTX_HIP(ctx, hipGetLastError());
-    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // temporaries are released on return
-    return 0;
-}
-
-int reads_group(Ctx *ctx, Reads *rd) {
-    if (rd->grouped) return 0;
-    PTX_TRY(build_step_read(ctx, rd, rd->max_node_id));
-    rd->grouped = true;
-    rd->binned = false;          // the species of a read now live in its slot record: the next binning pass writes them
-    return 0;
 }
 
 // node_base_cov[v] = number of covered bases (profile.rs:844/874, :1018-1023)
@@ -1318,19 +563,16 @@ __global__ void __launch_bounds__(256) count_nonzero_words_kernel(const uint32_t
 // The part of the coverage pass that depends on the binning only -- zero-filling the result arena and the walk sums of
 // long reads: the resident step issues it while the trio index is still being built on the side stream.
 int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio) {
-    const uint64_t words = (db->L + 31) / 32 + 1;
-    const uint64_t U = with_trio ? db->U : 0;
     // one arena, one memset: [bases V u64][trio_bases U u64][abort u64][bitmap words u32][full-node flags: 1 bit per node, padded by a window]
-    const uint64_t fwords = (db->V + 4096 + 63) / 32 + 2;     // padded by the largest LDS window
-    const size_t off_trio = db->V * 8, off_abort = off_trio + (U ? U : 1) * 8, off_bm = (off_abort + 8 + 15) & ~(size_t)15 /* (16-byte loads of the bit vector) */, off_full = off_bm + words * 4,
-                 total = off_full + fwords * 4;
+    const CovArenaLayout a = cov_arena_layout(db->V, with_trio ? db->U : 0, db->L);
+    const size_t off_trio = a.off_trio, off_bm = a.off_bm, off_full = a.off_full, total = a.total;
     PTX_HIP(ctx, db->d_cov_arena.alloc(total));
     uint8_t *base = db->d_cov_arena.p;
     db->d_bases.view(base, db->V);
-    db->d_trio_bases.view(base + off_trio, U ? U : 1);
-    db->d_abort = reinterpret_cast<unsigned long long *>(base + off_abort);
-    db->d_bitmap.view(base + off_bm, words);
-    db->d_full.view(base + off_full, fwords);
+    db->d_trio_bases.view(base + off_trio, a.n_trio);
+    db->d_abort = reinterpret_cast<unsigned long long *>(base + a.off_abort);
+    db->d_bitmap.view(base + off_bm, a.words);
+    db->d_full.view(base + off_full, a.fwords);
     // (d_cov is allocated by the pass that writes it -- popcount_kernel below, node_stats_launch: a resident step on the fused node pass has none)
     // the resident step's last readers left the arena zeroed (cov_arena_clean) unless its layout or place changed since: only the abort counter is reset
     const uint64_t sig = (uint64_t)(uintptr_t)base ^ ((uint64_t)total * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)off_bm << 1) ^ ((uint64_t)off_full << 2) ^ (uint64_t)off_trio;
@@ -1400,184 +642,158 @@ int coverage_arena_clean_async(Ctx *ctx, Db *db) {
     return 0;
 }
 
-int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool with_trio, bool defer_count) {
-    if (!rd->grouped) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: these reads are a slice kept as plain columns (to be routed to their owner), not resident reads");
-    const bool trace = ctx->cfg.trace && !defer_count;     // (the stage call of the file seam: where its milliseconds go)
-    auto t_prev = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (!trace) return;
+// ---- coverage_launch: its stopwatch and its phases, in the order it calls them
+// (the stage call of the file seam under hip_trace: where its milliseconds go)
+struct CovLap {
+    Ctx *ctx;
+    bool on;
+    std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+    void operator()(const char *what) {
+        if (!on) return;
         (void)hipStreamSynchronize(ctx->stream);
         const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "[node_coverage]        %-28s %9.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
-        t_prev = now;
-    };
+        std::fprintf(stderr, "[node_coverage]        %-28s %9.3f ms\n", what, std::chrono::duration<double, std::milli>(now - prev).count());
+        prev = now;
+    }
+};
+
+// the `active` table of the select-only kernels, which load the flag unconditionally: all ones when no species is deselected
+static int active_flags(Ctx *ctx, Db *db, const uint8_t *d_active, const uint8_t **out) {
+    if (!d_active) {
+        if (db->d_ones.n < db->S) { PTX_HIP(ctx, db->d_ones.alloc(db->S)); PTX_HIP(ctx, hipMemsetAsync(db->d_ones.p, 1, db->S, ctx->stream)); }
+        d_active = db->d_ones.p;
+    }
+    *out = d_active;
+    return 0;
+}
+
+// Only the items whose node block meets the id range of one of the db's species hold reads of its species (round 6: the file seam runs a selection
+// group by group over the same resident reads -- a read that starts outside every range is "U" for this db, and streaming its steps only to
+// find that out cost a group of a quarter of the species 6 ms where the whole selection as one db took 8).  Every read of an item starts inside
+// the item's block.  The groups of the seam are contiguous in the order of the species TABLE (by abundance), not of the ids: the items are
+// picked species by species into a list (a few hundred KB), not as one range (cov_item_select).  The list is made once per db and reads layout.
+struct ItemList { uint32_t n; const uint32_t *d; };   // d null: items 0 .. n - 1
+static int item_selection(Ctx *ctx, Db *db, const Reads *rd, ItemList *out) {
+    *out = {rd->n_items, nullptr};
+    if (db->item_sel_layout == rd->layout_id && rd->layout_id != 0) {        // the list made for these reads' layout by an earlier pass of this db
+        *out = {db->item_sel_n, db->item_sel_on ? db->d_item_sel.p : nullptr};
+    } else if (rd->h_item_block.size() == rd->n_items && rd->item_blk_shift > 0 && db->S && !db->h_range_start.empty()) {
+        const CovItemSel s = cov_item_select(rd->h_item_block, rd->item_blk_shift, db->h_range_start, db->h_range_end);
+        if (s.on && s.n_sel) PTX_TRY(upload(ctx, db->d_item_sel, s.sel.data(), s.sel.size()));
+        *out = {s.n_sel, s.on && s.n_sel ? db->d_item_sel.p : nullptr};
+        db->item_sel_layout = rd->layout_id; db->item_sel_n = s.n_sel; db->item_sel_on = s.on;
+    }
+    return 0;
+}
+
+// what the two uses of coverage_fast_kernel pass differently: the short-read one its work items, LONG the walk sums and its cuts of the stream
+struct CovFastTail {
+    const uint2 *items; int blk_shift; const uint32_t *long_sum, *long_len0; uint32_t only_long, chunk_groups, total_groups, win_back; const uint32_t *item_sel;
+};
+template <int U, int PASSES, int WIN, bool LONG>
+static void fast_launch_as(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_act, bool trio, int grid, const CovFastTail &t) {
+    if (grid <= 0) return;
+    const auto kernel = trio ? coverage_fast_kernel<true, U, PASSES, WIN, LONG> : coverage_fast_kernel<false, U, PASSES, WIN, LONG>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(COV_BLOCK), cov_lds_bytes(WIN), ctx->stream, t.items, rd->d_g_group_slot.p, rd->d_g_read_rec.p,
+                       rd->d_g_slot_rec.p, rd->d_g_node_id.p, rd->d_g_step_dup.p, d_act, db->d_node_rec.p, db->d_bit_off.p, db->V, db->d_bases.p,
+                       db->d_bitmap.p, db->d_full.p, db->d_trio_ent.p, db->d_trio_bases.p, db->d_abort, ctx->cfg.cov_ablate /* -DCOV_ABLATE builds only */,
+                       t.blk_shift, t.long_sum, t.long_len0, t.only_long, t.chunk_groups, t.total_groups, t.win_back, t.item_sel);
+}
+
+// Walks of <= 64 steps: the short-read kernel, one wave per 64-step group, PASSES groups per wave and workgroup (the LDS windows are zeroed and flushed
+// once per workgroup).  Groups in flight per wave, rounds per workgroup, nodes in the LDS window: 2 x 4 groups (2048 steps); 2 x 8 (4096 steps) on
+// streams of 2^28 steps and more, where a workgroup's start-up chain costs more (measured: 0.711 vs 0.768 ms at 8e7 steps, 11.7 vs 9.8 ms at 8e8).  The
+// window: 2304 nodes since round 5 -- an item's reads start inside one block of 2048 ids and the window begins 64..127 nodes in front of it, so 2304
+// hold every short read; the 3072 of rounds 3-4 cost 23.5 KB of LDS per workgroup = SIX waves per SIMD where the registers allow eight (19.7 KB:
+// eight).  The kernel waits for its gathers two thirds of the time: 6.46 -> 5.77 ms at 1e8 reads, 0.708 -> 0.639 at 1e7 (2048 nodes: 7.3 / 0.77,
+// the reads at a block's end fall off the window)
+static int fast_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_act, bool trio, const CovFastShape &f, const ItemList &list) {
+    const CovFastTail t{rd->d_g_items.p, rd->item_blk_shift, nullptr, nullptr, 0u, 0u, 0u, 0u, list.d};
+    const int grid = (int)list.n;
+    const auto is = [&](int u, int passes, int win) { return f.u == u && f.passes == passes && f.win == win; };
+    if (is(1, 8, 2048)) fast_launch_as<1, 8, 2048, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 4, 2048)) fast_launch_as<2, 4, 2048, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 8, 2048)) fast_launch_as<2, 8, 2048, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 8, 3072)) fast_launch_as<2, 8, 3072, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 8, 4096)) fast_launch_as<2, 8, 4096, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 4, 3072)) fast_launch_as<2, 4, 3072, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 8, 2304)) fast_launch_as<2, 8, 2304, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 8, 2560)) fast_launch_as<2, 8, 2560, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 4, 2304)) fast_launch_as<2, 4, 2304, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(2, 4, 2560)) fast_launch_as<2, 4, 2560, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(1, 8, 2304)) fast_launch_as<1, 8, 2304, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(4, 4, 2304)) fast_launch_as<4, 4, 2304, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(4, 4, 2048)) fast_launch_as<4, 4, 2048, false>(ctx, db, rd, d_act, trio, grid, t);
+    else if (is(4, 4, 3072)) fast_launch_as<4, 4, 3072, false>(ctx, db, rd, d_act, trio, grid, t);
+    else return fail(ctx, PANTAX_HIP_E_STATE, "coverage_launch: no short-read kernel of shape U = %d, PASSES = %d, WIN = %d", f.u, f.passes, f.win);
+    return 0;
+}
+
+// Groups that hold steps of longer walks (HiFi / ONT reads; cov_general: every group -- measurements, and the tests force it): round 6's select-only body
+// (coverage_fast_kernel<.., LONG>) over plain cuts of the stream.  Default shape: 2 groups in flight per wave, 64 groups (4096 steps) per workgroup, a
+// 3072-node window that begins 1024 nodes in front of the first live step (reverse-strand walks run down from their first node)
+static int long_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_act, bool trio, const CovPlan &plan) {
+    if (!rd->d_long_sum.p) { PTX_HIP(ctx, rd->d_long_sum.alloc(rd->R)); PTX_HIP(ctx, rd->d_long_len0.alloc(rd->R)); }   // (cov_general over short reads: never read)
+    const CovLongShape &l = plan.lng;
+    const uint32_t total_groups = (uint32_t)(rd->T_pad / 64);
+    const int grid = (int)((total_groups + l.chunk_groups - 1) / l.chunk_groups);
+    const CovFastTail t{nullptr, 0, rd->d_long_sum.p, rd->d_long_len0.p, plan.only_long ? 1u : 0u, l.chunk_groups, total_groups, l.win_back, nullptr};
+    if (l.u == 1 && l.win == 2048) fast_launch_as<1, 1, 2048, true>(ctx, db, rd, d_act, trio, grid, t);
+    else if (l.u == 1 && l.win == 3072) fast_launch_as<1, 1, 3072, true>(ctx, db, rd, d_act, trio, grid, t);
+    else if (l.u == 1 && l.win == 4096) fast_launch_as<1, 1, 4096, true>(ctx, db, rd, d_act, trio, grid, t);
+    else if (l.u == 2 && l.win == 2048) fast_launch_as<2, 1, 2048, true>(ctx, db, rd, d_act, trio, grid, t);
+    else if (l.u == 2 && l.win == 4096) fast_launch_as<2, 1, 4096, true>(ctx, db, rd, d_act, trio, grid, t);
+    else if (l.u == 2 && l.win == 3072) fast_launch_as<2, 1, 3072, true>(ctx, db, rd, d_act, trio, grid, t);
+    else return fail(ctx, PANTAX_HIP_E_STATE, "coverage_launch: no long-walk kernel of shape U = %d, WIN = %d", l.u, l.win);
+    return 0;
+}
+
+// node_base_cov of the stage call (the resident step leaves it to the node statistics pass: defer_count)
+static int count_launch(Ctx *ctx, Db *db) {
+    PTX_HIP(ctx, db->d_cov.alloc(db->V));
+    KTimer t(ctx, "popcount_kernel");
+    if (long_node_shape(db->L, db->V, ctx->cfg.ncs_prefix_min, ctx->cfg.ncs_no_prefix))
+        hipLaunchKernelGGL(popcount_long_kernel, dim3(grid_for((db->V + 63) / 64, 4, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, db->V,
+                           db->d_bit_off.p, db->d_full.p, db->d_bitmap.p, db->d_cov.p);
+    else
+        hipLaunchKernelGGL(popcount_kernel, dim3(grid_for(db->V, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, db->V,
+                           db->d_bit_off.p, db->d_full.p, db->d_bitmap.p, db->d_cov.p);
+    return 0;
+}
+
+int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool with_trio, bool defer_count) {
+    if (!rd->grouped) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: these reads are a slice kept as plain columns (to be routed to their owner), not resident reads");
+    const bool trace = ctx->cfg.trace && !defer_count;
+    CovLap lap{ctx, trace};
     if (!db->cov_prepared) PTX_TRY(coverage_prepare(ctx, db, rd, with_trio));
     lap("arena + zero fill");
     db->cov_prepared = false;
     db->trio_free_valid = false;   // a reader of the unique-trio tables goes onto the stream: the event of an earlier strain step no longer covers them
-    unsigned long long *d_abort = db->d_abort;
-    if (rd->R && rd->T_pad) {
-        const uint32_t xcd_map = (uint32_t)ctx->cfg.cov_xcd;   // 1: every XCD walks one contiguous eighth of the stream (measured slower: 1.42 vs 1.30 ms at cfg3)
-        const uint32_t ablate = ctx->cfg.cov_ablate;           // -DCOV_ABLATE builds only
-        const bool cov_general = ctx->cfg.cov_general;
-        const bool trio = with_trio && db->U;
-        const uint8_t *d_act_fast = d_active;
-        if (!d_act_fast) {   // the short-read kernel loads the flag unconditionally: all ones when no species is deselected
-            if (db->d_ones.n < db->S) { PTX_HIP(ctx, db->d_ones.alloc(db->S)); PTX_HIP(ctx, hipMemsetAsync(db->d_ones.p, 1, db->S, ctx->stream)); }
-            d_act_fast = db->d_ones.p;
-        }
-        // walks of <= 64 steps: the short-read kernel, one wave per 64-step group, PASSES groups per wave and workgroup (the LDS
-        // windows are zeroed and flushed once per workgroup).  Skipped when every walk is longer.
-        if (rd->n_long < rd->n_slots && rd->n_items && !cov_general) {
-            KTimer t(ctx, "coverage_fast_kernel");
-            // groups in flight per wave, rounds per workgroup, nodes in the LDS window: 2 x 4 groups (2048 steps); 2 x 8 (4096 steps) on streams of 2^28
-            // steps and more, where a workgroup's start-up chain costs more (measured: 0.711 vs 0.768 ms at 8e7 steps, 11.7 vs 9.8 ms at 8e8).  The window:
-            // 2304 nodes since round 5 -- an item's reads start inside one block of 2048 ids and the window begins 64..127 nodes in front of it, so 2304
-            // hold every short read; the 3072 of rounds 3-4 cost 23.5 KB of LDS per workgroup = SIX waves per SIMD where the registers allow eight (19.7 KB:
-            // eight).  The kernel waits for its gathers two thirds of the time: 6.46 -> 5.77 ms at 1e8 reads, 0.708 -> 0.639 at 1e7 (2048 nodes: 7.3 / 0.77,
-            // the reads at a block's end fall off the window)
-            int fshape = rd->T_pad >= (1ull << 28) ? 2823 : 2423;
-            if (ctx->cfg.covf_shape > 0) fshape = ctx->cfg.covf_shape;
-            // Only the items whose node block meets the id range of one of the db's species hold reads of its species (round 6: the file seam runs a selection
-            // group by group over the same resident reads -- a read that starts outside every range is "U" for this db, and streaming its steps only to
-            // find that out cost a group of a quarter of the species 6 ms where the whole selection as one db took 8).  Every read of an item starts inside
-            // the item's block.  The groups of the seam are contiguous in the order of the species TABLE (by abundance), not of the ids: the items are
-            // picked species by species into a list (a few hundred KB), not as one range.
-            uint32_t n_sel = rd->n_items;
-            const uint32_t *d_sel = nullptr;
-            if (db->item_sel_layout == rd->layout_id && rd->layout_id != 0) {        // the list made for these reads' layout by an earlier pass of this db
-                n_sel = db->item_sel_n;
-                d_sel = db->item_sel_on ? db->d_item_sel.p : nullptr;
-            } else if (rd->h_item_block.size() == rd->n_items && rd->item_blk_shift > 0 && db->S && !db->h_range_start.empty()) {
-                std::vector<std::pair<uint32_t, uint32_t>> rg;       // item ranges of the species, then merged
-                for (uint32_t s2 = 0; s2 < db->S; ++s2) {
-                    const uint32_t b_lo = (uint32_t)std::max<int64_t>(db->h_range_start[s2], 0) >> rd->item_blk_shift;
-                    const uint32_t b_hi = (uint32_t)std::min<int64_t>(std::max<int64_t>(db->h_range_end[s2], 0), 0xFFFFFFFFll) >> rd->item_blk_shift;
-                    uint32_t i_lo = (uint32_t)(std::lower_bound(rd->h_item_block.begin(), rd->h_item_block.end(), b_lo) - rd->h_item_block.begin());
-                    // An item carries the block of the FIRST read of its groups; the last group of the item in front may run on into this block (a group is
-                    // 64 steps of consecutive reads, and where reads are sparse a layout unit spans several blocks): its reads of block b_lo are this
-                    // species' too.  One item back is enough -- the next group already begins with a read of b_lo and opens an item of that block.
-                    if (i_lo > 0) --i_lo;
-                    const uint32_t i_hi = (uint32_t)(std::upper_bound(rd->h_item_block.begin(), rd->h_item_block.end(), b_hi) - rd->h_item_block.begin());
-                    if (i_hi > i_lo) rg.emplace_back(i_lo, i_hi);
-                }
-                std::sort(rg.begin(), rg.end());
-                std::vector<uint32_t> sel;
-                uint32_t done = 0;
-                for (const auto &r : rg) for (uint32_t i = std::max(r.first, done); i < r.second; ++i) { sel.push_back(i); done = i + 1; }
-                if (sel.size() + sel.size() / 8 < rd->n_items) {     // (worth the indirection)
-                    n_sel = (uint32_t)sel.size();
-                    if (n_sel) { PTX_TRY(upload(ctx, db->d_item_sel, sel.data(), sel.size())); d_sel = db->d_item_sel.p; }
-                }
-                db->item_sel_layout = rd->layout_id; db->item_sel_n = n_sel; db->item_sel_on = d_sel != nullptr || n_sel == 0;
-            }
-            if (trace) std::fprintf(stderr, "[node_coverage]        %u of %u items launched\n", n_sel, rd->n_items);
-#define COVF_ARGS rd->d_g_items.p, rd->d_g_group_slot.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, rd->d_g_node_id.p, rd->d_g_step_dup.p, d_act_fast, db->d_node_rec.p, \
-                  db->d_bit_off.p, db->V, db->d_bases.p, db->d_bitmap.p, db->d_full.p, db->d_trio_ent.p, db->d_trio_bases.p, d_abort, ablate, rd->item_blk_shift, \
-                  (const uint32_t *)nullptr, (const uint32_t *)nullptr, 0u, 0u, 0u, 0u, d_sel
-#define COVF_LAUNCH(UU, PP, WW)                                                                                                             \
-            {                                                                                                                            \
-                const int grid = (int)n_sel;                                                                                             \
-                if (grid <= 0) {}                                                                                                        \
-                else if (trio) hipLaunchKernelGGL((coverage_fast_kernel<true, UU, PP, WW>), dim3(grid), dim3(COV_BLOCK), cov_lds_bytes(WW), ctx->stream, COVF_ARGS); \
-                else hipLaunchKernelGGL((coverage_fast_kernel<false, UU, PP, WW>), dim3(grid), dim3(COV_BLOCK), cov_lds_bytes(WW), ctx->stream, COVF_ARGS);  \
-            }
-            switch (fshape) {                                              // <U><PASSES><window / 1024>
-                case 182: COVF_LAUNCH(1, 8, 2048) break;
-                case 242: COVF_LAUNCH(2, 4, 2048) break;
-                case 282: COVF_LAUNCH(2, 8, 2048) break;
-                case 283: COVF_LAUNCH(2, 8, 3072) break;
-                case 284: COVF_LAUNCH(2, 8, 4096) break;
-                case 243: COVF_LAUNCH(2, 4, 3072) break;
-                case 2823: COVF_LAUNCH(2, 8, 2304) break;                  // <U><PASSES><window / 256 as two digits - 70>: windows between 2048 and 3072 nodes
-                case 2825: COVF_LAUNCH(2, 8, 2560) break;
-                case 2423: COVF_LAUNCH(2, 4, 2304) break;
-                case 2425: COVF_LAUNCH(2, 4, 2560) break;
-                case 1823: COVF_LAUNCH(1, 8, 2304) break;
-                case 4423: COVF_LAUNCH(4, 4, 2304) break;
-                case 442: COVF_LAUNCH(4, 4, 2048) break;
-                case 443: COVF_LAUNCH(4, 4, 3072) break;
-                default: COVF_LAUNCH(2, 4, 2048) break;
-            }
-#undef COVF_LAUNCH
-#undef COVF_ARGS
-        }
-        // groups that hold steps of longer walks (HiFi / ONT reads): the general kernel.  U groups of 64 steps in flight per wave,
-        // PASSES rounds per workgroup (PANTAX_COV_SHAPE=<U><PASSES> picks another instantiation, for measurements);
-        // PANTAX_COV_GENERAL=1 sends every group through it (measurements, and the tests force it).
-        const bool long_by_step = ctx->cfg.cov_long == "step";   // round 5's kernel for the groups of longer walks (measurements, and the tests compare the two)
-        if ((rd->n_long || cov_general) && !long_by_step) {
-            // round 6: the select-only body (coverage_fast_kernel<.., LONG>) over plain cuts of the stream.  covl_shape = <U><groups per workgroup / 8><window /
-            // 1024 nodes><nodes in front of the first step / 256>: default 2 groups in flight per wave, 16 groups (1024 steps, ~2 HiFi reads) per workgroup,
-            // a 3072-node window that begins 1024 nodes in front of the first live step (reverse-strand walks run down from their first node)
-            KTimer t(ctx, "coverage_long_kernel");
-            if (!rd->d_long_sum.p) { PTX_HIP(ctx, rd->d_long_sum.alloc(rd->R)); PTX_HIP(ctx, rd->d_long_len0.alloc(rd->R)); }   // (cov_general over short reads: never read)
-            const uint32_t only_long = cov_general ? 0u : 1u;
-            int shape = ctx->cfg.covl_shape > 0 ? ctx->cfg.covl_shape : 2834;
-            // (four digits <U><G><W><B>, or five <U><GG><W><B> for more than 72 groups per workgroup)
-            const int su = shape >= 10000 ? shape / 10000 : shape / 1000, sg = shape >= 10000 ? shape / 100 % 100 : shape / 100 % 10, sw = shape / 10 % 10, sb = shape % 10;
-            const uint32_t chunk_groups = (uint32_t)std::max(1, sg) * 8u, total_groups = (uint32_t)(rd->T_pad / 64), win_back = (uint32_t)sb * 256u;
-            const int grid = (int)((total_groups + chunk_groups - 1) / chunk_groups);
-#define COVL_ARGS (const uint2 *)nullptr, rd->d_g_group_slot.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, rd->d_g_node_id.p, rd->d_g_step_dup.p, d_act_fast, db->d_node_rec.p, \
-                  db->d_bit_off.p, db->V, db->d_bases.p, db->d_bitmap.p, db->d_full.p, db->d_trio_ent.p, db->d_trio_bases.p, d_abort, ablate, 0, \
-                  (const uint32_t *)rd->d_long_sum.p, (const uint32_t *)rd->d_long_len0.p, only_long, chunk_groups, total_groups, win_back
-#define COVL_LAUNCH(UU, WW)                                                                                                                  \
-            {                                                                                                                                \
-                if (trio) hipLaunchKernelGGL((coverage_fast_kernel<true, UU, 1, WW, true>), dim3(grid), dim3(COV_BLOCK), cov_lds_bytes(WW), ctx->stream, COVL_ARGS); \
-                else hipLaunchKernelGGL((coverage_fast_kernel<false, UU, 1, WW, true>), dim3(grid), dim3(COV_BLOCK), cov_lds_bytes(WW), ctx->stream, COVL_ARGS);  \
-            }
-            if (grid > 0) switch (su * 10 + sw) {
-                case 12: COVL_LAUNCH(1, 2048) break;
-                case 13: COVL_LAUNCH(1, 3072) break;
-                case 14: COVL_LAUNCH(1, 4096) break;
-                case 22: COVL_LAUNCH(2, 2048) break;
-                case 24: COVL_LAUNCH(2, 4096) break;
-                default: COVL_LAUNCH(2, 3072) break;
-            }
-#undef COVL_LAUNCH
-#undef COVL_ARGS
-        }
-        if ((rd->n_long || cov_general) && long_by_step) {
-            KTimer t(ctx, "coverage_step_kernel");
-            const uint32_t only_long = cov_general ? 0u : 1u;
-            int shape = rd->T_pad >= (1ull << 25) ? 18 : 14;
-            if (ctx->cfg.cov_shape > 0) shape = ctx->cfg.cov_shape;
-#define COVS_ARGS rd->T_pad, rd->d_g_group_slot.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, rd->d_g_node_id.p, rd->d_g_step_dup.p, d_active, \
-                  db->d_node_rec.p, db->d_bases.p, db->d_bitmap.p, db->d_full.p, db->d_trio_ent.p, db->d_trio_bases.p, d_abort, rd->d_long_sum.p, \
-                  rd->d_long_len0.p, n_chunks, xcd_map, ablate, only_long
-#define COVS_LAUNCH(UU, PP)                                                                                                                  \
-            {                                                                                                                                \
-                const uint32_t n_chunks = (uint32_t)((rd->T_pad + (uint64_t)COV_BLOCK * UU * PP - 1) / ((uint64_t)COV_BLOCK * UU * PP));     \
-                const int grid = xcd_map ? (int)(((n_chunks + 7) / 8) * 8) : (int)n_chunks;                                                  \
-                if (trio) hipLaunchKernelGGL((coverage_step_kernel<true, UU, PP>), dim3(grid), dim3(COV_BLOCK), cov_lds_bytes(COV_WIN), ctx->stream, COVS_ARGS);  \
-                else hipLaunchKernelGGL((coverage_step_kernel<false, UU, PP>), dim3(grid), dim3(COV_BLOCK), cov_lds_bytes(COV_WIN), ctx->stream, COVS_ARGS);      \
-            }
-            switch (shape) {
-                case 22: COVS_LAUNCH(2, 2) break;
-                case 21: COVS_LAUNCH(2, 1) break;
-                case 41: COVS_LAUNCH(4, 1) break;
-                case 42: COVS_LAUNCH(4, 2) break;
-                case 18: COVS_LAUNCH(1, 8) break;
-                case 14: COVS_LAUNCH(1, 4) break;
-                default: COVS_LAUNCH(1, 4) break;
-            }
-#undef COVS_LAUNCH
-#undef COVS_ARGS
-        }
+    const bool trio = with_trio && db->U;
+    const uint8_t *d_act_fast = d_active;
+    if (rd->R && rd->T_pad) PTX_TRY(active_flags(ctx, db, d_active, &d_act_fast));
+    const CtxConfig &cfg = ctx->cfg;
+    const CovPlan plan = cov_plan(rd->T_pad, rd->n_long, rd->n_slots, rd->n_items, rd->R, cfg.cov_general, cfg.cov_long, cfg.covf_shape, cfg.covl_shape,
+                                  cfg.cov_shape, cfg.cov_xcd);
+    if (plan.run_fast) {
+        KTimer t(ctx, "coverage_fast_kernel");
+        ItemList list;
+        PTX_TRY(item_selection(ctx, db, rd, &list));
+        if (trace) std::fprintf(stderr, "[node_coverage]        %u of %u items launched\n", list.n, rd->n_items);
+        PTX_TRY(fast_launch(ctx, db, rd, d_act_fast, trio, plan.fast, list));
+    }
+    if (plan.run_long) {
+        KTimer t(ctx, "coverage_long_kernel");
+        PTX_TRY(long_launch(ctx, db, rd, d_act_fast, trio, plan));
+    }
+    if (plan.run_step) {   // round 5's kernel for the groups of longer walks (measurements, and the tests compare the two); it tests d_active for null itself
+        KTimer t(ctx, "coverage_step_kernel");
+        PTX_TRY(coverage_step_launch(ctx, db, rd, d_active, trio, plan));
     }
     PTX_HIP(ctx, hipGetLastError());
     lap("coverage kernels");
     db->cov_count_pending = defer_count && db->V != 0;   // the resident step: node_stats_launch counts the covered bases in its own pass
-    if (db->V && !defer_count) {
-        PTX_HIP(ctx, db->d_cov.alloc(db->V));
-        KTimer t(ctx, "popcount_kernel");
-        if (db->L / db->V >= (uint64_t)ctx->cfg.ncs_prefix_min && !ctx->cfg.ncs_no_prefix)     // long nodes on average: counts from a per-stretch prefix in LDS
-            hipLaunchKernelGGL(popcount_long_kernel, dim3(grid_for((db->V + 63) / 64, 4, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, db->V,
-                               db->d_bit_off.p, db->d_full.p, db->d_bitmap.p, db->d_cov.p);
-        else
-        hipLaunchKernelGGL(popcount_kernel, dim3(grid_for(db->V, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, db->V,
-                           db->d_bit_off.p, db->d_full.p, db->d_bitmap.p, db->d_cov.p);
-    }
+    if (db->V && !defer_count) PTX_TRY(count_launch(ctx, db));
     PTX_HIP(ctx, hipGetLastError());
     lap("popcount");
     db->cov_done = true;

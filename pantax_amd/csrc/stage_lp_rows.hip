@@ -5,6 +5,7 @@
 #include <vector>
 #include "lad.hpp"
 #include "lad_device.hpp"
+#include "cov_plan.hpp"
 #include "primitives.hpp"
 #include "wave.hpp"
 #include "scan_chained.hpp"
@@ -552,7 +553,7 @@ const char *lad_shape_name(LadShape s) { return s == LadShape::compact ? "compac
 bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg) {
     if (ctx->cfg.node_pass == "split" || !db->cov_count_pending || db->V == 0) return false;
     if (cfg->sample_nodes != 0 || ctx->cfg.cov_self_clean || db->cov_self_clean) return false;
-    if (db->L / db->V >= (uint64_t)ctx->cfg.ncs_prefix_min && !ctx->cfg.ncs_no_prefix) return false;
+    if (long_node_shape(db->L, db->V, ctx->cfg.ncs_prefix_min, ctx->cfg.ncs_no_prefix)) return false;
     return row_route(ctx, db).masks_in_sort;
 }
 

@@ -17,7 +17,7 @@
 //              read_strain_route=walk): a compact arena of W_s = ceil(K_s / 64) words per node over the species' K_s candidates only
 //              (bit = candidate index, candidates sorted by haplotype), built by read_strain_mask_kernel in one pass over the
 //              candidates' walks (64-bit atomic ORs: the result does not depend on their order).
-// read_strain_kernel walks the locus-grouped stream of the coverage pass (build_step_read, stage_cov.hip): a wave per 64-step group,
+// read_strain_kernel walks the locus-grouped stream of the coverage pass (build_step_read, stage_read_layout.hip): a wave per 64-step group,
 // a lane per step.  The AND of the masks over a walk's steps is a segmented scan over the lanes on the DPP path; walks of <= 64 steps
 // never straddle a group, so the lane of the last step holds the walk's AND and decides there.  Walks of more than 64 steps (long
 // reads) AND their per-group partials into a per-slot word set to all ones first (64-bit atomic AND), and read_strain_long_kernel
@@ -36,7 +36,7 @@ namespace ptx {
 namespace {
 
 constexpr uint32_t RS_NO_SLOT = 0xFFFFFFFFu;
-// step codes of the grouped stream (stage_cov.hip: STEP_PAD, STEP_START)
+// step codes of the grouped stream (cov_device.hpp: STEP_PAD, STEP_START)
 constexpr uint32_t RS_STEP_PAD = 0xFFu, RS_STEP_START = 0x40u;
 constexpr uint64_t RS_TILE = 4096;   // walk positions per tile of the mask pass (one wave)
 
