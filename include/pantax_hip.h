@@ -220,6 +220,33 @@ typedef struct {
 int pantax_hip_read_strains(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
                             uint32_t *hap_out /*[R]*/, int32_t *n_out /*[R]*/, double *post_out /*[R]*/);
 
+/* ---- per-strain coverage track (the --strain-coverage report; not a stage of the reference): coverage along the genome of selected haplotypes,
+ * in windows of W bases, from what pantax_hip_node_coverage leaves on the device.  For a species s, a species-local haplotype h and W >= 1:
+ *   v_0 .. v_{n-1} = the walk of h as global node indices (a node visited twice counts at both visits);
+ *   o_i = sum_{j<i} node_len[v_j] (u64) = the path offset of step i;  G_h = sum_i node_len[v_i];
+ *   step i belongs to window w_i = o_i / W: the window that holds the node's FIRST base (the model's walks carry no orientation,
+ *     profile.rs:1333-1342, types.rs:51-55: a node cannot be cut at a window border, and it is not);
+ *   h has n_win(h) = ceil(G_h / W) windows (none when G_h = 0); window w carries
+ *     n_nodes (u32) = the number of its steps,            len (u64)   = sum of node_len[v_i] over them,
+ *     covered (u64) = sum of node_base_cov[v_i],          bases (u64) = sum of bases_per_node[v_i]   (both as pantax_hip_node_coverage hands them out);
+ *   a window in which no node starts (a node longer than W runs through it) holds four zeros.
+ * Integers only: results are exact and independent of any order.
+ * win_off_out [C+1] = the prefix of n_win in the order of sel_hap; it is ALWAYS written.  When its total exceeds `cap` (the windows the four arrays
+ * hold) the call returns PANTAX_HIP_E_LIMIT with win_off_out filled and nothing else touched: a caller sizes its arrays by calling once with cap = 0.
+ * Requires that the db holds the coverage result of a pantax_hip_node_coverage call (a pantax_hip_strain_profile behind it changes nothing).  A resident
+ * step (pantax_hip_profile_step / _enqueue) counts the covered bases inside its own passes and may already have zeroed the coverage arena: behind one,
+ * and before any coverage pass, the call returns PANTAX_HIP_E_STATE.  PANTAX_HIP_E_INVALID: W = 0, a haplotype index out of range, a haplotype twice
+ * within a species, n_species different from the db's.  An empty selection, or a species without selected haplotypes, is fine. */
+typedef struct {
+    uint32_t n_species;       /* must equal the db's */
+    const uint64_t *sel_off;  /* [S+1] species s owns the selection entries [sel_off[s], sel_off[s+1]) */
+    const uint32_t *sel_hap;  /* [C] species-local haplotype index, any order, no repeats within a species */
+    uint64_t window;          /* W >= 1 */
+} pantax_hip_cov_track_set;
+int pantax_hip_strain_cov_track(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_cov_track_set *sel,
+                                uint64_t *win_off_out /*[C+1]*/, uint64_t cap /* windows the four arrays hold */,
+                                uint32_t *n_nodes_out, uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -406,6 +433,13 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
      * "U U - 0" when the read is not counted in a species or its species has no candidates.  Written only by a run that performs the
      * strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
     const char *read_strain_file;
+    /* --strain-coverage: path of the per-strain coverage track (pantax_hip_strain_cov_track over every group of species, right behind the group's strain
+     * step; NULL or "None" = off).  TSV with a header; the strains are the rows of strain_abundance.txt, in its order, every strain's windows ascending:
+     * species_taxid, strain_taxid, genome_ID (as in the strain table), start = w * W, end = min((w + 1) * W, G_h), n_nodes, len, covered, bases,
+     * depth = bases / len, breadth = covered / len (f64, shortest round-trip digits).  Windows with len = 0 are not written.  Written only by a run
+     * that performs the strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID (rows would have to be joined across ranks). */
+    const char *strain_coverage_file;
+    int64_t strain_coverage_window; /* --strain-coverage-window: W in bases; 0 = the default of 10000; negative: PANTAX_HIP_E_INVALID */
 } pantax_hip_profiling_config;
 
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in

@@ -443,6 +443,7 @@ int pantax_hip_node_coverage(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_
     // the rows are filed in: the permutation is made before the pass (it may rebuild the index with the window starts: same rows)
     if (trio_bases_out && db->U) PTX_TRY(trio_export_ensure(ctx, db));
     PTX_TRY(coverage_launch(ctx, db, reads, d_active, db->trio_built));
+    db->cov_stage = true;
     unsigned long long *d_abort = db->d_abort;
     unsigned long long h_abort = 0;
     std::vector<uint32_t> cov32;

@@ -53,6 +53,14 @@ int check_args(Run &run) {
     if (p.want_rs && (W > 1 || p.sharded))
         return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-read strain report (read_strain_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
                     p.sharded ? ", sharded" : "");
+    // --strain-coverage: the same reason -- the windows of a strain live on the rank that owns its species
+    p.ct_path = opt(cfg->strain_coverage_file);
+    p.want_ct = !p.ct_path.empty() && p.ct_path != "None";
+    if (p.want_ct && (W > 1 || p.sharded))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain coverage track (strain_coverage_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
+                    p.sharded ? ", sharded" : "");
+    if (p.want_ct && cfg->strain_coverage_window < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "profile: strain_coverage_window %lld", (long long)cfg->strain_coverage_window);
+    p.ct_window = p.want_ct && cfg->strain_coverage_window > 0 ? (uint64_t)cfg->strain_coverage_window : 10000;
     p.db_dir = opt(cfg->db); p.wd = opt(cfg->wd); p.out_dir = opt(cfg->output_dir);
     if (p.out_dir.empty()) p.out_dir = p.wd;
     if (!is_dir(p.db_dir)) return fail(ctx, PANTAX_HIP_E_IO, "Specified PanTax database directory '%s' is not a valid directory path", p.db_dir.c_str());
@@ -80,10 +88,14 @@ int decide_resume(Run &run) {
         run.p.full_path = d[0] != 0.0; run.p.strain_only = d[1] != 0.0; run.p.strain_done = d[2] != 0.0;
     }
     run.p.rs_run = run.p.want_rs && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
+    run.p.ct_run = run.p.want_ct && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.want_report = run.p.full_path && !run.p.report.empty() && run.p.report != "None";
     return 0;
 }
-void rs_skipped(const RunPlan &p) { if (p.want_rs) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rs_path.c_str()); }
+void rs_skipped(const RunPlan &p) {
+    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr})
+        if (f) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", f->c_str());
+}
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
 // ALL species ranges (ranges-only db), counters on the device
 int ingest_local(Run &run, Ingest &in) {
@@ -439,6 +451,8 @@ int route_reads(Run &run, Ingest &in, const Selection &sn, int *unpack_rc) {
 }
 // rows keep (species position in the selection, running number) so that any merge reproduces the one-process order
 struct OutRow { double key; uint32_t k, seq; std::string line; };
+// a row of strain_abundance.txt as the --strain-coverage report follows it: its sort key, its haplotype (into ShardResult::hap_names), its joined genome or null
+struct TrackRow { double key; uint32_t k; uint64_t hap; const GenomeRow *gr; };
 bool write_part(const std::string &path, const std::vector<OutRow> &rows) {
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -484,7 +498,7 @@ int gather_rows(Run &run, std::vector<OutRow> &ori_rows, std::vector<OutRow> &fi
 }
 // ---- a15: abundance_est (profile.rs:3091-3289).  local_rc: this rank's status since the last collective (routing, shard); it travels in the one
 // exchange of the strain level.  Collectives: {failure flag, the two normalisers} (all-reduce), [the barrier behind the part files (all-reduce)].
-int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, int local_rc, std::vector<GenomeRow> &genomes) {
+int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, int local_rc, std::vector<GenomeRow> &genomes, std::vector<TrackRow> &track_rows) {
     const uint32_t Su = (uint32_t)sh.use.size();
     if (local_rc == 0) {
         const std::string err = read_genomes_info(path_join(run.p.db_dir, "genomes_info.txt"), genomes);   // the reference always reads <db>/genomes_info.txt (:3099)
@@ -526,6 +540,7 @@ int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardRe
             for (const GenomeRow *gr : grs) {
                 ori_rows.push_back({0.0, sh.use[k], seq, strain_row_text(species, gr, m, hs ? m.second_sol / sum_all : 0.0, hs, false)});
                 if (pass[h]) final_rows.push_back({m.second_sol / sum_pass, sh.use[k], seq, strain_row_text(species, gr, m, m.second_sol / sum_pass, true, !run.cfg->full)});   // :3250-3284
+                if (pass[h] && run.p.ct_run) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
                 ++seq;
             }
         }
@@ -570,6 +585,34 @@ int read_strains_report(Run &run, const Ingest &in, const ShardResult &sh, const
     run.lap("read strains report");
     return 0;
 }
+// --strain-coverage: the windows of every row of strain_abundance.txt, in its order (the same stable sort on the same keys)
+int cov_track_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, std::vector<TrackRow> &rows) {
+    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });
+    std::ofstream f(run.p.ct_path);
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.ct_path.c_str());
+    f << "species_taxid\tstrain_taxid\tgenome_ID\tstart\tend\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\n";
+    const uint64_t W = run.p.ct_window;
+    for (const TrackRow &r : rows) {
+        const int64_t e = sh.ct_entry[r.hap];
+        if (e < 0) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no coverage track", sh.hap_names[r.hap].c_str());
+        std::string head = in.ranges[sn.sel[sh.use[r.k]]].species;
+        head += '\t'; if (r.gr) head += r.gr->strain_taxid;
+        head += '\t'; if (r.gr) head += r.gr->genome_id;
+        const uint64_t w0 = sh.ct_win_off[e], w1 = sh.ct_win_off[e + 1];
+        uint64_t G = 0;
+        for (uint64_t i = w0; i < w1; ++i) G += sh.ct_len[i];
+        for (uint64_t i = w0; i < w1; ++i) {
+            if (sh.ct_len[i] == 0) continue;   // no node starts here: a longer node runs through
+            const uint64_t start = (i - w0) * W, end = i + 1 == w1 ? G : start + W;   // (only the last window can be cut short: start + W <= G before it)
+            f << head << '\t' << start << '\t' << end << '\t' << sh.ct_n_nodes[i] << '\t' << sh.ct_len[i] << '\t' << sh.ct_covered[i] << '\t' << sh.ct_bases[i] << '\t'
+              << fmt_f64((double)sh.ct_bases[i] / (double)sh.ct_len[i]) << '\t' << fmt_f64((double)sh.ct_covered[i] / (double)sh.ct_len[i]) << '\n';
+        }
+    }
+    f.close();
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.ct_path.c_str());
+    run.lap("strain coverage report");
+    return 0;
+}
 // The phases in order.  `rc` is this rank's status since the last collective (RankComm's rule): PTX_TRY where a phase has ended in the collective
 // that carried it, an assignment where the next collective carries it.
 int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
@@ -612,8 +655,10 @@ int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
         sh = run_shard(run, in, sn, /*use_images=*/false);
     }
     std::vector<GenomeRow> genomes;
-    PTX_TRY(strain_tables(run, in, sn, sh, rc ? rc : sh.rc, genomes));                       // all-reduce: status + normalisers [+ barrier]
-    return p.rs_run ? read_strains_report(run, in, sh, genomes) : 0;
+    std::vector<TrackRow> track_rows;
+    PTX_TRY(strain_tables(run, in, sn, sh, rc ? rc : sh.rc, genomes, track_rows));           // all-reduce: status + normalisers [+ barrier]
+    if (p.rs_run) PTX_TRY(read_strains_report(run, in, sh, genomes));
+    return p.ct_run ? cov_track_report(run, in, sn, sh, track_rows) : 0;
 }
 
 }  // namespace

@@ -18,6 +18,9 @@ static void usage() {
             "  --force  -R <reads_classification.tsv>  --range-file F  --species-len-file F  --reads-binning-file F\n"
             "  --read-strains F   per-read strain report: one row per GAF record (the -R order) with read_id, species_taxid, genome_ID,\n"
             "                     strain_taxid, n_compatible, posterior of the reported strain that contains the read's nodes (one rank only)\n"
+            "  --strain-coverage F   per-strain coverage track: for every row of strain_abundance.txt the windows along its genome with species_taxid,\n"
+            "                     strain_taxid, genome_ID, start, end, n_nodes, len, covered, bases, depth, breadth (a node counts where it starts; one rank only)\n"
+            "  --strain-coverage-window N   its window in bases (default 10000)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -88,6 +91,8 @@ int main(int argc, char **argv) {
         else if (a == "--species-len-file") c.species_len_file = next();
         else if (a == "--reads-binning-file") c.reads_binning_file = next();
         else if (a == "--read-strains") c.read_strain_file = next();
+        else if (a == "--strain-coverage") c.strain_coverage_file = next();
+        else if (a == "--strain-coverage-window") c.strain_coverage_window = atoll(next());
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

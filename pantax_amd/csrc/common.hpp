@@ -434,6 +434,7 @@ struct Db {
     DevBuf<uint32_t> d_sp_chunk_off; // [S+1] first chunk of every species (species without rows: empty range)
     // coverage state (a8), resident for the strain step
     bool cov_done = false;
+    bool cov_stage = false;          // ... left by the stage call pantax_hip_node_coverage (node_base_cov counted into d_cov), not by a resident step: what pantax_hip_strain_cov_track reads
     // d_bases, d_trio_bases, the abort counter and d_bitmap are windows of one arena: one memset per coverage pass
     DevBuf<uint8_t> d_cov_arena;
     unsigned long long *d_abort = nullptr;
@@ -683,6 +684,10 @@ bool use_node_haps(const Ctx *ctx, const Db *db);
 // file order, only the entries of reads binned to a species of db are written
 int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, uint32_t *hap_out,
                         int32_t *n_out, double *post_out);
+// stage_cov_track.hip (pantax_hip_strain_cov_track): selection validated by the caller; win_off_out [C+1] is always written, the four arrays only when the
+// windows fit `cap`
+int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, uint32_t *n_nodes_out,
+                     uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out);
 struct HostReads;
 // stage_gaf.hip: text -> host columns (+ walks unless `resident` is given, which then owns the packed reads in HBM)
 int gaf_tokenize_device(Ctx *ctx, const char *text, uint64_t size, HostReads &out, Reads *resident = nullptr, int fd = -1, uint64_t file_base = 0, bool group = true,

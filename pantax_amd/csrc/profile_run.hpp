@@ -21,7 +21,9 @@ struct RunPlan {
     bool sharded = false;                                               // the ingest is sharded too (an alltoallv callback); W, rk, use_comm: RankComm
     bool full_path = false, strain_only = false, strain_done = false;   // rank 0's look at the work directory, followed by every rank
     bool want_report = false, want_rs = false, rs_run = false;          // rs_run: this call runs a strain step and writes the --read-strains report
-    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, gaf_path;
+    bool want_ct = false, ct_run = false;                               // ct_run: ... and writes the --strain-coverage track
+    uint64_t ct_window = 0;                                             // its window W in bases
+    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, gaf_path;
 };
 // what every phase is handed: the two handles, the plan, the ranks, the trace clock
 struct Run { pantax_hip_ctx *ctx; const pantax_hip_profiling_config *cfg; RunPlan p; RankComm comm; Lap lap; };
@@ -58,9 +60,14 @@ struct ShardResult {
     std::vector<uint64_t> rs_hap;
     std::vector<int32_t> rs_n;
     std::vector<double> rs_post;
+    // --strain-coverage: the windows of every haplotype among the rows of strain_abundance.txt, group after group.  ct_entry[h] = its entry or -1 ([hap_names]);
+    // entry e owns the windows [ct_win_off[e], ct_win_off[e + 1]) of the four arrays
+    std::vector<int64_t> ct_entry;
+    std::vector<uint64_t> ct_win_off{0}, ct_len, ct_covered, ct_bases;
+    std::vector<uint32_t> ct_n_nodes;
     bool image_fault = false;          // rc is the load-time refusal of a group that holds images ...
     std::string fault_images;          // ... these (the check names a haplotype, not a file), for the warning
 };
-// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, image write-back)
+// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, image write-back)
 ShardResult run_shard(Run &run, Ingest &in, const Selection &sn, bool use_images);
 }  // namespace ptx

@@ -1,5 +1,5 @@
 // profile_shard.cpp -- run_shard (profile_run.hpp): a6 - a14 of the file seam for this rank's selected species.  Where every graph comes from
-// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains per group, image write-back.
+// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains and the strain coverage track per group, image write-back.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -108,16 +108,19 @@ int start_load(pantax_hip_ctx *ctx, const int64_t *g_rs, const int64_t *g_re, co
     });
     return 0;
 }
-// --read-strains for the species [k0, k1) of the db that has just gone through its strain step
-int group_read_strains(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
+// this group's rows of strain_abundance.txt as bits over the shard's haplotypes: the a15 filter is row-local, so the group decides it in its own turn
+int group_pass_bits(Run &run, uint32_t k0, uint32_t k1, const ShardResult &sh, std::vector<uint8_t> &pass_g) {
     const uint32_t Sg = k1 - k0;
-    const uint64_t R = in.R;
-    // the candidates are this group's rows of strain_abundance.txt: the a15 filter is row-local, so the group decides it in its own turn
     std::vector<uint8_t> rep_g(Sg);
     for (uint32_t k = k0; k < k1; ++k) rep_g[k - k0] = (sh.info[k].status1 == 0 && sh.info[k].status2 == 0) ? 1 : 0;
-    std::vector<uint8_t> pass_g(sh.hap_names.size() ? sh.hap_names.size() : 1, 0);
-    PTX_TRY(pantax_hip_abundance_filter(Sg, sh.hap_off.data() + k0, sh.met.data(), rep_g.data(), run.cfg->single_cov_diff, run.cfg->min_cov, pass_g.data(),
-                                        nullptr, nullptr, nullptr, nullptr));
+    pass_g.assign(sh.hap_names.size() ? sh.hap_names.size() : 1, 0);
+    return pantax_hip_abundance_filter(Sg, sh.hap_off.data() + k0, sh.met.data(), rep_g.data(), run.cfg->single_cov_diff, run.cfg->min_cov, pass_g.data(),
+                                       nullptr, nullptr, nullptr, nullptr);
+}
+// --read-strains for the species [k0, k1) of the db that has just gone through its strain step; the candidates are the group's rows (pass_g)
+int group_read_strains(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
+    const uint32_t Sg = k1 - k0;
+    const uint64_t R = in.R;
     std::vector<uint64_t> c_off(Sg + 1, 0);
     std::vector<uint32_t> c_hap;
     std::vector<double> c_w;
@@ -143,6 +146,28 @@ int group_read_strains(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k
         sh.rs_hap[r] = t_n[r] > 0 && g_sp[r] >= 0 ? sh.hap_off[k0 + (uint32_t)g_sp[r]] + t_hap[r] : ~0ull;
     }
     run.lap("  read strains");
+    return 0;
+}
+// --strain-coverage for the same species, while the coverage result of the group is still on the device: the windows of the group's rows (pass_g)
+int group_cov_track(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint64_t> s_off(Sg + 1, 0);
+    std::vector<uint32_t> s_hap;
+    const size_t entry0 = sh.ct_win_off.size() - 1;   // entries of the groups before
+    for (uint32_t k = k0; k < k1; ++k) {
+        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
+            if (pass_g[h]) { sh.ct_entry[h] = (int64_t)(entry0 + s_hap.size()); s_hap.push_back((uint32_t)(h - sh.hap_off[k])); }
+        s_off[k - k0 + 1] = s_hap.size();
+    }
+    const pantax_hip_cov_track_set set{Sg, s_off.data(), s_hap.data(), run.p.ct_window};
+    std::vector<uint64_t> w_off(s_hap.size() + 1, 0);
+    const int rc_size = pantax_hip_strain_cov_track(run.ctx, db, &set, w_off.data(), 0, nullptr, nullptr, nullptr, nullptr);   // sizes: E_LIMIT unless there is no window
+    if (rc_size != 0 && rc_size != PANTAX_HIP_E_LIMIT) return rc_size;
+    const uint64_t n = w_off[s_hap.size()], at = sh.ct_len.size();
+    sh.ct_n_nodes.resize(at + n); sh.ct_len.resize(at + n); sh.ct_covered.resize(at + n); sh.ct_bases.resize(at + n);
+    if (n) PTX_TRY(pantax_hip_strain_cov_track(run.ctx, db, &set, w_off.data(), n, sh.ct_n_nodes.data() + at, sh.ct_len.data() + at, sh.ct_covered.data() + at, sh.ct_bases.data() + at));
+    for (size_t e = 0; e < s_hap.size(); ++e) sh.ct_win_off.push_back(at + w_off[e + 1]);
+    run.lap("  strain coverage track");
     return 0;
 }
 // one pass: sources, parts, groups; per group the loader hand-over, then binning against the selected ranges, index, coverage, strain step
@@ -191,6 +216,7 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
         sh.hap_off[k + 1] = sh.hap_names.size();
     }
     sh.met.resize(sh.hap_names.size());
+    if (run.p.ct_run) sh.ct_entry.assign(sh.hap_names.size(), -1);
     const std::vector<Group> groups = make_groups(run.ctx, parts);
     const bool piped = groups.size() > 1;
     if (piped && !run.ctx->stream_up) PTX_HIP(run.ctx, hipStreamCreateWithFlags(&run.ctx->stream_up, hipStreamNonBlocking));
@@ -235,7 +261,12 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
                                     run.cfg->sample_test ? 500 : run.cfg->sample_nodes, run.cfg->solver_semantics};
         PTX_TRY(pantax_hip_strain_profile(run.ctx, db, &sc, nullptr, cov.data() + k0, sh.met.data() + sh.hap_off[k0], sh.info.data() + k0));
         run.lap("strain step");
-        if (run.p.rs_run) PTX_TRY(group_read_strains(run, in, db, k0, k1, sh));
+        if (run.p.rs_run || run.p.ct_run) {   // the two reports on the group's rows of the strain table, decided once
+            std::vector<uint8_t> pass_g;
+            PTX_TRY(group_pass_bits(run, k0, k1, sh, pass_g));
+            if (run.p.rs_run) PTX_TRY(group_read_strains(run, in, db, k0, k1, pass_g, sh));
+            if (run.p.ct_run) PTX_TRY(group_cov_track(run, db, k0, k1, pass_g, sh));
+        }
         if (run.cfg->image_cache == 2) {   // leave images behind for the next run
             for (uint32_t k = k0; k < k1; ++k)
                 if (src[sh.use[k]].kind != 1) {

@@ -768,6 +768,7 @@ int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool w
     if (!db->cov_prepared) PTX_TRY(coverage_prepare(ctx, db, rd, with_trio));
     lap("arena + zero fill");
     db->cov_prepared = false;
+    db->cov_stage = false;         // (pantax_hip_node_coverage sets it behind its own pass)
     db->trio_free_valid = false;   // a reader of the unique-trio tables goes onto the stream: the event of an earlier strain step no longer covers them
     const bool trio = with_trio && db->U;
     const uint8_t *d_act_fast = d_active;

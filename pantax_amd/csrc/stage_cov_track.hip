@@ -1,0 +1,253 @@
+// stage_cov_track.hip -- per-strain windowed coverage track (pantax_hip_strain_cov_track, the --strain-coverage report): coverage along the genome of
+// selected haplotypes, from what the coverage pass leaves in HBM.  Not a stage of the reference.
+//
+// Contract (include/pantax_hip.h, DESIGN.md "Per-strain coverage track"): along the walk v_0 .. v_{n-1} of a haplotype, step i starts at the path offset
+// o_i = sum_{j<i} node_len[v_j] (u64) and belongs to window w_i = o_i / W -- the window of the node's FIRST base; a node is never cut.  Per window:
+// the number of steps, and the sums of node_len, node_base_cov and bases_per_node over them.  Integers only: the result does not depend on any order.
+//
+// A selected walk is cut into tiles at the multiples of CT_TILE path positions (so a lane's quads of node ids are 16-byte aligned); a wave per tile,
+// 16 consecutive positions per lane.
+//   cov_track_len_kernel    the summed node length of every tile.  The host scans the sums per haplotype: base offset of every tile, G_h, n_win.
+//   cov_track_accum_kernel  o_i from the lane's own 16 lengths on top of the DPP scan of the lane sums on top of the tile base.  Window ids do not
+//                           decrease along a walk: a lane folds its positions into runs of equal id, adds the runs that END inside it to the output
+//                           itself, and hands its last run to a segmented DPP scan over the lanes (a lane opens a segment when its first window is
+//                           not its predecessor's last, or when it closed a run itself).  The last lane of a segment adds the segment's sums: one
+//                           64-bit atomic per (wave, window) and quantity wherever windows are longer than a lane's 16 nodes.
+//
+// Algorithmic bytes (P_sel selected path positions, n_win windows):
+//   4 P_sel (node ids) + 4 P_sel (lengths)                  cov_track_len_kernel
+//   4 P_sel (node ids) + (4 + 4 + 8) P_sel (len, cov, bases)  cov_track_accum_kernel
+//   28 n_win                                                 the four output arrays (zero fill, atomics, download)
+#include <algorithm>
+#include "common.hpp"
+#include "primitives.hpp"
+#include "wave.hpp"
+
+namespace ptx {
+
+namespace {
+
+constexpr uint64_t CT_TILE = 1024;   // path positions per tile: 64 lanes x 16
+
+struct CtTile { uint64_t p0; uint32_t n, node_base; };        // global path positions [p0, p0 + n), inside one aligned block of CT_TILE; first global node of the species
+struct CtTileOut { uint64_t base, out0, n_win; };             // o of position p0; first output window of the haplotype; its number of windows
+
+// the global node indices of the lane's 16 positions q0 .. q0 + 15 (q0 a multiple of 16); bit j of the result: position j lies in [lo, hi).
+// A dead position names the node of position `lo`: every gather below stays inside its array, its value is dropped by a select.
+__device__ __forceinline__ uint32_t ct_load_ids(const uint32_t *__restrict__ path_nodes, uint64_t q0, uint64_t lo, uint64_t hi, uint32_t node_base, uint32_t (&v)[16]) {
+    uint32_t live = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint64_t q = q0 + 4u * k;
+        if ((q >= lo) & (q + 4 <= hi)) {   // a quad inside the tile: one 16-byte load (false only in the first and last lane of a walk)
+            const uint4 x = *reinterpret_cast<const uint4 *>(path_nodes + q);
+            v[4 * k] = x.x; v[4 * k + 1] = x.y; v[4 * k + 2] = x.z; v[4 * k + 3] = x.w;
+            live |= 0xFu << (4 * k);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint64_t pos = q + e;
+                const bool in = (pos >= lo) & (pos < hi);
+                v[4 * k + e] = path_nodes[in ? pos : lo];
+                live |= (in ? 1u : 0u) << (4 * k + e);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] += node_base;
+    return live;
+}
+
+__global__ void __launch_bounds__(256) cov_track_len_kernel(uint32_t n_tiles, const CtTile *__restrict__ tiles, const uint32_t *__restrict__ path_nodes,
+                                                            const uint32_t *__restrict__ node_len, unsigned long long *__restrict__ tile_sum) {
+    const int lane = threadIdx.x & 63;
+    for (uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * 4) {
+        const CtTile tl = tiles[t];
+        uint32_t v[16];
+        const uint32_t live = ct_load_ids(path_nodes, (tl.p0 & ~(CT_TILE - 1)) + 16u * (uint32_t)lane, tl.p0, tl.p0 + tl.n, tl.node_base, v);
+        unsigned long long s = 0ull;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) { const uint32_t l = node_len[v[j]]; s += ((live >> j) & 1u) ? l : 0u; }
+        s = wave_reduce(s, [](unsigned long long a, unsigned long long b) { return a + b; });
+        if (lane == 0) tile_sum[t] = s;
+    }
+}
+
+// inclusive prefix sum of a 64-bit value over the 64 lanes (the steps of wave_incl_scan_dpp, wave.hpp, on both halves)
+__device__ __forceinline__ unsigned long long ct_incl_scan64(unsigned long long v) {
+#define CT_STEP(CTRL, RM, BC)                                                                                        \
+    {                                                                                                                \
+        const uint32_t tl = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, RM, 0xF, BC);           \
+        const uint32_t th = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, RM, 0xF, BC);   \
+        v += ((unsigned long long)th << 32) | tl;                                                                    \
+    }
+    CT_STEP(0x111, 0xF, true) CT_STEP(0x112, 0xF, true) CT_STEP(0x114, 0xF, true) CT_STEP(0x118, 0xF, true)
+    CT_STEP(0x142, 0xA, false) CT_STEP(0x143, 0xC, false)
+#undef CT_STEP
+    return v;
+}
+
+// the four sums of a run of steps of one window
+struct CtAcc { uint32_t n; unsigned long long len, cov, bases; };
+
+// inclusive sum over the lanes [seg, lane] (seg <= lane: the first lane of my segment); all 64 lanes active.  The steps of seg_and (stage_read_strain.hip):
+// a lane takes a value only from a source lane of its own segment; lanes a row operation does not reach read zero.
+__device__ __forceinline__ void ct_seg_scan(CtAcc &a, int lane, int seg) {
+#define CT_MOVE(x, CTRL, RM, BC) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), CTRL, RM, 0xF, BC))
+#define CT_STEP(CTRL, RM, BC, SRC)                                                                                                             \
+    {                                                                                                                                          \
+        const uint32_t tn = CT_MOVE(a.n, CTRL, RM, BC);                                                                                        \
+        const unsigned long long tlen = ((unsigned long long)CT_MOVE((uint32_t)(a.len >> 32), CTRL, RM, BC) << 32) | CT_MOVE((uint32_t)a.len, CTRL, RM, BC);       \
+        const unsigned long long tcov = ((unsigned long long)CT_MOVE((uint32_t)(a.cov >> 32), CTRL, RM, BC) << 32) | CT_MOVE((uint32_t)a.cov, CTRL, RM, BC);       \
+        const unsigned long long tbas = ((unsigned long long)CT_MOVE((uint32_t)(a.bases >> 32), CTRL, RM, BC) << 32) | CT_MOVE((uint32_t)a.bases, CTRL, RM, BC);   \
+        const bool take = (SRC) >= seg;                                                                                                        \
+        a.n += take ? tn : 0u; a.len += take ? tlen : 0ull; a.cov += take ? tcov : 0ull; a.bases += take ? tbas : 0ull;                        \
+    }
+    CT_STEP(0x111, 0xF, true, lane - 1)
+    CT_STEP(0x112, 0xF, true, lane - 2)
+    CT_STEP(0x114, 0xF, true, lane - 4)
+    CT_STEP(0x118, 0xF, true, lane - 8)
+    CT_STEP(0x142, 0xA, false, (lane & ~15) - 1)   // rows 1 and 3 <- lanes 15 and 47
+    CT_STEP(0x143, 0xC, false, 31)                 // rows 2 and 3 <- lane 31
+#undef CT_STEP
+#undef CT_MOVE
+}
+
+struct CtOut { uint32_t *n; unsigned long long *len, *cov, *bases; };
+
+// window w of the haplotype whose windows start at out0; guarded by the haplotype's window count (a live step always lies below it: node lengths are > 0)
+__device__ __forceinline__ void ct_add(const CtOut &o, uint64_t out0, uint64_t n_win, bool on, uint64_t w, const CtAcc &a) {
+    if (on & (w < n_win)) {
+        const uint64_t i = out0 + w;
+        atomicAdd(o.n + i, a.n); atomicAdd(o.len + i, a.len); atomicAdd(o.cov + i, a.cov); atomicAdd(o.bases + i, a.bases);
+    }
+}
+
+__global__ void __launch_bounds__(256) cov_track_accum_kernel(uint32_t n_tiles, const CtTile *__restrict__ tiles, const CtTileOut *__restrict__ touts,
+                                                              const uint32_t *__restrict__ path_nodes, const uint32_t *__restrict__ node_len,
+                                                              const uint32_t *__restrict__ cov, const unsigned long long *__restrict__ bases, uint64_t W, CtOut out) {
+    const int lane = threadIdx.x & 63;
+    for (uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * 4) {
+        const CtTile tl = tiles[t];
+        const CtTileOut to = touts[t];
+        uint32_t v[16], len[16], cv[16];
+        unsigned long long bs[16];
+        const uint32_t live = ct_load_ids(path_nodes, (tl.p0 & ~(CT_TILE - 1)) + 16u * (uint32_t)lane, tl.p0, tl.p0 + tl.n, tl.node_base, v);
+        unsigned long long lane_sum = 0ull;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const bool on = (live >> j) & 1u;
+            const uint32_t l = node_len[v[j]], c = cov[v[j]];
+            const unsigned long long b = bases[v[j]];
+            len[j] = on ? l : 0u; cv[j] = on ? c : 0u; bs[j] = on ? b : 0ull;
+            lane_sum += len[j];
+        }
+        const uint64_t o0 = to.base + (ct_incl_scan64(lane_sum) - lane_sum);   // path offset of the lane's first position
+        // the window of the running position: one division per lane, another only where a step leaves its window
+        uint64_t w = o0 / W, rem = o0 - w * W;
+        uint64_t w_first = 0, w_cur = 0;
+        bool have = false, closed = false;
+        CtAcc acc{0u, 0ull, 0ull, 0ull};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const bool on = (live >> j) & 1u;
+            if (on & have & (w != w_cur)) {   // the run before this step ends inside the lane
+                ct_add(out, to.out0, to.n_win, true, w_cur, acc);
+                acc = CtAcc{0u, 0ull, 0ull, 0ull};
+                closed = true;
+            }
+            w_first = (on & !have) ? w : w_first;
+            w_cur = on ? w : w_cur;
+            have = have | on;
+            acc.n += on ? 1u : 0u; acc.len += len[j]; acc.cov += cv[j]; acc.bases += bs[j];
+            rem += len[j];
+            if (rem >= W) { const uint64_t k = rem / W; w += k; rem -= k * W; }
+        }
+        // the lane's last run goes on over the lanes that follow: a lane opens a segment unless it is the plain continuation of its predecessor's run
+        const uint32_t p_lo = wave_shr1((uint32_t)w_cur), p_hi = wave_shr1((uint32_t)(w_cur >> 32)), p_have = wave_shr1(have ? 1u : 0u);
+        const uint64_t w_prev = ((uint64_t)p_hi << 32) | p_lo;
+        const bool head = (lane == 0) | !have | (p_have == 0u) | closed | (w_first != w_prev);
+        const unsigned long long heads = __builtin_amdgcn_ballot_w64(head);
+        const int seg = 63 - __builtin_clzll(heads & (~0ull >> (63 - lane)));   // (bit 0 is always set)
+        ct_seg_scan(acc, lane, seg);
+        const bool last = have & ((lane == 63) | (((heads >> 1) >> lane) & 1ull));   // the segment ends here: among live lanes only
+        ct_add(out, to.out0, to.n_win, last, w_cur, acc);
+    }
+}
+
+}  // namespace
+
+// sel_off [S+1], sel_hap validated by the caller (in range, no repeats).  win_off_out [C+1] is always written; more than `cap` windows: PANTAX_HIP_E_LIMIT
+// and nothing else is touched.
+int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, uint32_t *n_nodes_out,
+                     uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out) {
+    const uint32_t S = db->S;
+    const uint64_t C = sel_off[S];
+    std::vector<CtTile> tiles;
+    std::vector<uint64_t> tile_first(C + 1, 0);   // first tile of every selected haplotype
+    for (uint32_t s = 0; s < S; ++s)
+        for (uint64_t c = sel_off[s]; c < sel_off[s + 1]; ++c) {
+            const uint64_t h = db->h_hap_off[s] + sel_hap[c], p1 = db->h_path_off[h + 1];
+            for (uint64_t p = db->h_path_off[h]; p < p1;) {
+                const uint64_t e = std::min(p1, (p & ~(CT_TILE - 1)) + CT_TILE);
+                tiles.push_back(CtTile{p, (uint32_t)(e - p), (uint32_t)db->h_node_off[s]});
+                p = e;
+            }
+            tile_first[c + 1] = tiles.size();
+        }
+    if (tiles.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_cov_track: %llu tiles of selected walks exceed 32-bit positions", (unsigned long long)tiles.size());
+    const uint32_t n_tiles = (uint32_t)tiles.size();
+    DevBuf<CtTile> d_tiles;
+    DevBuf<unsigned long long> d_sum;
+    std::vector<unsigned long long> sums(n_tiles);
+    if (n_tiles) {
+        PTX_TRY(upload(ctx, d_tiles, tiles.data(), tiles.size()));
+        PTX_HIP(ctx, d_sum.alloc(n_tiles));
+        {
+            KTimer tm(ctx, "cov_track_len_kernel");
+            hipLaunchKernelGGL(cov_track_len_kernel, dim3(grid_for(n_tiles, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_tiles, d_tiles.p, db->d_path_nodes.p,
+                               db->d_node_len.p, d_sum.p);
+        }
+        PTX_HIP(ctx, hipGetLastError());
+        PTX_TRY(download(ctx, sums.data(), d_sum.p, n_tiles));
+        PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // per haplotype: the exclusive scan of its tiles' sums, its length, its windows
+    std::vector<CtTileOut> touts(n_tiles);
+    win_off_out[0] = 0;
+    for (uint64_t c = 0; c < C; ++c) {
+        uint64_t g = 0;
+        for (uint64_t t = tile_first[c]; t < tile_first[c + 1]; ++t) { touts[t].base = g; g += sums[t]; }
+        const uint64_t n_win = g / W + (g % W ? 1 : 0);
+        for (uint64_t t = tile_first[c]; t < tile_first[c + 1]; ++t) { touts[t].out0 = win_off_out[c]; touts[t].n_win = n_win; }
+        win_off_out[c + 1] = win_off_out[c] + n_win;
+    }
+    const uint64_t N = win_off_out[C];
+    if (N > cap) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_cov_track: the selection has %llu windows, the output arrays hold %llu (win_off_out is filled: size the arrays by it)",
+                             (unsigned long long)N, (unsigned long long)cap);
+    if (N == 0) return 0;
+    if (!n_nodes_out || !len_out || !covered_out || !bases_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: null output array");
+    if (N > (~(size_t)0) / 32) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_cov_track: %llu windows", (unsigned long long)N);
+    // one device block, zero-filled once: [len N u64][covered N u64][bases N u64][n_nodes N u32]
+    DevBuf<uint8_t> d_out;
+    DevBuf<CtTileOut> d_touts;
+    PTX_HIP(ctx, d_out.alloc((size_t)N * 28));
+    PTX_TRY(zero_fill(ctx, d_out.p, (size_t)N * 28));
+    PTX_TRY(upload(ctx, d_touts, touts.data(), touts.size()));
+    unsigned long long *o64 = reinterpret_cast<unsigned long long *>(d_out.p);
+    const CtOut out{reinterpret_cast<uint32_t *>(o64 + 3 * N), o64, o64 + N, o64 + 2 * N};
+    {
+        KTimer tm(ctx, "cov_track_accum_kernel");
+        hipLaunchKernelGGL(cov_track_accum_kernel, dim3(grid_for(n_tiles, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_tiles, d_tiles.p, d_touts.p,
+                           db->d_path_nodes.p, db->d_node_len.p, db->d_cov.p, db->d_bases.p, W, out);
+    }
+    PTX_HIP(ctx, hipGetLastError());
+    PTX_TRY(download(ctx, (unsigned long long *)len_out, out.len, N));
+    PTX_TRY(download(ctx, (unsigned long long *)covered_out, out.cov, N));
+    PTX_TRY(download(ctx, (unsigned long long *)bases_out, out.bases, N));
+    PTX_TRY(download(ctx, n_nodes_out, out.n, N));
+    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host arrays are filled, the temporaries are released on return
+    return 0;
+}
+
+}  // namespace ptx

@@ -320,6 +320,26 @@ class Engine:
         self._check(self.lib.pantax_hip_read_strains(self.ctx, self.db, self.reads, C.byref(cs), p(hap), p(n), p(post)))
         return hap, n, post
 
+    def strain_cov_track(self, sel_off, sel_hap, window):
+        """Per-strain windowed coverage track (pantax_hip_strain_cov_track) of the coverage result get_node_abundances left on the device.
+        sel_off [S+1], sel_hap (species-local haplotype indices, no repeats within a species), window W >= 1 in bases ->
+        (win_off uint64 [C+1], n_nodes uint32, len, covered, bases uint64): the windows of selection entry c are [win_off[c], win_off[c+1])."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("strain_cov_track: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        cs = _ffi.CovTrackSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, int(window))
+        win_off = np.zeros(len(sh) + 1, dtype=np.uint64)
+        rc = self.lib.pantax_hip_strain_cov_track(self.ctx, self.db, C.byref(cs), p(win_off), 0, None, None, None, None)   # sizes the arrays
+        if rc != _ffi.E_LIMIT:
+            self._check(rc)
+        n = int(win_off[-1])
+        n_nodes = np.zeros(n, dtype=np.uint32)
+        ln, covered, bases = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        if n:
+            self._check(self.lib.pantax_hip_strain_cov_track(self.ctx, self.db, C.byref(cs), p(win_off), n, p(n_nodes), p(ln), p(covered), p(bases)))
+        return win_off, n_nodes, ln, covered, bases
+
     def trio_nodes_info(self, fetch=True):
         n = C.c_uint64(0)
         self._check(self.lib.pantax_hip_trio_index(self.ctx, self.db, C.byref(n)))
@@ -473,11 +493,13 @@ class Engine:
                 min_species_abundance=1e-4, min_cov=0, min_depth=0, shift=False, filtered=True, full=True, force=False,
                 mode=2, sample_nodes=0, designated_species=None, zip="serialize", out_binning_file=None,
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
-                allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None):
+                allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
+                strain_coverage_file=None, strain_coverage_window=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
-        (--read-strains; one rank only)."""
+        (--read-strains; one rank only).  strain_coverage_file: path of the per-strain windowed coverage track (--strain-coverage; one rank
+        only), strain_coverage_window its window in bases (0: 10000)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -488,7 +510,8 @@ class Engine:
             filtered=int(filtered), full=int(full), force=int(force), mode=mode, sample_nodes=sample_nodes,
             designated_species=enc(designated_species), zip=enc(zip), rank=int(rank), world_size=int(world_size),
             image_cache=int(image_cache), sample_test=int(sample_test), solver_semantics=int(solver_semantics),
-            minimization_min_cov=float(minimization_min_cov), read_strain_file=enc(read_strain_file))
+            minimization_min_cov=float(minimization_min_cov), read_strain_file=enc(read_strain_file),
+            strain_coverage_file=enc(strain_coverage_file), strain_coverage_window=int(strain_coverage_window))
         cb = None
         if allreduce is not None:   # allreduce(np.ndarray float64) sums it in place over the ranks
             def _cb(_user, buf, n):
