@@ -247,6 +247,31 @@ int pantax_hip_strain_cov_track(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
                                 uint64_t *win_off_out /*[C+1]*/, uint64_t cap /* windows the four arrays hold */,
                                 uint32_t *n_nodes_out, uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out);
 
+/* ---- per-strain node evidence (the --strain-evidence report; not a stage of the reference): what in the sample separates a selected haplotype from
+ * the other selected haplotypes of its species, and the coverage of the species that no selected haplotype explains, from what pantax_hip_node_coverage
+ * leaves on the device.  For a species s of the db, Sel_s = its selected species-local haplotype indices, K_s = |Sel_s|.  Every node v of s is counted
+ * once, whether or not any walk visits it:
+ *   M(v) = { h in Sel_s : the walk of h visits v at least once } -- node-level membership, the 0/1 matrix of the LP (profile.rs:1333-1342): a node
+ *          walked twice by h counts once (the coverage track above counts visits);   m(v) = |M(v)|;
+ *   Q(v) = (1, node_len[v], node_base_cov[v], bases_per_node[v]), the last two as pantax_hip_node_coverage hands them out; all four u64.
+ * Every output is a sum of Q(v), its four numbers in the order { n_nodes, len, covered, bases }:
+ *   per selection entry c (haplotype h of species s):   all[c] = sum over v with h in M(v);   private[c] = sum over v with M(v) = {h};
+ *   per species s:   total[s] = sum over every node;   orphan[s] = sum over m(v) = 0;   core[s] = sum over m(v) = K_s when K_s >= 1, four zeros when K_s = 0.
+ * Integers only: results are exact and independent of any order.
+ * hap_out [C][2][4] = { all, private } of every selection entry in the order of sel_hap; species_out [S][3][4] = { total, orphan, core } of every species.
+ * The caller knows both sizes: there is no sizing call.  An empty selection, or a species without selected haplotypes, is fine: total and orphan are
+ * written for every species.  State rules of pantax_hip_strain_cov_track: the db must hold the coverage result of a pantax_hip_node_coverage call (a
+ * pantax_hip_strain_profile behind it changes nothing); behind a resident step (pantax_hip_profile_step / _enqueue), and before any coverage pass, the
+ * call returns PANTAX_HIP_E_STATE and says why.  PANTAX_HIP_E_INVALID: n_species different from the db's, a haplotype index out of range, a haplotype
+ * twice within a species. */
+typedef struct {
+    uint32_t n_species;       /* must equal the db's */
+    const uint64_t *sel_off;  /* [S+1] species s owns the selection entries [sel_off[s], sel_off[s+1]) */
+    const uint32_t *sel_hap;  /* [C] species-local haplotype index, any order, no repeats within a species */
+} pantax_hip_evidence_set;
+int pantax_hip_strain_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel,
+                               uint64_t *hap_out /*[C][2][4]: all, private*/, uint64_t *species_out /*[S][3][4]: total, orphan, core*/);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -440,6 +465,15 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
      * that performs the strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID (rows would have to be joined across ranks). */
     const char *strain_coverage_file;
     int64_t strain_coverage_window; /* --strain-coverage-window: W in bases; 0 = the default of 10000; negative: PANTAX_HIP_E_INVALID */
+    /* --strain-evidence: path of the per-strain node evidence report (pantax_hip_strain_evidence over every group of species, right behind the group's
+     * strain step; Sel_s = the species' rows of strain_abundance.txt; NULL or "None" = off).  TSV with a header, long format:
+     * species_taxid, strain_taxid, genome_ID, class, n_nodes, len, covered, bases, depth = bases / len, breadth = covered / len (f64, shortest round-trip
+     * digits; "-" when len = 0), predicted_coverage.  First the strains in the order of strain_abundance.txt, classes "all" then "private" each
+     * (predicted_coverage = the unrounded second_sol); then every species that went through a strain step, in the order the run took them (the order of
+     * species_abundance.txt among the selected species), classes "total", "orphan", "core" with strain_taxid = genome_ID = "-"; "core" is left
+     * out for a species without rows; predicted_coverage is "-" on total and orphan, and on core the f64 sum of the species' reported strains in
+     * ascending haplotype index.  Written only by a run that performs the strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
+    const char *strain_evidence_file;
 } pantax_hip_profiling_config;
 
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in

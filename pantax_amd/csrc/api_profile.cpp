@@ -61,6 +61,12 @@ int check_args(Run &run) {
                     p.sharded ? ", sharded" : "");
     if (p.want_ct && cfg->strain_coverage_window < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "profile: strain_coverage_window %lld", (long long)cfg->strain_coverage_window);
     p.ct_window = p.want_ct && cfg->strain_coverage_window > 0 ? (uint64_t)cfg->strain_coverage_window : 10000;
+    // --strain-evidence: the same again -- a species' sums live on the rank that owns it
+    p.ev_path = opt(cfg->strain_evidence_file);
+    p.want_ev = !p.ev_path.empty() && p.ev_path != "None";
+    if (p.want_ev && (W > 1 || p.sharded))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain node evidence report (strain_evidence_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
+                    p.sharded ? ", sharded" : "");
     p.db_dir = opt(cfg->db); p.wd = opt(cfg->wd); p.out_dir = opt(cfg->output_dir);
     if (p.out_dir.empty()) p.out_dir = p.wd;
     if (!is_dir(p.db_dir)) return fail(ctx, PANTAX_HIP_E_IO, "Specified PanTax database directory '%s' is not a valid directory path", p.db_dir.c_str());
@@ -89,11 +95,12 @@ int decide_resume(Run &run) {
     }
     run.p.rs_run = run.p.want_rs && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.ct_run = run.p.want_ct && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
+    run.p.ev_run = run.p.want_ev && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.want_report = run.p.full_path && !run.p.report.empty() && run.p.report != "None";
     return 0;
 }
 void rs_skipped(const RunPlan &p) {
-    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr})
+    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr, p.want_ev ? &p.ev_path : nullptr})
         if (f) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", f->c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
@@ -451,7 +458,7 @@ int route_reads(Run &run, Ingest &in, const Selection &sn, int *unpack_rc) {
 }
 // rows keep (species position in the selection, running number) so that any merge reproduces the one-process order
 struct OutRow { double key; uint32_t k, seq; std::string line; };
-// a row of strain_abundance.txt as the --strain-coverage report follows it: its sort key, its haplotype (into ShardResult::hap_names), its joined genome or null
+// a row of strain_abundance.txt as the --strain-coverage and --strain-evidence reports follow it: its sort key, its haplotype (into ShardResult::hap_names), its joined genome or null
 struct TrackRow { double key; uint32_t k; uint64_t hap; const GenomeRow *gr; };
 bool write_part(const std::string &path, const std::vector<OutRow> &rows) {
     FILE *f = std::fopen(path.c_str(), "wb");
@@ -540,7 +547,7 @@ int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardRe
             for (const GenomeRow *gr : grs) {
                 ori_rows.push_back({0.0, sh.use[k], seq, strain_row_text(species, gr, m, hs ? m.second_sol / sum_all : 0.0, hs, false)});
                 if (pass[h]) final_rows.push_back({m.second_sol / sum_pass, sh.use[k], seq, strain_row_text(species, gr, m, m.second_sol / sum_pass, true, !run.cfg->full)});   // :3250-3284
-                if (pass[h] && run.p.ct_run) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
+                if (pass[h] && (run.p.ct_run || run.p.ev_run)) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
                 ++seq;
             }
         }
@@ -613,6 +620,45 @@ int cov_track_report(Run &run, const Ingest &in, const Selection &sn, const Shar
     run.lap("strain coverage report");
     return 0;
 }
+// --strain-evidence: {all, private} of every row of strain_abundance.txt, in its order (the same stable sort on the same keys), then {total, orphan, core}
+// of every species of the shard in the order it went through the device (the selection's: the species table's)
+int evidence_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, std::vector<TrackRow> &rows) {
+    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });
+    std::ofstream f(run.p.ev_path);
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.ev_path.c_str());
+    f << "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\tpredicted_coverage\n";
+    const auto put = [&f](const std::string &head, const char *cls, const uint64_t *q, const std::string &pc) {   // q = {n_nodes, len, covered, bases}
+        f << head << '\t' << cls << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << q[3] << '\t';
+        if (q[1]) f << fmt_f64((double)q[3] / (double)q[1]) << '\t' << fmt_f64((double)q[2] / (double)q[1]);
+        else f << "-\t-";
+        f << '\t' << pc << '\n';
+    };
+    for (const TrackRow &r : rows) {
+        const int64_t e = sh.ev_entry[r.hap];
+        if (e < 0) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no node evidence", sh.hap_names[r.hap].c_str());
+        std::string head = in.ranges[sn.sel[sh.use[r.k]]].species;
+        head += '\t'; if (r.gr) head += r.gr->strain_taxid;
+        head += '\t'; if (r.gr) head += r.gr->genome_id;
+        const std::string pc = fmt_f64(sh.met[r.hap].second_sol);
+        put(head, "all", sh.ev_hap.data() + 8 * e, pc);
+        put(head, "private", sh.ev_hap.data() + 8 * e + 4, pc);
+    }
+    for (uint32_t k = 0; k < (uint32_t)sh.use.size(); ++k) {
+        const std::string head = in.ranges[sn.sel[sh.use[k]]].species + "\t-\t-";
+        const uint64_t *q = sh.ev_species.data() + 12 * (size_t)k;
+        put(head, "total", q, "-");
+        put(head, "orphan", q + 4, "-");
+        double pc = 0.0;
+        bool any = false;
+        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
+            if (sh.ev_entry[h] >= 0) { pc += sh.met[h].second_sol; any = true; }
+        if (any) put(head, "core", q + 8, fmt_f64(pc));
+    }
+    f.close();
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.ev_path.c_str());
+    run.lap("strain evidence report");
+    return 0;
+}
 // The phases in order.  `rc` is this rank's status since the last collective (RankComm's rule): PTX_TRY where a phase has ended in the collective
 // that carried it, an assignment where the next collective carries it.
 int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
@@ -658,7 +704,8 @@ int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
     std::vector<TrackRow> track_rows;
     PTX_TRY(strain_tables(run, in, sn, sh, rc ? rc : sh.rc, genomes, track_rows));           // all-reduce: status + normalisers [+ barrier]
     if (p.rs_run) PTX_TRY(read_strains_report(run, in, sh, genomes));
-    return p.ct_run ? cov_track_report(run, in, sn, sh, track_rows) : 0;
+    if (p.ct_run) PTX_TRY(cov_track_report(run, in, sn, sh, track_rows));
+    return p.ev_run ? evidence_report(run, in, sn, sh, track_rows) : 0;
 }
 
 }  // namespace

@@ -498,38 +498,63 @@ int pantax_hip_read_strains(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_r
     return read_strains_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), hap_out, n_out, post_out);
 }
 
+// what the two node reports behind the coverage pass share: the db's species count (checked first, as before the window of the track), a selection of
+// species-local haplotypes (in range, no repeats within a species) ...
+static int check_species_count(pantax_hip_ctx *ctx, const pantax_hip_db *db, const char *what, uint32_t n_species) {
+    return n_species == db->S ? 0 : fail(ctx, PANTAX_HIP_E_INVALID, "%s: the selection has %u species, the db %u", what, n_species, db->S);
+}
+static int check_hap_selection(pantax_hip_ctx *ctx, const pantax_hip_db *db, const char *what, const uint64_t *sel_off, const uint32_t *sel_hap) {
+    const uint32_t S = db->S;
+    if (db->d_path_nodes.p == nullptr || db->h_path_off.size() != db->H + 1)
+        return fail(ctx, PANTAX_HIP_E_STATE, "%s: the db was uploaded without graphs (ranges only)", what);
+    if (sel_off[0] != 0) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: sel_off[0] = %llu", what, (unsigned long long)sel_off[0]);
+    for (uint32_t s = 0; s < S; ++s)
+        if (sel_off[s + 1] < sel_off[s]) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: sel_off decreases at species %u", what, s);
+    if (sel_off[S] && !sel_hap) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: null sel_hap", what);
+    std::vector<uint8_t> seen;
+    for (uint32_t s = 0; s < S; ++s) {
+        const uint64_t nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
+        seen.assign(nh, 0);
+        for (uint64_t c = sel_off[s]; c < sel_off[s + 1]; ++c) {
+            const uint32_t h = sel_hap[c];
+            if (h >= nh) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: species %u has %llu haplotypes, selected %u", what, s, (unsigned long long)nh, h);
+            if (seen[h]) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: haplotype %u of species %u is selected twice", what, h, s);
+            seen[h] = 1;
+        }
+    }
+    return 0;
+}
+// ... and what their kernels read: bases_per_node in the coverage arena, node_base_cov in d_cov -- as the STAGE call leaves them
+static int check_stage_coverage(pantax_hip_ctx *ctx, const pantax_hip_db *db, const char *what) {
+    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "%s: %d enqueued step(s) of this db have not been collected", what, db->step_inflight);
+    const bool arena_gone = db->cov_arena_clean || db->cov_clean_pending;
+    if (!db->cov_done || !db->cov_stage || db->cov_count_pending || arena_gone || db->d_cov.n < db->V || (db->V && (!db->d_cov.p || !db->d_bases.p)))
+        return fail(ctx, PANTAX_HIP_E_STATE, "%s: the db holds no coverage result of pantax_hip_node_coverage%s; call pantax_hip_node_coverage first", what,
+                    db->cov_done || arena_gone ? " (a resident step counts the covered bases in its own passes, keeps no node_base_cov and may have zeroed the coverage arena)" : "");
+    return 0;
+}
+
 int pantax_hip_strain_cov_track(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_cov_track_set *sel, uint64_t *win_off_out, uint64_t cap,
                                 uint32_t *n_nodes_out, uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;
     if (!db || !sel || !sel->sel_off || !win_off_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: null argument");
     PTX_ENTER(ctx);
-    const uint32_t S = db->S;
-    if (sel->n_species != S) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: the selection has %u species, the db %u", sel->n_species, S);
+    PTX_TRY(check_species_count(ctx, db, "strain_cov_track", sel->n_species));
     if (sel->window == 0) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: window of 0 bases");
-    if (db->d_path_nodes.p == nullptr || db->h_path_off.size() != db->H + 1)
-        return fail(ctx, PANTAX_HIP_E_STATE, "strain_cov_track: the db was uploaded without graphs (ranges only)");
-    if (sel->sel_off[0] != 0) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: sel_off[0] = %llu", (unsigned long long)sel->sel_off[0]);
-    for (uint32_t s = 0; s < S; ++s)
-        if (sel->sel_off[s + 1] < sel->sel_off[s]) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: sel_off decreases at species %u", s);
-    if (sel->sel_off[S] && !sel->sel_hap) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: null sel_hap");
-    std::vector<uint8_t> seen;
-    for (uint32_t s = 0; s < S; ++s) {
-        const uint64_t nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
-        seen.assign(nh, 0);
-        for (uint64_t c = sel->sel_off[s]; c < sel->sel_off[s + 1]; ++c) {
-            const uint32_t h = sel->sel_hap[c];
-            if (h >= nh) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: species %u has %llu haplotypes, selected %u", s, (unsigned long long)nh, h);
-            if (seen[h]) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: haplotype %u of species %u is selected twice", h, s);
-            seen[h] = 1;
-        }
-    }
-    // what the kernels gather: bases_per_node in the coverage arena, node_base_cov in d_cov -- as the STAGE call leaves them
-    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "strain_cov_track: %d enqueued step(s) of this db have not been collected", db->step_inflight);
-    const bool arena_gone = db->cov_arena_clean || db->cov_clean_pending;
-    if (!db->cov_done || !db->cov_stage || db->cov_count_pending || arena_gone || db->d_cov.n < db->V || (db->V && (!db->d_cov.p || !db->d_bases.p)))
-        return fail(ctx, PANTAX_HIP_E_STATE, "strain_cov_track: the db holds no coverage result of pantax_hip_node_coverage%s; call pantax_hip_node_coverage first",
-                    db->cov_done || arena_gone ? " (a resident step counts the covered bases in its own passes, keeps no node_base_cov and may have zeroed the coverage arena)" : "");
+    PTX_TRY(check_hap_selection(ctx, db, "strain_cov_track", sel->sel_off, sel->sel_hap));
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_cov_track"));
     return cov_track_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->window, win_off_out, cap, n_nodes_out, len_out, covered_out, bases_out);
+}
+
+int pantax_hip_strain_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *hap_out, uint64_t *species_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_evidence: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_evidence", sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_evidence", sel->sel_off, sel->sel_hap));
+    if ((sel->sel_off[db->S] && !hap_out) || (db->S && !species_out)) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_evidence: null output array");
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_evidence"));
+    return evidence_launch(ctx, db, sel->sel_off, sel->sel_hap, hap_out, species_out);
 }
 
 }  // extern "C"

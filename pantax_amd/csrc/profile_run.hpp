@@ -23,7 +23,8 @@ struct RunPlan {
     bool want_report = false, want_rs = false, rs_run = false;          // rs_run: this call runs a strain step and writes the --read-strains report
     bool want_ct = false, ct_run = false;                               // ct_run: ... and writes the --strain-coverage track
     uint64_t ct_window = 0;                                             // its window W in bases
-    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, gaf_path;
+    bool want_ev = false, ev_run = false;                               // ev_run: ... and writes the --strain-evidence report
+    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, ev_path, gaf_path;
 };
 // what every phase is handed: the two handles, the plan, the ranks, the trace clock
 struct Run { pantax_hip_ctx *ctx; const pantax_hip_profiling_config *cfg; RunPlan p; RankComm comm; Lap lap; };
@@ -65,9 +66,13 @@ struct ShardResult {
     std::vector<int64_t> ct_entry;
     std::vector<uint64_t> ct_win_off{0}, ct_len, ct_covered, ct_bases;
     std::vector<uint32_t> ct_n_nodes;
+    // --strain-evidence: the sums of every haplotype among the rows of strain_abundance.txt, group after group, and of every species of the shard.
+    // ev_entry[h] = its entry or -1 ([hap_names]); entry e owns ev_hap[8e .. 8e + 8) = {all, private}; species k owns ev_species[12k .. 12k + 12) = {total, orphan, core}
+    std::vector<int64_t> ev_entry;
+    std::vector<uint64_t> ev_hap, ev_species;
     bool image_fault = false;          // rc is the load-time refusal of a group that holds images ...
     std::string fault_images;          // ... these (the check names a haplotype, not a file), for the warning
 };
-// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, image write-back)
+// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, node evidence, image write-back)
 ShardResult run_shard(Run &run, Ingest &in, const Selection &sn, bool use_images);
 }  // namespace ptx

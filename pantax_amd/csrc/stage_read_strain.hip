@@ -38,7 +38,6 @@ namespace {
 constexpr uint32_t RS_NO_SLOT = 0xFFFFFFFFu;
 // step codes of the grouped stream (cov_device.hpp: STEP_PAD, STEP_START)
 constexpr uint32_t RS_STEP_PAD = 0xFFu, RS_STEP_START = 0x40u;
-constexpr uint64_t RS_TILE = 4096;   // walk positions per tile of the mask pass (one wave)
 
 struct RsSpecies {
     unsigned long long cand_bits;   // route 1: bit j = haplotype j is a candidate
@@ -48,7 +47,6 @@ struct RsSpecies {
     uint32_t nw;                    // mask words per node (route 1: 1)
     uint32_t bit_base;              // first entry of the species in bit_w / bit_hap
 };
-struct RsTile { uint64_t p0, p1, word0; uint32_t nw, k; };   // walk positions [p0, p1) of candidate k; its words start at word0 (+ local node * nw)
 struct RsResult { uint32_t hap; int32_t n; double post; };
 
 // slot of the step held by `lane` (all 64 lanes): group_first_slot owns the group's first step, every later walk start advances it
@@ -103,11 +101,11 @@ __device__ __forceinline__ RsResult rs_finish(const RsSpecies &st, const uint32_
 }
 
 // route 2: a wave per tile of one candidate's walk; bit k of the candidate's word on every node the stretch visits
-__global__ void __launch_bounds__(256) read_strain_mask_kernel(uint32_t n_tiles, const RsTile *__restrict__ tiles, const uint32_t *__restrict__ path_nodes,
+__global__ void __launch_bounds__(256) read_strain_mask_kernel(uint32_t n_tiles, const WalkMaskTile *__restrict__ tiles, const uint32_t *__restrict__ path_nodes,
                                                                unsigned long long *__restrict__ mask) {
     const int lane = threadIdx.x & 63;
     for (uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * 4) {
-        const RsTile tl = tiles[t];
+        const WalkMaskTile tl = tiles[t];
         const unsigned long long bit = 1ull << (tl.k & 63u);
         const uint64_t wb = tl.word0 + (tl.k >> 6);
         for (uint64_t p = tl.p0 + (uint64_t)lane; p < tl.p1; p += 64) atomicOr(&mask[wb + (uint64_t)path_nodes[p] * tl.nw], bit);
@@ -196,6 +194,32 @@ __global__ void __launch_bounds__(256) read_strain_gather_kernel(uint64_t R, con
 
 }  // namespace
 
+// route 2 for both of its users (read_strains_launch below, evidence_launch in stage_evidence.hip).  add_species: ceil(K / 64) words per node of the
+// species behind what the arena holds so far (bit k = the walk of haps[k]), and the tiles of those K walks ...
+uint64_t WalkMasks::add_species(const Db *db, uint32_t s, const uint32_t *haps, uint64_t K) {
+    const uint64_t base = words;
+    const uint32_t nw = (uint32_t)((K + 63) / 64);
+    words += (db->h_node_off[s + 1] - db->h_node_off[s]) * nw;
+    for (uint64_t k = 0; k < K; ++k) {
+        const uint64_t h = db->h_hap_off[s] + haps[k];
+        for (uint64_t p = db->h_path_off[h]; p < db->h_path_off[h + 1]; p += WALK_MASK_TILE)
+            tiles.push_back(WalkMaskTile{p, std::min(p + WALK_MASK_TILE, db->h_path_off[h + 1]), base, nw, (uint32_t)k});
+    }
+    return base;
+}
+// ... and the pass over them: the arena zero-filled, then one 64-bit atomic OR per visit (the result does not depend on their order)
+int WalkMasks::build(Ctx *ctx, const Db *db) {
+    PTX_HIP(ctx, d_mask.alloc(words ? words : 1));
+    if (words) PTX_TRY(zero_fill(ctx, d_mask.p, words * sizeof(unsigned long long)));
+    if (tiles.empty()) return 0;
+    if (tiles.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "walk masks: %llu tiles of selected walks exceed 32-bit positions", (unsigned long long)tiles.size());
+    PTX_TRY(upload(ctx, d_tiles, tiles.data(), tiles.size()));
+    KTimer tm(ctx, "read_strain_mask_kernel");
+    hipLaunchKernelGGL(read_strain_mask_kernel, dim3(grid_for(tiles.size(), 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, (uint32_t)tiles.size(), d_tiles.p,
+                       db->d_path_nodes.p, d_mask.p);
+    return 0;
+}
+
 int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, uint32_t *hap_out,
                         int32_t *n_out, double *post_out) {
     const uint32_t S = db->S;
@@ -204,8 +228,7 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
     std::vector<RsSpecies> tab(S ? S : 1);
     std::vector<double> bit_w(H + C + 1, 0.0);
     std::vector<uint32_t> bit_hap(H + C + 1, 0u);
-    std::vector<RsTile> tiles;
-    uint64_t arena = 0;
+    WalkMasks wm;
     uint32_t long_nw = 1;
     for (uint32_t s = 0; s < S; ++s) {
         RsSpecies &st = tab[s];
@@ -220,14 +243,12 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
                 bit_hap[st.bit_base + cand_hap[c]] = cand_hap[c];
             }
         } else {
-            st.route = 2; st.nw = (uint32_t)((K + 63) / 64); st.bit_base = (uint32_t)(H + cand_off[s]); st.mask_base = arena;
-            arena += (db->h_node_off[s + 1] - db->h_node_off[s]) * st.nw;
+            st.route = 2; st.nw = (uint32_t)((K + 63) / 64); st.bit_base = (uint32_t)(H + cand_off[s]);
+            st.mask_base = wm.add_species(db, s, cand_hap + cand_off[s], K);
             for (uint64_t k = 0; k < K; ++k) {
-                const uint64_t c = cand_off[s] + k, h = db->h_hap_off[s] + cand_hap[c];
+                const uint64_t c = cand_off[s] + k;
                 bit_w[st.bit_base + k] = cand_w[c];
                 bit_hap[st.bit_base + k] = cand_hap[c];
-                for (uint64_t p = db->h_path_off[h]; p < db->h_path_off[h + 1]; p += RS_TILE)
-                    tiles.push_back(RsTile{p, std::min(p + RS_TILE, db->h_path_off[h + 1]), st.mask_base, st.nw, (uint32_t)k});
             }
         }
         long_nw = std::max(long_nw, st.nw);
@@ -236,20 +257,12 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
     DevBuf<RsSpecies> d_tab;
     DevBuf<double> d_bit_w;
     DevBuf<uint32_t> d_bit_hap;
-    DevBuf<RsTile> d_tiles;
-    DevBuf<unsigned long long> d_mask, d_long;
+    DevBuf<unsigned long long> d_long;
     DevBuf<RsResult> d_res;
     PTX_TRY(upload(ctx, d_tab, tab.data(), tab.size()));
     PTX_TRY(upload(ctx, d_bit_w, bit_w.data(), bit_w.size()));
     PTX_TRY(upload(ctx, d_bit_hap, bit_hap.data(), bit_hap.size()));
-    PTX_HIP(ctx, d_mask.alloc(arena ? arena : 1));
-    if (!tiles.empty()) {
-        PTX_TRY(upload(ctx, d_tiles, tiles.data(), tiles.size()));
-        PTX_TRY(zero_fill(ctx, d_mask.p, arena * sizeof(unsigned long long)));
-        KTimer tm(ctx, "read_strain_mask_kernel");
-        hipLaunchKernelGGL(read_strain_mask_kernel, dim3(grid_for(tiles.size(), 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, (uint32_t)tiles.size(), d_tiles.p,
-                           db->d_path_nodes.p, d_mask.p);
-    }
+    PTX_TRY(wm.build(ctx, db));
     const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
     PTX_HIP(ctx, d_res.alloc(n_slots ? n_slots : 1));
     const bool any_long = rd->n_long != 0;
@@ -259,7 +272,7 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
         KTimer tm(ctx, "read_strain_kernel");
         hipLaunchKernelGGL(read_strain_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->d_g_group_slot.p,
                            rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p,
-                           by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, d_mask.p, d_bit_w.p, d_bit_hap.p,
+                           by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, wm.d_mask.p, d_bit_w.p, d_bit_hap.p,
                            d_long.p, long_nw, d_res.p);
     }
     if (n_slots && any_long) {

@@ -340,6 +340,20 @@ class Engine:
             self._check(self.lib.pantax_hip_strain_cov_track(self.ctx, self.db, C.byref(cs), p(win_off), n, p(n_nodes), p(ln), p(covered), p(bases)))
         return win_off, n_nodes, ln, covered, bases
 
+    def strain_evidence(self, sel_off, sel_hap):
+        """Per-strain node evidence (pantax_hip_strain_evidence) of the coverage result get_node_abundances left on the device.
+        sel_off [S+1], sel_hap (species-local haplotype indices, no repeats within a species) -> (hap uint64 [C, 2, 4]: all / private of every
+        selection entry, species uint64 [S, 3, 4]: total / orphan / core), the last axis {n_nodes, len, covered, bases}."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("strain_evidence: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        cs = _ffi.EvidenceSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None)
+        hap = np.zeros((len(sh), 2, 4), dtype=np.uint64)
+        species = np.zeros((self.S, 3, 4), dtype=np.uint64)
+        self._check(self.lib.pantax_hip_strain_evidence(self.ctx, self.db, C.byref(cs), p(hap) if len(sh) else None, p(species) if self.S else None))
+        return hap, species
+
     def trio_nodes_info(self, fetch=True):
         n = C.c_uint64(0)
         self._check(self.lib.pantax_hip_trio_index(self.ctx, self.db, C.byref(n)))
@@ -494,12 +508,13 @@ class Engine:
                 mode=2, sample_nodes=0, designated_species=None, zip="serialize", out_binning_file=None,
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
-                strain_coverage_file=None, strain_coverage_window=0):
+                strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
         (--read-strains; one rank only).  strain_coverage_file: path of the per-strain windowed coverage track (--strain-coverage; one rank
-        only), strain_coverage_window its window in bases (0: 10000)."""
+        only), strain_coverage_window its window in bases (0: 10000).  strain_evidence_file: path of the per-strain node evidence report
+        (--strain-evidence; one rank only)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -511,7 +526,8 @@ class Engine:
             designated_species=enc(designated_species), zip=enc(zip), rank=int(rank), world_size=int(world_size),
             image_cache=int(image_cache), sample_test=int(sample_test), solver_semantics=int(solver_semantics),
             minimization_min_cov=float(minimization_min_cov), read_strain_file=enc(read_strain_file),
-            strain_coverage_file=enc(strain_coverage_file), strain_coverage_window=int(strain_coverage_window))
+            strain_coverage_file=enc(strain_coverage_file), strain_coverage_window=int(strain_coverage_window),
+            strain_evidence_file=enc(strain_evidence_file))
         cb = None
         if allreduce is not None:   # allreduce(np.ndarray float64) sums it in place over the ranks
             def _cb(_user, buf, n):
