@@ -359,12 +359,12 @@ struct Db {
     bool nh_built = false, nh_walk_too = false;
     DevBuf<uint32_t> d_tile_rank;    // [n_tiles] rank of the tile in path order (hap-major)
     DevBuf<uint32_t> d_hap_tile_off; // [H+1] first path-order tile of every haplotype
-    // node-block run table of the walks (trio_runs_build, stage_trio.hip; a layout table like d_tiles, built once at upload):
+    // node-block run table of the walks (trio_runs_build, stage_trio_tables.hip; a layout table like d_tiles, built once at upload):
     // every species' nodes are cut into blocks of TRIO_BLK nodes, every walk into maximal runs of consecutive positions
     // whose nodes lie in ONE block; runs are grouped by block.  The unique-trio build then gives each block to one
     // workgroup, which sees every window whose middle node lies in the block -- whatever haplotype it is on.  Only species the visit
     // table leaves to this path have blocks.
-    // visit table of the walks (trio_visits_build, stage_trio.hip; the default path of the unique-trio build since round 4): the interior
+    // visit table of the walks (trio_visits_build, stage_trio_tables.hip; the default path of the unique-trio build since round 4): the interior
     // positions listed node by node in groups of 64 visits that no node straddles
     bool trio_visit_ok = false;
     uint32_t n_vgroups = 0;

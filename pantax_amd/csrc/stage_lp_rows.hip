@@ -28,7 +28,7 @@ __global__ void __launch_bounds__(256) mask_kernel(const uint2 *__restrict__ til
                                                    const uint32_t *__restrict__ wide_off /* null: no species can be wide */,
                                                    const uint32_t *__restrict__ wide_nw, unsigned long long *__restrict__ maskw,
                                                    const uint64_t *__restrict__ by_node_hap_off /* non-null: species of <= 64 haplotypes were done by mask_nodes_kernel */) {
-    const uint2 tile = tiles[blockIdx.x];   // {hap, chunk}: see stage_trio.hip
+    const uint2 tile = tiles[blockIdx.x];   // {hap, chunk}: see trio_device.hpp
     if (tile.x == 0xFFFFFFFFu) return;      // filler tile
     const uint32_t h = tile.x;
     const int bit = hap_bit[h];

@@ -951,9 +951,10 @@ def test_rebuild_in_one_pass_files_the_rows_of_the_first_build(eng, seed, S, H, 
 def test_step_on_a_mixed_database(eng, seed, S, H, every, set_opt):
     """A database that holds species of BOTH kinds -- single-strain species (the visit table's) beside species of 70-80 strains (a node with
     more than 64 visits: node-block kernel).  The step's rebuild files the first kind's lookup rows from the visit kernel's records and the
-    second kind's by the pass over their walks, behind them; the stage calls (which want the export copies) take the pass over the walks for
-    the whole db.  Both give the same per-haplotype metrics, and those of the step with the rows forced through the walks (PANTAX_TRIO_ROWS=path);
-    the integers of the stage calls are checked against the oracle."""
+    second kind's by the pass over their walks, behind them; the stage calls (which want the export copies) take the same two routes and keep
+    the window start of every row besides (the route does not depend on who asks: tests/test_gpu_trio_plan.py pins it).  The step gives the same
+    per-haplotype metrics with the rows forced through the walks for the whole db (PANTAX_TRIO_ROWS=path); the integers of the stage calls are
+    checked against the oracle."""
     from oracle import oracle as orc
     import synthdata as synth
     from tests.helpers import select_reads
