@@ -220,6 +220,29 @@ typedef struct {
 int pantax_hip_read_strains(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
                             uint32_t *hap_out /*[R]*/, int32_t *n_out /*[R]*/, double *post_out /*[R]*/);
 
+/* ---- per-strain read support (the --strain-read-support report; not a stage of the reference): how many reads support every candidate strain, how many
+ * support it alone, how many reads of the species fit no candidate, and which candidates the reads cannot tell apart.  The inputs, a counted read, N(r),
+ * C(r) and the assigned strain are those of pantax_hip_read_strains above (argmax of w over C(r), ties to the smallest haplotype index; node-set
+ * containment).  K_s = the candidates of species s.  For a counted read r of species s:
+ *   Q(r) = (1, n_steps(r), span(r)), all u64: n_steps = the steps of the read's walk, span = pend - pstart of the read (0 if pend < pstart).
+ * Every output is a sum of Q(r), its three numbers in the order { n_reads, n_steps, span }:
+ *   per candidate entry c (haplotype h of species s), hap_out [C][3][3] in the order of cand_hap:
+ *     compatible[c] = sum over h in C(r);   unique[c] = sum over C(r) = {h};   assigned[c] = sum over the reads assigned to h;
+ *   per species, species_out [S][4][3]:
+ *     counted[s] = sum over every counted read of s (also when K_s = 0);   unexplained[s] = sum over C(r) empty;   ambiguous[s] = sum over |C(r)| >= 2;
+ *     uninformative[s] = sum over |C(r)| = K_s;   the last three are three zeros each when K_s = 0;
+ *   shared reads, pair_out [pair_off[S]] (n_reads only): pair_out[pair_off[s] + a * K_s + b] = the counted reads with the candidates at positions a and b of
+ *     the species' candidate list both in C(r); symmetric, the diagonal equals compatible.n_reads.  A species of K_s > 64 owns no block (pair_off does not
+ *     advance for it).  pair_off_out [S+1] is computed on the host and always written; more than pair_cap entries: PANTAX_HIP_E_LIMIT with nothing else
+ *     touched (call with pair_cap = 0 to size pair_out).
+ * Integers only: results are exact and independent of any order.  For every species of K_s >= 1: counted = unexplained + sum of assigned;
+ * sum of unique + ambiguous + unexplained = counted; unique <= assigned <= compatible.  State rules and PANTAX_HIP_E_INVALID cases of
+ * pantax_hip_read_strains.  An empty candidate set is fine: counted is still written. */
+int pantax_hip_strain_read_support(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
+                                   uint64_t *hap_out /*[C][3][3]: compatible, unique, assigned*/,
+                                   uint64_t *species_out /*[S][4][3]: counted, unexplained, ambiguous, uninformative*/,
+                                   uint64_t *pair_off_out /*[S+1]*/, uint64_t pair_cap /* entries pair_out holds */, uint64_t *pair_out);
+
 /* ---- per-strain coverage track (the --strain-coverage report; not a stage of the reference): coverage along the genome of selected haplotypes,
  * in windows of W bases, from what pantax_hip_node_coverage leaves on the device.  For a species s, a species-local haplotype h and W >= 1:
  *   v_0 .. v_{n-1} = the walk of h as global node indices (a node visited twice counts at both visits);
@@ -474,6 +497,16 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
      * out for a species without rows; predicted_coverage is "-" on total and orphan, and on core the f64 sum of the species' reported strains in
      * ascending haplotype index.  Written only by a run that performs the strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
     const char *strain_evidence_file;
+    /* --strain-read-support: path of the per-strain read support report (pantax_hip_strain_read_support over every group of species, right behind the
+     * group's strain step; candidates and weights as for read_strain_file; NULL or "None" = off).  TSV with a header, long format: species_taxid,
+     * strain_taxid, genome_ID, class, n_reads, n_steps, span, fraction, other_strain_taxid.  First the strains in the order of strain_abundance.txt, classes
+     * "compatible", "unique", "assigned" each (fraction = n_reads / the species' counted n_reads, f64 with shortest round-trip digits, "-" when that is 0;
+     * other_strain_taxid "-"); then every species that went through a strain step, in the order the run took them, classes "counted", "unexplained",
+     * "ambiguous", "uninformative" with strain_taxid = genome_ID = other_strain_taxid = "-" (a species without rows: "counted" only); then one row of class
+     * "shared" per pair a < b of rows of a species of at most 64 rows with a non-zero count: a's strain columns, other_strain_taxid = b's strain taxid,
+     * n_steps = span = "-", fraction = the count / min(compatible_a, compatible_b).  Written only by a run that performs the strain step; world_size > 1 or a
+     * sharded ingest with it is PANTAX_HIP_E_INVALID. */
+    const char *strain_read_support_file;
 } pantax_hip_profiling_config;
 
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in

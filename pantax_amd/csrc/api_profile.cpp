@@ -67,6 +67,12 @@ int check_args(Run &run) {
     if (p.want_ev && (W > 1 || p.sharded))
         return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain node evidence report (strain_evidence_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
                     p.sharded ? ", sharded" : "");
+    // --strain-read-support: the same again -- a species' reads live on the rank that owns it
+    p.sup_path = opt(cfg->strain_read_support_file);
+    p.want_sup = !p.sup_path.empty() && p.sup_path != "None";
+    if (p.want_sup && (W > 1 || p.sharded))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain read support report (strain_read_support_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
+                    p.sharded ? ", sharded" : "");
     p.db_dir = opt(cfg->db); p.wd = opt(cfg->wd); p.out_dir = opt(cfg->output_dir);
     if (p.out_dir.empty()) p.out_dir = p.wd;
     if (!is_dir(p.db_dir)) return fail(ctx, PANTAX_HIP_E_IO, "Specified PanTax database directory '%s' is not a valid directory path", p.db_dir.c_str());
@@ -96,11 +102,12 @@ int decide_resume(Run &run) {
     run.p.rs_run = run.p.want_rs && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.ct_run = run.p.want_ct && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.ev_run = run.p.want_ev && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
+    run.p.sup_run = run.p.want_sup && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.want_report = run.p.full_path && !run.p.report.empty() && run.p.report != "None";
     return 0;
 }
 void rs_skipped(const RunPlan &p) {
-    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr, p.want_ev ? &p.ev_path : nullptr})
+    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr, p.want_ev ? &p.ev_path : nullptr, p.want_sup ? &p.sup_path : nullptr})
         if (f) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", f->c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
@@ -547,7 +554,7 @@ int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardRe
             for (const GenomeRow *gr : grs) {
                 ori_rows.push_back({0.0, sh.use[k], seq, strain_row_text(species, gr, m, hs ? m.second_sol / sum_all : 0.0, hs, false)});
                 if (pass[h]) final_rows.push_back({m.second_sol / sum_pass, sh.use[k], seq, strain_row_text(species, gr, m, m.second_sol / sum_pass, true, !run.cfg->full)});   // :3250-3284
-                if (pass[h] && (run.p.ct_run || run.p.ev_run)) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
+                if (pass[h] && (run.p.ct_run || run.p.ev_run || run.p.sup_run)) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
                 ++seq;
             }
         }
@@ -659,6 +666,63 @@ int evidence_report(Run &run, const Ingest &in, const Selection &sn, const Shard
     run.lap("strain evidence report");
     return 0;
 }
+// --strain-read-support: {compatible, unique, assigned} of every row of strain_abundance.txt, in its order; {counted, unexplained, ambiguous, uninformative} of
+// every species of the shard in the order it went through the device (a species without rows: counted only); the shared reads of every pair of rows
+int read_support_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, std::vector<TrackRow> &rows) {
+    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });
+    std::ofstream f(run.p.sup_path);
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.sup_path.c_str());
+    f << "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_reads\tn_steps\tspan\tfraction\tother_strain_taxid\n";
+    const auto frac = [](uint64_t n, uint64_t of) { return of ? fmt_f64((double)n / (double)of) : std::string("-"); };
+    const auto put = [&](const std::string &head, const char *cls, const uint64_t *q, uint64_t of) {   // q = {n_reads, n_steps, span}
+        f << head << '\t' << cls << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << frac(q[0], of) << "\t-\n";
+    };
+    const auto strain_head = [&](const TrackRow &r) {
+        std::string head = in.ranges[sn.sel[sh.use[r.k]]].species;
+        head += '\t'; if (r.gr) head += r.gr->strain_taxid;
+        head += '\t'; if (r.gr) head += r.gr->genome_id;
+        return head;
+    };
+    std::vector<const TrackRow *> row_of(sh.sup_hap.size() / 9, nullptr);   // entry -> its first row of the table
+    for (const TrackRow &r : rows) {
+        const int64_t e = sh.sup_entry[r.hap];
+        if (e < 0) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no read support", sh.hap_names[r.hap].c_str());
+        if (!row_of[e]) row_of[e] = &r;
+        const std::string head = strain_head(r);
+        const uint64_t of = sh.sup_species[12 * (size_t)r.k];
+        put(head, "compatible", sh.sup_hap.data() + 9 * e, of);
+        put(head, "unique", sh.sup_hap.data() + 9 * e + 3, of);
+        put(head, "assigned", sh.sup_hap.data() + 9 * e + 6, of);
+    }
+    for (uint32_t k = 0; k < (uint32_t)sh.use.size(); ++k) {
+        const std::string head = in.ranges[sn.sel[sh.use[k]]].species + "\t-\t-";
+        const uint64_t *q = sh.sup_species.data() + 12 * (size_t)k;
+        put(head, "counted", q, q[0]);
+        if (!sh.sup_K[k]) continue;
+        put(head, "unexplained", q + 3, q[0]);
+        put(head, "ambiguous", q + 6, q[0]);
+        put(head, "uninformative", q + 9, q[0]);
+    }
+    for (uint32_t k = 0; k < (uint32_t)sh.use.size(); ++k) {
+        const uint64_t K = sh.sup_K[k];
+        if (K < 2 || K > 64) continue;
+        int64_t e0 = -1;                                                        // the species' entries are consecutive, in ascending haplotype index
+        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1] && e0 < 0; ++h) e0 = sh.sup_entry[h];
+        const uint64_t *pm = sh.sup_pair.data() + sh.sup_pair_off[k];
+        for (uint64_t a = 0; a < K; ++a)
+            for (uint64_t b = a + 1; b < K; ++b) {
+                const uint64_t n = pm[a * K + b];
+                if (!n || e0 < 0 || !row_of[e0 + a] || !row_of[e0 + b]) continue;
+                const TrackRow &ra = *row_of[e0 + a], &rb = *row_of[e0 + b];
+                f << strain_head(ra) << "\tshared\t" << n << "\t-\t-\t" << frac(n, std::min(pm[a * K + a], pm[b * K + b])) << '\t'
+                  << (rb.gr ? rb.gr->strain_taxid : std::string()) << '\n';
+            }
+    }
+    f.close();
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.sup_path.c_str());
+    run.lap("strain read support report");
+    return 0;
+}
 // The phases in order.  `rc` is this rank's status since the last collective (RankComm's rule): PTX_TRY where a phase has ended in the collective
 // that carried it, an assignment where the next collective carries it.
 int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
@@ -705,7 +769,8 @@ int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
     PTX_TRY(strain_tables(run, in, sn, sh, rc ? rc : sh.rc, genomes, track_rows));           // all-reduce: status + normalisers [+ barrier]
     if (p.rs_run) PTX_TRY(read_strains_report(run, in, sh, genomes));
     if (p.ct_run) PTX_TRY(cov_track_report(run, in, sn, sh, track_rows));
-    return p.ev_run ? evidence_report(run, in, sn, sh, track_rows) : 0;
+    if (p.ev_run) PTX_TRY(evidence_report(run, in, sn, sh, track_rows));
+    return p.sup_run ? read_support_report(run, in, sn, sh, track_rows) : 0;
 }
 
 }  // namespace

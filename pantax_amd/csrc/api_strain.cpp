@@ -458,44 +458,76 @@ int pantax_hip_pao_solve(pantax_hip_ctx *ctx, uint32_t n_nodes, const int64_t *n
     return 0;
 }
 
+// what the two passes over the reads' candidate masks share: the state they need, a candidate set in range and without repeats -> every species'
+// candidates in ascending haplotype order (bit order = the order of the sum and of the tie rule), ord[c] = the caller's entry of sorted candidate c
+static int check_read_strain_set(pantax_hip_ctx *ctx, const pantax_hip_db *db, const pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
+                                 const char *what, std::vector<uint32_t> &hap, std::vector<double> &w, std::vector<uint64_t> &ord_all) {
+    const uint32_t S = db->S;
+    if (cand->n_species != S) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: the candidate set has %u species, the db %u", what, cand->n_species, S);
+    if (!reads->binned || reads->binned_db != db->uid || !reads->grouped)
+        return fail(ctx, PANTAX_HIP_E_STATE, "%s: call pantax_hip_bin_reads on these reads against this db first", what);
+    if (db->d_path_nodes.p == nullptr || db->h_path_off.size() != db->H + 1)
+        return fail(ctx, PANTAX_HIP_E_STATE, "%s: the db was uploaded without graphs (ranges only)", what);
+    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "%s: %d enqueued step(s) of this db have not been collected", what, db->step_inflight);
+    if (cand->cand_off[0] != 0) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: cand_off[0] = %llu", what, (unsigned long long)cand->cand_off[0]);
+    for (uint32_t s = 0; s < S; ++s)
+        if (cand->cand_off[s + 1] < cand->cand_off[s]) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: cand_off decreases at species %u", what, s);
+    const uint64_t C = cand->cand_off[S];
+    if (C && (!cand->cand_hap || !cand->cand_w)) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: null cand_hap / cand_w", what);
+    hap.resize(C); w.resize(C); ord_all.resize(C);
+    std::vector<uint64_t> ord;
+    for (uint32_t s = 0; s < S; ++s) {
+        const uint64_t c0 = cand->cand_off[s], c1 = cand->cand_off[s + 1], nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
+        ord.resize(c1 - c0);
+        for (uint64_t c = c0; c < c1; ++c) {
+            if (cand->cand_hap[c] >= nh) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: species %u has %llu haplotypes, candidate %u", what, s, (unsigned long long)nh, cand->cand_hap[c]);
+            ord[c - c0] = c;
+        }
+        std::sort(ord.begin(), ord.end(), [&](uint64_t a, uint64_t b) { return cand->cand_hap[a] < cand->cand_hap[b]; });
+        for (uint64_t i = 0; i < ord.size(); ++i) {
+            if (i && cand->cand_hap[ord[i]] == cand->cand_hap[ord[i - 1]])
+                return fail(ctx, PANTAX_HIP_E_INVALID, "%s: haplotype %u of species %u is a candidate twice", what, cand->cand_hap[ord[i]], s);
+            hap[c0 + i] = cand->cand_hap[ord[i]];
+            w[c0 + i] = cand->cand_w[ord[i]];
+            ord_all[c0 + i] = ord[i];
+        }
+    }
+    return 0;
+}
+
 int pantax_hip_read_strains(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
                             uint32_t *hap_out, int32_t *n_out, double *post_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;
     if (!db || !reads || !cand || !cand->cand_off || (reads->R && (!hap_out || !n_out || !post_out)))
         return fail(ctx, PANTAX_HIP_E_INVALID, "read_strains: null argument");
     PTX_ENTER(ctx);
-    const uint32_t S = db->S;
-    if (cand->n_species != S) return fail(ctx, PANTAX_HIP_E_INVALID, "read_strains: the candidate set has %u species, the db %u", cand->n_species, S);
-    if (!reads->binned || reads->binned_db != db->uid || !reads->grouped)
-        return fail(ctx, PANTAX_HIP_E_STATE, "read_strains: call pantax_hip_bin_reads on these reads against this db first");
-    if (db->d_path_nodes.p == nullptr || db->h_path_off.size() != db->H + 1)
-        return fail(ctx, PANTAX_HIP_E_STATE, "read_strains: the db was uploaded without graphs (ranges only)");
-    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "read_strains: %d enqueued step(s) of this db have not been collected", db->step_inflight);
-    if (cand->cand_off[0] != 0) return fail(ctx, PANTAX_HIP_E_INVALID, "read_strains: cand_off[0] = %llu", (unsigned long long)cand->cand_off[0]);
-    for (uint32_t s = 0; s < S; ++s)
-        if (cand->cand_off[s + 1] < cand->cand_off[s]) return fail(ctx, PANTAX_HIP_E_INVALID, "read_strains: cand_off decreases at species %u", s);
-    const uint64_t C = cand->cand_off[S];
-    if (C && (!cand->cand_hap || !cand->cand_w)) return fail(ctx, PANTAX_HIP_E_INVALID, "read_strains: null cand_hap / cand_w");
-    // every species' candidates in ascending haplotype order: bit order = the order of the sum and of the tie rule
-    std::vector<uint32_t> hap(C);
-    std::vector<double> w(C);
+    std::vector<uint32_t> hap;
+    std::vector<double> w;
     std::vector<uint64_t> ord;
-    for (uint32_t s = 0; s < S; ++s) {
-        const uint64_t c0 = cand->cand_off[s], c1 = cand->cand_off[s + 1], nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
-        ord.resize(c1 - c0);
-        for (uint64_t c = c0; c < c1; ++c) {
-            if (cand->cand_hap[c] >= nh) return fail(ctx, PANTAX_HIP_E_INVALID, "read_strains: species %u has %llu haplotypes, candidate %u", s, (unsigned long long)nh, cand->cand_hap[c]);
-            ord[c - c0] = c;
-        }
-        std::sort(ord.begin(), ord.end(), [&](uint64_t a, uint64_t b) { return cand->cand_hap[a] < cand->cand_hap[b]; });
-        for (uint64_t i = 0; i < ord.size(); ++i) {
-            if (i && cand->cand_hap[ord[i]] == cand->cand_hap[ord[i - 1]])
-                return fail(ctx, PANTAX_HIP_E_INVALID, "read_strains: haplotype %u of species %u is a candidate twice", cand->cand_hap[ord[i]], s);
-            hap[c0 + i] = cand->cand_hap[ord[i]];
-            w[c0 + i] = cand->cand_w[ord[i]];
-        }
-    }
+    PTX_TRY(check_read_strain_set(ctx, db, reads, cand, "read_strains", hap, w, ord));
     return read_strains_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), hap_out, n_out, post_out);
+}
+
+int pantax_hip_strain_read_support(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
+                                   uint64_t *hap_out, uint64_t *species_out, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !reads || !cand || !cand->cand_off || !pair_off_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_support: null argument");
+    PTX_ENTER(ctx);
+    std::vector<uint32_t> hap;
+    std::vector<double> w;
+    std::vector<uint64_t> ord;
+    PTX_TRY(check_read_strain_set(ctx, db, reads, cand, "strain_read_support", hap, w, ord));
+    const uint32_t S = db->S;
+    pair_off_out[0] = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        const uint64_t K = cand->cand_off[s + 1] - cand->cand_off[s];
+        pair_off_out[s + 1] = pair_off_out[s] + (K <= 64 ? K * K : 0);
+    }
+    if (pair_off_out[S] > pair_cap)
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_read_support: %llu pair entries, the caller's array holds %llu", (unsigned long long)pair_off_out[S], (unsigned long long)pair_cap);
+    if ((cand->cand_off[S] && !hap_out) || (S && !species_out) || (pair_off_out[S] && !pair_out))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_support: null output array");
+    return read_support_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), ord.data(), pair_off_out, hap_out, species_out, pair_out);
 }
 
 // what the two node reports behind the coverage pass share: the db's species count (checked first, as before the window of the track), a selection of

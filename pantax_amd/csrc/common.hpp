@@ -685,6 +685,10 @@ bool use_node_haps(const Ctx *ctx, const Db *db);
 // file order, only the entries of reads binned to a species of db are written
 int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, uint32_t *hap_out,
                         int32_t *n_out, double *post_out);
+// stage_read_support.hip (pantax_hip_strain_read_support): candidates of every species in ascending haplotype order, entry_of[c] = the caller's entry of
+// sorted candidate c, pair_off [S+1]; all validated by the caller.  hap_out [C][3][3] in the caller's order, species_out [S][4][3], pair_out [pair_off[S]]
+int read_support_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, const uint64_t *entry_of,
+                        const uint64_t *pair_off, uint64_t *hap_out, uint64_t *species_out, uint64_t *pair_out);
 // stage_read_strain.hip: node membership in selected walks as a compact arena -- ceil(K / 64) words per node of a species over its K selected haplotypes only
 // (bit k = the k-th of them), filled by 64-bit atomic ORs over those walks (read_strain_mask_kernel).  Route 2 of the per-read strain report and of the
 // node evidence report.  The object owns the device buffers: it outlives the kernels that read d_mask.

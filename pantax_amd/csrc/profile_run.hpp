@@ -24,7 +24,8 @@ struct RunPlan {
     bool want_ct = false, ct_run = false;                               // ct_run: ... and writes the --strain-coverage track
     uint64_t ct_window = 0;                                             // its window W in bases
     bool want_ev = false, ev_run = false;                               // ev_run: ... and writes the --strain-evidence report
-    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, ev_path, gaf_path;
+    bool want_sup = false, sup_run = false;                             // sup_run: ... and writes the --strain-read-support report
+    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, ev_path, sup_path, gaf_path;
 };
 // what every phase is handed: the two handles, the plan, the ranks, the trace clock
 struct Run { pantax_hip_ctx *ctx; const pantax_hip_profiling_config *cfg; RunPlan p; RankComm comm; Lap lap; };
@@ -70,9 +71,15 @@ struct ShardResult {
     // ev_entry[h] = its entry or -1 ([hap_names]); entry e owns ev_hap[8e .. 8e + 8) = {all, private}; species k owns ev_species[12k .. 12k + 12) = {total, orphan, core}
     std::vector<int64_t> ev_entry;
     std::vector<uint64_t> ev_hap, ev_species;
+    // --strain-read-support: the same for the read support.  sup_entry[h] = its entry or -1; entry e owns sup_hap[9e .. 9e + 9) = {compatible, unique, assigned};
+    // species k owns sup_species[12k .. 12k + 12) = {counted, unexplained, ambiguous, uninformative} and, when it has 1..64 rows, the K x K block of shared
+    // reads sup_pair[sup_pair_off[k] ..) over its entries in ascending order (K = sup_K[k])
+    std::vector<int64_t> sup_entry;
+    std::vector<uint64_t> sup_hap, sup_species, sup_pair, sup_pair_off;
+    std::vector<uint32_t> sup_K;
     bool image_fault = false;          // rc is the load-time refusal of a group that holds images ...
     std::string fault_images;          // ... these (the check names a haplotype, not a file), for the warning
 };
-// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, node evidence, image write-back)
+// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, node evidence, read support, image write-back)
 ShardResult run_shard(Run &run, Ingest &in, const Selection &sn, bool use_images);
 }  // namespace ptx

@@ -1,5 +1,5 @@
 // profile_shard.cpp -- run_shard (profile_run.hpp): a6 - a14 of the file seam for this rank's selected species.  Where every graph comes from
-// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains, the strain coverage track and the node evidence per group, image write-back.
+// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains, the strain coverage track, the node evidence and the read support per group, image write-back.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -187,6 +187,30 @@ int group_evidence(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const 
     run.lap("  strain evidence");
     return 0;
 }
+// --strain-read-support for the same species: the candidates and weights of group_read_strains, summed on the device (nothing per read comes back)
+int group_read_support(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint64_t> c_off(Sg + 1, 0), p_off(Sg + 1, 0);
+    std::vector<uint32_t> c_hap;
+    std::vector<double> c_w;
+    const size_t entry0 = sh.sup_hap.size() / 9;   // entries of the groups before
+    for (uint32_t k = k0; k < k1; ++k) {
+        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
+            if (pass_g[h]) { sh.sup_entry[h] = (int64_t)(entry0 + c_hap.size()); c_hap.push_back((uint32_t)(h - sh.hap_off[k])); c_w.push_back(sh.met[h].second_sol); }
+        c_off[k - k0 + 1] = c_hap.size();
+    }
+    const pantax_hip_read_strain_set cs{Sg, c_off.data(), c_hap.data(), c_w.data()};
+    sh.sup_hap.resize(9 * (entry0 + c_hap.size()));
+    uint64_t n_pair = 0;
+    for (uint32_t k = 0; k < Sg; ++k) { const uint64_t K = c_off[k + 1] - c_off[k]; sh.sup_K[k0 + k] = (uint32_t)K; n_pair += K <= 64 ? K * K : 0; }
+    const size_t pair0 = sh.sup_pair.size();
+    sh.sup_pair.resize(pair0 + n_pair);
+    PTX_TRY(pantax_hip_strain_read_support(run.ctx, db, in.reads.rd, &cs, sh.sup_hap.data() + 9 * entry0, sh.sup_species.data() + 12 * (size_t)k0, p_off.data(), n_pair,
+                                           sh.sup_pair.data() + pair0));
+    for (uint32_t k = 0; k < Sg; ++k) sh.sup_pair_off[k0 + k] = pair0 + p_off[k];
+    run.lap("  strain read support");
+    return 0;
+}
 // one pass: sources, parts, groups; per group the loader hand-over, then binning against the selected ranges, index, coverage, strain step
 int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, ShardResult &sh) {
     const uint32_t Ss = (uint32_t)sn.sel.size();
@@ -234,6 +258,10 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
     }
     sh.met.resize(sh.hap_names.size());
     if (run.p.ct_run) sh.ct_entry.assign(sh.hap_names.size(), -1);
+    if (run.p.sup_run) {
+        sh.sup_entry.assign(sh.hap_names.size(), -1); sh.sup_species.assign(12 * (size_t)Su, 0);
+        sh.sup_pair_off.assign(Su, 0); sh.sup_K.assign(Su, 0);
+    }
     if (run.p.ev_run) { sh.ev_entry.assign(sh.hap_names.size(), -1); sh.ev_species.assign(12 * (size_t)Su, 0); }
     const std::vector<Group> groups = make_groups(run.ctx, parts);
     const bool piped = groups.size() > 1;
@@ -279,12 +307,13 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
                                     run.cfg->sample_test ? 500 : run.cfg->sample_nodes, run.cfg->solver_semantics};
         PTX_TRY(pantax_hip_strain_profile(run.ctx, db, &sc, nullptr, cov.data() + k0, sh.met.data() + sh.hap_off[k0], sh.info.data() + k0));
         run.lap("strain step");
-        if (run.p.rs_run || run.p.ct_run || run.p.ev_run) {   // the three reports on the group's rows of the strain table, decided once
+        if (run.p.rs_run || run.p.ct_run || run.p.ev_run || run.p.sup_run) {   // the four reports on the group's rows of the strain table, decided once
             std::vector<uint8_t> pass_g;
             PTX_TRY(group_pass_bits(run, k0, k1, sh, pass_g));
             if (run.p.rs_run) PTX_TRY(group_read_strains(run, in, db, k0, k1, pass_g, sh));
             if (run.p.ct_run) PTX_TRY(group_cov_track(run, db, k0, k1, pass_g, sh));
             if (run.p.ev_run) PTX_TRY(group_evidence(run, db, k0, k1, pass_g, sh));
+            if (run.p.sup_run) PTX_TRY(group_read_support(run, in, db, k0, k1, pass_g, sh));
         }
         if (run.cfg->image_cache == 2) {   // leave images behind for the next run
             for (uint32_t k = k0; k < k1; ++k)

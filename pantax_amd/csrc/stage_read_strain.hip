@@ -29,56 +29,14 @@
 #include <cmath>
 #include "common.hpp"
 #include "primitives.hpp"
+#include "read_strain_device.hpp"
 #include "wave.hpp"
 
 namespace ptx {
 
 namespace {
 
-constexpr uint32_t RS_NO_SLOT = 0xFFFFFFFFu;
-// step codes of the grouped stream (cov_device.hpp: STEP_PAD, STEP_START)
-constexpr uint32_t RS_STEP_PAD = 0xFFu, RS_STEP_START = 0x40u;
-
-struct RsSpecies {
-    unsigned long long cand_bits;   // route 1: bit j = haplotype j is a candidate
-    uint64_t mask_base;             // route 2: first word of the species' node masks in the arena
-    uint32_t node_base;             // first global node index of the species
-    uint32_t route;                 // 0: no candidates, 1: node -> haplotype words, 2: compact masks
-    uint32_t nw;                    // mask words per node (route 1: 1)
-    uint32_t bit_base;              // first entry of the species in bit_w / bit_hap
-};
 struct RsResult { uint32_t hap; int32_t n; double post; };
-
-// slot of the step held by `lane` (all 64 lanes): group_first_slot owns the group's first step, every later walk start advances it
-__device__ __forceinline__ uint32_t rs_slot_in_group(uint32_t group_first_slot, uint32_t code, int lane) {
-    const unsigned long long starts = __builtin_amdgcn_ballot_w64((code != RS_STEP_PAD) & ((code & RS_STEP_START) != 0u)) & ~1ull;
-    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(starts >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)starts, 0u));
-    return group_first_slot + below + (uint32_t)((starts >> lane) & 1ull);
-}
-
-// DPP move whose invalid / masked-off lanes read all ones (the identity of AND)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint32_t dpp_ones(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)v, CTRL, ROW_MASK, 0xF, false); }
-
-// inclusive AND over lanes [seg, lane] (seg <= lane: the first lane of my walk in this wave); all 64 lanes active.  The steps of
-// wave_incl_scan_dpp: row_shr 1/2/4/8 inside the 16-lane rows, then the row results travel by row_bcast:15 and row_bcast:31; a lane
-// takes a value only from a source lane of its own walk.
-__device__ __forceinline__ unsigned long long seg_and(unsigned long long m, int lane, int seg) {
-    uint32_t lo = (uint32_t)m, hi = (uint32_t)(m >> 32);
-#define RS_STEP(CTRL, RM, SRC)                                                  \
-    {                                                                           \
-        const uint32_t tl = dpp_ones<CTRL, RM>(lo), th = dpp_ones<CTRL, RM>(hi); \
-        if ((SRC) >= seg) { lo &= tl; hi &= th; }                               \
-    }
-    RS_STEP(0x111, 0xF, lane - 1)
-    RS_STEP(0x112, 0xF, lane - 2)
-    RS_STEP(0x114, 0xF, lane - 4)
-    RS_STEP(0x118, 0xF, lane - 8)
-    RS_STEP(0x142, 0xA, (lane & ~15) - 1)   // rows 1 and 3 <- lanes 15 and 47
-    RS_STEP(0x143, 0xC, 31)                 // rows 2 and 3 <- lane 31
-#undef RS_STEP
-    return ((unsigned long long)hi << 32) | lo;
-}
 
 // the candidates of one mask word, ascending: count, sum (f64, in order), argmax (first of equal weights)
 __device__ __forceinline__ void rs_take(unsigned long long m, uint32_t w, const double *__restrict__ bit_w, uint32_t bit_base, double &best,
@@ -123,38 +81,19 @@ __global__ void __launch_bounds__(256) read_strain_kernel(uint32_t n_groups, uin
     for (uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6); g < n_groups; g += gridDim.x * 4) {
         const uint32_t gs = group_slot[g];                                   // (wave-uniform) NO_SLOT: a group of pads only
         if (gs == RS_NO_SLOT) continue;
-        const uint64_t t = (uint64_t)g * 64u + (uint64_t)lane;
-        const uint32_t code = step_code[t];
-        const uint32_t slot = rs_slot_in_group(gs, code, lane);
-        const bool live = code != RS_STEP_PAD && slot < n_slots;
-        uint4 rr = make_uint4(0u, 0u, 0u, 0u);
-        uint2 sr = make_uint2(0xFFFFFFFFu, 0u);
-        if (live) { rr = read_rec[slot]; sr = slot_rec[slot]; }
-        const bool counted = live && (int32_t)sr.x >= 0;
-        RsSpecies st{0ull, 0ull, 0u, 0u, 0u, 0u};
-        if (counted) st = tab[sr.x];
-        const uint32_t i = live ? (uint32_t)t - rr.x : 0u;                  // position in the walk (T_pad < 2^32)
-        const bool last = live && i + 1u == rr.y;
-        const bool is_long = rr.y > 64u;
-        const int seg = lane - (int)min(i, (uint32_t)lane);                 // first lane of my walk in this wave
-        const bool tail = live && (last || lane == 63);                      // last step of my walk in this wave
-        const uint32_t nw = st.route ? st.nw : 0u;
-        const uint32_t nw_max = wave_reduce(nw, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
-        const uint32_t v = counted ? g_node_id[t] + sr.y : 0u;               // global node index
-        const uint64_t mrow = st.mask_base + (uint64_t)(v - st.node_base) * nw;
+        const RsLane L = rs_lane(g, gs, lane, n_slots, step_code, g_node_id, read_rec, slot_rec, tab);
+        const uint32_t nw_max = wave_reduce(L.nw, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
         double best = -INFINITY, sum = 0.0;
         uint32_t besti = 0;
         int n = 0;
         for (uint32_t w = 0; w < nw_max; ++w) {                              // (wave-uniform trip count: seg_and wants every lane)
-            unsigned long long m = ~0ull;
-            if (w < nw) m = st.route == 1u ? (node_haps[v] & st.cand_bits) : mask[mrow + w];
-            m = seg_and(m, lane, seg);
-            if (tail && w < nw) {
-                if (is_long) atomicAnd(&long_acc[(uint64_t)slot * long_nw + w], m);
-                else if (last) rs_take(m, w, bit_w, st.bit_base, best, besti, sum, n);
+            const unsigned long long m = rs_lane_word(L, w, lane, node_haps, mask);
+            if (L.tail && w < L.nw) {
+                if (L.is_long) rs_long_partial(long_acc, long_nw, L.slot, w, m);
+                else if (L.last) rs_take(m, w, bit_w, L.st.bit_base, best, besti, sum, n);
             }
         }
-        if (last && counted && !is_long) res[slot] = rs_finish(st, bit_hap, best, besti, sum, n);
+        if (L.last && L.counted && !L.is_long) res[L.slot] = rs_finish(L.st, bit_hap, best, besti, sum, n);
     }
 }
 
@@ -224,35 +163,14 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
                         int32_t *n_out, double *post_out) {
     const uint32_t S = db->S;
     const uint64_t H = db->H, C = cand_off[S];
-    const bool by_node = db->nh_built && ctx->cfg.read_strain_route != "walk";
-    std::vector<RsSpecies> tab(S ? S : 1);
     std::vector<double> bit_w(H + C + 1, 0.0);
     std::vector<uint32_t> bit_hap(H + C + 1, 0u);
-    WalkMasks wm;
-    uint32_t long_nw = 1;
-    for (uint32_t s = 0; s < S; ++s) {
-        RsSpecies &st = tab[s];
-        st = RsSpecies{0ull, 0ull, (uint32_t)db->h_node_off[s], 0u, 0u, 0u};
-        const uint64_t K = cand_off[s + 1] - cand_off[s], nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
-        if (K == 0) continue;
-        if (by_node && nh <= 64) {
-            st.route = 1; st.nw = 1; st.bit_base = (uint32_t)db->h_hap_off[s];
-            for (uint64_t c = cand_off[s]; c < cand_off[s + 1]; ++c) {
-                st.cand_bits |= 1ull << cand_hap[c];
-                bit_w[st.bit_base + cand_hap[c]] = cand_w[c];
-                bit_hap[st.bit_base + cand_hap[c]] = cand_hap[c];
-            }
-        } else {
-            st.route = 2; st.nw = (uint32_t)((K + 63) / 64); st.bit_base = (uint32_t)(H + cand_off[s]);
-            st.mask_base = wm.add_species(db, s, cand_hap + cand_off[s], K);
-            for (uint64_t k = 0; k < K; ++k) {
-                const uint64_t c = cand_off[s] + k;
-                bit_w[st.bit_base + k] = cand_w[c];
-                bit_hap[st.bit_base + k] = cand_hap[c];
-            }
-        }
-        long_nw = std::max(long_nw, st.nw);
-    }
+    RsTable rt;
+    rs_table_build(ctx, db, cand_off, cand_hap, rt, [&](uint64_t at, uint64_t c) { bit_w[at] = cand_w[c]; bit_hap[at] = cand_hap[c]; });
+    std::vector<RsSpecies> &tab = rt.tab;
+    WalkMasks &wm = rt.wm;
+    const bool by_node = rt.by_node;
+    const uint32_t long_nw = rt.long_nw;
     if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "read_strains: %llu haplotypes + candidates exceed 32-bit positions", (unsigned long long)(H + C));
     DevBuf<RsSpecies> d_tab;
     DevBuf<double> d_bit_w;

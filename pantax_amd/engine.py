@@ -320,6 +320,26 @@ class Engine:
         self._check(self.lib.pantax_hip_read_strains(self.ctx, self.db, self.reads, C.byref(cs), p(hap), p(n), p(post)))
         return hap, n, post
 
+    def strain_read_support(self, cand_off, cand_hap, cand_w):
+        """Per-strain read support (pantax_hip_strain_read_support) of the resident reads, binned against the resident db.  The candidate set of
+        read_strains -> (hap uint64 [C, 3, 3]: compatible / unique / assigned of every candidate entry, species uint64 [S, 4, 3]: counted / unexplained /
+        ambiguous / uninformative, pair_off uint64 [S+1], pair uint64 [pair_off[-1]]: the K_s x K_s shared-read counts of every species of K_s <= 64);
+        the last axis of hap and species is {n_reads, n_steps, span}."""
+        co = as_c(cand_off, np.uint64)
+        ch = as_c(cand_hap, np.uint32)
+        cw = as_c(cand_w, np.float64)
+        if len(co) != self.S + 1 or len(ch) != int(co[-1]) or len(cw) != len(ch):
+            raise ValueError("strain_read_support: cand_off needs S + 1 entries and cand_hap / cand_w cand_off[-1] each")
+        cs = _ffi.ReadStrainSet(self.S, co.ctypes.data, ch.ctypes.data if len(ch) else None, cw.ctypes.data if len(cw) else None)
+        hap = np.zeros((len(ch), 3, 3), dtype=np.uint64)
+        species = np.zeros((self.S, 4, 3), dtype=np.uint64)
+        pair_off = np.zeros(self.S + 1, dtype=np.uint64)
+        k = np.diff(co.astype(np.int64))
+        pair = np.zeros(int((k[k <= 64] ** 2).sum()), dtype=np.uint64)
+        self._check(self.lib.pantax_hip_strain_read_support(self.ctx, self.db, self.reads, C.byref(cs), p(hap) if len(ch) else None,
+                                                            p(species) if self.S else None, p(pair_off), len(pair), p(pair) if len(pair) else None))
+        return hap, species, pair_off, pair
+
     def strain_cov_track(self, sel_off, sel_hap, window):
         """Per-strain windowed coverage track (pantax_hip_strain_cov_track) of the coverage result get_node_abundances left on the device.
         sel_off [S+1], sel_hap (species-local haplotype indices, no repeats within a species), window W >= 1 in bases ->
@@ -508,13 +528,13 @@ class Engine:
                 mode=2, sample_nodes=0, designated_species=None, zip="serialize", out_binning_file=None,
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
-                strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None):
+                strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
         (--read-strains; one rank only).  strain_coverage_file: path of the per-strain windowed coverage track (--strain-coverage; one rank
         only), strain_coverage_window its window in bases (0: 10000).  strain_evidence_file: path of the per-strain node evidence report
-        (--strain-evidence; one rank only)."""
+        (--strain-evidence; one rank only).  strain_read_support_file: path of the per-strain read support report (--strain-read-support; one rank only)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -527,7 +547,7 @@ class Engine:
             image_cache=int(image_cache), sample_test=int(sample_test), solver_semantics=int(solver_semantics),
             minimization_min_cov=float(minimization_min_cov), read_strain_file=enc(read_strain_file),
             strain_coverage_file=enc(strain_coverage_file), strain_coverage_window=int(strain_coverage_window),
-            strain_evidence_file=enc(strain_evidence_file))
+            strain_evidence_file=enc(strain_evidence_file), strain_read_support_file=enc(strain_read_support_file))
         cb = None
         if allreduce is not None:   # allreduce(np.ndarray float64) sums it in place over the ranks
             def _cb(_user, buf, n):
