@@ -295,6 +295,39 @@ typedef struct {
 int pantax_hip_strain_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel,
                                uint64_t *hap_out /*[C][2][4]: all, private*/, uint64_t *species_out /*[S][3][4]: total, orphan, core*/);
 
+/* ---- per-strain depth distribution (the --strain-depth report; not a stage of the reference): every depth of the reports above is a mean, bases / len
+ * over a set of nodes, and a mean is what fails where a mobile element at 400x lifts a strain whose other private nodes sit at 3x, or where a strain
+ * called from its core genome has a private genome that is mostly empty.  This call hands out the DISTRIBUTION of depth over the same sets of nodes.
+ * Selection, Sel_s, K_s, M(v), m(v), the inputs (node_len; bases_per_node as pantax_hip_node_coverage leaves it) and the state rules are exactly those
+ * of pantax_hip_strain_evidence, whose selection type it takes: every node of a species is counted once, membership is node-level (a node walked twice
+ * counts once); PANTAX_HIP_E_STATE behind a resident step and before any coverage pass; PANTAX_HIP_E_INVALID for an n_species different from the db's, a
+ * haplotype index out of range, a haplotype twice within a species.  On an error the output arrays are left as given.
+ *   depth of a node   d(v) = bases_per_node[v] / node_len[v] in u64 integer division; d(v) = 0 when node_len[v] = 0.
+ *   bin of a depth    PANTAX_HIP_DEPTH_BINS = 96 of them.  d < 32: bin = d (exact).  Otherwise, with e = floor(log2 d),
+ *                     bin = min(95, 32 + 4 (e - 5) + ((d >> (e - 2)) & 3)): four bins per octave from 2^5, and bin 95 also takes everything from 2^21 up.
+ *   bounds of a bin   lo(b) = b for b < 32, lo(b) = (4 + (b - 32) % 4) << (3 + (b - 32) / 4) for b >= 32; hi(b) = lo(b + 1), hi(95) = 2^64 - 1.  A depth d
+ *                     of bin b has lo(b) <= d < hi(b) (bin 95: d <= hi, the largest u64).
+ * Every output is a histogram [96][2]: per bin the u64 sums of (1, node_len[v]), in the order { n_nodes, len }, over the nodes of a class whose depth
+ * falls into the bin:
+ *   hap_out [C][2][96][2]      per selection entry, in the order of sel_hap: class all (h in M(v)), then private (M(v) = {h});
+ *   species_out [S][2][96][2]  per species: class total (every node), then orphan (m(v) = 0).  NULL: not computed.
+ * Integers only: results are exact and independent of any order.  An empty selection, or a species with nothing selected, is fine: total and orphan
+ * are still written for it.  Summed over its bins a histogram gives { n_nodes, len } of the same class of pantax_hip_strain_evidence.
+ * The option depth_route=walk (pantax_hip_set_option) takes every species' membership from its selected walks, as evidence_route=walk does. */
+#define PANTAX_HIP_DEPTH_BINS 96
+int pantax_hip_strain_depth(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel,
+                            uint64_t *hap_out /*[C][2][96][2]: all, private*/, uint64_t *species_out /*[S][2][96][2]: total, orphan; or NULL*/);
+/* Host-only helpers of the histograms (no ctx, no GPU; the bin function is the one source text the kernel compiles):
+ *   pantax_hip_depth_bin        the bin of a depth;
+ *   pantax_hip_depth_bin_range  lo(bin) and hi(bin); PANTAX_HIP_E_INVALID for bin >= 96 or a null pointer;
+ *   pantax_hip_depth_quantile   the length-weighted quantile of one histogram hist [96][2]: with T = the sum of len over the bins, the smallest bin whose
+ *                               cumulative len is at least max(1, ceil(T per_mille / 1000)) -> *bin_out, return 0.  T = 0: there is none, the return value
+ *                               is PANTAX_HIP_DEPTH_NONE and *bin_out is left alone.  per_mille > 1000 or a null pointer: PANTAX_HIP_E_INVALID. */
+#define PANTAX_HIP_DEPTH_NONE 1
+uint32_t pantax_hip_depth_bin(uint64_t d);
+int pantax_hip_depth_bin_range(uint32_t bin, uint64_t *lo, uint64_t *hi);
+int pantax_hip_depth_quantile(const uint64_t *hist /*[96][2]*/, uint32_t per_mille, uint32_t *bin_out);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -507,6 +540,15 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
      * n_steps = span = "-", fraction = the count / min(compatible_a, compatible_b).  Written only by a run that performs the strain step; world_size > 1 or a
      * sharded ingest with it is PANTAX_HIP_E_INVALID. */
     const char *strain_read_support_file;
+    /* --strain-depth: path of the per-strain depth distribution report (pantax_hip_strain_depth over every group of species, right behind the group's
+     * strain step; Sel_s = the species' rows of strain_abundance.txt; NULL or "None" = off).  TSV with a header, long format: species_taxid, strain_taxid,
+     * genome_ID, class, n_nodes, len, len_zero, q05, q25, q50, q75, q95, q50_hi, predicted_coverage.  First the strains in the order of
+     * strain_abundance.txt, classes "all" then "private" each (predicted_coverage = the unrounded second_sol); then every species that went through a
+     * strain step, in the order the run took them, classes "total" and "orphan" with strain_taxid = genome_ID = "-" and predicted_coverage "-".
+     * n_nodes and len are the histogram summed over its bins, len_zero the len of bin 0; qXX = lo(bin) of the length-weighted quantile
+     * (pantax_hip_depth_quantile at 50, 250, 500, 750, 950 per mille), q50_hi = hi(bin) of the median's bin: the resolution of the median.  Every quantile
+     * column is "-" when len = 0.  Written only by a run that performs the strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
+    const char *strain_depth_file;
 } pantax_hip_profiling_config;
 
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in

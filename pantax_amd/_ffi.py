@@ -22,12 +22,15 @@ SYMBOLS = [
     "pantax_hip_sample_ranks", "pantax_hip_chacha_block", "pantax_hip_gaf_filter", "pantax_hip_db_save_images", "pantax_hip_db_load_images",
     "pantax_hip_gaf_load", "pantax_hip_gaf_load_device", "pantax_hip_reads_load_gaf", "pantax_hip_reads_set_flags", "pantax_hip_gaf_view", "pantax_hip_gaf_free",
     "pantax_hip_graph_load", "pantax_hip_graph_view", "pantax_hip_graph_free", "pantax_hip_format_f64",
-    "pantax_hip_read_strains", "pantax_hip_strain_cov_track", "pantax_hip_strain_evidence", "pantax_hip_strain_read_support", "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
+    "pantax_hip_read_strains", "pantax_hip_strain_cov_track", "pantax_hip_strain_evidence", "pantax_hip_strain_read_support", "pantax_hip_strain_depth",
+    "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
 
 
 E_LIMIT = -4   # pantax_hip_status values the binding itself looks at
+DEPTH_BINS = 96   # PANTAX_HIP_DEPTH_BINS
+DEPTH_NONE = 1    # PANTAX_HIP_DEPTH_NONE: pantax_hip_depth_quantile of a histogram without length
 
 
 class PantaxHipError(RuntimeError):
@@ -100,7 +103,7 @@ class ProfilingConfig(C.Structure):
                 ("allreduce_sum", C.c_void_p), ("comm_user", C.c_void_p), ("alltoallv", C.c_void_p), ("comm_device_buffers", C.c_int32),
                 ("sample_test", C.c_int32), ("solver_semantics", C.c_int32), ("minimization_min_cov", C.c_double),
                 ("read_strain_file", C.c_char_p), ("strain_coverage_file", C.c_char_p), ("strain_coverage_window", C.c_int64),
-                ("strain_evidence_file", C.c_char_p), ("strain_read_support_file", C.c_char_p)]
+                ("strain_evidence_file", C.c_char_p), ("strain_read_support_file", C.c_char_p), ("strain_depth_file", C.c_char_p)]
 
 
 class ReadStrainSet(C.Structure):
@@ -152,6 +155,14 @@ def load():
                                                         C.c_uint64, C.c_void_p]
         _lib.pantax_hip_strain_evidence.restype = C.c_int
         _lib.pantax_hip_strain_evidence.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_strain_depth.restype = C.c_int
+        _lib.pantax_hip_strain_depth.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_depth_bin.restype = C.c_uint32
+        _lib.pantax_hip_depth_bin.argtypes = [C.c_uint64]
+        _lib.pantax_hip_depth_bin_range.restype = C.c_int
+        _lib.pantax_hip_depth_bin_range.argtypes = [C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        _lib.pantax_hip_depth_quantile.restype = C.c_int
+        _lib.pantax_hip_depth_quantile.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     return _lib
 
 

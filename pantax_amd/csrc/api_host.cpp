@@ -4,6 +4,7 @@
 #include <cmath>
 #include <vector>
 #include "common.hpp"
+#include "depth_device.hpp"
 
 using namespace ptx;
 
@@ -101,6 +102,33 @@ int pantax_hip_abundance_filter(uint32_t n_species, const uint64_t *hap_off, con
     if (sum_all_out) *sum_all_out = all;
     if (sum_pass_out) *sum_pass_out = pass;
     return 0;
+}
+
+// ---- the host side of the depth distribution report: the bin function the kernel uses (depth_device.hpp), its inverse and the quantile of a histogram
+static_assert(PANTAX_HIP_DEPTH_BINS == ptx::DEPTH_BINS, "header and kernel agree on the bins");
+
+uint32_t pantax_hip_depth_bin(uint64_t d) { return depth_bin(d); }
+
+int pantax_hip_depth_bin_range(uint32_t bin, uint64_t *lo, uint64_t *hi) {
+    if (bin >= DEPTH_BINS || !lo || !hi) return PANTAX_HIP_E_INVALID;
+    *lo = depth_bin_lo(bin);
+    *hi = bin + 1 < DEPTH_BINS ? depth_bin_lo(bin + 1) : ~0ull;
+    return 0;
+}
+
+int pantax_hip_depth_quantile(const uint64_t *hist, uint32_t per_mille, uint32_t *bin_out) {
+    if (!hist || !bin_out || per_mille > 1000) return PANTAX_HIP_E_INVALID;
+    unsigned __int128 T = 0;
+    for (uint32_t b = 0; b < DEPTH_BINS; ++b) T += hist[2 * b + 1];
+    if (T == 0) return PANTAX_HIP_DEPTH_NONE;
+    unsigned __int128 target = (T * per_mille + 999) / 1000;   // ceil(T per_mille / 1000)
+    if (target < 1) target = 1;
+    unsigned __int128 cum = 0;
+    for (uint32_t b = 0; b < DEPTH_BINS; ++b) {
+        cum += hist[2 * b + 1];
+        if (cum >= target) { *bin_out = b; return 0; }
+    }
+    return PANTAX_HIP_E_STATE;   // not reached: cum = T >= target at the last bin
 }
 
 }  // extern "C"

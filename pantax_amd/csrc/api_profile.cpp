@@ -73,6 +73,12 @@ int check_args(Run &run) {
     if (p.want_sup && (W > 1 || p.sharded))
         return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain read support report (strain_read_support_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
                     p.sharded ? ", sharded" : "");
+    // --strain-depth: the same again -- a species' histograms live on the rank that owns it
+    p.dp_path = opt(cfg->strain_depth_file);
+    p.want_dp = !p.dp_path.empty() && p.dp_path != "None";
+    if (p.want_dp && (W > 1 || p.sharded))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain depth distribution report (strain_depth_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
+                    p.sharded ? ", sharded" : "");
     p.db_dir = opt(cfg->db); p.wd = opt(cfg->wd); p.out_dir = opt(cfg->output_dir);
     if (p.out_dir.empty()) p.out_dir = p.wd;
     if (!is_dir(p.db_dir)) return fail(ctx, PANTAX_HIP_E_IO, "Specified PanTax database directory '%s' is not a valid directory path", p.db_dir.c_str());
@@ -103,11 +109,12 @@ int decide_resume(Run &run) {
     run.p.ct_run = run.p.want_ct && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.ev_run = run.p.want_ev && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.sup_run = run.p.want_sup && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
+    run.p.dp_run = run.p.want_dp && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.want_report = run.p.full_path && !run.p.report.empty() && run.p.report != "None";
     return 0;
 }
 void rs_skipped(const RunPlan &p) {
-    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr, p.want_ev ? &p.ev_path : nullptr, p.want_sup ? &p.sup_path : nullptr})
+    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr, p.want_ev ? &p.ev_path : nullptr, p.want_sup ? &p.sup_path : nullptr, p.want_dp ? &p.dp_path : nullptr})
         if (f) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", f->c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
@@ -465,7 +472,7 @@ int route_reads(Run &run, Ingest &in, const Selection &sn, int *unpack_rc) {
 }
 // rows keep (species position in the selection, running number) so that any merge reproduces the one-process order
 struct OutRow { double key; uint32_t k, seq; std::string line; };
-// a row of strain_abundance.txt as the --strain-coverage and --strain-evidence reports follow it: its sort key, its haplotype (into ShardResult::hap_names), its joined genome or null
+// a row of strain_abundance.txt as the --strain-coverage, --strain-evidence, --strain-read-support and --strain-depth reports follow it: its sort key, its haplotype (into ShardResult::hap_names), its joined genome or null
 struct TrackRow { double key; uint32_t k; uint64_t hap; const GenomeRow *gr; };
 bool write_part(const std::string &path, const std::vector<OutRow> &rows) {
     FILE *f = std::fopen(path.c_str(), "wb");
@@ -554,7 +561,7 @@ int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardRe
             for (const GenomeRow *gr : grs) {
                 ori_rows.push_back({0.0, sh.use[k], seq, strain_row_text(species, gr, m, hs ? m.second_sol / sum_all : 0.0, hs, false)});
                 if (pass[h]) final_rows.push_back({m.second_sol / sum_pass, sh.use[k], seq, strain_row_text(species, gr, m, m.second_sol / sum_pass, true, !run.cfg->full)});   // :3250-3284
-                if (pass[h] && (run.p.ct_run || run.p.ev_run || run.p.sup_run)) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
+                if (pass[h] && (run.p.ct_run || run.p.ev_run || run.p.sup_run || run.p.dp_run)) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
                 ++seq;
             }
         }
@@ -723,6 +730,50 @@ int read_support_report(Run &run, const Ingest &in, const Selection &sn, const S
     run.lap("strain read support report");
     return 0;
 }
+// --strain-depth: the depth histograms {all, private} of every row of strain_abundance.txt, in its order, then {total, orphan} of every species of the shard
+// in the order it went through the device; per histogram its node count, its length, the length at depth 0 and the length-weighted quantiles
+int depth_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, std::vector<TrackRow> &rows) {
+    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });
+    std::ofstream f(run.p.dp_path);
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.dp_path.c_str());
+    f << "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_nodes\tlen\tlen_zero\tq05\tq25\tq50\tq75\tq95\tq50_hi\tpredicted_coverage\n";
+    constexpr size_t HIST = 2 * PANTAX_HIP_DEPTH_BINS;   // u64 per histogram: [bin]{n_nodes, len}
+    const auto put = [&f](const std::string &head, const char *cls, const uint64_t *hist, const std::string &pc) {
+        uint64_t n = 0, len = 0;
+        for (uint32_t b = 0; b < PANTAX_HIP_DEPTH_BINS; ++b) { n += hist[2 * b]; len += hist[2 * b + 1]; }
+        f << head << '\t' << cls << '\t' << n << '\t' << len << '\t' << hist[1];
+        uint64_t hi50 = 0;
+        for (const uint32_t pm : {50u, 250u, 500u, 750u, 950u}) {
+            uint32_t bin = 0;
+            uint64_t lo = 0, hi = 0;
+            if (pantax_hip_depth_quantile(hist, pm, &bin) != 0) { f << "\t-"; continue; }   // len = 0
+            pantax_hip_depth_bin_range(bin, &lo, &hi);
+            if (pm == 500u) hi50 = hi;
+            f << '\t' << lo;
+        }
+        if (len) f << '\t' << hi50; else f << "\t-";
+        f << '\t' << pc << '\n';
+    };
+    for (const TrackRow &r : rows) {
+        const int64_t e = sh.dp_entry[r.hap];
+        if (e < 0) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no depth histogram", sh.hap_names[r.hap].c_str());
+        std::string head = in.ranges[sn.sel[sh.use[r.k]]].species;
+        head += '\t'; if (r.gr) head += r.gr->strain_taxid;
+        head += '\t'; if (r.gr) head += r.gr->genome_id;
+        const std::string pc = fmt_f64(sh.met[r.hap].second_sol);
+        put(head, "all", sh.dp_hap.data() + 2 * HIST * e, pc);
+        put(head, "private", sh.dp_hap.data() + 2 * HIST * e + HIST, pc);
+    }
+    for (uint32_t k = 0; k < (uint32_t)sh.use.size(); ++k) {
+        const std::string head = in.ranges[sn.sel[sh.use[k]]].species + "\t-\t-";
+        put(head, "total", sh.dp_species.data() + 2 * HIST * (size_t)k, "-");
+        put(head, "orphan", sh.dp_species.data() + 2 * HIST * (size_t)k + HIST, "-");
+    }
+    f.close();
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.dp_path.c_str());
+    run.lap("strain depth report");
+    return 0;
+}
 // The phases in order.  `rc` is this rank's status since the last collective (RankComm's rule): PTX_TRY where a phase has ended in the collective
 // that carried it, an assignment where the next collective carries it.
 int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
@@ -770,7 +821,8 @@ int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
     if (p.rs_run) PTX_TRY(read_strains_report(run, in, sh, genomes));
     if (p.ct_run) PTX_TRY(cov_track_report(run, in, sn, sh, track_rows));
     if (p.ev_run) PTX_TRY(evidence_report(run, in, sn, sh, track_rows));
-    return p.sup_run ? read_support_report(run, in, sn, sh, track_rows) : 0;
+    if (p.sup_run) PTX_TRY(read_support_report(run, in, sn, sh, track_rows));
+    return p.dp_run ? depth_report(run, in, sn, sh, track_rows) : 0;
 }
 
 }  // namespace

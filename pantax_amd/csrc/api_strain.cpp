@@ -589,4 +589,15 @@ int pantax_hip_strain_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pan
     return evidence_launch(ctx, db, sel->sel_off, sel->sel_hap, hap_out, species_out);
 }
 
+int pantax_hip_strain_depth(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *hap_out, uint64_t *species_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_depth: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_depth", sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_depth", sel->sel_off, sel->sel_hap));
+    if (sel->sel_off[db->S] && !hap_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_depth: null output array");   // (species_out may be null: no species histograms)
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_depth"));
+    return depth_launch(ctx, db, sel->sel_off, sel->sel_hap, hap_out, species_out);
+}
+
 }  // extern "C"

@@ -27,6 +27,10 @@ static void usage() {
             "  --strain-read-support F   per-strain read support: for every row of strain_abundance.txt the reads compatible with it, compatible with it alone\n"
             "                     (unique) and assigned to it, then per species the counted reads, those no reported strain explains (unexplained), those of\n"
             "                     several strains (ambiguous) and of all of them (uninformative), then the reads every pair of strains shares (one rank only)\n"
+            "  --strain-depth F   per-strain depth distribution: for every row of strain_abundance.txt the histogram of node depth over the nodes it walks\n"
+            "                     (class all) and over those no other reported strain of its species walks (private), then per species over every node\n"
+            "                     (total) and over the nodes no reported strain walks (orphan): n_nodes, len, len at depth 0, the length-weighted quantiles\n"
+            "                     q05 q25 q50 q75 q95 as the lower bound of their bin, and the upper bound of the median's bin (one rank only)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -101,6 +105,7 @@ int main(int argc, char **argv) {
         else if (a == "--strain-coverage-window") c.strain_coverage_window = atoll(next());
         else if (a == "--strain-evidence") c.strain_evidence_file = next();
         else if (a == "--strain-read-support") c.strain_read_support_file = next();
+        else if (a == "--strain-depth") c.strain_depth_file = next();
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

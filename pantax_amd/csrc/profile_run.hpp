@@ -25,7 +25,8 @@ struct RunPlan {
     uint64_t ct_window = 0;                                             // its window W in bases
     bool want_ev = false, ev_run = false;                               // ev_run: ... and writes the --strain-evidence report
     bool want_sup = false, sup_run = false;                             // sup_run: ... and writes the --strain-read-support report
-    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, ev_path, sup_path, gaf_path;
+    bool want_dp = false, dp_run = false;                               // dp_run: ... and writes the --strain-depth report
+    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, ev_path, sup_path, dp_path, gaf_path;
 };
 // what every phase is handed: the two handles, the plan, the ranks, the trace clock
 struct Run { pantax_hip_ctx *ctx; const pantax_hip_profiling_config *cfg; RunPlan p; RankComm comm; Lap lap; };
@@ -77,9 +78,14 @@ struct ShardResult {
     std::vector<int64_t> sup_entry;
     std::vector<uint64_t> sup_hap, sup_species, sup_pair, sup_pair_off;
     std::vector<uint32_t> sup_K;
+    // --strain-depth: the depth histograms ([96]{n_nodes, len} = 192 u64 each) of every haplotype among the rows of strain_abundance.txt, group after group,
+    // and of every species of the shard.  dp_entry[h] = its entry or -1 ([hap_names]); entry e owns dp_hap[384e .. 384e + 384) = {all, private}; species k
+    // owns dp_species[384k .. 384k + 384) = {total, orphan}
+    std::vector<int64_t> dp_entry;
+    std::vector<uint64_t> dp_hap, dp_species;
     bool image_fault = false;          // rc is the load-time refusal of a group that holds images ...
     std::string fault_images;          // ... these (the check names a haplotype, not a file), for the warning
 };
-// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, node evidence, read support, image write-back)
+// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, node evidence, read support, depth distribution, image write-back)
 ShardResult run_shard(Run &run, Ingest &in, const Selection &sn, bool use_images);
 }  // namespace ptx

@@ -1,5 +1,5 @@
 // profile_shard.cpp -- run_shard (profile_run.hpp): a6 - a14 of the file seam for this rank's selected species.  Where every graph comes from
-// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains, the strain coverage track, the node evidence and the read support per group, image write-back.
+// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains, the strain coverage track, the node evidence, the read support and the depth distribution per group, image write-back.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -211,6 +211,24 @@ int group_read_support(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k
     run.lap("  strain read support");
     return 0;
 }
+// --strain-depth for the same species and on the same coverage result: Sel_s = the group's rows (pass_g)
+int group_depth(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
+    constexpr size_t PER = 4 * PANTAX_HIP_DEPTH_BINS;   // u64 per entry and per species: two histograms of [96]{n_nodes, len}
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint64_t> s_off(Sg + 1, 0);
+    std::vector<uint32_t> s_hap;
+    const size_t entry0 = sh.dp_hap.size() / PER;   // entries of the groups before
+    for (uint32_t k = k0; k < k1; ++k) {
+        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
+            if (pass_g[h]) { sh.dp_entry[h] = (int64_t)(entry0 + s_hap.size()); s_hap.push_back((uint32_t)(h - sh.hap_off[k])); }
+        s_off[k - k0 + 1] = s_hap.size();
+    }
+    const pantax_hip_evidence_set set{Sg, s_off.data(), s_hap.data()};
+    sh.dp_hap.resize(PER * (entry0 + s_hap.size()));
+    PTX_TRY(pantax_hip_strain_depth(run.ctx, db, &set, sh.dp_hap.data() + PER * entry0, sh.dp_species.data() + PER * (size_t)k0));
+    run.lap("  strain depth");
+    return 0;
+}
 // one pass: sources, parts, groups; per group the loader hand-over, then binning against the selected ranges, index, coverage, strain step
 int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, ShardResult &sh) {
     const uint32_t Ss = (uint32_t)sn.sel.size();
@@ -263,6 +281,7 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
         sh.sup_pair_off.assign(Su, 0); sh.sup_K.assign(Su, 0);
     }
     if (run.p.ev_run) { sh.ev_entry.assign(sh.hap_names.size(), -1); sh.ev_species.assign(12 * (size_t)Su, 0); }
+    if (run.p.dp_run) { sh.dp_entry.assign(sh.hap_names.size(), -1); sh.dp_species.assign(4 * PANTAX_HIP_DEPTH_BINS * (size_t)Su, 0); }
     const std::vector<Group> groups = make_groups(run.ctx, parts);
     const bool piped = groups.size() > 1;
     if (piped && !run.ctx->stream_up) PTX_HIP(run.ctx, hipStreamCreateWithFlags(&run.ctx->stream_up, hipStreamNonBlocking));
@@ -307,13 +326,14 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
                                     run.cfg->sample_test ? 500 : run.cfg->sample_nodes, run.cfg->solver_semantics};
         PTX_TRY(pantax_hip_strain_profile(run.ctx, db, &sc, nullptr, cov.data() + k0, sh.met.data() + sh.hap_off[k0], sh.info.data() + k0));
         run.lap("strain step");
-        if (run.p.rs_run || run.p.ct_run || run.p.ev_run || run.p.sup_run) {   // the four reports on the group's rows of the strain table, decided once
+        if (run.p.rs_run || run.p.ct_run || run.p.ev_run || run.p.sup_run || run.p.dp_run) {   // the five reports on the group's rows of the strain table, decided once
             std::vector<uint8_t> pass_g;
             PTX_TRY(group_pass_bits(run, k0, k1, sh, pass_g));
             if (run.p.rs_run) PTX_TRY(group_read_strains(run, in, db, k0, k1, pass_g, sh));
             if (run.p.ct_run) PTX_TRY(group_cov_track(run, db, k0, k1, pass_g, sh));
             if (run.p.ev_run) PTX_TRY(group_evidence(run, db, k0, k1, pass_g, sh));
             if (run.p.sup_run) PTX_TRY(group_read_support(run, in, db, k0, k1, pass_g, sh));
+            if (run.p.dp_run) PTX_TRY(group_depth(run, db, k0, k1, pass_g, sh));
         }
         if (run.cfg->image_cache == 2) {   // leave images behind for the next run
             for (uint32_t k = k0; k < k1; ++k)

@@ -374,6 +374,21 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_evidence(self.ctx, self.db, C.byref(cs), p(hap) if len(sh) else None, p(species) if self.S else None))
         return hap, species
 
+    def strain_depth(self, sel_off, sel_hap, species=True):
+        """Per-strain depth distribution (pantax_hip_strain_depth) of the coverage result get_node_abundances left on the device.
+        sel_off [S+1], sel_hap as for strain_evidence -> (hap uint64 [C, 2, 96, 2]: the histograms all / private of every selection entry,
+        species uint64 [S, 2, 96, 2]: total / orphan), per bin of depth_bin {n_nodes, len}.  species=False: the species histograms are not
+        computed (species_out = NULL) and None is returned in their place."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("strain_depth: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        cs = _ffi.EvidenceSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None)
+        hap = np.zeros((len(sh), 2, _ffi.DEPTH_BINS, 2), dtype=np.uint64)
+        sp = np.zeros((self.S, 2, _ffi.DEPTH_BINS, 2), dtype=np.uint64) if species else None
+        self._check(self.lib.pantax_hip_strain_depth(self.ctx, self.db, C.byref(cs), p(hap) if len(sh) else None, p(sp) if species and self.S else None))
+        return hap, sp
+
     def trio_nodes_info(self, fetch=True):
         n = C.c_uint64(0)
         self._check(self.lib.pantax_hip_trio_index(self.ctx, self.db, C.byref(n)))
@@ -528,13 +543,15 @@ class Engine:
                 mode=2, sample_nodes=0, designated_species=None, zip="serialize", out_binning_file=None,
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
-                strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None):
+                strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
+                strain_depth_file=None):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
         (--read-strains; one rank only).  strain_coverage_file: path of the per-strain windowed coverage track (--strain-coverage; one rank
         only), strain_coverage_window its window in bases (0: 10000).  strain_evidence_file: path of the per-strain node evidence report
-        (--strain-evidence; one rank only).  strain_read_support_file: path of the per-strain read support report (--strain-read-support; one rank only)."""
+        (--strain-evidence; one rank only).  strain_read_support_file: path of the per-strain read support report (--strain-read-support; one rank only).
+        strain_depth_file: path of the per-strain depth distribution report (--strain-depth; one rank only)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -547,7 +564,8 @@ class Engine:
             image_cache=int(image_cache), sample_test=int(sample_test), solver_semantics=int(solver_semantics),
             minimization_min_cov=float(minimization_min_cov), read_strain_file=enc(read_strain_file),
             strain_coverage_file=enc(strain_coverage_file), strain_coverage_window=int(strain_coverage_window),
-            strain_evidence_file=enc(strain_evidence_file), strain_read_support_file=enc(strain_read_support_file))
+            strain_evidence_file=enc(strain_evidence_file), strain_read_support_file=enc(strain_read_support_file),
+            strain_depth_file=enc(strain_depth_file))
         cb = None
         if allreduce is not None:   # allreduce(np.ndarray float64) sums it in place over the ranks
             def _cb(_user, buf, n):
@@ -669,6 +687,34 @@ class Engine:
         if n < 0:
             self._check(n)
         return {names[i].decode(): (int(launches[i]), float(ms[i])) for i in range(min(n, cap))}
+
+
+def depth_bin(d):
+    """pantax_hip_depth_bin: the histogram bin (0 .. 95) of a node depth (any integer 0 <= d < 2^64).  Host only: no Engine is needed."""
+    return int(_ffi.load().pantax_hip_depth_bin(int(d)))
+
+
+def depth_bin_range(b):
+    """pantax_hip_depth_bin_range: (lo, hi) of bin b -- its depths are lo <= d < hi (bin 95: up to hi = 2^64 - 1).  ValueError for b > 95."""
+    lo, hi = C.c_uint64(0), C.c_uint64(0)
+    if _ffi.load().pantax_hip_depth_bin_range(int(b), C.byref(lo), C.byref(hi)) != 0:
+        raise ValueError("depth_bin_range: bin %r" % (b,))
+    return int(lo.value), int(hi.value)
+
+
+def depth_quantile(hist, per_mille):
+    """pantax_hip_depth_quantile: the bin of the length-weighted quantile of one histogram [96, 2] ({n_nodes, len} per bin), None when it holds no
+    length.  ValueError for per_mille > 1000."""
+    h = as_c(hist, np.uint64)
+    if h.shape != (_ffi.DEPTH_BINS, 2):
+        raise ValueError("depth_quantile: the histogram is [96, 2]")
+    out = C.c_uint32(0)
+    rc = _ffi.load().pantax_hip_depth_quantile(p(h), int(per_mille), C.byref(out))
+    if rc == _ffi.DEPTH_NONE:
+        return None
+    if rc != 0:
+        raise ValueError("depth_quantile: per_mille %r" % (per_mille,))
+    return int(out.value)
 
 
 def metrics_to_dicts(met, n=None):
