@@ -328,6 +328,49 @@ uint32_t pantax_hip_depth_bin(uint64_t d);
 int pantax_hip_depth_bin_range(uint32_t bin, uint64_t *lo, uint64_t *hi);
 int pantax_hip_depth_quantile(const uint64_t *hist /*[96][2]*/, uint32_t per_mille, uint32_t *bin_out);
 
+/* ---- unreported-strain near misses (the --strain-near-miss report; not a stage of the reference): the evidence call's `orphan` is coverage on nodes
+ * that no reported strain walks, "the sign of a strain that is in the sample and not in the table".  This call says which unreported haplotypes of the
+ * db would explain it.  For a species s of the db:
+ *   Sel_s  = the reported haplotypes, K_s = |Sel_s|;   Cand_s = the candidates, J_s = |Cand_s|.  Both hold species-local haplotype indices in any
+ *            order; a haplotype may not repeat within Sel_s or within Cand_s, and no haplotype may be in both.
+ * Every node v of s is counted once, whether or not any walk visits it:
+ *   M(v) = { h in Sel_s : the walk of h visits v at least once },  m(v) = |M(v)| -- exactly the node-level membership of pantax_hip_strain_evidence
+ *          (a node walked twice counts once);
+ *   N(v) = { h in Cand_s : the walk of h visits v at least once }, n(v) = |N(v)|;
+ *   Q(v) = (1, node_len[v], node_base_cov[v], bases_per_node[v]), the last two as pantax_hip_node_coverage leaves them; all four u64.
+ * Every output is a sum of Q(v), its four numbers in the order { n_nodes, len, covered, bases }:
+ *   per candidate entry c (haplotype h), cand_out [J][2][4] in the order of cand_hap:
+ *     novel[c]     = sum over m(v) = 0 and h in N(v)   -- the nodes h walks that no reported strain walks;
+ *     exclusive[c] = sum over m(v) = 0 and N(v) = {h}  -- the orphan nodes that, among the candidates, only h walks;
+ *   per species s, species_out [S][3][4]:
+ *     orphan[s]    = sum over m(v) = 0                 -- the evidence call's orphan, element for element;
+ *     claimed[s]   = sum over m(v) = 0 and n(v) >= 1;
+ *     contested[s] = sum over m(v) = 0 and n(v) >= 2.
+ * Integers only: results are exact and independent of any order.  Identities: exclusive <= novel; claimed = contested + the sum of exclusive over the
+ * species' candidates; contested <= claimed <= orphan; J_s = 1 gives novel = exclusive = claimed and contested = 0; novel[c] is at most the evidence
+ * call's all of the same haplotype; with Sel_s empty every node of the species is an orphan.
+ * The caller knows both sizes (J = cand_off[S]): there is no sizing call.  An empty Sel, an empty Cand, both empty, a species with neither: all fine,
+ * orphan is always written.  State rules of pantax_hip_strain_evidence: PANTAX_HIP_E_STATE behind a resident step and before any coverage pass.
+ * PANTAX_HIP_E_INVALID: n_species different from the db's, a haplotype index out of range, a haplotype twice within Sel_s or within Cand_s, a
+ * haplotype in both.  On an error the output arrays are left as given.
+ * The option near_miss_route=walk (pantax_hip_set_option) takes every species' membership from the walks of Sel_s ++ Cand_s, as evidence_route=walk
+ * does; near_miss_words=N (1 .. 4) caps the candidate mask words a wave counts in one pass over its nodes (default 4: 256 candidates). */
+typedef struct {
+    uint32_t n_species;        /* must equal the db's */
+    const uint64_t *sel_off;   /* [S+1] species s owns the reported entries [sel_off[s], sel_off[s+1]) */
+    const uint32_t *sel_hap;   /* species-local haplotype index, any order, no repeats within a species */
+    const uint64_t *cand_off;  /* [S+1] species s owns the candidate entries [cand_off[s], cand_off[s+1]) */
+    const uint32_t *cand_hap;  /* [J] species-local haplotype index, any order, no repeats within a species, none of sel_hap's of the species */
+} pantax_hip_near_miss_set;
+int pantax_hip_strain_near_miss(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_near_miss_set *sel,
+                                uint64_t *cand_out /*[J][2][4]: novel, exclusive*/, uint64_t *species_out /*[S][3][4]: orphan, claimed, contested*/);
+/* Host-only helper (no ctx, no GPU): the order in which one species' candidates are reported.  cand_hap [n_cand] and cand_out [n_cand][2][4] are the
+ * species' stretch of the call above.  rank_out [n_cand] receives candidate positions (0 .. n_cand - 1) ordered by novel.bases descending, then
+ * novel.covered descending, then haplotype index ascending; candidates with novel.bases = 0 are left out; only the first `top` are kept (0 keeps
+ * all); *n_out = the number written.  A null pointer among the four (whatever n_cand): PANTAX_HIP_E_INVALID, nothing written. */
+int pantax_hip_near_miss_rank(uint32_t n_cand, const uint32_t *cand_hap, const uint64_t *cand_out /*[n_cand][2][4]*/, uint32_t top,
+                              uint32_t *rank_out /*[n_cand]*/, uint32_t *n_out);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -549,6 +592,20 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
      * (pantax_hip_depth_quantile at 50, 250, 500, 750, 950 per mille), q50_hi = hi(bin) of the median's bin: the resolution of the median.  Every quantile
      * column is "-" when len = 0.  Written only by a run that performs the strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
     const char *strain_depth_file;
+    /* --strain-near-miss: path of the unreported-strain near-miss report (pantax_hip_strain_near_miss over every group of species, right behind the
+     * group's strain step; NULL or "None" = off).  Sel_s = the species' rows of strain_abundance.txt.  Cand_s of a species of <= 64 haplotypes = every other
+     * haplotype of the species; of a wider species = the unreported haplotypes that carry PANTAX_HIP_HAS_FRACTION, by unique_trio_nodes_fraction descending
+     * then index ascending, the first 256 (the cap bounds the node-mask arena).  TSV with a header, long format: species_taxid, strain_taxid, genome_ID, rank,
+     * class, n_nodes, len, covered, bases, depth, breadth, share, stage, unique_trio_nodes_fraction, frequencies_mean, first_sol, second_sol.  Candidate rows
+     * first: per species in the order the run took them, the candidates pantax_hip_near_miss_rank keeps with strain_near_miss_top, rank from 1, classes
+     * "novel", "exclusive", "all" each (all = the evidence call's all of the haplotype); depth = bases / len, breadth = covered / len ("-" when len = 0);
+     * share = bases / the species' orphan bases ("-" on class all and when that is 0); stage = where the haplotype left the path: first_filter (no
+     * PANTAX_HIP_HAS_FIRST), second_filter (HAS_FIRST, no HAS_SECOND), table_filter (HAS_SECOND, not a row of the table); the four metric columns are "-"
+     * where their has bit is clear; strain_taxid / genome_ID = the first genomes_info.txt row of the haplotype (empty without one).  Then every species
+     * that went through a strain step: classes "orphan", "claimed", "contested" with strain, rank, stage and metric columns "-", share = bases / orphan
+     * bases.  Written only by a run that performs the strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
+    const char *strain_near_miss_file;
+    int32_t strain_near_miss_top;   /* --strain-near-miss-top: candidates printed per species; 0 = the default of 5; negative: PANTAX_HIP_E_INVALID */
 } pantax_hip_profiling_config;
 
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in

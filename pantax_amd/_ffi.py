@@ -23,7 +23,8 @@ SYMBOLS = [
     "pantax_hip_gaf_load", "pantax_hip_gaf_load_device", "pantax_hip_reads_load_gaf", "pantax_hip_reads_set_flags", "pantax_hip_gaf_view", "pantax_hip_gaf_free",
     "pantax_hip_graph_load", "pantax_hip_graph_view", "pantax_hip_graph_free", "pantax_hip_format_f64",
     "pantax_hip_read_strains", "pantax_hip_strain_cov_track", "pantax_hip_strain_evidence", "pantax_hip_strain_read_support", "pantax_hip_strain_depth",
-    "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
+    "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_strain_near_miss", "pantax_hip_near_miss_rank",
+    "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
 
@@ -103,7 +104,8 @@ class ProfilingConfig(C.Structure):
                 ("allreduce_sum", C.c_void_p), ("comm_user", C.c_void_p), ("alltoallv", C.c_void_p), ("comm_device_buffers", C.c_int32),
                 ("sample_test", C.c_int32), ("solver_semantics", C.c_int32), ("minimization_min_cov", C.c_double),
                 ("read_strain_file", C.c_char_p), ("strain_coverage_file", C.c_char_p), ("strain_coverage_window", C.c_int64),
-                ("strain_evidence_file", C.c_char_p), ("strain_read_support_file", C.c_char_p), ("strain_depth_file", C.c_char_p)]
+                ("strain_evidence_file", C.c_char_p), ("strain_read_support_file", C.c_char_p), ("strain_depth_file", C.c_char_p),
+                ("strain_near_miss_file", C.c_char_p), ("strain_near_miss_top", C.c_int32)]
 
 
 class ReadStrainSet(C.Structure):
@@ -116,6 +118,10 @@ class CovTrackSet(C.Structure):
 
 class EvidenceSet(C.Structure):
     _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p)]
+
+
+class NearMissSet(C.Structure):
+    _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p), ("cand_off", C.c_void_p), ("cand_hap", C.c_void_p)]
 
 
 # int (*allreduce_sum)(void *user, double *buf, uint64_t n)
@@ -157,6 +163,10 @@ def load():
         _lib.pantax_hip_strain_evidence.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_void_p]
         _lib.pantax_hip_strain_depth.restype = C.c_int
         _lib.pantax_hip_strain_depth.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_strain_near_miss.restype = C.c_int
+        _lib.pantax_hip_strain_near_miss.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(NearMissSet), C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_near_miss_rank.restype = C.c_int
+        _lib.pantax_hip_near_miss_rank.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
         _lib.pantax_hip_depth_bin.restype = C.c_uint32
         _lib.pantax_hip_depth_bin.argtypes = [C.c_uint64]
         _lib.pantax_hip_depth_bin_range.restype = C.c_int

@@ -131,4 +131,22 @@ int pantax_hip_depth_quantile(const uint64_t *hist, uint32_t per_mille, uint32_t
     return PANTAX_HIP_E_STATE;   // not reached: cum = T >= target at the last bin
 }
 
+// ---- the host side of the near-miss report: the order in which one species' candidates are printed
+int pantax_hip_near_miss_rank(uint32_t n_cand, const uint32_t *cand_hap, const uint64_t *cand_out, uint32_t top, uint32_t *rank_out, uint32_t *n_out) {
+    if (!cand_hap || !cand_out || !rank_out || !n_out) return PANTAX_HIP_E_INVALID;
+    std::vector<uint32_t> ord;
+    for (uint32_t c = 0; c < n_cand; ++c)
+        if (cand_out[8 * (size_t)c + 3]) ord.push_back(c);   // novel.bases > 0
+    std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
+        const uint64_t *qa = cand_out + 8 * (size_t)a, *qb = cand_out + 8 * (size_t)b;   // novel {n_nodes, len, covered, bases}
+        if (qa[3] != qb[3]) return qa[3] > qb[3];
+        if (qa[2] != qb[2]) return qa[2] > qb[2];
+        return cand_hap[a] != cand_hap[b] ? cand_hap[a] < cand_hap[b] : a < b;
+    });
+    if (top && ord.size() > top) ord.resize(top);
+    std::copy(ord.begin(), ord.end(), rank_out);
+    *n_out = (uint32_t)ord.size();
+    return 0;
+}
+
 }  // extern "C"

@@ -79,6 +79,14 @@ int check_args(Run &run) {
     if (p.want_dp && (W > 1 || p.sharded))
         return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain depth distribution report (strain_depth_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
                     p.sharded ? ", sharded" : "");
+    // --strain-near-miss: the same again -- a species' orphan nodes and its candidates live on the rank that owns it
+    p.nm_path = opt(cfg->strain_near_miss_file);
+    p.want_nm = !p.nm_path.empty() && p.nm_path != "None";
+    if (p.want_nm && (W > 1 || p.sharded))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the unreported-strain near-miss report (strain_near_miss_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
+                    p.sharded ? ", sharded" : "");
+    if (p.want_nm && cfg->strain_near_miss_top < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "profile: strain_near_miss_top %d", (int)cfg->strain_near_miss_top);
+    p.nm_top = p.want_nm && cfg->strain_near_miss_top > 0 ? (uint32_t)cfg->strain_near_miss_top : 5u;
     p.db_dir = opt(cfg->db); p.wd = opt(cfg->wd); p.out_dir = opt(cfg->output_dir);
     if (p.out_dir.empty()) p.out_dir = p.wd;
     if (!is_dir(p.db_dir)) return fail(ctx, PANTAX_HIP_E_IO, "Specified PanTax database directory '%s' is not a valid directory path", p.db_dir.c_str());
@@ -110,11 +118,12 @@ int decide_resume(Run &run) {
     run.p.ev_run = run.p.want_ev && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.sup_run = run.p.want_sup && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.dp_run = run.p.want_dp && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
+    run.p.nm_run = run.p.want_nm && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
     run.p.want_report = run.p.full_path && !run.p.report.empty() && run.p.report != "None";
     return 0;
 }
 void rs_skipped(const RunPlan &p) {
-    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr, p.want_ev ? &p.ev_path : nullptr, p.want_sup ? &p.sup_path : nullptr, p.want_dp ? &p.dp_path : nullptr})
+    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr, p.want_ev ? &p.ev_path : nullptr, p.want_sup ? &p.sup_path : nullptr, p.want_dp ? &p.dp_path : nullptr, p.want_nm ? &p.nm_path : nullptr})
         if (f) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", f->c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
@@ -774,6 +783,40 @@ int depth_report(Run &run, const Ingest &in, const Selection &sn, const ShardRes
     run.lap("strain depth report");
     return 0;
 }
+// --strain-near-miss: per species of the shard, in the order it went through the device, the candidates group_near_miss kept, in rank order, classes novel,
+// exclusive, all each; then {orphan, claimed, contested} of every species.  strain_taxid / genome_ID: the first genomes_info.txt row of the haplotype
+int near_miss_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, const std::vector<GenomeRow> &genomes) {
+    std::unordered_map<std::string, size_t> first_genome;
+    for (size_t i = genomes.size(); i-- > 0;) first_genome[genomes[i].hap_id] = i;
+    std::ofstream f(run.p.nm_path);
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.nm_path.c_str());
+    f << "species_taxid\tstrain_taxid\tgenome_ID\trank\tclass\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\tshare\tstage\tunique_trio_nodes_fraction\tfrequencies_mean\tfirst_sol\tsecond_sol\n";
+    const uint32_t Su = (uint32_t)sh.use.size();
+    for (uint32_t k = 0; k < Su; ++k) {
+        const std::string &species = in.ranges[sn.sel[sh.use[k]]].species;
+        const uint64_t orphan_bases = sh.nm_species[12 * (size_t)k + 3];
+        for (uint64_t i = sh.nm_row_off[k]; i < sh.nm_row_off[k + 1]; ++i) {
+            const ShardResult::NearMissRow &r = sh.nm_rows[i];
+            const auto it = first_genome.find(sh.hap_names[r.hap]);
+            const GenomeRow *gr = it != first_genome.end() ? &genomes[it->second] : nullptr;
+            const uint32_t rank = (uint32_t)(i - sh.nm_row_off[k]) + 1;
+            f << near_miss_row_text(species, gr, &sh.met[r.hap], rank, "novel", r.q, true, orphan_bases) << '\n'
+              << near_miss_row_text(species, gr, &sh.met[r.hap], rank, "exclusive", r.q + 4, true, orphan_bases) << '\n'
+              << near_miss_row_text(species, gr, &sh.met[r.hap], rank, "all", r.q + 8, false, orphan_bases) << '\n';
+        }
+    }
+    for (uint32_t k = 0; k < Su; ++k) {
+        const std::string &species = in.ranges[sn.sel[sh.use[k]]].species;
+        const uint64_t *q = sh.nm_species.data() + 12 * (size_t)k;
+        f << near_miss_row_text(species, nullptr, nullptr, 0, "orphan", q, true, q[3]) << '\n'
+          << near_miss_row_text(species, nullptr, nullptr, 0, "claimed", q + 4, true, q[3]) << '\n'
+          << near_miss_row_text(species, nullptr, nullptr, 0, "contested", q + 8, true, q[3]) << '\n';
+    }
+    f.close();
+    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.nm_path.c_str());
+    run.lap("strain near-miss report");
+    return 0;
+}
 // The phases in order.  `rc` is this rank's status since the last collective (RankComm's rule): PTX_TRY where a phase has ended in the collective
 // that carried it, an assignment where the next collective carries it.
 int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
@@ -822,7 +865,8 @@ int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
     if (p.ct_run) PTX_TRY(cov_track_report(run, in, sn, sh, track_rows));
     if (p.ev_run) PTX_TRY(evidence_report(run, in, sn, sh, track_rows));
     if (p.sup_run) PTX_TRY(read_support_report(run, in, sn, sh, track_rows));
-    return p.dp_run ? depth_report(run, in, sn, sh, track_rows) : 0;
+    if (p.dp_run) PTX_TRY(depth_report(run, in, sn, sh, track_rows));
+    return p.nm_run ? near_miss_report(run, in, sn, sh, genomes) : 0;
 }
 
 }  // namespace

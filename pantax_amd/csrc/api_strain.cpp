@@ -600,4 +600,23 @@ int pantax_hip_strain_depth(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax
     return depth_launch(ctx, db, sel->sel_off, sel->sel_hap, hap_out, species_out);
 }
 
+int pantax_hip_strain_near_miss(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_near_miss_set *sel, uint64_t *cand_out, uint64_t *species_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off || !sel->cand_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_near_miss: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_near_miss", sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_near_miss", sel->sel_off, sel->sel_hap));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_near_miss (candidates)", sel->cand_off, sel->cand_hap));
+    std::vector<uint8_t> reported;
+    for (uint32_t s = 0; s < db->S; ++s) {   // both sets are in range and free of repeats: are they disjoint?
+        reported.assign(db->h_hap_off[s + 1] - db->h_hap_off[s], 0);
+        for (uint64_t c = sel->sel_off[s]; c < sel->sel_off[s + 1]; ++c) reported[sel->sel_hap[c]] = 1;
+        for (uint64_t c = sel->cand_off[s]; c < sel->cand_off[s + 1]; ++c)
+            if (reported[sel->cand_hap[c]]) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_near_miss: haplotype %u of species %u is reported and a candidate", sel->cand_hap[c], s);
+    }
+    if ((sel->cand_off[db->S] && !cand_out) || (db->S && !species_out)) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_near_miss: null output array");
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_near_miss"));
+    return near_miss_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->cand_off, sel->cand_hap, cand_out, species_out);
+}
+
 }  // extern "C"

@@ -31,6 +31,11 @@ static void usage() {
             "                     (class all) and over those no other reported strain of its species walks (private), then per species over every node\n"
             "                     (total) and over the nodes no reported strain walks (orphan): n_nodes, len, len at depth 0, the length-weighted quantiles\n"
             "                     q05 q25 q50 q75 q95 as the lower bound of their bin, and the upper bound of the median's bin (one rank only)\n"
+            "  --strain-near-miss F   unreported-strain near misses: per species the unreported haplotypes of the db that walk the most aligned bases on nodes\n"
+            "                     no row of strain_abundance.txt walks (class novel), the part no other candidate walks (exclusive) and their whole walk (all),\n"
+            "                     with the filter that dropped them; then per species the orphan nodes, those some candidate walks (claimed), those\n"
+            "                     several do (contested) (one rank only)\n"
+            "  --strain-near-miss-top N   candidates printed per species (default 5)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -106,6 +111,8 @@ int main(int argc, char **argv) {
         else if (a == "--strain-evidence") c.strain_evidence_file = next();
         else if (a == "--strain-read-support") c.strain_read_support_file = next();
         else if (a == "--strain-depth") c.strain_depth_file = next();
+        else if (a == "--strain-near-miss") c.strain_near_miss_file = next();
+        else if (a == "--strain-near-miss-top") c.strain_near_miss_top = atoi(next());
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

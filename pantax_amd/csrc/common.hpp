@@ -146,6 +146,8 @@ struct CtxConfig {
     std::string evidence_route;      // "walk": the node evidence report takes the membership of every species from its selected walks (the compact masks), not from the node -> haplotype words
     std::string depth_route;         // "walk": the depth distribution report takes the membership of every species from its selected walks (the compact masks), not from the node -> haplotype words
     int depth_grid = 0;              // > 0: at most this many workgroups in the depth distribution pass (tests: 1 sends every item, and every change of species and tile, through one workgroup)
+    std::string near_miss_route;     // "walk": the near-miss report takes the membership of every species from the walks of Sel ++ Cand (the compact masks), not from the node -> haplotype words
+    int near_miss_words = 0;         // 1 .. 4: candidate mask words a wave of the near-miss pass counts in one pass over its nodes (0 = 4; tests: 1 sends a species of 200 haplotypes through the tiled passes)
     std::string read_strain_route;   // "walk": the per-read strain masks of every species from its candidates' walks (stage_read_strain.hip), not from the node -> haplotype words
     bool cov_general = false;        // every group through the kernel of the longer walks (coverage_fast_kernel<.., LONG>; cov_long=step: coverage_step_kernel)
     std::string cov_long;            // "step": round 5's coverage_step_kernel for the groups that hold steps of walks of more than 64 steps
@@ -708,6 +710,9 @@ struct WalkMasks {
 int evidence_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t *hap_out, uint64_t *species_out);
 // stage_depth.hip (pantax_hip_strain_depth): selection validated by the caller; hap_out [C][2][96][2], species_out [S][2][96][2] or null
 int depth_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t *hap_out, uint64_t *species_out);
+// stage_near_miss.hip (pantax_hip_strain_near_miss): both sets validated by the caller; cand_out [J][2][4], species_out [S][3][4]
+int near_miss_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *cand_off, const uint32_t *cand_hap, uint64_t *cand_out,
+                     uint64_t *species_out);
 // stage_cov_track.hip (pantax_hip_strain_cov_track): selection validated by the caller; win_off_out [C+1] is always written, the four arrays only when the
 // windows fit `cap`
 int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, uint32_t *n_nodes_out,

@@ -87,4 +87,29 @@ std::string strain_row_text(const std::string &species, const GenomeRow *gr, con
     s += '\t' + cell(m.has & PANTAX_HIP_HAS_TOTAL_DIFF, m.total_cov_diff, rnd);
     return s;
 }
+const char *near_miss_stage(const pantax_hip_hap_metrics &m) {
+    if (!(m.has & PANTAX_HIP_HAS_FIRST)) return "first_filter";
+    return (m.has & PANTAX_HIP_HAS_SECOND) ? "table_filter" : "second_filter";   // (a survivor the highs semantics leave without a second_sol counts with the second filter)
+}
+std::string near_miss_row_text(const std::string &species, const GenomeRow *gr, const pantax_hip_hap_metrics *m, uint32_t rank, const char *cls, const uint64_t *q,
+                               bool with_share, uint64_t orphan_bases) {
+    const auto metric = [m](uint32_t bit, double v) { return m && (m->has & bit) ? fmt_f64(v) : std::string("-"); };
+    std::string s = species;
+    if (m) {
+        s += '\t'; if (gr) s += gr->strain_taxid;
+        s += '\t'; if (gr) s += gr->genome_id;
+        s += '\t' + std::to_string(rank);
+    } else s += "\t-\t-\t-";
+    s += '\t'; s += cls;
+    for (int i = 0; i < 4; ++i) s += '\t' + std::to_string(q[i]);
+    if (q[1]) s += '\t' + fmt_f64((double)q[3] / (double)q[1]) + '\t' + fmt_f64((double)q[2] / (double)q[1]);
+    else s += "\t-\t-";
+    s += '\t' + (with_share && orphan_bases ? fmt_f64((double)q[3] / (double)orphan_bases) : std::string("-"));
+    s += '\t'; s += m ? near_miss_stage(*m) : "-";
+    s += '\t' + metric(PANTAX_HIP_HAS_FRACTION, m ? m->unique_trio_nodes_fraction : 0.0);
+    s += '\t' + metric(PANTAX_HIP_HAS_FREQ_MEAN, m ? m->frequencies_mean : 0.0);
+    s += '\t' + metric(PANTAX_HIP_HAS_FIRST, m ? m->first_sol : 0.0);
+    s += '\t' + metric(PANTAX_HIP_HAS_SECOND, m ? m->second_sol : 0.0);
+    return s;
+}
 }  // namespace ptx

@@ -26,7 +26,9 @@ struct RunPlan {
     bool want_ev = false, ev_run = false;                               // ev_run: ... and writes the --strain-evidence report
     bool want_sup = false, sup_run = false;                             // sup_run: ... and writes the --strain-read-support report
     bool want_dp = false, dp_run = false;                               // dp_run: ... and writes the --strain-depth report
-    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, ev_path, sup_path, dp_path, gaf_path;
+    bool want_nm = false, nm_run = false;                               // nm_run: ... and writes the --strain-near-miss report
+    uint32_t nm_top = 5;                                                // candidates it prints per species
+    std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, rs_path, ct_path, ev_path, sup_path, dp_path, nm_path, gaf_path;
 };
 // what every phase is handed: the two handles, the plan, the ranks, the trace clock
 struct Run { pantax_hip_ctx *ctx; const pantax_hip_profiling_config *cfg; RunPlan p; RankComm comm; Lap lap; };
@@ -83,9 +85,14 @@ struct ShardResult {
     // owns dp_species[384k .. 384k + 384) = {total, orphan}
     std::vector<int64_t> dp_entry;
     std::vector<uint64_t> dp_hap, dp_species;
+    // --strain-near-miss: species k owns nm_species[12k .. 12k + 12) = {orphan, claimed, contested} and the printed candidates nm_rows[nm_row_off[k] ..
+    // nm_row_off[k + 1]) in rank order: the haplotype ([hap_names]) and q = {novel, exclusive, all} x {n_nodes, len, covered, bases}
+    struct NearMissRow { uint64_t hap; uint64_t q[12]; };
+    std::vector<uint64_t> nm_species, nm_row_off;
+    std::vector<NearMissRow> nm_rows;
     bool image_fault = false;          // rc is the load-time refusal of a group that holds images ...
     std::string fault_images;          // ... these (the check names a haplotype, not a file), for the warning
 };
-// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, node evidence, read support, depth distribution, image write-back)
+// profile_shard.cpp: everything a rank does on its own shard (sources, groups, loader, device sequence, read strains, coverage track, node evidence, read support, depth distribution, near misses, image write-back)
 ShardResult run_shard(Run &run, Ingest &in, const Selection &sn, bool use_images);
 }  // namespace ptx

@@ -1,5 +1,5 @@
 // profile_shard.cpp -- run_shard (profile_run.hpp): a6 - a14 of the file seam for this rank's selected species.  Where every graph comes from
-// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains, the strain coverage track, the node evidence, the read support and the depth distribution per group, image write-back.
+// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains, the strain coverage track, the node evidence, the read support, the depth distribution and the near misses per group, image write-back.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -229,6 +229,57 @@ int group_depth(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std
     run.lap("  strain depth");
     return 0;
 }
+// --strain-near-miss for the same species and on the same coverage result: Sel_s = the group's rows (pass_g); Cand_s = every other haplotype of a species of
+// <= 64 haplotypes, of a wider one the unreported haplotypes that have a unique_trio_nodes_fraction, the 256 largest (ties: lower index first) -- the cap
+// bounds the node-mask arena of the walk route at four words a node.  The candidates pantax_hip_near_miss_rank keeps are the ones printed; their `all`
+// comes from one evidence call of the group over them alone
+int group_near_miss(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
+    constexpr uint64_t WIDE_CAP = 256;
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint64_t> s_off(Sg + 1, 0), c_off(Sg + 1, 0);
+    std::vector<uint32_t> s_hap, c_hap;
+    for (uint32_t k = k0; k < k1; ++k) {
+        const uint64_t h0 = sh.hap_off[k], nh = sh.hap_off[k + 1] - h0;
+        const size_t at = c_hap.size();
+        for (uint64_t h = h0; h < h0 + nh; ++h) {
+            if (pass_g[h]) s_hap.push_back((uint32_t)(h - h0));
+            else if (nh <= 64 || (sh.met[h].has & PANTAX_HIP_HAS_FRACTION)) c_hap.push_back((uint32_t)(h - h0));
+        }
+        if (nh > 64) {
+            std::stable_sort(c_hap.begin() + at, c_hap.end(), [&](uint32_t a, uint32_t b) { return sh.met[h0 + a].unique_trio_nodes_fraction > sh.met[h0 + b].unique_trio_nodes_fraction; });
+            if (c_hap.size() - at > WIDE_CAP) c_hap.resize(at + WIDE_CAP);
+        }
+        s_off[k - k0 + 1] = s_hap.size(); c_off[k - k0 + 1] = c_hap.size();
+    }
+    const pantax_hip_near_miss_set set{Sg, s_off.data(), s_hap.data(), c_off.data(), c_hap.data()};
+    std::vector<uint64_t> c_out(8 * c_hap.size());
+    PTX_TRY(pantax_hip_strain_near_miss(run.ctx, db, &set, c_out.data(), sh.nm_species.data() + 12 * (size_t)k0));
+    // the printed candidates of every species, in rank order
+    std::vector<uint64_t> p_off(Sg + 1, 0);
+    std::vector<uint32_t> p_hap, rank;
+    const size_t row0 = sh.nm_rows.size();
+    for (uint32_t k = k0; k < k1; ++k) {
+        const uint64_t c0 = c_off[k - k0], n = c_off[k - k0 + 1] - c0;
+        uint32_t kept = 0;
+        rank.assign(n ? n : 1, 0);
+        if (n) PTX_TRY(pantax_hip_near_miss_rank((uint32_t)n, c_hap.data() + c0, c_out.data() + 8 * c0, run.p.nm_top, rank.data(), &kept));
+        for (uint32_t i = 0; i < kept; ++i) {
+            ShardResult::NearMissRow r{};
+            r.hap = sh.hap_off[k] + c_hap[c0 + rank[i]];
+            std::copy(c_out.begin() + 8 * (c0 + rank[i]), c_out.begin() + 8 * (c0 + rank[i]) + 8, r.q);
+            sh.nm_rows.push_back(r);
+            p_hap.push_back(c_hap[c0 + rank[i]]);
+        }
+        p_off[k - k0 + 1] = p_hap.size();
+        sh.nm_row_off[k + 1] = sh.nm_rows.size();
+    }
+    const pantax_hip_evidence_set printed{Sg, p_off.data(), p_hap.data()};
+    std::vector<uint64_t> e_hap(8 * p_hap.size()), e_species(12 * (size_t)Sg);
+    PTX_TRY(pantax_hip_strain_evidence(run.ctx, db, &printed, e_hap.data(), e_species.data()));
+    for (size_t i = 0; i < p_hap.size(); ++i) std::copy(e_hap.begin() + 8 * i, e_hap.begin() + 8 * i + 4, sh.nm_rows[row0 + i].q + 8);   // all
+    run.lap("  strain near misses");
+    return 0;
+}
 // one pass: sources, parts, groups; per group the loader hand-over, then binning against the selected ranges, index, coverage, strain step
 int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, ShardResult &sh) {
     const uint32_t Ss = (uint32_t)sn.sel.size();
@@ -282,6 +333,7 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
     }
     if (run.p.ev_run) { sh.ev_entry.assign(sh.hap_names.size(), -1); sh.ev_species.assign(12 * (size_t)Su, 0); }
     if (run.p.dp_run) { sh.dp_entry.assign(sh.hap_names.size(), -1); sh.dp_species.assign(4 * PANTAX_HIP_DEPTH_BINS * (size_t)Su, 0); }
+    if (run.p.nm_run) { sh.nm_species.assign(12 * (size_t)Su, 0); sh.nm_row_off.assign(Su + 1, 0); }
     const std::vector<Group> groups = make_groups(run.ctx, parts);
     const bool piped = groups.size() > 1;
     if (piped && !run.ctx->stream_up) PTX_HIP(run.ctx, hipStreamCreateWithFlags(&run.ctx->stream_up, hipStreamNonBlocking));
@@ -326,7 +378,7 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
                                     run.cfg->sample_test ? 500 : run.cfg->sample_nodes, run.cfg->solver_semantics};
         PTX_TRY(pantax_hip_strain_profile(run.ctx, db, &sc, nullptr, cov.data() + k0, sh.met.data() + sh.hap_off[k0], sh.info.data() + k0));
         run.lap("strain step");
-        if (run.p.rs_run || run.p.ct_run || run.p.ev_run || run.p.sup_run || run.p.dp_run) {   // the five reports on the group's rows of the strain table, decided once
+        if (run.p.rs_run || run.p.ct_run || run.p.ev_run || run.p.sup_run || run.p.dp_run || run.p.nm_run) {   // the six reports on the group's rows of the strain table, decided once
             std::vector<uint8_t> pass_g;
             PTX_TRY(group_pass_bits(run, k0, k1, sh, pass_g));
             if (run.p.rs_run) PTX_TRY(group_read_strains(run, in, db, k0, k1, pass_g, sh));
@@ -334,6 +386,7 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
             if (run.p.ev_run) PTX_TRY(group_evidence(run, db, k0, k1, pass_g, sh));
             if (run.p.sup_run) PTX_TRY(group_read_support(run, in, db, k0, k1, pass_g, sh));
             if (run.p.dp_run) PTX_TRY(group_depth(run, db, k0, k1, pass_g, sh));
+            if (run.p.nm_run) PTX_TRY(group_near_miss(run, db, k0, k1, pass_g, sh));
         }
         if (run.cfg->image_cache == 2) {   // leave images behind for the next run
             for (uint32_t k = k0; k < k1; ++k)

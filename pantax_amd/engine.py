@@ -389,6 +389,21 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_depth(self.ctx, self.db, C.byref(cs), p(hap) if len(sh) else None, p(sp) if species and self.S else None))
         return hap, sp
 
+    def strain_near_miss(self, sel_off, sel_hap, cand_off, cand_hap):
+        """Unreported-strain near misses (pantax_hip_strain_near_miss) of the coverage result get_node_abundances left on the device.
+        sel_off [S+1], sel_hap: the reported haplotypes of every species; cand_off [S+1], cand_hap: the candidates (species-local indices, disjoint from
+        the reported ones) -> (cand uint64 [J, 2, 4]: novel / exclusive of every candidate entry, species uint64 [S, 3, 4]: orphan / claimed /
+        contested), each {n_nodes, len, covered, bases}."""
+        so, sh = as_c(sel_off, np.uint64), as_c(sel_hap, np.uint32)
+        co, ch = as_c(cand_off, np.uint64), as_c(cand_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]) or len(co) != self.S + 1 or len(ch) != int(co[-1]):
+            raise ValueError("strain_near_miss: sel_off / cand_off need S + 1 entries, sel_hap sel_off[-1] and cand_hap cand_off[-1]")
+        cs = _ffi.NearMissSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, co.ctypes.data, ch.ctypes.data if len(ch) else None)
+        cand = np.zeros((len(ch), 2, 4), dtype=np.uint64)
+        species = np.zeros((self.S, 3, 4), dtype=np.uint64)
+        self._check(self.lib.pantax_hip_strain_near_miss(self.ctx, self.db, C.byref(cs), p(cand) if len(ch) else None, p(species) if self.S else None))
+        return cand, species
+
     def trio_nodes_info(self, fetch=True):
         n = C.c_uint64(0)
         self._check(self.lib.pantax_hip_trio_index(self.ctx, self.db, C.byref(n)))
@@ -544,14 +559,15 @@ class Engine:
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
                 strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
-                strain_depth_file=None):
+                strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
         (--read-strains; one rank only).  strain_coverage_file: path of the per-strain windowed coverage track (--strain-coverage; one rank
         only), strain_coverage_window its window in bases (0: 10000).  strain_evidence_file: path of the per-strain node evidence report
         (--strain-evidence; one rank only).  strain_read_support_file: path of the per-strain read support report (--strain-read-support; one rank only).
-        strain_depth_file: path of the per-strain depth distribution report (--strain-depth; one rank only)."""
+        strain_depth_file: path of the per-strain depth distribution report (--strain-depth; one rank only).  strain_near_miss_file: path of the
+        unreported-strain near-miss report (--strain-near-miss; one rank only), strain_near_miss_top the candidates it prints per species (0: 5)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -565,7 +581,8 @@ class Engine:
             minimization_min_cov=float(minimization_min_cov), read_strain_file=enc(read_strain_file),
             strain_coverage_file=enc(strain_coverage_file), strain_coverage_window=int(strain_coverage_window),
             strain_evidence_file=enc(strain_evidence_file), strain_read_support_file=enc(strain_read_support_file),
-            strain_depth_file=enc(strain_depth_file))
+            strain_depth_file=enc(strain_depth_file), strain_near_miss_file=enc(strain_near_miss_file),
+            strain_near_miss_top=int(strain_near_miss_top))
         cb = None
         if allreduce is not None:   # allreduce(np.ndarray float64) sums it in place over the ranks
             def _cb(_user, buf, n):
@@ -715,6 +732,23 @@ def depth_quantile(hist, per_mille):
     if rc != 0:
         raise ValueError("depth_quantile: per_mille %r" % (per_mille,))
     return int(out.value)
+
+
+def near_miss_rank(cand_hap, cand_out, top=0):
+    """pantax_hip_near_miss_rank: the positions of one species' candidates (cand_hap [n], cand_out [n, 2, 4] of strain_near_miss) in the order of the
+    report -- novel bases descending, then novel covered descending, then haplotype index ascending; candidates without novel bases are left out; the
+    first `top` (0: all).  Host only: no Engine is needed."""
+    ch = as_c(cand_hap, np.uint32)
+    co = as_c(cand_out, np.uint64)
+    if co.shape != (len(ch), 2, 4):
+        raise ValueError("near_miss_rank: cand_out is [len(cand_hap), 2, 4]")
+    out = np.zeros(max(len(ch), 1), dtype=np.uint32)
+    n = C.c_uint32(0)
+    one = np.zeros(8, dtype=np.uint64)   # (a zero-length array has no address to hand over)
+    rc = _ffi.load().pantax_hip_near_miss_rank(len(ch), p(ch) if len(ch) else p(out), p(co) if len(ch) else p(one), int(top), p(out), C.byref(n))
+    if rc != 0:
+        raise ValueError("near_miss_rank: refused (%d)" % rc)
+    return out[:n.value].copy()
 
 
 def metrics_to_dicts(met, n=None):
