@@ -143,12 +143,10 @@ struct CtxConfig {
     std::string mask;                // "walk": membership masks from the path walk
     std::string row_sort;            // "radix" / "nodes"
     std::string objective;           // "nodes": the LP objective summed over the nodes
-    std::string evidence_route;      // "walk": the node evidence report takes the membership of every species from its selected walks (the compact masks), not from the node -> haplotype words
-    std::string depth_route;         // "walk": the depth distribution report takes the membership of every species from its selected walks (the compact masks), not from the node -> haplotype words
+    // "walk": the strain report takes the membership of every species from the chosen walks (the compact masks, route 2 of member_plan.hpp), not from the node -> haplotype words
+    std::string read_strain_route, evidence_route, depth_route, near_miss_route;
     int depth_grid = 0;              // > 0: at most this many workgroups in the depth distribution pass (tests: 1 sends every item, and every change of species and tile, through one workgroup)
-    std::string near_miss_route;     // "walk": the near-miss report takes the membership of every species from the walks of Sel ++ Cand (the compact masks), not from the node -> haplotype words
     int near_miss_words = 0;         // 1 .. 4: candidate mask words a wave of the near-miss pass counts in one pass over its nodes (0 = 4; tests: 1 sends a species of 200 haplotypes through the tiled passes)
-    std::string read_strain_route;   // "walk": the per-read strain masks of every species from its candidates' walks (stage_read_strain.hip), not from the node -> haplotype words
     bool cov_general = false;        // every group through the kernel of the longer walks (coverage_fast_kernel<.., LONG>; cov_long=step: coverage_step_kernel)
     std::string cov_long;            // "step": round 5's coverage_step_kernel for the groups that hold steps of walks of more than 64 steps
     int covl_shape = -1;             // shape of the long-walk kernel: <U><groups per workgroup / 8><window / 1024><back / 256> (default 2834)
@@ -693,19 +691,6 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
 // sorted candidate c, pair_off [S+1]; all validated by the caller.  hap_out [C][3][3] in the caller's order, species_out [S][4][3], pair_out [pair_off[S]]
 int read_support_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, const uint64_t *entry_of,
                         const uint64_t *pair_off, uint64_t *hap_out, uint64_t *species_out, uint64_t *pair_out);
-// stage_read_strain.hip: node membership in selected walks as a compact arena -- ceil(K / 64) words per node of a species over its K selected haplotypes only
-// (bit k = the k-th of them), filled by 64-bit atomic ORs over those walks (read_strain_mask_kernel).  Route 2 of the per-read strain report and of the
-// node evidence report.  The object owns the device buffers: it outlives the kernels that read d_mask.
-constexpr uint64_t WALK_MASK_TILE = 4096;   // walk positions per tile of the mask pass (one wave)
-struct WalkMaskTile { uint64_t p0, p1, word0; uint32_t nw, k; };   // walk positions [p0, p1) of selected walk k; its words start at word0 (+ local node * nw)
-struct WalkMasks {
-    std::vector<WalkMaskTile> tiles;
-    uint64_t words = 0;
-    DevBuf<WalkMaskTile> d_tiles;
-    DevBuf<unsigned long long> d_mask;
-    uint64_t add_species(const Db *db, uint32_t s, const uint32_t *haps, uint64_t K);   // -> first word of the species' node masks
-    int build(Ctx *ctx, const Db *db);                                                  // after the last add_species: zero fill + the pass over the tiles, on ctx->stream
-};
 // stage_evidence.hip (pantax_hip_strain_evidence): selection validated by the caller; hap_out [C][2][4], species_out [S][3][4]
 int evidence_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t *hap_out, uint64_t *species_out);
 // stage_depth.hip (pantax_hip_strain_depth): selection validated by the caller; hap_out [C][2][96][2], species_out [S][2][96][2] or null

@@ -1,12 +1,12 @@
 // read_strain_device.hpp -- what the two passes over the locus-grouped step stream that form the per-read candidate mask C(r) share
-// (stage_read_strain.hip: the per-read assignment; stage_read_support.hip: the per-strain read support): the species table and its host builder, the
+// (stage_read_strain.hip: the per-read assignment; stage_read_support.hip: the per-strain read support): the species table (member_plan.hpp), the
 // slot lookup, the segmented AND over the lanes of a wave, a lane's view of its step, and the per-slot partials of walks of more than 64 steps.
 // Device code and the host code that feeds it; include from .hip files only.
 #pragma once
 #include <algorithm>
 #include <vector>
 #include "common.hpp"
-#include "wave.hpp"
+#include "member_device.hpp"
 
 namespace ptx {
 
@@ -14,14 +14,7 @@ constexpr uint32_t RS_NO_SLOT = 0xFFFFFFFFu;
 // step codes of the grouped stream (cov_device.hpp: STEP_PAD, STEP_START)
 constexpr uint32_t RS_STEP_PAD = 0xFFu, RS_STEP_START = 0x40u;
 
-struct RsSpecies {
-    unsigned long long cand_bits;   // route 1: bit j = haplotype j is a candidate
-    uint64_t mask_base;             // route 2: first word of the species' node masks in the arena
-    uint32_t node_base;             // first global node index of the species
-    uint32_t route;                 // 0: no candidates, 1: node -> haplotype words, 2: compact masks
-    uint32_t nw;                    // mask words per node (route 1: 1)
-    uint32_t bit_base;              // first entry of the species in the per-bit arrays (bit_w / bit_hap, bit_w / bit_entry)
-};
+struct RsSpecies { MemberRow m; uint32_t bit_base; };   // bit_base: first entry of the species in the per-bit arrays (bit_w / bit_hap, bit_w / bit_entry)
 
 // slot of the step held by `lane` (all 64 lanes): group_first_slot owns the group's first step, every later walk start advances it
 __device__ __forceinline__ uint32_t rs_slot_in_group(uint32_t group_first_slot, uint32_t code, int lane) {
@@ -76,23 +69,23 @@ __device__ __forceinline__ RsLane rs_lane(uint32_t g, uint32_t gs, int lane, uin
     L.sr = make_uint2(0xFFFFFFFFu, 0u);
     if (L.live) { L.rr = read_rec[L.slot]; L.sr = slot_rec[L.slot]; }
     L.counted = L.live && (int32_t)L.sr.x >= 0;
-    L.st = RsSpecies{0ull, 0ull, 0u, 0u, 0u, 0u};
+    L.st = RsSpecies{};
     if (L.counted) L.st = tab[L.sr.x];
     const uint32_t i = L.live ? (uint32_t)t - L.rr.x : 0u;                // position in the walk (T_pad < 2^32)
     L.last = L.live && i + 1u == L.rr.y;
     L.is_long = L.rr.y > 64u;
     L.seg = lane - (int)min(i, (uint32_t)lane);
     L.tail = L.live && (L.last || lane == 63);
-    L.nw = L.st.route ? L.st.nw : 0u;
+    L.nw = L.st.m.route ? L.st.m.nw : 0u;
     L.v = L.counted ? g_node_id[t] + L.sr.y : 0u;
-    L.mrow = L.st.mask_base + (uint64_t)(L.v - L.st.node_base) * L.nw;
+    L.mrow = member_mask_row(L.st.m, L.v);
     return L;
 }
 // word w of the AND over my walk's steps in this wave, up to and including mine (all 64 lanes call it: a wave-uniform trip count over w)
 __device__ __forceinline__ unsigned long long rs_lane_word(const RsLane &L, uint32_t w, int lane, const unsigned long long *__restrict__ node_haps,
                                                            const unsigned long long *__restrict__ mask) {
     unsigned long long m = ~0ull;
-    if (w < L.nw) m = L.st.route == 1u ? (node_haps[L.v] & L.st.cand_bits) : mask[L.mrow + w];
+    if (w < L.nw) m = L.st.m.route == 1u ? (node_haps[L.v] & L.st.m.bits) : mask[L.mrow + w];
     return seg_and(m, lane, L.seg);
 }
 // walks of more than 64 steps: long_nw words per slot, set to all ones before the pass; every group ANDs its partial in (the order does not matter)
@@ -100,38 +93,24 @@ __device__ __forceinline__ void rs_long_partial(unsigned long long *__restrict__
     atomicAnd(&long_acc[(uint64_t)slot * long_nw + w], m);
 }
 
-// ---- host: the species table of a candidate set (candidates of every species in ascending haplotype order) --------------------------------------
-// route 1: bit = haplotype index, per-bit arrays at [hap_off[s] + haplotype]; route 2: bit = position among the species' candidates, per-bit arrays at
-// [H + candidate entry].  per_bit(position in the per-bit arrays, candidate entry) files what the caller keeps per bit; the arrays hold H + C + 1 entries.
+// ---- host: the species table of a candidate set, by member_plan.hpp; per_bit(position in the per-bit arrays of H + C + 1 entries, candidate entry) ----
 struct RsTable {
     std::vector<RsSpecies> tab;
     WalkMasks wm;
     uint32_t long_nw = 1;    // words per slot of the long-walk partials: the widest species
-    bool by_node = false;    // route 1 is open (node -> haplotype words built, not switched off)
+    bool by_node = false;    // route 1 is open
 };
 template <class PerBit>
 inline void rs_table_build(const Ctx *ctx, const Db *db, const uint64_t *cand_off, const uint32_t *cand_hap, RsTable &t, PerBit &&per_bit) {
     const uint32_t S = db->S;
-    const uint64_t H = db->H;
-    t.by_node = db->nh_built && ctx->cfg.read_strain_route != "walk";
-    t.tab.assign(S ? S : 1, RsSpecies{0ull, 0ull, 0u, 0u, 0u, 0u});
+    t.by_node = member_by_node(db->nh_built, ctx->cfg.read_strain_route);
+    t.tab.assign(S ? S : 1, RsSpecies{});
     for (uint32_t s = 0; s < S; ++s) {
         RsSpecies &st = t.tab[s];
-        st = RsSpecies{0ull, 0ull, (uint32_t)db->h_node_off[s], 0u, 0u, 0u};
-        const uint64_t K = cand_off[s + 1] - cand_off[s], nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
-        if (K == 0) continue;
-        if (t.by_node && nh <= 64) {
-            st.route = 1; st.nw = 1; st.bit_base = (uint32_t)db->h_hap_off[s];
-            for (uint64_t c = cand_off[s]; c < cand_off[s + 1]; ++c) {
-                st.cand_bits |= 1ull << cand_hap[c];
-                per_bit((uint64_t)st.bit_base + cand_hap[c], c);
-            }
-        } else {
-            st.route = 2; st.nw = (uint32_t)((K + 63) / 64); st.bit_base = (uint32_t)(H + cand_off[s]);
-            st.mask_base = t.wm.add_species(db, s, cand_hap + cand_off[s], K);
-            for (uint64_t k = 0; k < K; ++k) per_bit((uint64_t)st.bit_base + k, cand_off[s] + k);
-        }
-        t.long_nw = std::max(t.long_nw, st.nw);
+        st.m = t.wm.row(db, s, t.by_node, cand_hap + cand_off[s], cand_off[s + 1] - cand_off[s]);
+        st.bit_base = member_bit_base(st.m.route, db->h_hap_off[s], db->H, cand_off[s]);
+        member_file_bits(st.m.route, cand_hap + cand_off[s], st.m.K, 0, [&](uint64_t bit, uint64_t k) { per_bit(st.bit_base + bit, cand_off[s] + k); });
+        t.long_nw = std::max(t.long_nw, st.m.nw);
     }
 }
 

@@ -8,11 +8,7 @@
 // with the host helpers).  Every output is, per bin, the sum of (1, node_len[v]) over a class of nodes: per selection entry `all` (h in M(v)) and `private`
 // (M(v) = {h}), per species `total` (every node) and `orphan` (m(v) = 0).  Integers only: no order matters, no floating point on the device.
 //
-// Membership, as in stage_evidence.hip:
-//   route 1 -- species of <= 64 haplotypes whose node -> haplotype words were built at upload: word(v) = node_haps[v] & sel_bits[s], bit = haplotype index;
-//   route 2 -- every other species (and every species under depth_route=walk): ceil(K_s / 64) words per node over the selected haplotypes only, the
-//              compact arena of WalkMasks (bit = position in the selection).
-//
+// Membership: the two routes of member_plan.hpp over the selected haplotypes (option depth_route), nw = ceil(K_s / 64) words per node on route 2.
 // depth_hist_kernel: a histogram scatters over bins, so the node evidence kernel's reduction of K_s sums across the wave does not carry over: the
 // counters live in LDS and take 64-bit LDS atomics.  One selected haplotype costs 2 classes x 96 bins x {n_nodes, len} x 8 B = 3 KB, so 64 of them do not fit
 // beside a useful occupancy: the selected haplotypes of a species are taken in TILES of DP_HAPS = 8 (8 divides 64: a tile lies in one mask word), and the
@@ -35,6 +31,7 @@
 #include <algorithm>
 #include "common.hpp"
 #include "depth_device.hpp"
+#include "member_device.hpp"
 #include "primitives.hpp"
 
 namespace ptx {
@@ -50,17 +47,7 @@ constexpr uint32_t DP_WG_PER_CU = 5;
 static_assert(64 % DP_HAPS == 0, "a tile lies in one mask word");
 static_assert(DP_ROWS * DP_ROW * 8 * DP_WG_PER_CU <= 160 * 1024, "LDS of the resident workgroups");
 
-struct DpSpecies {
-    unsigned long long sel_bits;    // route 1: bit j = haplotype j is selected
-    uint64_t mask_base;             // route 2: first word of the species' node masks in the arena
-    uint32_t node_base;             // first global node index of the species
-    uint32_t route;                 // 0: nothing selected, 1: node -> haplotype words, 2: compact masks
-    uint32_t nw;                    // mask words per node (route 1: 1; route 0: 0)
-    uint32_t K;                     // selected haplotypes
-    uint32_t sel_base;              // first selection entry of the species
-    uint32_t pad;
-};
-struct DpItem { uint32_t first, n, species, tile; };   // global nodes [first, first + n) of one species, n <= DP_CHUNK, for the selected haplotypes 8 tile .. 8 tile + 7
+struct DpSpecies { MemberRow m; uint32_t sel_base, pad; };   // sel_base: first selection entry of the species.  An item is a MemberChunk: tile = the selected haplotypes 8 tile .. 8 tile + 7
 
 // the workgroup's counters -> global memory, zeroed on the way; between two barriers of the caller
 __device__ __forceinline__ void dp_flush(unsigned long long *__restrict__ cnt, uint32_t species, uint32_t entry0, unsigned long long *__restrict__ hap_out,
@@ -74,7 +61,7 @@ __device__ __forceinline__ void dp_flush(unsigned long long *__restrict__ cnt, u
     }
 }
 
-__global__ void __launch_bounds__(256) depth_hist_kernel(uint32_t n_items, uint32_t per_block, const DpItem *__restrict__ items, const DpSpecies *__restrict__ tab,
+__global__ void __launch_bounds__(256) depth_hist_kernel(uint32_t n_items, uint32_t per_block, const MemberChunk *__restrict__ items, const DpSpecies *__restrict__ tab,
                                                          const uint32_t *__restrict__ node_len, const unsigned long long *__restrict__ bases,
                                                          const unsigned long long *__restrict__ node_haps, const unsigned long long *__restrict__ mask,
                                                          const uint32_t *__restrict__ sel_hap, unsigned long long *__restrict__ hap_out /*[C][2][96][2]*/,
@@ -87,7 +74,7 @@ __global__ void __launch_bounds__(256) depth_hist_kernel(uint32_t n_items, uint3
     const uint32_t begin = (uint32_t)begin64, end = (uint32_t)std::min<uint64_t>(begin64 + per_block, n_items);
     uint32_t cur_species = 0u, cur_entry0 = 0u, cur_tile = 0u;
     for (uint32_t c = begin; c < end; ++c) {             // (everything below is uniform over the workgroup but the thread's nodes)
-        const DpItem it = items[c];
+        const MemberChunk it = items[c];
         const DpSpecies st = tab[it.species];
         if (c != begin && (it.species != cur_species || it.tile != cur_tile)) {
             __syncthreads();
@@ -96,11 +83,11 @@ __global__ void __launch_bounds__(256) depth_hist_kernel(uint32_t n_items, uint3
         }
         const uint32_t k0 = it.tile * DP_HAPS;
         cur_species = it.species; cur_tile = it.tile; cur_entry0 = st.sel_base + k0;
-        const uint32_t nb = st.K > k0 ? std::min(DP_HAPS, st.K - k0) : 0u;   // haplotypes of the tile
+        const uint32_t nb = st.m.K > k0 ? std::min(DP_HAPS, st.m.K - k0) : 0u;   // haplotypes of the tile
         const uint32_t tile_bits = (1u << nb) - 1u;
         uint32_t pos[DP_HAPS];                           // route 1: where the tile's haplotypes sit in the node -> haplotype word
 #pragma unroll
-        for (uint32_t j = 0; j < DP_HAPS; ++j) pos[j] = (st.route == 1u && j < nb) ? sel_hap[st.sel_base + k0 + j] : 0u;
+        for (uint32_t j = 0; j < DP_HAPS; ++j) pos[j] = (st.m.route == 1u && j < nb) ? sel_hap[st.sel_base + k0 + j] : 0u;
         const bool species_rows = it.tile == 0u && sp_out != nullptr;
         for (uint32_t t0 = 0; t0 < it.n; t0 += DP_SLAB) {
             uint32_t ln[4], tb[4], mm[4];
@@ -113,15 +100,15 @@ __global__ void __launch_bounds__(256) depth_hist_kernel(uint32_t n_items, uint3
                 const uint32_t v = it.first + (on[u] ? i : 0u);   // (a dead thread reads the item's first node and drops it)
                 ln[u] = node_len[v]; bs[u] = bases[v];
                 uint32_t m = 0u, t = 0u;
-                if (st.route == 1u) {
-                    const unsigned long long word = node_haps[v] & st.sel_bits;
+                if (st.m.route == 1u) {
+                    const unsigned long long word = node_haps[v] & st.m.bits;
                     m = (uint32_t)__popcll(word);
 #pragma unroll
                     for (uint32_t j = 0; j < DP_HAPS; ++j) t |= (uint32_t)((word >> pos[j]) & 1ull) << j;
-                } else if (st.route == 2u) {
-                    const uint64_t row = st.mask_base + (uint64_t)(v - st.node_base) * st.nw;
+                } else if (st.m.route == 2u) {
+                    const uint64_t row = member_mask_row(st.m, v);
                     const uint32_t wt = k0 >> 6, sh = k0 & 63u;
-                    for (uint32_t w = 0; w < st.nw; ++w) {
+                    for (uint32_t w = 0; w < st.m.nw; ++w) {
                         const unsigned long long x = mask[row + w];
                         m += (uint32_t)__popcll(x);
                         t = w == wt ? (uint32_t)(x >> sh) : t;
@@ -159,38 +146,24 @@ int depth_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_
     const uint64_t C = sel_off[S];
     if (C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_depth: %llu selection entries exceed 32-bit positions", (unsigned long long)C);
     if (db->V >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_depth: %llu nodes exceed 32-bit positions", (unsigned long long)db->V);
-    const bool by_node = db->nh_built && ctx->cfg.depth_route != "walk";
+    const bool by_node = member_by_node(db->nh_built, ctx->cfg.depth_route);
     const bool want_species = species_out != nullptr;
     std::vector<DpSpecies> tab(S ? S : 1);
-    std::vector<DpItem> items;
-    WalkMasks wm;
+    std::vector<MemberChunk> items;
+    MemberPass ps;
     for (uint32_t s = 0; s < S; ++s) {
-        DpSpecies &st = tab[s];
-        const uint64_t K = sel_off[s + 1] - sel_off[s], nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
-        st = DpSpecies{0ull, 0ull, (uint32_t)db->h_node_off[s], 0u, 0u, (uint32_t)K, (uint32_t)sel_off[s], 0u};
-        if (K && by_node && nh <= 64) {
-            st.route = 1; st.nw = 1;
-            for (uint64_t c = sel_off[s]; c < sel_off[s + 1]; ++c) st.sel_bits |= 1ull << sel_hap[c];
-        } else if (K) {
-            st.route = 2; st.nw = (uint32_t)((K + 63) / 64);
-            st.mask_base = wm.add_species(db, s, sel_hap + sel_off[s], K);
-        }
+        const uint64_t K = sel_off[s + 1] - sel_off[s];
+        tab[s] = DpSpecies{ps.wm.row(db, s, by_node, sel_hap + sel_off[s], K), (uint32_t)sel_off[s], 0u};
         const uint64_t tiles = K ? (K + DP_HAPS - 1) / DP_HAPS : (want_species ? 1 : 0);   // nothing selected: the species rows alone
-        for (uint64_t t = 0; t < tiles; ++t)
-            for (uint64_t v = db->h_node_off[s]; v < db->h_node_off[s + 1]; v += DP_CHUNK)
-                items.push_back(DpItem{(uint32_t)v, (uint32_t)std::min<uint64_t>(DP_CHUNK, db->h_node_off[s + 1] - v), s, (uint32_t)t});
+        member_chunks_add(items, s, db->h_node_off[s], db->h_node_off[s + 1], DP_CHUNK, tiles);
     }
     if (items.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_depth: %llu chunks of nodes", (unsigned long long)items.size());
     const size_t n_hap = (size_t)C * 2 * DP_ROW, n_sp = want_species ? (size_t)S * 2 * DP_ROW : 0;
     if (n_hap + n_sp == 0) return 0;
-    // one device block, zero-filled once: [hap C x 2 x 96 x 2][species S x 2 x 96 x 2]
-    DevBuf<unsigned long long> d_out;
     DevBuf<DpSpecies> d_tab;
     DevBuf<uint32_t> d_sel_hap;
-    DevBuf<DpItem> d_items;
-    PTX_HIP(ctx, d_out.alloc(n_hap + n_sp));
-    PTX_TRY(zero_fill(ctx, d_out.p, (n_hap + n_sp) * sizeof(unsigned long long)));
-    PTX_TRY(wm.build(ctx, db));
+    DevBuf<MemberChunk> d_items;
+    PTX_TRY(ps.open(ctx, db, n_hap + n_sp));   // one device block, zero-filled once: [hap C x 2 x 96 x 2][species S x 2 x 96 x 2]
     const uint32_t none = 0;
     if (!items.empty()) {
         PTX_TRY(upload(ctx, d_tab, tab.data(), tab.size()));
@@ -200,14 +173,10 @@ int depth_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_
         const uint32_t per_block = (uint32_t)((items.size() + grid - 1) / grid);
         KTimer tm(ctx, "depth_hist_kernel");
         hipLaunchKernelGGL(depth_hist_kernel, dim3(grid), dim3(256), 0, ctx->stream, (uint32_t)items.size(), per_block, d_items.p, d_tab.p, db->d_node_len.p,
-                           db->d_bases.p, by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, wm.d_mask.p, d_sel_hap.p,
-                           d_out.p, want_species ? d_out.p + n_hap : (unsigned long long *)nullptr);
+                           db->d_bases.p, by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, ps.wm.d_mask.p, d_sel_hap.p,
+                           ps.d_out.p, want_species ? ps.d_out.p + n_hap : (unsigned long long *)nullptr);
     }
-    PTX_HIP(ctx, hipGetLastError());
-    if (n_hap) PTX_TRY(download(ctx, (unsigned long long *)hap_out, d_out.p, n_hap));
-    if (n_sp) PTX_TRY(download(ctx, (unsigned long long *)species_out, d_out.p + n_hap, n_sp));
-    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host arrays are filled, the temporaries are released on return
-    return 0;
+    return ps.close(ctx, hap_out, n_hap, species_out, n_sp);
 }
 
 }  // namespace ptx

@@ -6,11 +6,7 @@
 // Q(v) = (1, node_len[v], node_base_cov[v], bases_per_node[v]) as u64.  Per selection entry: all = sum of Q over the nodes the haplotype visits, private =
 // over the nodes with M(v) = {the haplotype}.  Per species: total (every node), orphan (m = 0), core (m = K_s, K_s >= 1).  Integers only: no order matters.
 //
-// Membership, as in stage_read_strain.hip:
-//   route 1 -- species of <= 64 haplotypes whose node -> haplotype words were built at upload: word(v) = node_haps[v] & sel_bits[s], bit = haplotype index;
-//   route 2 -- every other species (and every species under evidence_route=walk): ceil(K_s / 64) words per node over the selected haplotypes only, the
-//              compact arena of WalkMasks (bit = position in the selection).
-//
+// Membership: the two routes of member_plan.hpp over the selected haplotypes (option evidence_route), nw = ceil(K_s / 64) words per node on route 2.
 // evidence_node_kernel: the host cuts every species' nodes into chunks of EV_CHUNK nodes; a chunk goes to a WAVE (four chunks in flight per workgroup: a
 // species of a few thousand nodes still spreads over several CUs, and nothing in the pass needs a workgroup barrier).  The wave takes its chunk in
 // tiles of 256 nodes, lane l the nodes l, l + 64, l + 128, l + 192 of the tile: every load instruction is one contiguous stretch of 256 or 512 bytes.
@@ -28,8 +24,8 @@
 // repeats come from L2 at best), behind the mask pass's 4 P_sel + 8 nw V_s (zero fill) + one 8-byte atomic per visit.
 #include <algorithm>
 #include "common.hpp"
+#include "member_device.hpp"
 #include "primitives.hpp"
-#include "wave.hpp"
 
 namespace ptx {
 
@@ -37,34 +33,9 @@ namespace {
 
 constexpr uint32_t EV_CHUNK = 1024;   // nodes per chunk (one wave)
 constexpr uint32_t EV_TILE = 256;     // nodes the wave holds in registers at a time: four per lane
-constexpr uint32_t EV_NO_ENTRY = 0xFFFFFFFFu;
 
-struct EvSpecies {
-    unsigned long long sel_bits;    // route 1: bit j = haplotype j is selected
-    uint64_t mask_base;             // route 2: first word of the species' node masks in the arena
-    uint32_t node_base;             // first global node index of the species
-    uint32_t route;                 // 0: nothing selected, 1: node -> haplotype words, 2: compact masks
-    uint32_t nw;                    // mask words per node (route 1: 1; route 0: 0)
-    uint32_t K;                     // selected haplotypes
-    uint32_t bit_base;              // first entry of the species in bit_entry
-    uint32_t pad;
-};
-struct EvChunk { uint32_t first, n, species, pad; };   // global nodes [first, first + n) of one species, n <= EV_CHUNK
+struct EvSpecies { MemberRow m; uint32_t bit_base, pad; };   // bit_base: first entry of the species in bit_entry
 
-struct EvQ { unsigned long long n, len, cov, bases; };
-__device__ __forceinline__ void ev_add(EvQ &a, bool on, uint32_t len, uint32_t cov, unsigned long long bases) {
-    a.n += on ? 1ull : 0ull; a.len += on ? (unsigned long long)len : 0ull; a.cov += on ? (unsigned long long)cov : 0ull; a.bases += on ? bases : 0ull;
-}
-__device__ __forceinline__ EvQ ev_wave_sum(const EvQ &a) {
-    const auto add = [](unsigned long long x, unsigned long long y) { return x + y; };
-    return EvQ{wave_reduce(a.n, add), wave_reduce(a.len, add), wave_reduce(a.cov, add), wave_reduce(a.bases, add)};
-}
-__device__ __forceinline__ void ev_flush(unsigned long long *__restrict__ dst, const EvQ &a) {
-    if (a.n) atomicAdd(dst, a.n);
-    if (a.len) atomicAdd(dst + 1, a.len);
-    if (a.cov) atomicAdd(dst + 2, a.cov);
-    if (a.bases) atomicAdd(dst + 3, a.bases);
-}
 // the wave's LDS counters change hands between its lanes (lane 0 adds, every lane zeroes and flushes its own bit): order the accesses inside the wave
 __device__ __forceinline__ void ev_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
@@ -72,7 +43,7 @@ __device__ __forceinline__ void ev_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-__global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, const EvChunk *__restrict__ chunks, const EvSpecies *__restrict__ tab,
+__global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, const MemberChunk *__restrict__ chunks, const EvSpecies *__restrict__ tab,
                                                             const uint32_t *__restrict__ node_len, const uint32_t *__restrict__ cov,
                                                             const unsigned long long *__restrict__ bases, const unsigned long long *__restrict__ node_haps,
                                                             const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ bit_entry,
@@ -81,14 +52,14 @@ __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, c
     const int lane = threadIdx.x & 63;
     unsigned long long *const cnt = s_cnt[threadIdx.x >> 6];
     for (uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6); c < n_chunks; c += gridDim.x * 4) {   // (everything below is uniform over the wave but the lane's nodes)
-        const EvChunk ch = chunks[c];
+        const MemberChunk ch = chunks[c];
         const EvSpecies st = tab[ch.species];
-        EvQ tot{0ull, 0ull, 0ull, 0ull}, orp{0ull, 0ull, 0ull, 0ull}, cor{0ull, 0ull, 0ull, 0ull};
-        const uint32_t passes = st.route ? st.nw : 1u;
+        MemberQ tot{0ull, 0ull, 0ull, 0ull}, orp{0ull, 0ull, 0ull, 0ull}, cor{0ull, 0ull, 0ull, 0ull};
+        const uint32_t passes = st.m.route ? st.m.nw : 1u;
         for (uint32_t w = 0; w < passes; ++w) {
             // the bits of word w that stand for a selected haplotype
-            const uint32_t left = st.route == 2u ? st.K - 64u * w : 0u;
-            const unsigned long long live = st.route == 1u ? st.sel_bits : (st.route == 2u ? (left >= 64u ? ~0ull : (1ull << left) - 1ull) : 0ull);
+            const uint32_t left = st.m.route == 2u ? st.m.K - 64u * w : 0u;
+            const unsigned long long live = st.m.route == 1u ? st.m.bits : (st.m.route == 2u ? (left >= 64u ? ~0ull : (1ull << left) - 1ull) : 0ull);
 #pragma unroll
             for (int q = 0; q < 8; ++q) cnt[q * 64 + lane] = 0ull;
             ev_wave_sync();
@@ -104,10 +75,10 @@ __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, c
                     ln[j] = node_len[v]; cv[j] = cov[v]; bs[j] = bases[v];
                     unsigned long long word = 0ull;
                     uint32_t m = 0u;
-                    if (st.route == 1u) { word = node_haps[v] & st.sel_bits; m = (uint32_t)__popcll(word); }
-                    else if (st.route == 2u) {
-                        const uint64_t row = st.mask_base + (uint64_t)(v - st.node_base) * st.nw;
-                        for (uint32_t w2 = 0; w2 < st.nw; ++w2) {
+                    if (st.m.route == 1u) { word = node_haps[v] & st.m.bits; m = (uint32_t)__popcll(word); }
+                    else if (st.m.route == 2u) {
+                        const uint64_t row = member_mask_row(st.m, v);
+                        for (uint32_t w2 = 0; w2 < st.m.nw; ++w2) {
                             const unsigned long long x = mask[row + w2];
                             m += (uint32_t)__popcll(x);
                             word = w2 == w ? x : word;
@@ -116,24 +87,24 @@ __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, c
                     wd[j] = on[j] ? word : 0ull;
                     one[j] = m == 1u;
                     if (w == 0u) {   // the species sums see every node once: in the first pass
-                        ev_add(tot, on[j], ln[j], cv[j], bs[j]);
-                        ev_add(orp, on[j] & (m == 0u), ln[j], cv[j], bs[j]);
-                        ev_add(cor, on[j] & (st.K != 0u) & (m == st.K), ln[j], cv[j], bs[j]);
+                        mq_add(tot, on[j], ln[j], cv[j], bs[j]);
+                        mq_add(orp, on[j] & (m == 0u), ln[j], cv[j], bs[j]);
+                        mq_add(cor, on[j] & (st.m.K != 0u) & (m == st.m.K), ln[j], cv[j], bs[j]);
                     }
                 }
                 const unsigned long long mine = wd[0] | wd[1] | wd[2] | wd[3];
                 for (unsigned long long rem = live; rem; rem &= rem - 1ull) {
                     const int b = __builtin_ctzll(rem);
                     if (__builtin_amdgcn_ballot_w64((mine >> b) & 1ull) == 0ull) continue;   // no node of the tile carries the bit
-                    EvQ a{0ull, 0ull, 0ull, 0ull}, p{0ull, 0ull, 0ull, 0ull};
+                    MemberQ a{0ull, 0ull, 0ull, 0ull}, p{0ull, 0ull, 0ull, 0ull};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const bool has = (wd[j] >> b) & 1ull;
-                        ev_add(a, has, ln[j], cv[j], bs[j]);
-                        ev_add(p, has & one[j], ln[j], cv[j], bs[j]);
+                        mq_add(a, has, ln[j], cv[j], bs[j]);
+                        mq_add(p, has & one[j], ln[j], cv[j], bs[j]);
                     }
-                    a = ev_wave_sum(a);
-                    p = ev_wave_sum(p);
+                    a = mq_wave_sum(a);
+                    p = mq_wave_sum(p);
                     if (lane == 0) {
                         cnt[0 * 64 + b] += a.n; cnt[1 * 64 + b] += a.len; cnt[2 * 64 + b] += a.cov; cnt[3 * 64 + b] += a.bases;
                         cnt[4 * 64 + b] += p.n; cnt[5 * 64 + b] += p.len; cnt[6 * 64 + b] += p.cov; cnt[7 * 64 + b] += p.bases;
@@ -143,7 +114,7 @@ __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, c
             ev_wave_sync();
             if ((live >> lane) & 1ull) {   // lane b owns bit b of this word
                 const uint32_t e = bit_entry[st.bit_base + 64u * w + (uint32_t)lane];
-                if (e != EV_NO_ENTRY) {
+                if (e != MEMBER_NO_ENTRY) {
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
                         const unsigned long long x = cnt[q * 64 + lane];
@@ -153,10 +124,10 @@ __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, c
             }
             ev_wave_sync();   // (the counters are zeroed again by the next pass or chunk)
         }
-        tot = ev_wave_sum(tot); orp = ev_wave_sum(orp); cor = ev_wave_sum(cor);
+        tot = mq_wave_sum(tot); orp = mq_wave_sum(orp); cor = mq_wave_sum(cor);
         if (lane == 0) {
             unsigned long long *const o = sp_out + (uint64_t)ch.species * 12u;
-            ev_flush(o, tot); ev_flush(o + 4, orp); ev_flush(o + 8, cor);
+            mq_flush(o, tot); mq_flush(o + 4, orp); mq_flush(o + 8, cor);
         }
     }
 }
@@ -169,37 +140,24 @@ int evidence_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *s
     const uint64_t H = db->H, C = sel_off[S];
     if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_evidence: %llu haplotypes + selection entries exceed 32-bit positions", (unsigned long long)(H + C));
     if (db->V >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_evidence: %llu nodes exceed 32-bit positions", (unsigned long long)db->V);
-    const bool by_node = db->nh_built && ctx->cfg.evidence_route != "walk";
+    const bool by_node = member_by_node(db->nh_built, ctx->cfg.evidence_route);
     std::vector<EvSpecies> tab(S ? S : 1);
-    std::vector<uint32_t> bit_entry(H + C + 1, EV_NO_ENTRY);   // route 1: [hap_off[s] + haplotype], route 2: [H + selection entry] -> selection entry
-    std::vector<EvChunk> chunks;
-    WalkMasks wm;
+    std::vector<uint32_t> bit_entry(H + C + 1, MEMBER_NO_ENTRY);   // [bit_base of the species + bit] -> selection entry
+    std::vector<MemberChunk> chunks;
+    MemberPass ps;
     for (uint32_t s = 0; s < S; ++s) {
         EvSpecies &st = tab[s];
-        const uint64_t K = sel_off[s + 1] - sel_off[s], nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
-        st = EvSpecies{0ull, 0ull, (uint32_t)db->h_node_off[s], 0u, 0u, (uint32_t)K, 0u, 0u};
-        if (K && by_node && nh <= 64) {
-            st.route = 1; st.nw = 1; st.bit_base = (uint32_t)db->h_hap_off[s];
-            for (uint64_t c = sel_off[s]; c < sel_off[s + 1]; ++c) { st.sel_bits |= 1ull << sel_hap[c]; bit_entry[st.bit_base + sel_hap[c]] = (uint32_t)c; }
-        } else if (K) {
-            st.route = 2; st.nw = (uint32_t)((K + 63) / 64); st.bit_base = (uint32_t)(H + sel_off[s]);
-            st.mask_base = wm.add_species(db, s, sel_hap + sel_off[s], K);
-            for (uint64_t c = sel_off[s]; c < sel_off[s + 1]; ++c) bit_entry[H + c] = (uint32_t)c;
-        }
-        for (uint64_t v = db->h_node_off[s]; v < db->h_node_off[s + 1]; v += EV_CHUNK)
-            chunks.push_back(EvChunk{(uint32_t)v, (uint32_t)std::min<uint64_t>(EV_CHUNK, db->h_node_off[s + 1] - v), s, 0u});
+        st.m = ps.wm.row(db, s, by_node, sel_hap + sel_off[s], sel_off[s + 1] - sel_off[s]);
+        st.bit_base = member_bit_base(st.m.route, db->h_hap_off[s], H, sel_off[s]);
+        member_file_bits(st.m.route, sel_hap + sel_off[s], st.m.K, 0, [&](uint64_t bit, uint64_t k) { bit_entry[st.bit_base + bit] = (uint32_t)(sel_off[s] + k); });
+        member_chunks_add(chunks, s, db->h_node_off[s], db->h_node_off[s + 1], EV_CHUNK, 1);
     }
-    if (chunks.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_evidence: %llu chunks of nodes", (unsigned long long)chunks.size());
     const size_t n_out = (size_t)C * 8 + (size_t)S * 12;
     if (n_out == 0) return 0;
-    // one device block, zero-filled once: [hap C x 8][species S x 12]
-    DevBuf<unsigned long long> d_out;
     DevBuf<EvSpecies> d_tab;
     DevBuf<uint32_t> d_bit_entry;
-    DevBuf<EvChunk> d_chunks;
-    PTX_HIP(ctx, d_out.alloc(n_out));
-    PTX_TRY(zero_fill(ctx, d_out.p, n_out * sizeof(unsigned long long)));
-    PTX_TRY(wm.build(ctx, db));
+    DevBuf<MemberChunk> d_chunks;
+    PTX_TRY(ps.open(ctx, db, n_out));   // one device block, zero-filled once: [hap C x 8][species S x 12]
     if (!chunks.empty()) {
         PTX_TRY(upload(ctx, d_tab, tab.data(), tab.size()));
         PTX_TRY(upload(ctx, d_bit_entry, bit_entry.data(), bit_entry.size()));
@@ -207,13 +165,9 @@ int evidence_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *s
         KTimer tm(ctx, "evidence_node_kernel");
         hipLaunchKernelGGL(evidence_node_kernel, dim3(grid_for(chunks.size(), 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, (uint32_t)chunks.size(), d_chunks.p, d_tab.p,
                            db->d_node_len.p, db->d_cov.p, db->d_bases.p, by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr,
-                           wm.d_mask.p, d_bit_entry.p, d_out.p, d_out.p + (size_t)C * 8);
+                           ps.wm.d_mask.p, d_bit_entry.p, ps.d_out.p, ps.d_out.p + (size_t)C * 8);
     }
-    PTX_HIP(ctx, hipGetLastError());
-    if (C) PTX_TRY(download(ctx, (unsigned long long *)hap_out, d_out.p, (size_t)C * 8));
-    if (S) PTX_TRY(download(ctx, (unsigned long long *)species_out, d_out.p + (size_t)C * 8, (size_t)S * 12));
-    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host arrays are filled, the temporaries are released on return
-    return 0;
+    return ps.close(ctx, hap_out, (size_t)C * 8, species_out, (size_t)S * 12);
 }
 
 }  // namespace ptx

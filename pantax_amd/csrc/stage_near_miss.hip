@@ -6,13 +6,9 @@
 // m = |M|, n = |N|, Q(v) = (1, node_len[v], node_base_cov[v], bases_per_node[v]) as u64.  Per candidate entry: novel = sum of Q over m(v) = 0 and h in N(v),
 // exclusive = over m(v) = 0 and N(v) = {h}.  Per species: orphan (m = 0), claimed (m = 0, n >= 1), contested (m = 0, n >= 2).  Integers only.
 //
-// Membership, the two routes of stage_evidence.hip:
-//   route 1 -- species of <= 64 haplotypes whose node -> haplotype words were built at upload: one word per node, x = node_haps[v]; orphan: x & sel_bits = 0;
-//              candidate word: x & cand_bits, bit = haplotype index;
-//   route 2 -- every other species (and every species under near_miss_route=walk): the compact arena of WalkMasks over the LIST Sel_s ++ Cand_s, bit =
-//              position in the list, nw = ceil((K_s + J_s) / 64) words per node.  Sel ends at bit K_s, in the middle of word K_s / 64: that word serves both
-//              sets under two masks.  The candidate words are the words K_s / 64 .. (K_s + J_s - 1) / 64 of the node.
-//
+// Membership: the two routes of member_plan.hpp (option near_miss_route) over the LIST Sel_s ++ Cand_s, laid out by near_miss_layout:
+//   route 1 -- one word per node, x = node_haps[v]; orphan: x & Sel's bits = 0; candidate word: x & cand_bits, bit = haplotype index;
+//   route 2 -- bit = position in the list.  Sel ends at bit K_s, in the middle of word K_s / 64: that word serves both sets under two masks.
 // near_miss_node_kernel: chunks of NM_CHUNK nodes of one species, a chunk per WAVE, tiles of 256 nodes, lane l the nodes l, l + 64, l + 128, l + 192 -- the
 // mapping of evidence_node_kernel.  What differs is that J is not small (every unreported haplotype of a species, possibly all 64 bits of a word) and that
 // only orphan nodes add to anything:
@@ -37,8 +33,8 @@
 // loaded tile are masked off; their cache lines still travel), behind the mask pass's 4 P_list + 8 nw V_s (zero fill) + one 8-byte atomic per visit.
 #include <algorithm>
 #include "common.hpp"
+#include "member_device.hpp"
 #include "primitives.hpp"
-#include "wave.hpp"
 
 namespace ptx {
 
@@ -47,38 +43,16 @@ namespace {
 constexpr uint32_t NM_CHUNK = 1024;   // nodes per chunk (one wave)
 constexpr uint32_t NM_TILE = 256;     // nodes the wave holds in registers at a time: four per lane
 constexpr uint32_t NM_WORDS = 4;      // candidate words a wave counts per pass, at most (16 KB of LDS a wave)
-constexpr uint32_t NM_NO_ENTRY = 0xFFFFFFFFu;
 
 struct NmSpecies {
-    unsigned long long sel_bits;    // route 1: bit j = haplotype j is reported
+    MemberRow m;                    // over Sel ++ Cand, but K and (route 1) bits are Sel's alone
     unsigned long long cand_bits;   // route 1: bit j = haplotype j is a candidate
-    uint64_t mask_base;             // route 2: first word of the species' node masks in the arena
-    uint32_t node_base;             // first global node index of the species
-    uint32_t route;                 // 0: neither set (every node is an orphan, nothing else to know), 1: node -> haplotype words, 2: compact masks
-    uint32_t nw;                    // route 2: mask words per node over Sel ++ Cand
-    uint32_t K, J;                  // reported haplotypes, candidates
-    uint32_t w0;                    // route 2: the word of the first candidate bit = K / 64 (route 1: 0)
-    uint32_t cwn;                   // candidate words of a node (route 1: 1 when J > 0)
+    uint32_t J, w0, cwn;            // candidates; near_miss_layout: the word of the first candidate bit, the candidate words of a node
     uint32_t bit_base;              // candidate word k (from w0), bit b -> bit_entry[bit_base + 64 k + b]
 };
-struct NmChunk { uint32_t first, n, species, pad; };   // global nodes [first, first + n) of one species, n <= NM_CHUNK
 
-struct NmQ { unsigned long long n, len, cov, bases; };
-__device__ __forceinline__ void nm_add(NmQ &a, bool on, uint32_t len, uint32_t cov, unsigned long long bases) {
-    a.n += on ? 1ull : 0ull; a.len += on ? (unsigned long long)len : 0ull; a.cov += on ? (unsigned long long)cov : 0ull; a.bases += on ? bases : 0ull;
-}
-__device__ __forceinline__ NmQ nm_wave_sum(const NmQ &a) {
-    const auto add = [](unsigned long long x, unsigned long long y) { return x + y; };
-    return NmQ{wave_reduce(a.n, add), wave_reduce(a.len, add), wave_reduce(a.cov, add), wave_reduce(a.bases, add)};
-}
-__device__ __forceinline__ void nm_flush(unsigned long long *__restrict__ dst, const NmQ &a) {
-    if (a.n) atomicAdd(dst, a.n);
-    if (a.len) atomicAdd(dst + 1, a.len);
-    if (a.cov) atomicAdd(dst + 2, a.cov);
-    if (a.bases) atomicAdd(dst + 3, a.bases);
-}
 // lane `lane` adds a wave-uniform sum to its own counters of class `cls` (0: novel, 1: exclusive) where its bit is in `bits`
-__device__ __forceinline__ void nm_count(unsigned long long *cnt, int lane, unsigned long long bits, int cls, const NmQ &a) {
+__device__ __forceinline__ void nm_count(unsigned long long *cnt, int lane, unsigned long long bits, int cls, const MemberQ &a) {
     if ((bits >> lane) & 1ull) {
         cnt[(cls * 4 + 0) * 64 + lane] += a.n; cnt[(cls * 4 + 1) * 64 + lane] += a.len;
         cnt[(cls * 4 + 2) * 64 + lane] += a.cov; cnt[(cls * 4 + 3) * 64 + lane] += a.bases;
@@ -87,7 +61,7 @@ __device__ __forceinline__ void nm_count(unsigned long long *cnt, int lane, unsi
 
 // MAXW: the candidate words a lane holds in registers per node (1: no species of the launch has more than one candidate word -- the whole of route 1)
 template <uint32_t MAXW>
-__global__ void __launch_bounds__(256) near_miss_node_kernel(uint32_t n_chunks, uint32_t W /* candidate words per pass: 1 .. MAXW */, const NmChunk *__restrict__ chunks,
+__global__ void __launch_bounds__(256) near_miss_node_kernel(uint32_t n_chunks, uint32_t W /* candidate words per pass: 1 .. MAXW */, const MemberChunk *__restrict__ chunks,
                                                              const NmSpecies *__restrict__ tab, const uint32_t *__restrict__ node_len, const uint32_t *__restrict__ cov,
                                                              const unsigned long long *__restrict__ bases, const unsigned long long *__restrict__ node_haps,
                                                              const unsigned long long *__restrict__ mask, const uint32_t *__restrict__ bit_entry,
@@ -98,12 +72,12 @@ __global__ void __launch_bounds__(256) near_miss_node_kernel(uint32_t n_chunks, 
     const auto bit_or = [](unsigned long long x, unsigned long long y) { return x | y; };
     const auto bit_and = [](unsigned long long x, unsigned long long y) { return x & y; };
     for (uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6); c < n_chunks; c += gridDim.x * 4) {   // (everything below is uniform over the wave but the lane's nodes)
-        const NmChunk ch = chunks[c];
+        const MemberChunk ch = chunks[c];
         const NmSpecies st = tab[ch.species];
-        NmQ orp{0ull, 0ull, 0ull, 0ull}, cla{0ull, 0ull, 0ull, 0ull}, con{0ull, 0ull, 0ull, 0ull};
+        MemberQ orp{0ull, 0ull, 0ull, 0ull}, cla{0ull, 0ull, 0ull, 0ull}, con{0ull, 0ull, 0ull, 0ull};
         // route 2: Sel's words are 0 .. sw - 1, the last of them cut at bit K % 64; the candidates start at that bit of word w0
-        const uint32_t sw = st.route == 2u ? (st.K + 63u) / 64u : 0u;
-        const unsigned long long sel_last = (st.K & 63u) ? (1ull << (st.K & 63u)) - 1ull : ~0ull;
+        const uint32_t sw = st.m.route == 2u ? member_words(st.m.K) : 0u;
+        const unsigned long long sel_last = (st.m.K & 63u) ? (1ull << (st.m.K & 63u)) - 1ull : ~0ull;
         const uint32_t passes = st.cwn ? (st.cwn + W - 1u) / W : 1u;
         for (uint32_t p = 0; p < passes; ++p) {
             const uint32_t k0 = p * W, kn = st.cwn > k0 ? min(W, st.cwn - k0) : 0u;   // this pass counts the candidate words k0 .. k0 + kn - 1
@@ -121,9 +95,9 @@ __global__ void __launch_bounds__(256) near_miss_node_kernel(uint32_t n_chunks, 
                     vv[j] = ch.first + (on ? i : 0u);   // (a dead lane reads the chunk's first node and drops it)
                     first[j] = 0ull;
                     bool free_of_sel = true;
-                    if (st.route == 1u) { first[j] = node_haps[vv[j]]; free_of_sel = (first[j] & st.sel_bits) == 0ull; }
-                    else if (st.route == 2u) {
-                        const uint64_t row = st.mask_base + (uint64_t)(vv[j] - st.node_base) * st.nw;
+                    if (st.m.route == 1u) { first[j] = node_haps[vv[j]]; free_of_sel = (first[j] & st.m.bits) == 0ull; }
+                    else if (st.m.route == 2u) {
+                        const uint64_t row = member_mask_row(st.m, vv[j]);
                         for (uint32_t w = 0; w < sw; ++w) {
                             const unsigned long long x = mask[row + w];
                             free_of_sel = free_of_sel && (x & (w + 1u == sw ? sel_last : ~0ull)) == 0ull;
@@ -142,12 +116,12 @@ __global__ void __launch_bounds__(256) near_miss_node_kernel(uint32_t n_chunks, 
                     for (uint32_t kk = 0; kk < MAXW; ++kk) wd[j][kk] = 0ull;
                     if (!orph[j]) continue;
                     ln[j] = node_len[vv[j]]; cv[j] = cov[vv[j]]; bs[j] = bases[vv[j]];
-                    if (st.route == 1u) { wd[j][0] = first[j] & st.cand_bits; nn[j] = (uint32_t)__popcll(wd[j][0]); }   // (cwn <= 1: k0 = 0)
-                    else if (st.route == 2u) {
-                        const uint64_t row = st.mask_base + (uint64_t)(vv[j] - st.node_base) * st.nw + st.w0;
+                    if (st.m.route == 1u) { wd[j][0] = first[j] & st.cand_bits; nn[j] = (uint32_t)__popcll(wd[j][0]); }   // (cwn <= 1: k0 = 0)
+                    else if (st.m.route == 2u) {
+                        const uint64_t row = member_mask_row(st.m, vv[j]) + st.w0;
                         for (uint32_t k = 0; k < st.cwn; ++k) {   // every candidate word for n(v); the words of this pass stay in registers
                             unsigned long long x = (k == 0u && st.w0 < sw) ? first[j] : mask[row + k];
-                            if (k == 0u) x &= ~((1ull << (st.K & 63u)) - 1ull);   // the bits below K % 64 of word w0 are Sel's
+                            if (k == 0u) x &= ~((1ull << (st.m.K & 63u)) - 1ull);   // the bits below K % 64 of word w0 are Sel's
                             nn[j] += (uint32_t)__popcll(x);
                             const uint32_t r = k - k0;
 #pragma unroll
@@ -158,14 +132,14 @@ __global__ void __launch_bounds__(256) near_miss_node_kernel(uint32_t n_chunks, 
                 if (p == 0u) {   // the species sums see every node once: in the first pass
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        nm_add(orp, orph[j], ln[j], cv[j], bs[j]);
-                        nm_add(cla, orph[j] & (nn[j] >= 1u), ln[j], cv[j], bs[j]);
-                        nm_add(con, orph[j] & (nn[j] >= 2u), ln[j], cv[j], bs[j]);
+                        mq_add(orp, orph[j], ln[j], cv[j], bs[j]);
+                        mq_add(cla, orph[j] & (nn[j] >= 1u), ln[j], cv[j], bs[j]);
+                        mq_add(con, orph[j] & (nn[j] >= 2u), ln[j], cv[j], bs[j]);
                     }
                 }
                 if (__builtin_amdgcn_ballot_w64((nn[0] | nn[1] | nn[2] | nn[3]) != 0u) == 0ull) continue;   // orphans no candidate walks
                 bool have_claimed = false;
-                NmQ claimed{0ull, 0ull, 0ull, 0ull};   // the tile's claimed sum, reduced when the first word needs it
+                MemberQ claimed{0ull, 0ull, 0ull, 0ull};   // the tile's claimed sum, reduced when the first word needs it
 #pragma unroll
                 for (uint32_t kk = 0; kk < MAXW; ++kk) {
                     if (kk >= kn) break;
@@ -179,33 +153,33 @@ __global__ void __launch_bounds__(256) near_miss_node_kernel(uint32_t n_chunks, 
                     every = wave_reduce(every, bit_and);
                     if (every) {
                         if (!have_claimed) {
-                            NmQ a{0ull, 0ull, 0ull, 0ull};
+                            MemberQ a{0ull, 0ull, 0ull, 0ull};
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) nm_add(a, nn[j] >= 1u, ln[j], cv[j], bs[j]);
-                            claimed = nm_wave_sum(a);
+                            for (int j = 0; j < 4; ++j) mq_add(a, nn[j] >= 1u, ln[j], cv[j], bs[j]);
+                            claimed = mq_wave_sum(a);
                             have_claimed = true;
                         }
                         nm_count(ck, lane, every, 0, claimed);
                     }
                     for (unsigned long long rem = occurs & ~every; rem; rem &= rem - 1ull) {   // novel: the nodes that carry the bit
                         const int b = __builtin_ctzll(rem);
-                        NmQ a{0ull, 0ull, 0ull, 0ull};
+                        MemberQ a{0ull, 0ull, 0ull, 0ull};
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) nm_add(a, (wd[j][kk] >> b) & 1ull, ln[j], cv[j], bs[j]);
-                        nm_count(ck, lane, 1ull << b, 0, nm_wave_sum(a));
+                        for (int j = 0; j < 4; ++j) mq_add(a, (wd[j][kk] >> b) & 1ull, ln[j], cv[j], bs[j]);
+                        nm_count(ck, lane, 1ull << b, 0, mq_wave_sum(a));
                     }
                     for (unsigned long long rem = wave_reduce(alone, bit_or); rem; rem &= rem - 1ull) {   // exclusive: the nodes whose only candidate it is
                         const int b = __builtin_ctzll(rem);
-                        NmQ a{0ull, 0ull, 0ull, 0ull};
+                        MemberQ a{0ull, 0ull, 0ull, 0ull};
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) nm_add(a, (nn[j] == 1u) & (bool)((wd[j][kk] >> b) & 1ull), ln[j], cv[j], bs[j]);
-                        nm_count(ck, lane, 1ull << b, 1, nm_wave_sum(a));
+                        for (int j = 0; j < 4; ++j) mq_add(a, (nn[j] == 1u) & (bool)((wd[j][kk] >> b) & 1ull), ln[j], cv[j], bs[j]);
+                        nm_count(ck, lane, 1ull << b, 1, mq_wave_sum(a));
                     }
                 }
             }
             for (uint32_t k = 0; k < kn; ++k) {   // lane b owns bit b of every word
                 const uint32_t e = bit_entry[st.bit_base + 64u * (k0 + k) + (uint32_t)lane];
-                if (e == NM_NO_ENTRY) continue;
+                if (e == MEMBER_NO_ENTRY) continue;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const unsigned long long x = cnt[(k * 8u + q) * 64u + lane];
@@ -213,10 +187,10 @@ __global__ void __launch_bounds__(256) near_miss_node_kernel(uint32_t n_chunks, 
                 }
             }
         }
-        orp = nm_wave_sum(orp); cla = nm_wave_sum(cla); con = nm_wave_sum(con);
+        orp = mq_wave_sum(orp); cla = mq_wave_sum(cla); con = mq_wave_sum(con);
         if (lane == 0) {
             unsigned long long *const o = sp_out + (uint64_t)ch.species * 12u;
-            nm_flush(o, orp); nm_flush(o + 4, cla); nm_flush(o + 8, con);
+            mq_flush(o, orp); mq_flush(o + 4, cla); mq_flush(o + 8, con);
         }
     }
 }
@@ -231,50 +205,37 @@ int near_miss_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
     if (db->H + sel_off[S] + J >= 0xFFFFFFFFull)
         return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_near_miss: %llu haplotypes + entries exceed 32-bit positions", (unsigned long long)(db->H + sel_off[S] + J));
     if (db->V >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_near_miss: %llu nodes exceed 32-bit positions", (unsigned long long)db->V);
-    const bool by_node = db->nh_built && ctx->cfg.near_miss_route != "walk";
+    const bool by_node = member_by_node(db->nh_built, ctx->cfg.near_miss_route);
     std::vector<NmSpecies> tab(S ? S : 1);
-    std::vector<uint32_t> bit_entry(1, NM_NO_ENTRY);   // [species' bit_base + 64 candidate word + bit] -> candidate entry
-    std::vector<NmChunk> chunks;
+    std::vector<uint32_t> bit_entry(1, MEMBER_NO_ENTRY);   // [species' bit_base + 64 candidate word + bit] -> candidate entry
+    std::vector<MemberChunk> chunks;
     std::vector<uint32_t> list;
-    WalkMasks wm;
+    MemberPass ps;
     uint32_t widest = 1;
     for (uint32_t s = 0; s < S; ++s) {
         NmSpecies &st = tab[s];
-        const uint64_t K = sel_off[s + 1] - sel_off[s], Js = cand_off[s + 1] - cand_off[s], nh = db->h_hap_off[s + 1] - db->h_hap_off[s];
-        st = NmSpecies{0ull, 0ull, 0ull, (uint32_t)db->h_node_off[s], 0u, 0u, (uint32_t)K, (uint32_t)Js, 0u, 0u, (uint32_t)bit_entry.size()};
-        if (K + Js && by_node && nh <= 64) {
-            st.route = 1; st.nw = 1; st.cwn = Js ? 1u : 0u;
-            bit_entry.resize(bit_entry.size() + 64u * st.cwn, NM_NO_ENTRY);
-            for (uint64_t c = sel_off[s]; c < sel_off[s + 1]; ++c) st.sel_bits |= 1ull << sel_hap[c];
-            for (uint64_t c = cand_off[s]; c < cand_off[s + 1]; ++c) { st.cand_bits |= 1ull << cand_hap[c]; bit_entry[st.bit_base + cand_hap[c]] = (uint32_t)c; }
-        } else if (K + Js) {
-            st.route = 2; st.nw = (uint32_t)((K + Js + 63) / 64); st.w0 = (uint32_t)(K / 64);
-            st.cwn = Js ? (uint32_t)((K + Js - 1) / 64) - st.w0 + 1u : 0u;
-            bit_entry.resize(bit_entry.size() + 64ull * st.cwn, NM_NO_ENTRY);
-            list.assign(sel_hap + sel_off[s], sel_hap + sel_off[s + 1]);
-            list.insert(list.end(), cand_hap + cand_off[s], cand_hap + cand_off[s + 1]);
-            st.mask_base = wm.add_species(db, s, list.data(), K + Js);
-            for (uint64_t c = cand_off[s]; c < cand_off[s + 1]; ++c) bit_entry[st.bit_base + (K + (c - cand_off[s]) - 64ull * st.w0)] = (uint32_t)c;
-        }
+        const uint32_t *sel = sel_hap + sel_off[s], *cand = cand_hap + cand_off[s];
+        const uint64_t K = sel_off[s + 1] - sel_off[s], Js = cand_off[s + 1] - cand_off[s];
+        list.assign(sel, sel + K); list.insert(list.end(), cand, cand + Js);
+        const MemberRow row = ps.wm.row(db, s, by_node, list.data(), K + Js);
+        const NearMissLayout lay = near_miss_layout(K, Js, row.route);
+        st = NmSpecies{row, row.route == 1u ? member_bits(cand, Js) : 0ull, (uint32_t)Js, lay.w0, lay.cwn, (uint32_t)bit_entry.size()};
+        st.m.K = (uint32_t)K; st.m.bits &= ~st.cand_bits;   // (the sets are disjoint)
+        bit_entry.resize(bit_entry.size() + 64ull * st.cwn, MEMBER_NO_ENTRY);
+        member_file_bits(row.route, cand, Js, lay.cand0, [&](uint64_t bit, uint64_t i) { bit_entry[st.bit_base + bit] = (uint32_t)(cand_off[s] + i); });
         widest = std::max(widest, st.cwn);
         if (bit_entry.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_near_miss: %llu candidate bits exceed 32-bit positions", (unsigned long long)bit_entry.size());
-        for (uint64_t v = db->h_node_off[s]; v < db->h_node_off[s + 1]; v += NM_CHUNK)
-            chunks.push_back(NmChunk{(uint32_t)v, (uint32_t)std::min<uint64_t>(NM_CHUNK, db->h_node_off[s + 1] - v), s, 0u});
+        member_chunks_add(chunks, s, db->h_node_off[s], db->h_node_off[s + 1], NM_CHUNK, 1);
     }
-    if (chunks.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_near_miss: %llu chunks of nodes", (unsigned long long)chunks.size());
     const int cap = ctx->cfg.near_miss_words;
     if (cap < 0 || cap > (int)NM_WORDS) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_near_miss: near_miss_words %d (1 .. %u)", cap, NM_WORDS);
     const uint32_t W = std::min(widest, cap ? (uint32_t)cap : NM_WORDS);
     const size_t n_out = (size_t)J * 8 + (size_t)S * 12;
     if (n_out == 0) return 0;
-    // one device block, zero-filled once: [candidates J x 8][species S x 12]
-    DevBuf<unsigned long long> d_out;
     DevBuf<NmSpecies> d_tab;
     DevBuf<uint32_t> d_bit_entry;
-    DevBuf<NmChunk> d_chunks;
-    PTX_HIP(ctx, d_out.alloc(n_out));
-    PTX_TRY(zero_fill(ctx, d_out.p, n_out * sizeof(unsigned long long)));
-    PTX_TRY(wm.build(ctx, db));
+    DevBuf<MemberChunk> d_chunks;
+    PTX_TRY(ps.open(ctx, db, n_out));   // one device block, zero-filled once: [candidates J x 8][species S x 12]
     if (!chunks.empty()) {
         PTX_TRY(upload(ctx, d_tab, tab.data(), tab.size()));
         PTX_TRY(upload(ctx, d_bit_entry, bit_entry.data(), bit_entry.size()));
@@ -282,14 +243,10 @@ int near_miss_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
         KTimer tm(ctx, "near_miss_node_kernel");
         hipLaunchKernelGGL(W == 1u ? near_miss_node_kernel<1> : near_miss_node_kernel<NM_WORDS>, dim3(grid_for(chunks.size(), 4, ctx->n_cu * 16)), dim3(256), 4u * W * 512u * sizeof(unsigned long long), ctx->stream,
                            (uint32_t)chunks.size(), W, d_chunks.p, d_tab.p, db->d_node_len.p, db->d_cov.p, db->d_bases.p,
-                           by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, wm.d_mask.p, d_bit_entry.p, d_out.p,
-                           d_out.p + (size_t)J * 8);
+                           by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, ps.wm.d_mask.p, d_bit_entry.p, ps.d_out.p,
+                           ps.d_out.p + (size_t)J * 8);
     }
-    PTX_HIP(ctx, hipGetLastError());
-    if (J) PTX_TRY(download(ctx, (unsigned long long *)cand_out, d_out.p, (size_t)J * 8));
-    if (S) PTX_TRY(download(ctx, (unsigned long long *)species_out, d_out.p + (size_t)J * 8, (size_t)S * 12));
-    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host arrays are filled, the temporaries are released on return
-    return 0;
+    return ps.close(ctx, cand_out, (size_t)J * 8, species_out, (size_t)S * 12);
 }
 
 }  // namespace ptx

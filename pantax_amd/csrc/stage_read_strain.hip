@@ -10,13 +10,7 @@
 // Only reads the coverage pass counts (slot species >= 0) are assigned; reads binned to a species of the db but dropped (flags,
 // duplicate-id rule) and reads of species without candidates come out as "not counted" (n = -1).
 //
-// Membership of a node in the candidates' walks, as one mask per node:
-//   route 1 -- species of <= 64 haplotypes whose node -> haplotype words were built at upload (Db::d_node_haps, node_haps_build):
-//              mask(v) = node_haps[v] & cand_bits[s], bit = haplotype index; no array of its own.
-//   route 2 -- every other species (more than 64 haplotypes: node_haps is zero there; no node -> haplotype words; option
-//              read_strain_route=walk): a compact arena of W_s = ceil(K_s / 64) words per node over the species' K_s candidates only
-//              (bit = candidate index, candidates sorted by haplotype), built by read_strain_mask_kernel in one pass over the
-//              candidates' walks (64-bit atomic ORs: the result does not depend on their order).
+// Membership of a node in the candidates' walks, as one mask per node (W_s words on route 2): the two routes of member_plan.hpp, option read_strain_route.
 // read_strain_kernel walks the locus-grouped stream of the coverage pass (build_step_read, stage_read_layout.hip): a wave per 64-step group,
 // a lane per step.  The AND of the masks over a walk's steps is a segmented scan over the lanes on the DPP path; walks of <= 64 steps
 // never straddle a group, so the lane of the last step holds the walk's AND and decides there.  Walks of more than 64 steps (long
@@ -52,22 +46,10 @@ __device__ __forceinline__ void rs_take(unsigned long long m, uint32_t w, const 
 }
 __device__ __forceinline__ RsResult rs_finish(const RsSpecies &st, const uint32_t *__restrict__ bit_hap, double best, uint32_t besti, double sum, int n) {
     RsResult o;
-    if (st.route == 0) { o.hap = 0xFFFFFFFFu; o.n = -1; o.post = 0.0; }
+    if (st.m.route == 0) { o.hap = 0xFFFFFFFFu; o.n = -1; o.post = 0.0; }
     else if (n == 0) { o.hap = 0xFFFFFFFFu; o.n = 0; o.post = 0.0; }
     else { o.hap = bit_hap[st.bit_base + besti]; o.n = n; o.post = best / sum; }
     return o;
-}
-
-// route 2: a wave per tile of one candidate's walk; bit k of the candidate's word on every node the stretch visits
-__global__ void __launch_bounds__(256) read_strain_mask_kernel(uint32_t n_tiles, const WalkMaskTile *__restrict__ tiles, const uint32_t *__restrict__ path_nodes,
-                                                               unsigned long long *__restrict__ mask) {
-    const int lane = threadIdx.x & 63;
-    for (uint32_t t = blockIdx.x * 4 + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * 4) {
-        const WalkMaskTile tl = tiles[t];
-        const unsigned long long bit = 1ull << (tl.k & 63u);
-        const uint64_t wb = tl.word0 + (tl.k >> 6);
-        for (uint64_t p = tl.p0 + (uint64_t)lane; p < tl.p1; p += 64) atomicOr(&mask[wb + (uint64_t)path_nodes[p] * tl.nw], bit);
-    }
 }
 
 __global__ void __launch_bounds__(256) read_strain_kernel(uint32_t n_groups, uint32_t n_slots, const uint32_t *__restrict__ group_slot,
@@ -110,8 +92,8 @@ __global__ void __launch_bounds__(256) read_strain_long_kernel(uint32_t n_slots,
         double best = -INFINITY, sum = 0.0;
         uint32_t besti = 0;
         int n = 0;
-        if (st.route)
-            for (uint32_t w = 0; w < st.nw; ++w) rs_take(long_acc[(uint64_t)s * long_nw + w], w, bit_w, st.bit_base, best, besti, sum, n);
+        if (st.m.route)
+            for (uint32_t w = 0; w < st.m.nw; ++w) rs_take(long_acc[(uint64_t)s * long_nw + w], w, bit_w, st.bit_base, best, besti, sum, n);
         res[s] = rs_finish(st, bit_hap, best, besti, sum, n);
     }
 }
@@ -133,70 +115,40 @@ __global__ void __launch_bounds__(256) read_strain_gather_kernel(uint64_t R, con
 
 }  // namespace
 
-// route 2 for both of its users (read_strains_launch below, evidence_launch in stage_evidence.hip).  add_species: ceil(K / 64) words per node of the
-// species behind what the arena holds so far (bit k = the walk of haps[k]), and the tiles of those K walks ...
-uint64_t WalkMasks::add_species(const Db *db, uint32_t s, const uint32_t *haps, uint64_t K) {
-    const uint64_t base = words;
-    const uint32_t nw = (uint32_t)((K + 63) / 64);
-    words += (db->h_node_off[s + 1] - db->h_node_off[s]) * nw;
-    for (uint64_t k = 0; k < K; ++k) {
-        const uint64_t h = db->h_hap_off[s] + haps[k];
-        for (uint64_t p = db->h_path_off[h]; p < db->h_path_off[h + 1]; p += WALK_MASK_TILE)
-            tiles.push_back(WalkMaskTile{p, std::min(p + WALK_MASK_TILE, db->h_path_off[h + 1]), base, nw, (uint32_t)k});
-    }
-    return base;
-}
-// ... and the pass over them: the arena zero-filled, then one 64-bit atomic OR per visit (the result does not depend on their order)
-int WalkMasks::build(Ctx *ctx, const Db *db) {
-    PTX_HIP(ctx, d_mask.alloc(words ? words : 1));
-    if (words) PTX_TRY(zero_fill(ctx, d_mask.p, words * sizeof(unsigned long long)));
-    if (tiles.empty()) return 0;
-    if (tiles.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "walk masks: %llu tiles of selected walks exceed 32-bit positions", (unsigned long long)tiles.size());
-    PTX_TRY(upload(ctx, d_tiles, tiles.data(), tiles.size()));
-    KTimer tm(ctx, "read_strain_mask_kernel");
-    hipLaunchKernelGGL(read_strain_mask_kernel, dim3(grid_for(tiles.size(), 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, (uint32_t)tiles.size(), d_tiles.p,
-                       db->d_path_nodes.p, d_mask.p);
-    return 0;
-}
-
 int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, uint32_t *hap_out,
                         int32_t *n_out, double *post_out) {
     const uint32_t S = db->S;
     const uint64_t H = db->H, C = cand_off[S];
+    if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "read_strains: %llu haplotypes + candidates exceed 32-bit positions", (unsigned long long)(H + C));
     std::vector<double> bit_w(H + C + 1, 0.0);
     std::vector<uint32_t> bit_hap(H + C + 1, 0u);
     RsTable rt;
     rs_table_build(ctx, db, cand_off, cand_hap, rt, [&](uint64_t at, uint64_t c) { bit_w[at] = cand_w[c]; bit_hap[at] = cand_hap[c]; });
-    std::vector<RsSpecies> &tab = rt.tab;
-    WalkMasks &wm = rt.wm;
-    const bool by_node = rt.by_node;
-    const uint32_t long_nw = rt.long_nw;
-    if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "read_strains: %llu haplotypes + candidates exceed 32-bit positions", (unsigned long long)(H + C));
     DevBuf<RsSpecies> d_tab;
     DevBuf<double> d_bit_w;
     DevBuf<uint32_t> d_bit_hap;
     DevBuf<unsigned long long> d_long;
     DevBuf<RsResult> d_res;
-    PTX_TRY(upload(ctx, d_tab, tab.data(), tab.size()));
+    PTX_TRY(upload(ctx, d_tab, rt.tab.data(), rt.tab.size()));
     PTX_TRY(upload(ctx, d_bit_w, bit_w.data(), bit_w.size()));
     PTX_TRY(upload(ctx, d_bit_hap, bit_hap.data(), bit_hap.size()));
-    PTX_TRY(wm.build(ctx, db));
+    PTX_TRY(rt.wm.build(ctx, db));
     const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
     PTX_HIP(ctx, d_res.alloc(n_slots ? n_slots : 1));
     const bool any_long = rd->n_long != 0;
-    PTX_HIP(ctx, d_long.alloc(any_long ? (size_t)n_slots * long_nw : 1));
-    if (any_long) PTX_HIP(ctx, hipMemsetAsync(d_long.p, 0xFF, (size_t)n_slots * long_nw * sizeof(unsigned long long), ctx->stream));
+    PTX_HIP(ctx, d_long.alloc(any_long ? (size_t)n_slots * rt.long_nw : 1));
+    if (any_long) PTX_HIP(ctx, hipMemsetAsync(d_long.p, 0xFF, (size_t)n_slots * rt.long_nw * sizeof(unsigned long long), ctx->stream));
     if (n_slots && n_groups) {
         KTimer tm(ctx, "read_strain_kernel");
         hipLaunchKernelGGL(read_strain_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->d_g_group_slot.p,
                            rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p,
-                           by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, wm.d_mask.p, d_bit_w.p, d_bit_hap.p,
-                           d_long.p, long_nw, d_res.p);
+                           rt.by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, rt.wm.d_mask.p, d_bit_w.p, d_bit_hap.p,
+                           d_long.p, rt.long_nw, d_res.p);
     }
     if (n_slots && any_long) {
         KTimer tm(ctx, "read_strain_long_kernel");
         hipLaunchKernelGGL(read_strain_long_kernel, dim3(grid_for(n_slots, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, n_slots, rd->d_g_read_rec.p,
-                           rd->d_g_slot_rec.p, d_tab.p, d_long.p, long_nw, d_bit_w.p, d_bit_hap.p, d_res.p);
+                           rd->d_g_slot_rec.p, d_tab.p, d_long.p, rt.long_nw, d_bit_w.p, d_bit_hap.p, d_res.p);
     }
     const uint64_t R = rd->R;
     if (R) {

@@ -114,7 +114,7 @@ __device__ __forceinline__ void sup_wave_reduce(int lane, bool decide, uint32_t 
         const SupSpecies su = sup[s0];
         unsigned long long *const so = out.sp + (uint64_t)s0 * 12u;
         sup_reduce_add(lane, mine, mb, steps, span, so);                     // counted
-        if (st.route == 0u) continue;
+        if (st.m.route == 0u) continue;
         {
             const bool un = mine && r.n == 0u, am = mine && r.n >= 2u, ui = mine && r.n == su.K;
             const unsigned long long b_un = __builtin_amdgcn_ballot_w64(un), b_am = __builtin_amdgcn_ballot_w64(am), b_ui = __builtin_amdgcn_ballot_w64(ui);
@@ -122,8 +122,8 @@ __device__ __forceinline__ void sup_wave_reduce(int lane, bool decide, uint32_t 
             if (b_am) sup_reduce_add(lane, am, b_am, steps, span, so + 6);
             if (b_ui) sup_reduce_add(lane, ui, b_ui, steps, span, so + 9);
         }
-        if (st.nw > 1u) continue;                                            // plain path: the lanes have filed their candidates themselves
-        const unsigned long long bits = st.route == 1u ? st.cand_bits : (su.K >= 64u ? ~0ull : (1ull << su.K) - 1ull);
+        if (st.m.nw > 1u) continue;                                            // plain path: the lanes have filed their candidates themselves
+        const unsigned long long bits = st.m.route == 1u ? st.m.bits : (su.K >= 64u ? ~0ull : (1ull << su.K) - 1ull);
         const unsigned long long mm = mine ? r.m0 : 0ull;
         unsigned long long present = 0ull;
         for (unsigned long long q = bits; q; q &= q - 1ull) {
@@ -203,9 +203,9 @@ __global__ void __launch_bounds__(256) read_support_long_kernel(uint32_t n_slots
         uint32_t sp = 0xFFFFFFFFu;
         if (in) { rr = read_rec[s]; sp = slot_rec[s].x; }
         const bool decide = in && rr.y > 64u && (int32_t)sp >= 0;
-        RsSpecies st{0ull, 0ull, 0u, 0u, 0u, 0u};
+        RsSpecies st{};
         if (decide) st = tab[sp];
-        const uint32_t nw = st.route ? st.nw : 0u;
+        const uint32_t nw = st.m.route ? st.m.nw : 0u;
         const uint32_t steps = rr.y, span = sup_span(rr);
         SupRead r{0ull, 0u, 0u, 0u, -INFINITY};
         for (uint32_t w = 0; w < nw; ++w) sup_take(long_acc[s * long_nw + w], w, st, nw > 1u, bit_w, bit_entry, out.hap, steps, span, r);
