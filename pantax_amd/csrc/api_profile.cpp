@@ -3,7 +3,7 @@
 // strain_abundance.txt, ori_strain_abundance.txt, optional reads_classification.tsv).
 // Host orchestration only; every per-read / per-node computation goes through the device stages.
 // profile_impl (at the end) is the sequence of the phases, functions of the structs of profile_run.hpp; the shard phase is profile_shard.cpp, the ranks
-// meet in RankComm (profile_comm.hpp), the I/O-free decisions are in profile_pure.cpp.
+// meet in RankComm (profile_comm.hpp), the I/O-free decisions are in profile_pure.cpp, the per-strain reports in report_plan.cpp / profile_reports.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -47,46 +47,8 @@ int check_args(Run &run) {
     c.use_comm = W > 1 || (cfg->world_size == 1 && cfg->allreduce_sum != nullptr);
     p.sharded = c.use_comm && cfg->alltoallv != nullptr;
     if (p.sharded && W > 64) return fail(ctx, PANTAX_HIP_E_LIMIT, "profile: the sharded ingest routes reads to at most 64 ranks (world_size %d)", W);
-    // --read-strains: the rows of a species live on the rank that owns it, the rows of the file on the rank of its byte range -- not joined here
-    p.rs_path = opt(cfg->read_strain_file);
-    p.want_rs = !p.rs_path.empty() && p.rs_path != "None";
-    if (p.want_rs && (W > 1 || p.sharded))
-        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-read strain report (read_strain_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
-                    p.sharded ? ", sharded" : "");
-    // --strain-coverage: the same reason -- the windows of a strain live on the rank that owns its species
-    p.ct_path = opt(cfg->strain_coverage_file);
-    p.want_ct = !p.ct_path.empty() && p.ct_path != "None";
-    if (p.want_ct && (W > 1 || p.sharded))
-        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain coverage track (strain_coverage_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
-                    p.sharded ? ", sharded" : "");
-    if (p.want_ct && cfg->strain_coverage_window < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "profile: strain_coverage_window %lld", (long long)cfg->strain_coverage_window);
-    p.ct_window = p.want_ct && cfg->strain_coverage_window > 0 ? (uint64_t)cfg->strain_coverage_window : 10000;
-    // --strain-evidence: the same again -- a species' sums live on the rank that owns it
-    p.ev_path = opt(cfg->strain_evidence_file);
-    p.want_ev = !p.ev_path.empty() && p.ev_path != "None";
-    if (p.want_ev && (W > 1 || p.sharded))
-        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain node evidence report (strain_evidence_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
-                    p.sharded ? ", sharded" : "");
-    // --strain-read-support: the same again -- a species' reads live on the rank that owns it
-    p.sup_path = opt(cfg->strain_read_support_file);
-    p.want_sup = !p.sup_path.empty() && p.sup_path != "None";
-    if (p.want_sup && (W > 1 || p.sharded))
-        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain read support report (strain_read_support_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
-                    p.sharded ? ", sharded" : "");
-    // --strain-depth: the same again -- a species' histograms live on the rank that owns it
-    p.dp_path = opt(cfg->strain_depth_file);
-    p.want_dp = !p.dp_path.empty() && p.dp_path != "None";
-    if (p.want_dp && (W > 1 || p.sharded))
-        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the per-strain depth distribution report (strain_depth_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
-                    p.sharded ? ", sharded" : "");
-    // --strain-near-miss: the same again -- a species' orphan nodes and its candidates live on the rank that owns it
-    p.nm_path = opt(cfg->strain_near_miss_file);
-    p.want_nm = !p.nm_path.empty() && p.nm_path != "None";
-    if (p.want_nm && (W > 1 || p.sharded))
-        return fail(ctx, PANTAX_HIP_E_INVALID, "profile: the unreported-strain near-miss report (strain_near_miss_file) needs one rank and an unsharded ingest (world_size %d%s)", W,
-                    p.sharded ? ", sharded" : "");
-    if (p.want_nm && cfg->strain_near_miss_top < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "profile: strain_near_miss_top %d", (int)cfg->strain_near_miss_top);
-    p.nm_top = p.want_nm && cfg->strain_near_miss_top > 0 ? (uint32_t)cfg->strain_near_miss_top : 5u;
+    std::string rep_err;   // the per-strain reports: wanted? one rank and an unsharded ingest; their two parameters (report_plan.cpp)
+    if (!plan_reports(cfg, W, p.sharded, p.rep, rep_err)) return fail(ctx, PANTAX_HIP_E_INVALID, "%s", rep_err.c_str());
     p.db_dir = opt(cfg->db); p.wd = opt(cfg->wd); p.out_dir = opt(cfg->output_dir);
     if (p.out_dir.empty()) p.out_dir = p.wd;
     if (!is_dir(p.db_dir)) return fail(ctx, PANTAX_HIP_E_IO, "Specified PanTax database directory '%s' is not a valid directory path", p.db_dir.c_str());
@@ -113,18 +75,13 @@ int decide_resume(Run &run) {
         PTX_TRY(run.comm.allreduce(d, 3));
         run.p.full_path = d[0] != 0.0; run.p.strain_only = d[1] != 0.0; run.p.strain_done = d[2] != 0.0;
     }
-    run.p.rs_run = run.p.want_rs && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
-    run.p.ct_run = run.p.want_ct && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
-    run.p.ev_run = run.p.want_ev && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
-    run.p.sup_run = run.p.want_sup && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
-    run.p.dp_run = run.p.want_dp && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
-    run.p.nm_run = run.p.want_nm && run.cfg->strain && !(run.p.full_path && run.p.strain_done);
+    resume_reports(run.p.rep, run.cfg->strain, run.p.full_path, run.p.strain_done);
     run.p.want_report = run.p.full_path && !run.p.report.empty() && run.p.report != "None";
     return 0;
 }
 void rs_skipped(const RunPlan &p) {
-    for (const std::string *f : {p.want_rs ? &p.rs_path : nullptr, p.want_ct ? &p.ct_path : nullptr, p.want_ev ? &p.ev_path : nullptr, p.want_sup ? &p.sup_path : nullptr, p.want_dp ? &p.dp_path : nullptr, p.want_nm ? &p.nm_path : nullptr})
-        if (f) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", f->c_str());
+    for (int i = 0; i < N_REPORTS; ++i)
+        if (p.rep.want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.path[i].c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
 // ALL species ranges (ranges-only db), counters on the device
@@ -152,7 +109,7 @@ int ingest_local(Run &run, Ingest &in) {
     // (no locus-grouped copy yet: the species decision needs the counters only -- the plain columns are binned in file order --, and the copy is
     // built while the first graphs travel, on an otherwise idle device; round 5 built it here, 27 ms behind the last byte of the GAF at 1e8 reads)
     PTX_TRY(gaf_tokenize_device(run.ctx, in.mf.data + in.text_begin, text_end - in.text_begin, in.hr, in.reads.rd, in.mf.fd, in.text_begin, /*group=*/false,
-                                /*want_id_spans=*/run.p.want_report || run.p.rs_run, /*want_host_columns=*/false));
+                                /*want_id_spans=*/run.p.want_report || run.p.rep.run[REP_READ_STRAINS], /*want_host_columns=*/false));
     in.R = in.R_all = in.reads.rd->R;
     run.lap("ranges + GAF tokenise");
     in.rs.resize(S); in.re.resize(S);
@@ -182,7 +139,7 @@ int host_cols(Run &run, Ingest &in) {
 // ingest: tokenise, bin all species, head rows; ends in the collective that carries its status
 int ingest(Run &run, Ingest &in) {
     int local_rc = ingest_local(run, in);
-    if (local_rc == 0 && (run.p.want_report || run.p.sharded || run.p.strain_only || run.p.rs_run)) local_rc = host_cols(run, in);
+    if (local_rc == 0 && (run.p.want_report || run.p.sharded || run.p.strain_only || run.p.rep.run[REP_READ_STRAINS])) local_rc = host_cols(run, in);
     // the read lengths of the first (up to 1000) binned rows of the FILE decide the equal-length branch (profile.rs:312-319): they are among the
     // first rows the binning pass hands back with its counters, unless those hold fewer than 1000 binned rows of a longer file
     if (local_rc == 0 && !in.have_cols) {
@@ -481,8 +438,6 @@ int route_reads(Run &run, Ingest &in, const Selection &sn, int *unpack_rc) {
 }
 // rows keep (species position in the selection, running number) so that any merge reproduces the one-process order
 struct OutRow { double key; uint32_t k, seq; std::string line; };
-// a row of strain_abundance.txt as the --strain-coverage, --strain-evidence, --strain-read-support and --strain-depth reports follow it: its sort key, its haplotype (into ShardResult::hap_names), its joined genome or null
-struct TrackRow { double key; uint32_t k; uint64_t hap; const GenomeRow *gr; };
 bool write_part(const std::string &path, const std::vector<OutRow> &rows) {
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -570,7 +525,7 @@ int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardRe
             for (const GenomeRow *gr : grs) {
                 ori_rows.push_back({0.0, sh.use[k], seq, strain_row_text(species, gr, m, hs ? m.second_sol / sum_all : 0.0, hs, false)});
                 if (pass[h]) final_rows.push_back({m.second_sol / sum_pass, sh.use[k], seq, strain_row_text(species, gr, m, m.second_sol / sum_pass, true, !run.cfg->full)});   // :3250-3284
-                if (pass[h] && (run.p.ct_run || run.p.ev_run || run.p.sup_run || run.p.dp_run)) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
+                if (pass[h] && run.p.rep.rows_run()) track_rows.push_back({m.second_sol / sum_pass, k, h, gr});   // (one rank: already in the order of final_rows)
                 ++seq;
             }
         }
@@ -589,232 +544,6 @@ int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardRe
     f << header;
     for (auto &r : final_rows) f << r.line << '\n';
     run.lap("tables");
-    return 0;
-}
-// --read-strains: one row per GAF record, in the -R report's order (read_id and species_taxid are its columns 1 and 3)
-int read_strains_report(Run &run, const Ingest &in, const ShardResult &sh, const std::vector<GenomeRow> &genomes) {
-    const std::string &rs_path = run.p.rs_path;
-    std::unordered_map<std::string, size_t> first_genome;   // the first genomes_info.txt row of every haplotype (the strain table's left join)
-    for (size_t i = genomes.size(); i-- > 0;) first_genome[genomes[i].hap_id] = i;
-    std::ofstream rf(rs_path);
-    if (!rf) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", rs_path.c_str());
-    for (uint64_t r = 0; r < in.R; ++r) {
-        rf.write(in.mf.data + in.text_begin + in.hr.id_span[r].first, in.hr.id_span[r].second);
-        rf << '\t' << (in.sp_idx[r] >= 0 ? in.ranges[in.sp_idx[r]].species : std::string("U")) << '\t';
-        if (sh.rs_n[r] < 0) rf << "U\tU\t-\t0\n";
-        else if (sh.rs_n[r] == 0 || sh.rs_hap[r] == ~0ull) rf << "U\tU\t0\t0\n";
-        else {
-            auto it = first_genome.find(sh.hap_names[sh.rs_hap[r]]);
-            if (it != first_genome.end()) rf << genomes[it->second].genome_id << '\t' << genomes[it->second].strain_taxid;
-            else rf << '\t';
-            rf << '\t' << sh.rs_n[r] << '\t' << fmt_f64(sh.rs_post[r]) << '\n';
-        }
-    }
-    rf.close();
-    if (!rf) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", rs_path.c_str());
-    run.lap("read strains report");
-    return 0;
-}
-// --strain-coverage: the windows of every row of strain_abundance.txt, in its order (the same stable sort on the same keys)
-int cov_track_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, std::vector<TrackRow> &rows) {
-    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });
-    std::ofstream f(run.p.ct_path);
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.ct_path.c_str());
-    f << "species_taxid\tstrain_taxid\tgenome_ID\tstart\tend\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\n";
-    const uint64_t W = run.p.ct_window;
-    for (const TrackRow &r : rows) {
-        const int64_t e = sh.ct_entry[r.hap];
-        if (e < 0) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no coverage track", sh.hap_names[r.hap].c_str());
-        std::string head = in.ranges[sn.sel[sh.use[r.k]]].species;
-        head += '\t'; if (r.gr) head += r.gr->strain_taxid;
-        head += '\t'; if (r.gr) head += r.gr->genome_id;
-        const uint64_t w0 = sh.ct_win_off[e], w1 = sh.ct_win_off[e + 1];
-        uint64_t G = 0;
-        for (uint64_t i = w0; i < w1; ++i) G += sh.ct_len[i];
-        for (uint64_t i = w0; i < w1; ++i) {
-            if (sh.ct_len[i] == 0) continue;   // no node starts here: a longer node runs through
-            const uint64_t start = (i - w0) * W, end = i + 1 == w1 ? G : start + W;   // (only the last window can be cut short: start + W <= G before it)
-            f << head << '\t' << start << '\t' << end << '\t' << sh.ct_n_nodes[i] << '\t' << sh.ct_len[i] << '\t' << sh.ct_covered[i] << '\t' << sh.ct_bases[i] << '\t'
-              << fmt_f64((double)sh.ct_bases[i] / (double)sh.ct_len[i]) << '\t' << fmt_f64((double)sh.ct_covered[i] / (double)sh.ct_len[i]) << '\n';
-        }
-    }
-    f.close();
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.ct_path.c_str());
-    run.lap("strain coverage report");
-    return 0;
-}
-// --strain-evidence: {all, private} of every row of strain_abundance.txt, in its order (the same stable sort on the same keys), then {total, orphan, core}
-// of every species of the shard in the order it went through the device (the selection's: the species table's)
-int evidence_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, std::vector<TrackRow> &rows) {
-    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });
-    std::ofstream f(run.p.ev_path);
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.ev_path.c_str());
-    f << "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\tpredicted_coverage\n";
-    const auto put = [&f](const std::string &head, const char *cls, const uint64_t *q, const std::string &pc) {   // q = {n_nodes, len, covered, bases}
-        f << head << '\t' << cls << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << q[3] << '\t';
-        if (q[1]) f << fmt_f64((double)q[3] / (double)q[1]) << '\t' << fmt_f64((double)q[2] / (double)q[1]);
-        else f << "-\t-";
-        f << '\t' << pc << '\n';
-    };
-    for (const TrackRow &r : rows) {
-        const int64_t e = sh.ev_entry[r.hap];
-        if (e < 0) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no node evidence", sh.hap_names[r.hap].c_str());
-        std::string head = in.ranges[sn.sel[sh.use[r.k]]].species;
-        head += '\t'; if (r.gr) head += r.gr->strain_taxid;
-        head += '\t'; if (r.gr) head += r.gr->genome_id;
-        const std::string pc = fmt_f64(sh.met[r.hap].second_sol);
-        put(head, "all", sh.ev_hap.data() + 8 * e, pc);
-        put(head, "private", sh.ev_hap.data() + 8 * e + 4, pc);
-    }
-    for (uint32_t k = 0; k < (uint32_t)sh.use.size(); ++k) {
-        const std::string head = in.ranges[sn.sel[sh.use[k]]].species + "\t-\t-";
-        const uint64_t *q = sh.ev_species.data() + 12 * (size_t)k;
-        put(head, "total", q, "-");
-        put(head, "orphan", q + 4, "-");
-        double pc = 0.0;
-        bool any = false;
-        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
-            if (sh.ev_entry[h] >= 0) { pc += sh.met[h].second_sol; any = true; }
-        if (any) put(head, "core", q + 8, fmt_f64(pc));
-    }
-    f.close();
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.ev_path.c_str());
-    run.lap("strain evidence report");
-    return 0;
-}
-// --strain-read-support: {compatible, unique, assigned} of every row of strain_abundance.txt, in its order; {counted, unexplained, ambiguous, uninformative} of
-// every species of the shard in the order it went through the device (a species without rows: counted only); the shared reads of every pair of rows
-int read_support_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, std::vector<TrackRow> &rows) {
-    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });
-    std::ofstream f(run.p.sup_path);
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.sup_path.c_str());
-    f << "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_reads\tn_steps\tspan\tfraction\tother_strain_taxid\n";
-    const auto frac = [](uint64_t n, uint64_t of) { return of ? fmt_f64((double)n / (double)of) : std::string("-"); };
-    const auto put = [&](const std::string &head, const char *cls, const uint64_t *q, uint64_t of) {   // q = {n_reads, n_steps, span}
-        f << head << '\t' << cls << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << frac(q[0], of) << "\t-\n";
-    };
-    const auto strain_head = [&](const TrackRow &r) {
-        std::string head = in.ranges[sn.sel[sh.use[r.k]]].species;
-        head += '\t'; if (r.gr) head += r.gr->strain_taxid;
-        head += '\t'; if (r.gr) head += r.gr->genome_id;
-        return head;
-    };
-    std::vector<const TrackRow *> row_of(sh.sup_hap.size() / 9, nullptr);   // entry -> its first row of the table
-    for (const TrackRow &r : rows) {
-        const int64_t e = sh.sup_entry[r.hap];
-        if (e < 0) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no read support", sh.hap_names[r.hap].c_str());
-        if (!row_of[e]) row_of[e] = &r;
-        const std::string head = strain_head(r);
-        const uint64_t of = sh.sup_species[12 * (size_t)r.k];
-        put(head, "compatible", sh.sup_hap.data() + 9 * e, of);
-        put(head, "unique", sh.sup_hap.data() + 9 * e + 3, of);
-        put(head, "assigned", sh.sup_hap.data() + 9 * e + 6, of);
-    }
-    for (uint32_t k = 0; k < (uint32_t)sh.use.size(); ++k) {
-        const std::string head = in.ranges[sn.sel[sh.use[k]]].species + "\t-\t-";
-        const uint64_t *q = sh.sup_species.data() + 12 * (size_t)k;
-        put(head, "counted", q, q[0]);
-        if (!sh.sup_K[k]) continue;
-        put(head, "unexplained", q + 3, q[0]);
-        put(head, "ambiguous", q + 6, q[0]);
-        put(head, "uninformative", q + 9, q[0]);
-    }
-    for (uint32_t k = 0; k < (uint32_t)sh.use.size(); ++k) {
-        const uint64_t K = sh.sup_K[k];
-        if (K < 2 || K > 64) continue;
-        int64_t e0 = -1;                                                        // the species' entries are consecutive, in ascending haplotype index
-        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1] && e0 < 0; ++h) e0 = sh.sup_entry[h];
-        const uint64_t *pm = sh.sup_pair.data() + sh.sup_pair_off[k];
-        for (uint64_t a = 0; a < K; ++a)
-            for (uint64_t b = a + 1; b < K; ++b) {
-                const uint64_t n = pm[a * K + b];
-                if (!n || e0 < 0 || !row_of[e0 + a] || !row_of[e0 + b]) continue;
-                const TrackRow &ra = *row_of[e0 + a], &rb = *row_of[e0 + b];
-                f << strain_head(ra) << "\tshared\t" << n << "\t-\t-\t" << frac(n, std::min(pm[a * K + a], pm[b * K + b])) << '\t'
-                  << (rb.gr ? rb.gr->strain_taxid : std::string()) << '\n';
-            }
-    }
-    f.close();
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.sup_path.c_str());
-    run.lap("strain read support report");
-    return 0;
-}
-// --strain-depth: the depth histograms {all, private} of every row of strain_abundance.txt, in its order, then {total, orphan} of every species of the shard
-// in the order it went through the device; per histogram its node count, its length, the length at depth 0 and the length-weighted quantiles
-int depth_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, std::vector<TrackRow> &rows) {
-    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });
-    std::ofstream f(run.p.dp_path);
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.dp_path.c_str());
-    f << "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_nodes\tlen\tlen_zero\tq05\tq25\tq50\tq75\tq95\tq50_hi\tpredicted_coverage\n";
-    constexpr size_t HIST = 2 * PANTAX_HIP_DEPTH_BINS;   // u64 per histogram: [bin]{n_nodes, len}
-    const auto put = [&f](const std::string &head, const char *cls, const uint64_t *hist, const std::string &pc) {
-        uint64_t n = 0, len = 0;
-        for (uint32_t b = 0; b < PANTAX_HIP_DEPTH_BINS; ++b) { n += hist[2 * b]; len += hist[2 * b + 1]; }
-        f << head << '\t' << cls << '\t' << n << '\t' << len << '\t' << hist[1];
-        uint64_t hi50 = 0;
-        for (const uint32_t pm : {50u, 250u, 500u, 750u, 950u}) {
-            uint32_t bin = 0;
-            uint64_t lo = 0, hi = 0;
-            if (pantax_hip_depth_quantile(hist, pm, &bin) != 0) { f << "\t-"; continue; }   // len = 0
-            pantax_hip_depth_bin_range(bin, &lo, &hi);
-            if (pm == 500u) hi50 = hi;
-            f << '\t' << lo;
-        }
-        if (len) f << '\t' << hi50; else f << "\t-";
-        f << '\t' << pc << '\n';
-    };
-    for (const TrackRow &r : rows) {
-        const int64_t e = sh.dp_entry[r.hap];
-        if (e < 0) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no depth histogram", sh.hap_names[r.hap].c_str());
-        std::string head = in.ranges[sn.sel[sh.use[r.k]]].species;
-        head += '\t'; if (r.gr) head += r.gr->strain_taxid;
-        head += '\t'; if (r.gr) head += r.gr->genome_id;
-        const std::string pc = fmt_f64(sh.met[r.hap].second_sol);
-        put(head, "all", sh.dp_hap.data() + 2 * HIST * e, pc);
-        put(head, "private", sh.dp_hap.data() + 2 * HIST * e + HIST, pc);
-    }
-    for (uint32_t k = 0; k < (uint32_t)sh.use.size(); ++k) {
-        const std::string head = in.ranges[sn.sel[sh.use[k]]].species + "\t-\t-";
-        put(head, "total", sh.dp_species.data() + 2 * HIST * (size_t)k, "-");
-        put(head, "orphan", sh.dp_species.data() + 2 * HIST * (size_t)k + HIST, "-");
-    }
-    f.close();
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.dp_path.c_str());
-    run.lap("strain depth report");
-    return 0;
-}
-// --strain-near-miss: per species of the shard, in the order it went through the device, the candidates group_near_miss kept, in rank order, classes novel,
-// exclusive, all each; then {orphan, claimed, contested} of every species.  strain_taxid / genome_ID: the first genomes_info.txt row of the haplotype
-int near_miss_report(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, const std::vector<GenomeRow> &genomes) {
-    std::unordered_map<std::string, size_t> first_genome;
-    for (size_t i = genomes.size(); i-- > 0;) first_genome[genomes[i].hap_id] = i;
-    std::ofstream f(run.p.nm_path);
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.nm_path.c_str());
-    f << "species_taxid\tstrain_taxid\tgenome_ID\trank\tclass\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\tshare\tstage\tunique_trio_nodes_fraction\tfrequencies_mean\tfirst_sol\tsecond_sol\n";
-    const uint32_t Su = (uint32_t)sh.use.size();
-    for (uint32_t k = 0; k < Su; ++k) {
-        const std::string &species = in.ranges[sn.sel[sh.use[k]]].species;
-        const uint64_t orphan_bases = sh.nm_species[12 * (size_t)k + 3];
-        for (uint64_t i = sh.nm_row_off[k]; i < sh.nm_row_off[k + 1]; ++i) {
-            const ShardResult::NearMissRow &r = sh.nm_rows[i];
-            const auto it = first_genome.find(sh.hap_names[r.hap]);
-            const GenomeRow *gr = it != first_genome.end() ? &genomes[it->second] : nullptr;
-            const uint32_t rank = (uint32_t)(i - sh.nm_row_off[k]) + 1;
-            f << near_miss_row_text(species, gr, &sh.met[r.hap], rank, "novel", r.q, true, orphan_bases) << '\n'
-              << near_miss_row_text(species, gr, &sh.met[r.hap], rank, "exclusive", r.q + 4, true, orphan_bases) << '\n'
-              << near_miss_row_text(species, gr, &sh.met[r.hap], rank, "all", r.q + 8, false, orphan_bases) << '\n';
-        }
-    }
-    for (uint32_t k = 0; k < Su; ++k) {
-        const std::string &species = in.ranges[sn.sel[sh.use[k]]].species;
-        const uint64_t *q = sh.nm_species.data() + 12 * (size_t)k;
-        f << near_miss_row_text(species, nullptr, nullptr, 0, "orphan", q, true, q[3]) << '\n'
-          << near_miss_row_text(species, nullptr, nullptr, 0, "claimed", q + 4, true, q[3]) << '\n'
-          << near_miss_row_text(species, nullptr, nullptr, 0, "contested", q + 8, true, q[3]) << '\n';
-    }
-    f.close();
-    if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", run.p.nm_path.c_str());
-    run.lap("strain near-miss report");
     return 0;
 }
 // The phases in order.  `rc` is this rank's status since the last collective (RankComm's rule): PTX_TRY where a phase has ended in the collective
@@ -861,12 +590,7 @@ int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
     std::vector<GenomeRow> genomes;
     std::vector<TrackRow> track_rows;
     PTX_TRY(strain_tables(run, in, sn, sh, rc ? rc : sh.rc, genomes, track_rows));           // all-reduce: status + normalisers [+ barrier]
-    if (p.rs_run) PTX_TRY(read_strains_report(run, in, sh, genomes));
-    if (p.ct_run) PTX_TRY(cov_track_report(run, in, sn, sh, track_rows));
-    if (p.ev_run) PTX_TRY(evidence_report(run, in, sn, sh, track_rows));
-    if (p.sup_run) PTX_TRY(read_support_report(run, in, sn, sh, track_rows));
-    if (p.dp_run) PTX_TRY(depth_report(run, in, sn, sh, track_rows));
-    return p.nm_run ? near_miss_report(run, in, sn, sh, genomes) : 0;
+    return reports::write(run, in, sn, sh, genomes, track_rows);                              // the files of the per-strain reports
 }
 
 }  // namespace

@@ -1,0 +1,369 @@
+// profile_reports.cpp -- the per-strain reports of the file seam (profile_reports.hpp): per group of species, behind its strain step, the group's rows of
+// strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
+// writes its file.  begin, collect_group and write at the end are the three places that name the reports.
+#include <algorithm>
+#include <fstream>
+#include <unordered_map>
+#include "profile_run.hpp"
+
+namespace ptx {
+namespace {
+constexpr size_t EVIDENCE_N = 4, DEPTH_N = 2 * PANTAX_HIP_DEPTH_BINS;   // u64 per class: {n_nodes, len, covered, bases}; a histogram of [96]{n_nodes, len}
+// The group's rows of strain_abundance.txt, decided in the group's own turn (the a15 filter is row-local) and read by all six reports: `pass` as bits over
+// the shard's haplotypes; per species of the group [off[k - k0], off[k - k0 + 1]) the species-local haplotypes `hap` in ascending order with their
+// second_sol weights `w`; the i-th of them is entry entry0 + i of ReportData
+struct GroupSel { std::vector<uint8_t> pass; std::vector<uint64_t> off; std::vector<uint32_t> hap; std::vector<double> w; size_t entry0 = 0; };
+int group_select(Run &run, uint32_t k0, uint32_t k1, ShardResult &sh, GroupSel &g) {
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint8_t> rep_g(Sg);
+    for (uint32_t k = k0; k < k1; ++k) rep_g[k - k0] = (sh.info[k].status1 == 0 && sh.info[k].status2 == 0) ? 1 : 0;
+    g.pass.assign(sh.hap_names.size() ? sh.hap_names.size() : 1, 0);
+    PTX_TRY(pantax_hip_abundance_filter(Sg, sh.hap_off.data() + k0, sh.met.data(), rep_g.data(), run.cfg->single_cov_diff, run.cfg->min_cov, g.pass.data(), nullptr, nullptr, nullptr, nullptr));
+    g.off.assign(Sg + 1, 0);
+    g.entry0 = sh.rep.n_entries;
+    for (uint32_t k = k0; k < k1; ++k) {
+        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
+            if (g.pass[h]) { sh.rep.entry[h] = (int64_t)(g.entry0 + g.hap.size()); g.hap.push_back((uint32_t)(h - sh.hap_off[k])); g.w.push_back(sh.met[h].second_sol); }
+        g.off[k - k0 + 1] = g.hap.size();
+    }
+    sh.rep.n_entries += g.hap.size();
+    return 0;
+}
+// --read-strains: the candidates of every read are the rows of its species
+int group_read_strains(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    const uint64_t R = in.R;
+    const pantax_hip_read_strain_set cs{k1 - k0, g.off.data(), g.hap.data(), g.w.data()};
+    constexpr int32_t UNTOUCHED = -3;   // entries of reads outside this group's species keep it
+    std::vector<uint32_t> t_hap(R, 0u);
+    std::vector<int32_t> t_n(R, UNTOUCHED), g_sp(R, -1);
+    std::vector<double> t_post(R, 0.0);
+    PTX_TRY(pantax_hip_read_strains(run.ctx, db, in.reads.rd, &cs, t_hap.data(), t_n.data(), t_post.data()));
+    if (R) {   // the group-local species of every read (the slot records of this group's binning pass)
+        PTX_TRY(species_ensure(run.ctx, in.reads.rd));
+        PTX_TRY(download(run.ctx, g_sp.data(), in.reads.rd->d_species.p, R));
+        PTX_HIP(run.ctx, hipStreamSynchronize(run.ctx->stream));
+    }
+    auto &rs = sh.rep.rs;
+    for (uint64_t r = 0; r < R; ++r) {
+        if (t_n[r] == UNTOUCHED) continue;
+        rs.n[r] = t_n[r]; rs.post[r] = t_post[r];
+        rs.hap[r] = t_n[r] > 0 && g_sp[r] >= 0 ? sh.hap_off[k0 + (uint32_t)g_sp[r]] + t_hap[r] : ~0ull;
+    }
+    run.lap("  read strains");
+    return 0;
+}
+// --strain-coverage, while the coverage result of the group is still on the device: the windows of the group's rows
+int group_cov_track(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &ct = sh.rep.ct;
+    const pantax_hip_cov_track_set set{k1 - k0, g.off.data(), g.hap.data(), run.p.rep.ct_window};
+    std::vector<uint64_t> w_off(g.hap.size() + 1, 0);
+    const int rc_size = pantax_hip_strain_cov_track(run.ctx, db, &set, w_off.data(), 0, nullptr, nullptr, nullptr, nullptr);   // sizes: E_LIMIT unless there is no window
+    if (rc_size != 0 && rc_size != PANTAX_HIP_E_LIMIT) return rc_size;
+    const uint64_t n = w_off[g.hap.size()], at = ct.len.size();
+    ct.n_nodes.resize(at + n); ct.len.resize(at + n); ct.covered.resize(at + n); ct.bases.resize(at + n);
+    if (n) PTX_TRY(pantax_hip_strain_cov_track(run.ctx, db, &set, w_off.data(), n, ct.n_nodes.data() + at, ct.len.data() + at, ct.covered.data() + at, ct.bases.data() + at));
+    for (size_t e = 0; e < g.hap.size(); ++e) ct.win_off.push_back(at + w_off[e + 1]);
+    run.lap("  strain coverage track");
+    return 0;
+}
+// --strain-evidence and --strain-depth, on the same coverage result: Sel_s = the group's rows; `call` writes n_hap u64 per entry and n_species per species
+int group_node_sums(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, decltype(&pantax_hip_strain_evidence) call, size_t n_hap, size_t n_species, ReportData::NodeSums &out, const char *lap) {
+    const pantax_hip_evidence_set set{k1 - k0, g.off.data(), g.hap.data()};
+    out.hap.resize(n_hap * (g.entry0 + g.hap.size()));
+    PTX_TRY(call(run.ctx, db, &set, out.hap.data() + n_hap * g.entry0, out.species.data() + n_species * (size_t)k0));
+    run.lap(lap);
+    return 0;
+}
+// --strain-read-support: the candidates and weights of group_read_strains, summed on the device (nothing per read comes back)
+int group_read_support(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &sup = sh.rep.sup;
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint64_t> p_off(Sg + 1, 0);
+    const pantax_hip_read_strain_set cs{Sg, g.off.data(), g.hap.data(), g.w.data()};
+    sup.hap.resize(9 * (g.entry0 + g.hap.size()));
+    uint64_t n_pair = 0;
+    for (uint32_t k = 0; k < Sg; ++k) { const uint64_t K = g.off[k + 1] - g.off[k]; sup.K[k0 + k] = (uint32_t)K; n_pair += K <= 64 ? K * K : 0; }
+    const size_t pair0 = sup.pair.size();
+    sup.pair.resize(pair0 + n_pair);
+    PTX_TRY(pantax_hip_strain_read_support(run.ctx, db, in.reads.rd, &cs, sup.hap.data() + 9 * g.entry0, sup.species.data() + 12 * (size_t)k0, p_off.data(), n_pair,
+                                           sup.pair.data() + pair0));
+    for (uint32_t k = 0; k < Sg; ++k) sup.pair_off[k0 + k] = pair0 + p_off[k];
+    run.lap("  strain read support");
+    return 0;
+}
+// --strain-near-miss, on the same coverage result: Sel_s = the group's rows; Cand_s = every other haplotype of a species of <= 64 haplotypes, of a wider
+// one the unreported haplotypes that have a unique_trio_nodes_fraction, the 256 largest (ties: lower index first) -- the cap bounds the node-mask arena
+// of the walk route at four words a node.  The candidates pantax_hip_near_miss_rank keeps are the ones printed; their `all` comes from one evidence
+// call of the group over them alone
+int group_near_miss(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    constexpr uint64_t WIDE_CAP = 256;
+    auto &nm = sh.rep.nm;
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint64_t> c_off(Sg + 1, 0);
+    std::vector<uint32_t> c_hap;
+    for (uint32_t k = k0; k < k1; ++k) {
+        const uint64_t h0 = sh.hap_off[k], nh = sh.hap_off[k + 1] - h0;
+        const size_t at = c_hap.size();
+        for (uint64_t h = h0; h < h0 + nh; ++h)
+            if (!g.pass[h] && (nh <= 64 || (sh.met[h].has & PANTAX_HIP_HAS_FRACTION))) c_hap.push_back((uint32_t)(h - h0));
+        if (nh > 64) {
+            std::stable_sort(c_hap.begin() + at, c_hap.end(), [&](uint32_t a, uint32_t b) { return sh.met[h0 + a].unique_trio_nodes_fraction > sh.met[h0 + b].unique_trio_nodes_fraction; });
+            if (c_hap.size() - at > WIDE_CAP) c_hap.resize(at + WIDE_CAP);
+        }
+        c_off[k - k0 + 1] = c_hap.size();
+    }
+    const pantax_hip_near_miss_set set{Sg, g.off.data(), g.hap.data(), c_off.data(), c_hap.data()};
+    std::vector<uint64_t> c_out(8 * c_hap.size());
+    PTX_TRY(pantax_hip_strain_near_miss(run.ctx, db, &set, c_out.data(), nm.species.data() + 12 * (size_t)k0));
+    // the printed candidates of every species, in rank order
+    std::vector<uint64_t> p_off(Sg + 1, 0);
+    std::vector<uint32_t> p_hap, rank;
+    const size_t row0 = nm.rows.size();
+    for (uint32_t k = k0; k < k1; ++k) {
+        const uint64_t c0 = c_off[k - k0], n = c_off[k - k0 + 1] - c0;
+        uint32_t kept = 0;
+        rank.assign(n ? n : 1, 0);
+        if (n) PTX_TRY(pantax_hip_near_miss_rank((uint32_t)n, c_hap.data() + c0, c_out.data() + 8 * c0, run.p.rep.nm_top, rank.data(), &kept));
+        for (uint32_t i = 0; i < kept; ++i) {
+            ReportData::NearMissRow r{};
+            r.hap = sh.hap_off[k] + c_hap[c0 + rank[i]];
+            std::copy(c_out.begin() + 8 * (c0 + rank[i]), c_out.begin() + 8 * (c0 + rank[i]) + 8, r.q);
+            nm.rows.push_back(r);
+            p_hap.push_back(c_hap[c0 + rank[i]]);
+        }
+        p_off[k - k0 + 1] = p_hap.size();
+        nm.row_off[k + 1] = nm.rows.size();
+    }
+    const pantax_hip_evidence_set printed{Sg, p_off.data(), p_hap.data()};
+    std::vector<uint64_t> e_hap(8 * p_hap.size()), e_species(12 * (size_t)Sg);
+    PTX_TRY(pantax_hip_strain_evidence(run.ctx, db, &printed, e_hap.data(), e_species.data()));
+    for (size_t i = 0; i < p_hap.size(); ++i) std::copy(e_hap.begin() + 8 * i, e_hap.begin() + 8 * i + 4, nm.rows[row0 + i].q + 8);   // all
+    run.lap("  strain near misses");
+    return 0;
+}
+
+// ---- the files: what every writer is handed, what the writers share, the six writers
+struct Writer {
+    Run &run; const Ingest &in; const Selection &sn; const ShardResult &sh; const std::vector<GenomeRow> &genomes;
+    const std::vector<TrackRow> &rows;                      // the rows of strain_abundance.txt, in its order
+    std::unordered_map<std::string, size_t> first_genome;   // the first genomes_info.txt row of every haplotype (the strain table's left join)
+    const ReportData &rep = sh.rep;
+    const uint32_t Su = (uint32_t)sh.use.size();
+    const std::string &species(uint32_t k) const { return in.ranges[sn.sel[sh.use[k]]].species; }
+    std::string species_head(uint32_t k) const { return species(k) + "\t-\t-"; }
+    std::string strain_head(const TrackRow &r) const { return species(r.k) + '\t' + (r.gr ? r.gr->strain_taxid : "") + '\t' + (r.gr ? r.gr->genome_id : ""); }
+    const GenomeRow *genome_of(uint64_t hap) const {
+        const auto it = first_genome.find(sh.hap_names[hap]);
+        return it != first_genome.end() ? &genomes[it->second] : nullptr;
+    }
+    // the row's entry; a row of the table that no group selected has no `what`
+    int entry_of(const TrackRow &r, const char *what, int64_t *e) const {
+        *e = rep.entry[r.hap];
+        return *e < 0 ? fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no %s", sh.hap_names[r.hap].c_str(), what) : 0;
+    }
+    // open, header, body(f), close and check, lap
+    template <class Body> int file(ReportId id, const char *header, const char *lap, Body body) const {
+        const std::string &path = run.p.rep.path[id];
+        std::ofstream f(path);
+        if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", path.c_str());
+        f << header;
+        PTX_TRY(body(f));
+        f.close();
+        if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", path.c_str());
+        run.lap(lap);
+        return 0;
+    }
+    // the body evidence and depth share: {all, private} of every row of strain_abundance.txt, in its order, then {total, orphan} and, of three classes,
+    // core of every species of the shard in the order it went through the device (the selection's: the species table's).  n u64 a class; put(head, class, q, pc)
+    template <class Put> int node_sums(const char *what, const ReportData::NodeSums &d, size_t n, size_t n_classes, Put put) const {
+        for (const TrackRow &r : rows) {
+            int64_t e; PTX_TRY(entry_of(r, what, &e));
+            const std::string head = strain_head(r), pc = fmt_f64(sh.met[r.hap].second_sol);
+            put(head, "all", d.hap.data() + 2 * n * e, pc);
+            put(head, "private", d.hap.data() + 2 * n * e + n, pc);
+        }
+        for (uint32_t k = 0; k < Su; ++k) {
+            const std::string head = species_head(k);
+            const uint64_t *q = d.species.data() + n_classes * n * k;
+            put(head, "total", q, "-");
+            put(head, "orphan", q + n, "-");
+            if (n_classes < 3) continue;
+            double pc = 0.0;
+            bool any = false;
+            for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
+                if (rep.entry[h] >= 0) { pc += sh.met[h].second_sol; any = true; }
+            if (any) put(head, "core", q + 2 * n, fmt_f64(pc));
+        }
+        return 0;
+    }
+    // --read-strains: one row per GAF record, in the -R report's order (read_id and species_taxid are its columns 1 and 3)
+    int read_strains() const {
+        return file(REP_READ_STRAINS, "", "read strains report", [&](std::ofstream &rf) {
+            for (uint64_t r = 0; r < in.R; ++r) {
+                rf.write(in.mf.data + in.text_begin + in.hr.id_span[r].first, in.hr.id_span[r].second);
+                rf << '\t' << (in.sp_idx[r] >= 0 ? in.ranges[in.sp_idx[r]].species : std::string("U")) << '\t';
+                if (rep.rs.n[r] < 0) rf << "U\tU\t-\t0\n";
+                else if (rep.rs.n[r] == 0 || rep.rs.hap[r] == ~0ull) rf << "U\tU\t0\t0\n";
+                else {
+                    if (const GenomeRow *gr = genome_of(rep.rs.hap[r])) rf << gr->genome_id << '\t' << gr->strain_taxid;
+                    else rf << '\t';
+                    rf << '\t' << rep.rs.n[r] << '\t' << fmt_f64(rep.rs.post[r]) << '\n';
+                }
+            }
+            return 0;
+        });
+    }
+    // --strain-coverage: the windows of every row of strain_abundance.txt, in its order
+    int cov_track() const {
+        const auto &ct = rep.ct;
+        const uint64_t W = run.p.rep.ct_window;
+        return file(REP_COVERAGE, "species_taxid\tstrain_taxid\tgenome_ID\tstart\tend\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\n", "strain coverage report", [&](std::ofstream &f) {
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "coverage track", &e));
+                const std::string head = strain_head(r);
+                const uint64_t w0 = ct.win_off[e], w1 = ct.win_off[e + 1];
+                uint64_t G = 0;
+                for (uint64_t i = w0; i < w1; ++i) G += ct.len[i];
+                for (uint64_t i = w0; i < w1; ++i) {
+                    if (ct.len[i] == 0) continue;   // no node starts here: a longer node runs through
+                    const uint64_t start = (i - w0) * W, end = i + 1 == w1 ? G : start + W;   // (only the last window can be cut short: start + W <= G before it)
+                    f << head << '\t' << start << '\t' << end << '\t' << ct.n_nodes[i] << '\t' << ct.len[i] << '\t' << ct.covered[i] << '\t' << ct.bases[i] << '\t'
+                      << fmt_f64((double)ct.bases[i] / (double)ct.len[i]) << '\t' << fmt_f64((double)ct.covered[i] / (double)ct.len[i]) << '\n';
+                }
+            }
+            return 0;
+        });
+    }
+    // --strain-evidence: the sums {n_nodes, len, covered, bases} of every class, with depth and breadth
+    int evidence() const {
+        return file(REP_EVIDENCE, "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\tpredicted_coverage\n", "strain evidence report", [&](std::ofstream &f) {
+            return node_sums("node evidence", rep.ev, EVIDENCE_N, 3, [&f](const std::string &head, const char *cls, const uint64_t *q, const std::string &pc) {
+                f << head << '\t' << cls << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << q[3] << '\t';
+                if (q[1]) f << fmt_f64((double)q[3] / (double)q[1]) << '\t' << fmt_f64((double)q[2] / (double)q[1]);
+                else f << "-\t-";
+                f << '\t' << pc << '\n';
+            });
+        });
+    }
+    // --strain-read-support: {compatible, unique, assigned} of every row of strain_abundance.txt, in its order; {counted, unexplained, ambiguous, uninformative}
+    // of every species of the shard in the order it went through the device (a species without rows: counted only); the shared reads of every pair of rows
+    int read_support() const {
+        const auto &sup = rep.sup;
+        return file(REP_READ_SUPPORT, "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_reads\tn_steps\tspan\tfraction\tother_strain_taxid\n", "strain read support report", [&](std::ofstream &f) {
+            const auto frac = [](uint64_t n, uint64_t of) { return of ? fmt_f64((double)n / (double)of) : std::string("-"); };
+            const auto put = [&](const std::string &head, const char *cls, const uint64_t *q, uint64_t of) {   // q = {n_reads, n_steps, span}
+                f << head << '\t' << cls << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << frac(q[0], of) << "\t-\n";
+            };
+            const char *const of_row[3] = {"compatible", "unique", "assigned"}, *const of_species[4] = {"counted", "unexplained", "ambiguous", "uninformative"};
+            std::vector<const TrackRow *> row_of(sup.hap.size() / 9, nullptr);   // entry -> its first row of the table
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "read support", &e));
+                if (!row_of[e]) row_of[e] = &r;
+                const std::string head = strain_head(r);
+                for (int c = 0; c < 3; ++c) put(head, of_row[c], sup.hap.data() + 9 * e + 3 * c, sup.species[12 * (size_t)r.k]);
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const std::string head = species_head(k);
+                const uint64_t *q = sup.species.data() + 12 * (size_t)k;
+                for (int c = 0; c < (sup.K[k] ? 4 : 1); ++c) put(head, of_species[c], q + 3 * c, q[0]);   // a species without rows: counted only
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const uint64_t K = sup.K[k];
+                if (K < 2 || K > 64) continue;
+                int64_t e0 = -1;                                                        // the species' entries are consecutive, in ascending haplotype index
+                for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1] && e0 < 0; ++h) e0 = rep.entry[h];
+                const uint64_t *pm = sup.pair.data() + sup.pair_off[k];
+                for (uint64_t a = 0; a < K; ++a)
+                    for (uint64_t b = a + 1; b < K; ++b) {
+                        const uint64_t n = pm[a * K + b];
+                        if (!n || e0 < 0 || !row_of[e0 + a] || !row_of[e0 + b]) continue;
+                        const TrackRow &ra = *row_of[e0 + a], &rb = *row_of[e0 + b];
+                        f << strain_head(ra) << "\tshared\t" << n << "\t-\t-\t" << frac(n, std::min(pm[a * K + a], pm[b * K + b])) << '\t'
+                          << (rb.gr ? rb.gr->strain_taxid : std::string()) << '\n';
+                    }
+            }
+            return 0;
+        });
+    }
+    // --strain-depth: per histogram of every class its node count, its length, the length at depth 0 and the length-weighted quantiles
+    int depth() const {
+        return file(REP_DEPTH, "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_nodes\tlen\tlen_zero\tq05\tq25\tq50\tq75\tq95\tq50_hi\tpredicted_coverage\n", "strain depth report", [&](std::ofstream &f) {
+            return node_sums("depth histogram", rep.dp, DEPTH_N, 2, [&f](const std::string &head, const char *cls, const uint64_t *hist, const std::string &pc) {
+                uint64_t n = 0, len = 0;
+                for (uint32_t b = 0; b < PANTAX_HIP_DEPTH_BINS; ++b) { n += hist[2 * b]; len += hist[2 * b + 1]; }
+                f << head << '\t' << cls << '\t' << n << '\t' << len << '\t' << hist[1];
+                uint64_t hi50 = 0;
+                for (const uint32_t pm : {50u, 250u, 500u, 750u, 950u}) {
+                    uint32_t bin = 0;
+                    uint64_t lo = 0, hi = 0;
+                    if (pantax_hip_depth_quantile(hist, pm, &bin) != 0) { f << "\t-"; continue; }   // len = 0
+                    pantax_hip_depth_bin_range(bin, &lo, &hi);
+                    if (pm == 500u) hi50 = hi;
+                    f << '\t' << lo;
+                }
+                if (len) f << '\t' << hi50; else f << "\t-";
+                f << '\t' << pc << '\n';
+            });
+        });
+    }
+    // --strain-near-miss: per species of the shard, in the order it went through the device, the candidates group_near_miss kept, in rank order, classes novel,
+    // exclusive, all each; then {orphan, claimed, contested} of every species.  strain_taxid / genome_ID: the first genomes_info.txt row of the haplotype
+    int near_miss() const {
+        const auto &nm = rep.nm;
+        return file(REP_NEAR_MISS, "species_taxid\tstrain_taxid\tgenome_ID\trank\tclass\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\tshare\tstage\tunique_trio_nodes_fraction\tfrequencies_mean\tfirst_sol\tsecond_sol\n",
+                    "strain near-miss report", [&](std::ofstream &f) {
+            const char *const cand[3] = {"novel", "exclusive", "all"}, *const spec[3] = {"orphan", "claimed", "contested"};
+            for (uint32_t k = 0; k < Su; ++k)
+                for (uint64_t i = nm.row_off[k]; i < nm.row_off[k + 1]; ++i) {
+                    const ReportData::NearMissRow &r = nm.rows[i];
+                    for (int c = 0; c < 3; ++c)   // the share of the orphan bases: not of `all`
+                        f << near_miss_row_text(species(k), genome_of(r.hap), &sh.met[r.hap], (uint32_t)(i - nm.row_off[k]) + 1, cand[c], r.q + 4 * c, c < 2, nm.species[12 * (size_t)k + 3]) << '\n';
+                }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const uint64_t *q = nm.species.data() + 12 * (size_t)k;
+                for (int c = 0; c < 3; ++c) f << near_miss_row_text(species(k), nullptr, nullptr, 0, spec[c], q + 4 * c, true, q[3]) << '\n';
+            }
+            return 0;
+        });
+    }
+};
+}  // namespace
+
+namespace reports {
+void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportData &rep) {
+    if (plan.any_run()) rep.entry.assign(H, -1);
+    if (plan.run[REP_READ_STRAINS]) { rep.rs.hap.assign(R, ~0ull); rep.rs.n.assign(R, -1); rep.rs.post.assign(R, 0.0); }
+    if (plan.run[REP_EVIDENCE]) rep.ev.species.assign(3 * EVIDENCE_N * (size_t)Su, 0);
+    if (plan.run[REP_READ_SUPPORT]) { rep.sup.species.assign(12 * (size_t)Su, 0); rep.sup.pair_off.assign(Su, 0); rep.sup.K.assign(Su, 0); }
+    if (plan.run[REP_DEPTH]) rep.dp.species.assign(2 * DEPTH_N * (size_t)Su, 0);
+    if (plan.run[REP_NEAR_MISS]) { rep.nm.species.assign(12 * (size_t)Su, 0); rep.nm.row_off.assign(Su + 1, 0); }
+}
+int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
+    const ReportPlan &plan = run.p.rep;
+    if (!plan.any_run()) return 0;
+    GroupSel g;
+    PTX_TRY(group_select(run, k0, k1, sh, g));
+    if (plan.run[REP_READ_STRAINS]) PTX_TRY(group_read_strains(run, in, db, k0, k1, g, sh));
+    if (plan.run[REP_COVERAGE]) PTX_TRY(group_cov_track(run, db, k0, k1, g, sh));
+    if (plan.run[REP_EVIDENCE]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_evidence, 2 * EVIDENCE_N, 3 * EVIDENCE_N, sh.rep.ev, "  strain evidence"));
+    if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
+    if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
+    if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh));
+    return 0;
+}
+int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, const std::vector<GenomeRow> &genomes, std::vector<TrackRow> &rows) {
+    const ReportPlan &plan = run.p.rep;
+    if (!plan.any_run()) return 0;
+    std::stable_sort(rows.begin(), rows.end(), [](const TrackRow &a, const TrackRow &b) { return a.key > b.key; });   // the table's own sort on the same keys
+    Writer w{run, in, sn, sh, genomes, rows, {}};
+    for (size_t i = genomes.size(); i-- > 0;) w.first_genome[genomes[i].hap_id] = i;
+    if (plan.run[REP_READ_STRAINS]) PTX_TRY(w.read_strains());
+    if (plan.run[REP_COVERAGE]) PTX_TRY(w.cov_track());
+    if (plan.run[REP_EVIDENCE]) PTX_TRY(w.evidence());
+    if (plan.run[REP_READ_SUPPORT]) PTX_TRY(w.read_support());
+    if (plan.run[REP_DEPTH]) PTX_TRY(w.depth());
+    if (plan.run[REP_NEAR_MISS]) PTX_TRY(w.near_miss());
+    return 0;
+}
+}  // namespace reports
+}  // namespace ptx

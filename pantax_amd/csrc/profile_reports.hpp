@@ -1,0 +1,47 @@
+// profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
+// while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a row
+// of REPORTS, a sub-struct here, and a line in each of begin / collect_group / write (profile_reports.cpp).
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+#include "report_plan.hpp"
+
+namespace ptx {
+struct Run; struct Ingest; struct Selection; struct ShardResult; struct GenomeRow;
+
+// A row of strain_abundance.txt as the row-following reports see it: its sort key, its species (into ShardResult::use), its haplotype (into hap_names), its
+// joined genome or null
+struct TrackRow { double key; uint32_t k; uint64_t hap; const GenomeRow *gr; };
+// Filled group after group.  The haplotypes among the rows of strain_abundance.txt are numbered in the order the groups select them: entry[h] = the number
+// of selected haplotypes before h over all groups so far, or -1 ([hap_names]).  Per-entry arrays of every report are indexed by it, per-species arrays by
+// the species' position k in ShardResult::use
+struct ReportData {
+    std::vector<int64_t> entry;
+    uint64_t n_entries = 0;
+    // --read-strains, file order: global haplotype index (into hap_names) of the assigned strain or ~0, |C(r)| or -1 (not counted), posterior
+    struct { std::vector<uint64_t> hap; std::vector<int32_t> n; std::vector<double> post; } rs;
+    // --strain-coverage: entry e owns the windows [win_off[e], win_off[e + 1]) of the four arrays
+    struct { std::vector<uint64_t> win_off{0}, len, covered, bases; std::vector<uint32_t> n_nodes; } ct;
+    // sums over nodes, n u64 a class: hap[2n e ..) = {all, private}; species[2n k ..) = {total, orphan} or species[3n k ..) = {total, orphan, core}
+    struct NodeSums { std::vector<uint64_t> hap, species; };
+    NodeSums ev;   // --strain-evidence: n = 4 {n_nodes, len, covered, bases}, three species classes
+    NodeSums dp;   // --strain-depth: n = 192, a depth histogram of [96]{n_nodes, len}, two species classes
+    // --strain-read-support: hap[9e ..) = {compatible, unique, assigned}; species[12k ..) = {counted, unexplained, ambiguous, uninformative}; a species of
+    // K[k] = 1..64 rows owns the K x K block of shared reads pair[pair_off[k] ..) over its entries in ascending order
+    struct { std::vector<uint64_t> hap, species, pair, pair_off; std::vector<uint32_t> K; } sup;
+    // --strain-near-miss: species[12k ..) = {orphan, claimed, contested}; the printed candidates rows[row_off[k] .. row_off[k + 1]) in rank order: the
+    // haplotype ([hap_names]) and q = {novel, exclusive, all} x {n_nodes, len, covered, bases}
+    struct NearMissRow { uint64_t hap; uint64_t q[12]; };
+    struct { std::vector<uint64_t> species, row_off; std::vector<NearMissRow> rows; } nm;
+};
+
+namespace reports {
+// sizes what the running reports index by read (R), haplotype (H) and species (Su) of the shard
+void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportData &rep);
+// the species [k0, k1) of the db that has just gone through its strain step: the group's rows of the strain table selected once, then each running report
+int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh);
+// behind the tables: the files of the running reports; `rows` come from strain_tables and are put into the table's order here
+int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, const std::vector<GenomeRow> &genomes, std::vector<TrackRow> &rows);
+}  // namespace reports
+}  // namespace ptx

@@ -1,5 +1,6 @@
 // profile_shard.cpp -- run_shard (profile_run.hpp): a6 - a14 of the file seam for this rank's selected species.  Where every graph comes from
-// (headers only), the cut into groups, the loader thread, the device sequence per group, read strains, the strain coverage track, the node evidence, the read support, the depth distribution and the near misses per group, image write-back.
+// (headers only), the cut into groups, the loader thread, the device sequence per group with the per-strain reports' turn behind the strain step
+// (reports::collect_group, profile_reports.cpp), image write-back.
 #include <algorithm>
 #include <chrono>
 #include <memory>
@@ -108,182 +109,9 @@ int start_load(pantax_hip_ctx *ctx, const int64_t *g_rs, const int64_t *g_re, co
     });
     return 0;
 }
-// this group's rows of strain_abundance.txt as bits over the shard's haplotypes: the a15 filter is row-local, so the group decides it in its own turn
-int group_pass_bits(Run &run, uint32_t k0, uint32_t k1, const ShardResult &sh, std::vector<uint8_t> &pass_g) {
-    const uint32_t Sg = k1 - k0;
-    std::vector<uint8_t> rep_g(Sg);
-    for (uint32_t k = k0; k < k1; ++k) rep_g[k - k0] = (sh.info[k].status1 == 0 && sh.info[k].status2 == 0) ? 1 : 0;
-    pass_g.assign(sh.hap_names.size() ? sh.hap_names.size() : 1, 0);
-    return pantax_hip_abundance_filter(Sg, sh.hap_off.data() + k0, sh.met.data(), rep_g.data(), run.cfg->single_cov_diff, run.cfg->min_cov, pass_g.data(),
-                                       nullptr, nullptr, nullptr, nullptr);
-}
-// --read-strains for the species [k0, k1) of the db that has just gone through its strain step; the candidates are the group's rows (pass_g)
-int group_read_strains(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
-    const uint32_t Sg = k1 - k0;
-    const uint64_t R = in.R;
-    std::vector<uint64_t> c_off(Sg + 1, 0);
-    std::vector<uint32_t> c_hap;
-    std::vector<double> c_w;
-    for (uint32_t k = k0; k < k1; ++k) {
-        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
-            if (pass_g[h]) { c_hap.push_back((uint32_t)(h - sh.hap_off[k])); c_w.push_back(sh.met[h].second_sol); }
-        c_off[k - k0 + 1] = c_hap.size();
-    }
-    const pantax_hip_read_strain_set cs{Sg, c_off.data(), c_hap.data(), c_w.data()};
-    constexpr int32_t UNTOUCHED = -3;   // entries of reads outside this group's species keep it
-    std::vector<uint32_t> t_hap(R, 0u);
-    std::vector<int32_t> t_n(R, UNTOUCHED), g_sp(R, -1);
-    std::vector<double> t_post(R, 0.0);
-    PTX_TRY(pantax_hip_read_strains(run.ctx, db, in.reads.rd, &cs, t_hap.data(), t_n.data(), t_post.data()));
-    if (R) {   // the group-local species of every read (the slot records of this group's binning pass)
-        PTX_TRY(species_ensure(run.ctx, in.reads.rd));
-        PTX_TRY(download(run.ctx, g_sp.data(), in.reads.rd->d_species.p, R));
-        PTX_HIP(run.ctx, hipStreamSynchronize(run.ctx->stream));
-    }
-    for (uint64_t r = 0; r < R; ++r) {
-        if (t_n[r] == UNTOUCHED) continue;
-        sh.rs_n[r] = t_n[r]; sh.rs_post[r] = t_post[r];
-        sh.rs_hap[r] = t_n[r] > 0 && g_sp[r] >= 0 ? sh.hap_off[k0 + (uint32_t)g_sp[r]] + t_hap[r] : ~0ull;
-    }
-    run.lap("  read strains");
-    return 0;
-}
-// --strain-coverage for the same species, while the coverage result of the group is still on the device: the windows of the group's rows (pass_g)
-int group_cov_track(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
-    const uint32_t Sg = k1 - k0;
-    std::vector<uint64_t> s_off(Sg + 1, 0);
-    std::vector<uint32_t> s_hap;
-    const size_t entry0 = sh.ct_win_off.size() - 1;   // entries of the groups before
-    for (uint32_t k = k0; k < k1; ++k) {
-        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
-            if (pass_g[h]) { sh.ct_entry[h] = (int64_t)(entry0 + s_hap.size()); s_hap.push_back((uint32_t)(h - sh.hap_off[k])); }
-        s_off[k - k0 + 1] = s_hap.size();
-    }
-    const pantax_hip_cov_track_set set{Sg, s_off.data(), s_hap.data(), run.p.ct_window};
-    std::vector<uint64_t> w_off(s_hap.size() + 1, 0);
-    const int rc_size = pantax_hip_strain_cov_track(run.ctx, db, &set, w_off.data(), 0, nullptr, nullptr, nullptr, nullptr);   // sizes: E_LIMIT unless there is no window
-    if (rc_size != 0 && rc_size != PANTAX_HIP_E_LIMIT) return rc_size;
-    const uint64_t n = w_off[s_hap.size()], at = sh.ct_len.size();
-    sh.ct_n_nodes.resize(at + n); sh.ct_len.resize(at + n); sh.ct_covered.resize(at + n); sh.ct_bases.resize(at + n);
-    if (n) PTX_TRY(pantax_hip_strain_cov_track(run.ctx, db, &set, w_off.data(), n, sh.ct_n_nodes.data() + at, sh.ct_len.data() + at, sh.ct_covered.data() + at, sh.ct_bases.data() + at));
-    for (size_t e = 0; e < s_hap.size(); ++e) sh.ct_win_off.push_back(at + w_off[e + 1]);
-    run.lap("  strain coverage track");
-    return 0;
-}
-// --strain-evidence for the same species and on the same coverage result: Sel_s = the group's rows (pass_g)
-int group_evidence(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
-    const uint32_t Sg = k1 - k0;
-    std::vector<uint64_t> s_off(Sg + 1, 0);
-    std::vector<uint32_t> s_hap;
-    const size_t entry0 = sh.ev_hap.size() / 8;   // entries of the groups before
-    for (uint32_t k = k0; k < k1; ++k) {
-        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
-            if (pass_g[h]) { sh.ev_entry[h] = (int64_t)(entry0 + s_hap.size()); s_hap.push_back((uint32_t)(h - sh.hap_off[k])); }
-        s_off[k - k0 + 1] = s_hap.size();
-    }
-    const pantax_hip_evidence_set set{Sg, s_off.data(), s_hap.data()};
-    sh.ev_hap.resize(8 * (entry0 + s_hap.size()));
-    PTX_TRY(pantax_hip_strain_evidence(run.ctx, db, &set, sh.ev_hap.data() + 8 * entry0, sh.ev_species.data() + 12 * (size_t)k0));
-    run.lap("  strain evidence");
-    return 0;
-}
-// --strain-read-support for the same species: the candidates and weights of group_read_strains, summed on the device (nothing per read comes back)
-int group_read_support(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
-    const uint32_t Sg = k1 - k0;
-    std::vector<uint64_t> c_off(Sg + 1, 0), p_off(Sg + 1, 0);
-    std::vector<uint32_t> c_hap;
-    std::vector<double> c_w;
-    const size_t entry0 = sh.sup_hap.size() / 9;   // entries of the groups before
-    for (uint32_t k = k0; k < k1; ++k) {
-        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
-            if (pass_g[h]) { sh.sup_entry[h] = (int64_t)(entry0 + c_hap.size()); c_hap.push_back((uint32_t)(h - sh.hap_off[k])); c_w.push_back(sh.met[h].second_sol); }
-        c_off[k - k0 + 1] = c_hap.size();
-    }
-    const pantax_hip_read_strain_set cs{Sg, c_off.data(), c_hap.data(), c_w.data()};
-    sh.sup_hap.resize(9 * (entry0 + c_hap.size()));
-    uint64_t n_pair = 0;
-    for (uint32_t k = 0; k < Sg; ++k) { const uint64_t K = c_off[k + 1] - c_off[k]; sh.sup_K[k0 + k] = (uint32_t)K; n_pair += K <= 64 ? K * K : 0; }
-    const size_t pair0 = sh.sup_pair.size();
-    sh.sup_pair.resize(pair0 + n_pair);
-    PTX_TRY(pantax_hip_strain_read_support(run.ctx, db, in.reads.rd, &cs, sh.sup_hap.data() + 9 * entry0, sh.sup_species.data() + 12 * (size_t)k0, p_off.data(), n_pair,
-                                           sh.sup_pair.data() + pair0));
-    for (uint32_t k = 0; k < Sg; ++k) sh.sup_pair_off[k0 + k] = pair0 + p_off[k];
-    run.lap("  strain read support");
-    return 0;
-}
-// --strain-depth for the same species and on the same coverage result: Sel_s = the group's rows (pass_g)
-int group_depth(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
-    constexpr size_t PER = 4 * PANTAX_HIP_DEPTH_BINS;   // u64 per entry and per species: two histograms of [96]{n_nodes, len}
-    const uint32_t Sg = k1 - k0;
-    std::vector<uint64_t> s_off(Sg + 1, 0);
-    std::vector<uint32_t> s_hap;
-    const size_t entry0 = sh.dp_hap.size() / PER;   // entries of the groups before
-    for (uint32_t k = k0; k < k1; ++k) {
-        for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
-            if (pass_g[h]) { sh.dp_entry[h] = (int64_t)(entry0 + s_hap.size()); s_hap.push_back((uint32_t)(h - sh.hap_off[k])); }
-        s_off[k - k0 + 1] = s_hap.size();
-    }
-    const pantax_hip_evidence_set set{Sg, s_off.data(), s_hap.data()};
-    sh.dp_hap.resize(PER * (entry0 + s_hap.size()));
-    PTX_TRY(pantax_hip_strain_depth(run.ctx, db, &set, sh.dp_hap.data() + PER * entry0, sh.dp_species.data() + PER * (size_t)k0));
-    run.lap("  strain depth");
-    return 0;
-}
-// --strain-near-miss for the same species and on the same coverage result: Sel_s = the group's rows (pass_g); Cand_s = every other haplotype of a species of
-// <= 64 haplotypes, of a wider one the unreported haplotypes that have a unique_trio_nodes_fraction, the 256 largest (ties: lower index first) -- the cap
-// bounds the node-mask arena of the walk route at four words a node.  The candidates pantax_hip_near_miss_rank keeps are the ones printed; their `all`
-// comes from one evidence call of the group over them alone
-int group_near_miss(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const std::vector<uint8_t> &pass_g, ShardResult &sh) {
-    constexpr uint64_t WIDE_CAP = 256;
-    const uint32_t Sg = k1 - k0;
-    std::vector<uint64_t> s_off(Sg + 1, 0), c_off(Sg + 1, 0);
-    std::vector<uint32_t> s_hap, c_hap;
-    for (uint32_t k = k0; k < k1; ++k) {
-        const uint64_t h0 = sh.hap_off[k], nh = sh.hap_off[k + 1] - h0;
-        const size_t at = c_hap.size();
-        for (uint64_t h = h0; h < h0 + nh; ++h) {
-            if (pass_g[h]) s_hap.push_back((uint32_t)(h - h0));
-            else if (nh <= 64 || (sh.met[h].has & PANTAX_HIP_HAS_FRACTION)) c_hap.push_back((uint32_t)(h - h0));
-        }
-        if (nh > 64) {
-            std::stable_sort(c_hap.begin() + at, c_hap.end(), [&](uint32_t a, uint32_t b) { return sh.met[h0 + a].unique_trio_nodes_fraction > sh.met[h0 + b].unique_trio_nodes_fraction; });
-            if (c_hap.size() - at > WIDE_CAP) c_hap.resize(at + WIDE_CAP);
-        }
-        s_off[k - k0 + 1] = s_hap.size(); c_off[k - k0 + 1] = c_hap.size();
-    }
-    const pantax_hip_near_miss_set set{Sg, s_off.data(), s_hap.data(), c_off.data(), c_hap.data()};
-    std::vector<uint64_t> c_out(8 * c_hap.size());
-    PTX_TRY(pantax_hip_strain_near_miss(run.ctx, db, &set, c_out.data(), sh.nm_species.data() + 12 * (size_t)k0));
-    // the printed candidates of every species, in rank order
-    std::vector<uint64_t> p_off(Sg + 1, 0);
-    std::vector<uint32_t> p_hap, rank;
-    const size_t row0 = sh.nm_rows.size();
-    for (uint32_t k = k0; k < k1; ++k) {
-        const uint64_t c0 = c_off[k - k0], n = c_off[k - k0 + 1] - c0;
-        uint32_t kept = 0;
-        rank.assign(n ? n : 1, 0);
-        if (n) PTX_TRY(pantax_hip_near_miss_rank((uint32_t)n, c_hap.data() + c0, c_out.data() + 8 * c0, run.p.nm_top, rank.data(), &kept));
-        for (uint32_t i = 0; i < kept; ++i) {
-            ShardResult::NearMissRow r{};
-            r.hap = sh.hap_off[k] + c_hap[c0 + rank[i]];
-            std::copy(c_out.begin() + 8 * (c0 + rank[i]), c_out.begin() + 8 * (c0 + rank[i]) + 8, r.q);
-            sh.nm_rows.push_back(r);
-            p_hap.push_back(c_hap[c0 + rank[i]]);
-        }
-        p_off[k - k0 + 1] = p_hap.size();
-        sh.nm_row_off[k + 1] = sh.nm_rows.size();
-    }
-    const pantax_hip_evidence_set printed{Sg, p_off.data(), p_hap.data()};
-    std::vector<uint64_t> e_hap(8 * p_hap.size()), e_species(12 * (size_t)Sg);
-    PTX_TRY(pantax_hip_strain_evidence(run.ctx, db, &printed, e_hap.data(), e_species.data()));
-    for (size_t i = 0; i < p_hap.size(); ++i) std::copy(e_hap.begin() + 8 * i, e_hap.begin() + 8 * i + 4, sh.nm_rows[row0 + i].q + 8);   // all
-    run.lap("  strain near misses");
-    return 0;
-}
 // one pass: sources, parts, groups; per group the loader hand-over, then binning against the selected ranges, index, coverage, strain step
 int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, ShardResult &sh) {
     const uint32_t Ss = (uint32_t)sn.sel.size();
-    if (run.p.rs_run) { sh.rs_hap.assign(in.R, ~0ull); sh.rs_n.assign(in.R, -1); sh.rs_post.assign(in.R, 0.0); }
     std::vector<HostGraph> graphs(Ss);
     std::vector<uint8_t> loaded(Ss, 1);
     std::vector<Source> src(Ss);
@@ -293,7 +121,6 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
     const uint32_t Su = (uint32_t)sh.use.size();
     sh.info.assign(Su, pantax_hip_solve_info{});
     sh.hap_off.assign(Su + 1, 0);
-    if (!Su) return 0;
     // one part per used species (where its two arrays lie), its range, its file, its coverage; the haplotype names of the shard in species order
     std::vector<int64_t> g_rs(Su), g_re(Su); std::vector<double> cov(Su);
     std::vector<GraphPart> parts(Su); std::vector<std::string> files(Su);
@@ -326,14 +153,8 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
         sh.hap_off[k + 1] = sh.hap_names.size();
     }
     sh.met.resize(sh.hap_names.size());
-    if (run.p.ct_run) sh.ct_entry.assign(sh.hap_names.size(), -1);
-    if (run.p.sup_run) {
-        sh.sup_entry.assign(sh.hap_names.size(), -1); sh.sup_species.assign(12 * (size_t)Su, 0);
-        sh.sup_pair_off.assign(Su, 0); sh.sup_K.assign(Su, 0);
-    }
-    if (run.p.ev_run) { sh.ev_entry.assign(sh.hap_names.size(), -1); sh.ev_species.assign(12 * (size_t)Su, 0); }
-    if (run.p.dp_run) { sh.dp_entry.assign(sh.hap_names.size(), -1); sh.dp_species.assign(4 * PANTAX_HIP_DEPTH_BINS * (size_t)Su, 0); }
-    if (run.p.nm_run) { sh.nm_species.assign(12 * (size_t)Su, 0); sh.nm_row_off.assign(Su + 1, 0); }
+    reports::begin(run.p.rep, Su, sh.hap_names.size(), in.R, sh.rep);
+    if (!Su) return 0;
     const std::vector<Group> groups = make_groups(run.ctx, parts);
     const bool piped = groups.size() > 1;
     if (piped && !run.ctx->stream_up) PTX_HIP(run.ctx, hipStreamCreateWithFlags(&run.ctx->stream_up, hipStreamNonBlocking));
@@ -378,16 +199,7 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
                                     run.cfg->sample_test ? 500 : run.cfg->sample_nodes, run.cfg->solver_semantics};
         PTX_TRY(pantax_hip_strain_profile(run.ctx, db, &sc, nullptr, cov.data() + k0, sh.met.data() + sh.hap_off[k0], sh.info.data() + k0));
         run.lap("strain step");
-        if (run.p.rs_run || run.p.ct_run || run.p.ev_run || run.p.sup_run || run.p.dp_run || run.p.nm_run) {   // the six reports on the group's rows of the strain table, decided once
-            std::vector<uint8_t> pass_g;
-            PTX_TRY(group_pass_bits(run, k0, k1, sh, pass_g));
-            if (run.p.rs_run) PTX_TRY(group_read_strains(run, in, db, k0, k1, pass_g, sh));
-            if (run.p.ct_run) PTX_TRY(group_cov_track(run, db, k0, k1, pass_g, sh));
-            if (run.p.ev_run) PTX_TRY(group_evidence(run, db, k0, k1, pass_g, sh));
-            if (run.p.sup_run) PTX_TRY(group_read_support(run, in, db, k0, k1, pass_g, sh));
-            if (run.p.dp_run) PTX_TRY(group_depth(run, db, k0, k1, pass_g, sh));
-            if (run.p.nm_run) PTX_TRY(group_near_miss(run, db, k0, k1, pass_g, sh));
-        }
+        PTX_TRY(reports::collect_group(run, in, db, k0, k1, sh));   // the per-strain reports take what they need while the group is resident
         if (run.cfg->image_cache == 2) {   // leave images behind for the next run
             for (uint32_t k = k0; k < k1; ++k)
                 if (src[sh.use[k]].kind != 1) {

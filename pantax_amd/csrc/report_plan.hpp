@@ -1,0 +1,42 @@
+// report_plan.hpp -- the per-strain reports of the file seam (pantax_hip_profile) as one table: which config field switches a report on, what its refusal
+// calls it, whether it follows the rows of strain_abundance.txt.  plan_reports / resume_reports decide from plain values which reports this call wants
+// and runs; nothing else in the seam spells a report's field name or repeats the rule.  pantax_hip.h and standard headers only:
+// tests/native/report_plan_check.cpp compiles this with the host compiler alone.
+#pragma once
+#include <cstdint>
+#include <string>
+#include "../../include/pantax_hip.h"
+
+namespace ptx {
+
+// in the order of the device calls within a group and of the files written
+enum ReportId { REP_READ_STRAINS, REP_COVERAGE, REP_EVIDENCE, REP_READ_SUPPORT, REP_DEPTH, REP_NEAR_MISS, N_REPORTS };
+struct ReportRow {
+    const char *pantax_hip_profiling_config::*field;   // the report's file: null, "" or "None" = off
+    const char *name;                                  // the field's name ...
+    const char *what;                                  // ... and the report's noun phrase, both for the refusal
+    bool rows;                                         // follows the rows of the strain table (a TrackRow consumer)
+};
+constexpr ReportRow REPORTS[N_REPORTS] = {
+    {&pantax_hip_profiling_config::read_strain_file, "read_strain_file", "per-read strain report", false},
+    {&pantax_hip_profiling_config::strain_coverage_file, "strain_coverage_file", "per-strain coverage track", true},
+    {&pantax_hip_profiling_config::strain_evidence_file, "strain_evidence_file", "per-strain node evidence report", true},
+    {&pantax_hip_profiling_config::strain_read_support_file, "strain_read_support_file", "per-strain read support report", true},
+    {&pantax_hip_profiling_config::strain_depth_file, "strain_depth_file", "per-strain depth distribution report", true},
+    {&pantax_hip_profiling_config::strain_near_miss_file, "strain_near_miss_file", "unreported-strain near-miss report", false},
+};
+struct ReportPlan {
+    std::string path[N_REPORTS];
+    bool want[N_REPORTS] = {}, run[N_REPORTS] = {};   // want: the caller named a file; run: this call runs a strain step and writes it
+    uint64_t ct_window = 10000;                       // window of the coverage track in bases
+    uint32_t nm_top = 5;                              // candidates the near-miss report prints per species
+    bool any_run() const { for (const bool r : run) if (r) return true; return false; }
+    bool rows_run() const { for (int i = 0; i < N_REPORTS; ++i) if (run[i] && REPORTS[i].rows) return true; return false; }
+};
+// cfg -> path, want and the two parameters.  A wanted report needs one rank and an unsharded ingest: its rows live on the rank that owns the species, the
+// rows of the GAF on the rank of their byte range -- not joined here.  false: the first failing check in table order, its message in err (E_INVALID)
+bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, ReportPlan &plan, std::string &err);
+// run[] from want[]: a wanted report is written by a call that runs a strain step
+void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_done);
+
+}  // namespace ptx

@@ -73,6 +73,40 @@ def gaf_quirks_text():
             b"r9\t90\t0\t90\t+\t>8>9\t200\t0\t90")
 
 
+def seam_world(tmp_path_factory, name, *set_args, **set_kw):
+    """The world of a file-seam test, for a module-scoped fixture to `yield from`: synthdata.make_set(*set_args, **set_kw) written out as a DB directory
+    and a GAF under a temporary directory `name`, and an engine that is closed behind the module -> (sset, root, db, gaf, engine)"""
+    import synthdata as synth
+    from pantax_amd.engine import Engine
+    sset = synth.make_set(*set_args, **set_kw)
+    root = tmp_path_factory.mktemp(name)
+    db = root / "db"
+    db.mkdir()
+    synth.write_db(sset, str(db))
+    gaf = root / "gfa_mapped.gaf"
+    synth.write_gaf(sset.reads, str(gaf))
+    e = Engine(0)
+    yield sset, root, db, gaf, e
+    e.close()
+
+
+def seam_profile(eng, db, wd, gaf, **kw):
+    """eng.profile into the work directory `wd` (created), run from inside it"""
+    wd.mkdir(exist_ok=True)
+    cwd = os.getcwd()
+    os.chdir(str(wd))                                    # ori_strain_abundance.txt goes to the current directory
+    try:
+        eng.profile(str(db), str(wd), str(gaf), **kw)
+    finally:
+        os.chdir(cwd)
+
+
+def seam_lines(path):
+    """a TSV file as a list of rows of cells"""
+    with open(path) as f:
+        return [l.rstrip("\n").split("\t") for l in f]
+
+
 def select_reads(reads, sel):
     """Sub-select reads `sel` (indices) from a PackedReads -> (step_off, node_id, pstart, pend)."""
     so = reads.step_off.astype(np.int64)

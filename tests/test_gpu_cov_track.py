@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests.conftest import ROOT
+from tests.helpers import seam_lines as _lines, seam_profile as _profile, seam_world
 from tests.cov_track_ref import track, walk_windows
 
 pytestmark = pytest.mark.gpu
@@ -193,33 +194,7 @@ def test_cov_track_sizing_and_state(eng, narrow):
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    import synthdata as synth
-    from pantax_amd.engine import Engine
-    sset = synth.make_set(32, 4, 5, 30000, 30000, present_frac=0.4, single_strain_every=4, with_ids=True)
-    root = tmp_path_factory.mktemp("pantax_ct")
-    db = root / "db"
-    db.mkdir()
-    synth.write_db(sset, str(db))
-    gaf = root / "gfa_mapped.gaf"
-    synth.write_gaf(sset.reads, str(gaf))
-    e = Engine(0)
-    yield sset, root, db, gaf, e
-    e.close()
-
-
-def _profile(eng, db, wd, gaf, **kw):
-    wd.mkdir(exist_ok=True)
-    cwd = os.getcwd()
-    os.chdir(str(wd))                                    # ori_strain_abundance.txt goes to the current directory
-    try:
-        eng.profile(str(db), str(wd), str(gaf), **kw)
-    finally:
-        os.chdir(cwd)
-
-
-def _lines(path):
-    with open(path) as f:
-        return [l.rstrip("\n").split("\t") for l in f]
+    yield from seam_world(tmp_path_factory, "pantax_ct", 32, 4, 5, 30000, 30000, present_frac=0.4, single_strain_every=4, with_ids=True)
 
 
 def test_profile_seam_strain_coverage(world, set_opt, capfd):

@@ -10,6 +10,7 @@ import pytest
 
 from tests import depth_ref as ref
 from tests.conftest import ROOT
+from tests.helpers import seam_lines as _lines, seam_profile as _profile, seam_world
 from tests.hap_stats_cases import pack_reads
 
 pytestmark = pytest.mark.gpu
@@ -295,33 +296,7 @@ def test_depth_state_and_arguments(eng, narrow):
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    import synthdata as synth
-    from pantax_amd.engine import Engine
-    sset = synth.make_set(32, 4, 5, 30000, 30000, present_frac=0.4, single_strain_every=4, with_ids=True)   # the small world of test_profile_seam_strain_evidence
-    root = tmp_path_factory.mktemp("pantax_dp")
-    db = root / "db"
-    db.mkdir()
-    synth.write_db(sset, str(db))
-    gaf = root / "gfa_mapped.gaf"
-    synth.write_gaf(sset.reads, str(gaf))
-    e = Engine(0)
-    yield sset, root, db, gaf, e
-    e.close()
-
-
-def _profile(eng, db, wd, gaf, **kw):
-    wd.mkdir(exist_ok=True)
-    cwd = os.getcwd()
-    os.chdir(str(wd))                                    # ori_strain_abundance.txt goes to the current directory
-    try:
-        eng.profile(str(db), str(wd), str(gaf), **kw)
-    finally:
-        os.chdir(cwd)
-
-
-def _lines(path):
-    with open(path) as f:
-        return [l.rstrip("\n").split("\t") for l in f]
+    yield from seam_world(tmp_path_factory, "pantax_dp", 32, 4, 5, 30000, 30000, present_frac=0.4, single_strain_every=4, with_ids=True)   # the small world of test_profile_seam_strain_evidence
 
 
 OTHER_REPORTS = {"read_strain_file": "rs.tsv", "strain_coverage_file": "ct.tsv", "strain_evidence_file": "ev.tsv", "strain_read_support_file": "sup.tsv"}

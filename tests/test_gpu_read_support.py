@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests.conftest import ROOT
+from tests.helpers import seam_lines as _lines, seam_profile as _profile, seam_world
 from tests.read_support_ref import check_identities, read_support
 
 pytestmark = pytest.mark.gpu
@@ -233,33 +234,7 @@ HEADER = ["species_taxid", "strain_taxid", "genome_ID", "class", "n_reads", "n_s
 
 @pytest.fixture(scope="module")
 def world(tmp_path_factory):
-    import synthdata as synth
-    from pantax_amd.engine import Engine
-    sset = synth.make_set(37, 2, 5, 12000, 30000, present_frac=0.6, with_ids=True)
-    root = tmp_path_factory.mktemp("pantax_sup")
-    db = root / "db"
-    db.mkdir()
-    synth.write_db(sset, str(db))
-    gaf = root / "gfa_mapped.gaf"
-    synth.write_gaf(sset.reads, str(gaf))
-    e = Engine(0)
-    yield sset, root, db, gaf, e
-    e.close()
-
-
-def _profile(eng, db, wd, gaf, **kw):
-    wd.mkdir(exist_ok=True)
-    cwd = os.getcwd()
-    os.chdir(str(wd))                                    # ori_strain_abundance.txt goes to the current directory
-    try:
-        eng.profile(str(db), str(wd), str(gaf), **kw)
-    finally:
-        os.chdir(cwd)
-
-
-def _lines(path):
-    with open(path) as f:
-        return [l.rstrip("\n").split("\t") for l in f]
+    yield from seam_world(tmp_path_factory, "pantax_sup", 37, 2, 5, 12000, 30000, present_frac=0.6, with_ids=True)
 
 
 def test_profile_seam_read_support(world, capfd):
