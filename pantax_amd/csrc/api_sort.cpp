@@ -29,21 +29,23 @@ extern "C" int pantax_hip_sort_rows(pantax_hip_ctx *ctx, uint64_t n, uint64_t *k
         const uint32_t S = (uint32_t)seg_val.size();
         const int pack_shift = algo == 5 ? 8 : -1;   // algo 5: masks below 256, the segment number travels in the mask word
         if (algo == 5) for (uint64_t i = 0; i < n; ++i) if (k1[i] >> 8) return fail(ctx, PANTAX_HIP_E_INVALID, "sort_rows: algo 5 takes k1 < 256");
-        DevBuf<uint64_t> dm, da, r16, osp, om, oa;
+        DevBuf<uint64_t> dm, da, r16, o[3];   // o: the output words -- {species, mask, a}, or {species << pack_shift | mask, a} and one unused
         DevBuf<uint32_t> d_base, wsb, dn;
         PTX_TRY(upload(ctx, dm, k1, n)); PTX_TRY(upload(ctx, da, k2, n));
         PTX_TRY(upload(ctx, d_base, base.data(), base.size()));
-        PTX_HIP(ctx, r16.alloc(4 * n)); PTX_HIP(ctx, osp.alloc(n)); PTX_HIP(ctx, om.alloc(n)); PTX_HIP(ctx, oa.alloc(n)); PTX_HIP(ctx, dn.alloc(1));
+        PTX_HIP(ctx, r16.alloc(4 * n)); PTX_HIP(ctx, dn.alloc(1));
+        for (auto &w : o) PTX_HIP(ctx, w.alloc(n));
         PTX_HIP(ctx, wsb.alloc(sample_sort_nodes_ws_elems(S, bound, n)));
-        PTX_TRY(sample_sort_nodes(ctx, reinterpret_cast<const double *>(da.p), dm.p, d_base.p, S, bound, n, r16.p, pack_shift >= 0 ? (uint64_t *)nullptr : osp.p, om.p, oa.p,
-                                  pack_shift, wsb.p, dn.p));
+        uint64_t *const ok[3] = {o[0].p, o[1].p, o[2].p};
+        PTX_TRY(sample_sort_nodes(ctx, reinterpret_cast<const double *>(da.p), dm.p, d_base.p, S, bound, n, r16.p, ok, pack_shift, wsb.p, dn.p));
         uint32_t nv = 0;
         PTX_TRY(download(ctx, &nv, dn.p, 1));
         PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         std::vector<uint64_t> hs(nv), hm(nv), ha(nv);
         if (nv) {
-            if (pack_shift < 0) PTX_TRY(download(ctx, hs.data(), osp.p, nv));
-            PTX_TRY(download(ctx, hm.data(), om.p, nv)); PTX_TRY(download(ctx, ha.data(), oa.p, nv));
+            const int wm = pack_shift >= 0 ? 0 : 1;   // the word that holds the mask
+            if (pack_shift < 0) PTX_TRY(download(ctx, hs.data(), o[0].p, nv));
+            PTX_TRY(download(ctx, hm.data(), o[wm].p, nv)); PTX_TRY(download(ctx, ha.data(), o[wm + 1].p, nv));
             PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
         for (uint64_t i = 0; i < n; ++i) {

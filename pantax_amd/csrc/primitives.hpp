@@ -3,6 +3,7 @@
 // from __ballot matching (64-bit masks), block offsets from an LDS table, one launch per stage.
 #pragma once
 #include "common.hpp"
+#include "ssn_plan.hpp"
 
 namespace ptx {
 
@@ -46,9 +47,10 @@ size_t sample_sort_ws_elems(uint64_t n_bound);
 int sample_sort3(Ctx *ctx, SortBufs a, SortBufs b, uint64_t n_bound, uint32_t *d_ws, const uint32_t *d_n);
 
 // The batched sort WITHOUT the compaction in front of it (sample_sort_nodes.hip): segment s = the nodes [node_base[s], node_base[s + 1])
-// (at most seg_bound <= SS_MAX_N of them), a node is a row when ab > 0 and mask != 0.  The rows of all segments end up back to back in
-// (ksp, km, ka) -- ksp null: species << pack_shift | mask in km -- every segment sorted by (mask, a); *d_n = their number.
-// rows16: 4 V words of scratch; d_ws: >= sample_sort_nodes_ws_elems(S, seg_bound, V) u32.
+// (at most seg_bound <= SSN_MAX_SEG of them, ssn_plan.hpp), a node is a row when ab > 0 and mask != 0.  The rows of all segments end up back to
+// back in the output words k, every segment sorted by (mask, a); *d_n = their number.  pack_shift < 0: k = {species, mask, a}; otherwise
+// k = {species << pack_shift | mask, a} and k[2] is not used.
+// rows16: 4 V words of scratch; d_ws: >= sample_sort_nodes_ws_elems(S, seg_bound, V) u32 (ssn_plan's total), a DevBuf allocation.
 // pat (optional): the runs of equal mask inside every segment, in order -- pat_mask / pat_start (first row) / pat_species of run k,
 // sp_pat_off[s] = first run of segment s ([S + 1]), *d_K = their number, pat_start[K] = the row count.  Arrays of >= V (+ 1) entries.
 struct RowPatterns {
@@ -56,7 +58,6 @@ struct RowPatterns {
     uint32_t *pat_start, *pat_species, *sp_pat_off, *d_K;
     double *c0;   // [S] or null: per segment the sum of ab over the nodes with ab > 0 and mask == 0 (the rows-free part of the LP's objective)
 };
-constexpr uint64_t SSN_MAX_SEG = 1ull << 26;   // nodes of one segment (buckets grow with the segment: beyond 4096 rows they are sorted through memory)
 // mask == null: the sort forms a node's membership mask itself from its haplotype word (and sums the candidates' covered bases and lengths
 // on the way: what mask_nodes_kernel does in a pass of its own) -- the mask array is then neither written nor read
 struct RowMaskSource {
@@ -83,7 +84,7 @@ struct NodeCovSource {
 };
 size_t sample_sort_nodes_ws_elems(uint32_t S, uint64_t seg_bound, uint64_t V);
 int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const uint32_t *d_node_base, uint32_t S, uint64_t seg_bound, uint64_t V,
-                      uint64_t *rows16, uint64_t *ksp, uint64_t *km, uint64_t *ka, int pack_shift, uint32_t *d_ws, uint32_t *d_n, const RowPatterns *pat = nullptr,
+                      uint64_t *rows16, uint64_t *const k[3], int pack_shift, uint32_t *d_ws, uint32_t *d_n, const RowPatterns *pat = nullptr,
                       const RowMaskSource *haps = nullptr, const NodeCovSource *fused = nullptr);
 
 // helper: passes covering bits [lo,hi) of a word, least significant first, appended to out

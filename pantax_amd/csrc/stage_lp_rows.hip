@@ -699,9 +699,8 @@ static int sort_rows(Ctx *ctx, Db *db, LadBatch *lb, const RowRoute &rt, int pma
             hp.node_haps = (const unsigned long long *)db->d_node_haps.p; hp.hap_off = db->d_hap_off.p; hp.hap_bit = lb->d_hap_bit.p; hp.sp_p = lb->d_p.p;
             hp.cov = db->d_cov.p; hp.node_len = db->d_node_len.p; hp.ratio = lb->d_ratio.p; hp.max_haps = rt.max_haps;
         }
-        PTX_TRY(sample_sort_nodes(ctx, fused ? (const double *)nullptr : lb->d_ab.p, lb->d_mask.p, db->d_node_base.p, S, rt.max_vs, V, db->d_row16.p, pack_shift >= 0 ? (uint64_t *)nullptr : ka[0].p,
-                                  pack_shift >= 0 ? ka[0].p : ka[1].p, pack_shift >= 0 ? ka[1].p : ka[2].p, pack_shift, db->d_ss_ws.p, d_n, &pat, rt.masks_in_sort ? &hp : nullptr,
-                                  fused ? &fz : nullptr));
+        PTX_TRY(sample_sort_nodes(ctx, fused ? (const double *)nullptr : lb->d_ab.p, lb->d_mask.p, db->d_node_base.p, S, rt.max_vs, V, db->d_row16.p, A.k, pack_shift, db->d_ss_ws.p, d_n, &pat,
+                                  rt.masks_in_sort ? &hp : nullptr, fused ? &fz : nullptr));
         if (fused) db->cov_count_pending = false;             // the covered bases were counted (and used) inside the sort
     } else if (rt.use_sample) {   // few rows: sample sort (6 launches) instead of 10+ radix passes of 3 launches each
         PTX_HIP(ctx, db->d_ss_ws.alloc(sample_sort_ws_elems(V)));

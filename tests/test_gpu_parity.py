@@ -1169,6 +1169,29 @@ def test_node_order_sample_sort_against_host_sort(eng, algo):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("algo", [4, 5])
+def test_node_order_sample_sort_many_small_segments_one_large(eng, algo):
+    """The same sort where the SEGMENT COUNT sets the partition geometry (ssn_plan): 4100 segments of one to three entries (masks 0 .. 7, 0 = no
+    row) around one of 6000 -- three tiles of 2048 nodes, and 3 x 4101 tiles in all exceed the 8192 workgroups the partition kernels aim at, so every
+    workgroup walks two tiles (per = 2, G = 2) and the last one's range [2, 4) is clamped to the segment's three.  Elsewhere only the segment of three
+    million nodes reaches per > 1."""
+    rng = np.random.default_rng(12)
+    sizes = rng.integers(1, 4, 4101)
+    sizes[2050] = 6000
+    k0 = np.repeat(np.arange(4101, dtype=np.uint64) * np.uint64(3) + np.uint64(1), sizes)
+    n = len(k0)
+    k1 = rng.integers(0, 8, n).astype(np.uint64)
+    k2 = rng.integers(0, 2 ** 62, n).astype(np.uint64)
+    got = eng.sort_rows(k0, k1, k2, algo=algo)
+    row = (k1 != 0) & (k2 != 0) & (k2 < np.uint64(0x7FF0000000000000))
+    exp = _host_sorted(k0[row], k1[row], k2[row])
+    nv = int(row.sum())
+    for g, e in zip(got, exp):
+        assert np.array_equal(g[:nv], e)
+        assert not g[nv:].any()
+
+
+@pytest.mark.gpu
 def test_concurrent_solver_calls_on_one_ctx(eng, golden_dir):
     """The reference calls its solver from rayon workers (profile.rs:3297-3304): pantax_hip_pao_solve from several host
     threads on ONE ctx is legal -- calls are serialised inside -- and every thread gets the answer of its own call."""
