@@ -371,6 +371,34 @@ int pantax_hip_strain_near_miss(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
 int pantax_hip_near_miss_rank(uint32_t n_cand, const uint32_t *cand_hap, const uint64_t *cand_out /*[n_cand][2][4]*/, uint32_t top,
                               uint32_t *rank_out /*[n_cand]*/, uint32_t *n_out);
 
+/* ---- pairwise strain distinguishability of a db (the --db-pairs mode; not a stage of the reference): the strain step's LP has one 0/1 column per haplotype
+ * over the nodes of its species (profile.rs:1333-1342); two haplotypes with equal columns cannot be told apart by it, and two whose columns differ on 300
+ * bases of nodes only where those 300 bases are covered.  This call says, before any sample, which selected haplotypes of the db can be separated and by how
+ * many bases of graph.  It takes the selection type of pantax_hip_strain_evidence; Sel_s, K_s, M(v) and m(v) are exactly as defined there: membership is
+ * node-level (a node walked twice counts once), and every node of a species is counted once whether or not any walk visits it.
+ *   Q(v) = (1, node_len[v]), both u64, in the order { n_nodes, len }.  Coverage is not read.
+ *   pair_out [pair_off[S]][2]:  pair_out[pair_off[s] + a * K_s + b] = sum of Q(v) over the nodes v with both sel_hap entries at positions a and b of the
+ *     species' list in M(v).  The block of a species is symmetric; its diagonal is the haplotype's own node set: { n_nodes, len } of the evidence call's all.
+ *   pair_off_out [S+1] (pair_off[s + 1] = pair_off[s] + K_s^2) is computed on the host and always written; more than pair_cap entries: PANTAX_HIP_E_LIMIT
+ *     with nothing else touched (call with pair_cap = 0 to size pair_out, as for pantax_hip_strain_read_support).
+ *   species_out [S][3][2] or NULL, { total, none, core } of every species: total = the sum over every node; none = over m(v) = 0; core = over m(v) = K_s,
+ *     two zeros when K_s = 0.  In the two columns they share they are the evidence call's total, orphan and core.
+ * Every K_s from 0 to 256 is served (256: the width of the four-word LAD path and of the near-miss candidates).  An empty selection, or a species with
+ * nothing selected, is fine.  Integers only: results are exact and independent of any order.
+ * Identities: pair[a][b] <= min(pair[a][a], pair[b][b]);  core <= pair[a][b] for all a, b;  K_s = 1 gives pair = core;  total = none + the sum over m >= 1.
+ * Derived by the host (the --db-pairs table prints them):
+ *   only_a(a, b) = pair[a][a] - pair[a][b]: what a walks and b does not;
+ *   distance(a, b) = only_a.len + only_b.len: the length of the symmetric difference, the bases of graph on which the LP can tell a from b.
+ * State: the call needs an uploaded db with its graphs and nothing else -- no reads, no coverage pass.  It is legal before or behind any other call, and it
+ * neither reads nor changes the coverage result or the step's state.
+ * Errors (on any of them the outputs other than pair_off_out are left as given): K_s > 256: PANTAX_HIP_E_LIMIT naming the species; PANTAX_HIP_E_INVALID:
+ * n_species different from the db's, a haplotype index out of range, a haplotype twice within a species; a db uploaded without graphs: PANTAX_HIP_E_STATE.
+ * The option hap_pairs_route=walk (pantax_hip_set_option) takes every species' membership from its selected walks, as evidence_route=walk does;
+ * hap_pairs_chunk=N cuts the node pass into chunks of N nodes (tests). */
+int pantax_hip_db_hap_pairs(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel,
+                            uint64_t *pair_off_out /*[S+1]*/, uint64_t pair_cap /* entries pair_out holds */, uint64_t *pair_out /*[pair_off[S]][2]*/,
+                            uint64_t *species_out /*[S][3][2]: total, none, core; or NULL*/);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -611,6 +639,31 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in
  * groups of species, one after the other, inside the call -- no limit on the size of the DB other than the device memory a single group needs. */
 int pantax_hip_profile(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg);
+
+/* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
+ * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of
+ * the range file with more than one haplotype, in range-file order; an unknown taxid is PANTAX_HIP_E_INVALID.  Their graphs are read with the host
+ * loaders by the file seam's choice of container (<db>/species_graph_info/<otu>.bin, .bin.lz4, .bin.zst per `zip`, else <db>/species_gfa/<otu>.gfa; images
+ * are not used) and go through the device in groups: a group ends before the species that would carry it past the path steps of one resident db (3e9, or
+ * the option db_path_steps_max) or past its node indices.  A species of more than 256 haplotypes is not computed (a `skipped` row, one line on stderr).
+ * TSV with a header: species_taxid, genome_ID_a, genome_ID_b, class, n_nodes_a, len_a, n_nodes_b, len_b, shared_nodes, shared_len, only_a_len, only_b_len,
+ * distance, jaccard.  Pair rows first, per species in that order, a < b in haplotype-index order, only those of distance <= max_distance when that is >= 0:
+ * genome_ID = the genome_ID of the haplotype's first row of <db>/genomes_info.txt (the strain table's join), the haplotype's own name without one;
+ * { n_nodes, len } of a and b = the diagonal; shared = pair[a][b]; only_a_len, only_b_len and distance as defined at pantax_hip_db_hap_pairs;
+ * class = "identical" (distance 0: the LP cannot separate them), "nested" (exactly one of only_a_len, only_b_len is 0: one strain has nothing of its own
+ * against the other) or "distinct"; jaccard = shared_len / (len_a + len_b - shared_len) as f64 with shortest round-trip digits, "-" when that is 0.
+ * Then one row per species, in the same order: class "species", genome_ID_a = the number of haplotypes, genome_ID_b = "-", n_nodes_a / len_a = total,
+ * shared_nodes / shared_len = core, distance = the smallest distance over ALL the species' pairs ("-" for a single haplotype), every other column "-"; or
+ * class "skipped" for a species over the limit, with the number of haplotypes and "-" elsewhere. */
+typedef struct {
+    const char *db;              /* -db: the database directory */
+    const char *out_file;        /* --db-pairs: the table */
+    const char *range_file;      /* --range-file, or NULL: <db>/species_range.txt */
+    const char *species;         /* --db-pairs-species: taxids separated by commas; NULL or "" = every species with more than one haplotype */
+    const char *zip;             /* --zip serialize | lz | zstd; NULL (--gfa) = GFA text */
+    int64_t max_distance;        /* --db-pairs-max-distance in bases; negative = every pair */
+} pantax_hip_db_pairs_config;
+int pantax_hip_db_pairs(pantax_hip_ctx *ctx, const pantax_hip_db_pairs_config *cfg);
 
 /* ---- a1 / a6 host readers (no GPU needed): the file contracts of the pipeline seam, exposed so a
  * caller that keeps its own orchestration can still reuse the tokenizer and graph loaders ---------- */

@@ -24,6 +24,7 @@ SYMBOLS = [
     "pantax_hip_graph_load", "pantax_hip_graph_view", "pantax_hip_graph_free", "pantax_hip_format_f64",
     "pantax_hip_read_strains", "pantax_hip_strain_cov_track", "pantax_hip_strain_evidence", "pantax_hip_strain_read_support", "pantax_hip_strain_depth",
     "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_strain_near_miss", "pantax_hip_near_miss_rank",
+    "pantax_hip_db_hap_pairs", "pantax_hip_db_pairs",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -124,6 +125,11 @@ class NearMissSet(C.Structure):
     _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p), ("cand_off", C.c_void_p), ("cand_hap", C.c_void_p)]
 
 
+class DbPairsConfig(C.Structure):
+    _fields_ = [("db", C.c_char_p), ("out_file", C.c_char_p), ("range_file", C.c_char_p), ("species", C.c_char_p), ("zip", C.c_char_p),
+                ("max_distance", C.c_int64)]
+
+
 # int (*allreduce_sum)(void *user, double *buf, uint64_t n)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_uint64)
 # int (*alltoallv)(void *user, const void *send, const uint64_t *send_off, void *recv, const uint64_t *recv_off)
@@ -165,6 +171,10 @@ def load():
         _lib.pantax_hip_strain_depth.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_void_p]
         _lib.pantax_hip_strain_near_miss.restype = C.c_int
         _lib.pantax_hip_strain_near_miss.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(NearMissSet), C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_db_hap_pairs.restype = C.c_int
+        _lib.pantax_hip_db_hap_pairs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_db_pairs.restype = C.c_int
+        _lib.pantax_hip_db_pairs.argtypes = [C.c_void_p, C.POINTER(DbPairsConfig)]
         _lib.pantax_hip_near_miss_rank.restype = C.c_int
         _lib.pantax_hip_near_miss_rank.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
         _lib.pantax_hip_depth_bin.restype = C.c_uint32

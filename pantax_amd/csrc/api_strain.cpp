@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
+#include "hap_pairs_plan.hpp"
 #include "lad.hpp"
 #include "primitives.hpp"
 
@@ -587,6 +588,24 @@ int pantax_hip_strain_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pan
     if ((sel->sel_off[db->S] && !hap_out) || (db->S && !species_out)) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_evidence: null output array");
     PTX_TRY(check_stage_coverage(ctx, db, "strain_evidence"));
     return evidence_launch(ctx, db, sel->sel_off, sel->sel_hap, hap_out, species_out);
+}
+
+int pantax_hip_db_hap_pairs(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out,
+                            uint64_t *species_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off || !pair_off_out) return fail(ctx, PANTAX_HIP_E_INVALID, "db_hap_pairs: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "db_hap_pairs", sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, "db_hap_pairs", sel->sel_off, sel->sel_hap));
+    // (no state beyond the uploaded graphs: the call reads node lengths, walks and the node -> haplotype words, and writes nothing of the db's)
+    const uint32_t S = db->S, wide = hap_pairs_offsets(S, sel->sel_off, pair_off_out);
+    if (wide != S)
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "db_hap_pairs: species %u has %llu selected haplotypes, the call serves %llu", wide, (unsigned long long)(sel->sel_off[wide + 1] - sel->sel_off[wide]),
+                    (unsigned long long)HAP_PAIRS_MAX_K);
+    if (pair_off_out[S] > pair_cap)
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "db_hap_pairs: %llu pair entries, the caller's array holds %llu", (unsigned long long)pair_off_out[S], (unsigned long long)pair_cap);
+    if (pair_off_out[S] && !pair_out) return fail(ctx, PANTAX_HIP_E_INVALID, "db_hap_pairs: null output array");
+    return hap_pairs_launch(ctx, db, sel->sel_off, sel->sel_hap, pair_off_out, pair_out, species_out);
 }
 
 int pantax_hip_strain_depth(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *hap_out, uint64_t *species_out) {

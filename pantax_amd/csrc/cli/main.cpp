@@ -11,6 +11,7 @@
 static void usage() {
     fprintf(stderr,
             "usage: pantax-hip -db <db_dir> --gaf <gfa_mapped.gaf> [-T <work_dir>] [--species] [--strain]\n"
+            "       pantax-hip -db <db_dir> --db-pairs <out.tsv> [--db-pairs-species a,b] [--db-pairs-max-distance N] [--gfa | --zip ...] [--range-file F] [--device N]\n"
             "  --short-read | --long-read     (sets --fr default 0.3 / 0.5)\n"
             "  --fr F  --fc F(0.46)  -a F(1e-4)  --sr F(0.85)  --sd F(0.2)  --shift true|false\n"
             "  --min_cov N  --min_depth N  --sample N (default 500000)  --sample_test  --ds a,b,c  --smode 0|1  --no-filter\n"
@@ -39,6 +40,11 @@ static void usage() {
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
+            "  --db-pairs <out.tsv>   no sample: which strains of the db the strain step's LP can ever separate.  Per species every pair of haplotypes with the\n"
+            "                     nodes and bases both walk, the bases only one of them walks and their sum (distance), class identical / nested / distinct,\n"
+            "                     then per species its total, its core and its smallest distance; needs -db only (--gfa, --zip, --range-file, --device apply)\n"
+            "  --db-pairs-species a,b,c   only these species (default: every species with more than one haplotype)\n"
+            "  --db-pairs-max-distance N   only the pairs at most N bases apart (0: the identical ones)\n"
             "  --gfa (read species_gfa/*.gfa instead of species_graph_info/*.bin)  --zip serialize|lz|zstd  --round (2-decimal output)  --device N\n"
             "  --ranks N --rank r   one process per GPU (start N of them; device = r unless --device): every rank tokenises 1/N of the\n"
             "                       GAF, reads travel to the owner of their species over RCCL, rank 0 writes the tables\n"
@@ -56,6 +62,9 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
+    pantax_hip_db_pairs_config pairs;
+    memset(&pairs, 0, sizeof(pairs));
+    pairs.max_distance = -1;
     int device = -1, ranks = 0, rank = -1;
     std::string id_file;
     // per-launch nonce of the id file (rccl_comm.hpp): something that changes from one launch to the next where the launcher offers it
@@ -119,6 +128,9 @@ int main(int argc, char **argv) {
         else if (a == "--filter-gaf") filter_gaf = true;
         else if (a == "--image-cache") c.image_cache = atoi(next());
         else if (a == "--filter-only") { filter_in = next(); if (i + 1 < argc && argv[i + 1][0] != '-') filter_out = argv[++i]; }
+        else if (a == "--db-pairs") pairs.out_file = next();
+        else if (a == "--db-pairs-species") pairs.species = next();
+        else if (a == "--db-pairs-max-distance") pairs.max_distance = atoll(next());
         else if (a == "--device") device = atoi(next());
         else if (a == "--ranks") ranks = atoi(next());
         else if (a == "--rank") rank = atoi(next());
@@ -139,6 +151,17 @@ int main(int argc, char **argv) {
         else printf("Filtered GAF: %llu lines, %llu alignment records, %llu written\n", (unsigned long long)nl, (unsigned long long)nr, (unsigned long long)nw);
         pantax_hip_destroy(fctx);
         return frc == 0 ? 0 : 1;
+    }
+    if (pairs.out_file) {   // a mode of its own, beside --filter-only: no GAF, no work directory, one rank
+        if (!c.db) { usage(); return 2; }
+        if (pairs.max_distance < -1) { fprintf(stderr, "pantax-hip: --db-pairs-max-distance %lld\n", (long long)pairs.max_distance); return 2; }
+        pairs.db = c.db; pairs.range_file = c.range_file; pairs.zip = c.zip;
+        pantax_hip_ctx *pctx = nullptr;
+        if (pantax_hip_init(&pctx, &device, 1) != 0) { fprintf(stderr, "pantax-hip: %s\n", pantax_hip_last_error(nullptr)); return 1; }
+        const int prc = pantax_hip_db_pairs(pctx, &pairs);
+        if (prc != 0) fprintf(stderr, "pantax-hip: error %d: %s\n", prc, pantax_hip_last_error(pctx));
+        pantax_hip_destroy(pctx);
+        return prc == 0 ? 0 : 1;
     }
     if (!c.db || !c.input_aln_file) { usage(); return 2; }
     if (c.unique_trio_nodes_fraction < 0) c.unique_trio_nodes_fraction = long_read ? 0.5 : 0.3;   // main.rs:108-114

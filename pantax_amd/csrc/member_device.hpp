@@ -9,8 +9,8 @@
 namespace ptx {
 
 // Route 2: node membership in chosen walks as a compact arena -- member_words(K) words per node of a species over its K chosen haplotypes only (bit k = the
-// k-th of them), filled by read_strain_mask_kernel (walk_masks.hip).  Its five users: read_strains_launch and read_support_launch (through rs_table_build),
-// evidence_launch, depth_launch, near_miss_launch (over Sel ++ Cand).  The object owns the device buffers: it outlives the kernels that read d_mask.
+// k-th of them), filled by read_strain_mask_kernel (walk_masks.hip).  Its six users: read_strains_launch and read_support_launch (through rs_table_build),
+// evidence_launch, depth_launch, near_miss_launch (over Sel ++ Cand), hap_pairs_launch.  The object owns the device buffers: it outlives the kernels that read d_mask.
 constexpr uint64_t WALK_MASK_TILE = 4096;   // walk positions per tile of the mask pass (one wave)
 struct WalkMaskTile { uint64_t p0, p1, word0; uint32_t nw, k; };   // walk positions [p0, p1) of chosen walk k; its words start at word0 (+ local node * nw)
 struct WalkMasks {
@@ -22,7 +22,7 @@ struct WalkMasks {
     uint64_t add_species(const Db *db, uint32_t s, const uint32_t *haps, uint64_t K);          // -> first word of the species' node masks
     int build(Ctx *ctx, const Db *db);   // after the last row / add_species: zero fill + the pass over the tiles, on ctx->stream
 };
-// What the launchers of the three node passes (evidence, depth, near miss) hold on the device around their kernel: the masks, and one output block [a | b]
+// What the launchers of the four node passes (evidence, depth, near miss, hap pairs) hold on the device around their kernel: the masks, and one output block [a | b]
 struct MemberPass {
     WalkMasks wm;
     DevBuf<unsigned long long> d_out;

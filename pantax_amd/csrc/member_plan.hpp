@@ -1,10 +1,10 @@
 // member_plan.hpp -- "which of the chosen haplotypes of this species walk node v?", the question of the five strain reports (read strains, read support,
-// node evidence, depth, near miss), decided once on the host as pure functions of plain values:
+// node evidence, depth, near miss) and of the db's pair sums (hap pairs: six users), decided once on the host as pure functions of plain values:
 //   route 0 -- nothing chosen;
 //   route 1 -- a species of <= 64 haplotypes whose node -> haplotype words were built at upload (Db::d_node_haps), the call's *_route option not "walk":
 //              word(v) = node_haps[v] & bits, bit = haplotype index; no array of its own;
 //   route 2 -- every other species: ceil(K / 64) words per node over the K chosen haplotypes only, bit = position in the chosen list (WalkMasks, member_device.hpp).
-// The launchers of the five reports follow it; nothing else decodes a *_route option, spells the route predicate or sizes a node's words.  Standard
+// The launchers of the six users follow it; nothing else decodes a *_route option, spells the route predicate or sizes a node's words.  Standard
 // headers only: tests/native/member_plan_check.cpp compiles this with the host compiler alone; MemberRow is also what the kernels read.
 #pragma once
 #include <cstdint>
@@ -24,7 +24,8 @@ struct MemberRow {
     uint32_t K;                // chosen haplotypes
 };
 template <class T> constexpr T member_words(T K) { return (K + 63) / 64; }   // words that hold K bits
-// route 1 is open: `route_opt` is the call's read_strain_route / evidence_route / depth_route / near_miss_route (any value but "walk": the default)
+// route 1 is open: `route_opt` is the call's read_strain_route / evidence_route / depth_route / near_miss_route / hap_pairs_route (any value but "walk":
+// the default)
 bool member_by_node(bool nh_built, const std::string &route_opt);
 unsigned long long member_bits(const uint32_t *haps, uint64_t K);   // bit haps[k] for every k (haplotype indices < 64)
 // the row of a species of `nh` haplotypes of which haps[0 .. K) are chosen; mask_base is left 0
@@ -40,7 +41,8 @@ inline uint32_t member_bit_base(uint32_t route, uint64_t hap_off_s, uint64_t H, 
 // a node's candidate words are w0 .. w0 + cwn - 1 and candidate i is bit cand0 + i counted from word w0.  Route 1: one word, bit = haplotype index.
 struct NearMissLayout { uint32_t nw = 0, w0 = 0, cwn = 0, cand0 = 0; };
 NearMissLayout near_miss_layout(uint64_t K, uint64_t J, uint32_t route);
-// The nodes [node_begin, node_end) of species s cut into chunks of `chunk` nodes, once per tile, tile-major; appended to `out`
+// The nodes [node_begin, node_end) of species s cut into chunks of `chunk` nodes, once per tile, tile-major; appended to `out` (hap pairs: a tile is a
+// block pair of mask words, hap_pairs_plan.hpp)
 struct MemberChunk { uint32_t first, n, species, tile; };   // global nodes [first, first + n), n <= chunk
 void member_chunks_add(std::vector<MemberChunk> &out, uint32_t s, uint64_t node_begin, uint64_t node_end, uint32_t chunk, uint64_t tiles);
 

@@ -404,6 +404,26 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_near_miss(self.ctx, self.db, C.byref(cs), p(cand) if len(ch) else None, p(species) if self.S else None))
         return cand, species
 
+    def hap_pairs(self, sel_off, sel_hap, species=True):
+        """Pairwise strain distinguishability (pantax_hip_db_hap_pairs) of the resident db: no reads, no coverage pass.  sel_off [S+1], sel_hap as for
+        strain_evidence (at most 256 haplotypes a species) -> (pair_off uint64 [S+1], pair uint64 [pair_off[-1], 2]: the K_s x K_s block of species s
+        from pair_off[s], row-major, {n_nodes, len} of the nodes both haplotypes walk, species uint64 [S, 3, 2]: total / none / core).  species=False:
+        the species sums are not fetched (species_out = NULL) and None is returned in their place."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("hap_pairs: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        cs = _ffi.EvidenceSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None)
+        pair_off = np.zeros(self.S + 1, dtype=np.uint64)
+        rc = self.lib.pantax_hip_db_hap_pairs(self.ctx, self.db, C.byref(cs), p(pair_off), 0, None, None)   # sizes the array
+        if rc != _ffi.E_LIMIT:
+            self._check(rc)
+        n = int(pair_off[-1])
+        pair = np.zeros((n, 2), dtype=np.uint64)
+        sp = np.zeros((self.S, 3, 2), dtype=np.uint64) if species else None
+        self._check(self.lib.pantax_hip_db_hap_pairs(self.ctx, self.db, C.byref(cs), p(pair_off), n, p(pair) if n else None, p(sp) if species and self.S else None))
+        return pair_off, pair, sp
+
     def trio_nodes_info(self, fetch=True):
         n = C.c_uint64(0)
         self._check(self.lib.pantax_hip_trio_index(self.ctx, self.db, C.byref(n)))
@@ -611,6 +631,17 @@ class Engine:
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
         self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
+
+    def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
+        """pantax_hip_db_pairs (the --db-pairs mode): the pairwise distinguishability table of a db directory -> out_file.  species: taxids (a list or a
+        comma-separated string; None = every species with more than one haplotype); max_distance: only pairs at most that many bases apart (None:
+        all); zip: "serialize" / "lz" / "zstd", None = GFA text."""
+        enc = lambda x: None if x is None else str(x).encode()
+        if species is not None and not isinstance(species, str):
+            species = ",".join(str(x) for x in species)
+        cfg = _ffi.DbPairsConfig(db=enc(db), out_file=enc(out_file), range_file=enc(range_file), species=enc(species), zip=enc(zip),
+                                 max_distance=-1 if max_distance is None else int(max_distance))
+        self._check(self.lib.pantax_hip_db_pairs(self.ctx, C.byref(cfg)))
 
     def save_images(self, paths, hap_names):
         """one device-ready image per species of the resident db: the graph alone (node lengths, walk offsets, packed walks,
