@@ -399,6 +399,31 @@ int pantax_hip_db_hap_pairs(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax
                             uint64_t *pair_off_out /*[S+1]*/, uint64_t pair_cap /* entries pair_out holds */, uint64_t *pair_out /*[pair_off[S]][2]*/,
                             uint64_t *species_out /*[S][3][2]: total, none, core; or NULL*/);
 
+/* ---- pairwise strain evidence (the --strain-pair-evidence report; not a stage of the reference): pantax_hip_db_hap_pairs says, before any sample, on how
+ * many bases of graph two haplotypes differ; the evidence call says what a selected haplotype has against ALL the others.  This call says, for every two
+ * selected haplotypes of a species, how much of the graph they share and of the graph that separates them the sample covered.  Selection, Sel_s, K_s, M(v)
+ * and m(v) are exactly those of pantax_hip_strain_evidence: membership is node-level (a node walked twice counts once), every node is counted once.
+ *   Q(v) = (1, node_len[v], node_base_cov[v], bases_per_node[v]), all four u64, in the order { n_nodes, len, covered, bases }: the evidence call's Q,
+ *     element for element.
+ *   pair_out [pair_off[S]][4]:  pair_out[pair_off[s] + a * K_s + b] = sum of Q(v) over the nodes v with both sel_hap entries at positions a and b of the
+ *     species' list in M(v).  The block of a species is symmetric, K_s x K_s, row-major from pair_off[s]; pair_off[s + 1] = pair_off[s] + K_s^2.
+ *   species_out [S][3][4] or NULL: { total, orphan, core } of every species, as the evidence call writes them.
+ * Every K_s from 0 to 256 is served; more: PANTAX_HIP_E_LIMIT naming the species.  Sizing as for pantax_hip_db_hap_pairs: pair_off_out is computed on the
+ * host and always written (once the selection is valid); more than pair_cap entries: PANTAX_HIP_E_LIMIT with nothing else touched (call with pair_cap = 0
+ * to size pair_out).  Integers only: results are exact and independent of any order; a u64 sum that overflows wraps exactly as the evidence call's does.
+ * Identities: columns 0:2 of pair_out equal pantax_hip_db_hap_pairs on the same selection;  the diagonal pair[a][a] equals the evidence call's all of the
+ * entry;  species_out equals the evidence call's;  pair[a][b] <= min(pair[a][a], pair[b][b]) in every column;  core <= pair[a][b] for all a, b.
+ * Derived by the host (the report prints them):
+ *   only_a(a, b) = pair[a][a] - pair[a][b] in all four columns: what a walks and b does not, and what the sample put there;
+ *   class(a, b) from the len column exactly as the --db-pairs table derives it: identical (only_a.len = only_b.len = 0), nested (one of them 0), distinct.
+ * State rules of pantax_hip_strain_evidence: the db must hold the coverage result of a pantax_hip_node_coverage call; behind a resident step
+ * (pantax_hip_profile_step / _enqueue), and before any coverage pass, the call returns PANTAX_HIP_E_STATE and says why.  PANTAX_HIP_E_INVALID as in the
+ * evidence call: n_species different from the db's, a haplotype index out of range, a haplotype twice within a species.  On any error the outputs other
+ * than pair_off_out are left as given.  The call obeys hap_pairs_route and hap_pairs_chunk (pantax_hip_set_option) as pantax_hip_db_hap_pairs does. */
+int pantax_hip_strain_pair_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel,
+                                    uint64_t *pair_off_out /*[S+1]*/, uint64_t pair_cap /* entries pair_out holds */, uint64_t *pair_out /*[pair_off[S]][4]*/,
+                                    uint64_t *species_out /*[S][3][4]: total, orphan, core; or NULL*/);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -634,6 +659,18 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
      * bases.  Written only by a run that performs the strain step; world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
     const char *strain_near_miss_file;
     int32_t strain_near_miss_top;   /* --strain-near-miss-top: candidates printed per species; 0 = the default of 5; negative: PANTAX_HIP_E_INVALID */
+    /* --strain-pair-evidence: path of the pairwise strain evidence report (pantax_hip_strain_pair_evidence over every group of species, right behind the
+     * group's evidence sums, on the same coverage result; NULL, "" or "None" = off).  Sel_s = the species' rows of strain_abundance.txt, in ascending
+     * haplotype index.  TSV with a header: species_taxid, strain_taxid, genome_ID, other_strain_taxid, other_genome_ID, class, n_nodes, len, covered, bases,
+     * depth, breadth, predicted_coverage, pair_class.  Species in the order they went through the device; for every two entries a < b of a species three
+     * rows: class "shared", head a, other b, pair[a][b], predicted_coverage = second_sol(a) + second_sol(b) (a lower bound of what is expected there: other
+     * strains may walk these nodes too); class "only", head a, other b, pair[a][a] - pair[a][b], predicted_coverage = second_sol(a); class "only", head b,
+     * other a, pair[b][b] - pair[a][b], predicted_coverage = second_sol(b).  An entry stands in the table with its first row of strain_abundance.txt.
+     * depth = bases / len, breadth = covered / len ("-" when len = 0).  pair_class, the same on the three rows: identical, nested or distinct, from the len
+     * column as the --db-pairs table derives it.  A species with fewer than two rows writes nothing; one with more than 256 rows writes one row of class
+     * "skipped" with "-" in every other column but the species', and the call is not made for it.  Written only by a run that performs the strain step;
+     * world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID. */
+    const char *strain_pair_evidence_file;
 } pantax_hip_profiling_config;
 
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in

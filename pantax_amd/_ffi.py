@@ -24,7 +24,7 @@ SYMBOLS = [
     "pantax_hip_graph_load", "pantax_hip_graph_view", "pantax_hip_graph_free", "pantax_hip_format_f64",
     "pantax_hip_read_strains", "pantax_hip_strain_cov_track", "pantax_hip_strain_evidence", "pantax_hip_strain_read_support", "pantax_hip_strain_depth",
     "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_strain_near_miss", "pantax_hip_near_miss_rank",
-    "pantax_hip_db_hap_pairs", "pantax_hip_db_pairs",
+    "pantax_hip_db_hap_pairs", "pantax_hip_db_pairs", "pantax_hip_strain_pair_evidence",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -106,7 +106,7 @@ class ProfilingConfig(C.Structure):
                 ("sample_test", C.c_int32), ("solver_semantics", C.c_int32), ("minimization_min_cov", C.c_double),
                 ("read_strain_file", C.c_char_p), ("strain_coverage_file", C.c_char_p), ("strain_coverage_window", C.c_int64),
                 ("strain_evidence_file", C.c_char_p), ("strain_read_support_file", C.c_char_p), ("strain_depth_file", C.c_char_p),
-                ("strain_near_miss_file", C.c_char_p), ("strain_near_miss_top", C.c_int32)]
+                ("strain_near_miss_file", C.c_char_p), ("strain_near_miss_top", C.c_int32), ("strain_pair_evidence_file", C.c_char_p)]
 
 
 class ReadStrainSet(C.Structure):
@@ -173,6 +173,8 @@ def load():
         _lib.pantax_hip_strain_near_miss.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(NearMissSet), C.c_void_p, C.c_void_p]
         _lib.pantax_hip_db_hap_pairs.restype = C.c_int
         _lib.pantax_hip_db_hap_pairs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_strain_pair_evidence.restype = C.c_int
+        _lib.pantax_hip_strain_pair_evidence.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         _lib.pantax_hip_db_pairs.restype = C.c_int
         _lib.pantax_hip_db_pairs.argtypes = [C.c_void_p, C.POINTER(DbPairsConfig)]
         _lib.pantax_hip_near_miss_rank.restype = C.c_int

@@ -29,8 +29,6 @@ std::string load_graph(const std::string &db_dir, const std::string &zip, const 
     return read_gfa(gfa, g);
 }
 
-const char *pair_class(uint64_t only_a, uint64_t only_b) { return only_a == 0 && only_b == 0 ? "identical" : (only_a == 0 || only_b == 0) ? "nested" : "distinct"; }
-
 // one group of species resident: upload, every haplotype selected, one call, the group's pair rows -> `out`, its species sums -> sp
 int run_group(pantax_hip_ctx *ctx, const pantax_hip_db_pairs_config *cfg, std::vector<PairsSpecies> &sp, const std::vector<uint32_t> &members, const std::vector<HostGraph> &graphs,
               const std::unordered_map<std::string, std::string> &genome_of, std::ostream &out) {
@@ -67,7 +65,7 @@ int run_group(pantax_hip_ctx *ctx, const pantax_hip_db_pairs_config *cfg, std::v
                 const uint64_t only_a = aa[1] - ab[1], only_b = bb[1] - ab[1], dist = only_a + only_b, uni = aa[1] + bb[1] - ab[1];
                 s.min_dist = std::min(s.min_dist, dist); s.has_dist = true;
                 if (cfg->max_distance >= 0 && dist > (uint64_t)cfg->max_distance) continue;
-                out << s.taxid << '\t' << name(a) << '\t' << name(b) << '\t' << pair_class(only_a, only_b) << '\t' << aa[0] << '\t' << aa[1] << '\t' << bb[0] << '\t' << bb[1] << '\t'
+                out << s.taxid << '\t' << name(a) << '\t' << name(b) << '\t' << hap_pair_class(only_a, only_b) << '\t' << aa[0] << '\t' << aa[1] << '\t' << bb[0] << '\t' << bb[1] << '\t'
                     << ab[0] << '\t' << ab[1] << '\t' << only_a << '\t' << only_b << '\t' << dist << '\t' << (uni ? fmt_f64((double)ab[1] / (double)uni) : std::string("-")) << '\n';
             }
     }

@@ -82,6 +82,8 @@ int decide_resume(Run &run) {
 void rs_skipped(const RunPlan &p) {
     for (int i = 0; i < N_REPORTS; ++i)
         if (p.rep.want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.path[i].c_str());
+    for (int i = 0; i < N_PAIR_REPORTS; ++i)
+        if (p.rep.pair_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.pair_path[i].c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
 // ALL species ranges (ranges-only db), counters on the device

@@ -608,6 +608,24 @@ int pantax_hip_db_hap_pairs(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax
     return hap_pairs_launch(ctx, db, sel->sel_off, sel->sel_hap, pair_off_out, pair_out, species_out);
 }
 
+int pantax_hip_strain_pair_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out,
+                                    uint64_t *species_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off || !pair_off_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_pair_evidence: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_pair_evidence", sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_pair_evidence", sel->sel_off, sel->sel_hap));
+    const uint32_t S = db->S, wide = hap_pairs_offsets(S, sel->sel_off, pair_off_out);
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_pair_evidence"));   // (the sizing call too: it sizes the array of a call that can run)
+    if (wide != S)
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_pair_evidence: species %u has %llu selected haplotypes, the call serves %llu", wide,
+                    (unsigned long long)(sel->sel_off[wide + 1] - sel->sel_off[wide]), (unsigned long long)HAP_PAIRS_MAX_K);
+    if (pair_off_out[S] > pair_cap)
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_pair_evidence: %llu pair entries, the caller's array holds %llu", (unsigned long long)pair_off_out[S], (unsigned long long)pair_cap);
+    if (pair_off_out[S] && !pair_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_pair_evidence: null output array");
+    return pair_evidence_launch(ctx, db, sel->sel_off, sel->sel_hap, pair_off_out, pair_out, species_out);
+}
+
 int pantax_hip_strain_depth(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *hap_out, uint64_t *species_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;
     if (!db || !sel || !sel->sel_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_depth: null argument");

@@ -37,6 +37,9 @@ static void usage() {
             "                     with the filter that dropped them; then per species the orphan nodes, those some candidate walks (claimed), those\n"
             "                     several do (contested) (one rank only)\n"
             "  --strain-near-miss-top N   candidates printed per species (default 5)\n"
+            "  --strain-pair-evidence F   pairwise strain evidence: for every two rows of strain_abundance.txt of a species the nodes both walk (class shared)\n"
+            "                     and the nodes only the one, only the other walks (only): n_nodes, len, covered, bases, depth, breadth, and whether the\n"
+            "                     two are identical, nested or distinct on the graph (one rank only)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -122,6 +125,7 @@ int main(int argc, char **argv) {
         else if (a == "--strain-depth") c.strain_depth_file = next();
         else if (a == "--strain-near-miss") c.strain_near_miss_file = next();
         else if (a == "--strain-near-miss-top") c.strain_near_miss_top = atoi(next());
+        else if (a == "--strain-pair-evidence") c.strain_pair_evidence_file = next();
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

@@ -696,6 +696,8 @@ int read_support_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
 int evidence_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t *hap_out, uint64_t *species_out);
 // stage_hap_pairs.hip: pantax_hip_db_hap_pairs behind its checks; pair_off [S+1] from hap_pairs_offsets
 int hap_pairs_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *pair_off, uint64_t *pair_out, uint64_t *species_out);
+// ... and pantax_hip_strain_pair_evidence behind its checks (coverage result resident): pair_out [..][4], species_out [S][3][4]
+int pair_evidence_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *pair_off, uint64_t *pair_out, uint64_t *species_out);
 // stage_depth.hip (pantax_hip_strain_depth): selection validated by the caller; hap_out [C][2][96][2], species_out [S][2][96][2] or null
 int depth_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t *hap_out, uint64_t *species_out);
 // stage_near_miss.hip (pantax_hip_strain_near_miss): both sets validated by the caller; cand_out [J][2][4], species_out [S][3][4]

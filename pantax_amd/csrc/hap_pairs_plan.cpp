@@ -26,12 +26,10 @@ uint32_t hap_pairs_cols(unsigned long long live_b) {
     return top < 8 ? 8u : top < 16 ? 16u : top < 32 ? 32u : 64u;
 }
 
-void hap_pairs_mirror(uint64_t *block, uint64_t K) {
+void hap_pairs_mirror(uint64_t *block, uint64_t K, uint32_t cols) {
     for (uint64_t b = 64; b < K; ++b)
-        for (uint64_t a = 0; a < b / 64 * 64; ++a) {
-            block[(b * K + a) * 2] = block[(a * K + b) * 2];
-            block[(b * K + a) * 2 + 1] = block[(a * K + b) * 2 + 1];
-        }
+        for (uint64_t a = 0; a < b / 64 * 64; ++a)
+            for (uint32_t q = 0; q < cols; ++q) block[(b * K + a) * cols + q] = block[(a * K + b) * cols + q];
 }
 
 }  // namespace ptx

@@ -1,4 +1,4 @@
-// hap_pairs_plan.hpp -- the host decisions of pantax_hip_db_hap_pairs (stage_hap_pairs.hip) as pure functions of plain values: the sizing of pair_off, the
+// hap_pairs_plan.hpp -- the host decisions of pantax_hip_db_hap_pairs and pantax_hip_strain_pair_evidence (stage_hap_pairs.hip) as pure functions of plain values: the sizing of pair_off, the
 // block pairs of a species' mask words and their tile numbers, the nodes a wave takes per chunk, the columns a wave keeps in registers, the mirror of the
 // lower triangle.  The work is C = B^T diag(Q) B over the 0/1 membership rows B of a species; its unit is a BLOCK PAIR (wa, wb), wa <= wb: the 64 haplotypes
 // of mask word wa against the 64 of word wb.  A species of nw words has nw (nw + 1) / 2 of them, numbered row-major over the upper triangle; that number is
@@ -42,8 +42,8 @@ inline unsigned long long hap_pairs_live(uint64_t K, uint32_t w) {
 uint32_t hap_pairs_chunk(uint32_t ka, uint32_t kb, int opt);
 // Columns a wave keeps in registers for a block pair whose live column bits are `live_b`: the smallest of 8, 16, 32, 64 above its highest bit (0: none)
 uint32_t hap_pairs_cols(unsigned long long live_b);
-// The K x K block of a species as the kernel leaves it (entries [a][b] of the block pairs wa <= wb; a diagonal block pair is whole): entries of { n, len }.
-// Fills [b][a] = [a][b] for a / 64 < b / 64.
-void hap_pairs_mirror(uint64_t *block /*[K][K][2]*/, uint64_t K);
+// The K x K block of a species as the kernel leaves it (entries [a][b] of the block pairs wa <= wb; a diagonal block pair is whole): entries of `cols`
+// u64, { n, len } of pantax_hip_db_hap_pairs or { n, len, covered, bases } of pantax_hip_strain_pair_evidence.  Fills [b][a] = [a][b] for a / 64 < b / 64.
+void hap_pairs_mirror(uint64_t *block /*[K][K][cols]*/, uint64_t K, uint32_t cols = 2);
 
 }  // namespace ptx

@@ -112,4 +112,8 @@ std::string near_miss_row_text(const std::string &species, const GenomeRow *gr, 
     s += '\t' + metric(PANTAX_HIP_HAS_SECOND, m ? m->second_sol : 0.0);
     return s;
 }
+const char *hap_pair_class(uint64_t only_a_len, uint64_t only_b_len) {
+    return only_a_len == 0 && only_b_len == 0 ? "identical" : (only_a_len == 0 || only_b_len == 0) ? "nested" : "distinct";
+}
+
 }  // namespace ptx

@@ -15,4 +15,6 @@ const char *near_miss_stage(const pantax_hip_hap_metrics &m);   // where an unre
 // looked at); q = {n_nodes, len, covered, bases}; share = q.bases / orphan_bases where with_share and orphan_bases > 0, else "-"
 std::string near_miss_row_text(const std::string &species, const GenomeRow *gr, const pantax_hip_hap_metrics *m, uint32_t rank, const char *cls, const uint64_t *q,
                                bool with_share, uint64_t orphan_bases);
+// class of a pair of haplotypes from the bases only one of them walks: identical, nested or distinct (the --db-pairs table and the pair evidence report)
+const char *hap_pair_class(uint64_t only_a_len, uint64_t only_b_len);
 }  // namespace ptx

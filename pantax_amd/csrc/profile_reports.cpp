@@ -1,9 +1,11 @@
 // profile_reports.cpp -- the per-strain reports of the file seam (profile_reports.hpp): per group of species, behind its strain step, the group's rows of
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
-// writes its file.  begin, collect_group and write at the end are the three places that name the reports.
+// writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
+// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way.
 #include <algorithm>
 #include <fstream>
 #include <unordered_map>
+#include "hap_pairs_plan.hpp"
 #include "profile_run.hpp"
 
 namespace ptx {
@@ -72,6 +74,28 @@ int group_node_sums(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const
     out.hap.resize(n_hap * (g.entry0 + g.hap.size()));
     PTX_TRY(call(run.ctx, db, &set, out.hap.data() + n_hap * g.entry0, out.species.data() + n_species * (size_t)k0));
     run.lap(lap);
+    return 0;
+}
+// --strain-pair-evidence, on the same coverage result: Sel_s = the group's rows, but for a species of more rows than the call serves, which gets no block
+int group_pair_evidence(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &pe = sh.rep.pe;
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint64_t> s_off(Sg + 1, 0), p_off(Sg + 1, 0);
+    std::vector<uint32_t> s_hap;
+    for (uint32_t k = 0; k < Sg; ++k) {
+        const uint64_t K = g.off[k + 1] - g.off[k];
+        pe.K[k0 + k] = (uint32_t)K;
+        if (K >= 2 && K <= HAP_PAIRS_MAX_K) s_hap.insert(s_hap.end(), g.hap.begin() + (ptrdiff_t)g.off[k], g.hap.begin() + (ptrdiff_t)g.off[k + 1]);
+        s_off[k + 1] = s_hap.size();
+    }
+    const pantax_hip_evidence_set set{Sg, s_off.data(), s_hap.data()};
+    const int rc_size = pantax_hip_strain_pair_evidence(run.ctx, db, &set, p_off.data(), 0, nullptr, nullptr);   // sizes: E_LIMIT unless there is no entry
+    if (rc_size != 0 && rc_size != PANTAX_HIP_E_LIMIT) return rc_size;
+    const size_t pair0 = pe.pair.size() / 4;
+    pe.pair.resize(4 * (pair0 + p_off[Sg]));
+    if (p_off[Sg]) PTX_TRY(pantax_hip_strain_pair_evidence(run.ctx, db, &set, p_off.data(), p_off[Sg], pe.pair.data() + 4 * pair0, nullptr));
+    for (uint32_t k = 0; k < Sg; ++k) pe.pair_off[k0 + k] = pair0 + p_off[k];
+    run.lap("  strain pair evidence");
     return 0;
 }
 // --strain-read-support: the candidates and weights of group_read_strains, summed on the device (nothing per read comes back)
@@ -162,8 +186,8 @@ struct Writer {
         return *e < 0 ? fail(run.ctx, PANTAX_HIP_E_STATE, "profile: strain %s is a row of the strain table but has no %s", sh.hap_names[r.hap].c_str(), what) : 0;
     }
     // open, header, body(f), close and check, lap
-    template <class Body> int file(ReportId id, const char *header, const char *lap, Body body) const {
-        const std::string &path = run.p.rep.path[id];
+    template <class Body> int file(ReportId id, const char *header, const char *lap, Body body) const { return file(run.p.rep.path[id], header, lap, body); }
+    template <class Body> int file(const std::string &path, const char *header, const char *lap, Body body) const {
         std::ofstream f(path);
         if (!f) return fail(run.ctx, PANTAX_HIP_E_IO, "cannot write %s", path.c_str());
         f << header;
@@ -326,6 +350,49 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-pair-evidence: per species of the shard, in the order it went through the device, for every two of its rows a < b (ascending haplotype index)
+    // what both walk (shared) and what only a, only b walks, as {n_nodes, len, covered, bases} with depth and breadth
+    int pair_evidence() const {
+        const auto &pe = rep.pe;
+        return file(run.p.rep.pair_path[PREP_EVIDENCE],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tother_strain_taxid\tother_genome_ID\tclass\tn_nodes\tlen\tcovered\tbases\tdepth\tbreadth\tpredicted_coverage\tpair_class\n",
+                    "strain pair evidence report", [&](std::ofstream &f) {
+            std::vector<const TrackRow *> row_of(rep.n_entries, nullptr);   // entry -> its first row of the table
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "pair evidence", &e));
+                if (!row_of[e]) row_of[e] = &r;
+            }
+            const auto put = [&](const TrackRow &head, const TrackRow &other, const char *cls, const uint64_t *q, double pc, const char *pair_cls) {
+                f << strain_head(head) << '\t' << (other.gr ? other.gr->strain_taxid : std::string()) << '\t' << (other.gr ? other.gr->genome_id : std::string()) << '\t' << cls << '\t'
+                  << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << q[3] << '\t';
+                if (q[1]) f << fmt_f64((double)q[3] / (double)q[1]) << '\t' << fmt_f64((double)q[2] / (double)q[1]);
+                else f << "-\t-";
+                f << '\t' << fmt_f64(pc) << '\t' << pair_cls << '\n';
+            };
+            for (uint32_t k = 0; k < Su; ++k) {
+                const uint64_t K = pe.K[k];
+                if (K < 2) continue;
+                if (K > HAP_PAIRS_MAX_K) { f << species(k) << "\t-\t-\t-\t-\tskipped\t-\t-\t-\t-\t-\t-\t-\t-\n"; continue; }
+                int64_t e0 = -1;                                                        // the species' entries are consecutive, in ascending haplotype index
+                for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1] && e0 < 0; ++h) e0 = rep.entry[h];
+                const uint64_t *pm = pe.pair.data() + 4 * pe.pair_off[k];
+                for (uint64_t a = 0; a < K; ++a)
+                    for (uint64_t b = a + 1; b < K; ++b) {
+                        if (e0 < 0 || !row_of[e0 + a] || !row_of[e0 + b]) continue;
+                        const TrackRow &ra = *row_of[e0 + a], &rb = *row_of[e0 + b];
+                        const uint64_t *aa = pm + 4 * (a * K + a), *bb = pm + 4 * (b * K + b), *ab = pm + 4 * (a * K + b);
+                        uint64_t only_a[4], only_b[4];
+                        for (int q = 0; q < 4; ++q) { only_a[q] = aa[q] - ab[q]; only_b[q] = bb[q] - ab[q]; }
+                        const char *const pc = hap_pair_class(only_a[1], only_b[1]);
+                        const double sa = sh.met[ra.hap].second_sol, sb = sh.met[rb.hap].second_sol;
+                        put(ra, rb, "shared", ab, sa + sb, pc);
+                        put(ra, rb, "only", only_a, sa, pc);
+                        put(rb, ra, "only", only_b, sb, pc);
+                    }
+            }
+            return 0;
+        });
+    }
 };
 }  // namespace
 
@@ -337,6 +404,7 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.run[REP_READ_SUPPORT]) { rep.sup.species.assign(12 * (size_t)Su, 0); rep.sup.pair_off.assign(Su, 0); rep.sup.K.assign(Su, 0); }
     if (plan.run[REP_DEPTH]) rep.dp.species.assign(2 * DEPTH_N * (size_t)Su, 0);
     if (plan.run[REP_NEAR_MISS]) { rep.nm.species.assign(12 * (size_t)Su, 0); rep.nm.row_off.assign(Su + 1, 0); }
+    if (plan.pair_run[PREP_EVIDENCE]) { rep.pe.pair_off.assign(Su, 0); rep.pe.K.assign(Su, 0); }
 }
 int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
     const ReportPlan &plan = run.p.rep;
@@ -346,6 +414,7 @@ int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, ui
     if (plan.run[REP_READ_STRAINS]) PTX_TRY(group_read_strains(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_COVERAGE]) PTX_TRY(group_cov_track(run, db, k0, k1, g, sh));
     if (plan.run[REP_EVIDENCE]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_evidence, 2 * EVIDENCE_N, 3 * EVIDENCE_N, sh.rep.ev, "  strain evidence"));
+    if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(group_pair_evidence(run, db, k0, k1, g, sh));
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh));
@@ -363,6 +432,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(w.read_support());
     if (plan.run[REP_DEPTH]) PTX_TRY(w.depth());
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(w.near_miss());
+    if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(w.pair_evidence());
     return 0;
 }
 }  // namespace reports

@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a row
-// of REPORTS, a sub-struct here, and a line in each of begin / collect_group / write (profile_reports.cpp).
+// of REPORTS (or of PAIR_REPORTS), a sub-struct here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -34,6 +34,9 @@ struct ReportData {
     // haplotype ([hap_names]) and q = {novel, exclusive, all} x {n_nodes, len, covered, bases}
     struct NearMissRow { uint64_t hap; uint64_t q[12]; };
     struct { std::vector<uint64_t> species, row_off; std::vector<NearMissRow> rows; } nm;
+    // --strain-pair-evidence: a species of K[k] = 2..256 rows owns the K x K block of {n_nodes, len, covered, bases} from entry pair_off[k] of pair (four u64
+    // an entry) over its entries in ascending order; K[k] is the species' number of rows whether or not it has a block
+    struct { std::vector<uint64_t> pair, pair_off; std::vector<uint32_t> K; } pe;
 };
 
 namespace reports {

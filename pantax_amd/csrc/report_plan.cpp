@@ -3,18 +3,27 @@
 
 namespace ptx {
 
+namespace {
+// the one rule of a row of either table: its path, whether it is wanted, and the refusal of a wanted report on several ranks or a sharded ingest
+bool plan_row(const ReportRow &row, const pantax_hip_profiling_config *cfg, int W, bool sharded, std::string &path_out, bool &want, std::string &err) {
+    const char *path = cfg->*row.field;
+    path_out = path ? path : "";
+    want = !path_out.empty() && path_out != "None";
+    if (want && (W > 1 || sharded)) {
+        err = std::string("profile: the ") + row.what + " (" + row.name + ") needs one rank and an unsharded ingest (world_size " + std::to_string(W) + (sharded ? ", sharded)" : ")");
+        return false;
+    }
+    return true;
+}
+// ... and when a wanted report runs
+bool runs(bool want, bool strain, bool full_path, bool strain_done) { return want && strain && !(full_path && strain_done); }
+}  // namespace
+
 bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, ReportPlan &plan, std::string &err) {
     plan = ReportPlan();
     for (int i = 0; i < N_REPORTS; ++i) {
-        const char *path = cfg->*REPORTS[i].field;
-        plan.path[i] = path ? path : "";
-        plan.want[i] = !plan.path[i].empty() && plan.path[i] != "None";
+        if (!plan_row(REPORTS[i], cfg, W, sharded, plan.path[i], plan.want[i], err)) return false;
         if (!plan.want[i]) continue;
-        if (W > 1 || sharded) {
-            err = std::string("profile: the ") + REPORTS[i].what + " (" + REPORTS[i].name + ") needs one rank and an unsharded ingest (world_size " + std::to_string(W) +
-                  (sharded ? ", sharded)" : ")");
-            return false;
-        }
         if (i == REP_COVERAGE) {
             if (cfg->strain_coverage_window < 0) { err = "profile: strain_coverage_window " + std::to_string((long long)cfg->strain_coverage_window); return false; }
             if (cfg->strain_coverage_window > 0) plan.ct_window = (uint64_t)cfg->strain_coverage_window;
@@ -24,11 +33,14 @@ bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, R
             if (cfg->strain_near_miss_top > 0) plan.nm_top = (uint32_t)cfg->strain_near_miss_top;
         }
     }
+    for (int i = 0; i < N_PAIR_REPORTS; ++i)
+        if (!plan_row(PAIR_REPORTS[i], cfg, W, sharded, plan.pair_path[i], plan.pair_want[i], err)) return false;
     return true;
 }
 
 void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_done) {
-    for (int i = 0; i < N_REPORTS; ++i) plan.run[i] = plan.want[i] && strain && !(full_path && strain_done);
+    for (int i = 0; i < N_REPORTS; ++i) plan.run[i] = runs(plan.want[i], strain, full_path, strain_done);
+    for (int i = 0; i < N_PAIR_REPORTS; ++i) plan.pair_run[i] = runs(plan.pair_want[i], strain, full_path, strain_done);
 }
 
 }  // namespace ptx

@@ -1,7 +1,7 @@
 // report_plan.hpp -- the per-strain reports of the file seam (pantax_hip_profile) as one table: which config field switches a report on, what its refusal
 // calls it, whether it follows the rows of strain_abundance.txt.  plan_reports / resume_reports decide from plain values which reports this call wants
 // and runs; nothing else in the seam spells a report's field name or repeats the rule.  pantax_hip.h and standard headers only:
-// tests/native/report_plan_check.cpp compiles this with the host compiler alone.
+// tests/native/report_plan_check.cpp and pair_report_plan_check.cpp compile this with the host compiler alone.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -25,16 +25,28 @@ constexpr ReportRow REPORTS[N_REPORTS] = {
     {&pantax_hip_profiling_config::strain_depth_file, "strain_depth_file", "per-strain depth distribution report", true},
     {&pantax_hip_profiling_config::strain_near_miss_file, "strain_near_miss_file", "unreported-strain near-miss report", false},
 };
+// A second id space: the reports about PAIRS of rows of the strain table.  Same row type, same rule (plan_reports / resume_reports apply it to both
+// tables through one helper), own want / run / path in the plan.  In the stated order of refusals the per-strain table comes first, then this one.
+enum PairReportId { PREP_EVIDENCE, N_PAIR_REPORTS };
+constexpr ReportRow PAIR_REPORTS[N_PAIR_REPORTS] = {
+    {&pantax_hip_profiling_config::strain_pair_evidence_file, "strain_pair_evidence_file", "pairwise strain evidence report", true},
+};
 struct ReportPlan {
-    std::string path[N_REPORTS];
+    std::string path[N_REPORTS], pair_path[N_PAIR_REPORTS];
     bool want[N_REPORTS] = {}, run[N_REPORTS] = {};   // want: the caller named a file; run: this call runs a strain step and writes it
+    bool pair_want[N_PAIR_REPORTS] = {}, pair_run[N_PAIR_REPORTS] = {};
     uint64_t ct_window = 10000;                       // window of the coverage track in bases
     uint32_t nm_top = 5;                              // candidates the near-miss report prints per species
-    bool any_run() const { for (const bool r : run) if (r) return true; return false; }
-    bool rows_run() const { for (int i = 0; i < N_REPORTS; ++i) if (run[i] && REPORTS[i].rows) return true; return false; }
+    bool any_run() const { for (const bool r : run) if (r) return true; for (const bool r : pair_run) if (r) return true; return false; }
+    bool rows_run() const {
+        for (int i = 0; i < N_REPORTS; ++i) if (run[i] && REPORTS[i].rows) return true;
+        for (int i = 0; i < N_PAIR_REPORTS; ++i) if (pair_run[i] && PAIR_REPORTS[i].rows) return true;
+        return false;
+    }
 };
 // cfg -> path, want and the two parameters.  A wanted report needs one rank and an unsharded ingest: its rows live on the rank that owns the species, the
-// rows of the GAF on the rank of their byte range -- not joined here.  false: the first failing check in table order, its message in err (E_INVALID)
+// rows of the GAF on the rank of their byte range -- not joined here.  false: the first failing check in table order (REPORTS, then
+// PAIR_REPORTS), its message in err (E_INVALID)
 bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, ReportPlan &plan, std::string &err);
 // run[] from want[]: a wanted report is written by a call that runs a strain step
 void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_done);

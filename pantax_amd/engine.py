@@ -424,6 +424,26 @@ class Engine:
         self._check(self.lib.pantax_hip_db_hap_pairs(self.ctx, self.db, C.byref(cs), p(pair_off), n, p(pair) if n else None, p(sp) if species and self.S else None))
         return pair_off, pair, sp
 
+    def pair_evidence(self, sel_off, sel_hap, species=True):
+        """Pairwise strain evidence (pantax_hip_strain_pair_evidence) of the coverage result get_node_abundances left on the device.  sel_off [S+1],
+        sel_hap as for strain_evidence (at most 256 haplotypes a species) -> (pair_off uint64 [S+1], pair uint64 [pair_off[-1], 4]: the K_s x K_s block
+        of species s from pair_off[s], row-major, {n_nodes, len, covered, bases} of the nodes both haplotypes walk, species uint64 [S, 3, 4]: total /
+        orphan / core).  species=False: the species sums are not fetched (species_out = NULL) and None is returned in their place."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("pair_evidence: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        cs = _ffi.EvidenceSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None)
+        pair_off = np.zeros(self.S + 1, dtype=np.uint64)
+        rc = self.lib.pantax_hip_strain_pair_evidence(self.ctx, self.db, C.byref(cs), p(pair_off), 0, None, None)   # sizes the array
+        if rc != _ffi.E_LIMIT:
+            self._check(rc)
+        n = int(pair_off[-1])
+        pair = np.zeros((n, 4), dtype=np.uint64)
+        sp = np.zeros((self.S, 3, 4), dtype=np.uint64) if species else None
+        self._check(self.lib.pantax_hip_strain_pair_evidence(self.ctx, self.db, C.byref(cs), p(pair_off), n, p(pair) if n else None, p(sp) if species and self.S else None))
+        return pair_off, pair, sp
+
     def trio_nodes_info(self, fetch=True):
         n = C.c_uint64(0)
         self._check(self.lib.pantax_hip_trio_index(self.ctx, self.db, C.byref(n)))
@@ -579,7 +599,7 @@ class Engine:
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
                 strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
-                strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0):
+                strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -587,7 +607,8 @@ class Engine:
         only), strain_coverage_window its window in bases (0: 10000).  strain_evidence_file: path of the per-strain node evidence report
         (--strain-evidence; one rank only).  strain_read_support_file: path of the per-strain read support report (--strain-read-support; one rank only).
         strain_depth_file: path of the per-strain depth distribution report (--strain-depth; one rank only).  strain_near_miss_file: path of the
-        unreported-strain near-miss report (--strain-near-miss; one rank only), strain_near_miss_top the candidates it prints per species (0: 5)."""
+        unreported-strain near-miss report (--strain-near-miss; one rank only), strain_near_miss_top the candidates it prints per species (0: 5).
+        strain_pair_evidence_file: path of the pairwise strain evidence report (--strain-pair-evidence; one rank only)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -602,7 +623,7 @@ class Engine:
             strain_coverage_file=enc(strain_coverage_file), strain_coverage_window=int(strain_coverage_window),
             strain_evidence_file=enc(strain_evidence_file), strain_read_support_file=enc(strain_read_support_file),
             strain_depth_file=enc(strain_depth_file), strain_near_miss_file=enc(strain_near_miss_file),
-            strain_near_miss_top=int(strain_near_miss_top))
+            strain_near_miss_top=int(strain_near_miss_top), strain_pair_evidence_file=enc(strain_pair_evidence_file))
         cb = None
         if allreduce is not None:   # allreduce(np.ndarray float64) sums it in place over the ranks
             def _cb(_user, buf, n):
