@@ -171,6 +171,11 @@ struct CtxConfig {
     std::string node_pass;           // "split": the resident step keeps node_cov_stats_kernel + ssn_hist_kernel where it would take the fused node_rows_kernel (tests compare, measurements)
     std::string lad_shape;           // LDS shape of the <= 16-column LAD solver: "" / "auto": compact when the batch has more species than the device has CUs, else roomy
                                      // (lad_shape(), lad.hpp); "roomy" / "compact": that shape for every such launch (tests compare, measurements)
+    std::string ssn_keys;            // node-order row sort: which rows get their key words (species / mask) next to the abundance.  "" / "auto": all of them where the caller
+                                     // reads the keys (pantax_hip_sort_rows), only those ssn_heads_kernel reads where the sort forms the pattern tables itself (the step);
+                                     // "all" / "needed": that mode ("needed" without pattern tables: PANTAX_HIP_E_INVALID) (tests compare, measurements)
+    bool ssn_poison_keys = false;    // tests: a sort in the "needed" mode first fills the key words with 0xA5 bytes -- a read of a word this sort did not store shows
+    int ssn_ties_async = -1;         // node-order row sort: the tie fill on the side stream, beside the scatter and the bucket sorts (1); 0: in line; -1: SSN_TIES_ASYNC_AUTO of ssn_plan.hpp (off)
     bool no_absent_skip = false;     // the statistics / histogram passes of the step read the species the species level dropped like the others (tests compare, measurements)
     bool ssn_debug = false, scan_no_huge = false, flag_rank_chained = false, ratio_kernel = false, mask_pass = false, trio_free_at_filter = false,
          trio_after_step = false;
@@ -196,6 +201,7 @@ struct Ctx {
     hipStream_t stream2 = nullptr;   // side stream of the resident step (the trio index does not depend on the reads)
     hipStream_t stream_up = nullptr; // copy stream of the file seam's graph loader thread (round 6; created on first use): the next group of species travels while this one's tables are built
     hipEvent_t ev_fork = nullptr;
+    hipEvent_t ev_ssn_fork = nullptr, ev_ssn_join = nullptr;   // the row sort's tie fill on the side stream (option ssn_ties_async; created on first use)
     hipEvent_t ev_seq = nullptr;     // orders the side stream behind everything enqueued on the main stream so far (steps run strictly one after the other on the device)
     std::string err;
     std::mutex err_mu;               // guards `err` alone (fail() may run before PTX_ENTER)

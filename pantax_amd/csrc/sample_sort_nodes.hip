@@ -17,7 +17,7 @@
 //                          per segment -> first output row of every segment, total row count
 //   4. ssn_partition.hip : rows {mask, a} as 16-byte records into their bucket (slots from LDS counters seeded by the matrix row) -- the rows of
 //                          the EVEN buckets only: a tie bucket holds copies of one key, so it is written as a fill of the output (coalesced) and
-//                          its rows never travel.  One 16-byte store per row is what this pass costs (tools/native/scatter_probe.hip: 2e8 rows
+//                          its rows never travel -- and of its rows the step keeps `a` alone, so the fill stores no key words (ssn_keys_all).  One 16-byte store per row is what this pass costs (tools/native/scatter_probe.hip: 2e8 rows
 //                          into 2048 buckets 4.2 ms, 1024: 3.5, 256: 2.9; the real rows, which tie massively, take 3.15 ms either way)
 //   5. ssn_local.hip     : a wave per even bucket, up to 512 rows sorted in registers; 513 .. 1024 rows in a second kernel; the rare larger buckets
 //                          through an LDS network, above 4096 rows (every bucket of a species of millions of nodes) in place through memory
@@ -53,6 +53,9 @@ int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const ui
         return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: the fused node pass takes haplotype words and the coverage arena");
     if (!fused && !ab) return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: no abundance array");
 
+    const int keys_all = ssn_keys_all(ctx->cfg.ssn_keys.c_str(), pat != nullptr);
+    if (keys_all < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: option ssn_keys=%s%s", ctx->cfg.ssn_keys.c_str(), pat ? "" : " (a sort whose caller reads the keys stores all of them)");
+
     const SsnPlan pl = ssn_plan(S, seg_bound, V);
     Sn sn;
     sn.node_base = d_node_base; sn.ab = ab; sn.mask = haps ? nullptr : mask;
@@ -76,6 +79,11 @@ int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const ui
     sn.km = pack_shift >= 0 ? k[0] : k[1];
     sn.ka = pack_shift >= 0 ? k[1] : k[2];
     sn.pack_shift = pack_shift;
+    sn.keys_all = (uint32_t)keys_all;
+    if (!keys_all && ctx->cfg.ssn_poison_keys) {   // tests: the buffers outlive the step, and an earlier sort's key words would pass for this one's
+        PTX_TRY(byte_fill(ctx, sn.km, 0xA5, V * sizeof(uint64_t)));
+        if (sn.ksp) PTX_TRY(byte_fill(ctx, sn.ksp, 0xA5, V * sizeof(uint64_t)));
+    }
 
     { KTimer t(ctx, "ssn_sample_kernel");
       ssn_sample_launch(ctx, sn, S, fused != nullptr); }
@@ -92,12 +100,42 @@ int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const ui
     }
     { KTimer t(ctx, "ssn_offsets_kernel");
       ssn_offsets_launch(ctx, sn, S, d_n); }
+    // The tie fill writes the odd bucket ranges of the output and reads the bucket starts, the splitter tree and seg_out, all complete behind the offsets
+    // kernels; the scatter and the local sorts touch the even buckets and the scratch.  ssn_ties_async: the fill goes onto the side stream from here and is
+    // joined in front of the first reader of the whole output (the heads kernel; without `pat`, the caller).  The guard joins on the host if anything
+    // between fork and join fails: nothing may return with the fill still running unordered on the side stream.
+    const bool clocked = ctx->timing && ctx->timing_filter.empty();
+    const bool ties_async = ssn_ties_async(ctx->cfg.ssn_ties_async, clocked, ctx->stream_main != nullptr, ctx->stream2 != nullptr);
+    struct TieJoin {
+        Ctx *c; bool armed;
+        ~TieJoin() { if (armed) (void)hipStreamSynchronize(c->stream2); }
+    } tie_join{ctx, false};
+    if (ties_async) {
+        if (!ctx->ev_ssn_fork) PTX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_ssn_fork, hipEventDisableTiming));
+        if (!ctx->ev_ssn_join) PTX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_ssn_join, hipEventDisableTiming));
+        PTX_HIP(ctx, hipEventRecord(ctx->ev_ssn_fork, ctx->stream));
+        PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_ssn_fork, 0));
+        hipStream_t main_stream = ctx->stream;
+        ctx->stream_main = main_stream; ctx->stream = ctx->stream2;
+        tie_join.armed = true;
+        { KTimer t(ctx, "ssn_ties_kernel");
+          ssn_ties_launch(ctx, sn, S, pl.tie_grid); }
+        const hipError_t e = hipEventRecord(ctx->ev_ssn_join, ctx->stream2);
+        ctx->stream = main_stream; ctx->stream_main = nullptr;
+        PTX_HIP(ctx, e);
+    }
     { KTimer t(ctx, "ssn_scatter_kernel");
       ssn_scatter_launch(ctx, sn, S); }
-    { KTimer t(ctx, "ssn_ties_kernel");
-      ssn_ties_launch(ctx, sn, S, pl.tie_grid); }
+    if (!ties_async) {
+        KTimer t(ctx, "ssn_ties_kernel");
+        ssn_ties_launch(ctx, sn, S, pl.tie_grid);
+    }
     { KTimer t(ctx, "ssn_local_wave_kernel");
       ssn_local_launch(ctx, sn, S); }
+    if (ties_async) {
+        PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_ssn_join, 0));
+        tie_join.armed = false;   // joined: everything later on the main stream is ordered behind the fill
+    }
     if (pat) {
         KTimer t(ctx, "ssn_heads_kernel");
         ssn_patterns_launch(ctx, sn, S, sub_k, *pat, d_n);

@@ -42,11 +42,18 @@ struct Sn {
     uint32_t G, per;             // partition workgroups per segment, tiles each of them walks
     uint32_t skip_empty;         // segments without LP columns are not read by the histogram pass (option no_absent_skip: 0)
     uint32_t ablate;             // -DSSN_ABLATE builds: parts of ssn_hist_kernel left out (measurements; the results are wrong)
+    uint32_t keys_all;           // 1: every row gets its key words (km, ksp) -- the caller reads them (pantax_hip_sort_rows); 0: only the rows ssn_heads_kernel reads do
+                                 // (sn_keys_needed(), decided by sample_sort_nodes): `ka` is all the step keeps of the sorted rows
     __device__ __forceinline__ uint32_t *w(uint32_t s) const { return ws + (size_t)s * SN_WS_WORDS; }
     __device__ __forceinline__ uint64_t key_word(uint32_t s, uint64_t m) const { return pack_shift >= 0 ? (((uint64_t)s << pack_shift) | m) : m; }
     __device__ __forceinline__ void put(uint32_t s, uint32_t pos, uint64_t m, uint64_t a) const {
         km[pos] = key_word(s, m); ka[pos] = a;
         if (ksp) ksp[pos] = s;
+    }
+    // a row whose key words only ssn_heads_kernel could want: `read` = it lies where that kernel looks (a mixed bucket pair)
+    __device__ __forceinline__ void put_if(bool read, uint32_t s, uint32_t pos, uint64_t m, uint64_t a) const {
+        ka[pos] = a;
+        if (keys_all || read) { km[pos] = key_word(s, m); if (ksp) ksp[pos] = s; }
     }
 };
 
@@ -120,6 +127,17 @@ __device__ __forceinline__ uint32_t tree_rank(uint32_t k) {
 __device__ __forceinline__ uint32_t tree_node(uint32_t rank) {
     const uint32_t q = rank + 1u, tz = (uint32_t)__builtin_ctz(q);
     return (1u << ((uint32_t)SN_LEVELS - 1u - tz)) + ((q >> tz) >> 1);
+}
+
+// Bucket pair j (the even bucket 2j: the rows between splitters j - 1 and j; the tie bucket 2j + 1: the copies of splitter j) is MIXED when its even bucket
+// may hold rows of more than one mask: the two splitters differ in their mask, or one of them does not exist (pair 0, the last pair).  Otherwise every row
+// of bucket 2j has the mask of splitter j (*mv): the local sorts move `a` alone through their networks and store no key words for it (Sn::keys_all == 0),
+// and ssn_heads_kernel, which reads the rows of the mixed pairs only, never looks at it.  The one spelling both sides share.
+__device__ __forceinline__ bool sn_pair_mixed(const ulonglong2 *__restrict__ tree, uint32_t j, uint64_t *mv = nullptr) {
+    if (j == 0 || j >= (uint32_t)SN_NSPLIT) { if (mv) *mv = 0; return true; }
+    const uint64_t ma = tree[tree_node(j - 1)].x, mb = tree[tree_node(j)].x;
+    if (mv) *mv = mb;
+    return ma != mb;
 }
 
 // the tiles [t0, t1) of workgroup g of a segment of n nodes

@@ -65,6 +65,7 @@ __device__ __forceinline__ void wave_sort_regs(uint64_t (&m)[L], uint64_t (&a)[L
 // one bucket of n <= 64 L rows: src (16-byte records) -> sorted -> the segment's output at dst
 template <int L, bool TWO>
 __device__ __forceinline__ void wave_sort_bucket(const Sn &sn, uint32_t s, const ulonglong2 *__restrict__ src, uint32_t n, uint32_t dst, uint64_t mv) {
+    // TWO = the pair is mixed (sn_pair_mixed): its rows keep their key words in every mode
     const uint32_t lane = threadIdx.x & 63;
     uint64_t m[L], a[L];
 #pragma unroll
@@ -77,7 +78,7 @@ __device__ __forceinline__ void wave_sort_bucket(const Sn &sn, uint32_t s, const
 #pragma unroll
     for (int e = 0; e < L; ++e) {
         const uint32_t i = lane * (uint32_t)L + (uint32_t)e;
-        if (i < n) sn.put(s, dst + i, TWO ? m[e] : mv, a[e]);
+        if (i < n) sn.put_if(TWO, s, dst + i, TWO ? m[e] : mv, a[e]);
     }
 }
 
@@ -96,15 +97,11 @@ __global__ void __launch_bounds__(256) ssn_local_wave_kernel(Sn sn) {
     const uint32_t m = st1 - st;
     if (m == 0) return;
     const ulonglong2 *src = sn.rows + o + st;
-    if (m == 1) { if (lane == 0) { const ulonglong2 r = src[0]; sn.put(s, out + st, r.x, r.y); } return; }
     if (m > (uint32_t)SN_WAVE_CAP) { if (lane == 0) w[SN_OFF_MED + atomicAdd(&w[SN_OFF_FLAGS + 2], 1u)] = 2 * j; return; }
     // between two splitters with the same mask every row has that mask: only `a` moves through the network
-    bool one = false;
     uint64_t mv = 0;
-    if (j > 0 && j < (uint32_t)SN_NSPLIT) {
-        const uint64_t ma = tree[tree_node(j - 1)].x, mb = tree[tree_node(j)].x;
-        one = ma == mb; mv = mb;
-    }
+    const bool one = !sn_pair_mixed(tree, j, &mv);
+    if (m == 1) { if (lane == 0) { const ulonglong2 r = src[0]; sn.put_if(!one, s, out + st, r.x, r.y); } return; }
     const uint32_t dst = out + st;
     if (one) {
         if (m <= 64) wave_sort_bucket<1, false>(sn, s, src, m, dst, mv);
@@ -131,12 +128,8 @@ __global__ void __launch_bounds__(256) ssn_local_wave2_kernel(Sn sn) {
         const uint32_t bid = w[SN_OFF_MED + wi], j = bid >> 1;
         const uint32_t st = bucket_start[bid], m = bucket_start[bid + 1] - st;
         if (m > (uint32_t)SN_WAVE_CAP2) { if (lane == 0) w[SN_OFF_BIG + atomicAdd(&w[SN_OFF_FLAGS + 1], 1u)] = bid; continue; }
-        bool one = false;
         uint64_t mv = 0;
-        if (j > 0 && j < (uint32_t)SN_NSPLIT) {
-            const uint64_t ma = tree[tree_node(j - 1)].x, mb = tree[tree_node(j)].x;
-            one = ma == mb; mv = mb;
-        }
+        const bool one = !sn_pair_mixed(tree, j, &mv);
         if (one) wave_sort_bucket<16, false>(sn, s, sn.rows + o + st, m, out + st, mv);
         else wave_sort_bucket<16, true>(sn, s, sn.rows + o + st, m, out + st, mv);
     }
@@ -156,9 +149,11 @@ __global__ void __launch_bounds__(256) ssn_local_kernel(Sn sn) {
         return;
     }
     const uint32_t *bucket_start = w + SN_OFF_START;
+    const ulonglong2 *tree = reinterpret_cast<const ulonglong2 *>(w + SN_OFF_TREE);
     const uint32_t n_work = w[SN_OFF_FLAGS + 1];
     for (uint32_t wi = blockIdx.x; wi < n_work; wi += gridDim.x) {
         const uint32_t bid = w[SN_OFF_BIG + wi];
+        const bool mixed = sn_pair_mixed(tree, bid >> 1);   // (both networks here move whole keys; what is left out is the store of the key words)
         const uint32_t st = bucket_start[bid], m = bucket_start[bid + 1] - st;
         const ulonglong2 *src = sn.rows + o + st;
         const uint32_t dst = out + st;
@@ -171,7 +166,7 @@ __global__ void __launch_bounds__(256) ssn_local_kernel(Sn sn) {
             }
             __syncthreads();
             bitonic2<256>(km, ka, N);
-            for (uint32_t i = threadIdx.x; i < m; i += 256) sn.put(s, dst + i, km[i], ka[i]);
+            for (uint32_t i = threadIdx.x; i < m; i += 256) sn.put_if(mixed, s, dst + i, km[i], ka[i]);
             continue;
         }
         // A bucket of more than SN_CAP rows (an unrepresentative sample; every bucket of a segment of millions of rows): the network runs
@@ -201,7 +196,7 @@ __global__ void __launch_bounds__(256) ssn_local_kernel(Sn sn) {
                 __syncthreads();
             }
         }
-        for (uint32_t i = threadIdx.x; i < m; i += 256) { const ulonglong2 r = buf[i]; sn.put(s, dst + i, r.x, r.y); }
+        for (uint32_t i = threadIdx.x; i < m; i += 256) { const ulonglong2 r = buf[i]; sn.put_if(mixed, s, dst + i, r.x, r.y); }
     }
 }
 }  // namespace

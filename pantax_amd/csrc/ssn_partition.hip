@@ -129,7 +129,9 @@ __global__ void __launch_bounds__(256) ssn_ties_kernel(Sn sn) {
             const uint32_t a = max(s_start[q], r0), e = min(s_start[q + 1], r1);
             if (e <= a) continue;                                // (workgroup-uniform; a non-empty odd bucket has j < SN_NSPLIT)
             const ulonglong2 key = s_key[(q - qb) >> 1];
-            for (uint32_t i = a + threadIdx.x; i < e; i += 256) sn.put(s, out + i, key.x, key.y);
+            // (keys_all == 0: `a` alone -- of a tie bucket ssn_heads_kernel wants the first row's mask at most, and takes it from the splitter tree)
+            if (sn.keys_all) for (uint32_t i = a + threadIdx.x; i < e; i += 256) sn.put(s, out + i, key.x, key.y);
+            else for (uint32_t i = a + threadIdx.x; i < e; i += 256) sn.ka[out + i] = key.y;
         }
     }
 }

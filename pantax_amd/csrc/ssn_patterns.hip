@@ -24,31 +24,53 @@ __global__ void __launch_bounds__(256) ssn_heads_kernel(Sn sn, uint32_t *__restr
     uint32_t cnt = 0;
     if (n != 0 && (!small || wave == 0)) {
         ulonglong2 *heads = sn.rows + o + (small ? 0u : start[2 * HP * wave]);   // {mask word as stored, first row of the run}
-        auto scan_rows = [&](uint32_t r0, uint32_t r1) {      // rows [r0, r1) of the output, in order
+        // rows [r0, r1) of the output, in order.  Only key words that were STORED may be read (Sn::keys_all == 0: those of the small segments and of the even
+        // buckets of mixed pairs), so the caller says what it knows from the splitters: pm0 = the mask word of row r0 - 1 (used when r0 > out), and row
+        // `tie` (~0u: none) has the mask word tm.  Every other km read here is a row of [r0, r1) other than `tie`.
+        auto scan_rows = [&](uint32_t r0, uint32_t r1, uint64_t pm0, uint32_t tie, uint64_t tm) {
             for (uint32_t base = r0; base < r1; base += 64) {
                 const uint32_t i = base + lane;
                 const bool in = i < r1;
-                const uint64_t m = in ? sn.km[i] : 0ull, pm = (in && i > out) ? sn.km[i - 1] : 0ull;
+                const uint64_t m = in ? (i == tie ? tm : sn.km[i]) : 0ull, pm = (in && i > out) ? (i == r0 ? pm0 : sn.km[i - 1]) : 0ull;
                 const bool head = in && (i == out || m != pm);
                 const uint64_t bal = __ballot(head);
                 if (head) heads[cnt + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = make_ulonglong2(m, (uint64_t)i);
                 cnt += (uint32_t)__popcll(bal);
             }
         };
-        if (small) scan_rows(out, out + n);                   // a small segment has no splitters
+        if (small) scan_rows(out, out + n, 0ull, ~0u, 0ull);  // a small segment has no splitters (and all its key words: r0 == out, no row in front)
         else {
             const ulonglong2 *tree = reinterpret_cast<const ulonglong2 *>(w + SN_OFF_TREE);
             const uint32_t j = HP * wave + (lane < (uint32_t)HP ? lane : 0u);
-            bool c = j == 0 || j == (uint32_t)SN_NLEAF - 1;
-            if (!c) c = tree[tree_node(j)].x != tree[tree_node(j - 1)].x;
+            const bool c = sn_pair_mixed(tree, j);            // the pairs whose even bucket the local sorts stored with key words
             uint64_t bal = __ballot(c && lane < (uint32_t)HP);
             while (bal) {
                 const uint32_t jj = HP * wave + (uint32_t)__builtin_ctzll(bal);
                 bal &= bal - 1;
                 // the odd bucket of the pair holds copies of ONE key (splitter jj): a head can only be its first row -- the rest is not read (round 6:
                 // with fifty strains nearly every splitter changes the mask, and a tie bucket of 1e5 rows kept one wave reading for the whole 0.43 ms)
-                const uint32_t e0 = start[2 * jj + 1], e1 = start[2 * jj + 2];
-                scan_rows(out + start[2 * jj], out + (e1 > e0 ? e0 + 1u : e1));
+                // -- and that row's mask is the splitter's, so it comes from the tree (the tie fill stores no key words where nothing else reads them).
+                const uint32_t b0 = start[2 * jj], e0 = start[2 * jj + 1], e1 = start[2 * jj + 2];
+                const bool tie = e1 > e0;                     // (then jj < SN_NSPLIT: the last odd bucket stays empty)
+                if (!tie && e0 == b0) continue;
+                const uint64_t tm = tie ? sn.key_word(s, tree[tree_node(jj)].x) : 0ull;
+                // The row in front of the range, r0 - 1 (when the segment has one: b0 > 0).  It is the last row of the nearest non-empty bucket below 2 jj.
+                // As a rule that is the tie bucket 2 jj - 1: splitter jj - 1 is a sampled row, and the node pass files that very node as equal to it.  The
+                // bucket is empty only when splitter jj - 1 repeats an earlier splitter as a whole key -- the descent files the equal rows under ONE of the
+                // copies, and the even buckets between copies hold nothing -- or is a pad behind the valid samples.  So walk down over the empty buckets to
+                // the one that holds the row, whichever it is: a tie bucket q has the mask of splitter q / 2 (for a repeated splitter: the same mask, one
+                // of its copies); an even bucket of a pair that is not mixed has the mask of its upper splitter; the even bucket of a mixed pair was stored
+                // with its key words.  No case reads a word that was not written, and none depends on the rule above.
+                uint64_t pm0 = 0ull;
+                if (b0 > 0) {
+                    uint32_t q = 2 * jj - 1;                  // (b0 > 0: jj > 0 and a non-empty bucket below 2 jj exists; the walk is the same in every lane)
+                    while (start[q + 1] == start[q]) --q;
+                    uint64_t mv = 0;
+                    if ((q & 1u) != 0u) pm0 = sn.key_word(s, tree[tree_node(q >> 1)].x);
+                    else if (sn_pair_mixed(tree, q >> 1, &mv)) pm0 = sn.km[out + b0 - 1];
+                    else pm0 = sn.key_word(s, mv);
+                }
+                scan_rows(out + b0, out + e0 + (tie ? 1u : 0u), pm0, tie ? out + e0 : ~0u, tm);
             }
         }
     }

@@ -1,6 +1,7 @@
 // ssn_plan.cpp -- geometry and workspace layout of the node-order row sort (ssn_plan.hpp).  Nothing here touches the device.
 #include "ssn_plan.hpp"
 #include <algorithm>
+#include <cstring>
 
 namespace ptx {
 
@@ -35,6 +36,18 @@ SsnPlan ssn_plan(uint32_t S, uint64_t seg_bound, uint64_t V) {
     p.npart = take(SN_NODE_PARTIAL_WORDS * SG, true);
     p.total_words = at;
     return p;
+}
+
+int ssn_keys_all(const char *option, bool has_patterns) {
+    if (!option || !*option || std::strcmp(option, "auto") == 0) return has_patterns ? 0 : 1;
+    if (std::strcmp(option, "all") == 0) return 1;
+    if (std::strcmp(option, "needed") == 0) return has_patterns ? 0 : -1;
+    return -1;
+}
+
+bool ssn_ties_async(int option, bool clocked, bool on_side_stream, bool have_side_stream) {
+    if (clocked || on_side_stream || !have_side_stream) return false;
+    return option > 0 || (option < 0 && SSN_TIES_ASYNC_AUTO);
 }
 
 }  // namespace ptx

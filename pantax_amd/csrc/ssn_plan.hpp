@@ -26,6 +26,8 @@ constexpr uint32_t SN_TIE_ROWS = 8192;           // consecutive output rows of a
 #define SN_HEAD_PAIRS 64                          // bucket pairs a wave of ssn_heads_kernel looks at (round 6: 16 and 4 measured slower or equal)
 #endif
 constexpr int SN_HP = SN_HEAD_PAIRS, SN_NWH = SN_NLEAF / SN_HP;   // ... and the waves per segment
+constexpr bool SSN_TIES_ASYNC_AUTO = false;      // option ssn_ties_async = -1 (ssn_ties_async() below).  Off: at cfg4 the step gained 0.13 .. 0.2 ms, but in the plain bench
+                                                 // series the ranges of the runs with and without it overlap; not measured on the smaller workloads
 constexpr uint64_t SSN_MAX_SEG = 1ull << 26;   // nodes of one segment (buckets grow with the segment: beyond 4096 rows they are sorted through memory)
 
 // per-segment workspace (u32 words), SN_WS_WORDS apart (a multiple of four: the tree's 16-byte nodes stay aligned)
@@ -58,5 +60,13 @@ struct SsnPlan {
     size_t total_words = 0;
 };
 SsnPlan ssn_plan(uint32_t S, uint64_t seg_bound, uint64_t V);
+
+// Which rows of the sort's output get their key words (Sn::keys_all), from option ssn_keys and whether the sort forms the pattern tables itself.  With the
+// tables the rows' keys have one reader, ssn_heads_kernel, which looks at the mixed bucket pairs only (sn_pair_mixed) and the step keeps the abundances
+// alone; without them (pantax_hip_sort_rows) the keys ARE the result.  1: all, 0: the needed ones, -1: an unknown value, or "needed" without the tables.
+int ssn_keys_all(const char *option, bool has_patterns);
+// The tie fill on the side stream (option ssn_ties_async; -1 = what the measurements of DESIGN.md section 4 decided).  Never while every launch is being
+// clocked (a bracket on the side stream would time the overlap, and the per-kernel table wants the fill's own time), and never from the side stream itself.
+bool ssn_ties_async(int option, bool clocked, bool on_side_stream, bool have_side_stream);
 
 }  // namespace ptx
