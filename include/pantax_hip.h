@@ -497,6 +497,25 @@ int pantax_hip_trio_index_prefetch(pantax_hip_ctx *ctx, pantax_hip_db *db);
  * the mask word on the device (the step's two-word records).  (3, round 3's segmented sort, is gone: PANTAX_HIP_E_INVALID.) */
 int pantax_hip_sort_rows(pantax_hip_ctx *ctx, uint64_t n, uint64_t *k0, uint64_t *k1, uint64_t *k2, int algo);
 
+/* ---- the device primitives under every stage as host-buffer utilities (api_primitives.cpp): each uploads, runs on the ctx's stream, downloads
+ * and synchronises.  They exist so that tests can compare the primitives with a host reference at the shapes the product runs them at.
+ *
+ * scan: out[i] = in[0] + .. + in[i - 1] in 32-bit arithmetic over n items of item_bytes = 1 or 4 bytes; *total_out (may be NULL) = the sum of all,
+ * *tile_items_out (may be NULL) = the items per workgroup the launch used (2048, 8192 or 16384: by n, or what the ctx's option "scan_tile"
+ * forces).  in_place != 0 (4-byte items only): the device scan reads and writes one buffer. */
+int pantax_hip_scan(pantax_hip_ctx *ctx, uint64_t n, const void *in, int item_bytes, int in_place, uint32_t *out, uint32_t *total_out,
+                    uint32_t *tile_items_out);
+/* radix sort: n records of nw = 1, 2 or 3 key words (k0 .. k[nw - 1]; the others NULL) and an optional 32-bit payload (NULL: none), sorted in
+ * place by a stable LSD radix sort over the n_passes digits (k[pass_word[p]] >> pass_shift[p]) & 0xFF, pass 0 the least significant.  n fixes the
+ * launch geometry, n_actual <= n is the record count the device is given: the first n_actual records come back sorted, the others as they went
+ * in (both device sides hold the caller's records beforehand; all n records of the side that holds the result are fetched).
+ * *result_in_b_out (may be NULL) = 1 when the result ended on the second side (an odd number of passes). */
+int pantax_hip_radix_sort(pantax_hip_ctx *ctx, uint64_t n, uint64_t n_actual, int nw, uint64_t *k0, uint64_t *k1, uint64_t *k2, uint32_t *payload,
+                          const int32_t *pass_word, const int32_t *pass_shift, int n_passes, int *result_in_b_out);
+/* fill: a device buffer of buf_bytes is set to the byte `sentinel`, then [off, off + bytes) of it to `byte` by the library's fill (the runtime's
+ * memset below 1 MiB, 16-byte stores from every CU from there on); out[buf_bytes] = the whole buffer afterwards. */
+int pantax_hip_fill(pantax_hip_ctx *ctx, uint64_t buf_bytes, int sentinel, uint64_t off, uint64_t bytes, int byte, uint8_t *out);
+
 /* filter_max_alignment_mt (gaf_filter.rs:44-97, called by alignment.rs:171 on long-read GAFs): per read id
  * keep the line with the largest (matches, identity) if it also has mapq > 20 and span > 1000; one line per id.
  * Parsed and grouped on the device; the kept lines are written in FILE ORDER (the reference's order and its choice

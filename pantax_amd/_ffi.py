@@ -19,6 +19,7 @@ SYMBOLS = [
     "pantax_hip_bin_reads", "pantax_hip_species_profile", "pantax_hip_db_reset", "pantax_hip_abundance_filter",
     "pantax_hip_trio_index", "pantax_hip_trio_get", "pantax_hip_node_coverage",
     "pantax_hip_strain_profile", "pantax_hip_strain_node_stats", "pantax_hip_strain_hap_stats", "pantax_hip_pao_solve", "pantax_hip_pao_solve_batch", "pantax_hip_profile", "pantax_hip_profile_step", "pantax_hip_profile_step_enqueue", "pantax_hip_profile_step_collect", "pantax_hip_trio_index_prefetch", "pantax_hip_sort_rows",
+    "pantax_hip_scan", "pantax_hip_radix_sort", "pantax_hip_fill",
     "pantax_hip_sample_ranks", "pantax_hip_chacha_block", "pantax_hip_gaf_filter", "pantax_hip_db_save_images", "pantax_hip_db_load_images",
     "pantax_hip_gaf_load", "pantax_hip_gaf_load_device", "pantax_hip_reads_load_gaf", "pantax_hip_reads_set_flags", "pantax_hip_gaf_view", "pantax_hip_gaf_free",
     "pantax_hip_graph_load", "pantax_hip_graph_view", "pantax_hip_graph_free", "pantax_hip_format_f64",
@@ -179,6 +180,13 @@ def load():
         _lib.pantax_hip_db_pairs.argtypes = [C.c_void_p, C.POINTER(DbPairsConfig)]
         _lib.pantax_hip_near_miss_rank.restype = C.c_int
         _lib.pantax_hip_near_miss_rank.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        _lib.pantax_hip_scan.restype = C.c_int
+        _lib.pantax_hip_scan.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib.pantax_hip_radix_sort.restype = C.c_int
+        _lib.pantax_hip_radix_sort.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.POINTER(C.c_int)]
+        _lib.pantax_hip_fill.restype = C.c_int
+        _lib.pantax_hip_fill.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
         _lib.pantax_hip_depth_bin.restype = C.c_uint32
         _lib.pantax_hip_depth_bin.argtypes = [C.c_uint64]
         _lib.pantax_hip_depth_bin_range.restype = C.c_int

@@ -171,6 +171,8 @@ struct CtxConfig {
     std::string node_pass;           // "split": the resident step keeps node_cov_stats_kernel + ssn_hist_kernel where it would take the fused node_rows_kernel (tests compare, measurements)
     std::string lad_shape;           // LDS shape of the <= 16-column LAD solver: "" / "auto": compact when the batch has more species than the device has CUs, else roomy
                                      // (lad_shape(), lad.hpp); "roomy" / "compact": that shape for every such launch (tests compare, measurements)
+    std::string scan_tile;           // tile of the chained scan (scan_tile_items(), scan_chained.hpp): "" / "auto": by the number of items (2048 items, 8192 from 2^22 items on, 16384 from
+                                     // 2^26 on unless scan_no_huge); "small" / "big" / "huge": that tile for every scan of the ctx, whatever its size (tests run the big tiles at test sizes)
     std::string ssn_keys;            // node-order row sort: which rows get their key words (species / mask) next to the abundance.  "" / "auto": all of them where the caller
                                      // reads the keys (pantax_hip_sort_rows), only those ssn_heads_kernel reads where the sort forms the pattern tables itself (the step);
                                      // "all" / "needed": that mode ("needed" without pattern tables: PANTAX_HIP_E_INVALID) (tests compare, measurements)

@@ -103,7 +103,7 @@ const OptDesc OPTIONS[] = {
     OPT("covf_shape", O_INT, covf_shape), OPT("cov_xcd", O_INT, cov_xcd), OPT("group_bucket_bits", O_INT, group_bucket_bits), OPT("tv_ablate", O_U32, tv_ablate),
     OPT("cov_ablate", O_U32, cov_ablate), OPT("ssn_ablate", O_U32, ssn_ablate), OPT("no_absent_skip", O_BOOL, no_absent_skip), OPT("node_pass", O_STR, node_pass), OPT("bin_route", O_STR, bin_route), OPT("lad_shape", O_STR, lad_shape), OPT("ssn_debug", O_BOOL, ssn_debug),
     OPT("ssn_keys", O_STR, ssn_keys), OPT("ssn_poison_keys", O_BOOL, ssn_poison_keys), OPT("ssn_ties_async", O_INT, ssn_ties_async),
-    OPT("scan_no_huge", O_BOOL, scan_no_huge), OPT("flag_rank_chained", O_BOOL, flag_rank_chained), OPT("ratio_kernel", O_BOOL, ratio_kernel),
+    OPT("scan_no_huge", O_BOOL, scan_no_huge), OPT("scan_tile", O_STR, scan_tile), OPT("flag_rank_chained", O_BOOL, flag_rank_chained), OPT("ratio_kernel", O_BOOL, ratio_kernel),
     OPT("mask_pass", O_BOOL, mask_pass), OPT("trio_free_at_filter", O_BOOL, trio_free_at_filter), OPT("trio_after_step", O_BOOL, trio_after_step),
 };
 #undef OPT

@@ -15,6 +15,17 @@ namespace ptx {
 constexpr uint64_t SCAN_BIG_N = 1u << 22, SCAN_HUGE_N = 1u << 26;
 constexpr int SCAN_TILE_SMALL = 256 * 8, SCAN_TILE_BIG = 512 * 16, SCAN_TILE_HUGE = 1024 * 16;   // 16384-item tiles from 2^26 items on (round 3: 3.2e8-item scans at cfg4)
 
+// The one place a scan's tile size is decided: the rule above, or the tile the option scan_tile forces on every scan of the ctx whatever n
+// ("small" / "big" / "huge": tests run the big tiles, and the functors fused into them, at test sizes).  0: the option names no tile.
+inline uint32_t scan_tile_items(const CtxConfig &cfg, uint64_t n) {
+    const std::string &opt = cfg.scan_tile;
+    if (opt == "small") return SCAN_TILE_SMALL;
+    if (opt == "big") return SCAN_TILE_BIG;
+    if (opt == "huge") return SCAN_TILE_HUGE;
+    if (!opt.empty() && opt != "auto") return 0;
+    return n >= SCAN_HUGE_N && !cfg.scan_no_huge ? SCAN_TILE_HUGE : n >= SCAN_BIG_N ? SCAN_TILE_BIG : SCAN_TILE_SMALL;
+}
+
 // Single-pass chained scan (decoupled look-back): ONE launch per scan.  A workgroup takes a ticket (tiles are
 // therefore started in order, so the tiles it waits for are already running), scans its tile of SCAN_TILE items,
 // publishes {epoch, flag, value} of the tile in one 64-bit word -- first its aggregate, later its inclusive
@@ -113,8 +124,10 @@ int exclusive_scan_fn(Ctx *ctx, Load load, Store store, uint64_t n, uint32_t *d_
         if (d_total) PTX_HIP(ctx, hipMemsetAsync(d_total, 0, sizeof(uint32_t), ctx->stream));
         return 0;
     }
-    const bool big = n >= SCAN_BIG_N, huge = n >= SCAN_HUGE_N && !ctx->cfg.scan_no_huge;
-    const uint32_t tile_items = huge ? SCAN_TILE_HUGE : big ? SCAN_TILE_BIG : SCAN_TILE_SMALL;
+    const uint32_t tile_items = scan_tile_items(ctx->cfg, n);
+    if (tile_items == 0)
+        return fail(ctx, PANTAX_HIP_E_INVALID, "scan: option scan_tile is \"auto\", \"small\", \"big\" or \"huge\", not \"%s\"", ctx->cfg.scan_tile.c_str());
+    const bool big = tile_items == SCAN_TILE_BIG, huge = tile_items == SCAN_TILE_HUGE;
     const uint32_t nb = (uint32_t)((n + tile_items - 1) / tile_items);
     const size_t need = 2 + 2 * (size_t)nb;   // u32 words: ticket, pad, one u64 per tile
     // one workspace per stream: launches of one stream follow each other, a scan of the side stream may run beside one of the main stream

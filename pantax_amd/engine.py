@@ -725,6 +725,38 @@ class Engine:
         self._check(self.lib.pantax_hip_sort_rows(self.ctx, C.c_uint64(len(k[0])), p(k[0]), p(k[1]), p(k[2]), int(algo)))
         return k
 
+    def scan(self, x, in_place=False):
+        """pantax_hip_scan: the chained exclusive scan of a uint8 or uint32 array in 32-bit arithmetic -> (out uint32 [n], total, items per workgroup of the
+        launch).  in_place (uint32 only): the device scan reads and writes one buffer."""
+        x = np.ascontiguousarray(x)
+        if x.dtype not in (np.uint8, np.uint32):
+            raise TypeError("scan takes uint8 or uint32 items, not %s" % x.dtype)
+        out = np.empty(len(x), dtype=np.uint32)
+        total, tile = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.pantax_hip_scan(self.ctx, len(x), p(x), x.dtype.itemsize, int(bool(in_place)), p(out), C.byref(total), C.byref(tile)))
+        return out, total.value, tile.value
+
+    def radix_sort(self, keys, passes, payload=None, n_actual=None):
+        """pantax_hip_radix_sort: the records (keys[0][i], .. keys[nw - 1][i][, payload[i]]), nw = 1 .. 3, through the stable LSD radix sort over the digits
+        passes = [(word, shift), ..], least significant first.  n_actual (default: all) is the record count the device is given while len(keys[0]) fixes the
+        launch geometry -> (key words, payload or None, True when the result ended on the second side)."""
+        k = [np.ascontiguousarray(w, dtype=np.uint64).copy() for w in keys]
+        n = len(k[0])
+        v = None if payload is None else np.ascontiguousarray(payload, dtype=np.uint32).copy()
+        pw = np.ascontiguousarray([w for w, _ in passes], dtype=np.int32)
+        ps = np.ascontiguousarray([s for _, s in passes], dtype=np.int32)
+        in_b = C.c_int(0)
+        kp = [p(w) for w in k] + [None] * (3 - len(k))
+        self._check(self.lib.pantax_hip_radix_sort(self.ctx, n, n if n_actual is None else int(n_actual), len(k), kp[0], kp[1], kp[2], p(v), p(pw), p(ps), len(passes),
+                                                   C.byref(in_b)))
+        return k, v, bool(in_b.value)
+
+    def fill(self, buf_bytes, off, nbytes, byte, sentinel):
+        """pantax_hip_fill: a device buffer of buf_bytes set to `sentinel`, then [off, off + nbytes) of it to `byte` by the library's fill -> the whole buffer"""
+        out = np.empty(buf_bytes, dtype=np.uint8)
+        self._check(self.lib.pantax_hip_fill(self.ctx, int(buf_bytes), int(sentinel), int(off), int(nbytes), int(byte), p(out)))
+        return out
+
     def strain_node_stats(self):
         """pantax_hip_strain_node_stats: per-species (amax, nvalid, nzsum, nzcnt) of the strain step collected last, unrounded"""
         amax, nzsum = np.zeros(self.S), np.zeros(self.S)

@@ -32,6 +32,11 @@ CASES = [
     # without the node -> haplotype words every mask comes from the path walk and every ratio sum from ratio_kernel
     ("mask_walk", "narrow", {"mask": "walk"}, 0, {"node_cov_stats_kernel", "mask_kernel", "ratio_kernel", "row_emit_kernel"}),
 ]
+# the two fused scans of the step -- the pattern tables behind a whole-row sort (Pat), the a11 sampling (Sample, bracketed as row_sample_kernel) -- again under
+# the 8192- and the 16384-item tile, which the size rule takes only from 2^22 / 2^26 items on (option scan_tile, scan_chained.hpp): same routes, same tables
+SCAN_LABEL = {"defaults": "scan_chained_kernel<Pat>", "nodes_sampled": "row_sample_kernel"}
+CASES += [("%s_scan_%s" % (name, tile), key, dict(options, scan_tile=tile), sample_nodes, expected)
+          for tile in ("big", "huge") for name, key, options, sample_nodes, expected in CASES if name in SCAN_LABEL]
 
 
 @pytest.fixture(scope="module")
@@ -117,3 +122,5 @@ def test_route_and_tables(eng, world, set_opt, name, key, options, sample_nodes,
     if sample_nodes:
         assert max(stats["n_rows"]) == sample_nodes          # (a11 really sampled)
     assert ran & LABELS == expected, sorted(ran & LABELS)
+    if "scan_tile" in options:
+        assert SCAN_LABEL[name.split("_scan_")[0]] in ran, sorted(ran)

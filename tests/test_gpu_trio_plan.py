@@ -32,6 +32,10 @@ CASES = [
     ("mixed_first", "mixed", {}, False, {VISIT, BLOCK, PREFIX, ROWS, SCAN_SLOW, LOOKUP, CANON}),
     ("mixed_rebuild", "mixed", {}, True, {FILE, BLOCK, SCAN_SLOW, LOOKUP, CANON}),
 ]
+# the three fused scans of the build (GroupCount, TrioFirst, SlowFirst) again under the 8192- and the 16384-item tile, which the size rule takes only from
+# 2^22 / 2^26 items on (option scan_tile, scan_chained.hpp): same routes, same tables
+CASES += [("%s_scan_%s" % (name, tile), key, dict(options, scan_tile=tile), rebuild, expected)
+          for tile in ("big", "huge") for name, key, options, rebuild, expected in CASES if name in ("prefix_chained", "rows_path", "mixed_first")]
 
 
 @pytest.fixture(scope="module")
