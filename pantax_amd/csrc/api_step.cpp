@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 #include "lad.hpp"
+#include "ssn_plan.hpp"
 
 using namespace ptx;
 
@@ -29,6 +30,9 @@ void copy_species_out(void *arg) {   // runs right after the step's single wait
 int step_enqueue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const double *avg_len, const pantax_hip_step_config *cfg) {
     if (db->d_node_rec.p == nullptr) return fail(ctx, PANTAX_HIP_E_STATE, "profile_step: the db was uploaded without graphs (ranges only)");
     if (db->step_inflight >= 2) return fail(ctx, PANTAX_HIP_E_STATE, "profile_step_enqueue: two steps of this db are already in flight; collect one first");
+    // (an option the fused node pass would refuse in the middle of the step, behind the coverage pass: refused here, before anything is enqueued)
+    if (ssn_node_bits(ctx->cfg.node_bits.c_str(), ctx->cfg.node_bits_words) < 0)
+        return fail(ctx, PANTAX_HIP_E_INVALID, "profile_step: option node_bits is \"range\" or \"gather\" and node_bits_words 0, 1 or 2, not \"%s\" and %d", ctx->cfg.node_bits.c_str(), ctx->cfg.node_bits_words);
     const uint32_t S = db->S;
     const int slot = db->step_enq;
     // debug aid (PANTAX_HIP_TRACE): host time of the sections of an enqueue that took more than 2 ms

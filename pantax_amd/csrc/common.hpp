@@ -169,6 +169,9 @@ struct CtxConfig {
     std::string bin_route;           // "walk": the binning pass of resident reads finds a walk's smallest and largest id by reading the walk (bin_slots_kernel) where it would take
                                      // them from the record filed at upload (bin_mm_kernel; "minmax" or empty) (tests compare, measurements)
     std::string node_pass;           // "split": the resident step keeps node_cov_stats_kernel + ssn_hist_kernel where it would take the fused node_rows_kernel (tests compare, measurements)
+    std::string node_bits;           // fused node pass, a node's bit-vector words: "" / "range": an item's stretch of the bit vector is loaded whole with the streams and served by wave
+                                     // shuffles; "gather": every node loads its own words behind the scan of the lengths (tests compare, measurements)
+    int node_bits_words = 0;         // words a lane holds of an item's stretch: 0 (= 2) / 2: 4 096 bits an item, 1: 2 048 -- a longer item gathers (tests: 1, so that ordinary graphs take both ways)
     std::string lad_shape;           // LDS shape of the <= 16-column LAD solver: "" / "auto": compact when the batch has more species than the device has CUs, else roomy
                                      // (lad_shape(), lad.hpp); "roomy" / "compact": that shape for every such launch (tests compare, measurements)
     std::string scan_tile;           // tile of the chained scan (scan_tile_items(), scan_chained.hpp): "" / "auto": by the number of items (2048 items, 8192 from 2^22 items on, 16384 from

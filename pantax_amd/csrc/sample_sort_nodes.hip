@@ -55,6 +55,8 @@ int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const ui
 
     const int keys_all = ssn_keys_all(ctx->cfg.ssn_keys.c_str(), pat != nullptr);
     if (keys_all < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: option ssn_keys=%s%s", ctx->cfg.ssn_keys.c_str(), pat ? "" : " (a sort whose caller reads the keys stores all of them)");
+    const int node_bits = ssn_node_bits(ctx->cfg.node_bits.c_str(), ctx->cfg.node_bits_words);
+    if (node_bits < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "sample_sort_nodes: option node_bits is \"range\" or \"gather\" and node_bits_words 0, 1 or 2, not \"%s\" and %d", ctx->cfg.node_bits.c_str(), ctx->cfg.node_bits_words);
 
     const SsnPlan pl = ssn_plan(S, seg_bound, V);
     Sn sn;
@@ -93,7 +95,7 @@ int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const ui
         // i.e. behind this launch; the event the next step's index rebuild waits for (ev_trio_free) was recorded before the sort and concerns the trio
         // tables only, which nothing here reads.
         KTimer t(ctx, "node_rows_kernel");
-        ssn_node_rows_launch(ctx, sn, S, haps->max_haps);
+        ssn_node_rows_launch(ctx, sn, S, haps->max_haps, node_bits);
     } else {
         KTimer t(ctx, "ssn_hist_kernel");
         ssn_hist_launch(ctx, sn, S, haps != nullptr, haps ? haps->max_haps : 0u);

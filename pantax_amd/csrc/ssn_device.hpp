@@ -41,7 +41,7 @@ struct Sn {
     int pack_shift;
     uint32_t G, per;             // partition workgroups per segment, tiles each of them walks
     uint32_t skip_empty;         // segments without LP columns are not read by the histogram pass (option no_absent_skip: 0)
-    uint32_t ablate;             // -DSSN_ABLATE builds: parts of ssn_hist_kernel left out (measurements; the results are wrong)
+    uint32_t ablate;             // -DSSN_ABLATE / -DNODE_ROWS_ABLATE builds: parts of ssn_hist_kernel / node_rows_kernel left out (measurements; the results are wrong)
     uint32_t keys_all;           // 1: every row gets its key words (km, ksp) -- the caller reads them (pantax_hip_sort_rows); 0: only the rows ssn_heads_kernel reads do
                                  // (sn_keys_needed(), decided by sample_sort_nodes): `ka` is all the step keeps of the sorted rows
     __device__ __forceinline__ uint32_t *w(uint32_t s) const { return ws + (size_t)s * SN_WS_WORDS; }
@@ -168,14 +168,22 @@ __device__ __forceinline__ void bitonic2(uint64_t *km, uint64_t *ka, uint32_t N)
 #else
 #define SSN_ABL(b) false
 #endif
+// -DNODE_ROWS_ABLATE + the same option: parts of node_rows_kernel left out -- 1 no bit-vector loads (covered bases of a node without a full-node flag: 0),
+// 2 no tree descent (measurements; the results are wrong)
+#ifdef NODE_ROWS_ABLATE
+#define NRK_ABL(b) ((sn.ablate & (b)) != 0u)
+#else
+#define NRK_ABL(b) false
+#endif
 
 // ---- host side: the stages, each in the file that holds its kernels.  All enqueue on ctx->stream, S = the number of segments (grid.y or grid.x of
 // every launch); the entry point times them under its KTimer labels and asks for the launch error once, at the end ----
 // ssn_sample.hip: ssn_gather_kernel + ssn_sample_kernel<fused>
 void ssn_sample_launch(Ctx *ctx, const Sn &sn, uint32_t S, bool fused);
 // ssn_node_pass.hip: the resident step's one pass (node_rows_kernel + node_rows_final_kernel), or its two-kernel twin ssn_hist_kernel<haps>;
-// max_haps sizes the column tables in dynamic LDS
-void ssn_node_rows_launch(Ctx *ctx, const Sn &sn, uint32_t S, uint32_t max_haps);
+// max_haps sizes the column tables in dynamic LDS; node_bits (ssn_node_bits(), ssn_plan.hpp): 0 every node gathers its bit-vector words, 1 / 2 an item's
+// stretch of the bit vector is loaded whole, that many words a lane
+void ssn_node_rows_launch(Ctx *ctx, const Sn &sn, uint32_t S, uint32_t max_haps, int node_bits);
 void ssn_hist_launch(Ctx *ctx, const Sn &sn, uint32_t S, bool haps, uint32_t max_haps);
 // ssn_partition.hip: bucket starts and the segments' first output rows (*d_n = the row count); the travelling rows into their buckets; the tie buckets
 // as fills (tie_grid: SsnPlan's)

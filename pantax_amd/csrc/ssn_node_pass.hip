@@ -180,6 +180,23 @@ __global__ void __launch_bounds__(256) ssn_hist_kernel(Sn sn) {
 // sums of path_cov_ratio: a node without a column (empty mask), or one a step covered whole (flag), does not fetch its bit-vector words at all.
 constexpr int SN_HALF = SN_ITEMS >= 8 ? SN_ITEMS / 2 : SN_ITEMS;
 static_assert(SN_ITEMS % SN_HALF == 0, "whole halves");
+// NB (options node_bits / node_bits_words; ssn_node_bits(), ssn_plan.hpp): where a node's bit-vector words come from.
+//   0 ("gather"): every node that has a consumer for its count loads its first, last and interior words itself, behind the scan of the lengths -- a
+//      second round trip to memory (and one per interior word) that practically every half pays in full: among its 256 nodes one nearly always counts.
+//   1, 2 ("range", the default: 2): the words of an item's 64 consecutive nodes are ONE contiguous stretch of the bit vector, from bit_off of the item's
+//      first node to bit_off of the node behind its last (the array has V + 1 entries).  Both ends are wave-uniform and DB-static: lane l & 7 of a wave
+//      requests end (l & 1) of item (l >> 1) of the COMING half at the top of a half (the first half's: beside the tree copy), and they move to scalar
+//      registers where the half's streams have arrived -- two VGPRs.  Lane l then loads word l (and word 64 + l with NB = 2) of each stretch IN FRONT of
+//      the four streams (a scheduling barrier keeps the order), so the half's first wait covers them: one level of the dependent chain is gone, and the
+//      gathers are one or two coalesced requests per item.  Served from registers: the words' prefix of set bits (DPP scan, no LDS) and the word a node
+//      starts in come from the lane that holds them by two shuffles (ds_bpermute; four with NB = 2); the set bits below the node's first bit follow,
+//      and a node's covered bases are the NEXT lane's value minus its own (DPP shift; the last lane's neighbour is the stretch's end, wave-uniform) --
+//      interior words need no loop.  An item whose stretch is longer than 64 NB words (2 048 / 4 096 bits) takes the gather loads instead
+//      (wave-uniform), so any graph stays exact.  Every shuffle runs with all lanes of the wave active, under wave-uniform conditions only.
+// Which nodes are counted and the order of every sum are the same for all three: the covered bases are integers.
+constexpr int SN_HALVES = SN_ITEMS / SN_HALF;
+static_assert(2 * SN_HALF <= 64, "a lane per end of the half's items");
+template <int NB>
 __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
     __shared__ ulonglong2 tree[SN_NLEAF];
     __shared__ uint32_t s_hist[SN_NBUCKET];
@@ -212,6 +229,16 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
     }
     const ulonglong2 *gt = reinterpret_cast<const ulonglong2 *>(w + SN_OFF_TREE);
     __shared__ uint32_t s_nstage;
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) << 6;
+    constexpr int HALF = SN_HALF;                                // items in flight together
+    // NB: this lane's end of the items of half q of the segment (a half is HALF * 256 consecutive nodes; behind the segment's end: the end itself, an empty stretch)
+    auto end_of = [&](uint32_t q) -> uint64_t {
+        const uint32_t i = q * (uint32_t)(HALF * 256) + (uint32_t)((lane >> 1) % HALF) * 256u + wave64 + (uint32_t)(lane & 1) * 64u;
+        return sn.fz.bit_off[o + (i < n ? i : n)];
+    };
+    uint64_t endv = 0;
+    if (NB && t0 < t1) endv = end_of(t0 * (uint32_t)SN_HALVES);
     for (int i = threadIdx.x; i < SN_NBUCKET; i += 256) s_hist[i] = 0;
     if (threadIdx.x == 0) s_nstage = 0;
     if (t0 < t1) for (int i = threadIdx.x; i < SN_NLEAF; i += 256) tree[i] = gt[i];
@@ -229,13 +256,13 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
         s_dyn_tab[b * 256 + threadIdx.x] = e;
     }
     __syncthreads();
+    uint64_t eb[2 * HALF];                                       // NB: the ends of the coming half's items (wave-uniform: scalar registers)
+#pragma unroll
+    for (int k = 0; k < 2 * HALF; ++k) eb[k] = NB ? lane_get(endv, k) : 0ull;
     unsigned long long c8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, l8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const uint32_t stage0 = o + t0 * SN_TILE;                    // (the staged rows: see ssn_hist_kernel)
-    const int lane = threadIdx.x & 63;
-    const uint32_t wave64 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) << 6;
     double cacc = 0.0;                                           // abundances of this thread's nodes with an empty mask
     NodeAcc nacc;                                                // statistics of this thread's nodes
-    constexpr int HALF = SN_HALF;                                // items in flight together
     for (uint32_t t = t0; t < t1; ++t) {
 #pragma unroll
       for (int hb = 0; hb < SN_ITEMS; hb += HALF) {
@@ -246,7 +273,29 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
         {
             unsigned long long bs[HALF];
             uint32_t fw[HALF];
-            uint64_t g0[HALF];
+            uint64_t gb[HALF];                                   // first bit of the wave's 64 nodes (wave-uniform)
+            uint32_t ex[HALF];                                   // ... and of every node, from there
+            uint32_t bw0[HALF], bw1[HALF];                       // NB, an item that fits: words lane and 64 + lane of its stretch; otherwise a node's first and last word
+            bool fits[HALF];                                     // NB: the stretch was loaded (wave-uniform)
+            uint32_t nwv[HALF], tbv[HALF];                       // NB: words and bits of the item's stretch (wave-uniform)
+            if (NB) {                                            // the items' stretches of the bit vector: requested in front of the streams, so the first wait covers them
+#pragma unroll
+                for (int r = 0; r < HALF; ++r) {
+                    const uint64_t b0 = eb[2 * r], b1 = eb[2 * r + 1], w0 = b0 >> 5;
+                    const uint32_t nw = b1 > b0 ? (uint32_t)(((b1 - 1) >> 5) - w0) + 1u : 0u, cap = 64u * (uint32_t)NB;
+                    gb[r] = b0;
+                    nwv[r] = nw;
+                    tbv[r] = (uint32_t)(b1 - b0);
+                    fits[r] = nw <= cap && !NRK_ABL(1u);
+                    // no branch: a lane behind the stretch's last word (or behind the capacity) loads that word again; an empty stretch (behind the segment's end) word 0
+                    const uint32_t top = nw ? (nw < cap ? nw : cap) - 1u : 0u;
+                    const uint32_t *wp = sn.fz.bitmap + (nw ? w0 : 0ull);
+                    bw0[r] = wp[(uint32_t)lane < top ? (uint32_t)lane : top];
+                    bw1[r] = NB > 1 ? wp[(uint32_t)lane + 64u < top ? (uint32_t)lane + 64u : top] : 0u;
+                }
+                endv = end_of(t * (uint32_t)SN_HALVES + (uint32_t)(hb / HALF) + 1u);   // the coming half's ends: a whole half ahead of their use
+                __builtin_amdgcn_sched_barrier(0);               // (these requests stay in front of the streams)
+            }
 #pragma unroll
             for (int r = 0; r < HALF; ++r) {                     // the four streams of the half
                 const uint32_t i = base + (uint32_t)r * 256u;
@@ -256,13 +305,20 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
                 fw[r] = in ? sn.fz.full[(o + i) >> 5] : 0u;
                 mv[r] = in ? sn.hp.node_haps[o + i] : 0ull;
             }
+            if (!NB) {
 #pragma unroll
-            for (int r = 0; r < HALF; ++r) {                     // first bit of the wave's 64 nodes (wave-uniform), then of every node
-                const uint32_t i0 = t * SN_TILE + (uint32_t)(hb + r) * 256u + wave64;
-                g0[r] = i0 < n ? sn.fz.bit_off[o + i0] : 0ull;
+                for (int r = 0; r < HALF; ++r) {                 // first bit of the wave's 64 nodes (wave-uniform)
+                    const uint32_t i0 = t * SN_TILE + (uint32_t)(hb + r) * 256u + wave64;
+                    gb[r] = i0 < n ? sn.fz.bit_off[o + i0] : 0ull;
+                    fits[r] = false; nwv[r] = tbv[r] = 0u;
+                }
             }
 #pragma unroll
-            for (int r = 0; r < HALF; ++r) g0[r] += wave_incl_scan_dpp(lv[r]) - lv[r];   // (a species' bases fit 32 bits: checked at upload)
+            for (int r = 0; r < HALF; ++r) ex[r] = wave_incl_scan_dpp(lv[r]) - lv[r];   // ... then of every node (a species' bases fit 32 bits: checked at upload)
+            if (NB) {                                            // (the streams have arrived, and the ends requested before them)
+#pragma unroll
+                for (int k = 0; k < 2 * HALF; ++k) eb[k] = lane_get(endv, k);
+            }
             bool whole[HALF];
 #pragma unroll
             for (int r = 0; r < HALF; ++r) {                     // haplotype word -> columns
@@ -272,20 +328,44 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
                 mv[r] = m;
                 whole[r] = (fw[r] >> ((o + base + (uint32_t)r * 256u) & 31u)) & 1u;   // a step covered the whole node: a flag instead of marked bits
             }
-            uint32_t bw0[HALF], bw1[HALF];                       // first and last bit-vector word of every node that has a consumer for its count: independent loads, issued together
 #pragma unroll
-            for (int r = 0; r < HALF; ++r) {
-                const bool count = lv[r] != 0u && mv[r] != 0ull && !whole[r];   // (l = 0 behind the segment's end)
-                bw0[r] = count ? sn.fz.bitmap[g0[r] >> 5] : 0u;
-                bw1[r] = count ? sn.fz.bitmap[(g0[r] + lv[r] - 1) >> 5] : 0u;
+            for (int r = 0; r < HALF; ++r) {                     // gather: first and last bit-vector word of every node that has a consumer for its count: independent loads, issued together
+                if (NB && fits[r]) continue;                     // (wave-uniform)
+                const bool count = lv[r] != 0u && mv[r] != 0ull && !whole[r] && !NRK_ABL(1u);   // (l = 0 behind the segment's end)
+                const uint64_t g0 = gb[r] + ex[r];
+                bw0[r] = count ? sn.fz.bitmap[g0 >> 5] : 0u;
+                bw1[r] = count ? sn.fz.bitmap[(g0 + lv[r] - 1) >> 5] : 0u;
             }
 #pragma unroll
             for (int r = 0; r < HALF; ++r) {
                 const uint32_t i = base + (uint32_t)r * 256u;
+                const bool count = lv[r] != 0u && mv[r] != 0ull && !whole[r] && !NRK_ABL(1u);
                 uint32_t c = whole[r] ? lv[r] : 0u;
-                if (lv[r] != 0u && mv[r] != 0ull && !whole[r]) {
-                    const uint64_t g1 = g0[r] + lv[r], w0 = g0[r] >> 5, w1 = (g1 - 1) >> 5;
-                    const uint32_t m0 = 0xFFFFFFFFu << (g0[r] & 31), m1 = 0xFFFFFFFFu >> (31 - (uint32_t)((g1 - 1) & 31));
+                if (NB && fits[r]) {                             // (wave-uniform: every lane takes part in the shuffles)
+                    // E = the set bits of the stretch below the node's first bit, from the words' prefix of set bits (DPP scan) and the word the bit lies in, both
+                    // fetched from the lane that holds them.  The nodes of a wave follow each other in the bit vector, so a node's covered bases are the NEXT
+                    // lane's E minus its own, and the last lane's neighbour is the stretch's end (wave-uniform): no loop over interior words, no last word
+                    const uint32_t nw = nwv[r], last = nw ? nw - 1u : 0u;
+                    const uint32_t q0 = (uint32_t)lane < nw ? __popc(bw0[r]) : 0u, s0 = wave_incl_scan_dpp(q0);
+                    uint32_t q1 = 0u, s1 = 0u;
+                    if (NB > 1) { q1 = (uint32_t)lane + 64u < nw ? __popc(bw1[r]) : 0u; s1 = wave_incl_scan_dpp(q1) + lane_get(s0, 63); }
+                    const uint32_t f0 = ((uint32_t)gb[r] & 31u) + ex[r], j0 = f0 >> 5;   // bits from the stretch's first word on
+                    uint32_t x = (uint32_t)__shfl((int)bw0[r], (int)(j0 & 63u)), px = (uint32_t)__shfl((int)(s0 - q0), (int)(j0 & 63u));
+                    if (NB > 1) {
+                        const uint32_t y = (uint32_t)__shfl((int)bw1[r], (int)(j0 & 63u)), py = (uint32_t)__shfl((int)(s1 - q1), (int)(j0 & 63u));
+                        if (j0 & 64u) { x = y; px = py; }
+                    }
+                    // the end: the prefix of the last word less its bits behind the stretch's last bit (they are the next item's)
+                    const uint32_t fe = ((uint32_t)gb[r] & 31u) + tbv[r];
+                    uint32_t wl = lane_get(bw0[r], (int)(last & 63u)), sl = lane_get(s0, (int)(last & 63u));
+                    if (NB > 1 && last >= 64u) { wl = lane_get(bw1[r], (int)(last & 63u)); sl = lane_get(s1, (int)(last & 63u)); }
+                    const uint32_t ce = sl - (uint32_t)__popc(wl & ~(0xFFFFFFFFu >> (31u - ((fe - 1u) & 31u))));
+                    const uint32_t e = j0 >= nw ? ce : px + (uint32_t)__popc(x & ((1u << (f0 & 31u)) - 1u));   // (a lane behind the segment's end, or a node that starts where the stretch ends)
+                    const uint32_t cc = wave_shl1(e, ce) - e;
+                    if (count) c = cc;
+                } else if (count) {
+                    const uint64_t g0 = gb[r] + ex[r], g1 = g0 + lv[r], w0 = g0 >> 5, w1 = (g1 - 1) >> 5;
+                    const uint32_t m0 = 0xFFFFFFFFu << (g0 & 31), m1 = 0xFFFFFFFFu >> (31 - (uint32_t)((g1 - 1) & 31));
                     c = w0 == w1 ? __popc(bw0[r] & m0 & m1) : __popc(bw0[r] & m0) + __popc(bw1[r] & m1);
                     for (uint64_t ww = w0 + 1; ww < w1; ++ww) c += __popc(sn.fz.bitmap[ww]);   // nodes of more than 33 bases
                 }
@@ -322,11 +402,13 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
             if (av[r] > 0.0 && mv[r] != 0ull) {                  // (nodes behind the segment's end were loaded as zeros)
                 const Key2 key{mv[r], abits};
                 uint32_t k = 1;
+                if (NRK_ABL(2u)) k = (uint32_t)SN_NLEAF + ((uint32_t)(abits >> 30) & (uint32_t)(SN_NLEAF - 1));
+                else
 #pragma unroll
                 for (int l = 0; l < SN_LEVELS; ++l) { const ulonglong2 nd = tree[k]; k = 2u * k + (less2(Key2{nd.x, nd.y}, key) ? 1u : 0u); }
                 const uint32_t lo = k - (uint32_t)SN_NLEAF;   // splitters less than the key
                 uint32_t eq = 0;
-                if (lo < (uint32_t)SN_NSPLIT) { const ulonglong2 nd = tree[tree_node(lo)]; eq = eq2(Key2{nd.x, nd.y}, key) ? 1u : 0u; }
+                if (lo < (uint32_t)SN_NSPLIT && !NRK_ABL(2u)) { const ulonglong2 nd = tree[tree_node(lo)]; eq = eq2(Key2{nd.x, nd.y}, key) ? 1u : 0u; }
                 id = 2u * lo + eq;
                 atomicAdd(&s_hist[id], 1u);
             }
@@ -391,8 +473,11 @@ __global__ void __launch_bounds__(64) node_rows_final_kernel(Sn sn) {
 }
 }  // namespace
 
-void ssn_node_rows_launch(Ctx *ctx, const Sn &sn, uint32_t S, uint32_t max_haps) {
-    hipLaunchKernelGGL(node_rows_kernel, dim3(sn.G, S), dim3(256), (size_t)((max_haps + 7) / 8) * 256 * sizeof(unsigned long long), ctx->stream, sn);
+void ssn_node_rows_launch(Ctx *ctx, const Sn &sn, uint32_t S, uint32_t max_haps, int node_bits) {
+    const size_t lds = (size_t)((max_haps + 7) / 8) * 256 * sizeof(unsigned long long);
+    if (node_bits == 0) hipLaunchKernelGGL(node_rows_kernel<0>, dim3(sn.G, S), dim3(256), lds, ctx->stream, sn);
+    else if (node_bits == 1) hipLaunchKernelGGL(node_rows_kernel<1>, dim3(sn.G, S), dim3(256), lds, ctx->stream, sn);
+    else hipLaunchKernelGGL(node_rows_kernel<2>, dim3(sn.G, S), dim3(256), lds, ctx->stream, sn);
     hipLaunchKernelGGL(node_rows_final_kernel, dim3(S), dim3(64), 0, ctx->stream, sn);
 }
 

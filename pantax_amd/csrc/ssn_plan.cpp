@@ -45,6 +45,13 @@ int ssn_keys_all(const char *option, bool has_patterns) {
     return -1;
 }
 
+int ssn_node_bits(const char *option, int words) {
+    if (words < 0 || words > 2) return -1;
+    if (!option || !*option || std::strcmp(option, "range") == 0) return words ? words : SSN_NODE_BITS_WORDS;
+    if (std::strcmp(option, "gather") == 0) return 0;
+    return -1;
+}
+
 bool ssn_ties_async(int option, bool clocked, bool on_side_stream, bool have_side_stream) {
     if (clocked || on_side_stream || !have_side_stream) return false;
     return option > 0 || (option < 0 && SSN_TIES_ASYNC_AUTO);

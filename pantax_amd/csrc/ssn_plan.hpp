@@ -65,6 +65,10 @@ SsnPlan ssn_plan(uint32_t S, uint64_t seg_bound, uint64_t V);
 // tables the rows' keys have one reader, ssn_heads_kernel, which looks at the mixed bucket pairs only (sn_pair_mixed) and the step keeps the abundances
 // alone; without them (pantax_hip_sort_rows) the keys ARE the result.  1: all, 0: the needed ones, -1: an unknown value, or "needed" without the tables.
 int ssn_keys_all(const char *option, bool has_patterns);
+// Where node_rows_kernel takes a node's bit-vector words from (options node_bits, node_bits_words): 0 every node gathers them ("gather"), 1 / 2 an item's
+// stretch of the bit vector is loaded whole, that many words a lane ("" / "range"; words 0 = the default, SSN_NODE_BITS_WORDS).  -1: an unknown value.
+constexpr int SSN_NODE_BITS_WORDS = 2;
+int ssn_node_bits(const char *option, int words);
 // The tie fill on the side stream (option ssn_ties_async; -1 = what the measurements of DESIGN.md section 4 decided).  Never while every launch is being
 // clocked (a bracket on the side stream would time the overlap, and the per-kernel table wants the fill's own time), and never from the side stream itself.
 bool ssn_ties_async(int option, bool clocked, bool on_side_stream, bool have_side_stream);

@@ -65,6 +65,10 @@ __device__ __forceinline__ void wave_reduce_pair(A &a, B &b, Better better) {
 __device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t fill = 0u) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xF, 0xF, false);
 }
+// ... and towards lower lanes: lane i receives lane i+1's value, lane 63 `fill` (DPP wave_shl:1)
+__device__ __forceinline__ uint32_t wave_shl1(uint32_t v, uint32_t fill = 0u) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x130, 0xF, 0xF, false);
+}
 // the same with a zero for lane 0 through bound_ctrl: no `old` operand, so a chain of shifts needs no register copies
 __device__ __forceinline__ uint32_t wave_shr1z(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xF, 0xF, true); }
 // inclusive prefix sum over the 64 lanes on the DPP path: row_shr 1/2/4/8 inside the 16-lane rows (zero fill), then the
