@@ -737,6 +737,23 @@ int pantax_hip_gaf_load(const char *path, int n_threads, pantax_hip_gaf **out, c
  * a long cs tag is kilobytes to megabytes: far inside the default. */
 int pantax_hip_gaf_load_device(pantax_hip_ctx *ctx, const char *path, pantax_hip_gaf **out);
 int pantax_hip_gaf_view(const pantax_hip_gaf *gaf, pantax_hip_packed_reads *view_out);
+/* What a tokenizer knows about the read ids, and which route the device tokenizer took (read-only; the arrays live as long as the handle).
+ * id_hash = FNV-1a-64 of the id bytes with the final avalanche h ^= h >> 32; h *= 0xd6e8feb86659fd93; h ^= h >> 32 (the key of the
+ * duplicate-id rule, profile.rs:361-437).  The route fields are there for tests: they tell which path a given text was tokenised on and
+ * change nothing.  The first call on a handle that kept id spans copies them into id_off / id_len: not to be raced from two threads. */
+typedef struct {
+    uint64_t n_reads;
+    const uint64_t *id_hash;  /* [R] */
+    const uint64_t *id_off;   /* [R] where the id starts in the file; NULL when the spans were not kept (pantax_hip_reads_load_gaf) */
+    const uint32_t *id_len;   /* [R] its length in bytes; NULL when the spans were not kept */
+    int32_t ids_distinct;     /* 1 = no two reads share an id hash, 0 = some do, -1 = not checked (host tokenizer, empty text) */
+    int32_t id_check;         /* who decided ids_distinct: 0 = nobody (host tokenizer, fewer than two reads), 1 = the hash set filled piece by
+                               * piece, 2 = the sort of all hashes behind the last piece (the set was sized too small for the text) */
+    uint32_t n_pieces;        /* pieces the device tokenizer cut the text into (host tokenizer: 0) */
+    uint32_t n_grow_r;        /* times the joined per-read columns were enlarged with reads already in them */
+    uint32_t n_grow_t;        /* the same for the joined step column with steps already in it */
+} pantax_hip_gaf_ids_view;
+int pantax_hip_gaf_ids(const pantax_hip_gaf *gaf, pantax_hip_gaf_ids_view *view_out);
 /* file -> packed reads RESIDENT in HBM, tokenised on the device, ready for pantax_hip_bin_reads; the walks never
  * visit the host.  The text travels in pieces on an upload stream (pread into a pinned ring on a few host threads) while the
  * piece before is tokenised.  gaf_out (optional) receives the host-side columns (read_len, mapq, flags; its view has

@@ -21,7 +21,7 @@ SYMBOLS = [
     "pantax_hip_strain_profile", "pantax_hip_strain_node_stats", "pantax_hip_strain_hap_stats", "pantax_hip_pao_solve", "pantax_hip_pao_solve_batch", "pantax_hip_profile", "pantax_hip_profile_step", "pantax_hip_profile_step_enqueue", "pantax_hip_profile_step_collect", "pantax_hip_trio_index_prefetch", "pantax_hip_sort_rows",
     "pantax_hip_scan", "pantax_hip_radix_sort", "pantax_hip_fill",
     "pantax_hip_sample_ranks", "pantax_hip_chacha_block", "pantax_hip_gaf_filter", "pantax_hip_db_save_images", "pantax_hip_db_load_images",
-    "pantax_hip_gaf_load", "pantax_hip_gaf_load_device", "pantax_hip_reads_load_gaf", "pantax_hip_reads_set_flags", "pantax_hip_gaf_view", "pantax_hip_gaf_free",
+    "pantax_hip_gaf_load", "pantax_hip_gaf_load_device", "pantax_hip_reads_load_gaf", "pantax_hip_reads_set_flags", "pantax_hip_gaf_view", "pantax_hip_gaf_ids", "pantax_hip_gaf_free",
     "pantax_hip_graph_load", "pantax_hip_graph_view", "pantax_hip_graph_free", "pantax_hip_format_f64",
     "pantax_hip_read_strains", "pantax_hip_strain_cov_track", "pantax_hip_strain_evidence", "pantax_hip_strain_read_support", "pantax_hip_strain_depth",
     "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_strain_near_miss", "pantax_hip_near_miss_rank",
@@ -56,6 +56,12 @@ class PackedReads(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_steps", C.c_uint64), ("step_off", C.c_void_p), ("node_id", C.c_void_p),
                 ("pstart", C.c_void_p), ("pend", C.c_void_p), ("qlen", C.c_void_p), ("mapq", C.c_void_p),
                 ("flags", C.c_void_p)]
+
+
+class GafIdsView(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("id_hash", C.c_void_p), ("id_off", C.c_void_p), ("id_len", C.c_void_p),
+                ("ids_distinct", C.c_int32), ("id_check", C.c_int32), ("n_pieces", C.c_uint32), ("n_grow_r", C.c_uint32),
+                ("n_grow_t", C.c_uint32)]
 
 
 class HapMetrics(C.Structure):

@@ -44,6 +44,27 @@ int pantax_hip_gaf_view(const pantax_hip_gaf *gaf, pantax_hip_packed_reads *v) {
     v->qlen = r.qlen.data(); v->mapq = r.mapq.data(); v->flags = r.flags.data();
     return 0;
 }
+int pantax_hip_gaf_ids(const pantax_hip_gaf *gaf, pantax_hip_gaf_ids_view *v) {
+    if (!gaf || !v) return PANTAX_HIP_E_INVALID;
+    const HostReads &r = gaf->reads;
+    const uint64_t R = r.id_hash.size();
+    const bool spans = R > 0 && r.id_span.size() == R;
+    try {
+        if (spans && gaf->span_off.size() != R) {   // first call: the vector of pairs as two plain arrays
+            gaf->span_off.resize(R); gaf->span_len.resize(R);
+            for (uint64_t i = 0; i < R; ++i) { gaf->span_off[i] = r.id_span[i].first; gaf->span_len[i] = r.id_span[i].second; }
+        }
+    } catch (const std::exception &) {
+        return PANTAX_HIP_E_LIMIT;   // out of host memory
+    }
+    v->n_reads = R;
+    v->id_hash = R ? r.id_hash.data() : nullptr;
+    v->id_off = spans ? gaf->span_off.data() : nullptr;
+    v->id_len = spans ? gaf->span_len.data() : nullptr;
+    v->ids_distinct = r.ids_distinct; v->id_check = r.id_check;
+    v->n_pieces = r.n_pieces; v->n_grow_r = r.n_grow_r; v->n_grow_t = r.n_grow_t;
+    return 0;
+}
 void pantax_hip_gaf_free(pantax_hip_gaf *gaf) { delete gaf; }
 
 int pantax_hip_graph_load(const char *path, int format, pantax_hip_graph **out, const char **err_out) {

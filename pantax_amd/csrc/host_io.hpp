@@ -36,6 +36,10 @@ struct HostReads {
     std::vector<std::pair<uint64_t, uint32_t>> id_span;   // offset/len of read_id in the mapped file (binning report)
     uint64_t n_lines = 0;
     int ids_distinct = -1;                // device tokenizer: 1 = no two reads share an id hash, 0 = some do; -1 = not checked
+    // the route the device tokenizer took (pantax_hip_gaf_ids; read by tests only): pieces tokenised, enlargements of the joined per-read / step
+    // columns with contents to carry over, and who decided ids_distinct (0 = nobody, 1 = the hash set, 2 = sort + dup_count_kernel)
+    uint32_t n_pieces = 0, n_grow_r = 0, n_grow_t = 0;
+    int id_check = 0;
 };
 // tokenises the GAF columns rcls.rs:127-137 selects; keeps the mapping alive in `keep` for id_span
 struct MappedFile {
@@ -49,7 +53,12 @@ std::string parse_gaf(const MappedFile &mf, HostReads &out, int n_threads);
 
 }  // namespace ptx
 // the handle behind pantax_hip_gaf_load / pantax_hip_gaf_load_device
-struct pantax_hip_gaf { ptx::MappedFile mf; ptx::HostReads reads; };
+struct pantax_hip_gaf {
+    ptx::MappedFile mf;
+    ptx::HostReads reads;
+    mutable std::vector<uint64_t> span_off;   // reads.id_span as two plain arrays, filled by the first pantax_hip_gaf_ids
+    mutable std::vector<uint32_t> span_len;
+};
 namespace ptx {
 
 

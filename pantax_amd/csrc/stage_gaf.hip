@@ -264,6 +264,7 @@ struct GafJoined {
     bool set_ok = false;
     uint64_t R = 0, T = 0, cap_r = 0, cap_t = 0;
     std::vector<uint64_t> piece_r0;   // first read of every piece (id spans are piece-local)
+    uint32_t n_grow_r = 0, n_grow_t = 0;   // enlargements that had contents to carry over (HostReads reports them)
 };
 struct GafWork {
     DevBuf<uint32_t> nl_pos, tile_cnt, tile_base, tot, scan_tmp, r32[8], ridx, soff;
@@ -284,11 +285,13 @@ static int joined_reserve(Ctx *ctx, GafJoined &J, uint64_t need_r, uint64_t need
     if (need_t > J.cap_t || !J.o32[1].p) {
         const uint64_t want = std::max<uint64_t>(need_t, J.cap_t + J.cap_t / 2);
         PTX_TRY(grow32(J.o32[1], J.T, want ? want : 1));
+        if (J.T) ++J.n_grow_t;
         J.cap_t = want;
     }
     if (need_r > J.cap_r || !J.o32[0].p) {
         const uint64_t want = std::max<uint64_t>(need_r, J.cap_r + J.cap_r / 2);
         PTX_TRY(grow32(J.o32[0], J.R ? J.R + 1 : 0, want + 1));
+        if (J.R) ++J.n_grow_r;
         for (int k = 2; k < 7; ++k) PTX_TRY(grow32(J.o32[k], J.R, want ? want : 1));
         for (auto &b : J.o8) {
             DevBuf<uint8_t> nb;
@@ -567,8 +570,9 @@ int gaf_tokenize_device(Ctx *ctx, const char *text, uint64_t size, HostReads &ou
     DevBuf<uint32_t> hs_table, dup_cnt;
     uint32_t n_dup = 0;
     if (J.set_ok) {                                     // decided piece by piece, beside the upload
-        if (R > 1) PTX_TRY(download(ctx, &n_dup, J.dup_cnt.p, 1));
+        if (R > 1) { PTX_TRY(download(ctx, &n_dup, J.dup_cnt.p, 1)); out.id_check = 1; }
     } else if (R > 1) {
+        out.id_check = 2;
         J.id_set.release();                             // the set overflowed (16 bytes per read of HBM): gone before the sort's buffers come
 
         PTX_HIP(ctx, hs_a.alloc(R)); PTX_HIP(ctx, hs_b.alloc(R)); PTX_HIP(ctx, hs_table.alloc(sort_table_elems(R))); PTX_HIP(ctx, dup_cnt.alloc(1));
@@ -605,6 +609,7 @@ int gaf_tokenize_device(Ctx *ctx, const char *text, uint64_t size, HostReads &ou
     }
     out.n_lines = R;
     out.ids_distinct = n_dup == 0 ? 1 : 0;
+    out.n_pieces = (uint32_t)NP; out.n_grow_r = J.n_grow_r; out.n_grow_t = J.n_grow_t;
     if (trace) std::fprintf(stderr, "[gaf_tokenize] total inside gaf_tokenize_device      %9.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_enter).count());
     return 0;
 }
@@ -632,7 +637,8 @@ extern "C" int pantax_hip_gaf_load_device(pantax_hip_ctx *ctx, const char *path,
     pantax_hip_gaf *g = new pantax_hip_gaf();
     std::string e = g->mf.open(path);
     if (!e.empty()) { delete g; return fail(ctx, PANTAX_HIP_E_IO, "%s", e.c_str()); }
-    const int rc = gaf_tokenize_device(ctx, g->mf.data, g->mf.size, g->reads, nullptr, g->mf.fd);
+    // the caller keeps its own orchestration: the id spans come along, as they do from the host tokenizer (pantax_hip_gaf_ids)
+    const int rc = gaf_tokenize_device(ctx, g->mf.data, g->mf.size, g->reads, nullptr, g->mf.fd, 0, true, /*want_id_spans=*/true);
     if (rc != 0) { delete g; return rc; }
     *out = g;
     return 0;

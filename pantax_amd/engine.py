@@ -183,10 +183,10 @@ class Engine:
         mapq = np.where((reads.mapq < 0) | (reads.mapq > 254), 255, reads.mapq)
         self.upload_reads(reads.step_off, reads.node_id, reads.pstart, reads.pend, reads.qlen, mapq, flags)
 
-    def load_reads_from_gaf(self, path, columns=True):
+    def load_reads_from_gaf(self, path, columns=True, ids=False):
         """GAF file -> packed reads resident in HBM, tokenised on the device (pantax_hip_reads_load_gaf).
         -> dict(qlen, mapq, flags) of the host-side columns (columns=False: None, nothing is copied out); the walks stay on
-        the device."""
+        the device.  ids=True adds the keys of pantax_amd.io.gaf_ids (id hashes and the tokenizer's route; no id spans on this path)."""
         if self.reads:
             self.lib.pantax_hip_reads_free(self.ctx, self.reads)
             self.reads = None
@@ -204,7 +204,11 @@ class Engine:
             self.R = int(v.n_reads)
             arr = lambda ptr, dt: (np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(self.R,)).copy()
                                    if self.R else np.zeros(0, dtype=dt))
-            return dict(qlen=arr(v.qlen, np.uint32), mapq=arr(v.mapq, np.uint8), flags=arr(v.flags, np.uint8))
+            out = dict(qlen=arr(v.qlen, np.uint32), mapq=arr(v.mapq, np.uint8), flags=arr(v.flags, np.uint8))
+            if ids:
+                from . import io as pio
+                out.update(pio.gaf_ids(self.lib, gaf))
+            return out
         finally:
             self.lib.pantax_hip_gaf_free(gaf)
 

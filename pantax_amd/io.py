@@ -13,9 +13,24 @@ def _arr(ptr, n, dtype):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dtype))), shape=(n,)).copy()
 
 
-def load_gaf(path, n_threads=4, engine=None):
+def gaf_ids(lib, h):
+    """pantax_hip_gaf_ids of a gaf handle -> dict(id_hash uint64 [R], id_off uint64 [R] / id_len uint32 [R] (None where the handle kept no id
+    spans), ids_distinct, id_check, n_pieces, n_grow_r, n_grow_t): what the tokenizer knows about the read ids and the route it took"""
+    v = _ffi.GafIdsView()
+    rc = lib.pantax_hip_gaf_ids(h, C.byref(v))
+    if rc != 0:
+        raise _ffi.PantaxHipError(rc, "pantax_hip_gaf_ids")
+    R = v.n_reads
+    spans = R == 0 or bool(v.id_off)
+    return dict(id_hash=_arr(v.id_hash, R, np.uint64), id_off=_arr(v.id_off, R, np.uint64) if spans else None,
+                id_len=_arr(v.id_len, R, np.uint32) if spans else None, ids_distinct=int(v.ids_distinct), id_check=int(v.id_check),
+                n_pieces=int(v.n_pieces), n_grow_r=int(v.n_grow_r), n_grow_t=int(v.n_grow_t))
+
+
+def load_gaf(path, n_threads=4, engine=None, ids=False):
     """-> dict(step_off, node_id, pstart, pend, qlen, mapq, flags) of numpy arrays (packed layout).
-    engine=None: the host tokenizer; an Engine: the same tokenisation on its GPU (pantax_hip_gaf_load_device)."""
+    engine=None: the host tokenizer; an Engine: the same tokenisation on its GPU (pantax_hip_gaf_load_device).
+    ids=True: the keys of gaf_ids as well."""
     lib = _ffi.load()
     h = C.c_void_p()
     err = C.c_char_p()
@@ -31,9 +46,12 @@ def load_gaf(path, n_threads=4, engine=None):
         v = _ffi.PackedReads()
         lib.pantax_hip_gaf_view(h, C.byref(v))
         R, T = v.n_reads, v.n_steps
-        return dict(step_off=_arr(v.step_off, R + 1, np.uint32), node_id=_arr(v.node_id, T, np.uint32),
-                    pstart=_arr(v.pstart, R, np.uint32), pend=_arr(v.pend, R, np.uint32), qlen=_arr(v.qlen, R, np.uint32),
-                    mapq=_arr(v.mapq, R, np.uint8), flags=_arr(v.flags, R, np.uint8))
+        out = dict(step_off=_arr(v.step_off, R + 1, np.uint32), node_id=_arr(v.node_id, T, np.uint32),
+                   pstart=_arr(v.pstart, R, np.uint32), pend=_arr(v.pend, R, np.uint32), qlen=_arr(v.qlen, R, np.uint32),
+                   mapq=_arr(v.mapq, R, np.uint8), flags=_arr(v.flags, R, np.uint8))
+        if ids:
+            out.update(gaf_ids(lib, h))
+        return out
     finally:
         lib.pantax_hip_gaf_free(h)
 

@@ -471,3 +471,107 @@ def oracle_tables_parallel(sset, threads=8, fr=0.3, fc=0.46, sr=0.85, sd=0.2, mi
     out = [(sp_, hap, m["predicted_coverage"], m["predicted_coverage"] / tot, m) for sp_, hap, m in rows]
     out.sort(key=lambda r: -r[3])
     return species_rows, out, sp
+
+
+# ---------------------------------------------------------------------------------------------
+# read ids of a GAF text and the texts that send the device tokenizer down its rarely taken routes (tests/test_gaf_ids.py,
+# tests/test_gpu_gaf_join.py)
+# ---------------------------------------------------------------------------------------------
+def gaf_id_hash(b):
+    """The id hash of both tokenizers, restated: FNV-1a-64 over the id bytes, then the avalanche h ^= h >> 32; h *= 0xd6e8feb86659fd93; h ^= h >> 32"""
+    m = 0xFFFFFFFFFFFFFFFF
+    h = 0xcbf29ce484222325
+    for c in b:
+        h = ((h ^ c) * 0x100000001b3) & m
+    h ^= h >> 32
+    h = (h * 0xd6e8feb86659fd93) & m
+    h ^= h >> 32
+    return h
+
+
+def gaf_id_spans(text):
+    """(offset, length) in `text` of field 0 of every row: records end at '\\n' (a '\\r' in front of it belongs to the line end), empty lines and lines
+    starting with '@' give no row, the field ends at the first tab or at the line end.  -> (off int64 [R], len int64 [R])"""
+    off, ln = [], []
+    pos = 0
+    for line in text.split(b"\n"):
+        start = pos
+        pos += len(line) + 1
+        if line.endswith(b"\r"):
+            line = line[:-1]
+        if not line or line.startswith(b"@"):
+            continue
+        t = line.find(b"\t")
+        off.append(start)
+        ln.append(len(line) if t < 0 else t)
+    return np.array(off, dtype=np.int64), np.array(ln, dtype=np.int64)
+
+
+def gaf_ids_expected(text):
+    """-> (id_hash uint64 [R], id_off uint64 [R], id_len uint32 [R]) of a GAF text, from the two restatements above"""
+    off, ln = gaf_id_spans(text)
+    h = np.array([gaf_id_hash(text[o:o + n]) for o, n in zip(off.tolist(), ln.tolist())], dtype=np.uint64)
+    return h, off.astype(np.uint64), ln.astype(np.uint32)
+
+
+def gaf_piece_cuts(text, piece_bytes):
+    """[(begin, end)] of the pieces the device tokenizer cuts a text into under the option gaf_piece_bytes: at most piece_bytes each, ending behind the last
+    line end inside (the last piece takes what is left)"""
+    out, off, n = [], 0, len(text)
+    while off < n:
+        end = min(n, off + piece_bytes)
+        if end < n:
+            k = text.rfind(b"\n", off, end)
+            assert k >= 0, "a line longer than a piece"
+            end = k + 1
+        out.append((off, end))
+        off = end
+    return out
+
+
+def gaf_join_line(rid, walk, tail=b""):
+    return b"%s\t150\t0\t150\t+\t%s\t400\t3\t153\t150\t150\t60%s\n" % (rid, walk, tail)
+
+
+def gaf_join_layout(name):
+    """The lines of a text whose density changes from piece to piece (pieces of 65536 bytes), as a list of (read id or None, line): None marks a comment
+    line.  A: 20 reads, a block of comments, 6000 short reads -- a sparse first piece, so the joined columns (sized from it) grow with reads in them and
+    the id hash set (sized from it) overflows.  B: 1500 one-step reads with a long 13th field, then 1500 reads of 100 steps: only the step column grows.
+    C: the 6000 short reads of A alone: uniform, nothing grows, the set decides.  D: lines that shrink in three stages (tails of 400, 100 and 0 bytes):
+    the per-read columns grow twice and the set overflows."""
+    rid = lambda i: b"r%d" % i
+    body = [(rid(100 + i), gaf_join_line(rid(100 + i), b">%d<%d" % (i % 50 + 1, i % 7 + 1))) for i in range(6000)]
+    if name == "A":
+        return ([(rid(i), gaf_join_line(rid(i), b">1>2")) for i in range(20)] + [(None, b"@" + b"x" * 98 + b"\n")] * 600 + body)
+    if name == "B":
+        long_walk = b"".join(b">%d" % (k % 9 + 1) for k in range(100))
+        return ([(rid(i), gaf_join_line(rid(i), b">1", b"\t" + b"c" * 198)) for i in range(1500)]
+                + [(rid(5000 + i), gaf_join_line(rid(5000 + i), long_walk)) for i in range(1500)])
+    if name == "C":
+        return body
+    if name == "D":
+        return ([(rid(i), gaf_join_line(rid(i), b">1", b"\t" + b"c" * 400)) for i in range(300)]
+                + [(rid(1000 + i), gaf_join_line(rid(1000 + i), b">1", b"\t" + b"c" * 100)) for i in range(3000)]
+                + [(rid(10000 + i), gaf_join_line(rid(10000 + i), b">1")) for i in range(12000)])
+    raise KeyError(name)
+
+
+def gaf_join_text(lines, rename=None):
+    """the text of gaf_join_layout lines; rename {read index: new id} replaces the ids of those reads (read index = position among the non-comment lines)"""
+    rename = rename or {}
+    out, r = [], 0
+    for rid, line in lines:
+        if rid is not None:
+            if r in rename:
+                assert line.startswith(rid + b"\t")
+                line = rename[r] + line[len(rid):]
+            r += 1
+        out.append(line)
+    return b"".join(out)
+
+
+def gaf_id_edge_text():
+    """ids of 0 (the line starts with a tab), 1, 7, 8 and 9 bytes, lines without any tab, an id behind CR LF lines; no final line end"""
+    rest = b"\t150\t0\t150\t+\t>3>4\t400\t3\t153\t150\t150\t60\n"
+    return (b"\t150\t0\t150\t+\t>1\t400\t3\t153\t150\t150\t60\n" + b"a" + rest + b"abcdefg" + rest + b"abcdefgh" + rest + b"abcdefghi" + rest
+            + b"notab\n" + b"\t\n" + b"crlf_no_tab\r\n" + b"x\t1\r\n" + b"@c\n" + b"lastline_without_tab")

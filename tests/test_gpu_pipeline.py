@@ -227,6 +227,84 @@ def test_profile_seam_duplicate_read_ids(world):
     assert any(abs(a[2] - b[2]) > 1e-9 for a, b in zip(plain, exp_strain)) or len(plain) != len(exp_strain)
 
 
+def _piece_size_that_overflows_the_id_set(text):
+    """A gaf_piece_bytes (64 KiB .. a quarter of the text) under which the device tokenizer's id hash set is too small for `text`, or None.  Replays the
+    rule of tokenize_piece (stage_gaf.hip): the first piece's rows R0 size the joined per-read columns, max(R0, int(R0 * 1.03 * size / piece size) + 1024);
+    the set gets the first power of two (from 1024) that is at least twice that; it is given up once the reads so far exceed 0.7 of its slots.
+    This only CHOOSES AN INPUT: which route the tokenizer took is asserted on its own counters."""
+    size = len(text)
+    is_row = lambda l: bool(l.rstrip(b"\r")) and not l.startswith(b"@")
+    n_rows = sum(1 for l in text.split(b"\n") if is_row(l))
+    piece = 65536
+    while piece <= size // 4:
+        k = text.rfind(b"\n", 0, piece)
+        if k < 0:
+            return None
+        first = text[:k + 1]
+        r0 = sum(1 for l in first.split(b"\n") if is_row(l))
+        cap_r = max(r0, min(0xFFFFFFFE, int(r0 * (1.03 * size / len(first))) + 1024))
+        slots = 1024
+        while slots < 2 * cap_r:
+            slots <<= 1
+        if n_rows > 0.7 * slots:
+            return piece
+        piece *= 2
+    return None
+
+
+def test_profile_seam_duplicate_read_ids_decided_by_the_hash_sort(world, set_opt):
+    """test_profile_seam_duplicate_read_ids with the duplicates found on the tokenizer's OTHER route: a block of comment lines behind the first 20 reads
+    makes the first piece sparse, the id hash set sized from it overflows, and the verdict "some reads share an id" comes from the sort of all id hashes
+    and dup_count_kernel.  A false "all distinct" there would skip the duplicate-id rule (profile.rs:361-437) and give the plain strain table."""
+    import copy
+    import synthdata as synth
+    from pantax_amd import io as pio
+    sset, root, db, gaf, eng = world
+    rd = copy.copy(sset.reads)
+    R = rd.n_reads
+    _, _, sp = _oracle_tables(sset)
+    ids = ["S0R%d/1" % r for r in range(R)]
+    rng = np.random.default_rng(5)
+    mapped = np.nonzero(sp >= 0)[0]
+    drop = np.zeros(R, bool)
+    n_same = n_mixed = 0
+    for a, b in rng.choice(mapped, size=(3000, 2), replace=False):
+        ids[b] = ids[a]
+        if sp[a] == sp[b]:
+            n_same += 1
+        else:
+            drop[a] = drop[b] = True
+            n_mixed += 1
+    assert n_same > 50 and n_mixed > 50
+    rd.read_id = ids
+    gaf2 = root / "dup_sparse_head.gaf"
+    synth.write_gaf(rd, str(gaf2))
+    lines = gaf2.read_bytes().split(b"\n")
+    text = b"\n".join(lines[:20]) + b"\n" + (b"@" + b"x" * 98 + b"\n") * 3000 + b"\n".join(lines[20:])
+    gaf2.write_bytes(text)
+    piece = _piece_size_that_overflows_the_id_set(text)
+    if piece is None:
+        pytest.skip("no piece size between 64 KiB and a quarter of the file overflows the id hash set of this text")
+    set_opt(eng, "gaf_piece_bytes", str(piece))
+    # the same text through the same tokenizer, where its route can be read: the sort decided, and found duplicates
+    view = pio.load_gaf(gaf2, engine=eng, ids=True)
+    assert view["id_check"] == 2 and view["n_pieces"] > 1, {k: view[k] for k in ("id_check", "ids_distinct", "n_pieces")}
+    exp_species, exp_strain, _ = _oracle_tables(sset, strain_drop=drop)
+    wd = root / "wd_dup_sort"
+    wd.mkdir()
+    cwd = os.getcwd()
+    os.chdir(str(wd))
+    try:
+        eng.profile(str(db), str(wd), str(gaf2))
+    finally:
+        os.chdir(cwd)
+    _check_outputs(str(wd), sset, exp_species, exp_strain)
+    assert view["ids_distinct"] == 0
+    # and the rule changes the answer here: without it the strain table differs
+    _, plain, _ = _oracle_tables(sset)
+    assert any(abs(a[2] - b[2]) > 1e-9 for a, b in zip(plain, exp_strain)) or len(plain) != len(exp_strain)
+
+
 def test_profile_seam_default_sample_limit(world):
     """--sample 500000 (the reference's default, cli.rs:227) leaves species with fewer valid rows alone."""
     sset, root, db, gaf, eng = world
