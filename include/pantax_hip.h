@@ -424,6 +424,43 @@ int pantax_hip_strain_pair_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, cons
                                     uint64_t *pair_off_out /*[S+1]*/, uint64_t pair_cap /* entries pair_out holds */, uint64_t *pair_out /*[pair_off[S]][4]*/,
                                     uint64_t *species_out /*[S][3][4]: total, orphan, core; or NULL*/);
 
+/* ---- model fit per strain (the --strain-fit report; not a stage of the reference): the reports above describe the SAMPLE on sets of nodes; this call
+ * describes the FIT -- how far a table of strains with their predicted coverages is from the sample, node by node.  The strain step's LP has a row only
+ * for a node with coverage (profile.rs:1380-1385), so a strain reported at 8x whose private genome is empty pays nothing for that; and a node that some
+ * but not all reported strains walk is judged by no other report.  Selection, Sel_s, K_s, M(v) and m(v) are exactly those of pantax_hip_strain_evidence:
+ * membership is node-level (a node walked twice counts once), every node of a species is counted once.  Every selection entry carries a weight sel_w, the
+ * coverage predicted for its haplotype (the LP's x_h).
+ *   p(v) = the f64 sum of sel_w over M(v): it starts from +0.0 and adds in ASCENDING species-local haplotype index, whatever the order of sel_hap, with
+ *          plain IEEE-754 additions (no fused operation, no reassociation);
+ *   t(v) = p(v) * (double)node_len[v], one IEEE multiplication;
+ *   E(v) = the bases the table predicts on v, a u64: 0 when !(t > 0);  2^62 when t >= 2^62;  otherwise t rounded to the nearest integer, ties to even;
+ *   b(v) = bases_per_node[v] as pantax_hip_node_coverage leaves it;
+ *   excess(v) = b > E ? b - E : 0 (the sample has more than the table explains);   deficit(v) = E > b ? E - b : 0 (the table predicts more than the sample has);
+ *   blind(v) holds exactly when b == 0 && E > 0: the LP had no row for such a node;
+ *   Q(v) = (1, node_len[v], b, E, excess, deficit, blind ? 1 : 0, blind ? E : 0), eight u64, in the order
+ *          { n_nodes, len, bases, expected, excess, deficit, blind_nodes, blind_expected }.
+ * Every output is a sum of Q(v):
+ *   per selection entry c (haplotype h of species s):   all[c] = sum over v with h in M(v);   private[c] = sum over v with M(v) = {h};
+ *   per species s:   total[s] = sum over every node;   explained[s] = sum over m(v) >= 1;   orphan[s] = sum over m(v) = 0 (there E = 0: excess = bases).
+ * hap_out [C][2][8] = { all, private } of every selection entry in the order of sel_hap; species_out [S][3][8] = { total, explained, orphan } of every
+ * species.  E(v) is a deterministic function of the inputs and the sums are integers: results are exact and independent of any order; a u64 sum that
+ * overflows wraps, as the evidence call's does.  Identities, column by column, modulo 2^64:  bases + deficit == expected + excess in every class;
+ * total == explained + orphan;  blind_expected <= deficit;  columns { n_nodes, len, bases } of all, private, total and orphan equal columns { 0, 1, 3 } of
+ * pantax_hip_strain_evidence on the same selection;  K_s = 1 gives all == private == explained;  all weights zero gives expected == deficit ==
+ * blind_nodes == blind_expected == 0.  Every K_s the evidence call serves is served; an empty selection, or a species without selected haplotypes, is
+ * fine (total == orphan).  State rules of pantax_hip_strain_evidence: PANTAX_HIP_E_STATE behind a resident step and before any coverage pass.
+ * PANTAX_HIP_E_INVALID as in the evidence call (n_species different from the db's, a haplotype index out of range, a haplotype twice within a species),
+ * and for a weight that is NaN, infinite or negative, or a null sel_w with C > 0.  On any error the outputs are left as given.
+ * The option fit_route=walk (pantax_hip_set_option) takes every species' membership from its selected walks, as evidence_route=walk does. */
+typedef struct {
+    uint32_t n_species;       /* must equal the db's */
+    const uint64_t *sel_off;  /* [S+1] species s owns the selection entries [sel_off[s], sel_off[s+1]) */
+    const uint32_t *sel_hap;  /* [C] species-local haplotype index, any order, no repeats within a species */
+    const double *sel_w;      /* [C] predicted coverage of the entry: finite, >= 0 */
+} pantax_hip_fit_set;
+int pantax_hip_strain_fit(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_fit_set *sel,
+                          uint64_t *hap_out /*[C][2][8]: all, private*/, uint64_t *species_out /*[S][3][8]: total, explained, orphan*/);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -695,6 +732,27 @@ typedef struct { /* ProfilingConfig (types.rs:57-91) as plain C; NULL path = ref
 /* A selection whose graphs hold more path steps than one resident db addresses (2^32: BASELINE configs[4] on one GPU) goes through the device in
  * groups of species, one after the other, inside the call -- no limit on the size of the DB other than the device memory a single group needs. */
 int pantax_hip_profile(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg);
+
+/* The sized extension of the pipeline seam.  pantax_hip_profiling_config keeps its size for the callers compiled against it: outputs added after
+ * strain_pair_evidence_file are appended HERE, one field each, and reach the seam through pantax_hip_profile_with_ext.  struct_size is
+ * sizeof(pantax_hip_profile_ext) as the caller's header has it: a field that does not lie wholly inside struct_size reads as off, so a caller built
+ * against an older header keeps working against a newer library; struct_size below 8 or not a multiple of 8 is PANTAX_HIP_E_INVALID.  ext == NULL:
+ * everything here is off, and pantax_hip_profile(ctx, cfg) is pantax_hip_profile_with_ext(ctx, cfg, NULL). */
+typedef struct {
+    uint64_t struct_size;         /* sizeof(pantax_hip_profile_ext) as the caller's header has it */
+    /* --strain-fit: path of the model fit report (pantax_hip_strain_fit over every group of species, right behind the group's evidence sums, on the same
+     * coverage result; NULL, "" or "None" = off).  Sel_s = the species' rows of strain_abundance.txt, sel_w = their unrounded second_sol (the number the
+     * evidence report prints as predicted_coverage).  TSV with a header, long format: species_taxid, strain_taxid, genome_ID, class, n_nodes, len, bases,
+     * expected, excess, deficit, blind_nodes, blind_expected, fit, predicted_coverage.  First the strains in the order of strain_abundance.txt, classes
+     * "all" then "private" each (predicted_coverage = the weight); then every species that went through a strain step, in the order the run took them,
+     * classes "total", "explained", "orphan" with strain_taxid = genome_ID = "-"; "explained" is left out for a species without rows, its
+     * predicted_coverage is the f64 sum of the species' weights in ascending haplotype index; predicted_coverage is "-" on total and orphan.
+     * fit = 1 - (double)(excess + deficit) / (double)(bases + expected) (f64, shortest round-trip digits; "-" when bases + expected = 0): 1 where the
+     * table reproduces the sample on these nodes, 0 where nothing coincides.  Written only by a run that performs the strain step; world_size > 1 or a
+     * sharded ingest with it is PANTAX_HIP_E_INVALID. */
+    const char *strain_fit_file;
+} pantax_hip_profile_ext;
+int pantax_hip_profile_with_ext(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg, const pantax_hip_profile_ext *ext);
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

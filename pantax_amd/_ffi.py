@@ -25,7 +25,7 @@ SYMBOLS = [
     "pantax_hip_graph_load", "pantax_hip_graph_view", "pantax_hip_graph_free", "pantax_hip_format_f64",
     "pantax_hip_read_strains", "pantax_hip_strain_cov_track", "pantax_hip_strain_evidence", "pantax_hip_strain_read_support", "pantax_hip_strain_depth",
     "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_strain_near_miss", "pantax_hip_near_miss_rank",
-    "pantax_hip_db_hap_pairs", "pantax_hip_db_pairs", "pantax_hip_strain_pair_evidence",
+    "pantax_hip_db_hap_pairs", "pantax_hip_db_pairs", "pantax_hip_strain_pair_evidence", "pantax_hip_strain_fit", "pantax_hip_profile_with_ext",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -128,6 +128,15 @@ class EvidenceSet(C.Structure):
     _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p)]
 
 
+class FitSet(C.Structure):
+    _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p), ("sel_w", C.c_void_p)]
+
+
+class ProfileExt(C.Structure):
+    """pantax_hip_profile_ext: the sized extension of ProfilingConfig; struct_size = ctypes.sizeof(ProfileExt)"""
+    _fields_ = [("struct_size", C.c_uint64), ("strain_fit_file", C.c_char_p)]
+
+
 class NearMissSet(C.Structure):
     _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p), ("cand_off", C.c_void_p), ("cand_hap", C.c_void_p)]
 
@@ -182,6 +191,10 @@ def load():
         _lib.pantax_hip_db_hap_pairs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         _lib.pantax_hip_strain_pair_evidence.restype = C.c_int
         _lib.pantax_hip_strain_pair_evidence.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_strain_fit.restype = C.c_int
+        _lib.pantax_hip_strain_fit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FitSet), C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_profile_with_ext.restype = C.c_int
+        _lib.pantax_hip_profile_with_ext.argtypes = [C.c_void_p, C.POINTER(ProfilingConfig), C.POINTER(ProfileExt)]
         _lib.pantax_hip_db_pairs.restype = C.c_int
         _lib.pantax_hip_db_pairs.argtypes = [C.c_void_p, C.POINTER(DbPairsConfig)]
         _lib.pantax_hip_near_miss_rank.restype = C.c_int

@@ -48,7 +48,7 @@ int check_args(Run &run) {
     p.sharded = c.use_comm && cfg->alltoallv != nullptr;
     if (p.sharded && W > 64) return fail(ctx, PANTAX_HIP_E_LIMIT, "profile: the sharded ingest routes reads to at most 64 ranks (world_size %d)", W);
     std::string rep_err;   // the per-strain reports: wanted? one rank and an unsharded ingest; their two parameters (report_plan.cpp)
-    if (!plan_reports(cfg, W, p.sharded, p.rep, rep_err)) return fail(ctx, PANTAX_HIP_E_INVALID, "%s", rep_err.c_str());
+    if (!plan_reports(cfg, W, p.sharded, p.rep, rep_err) || !plan_ext_reports(run.ext, W, p.sharded, p.rep, rep_err)) return fail(ctx, PANTAX_HIP_E_INVALID, "%s", rep_err.c_str());
     p.db_dir = opt(cfg->db); p.wd = opt(cfg->wd); p.out_dir = opt(cfg->output_dir);
     if (p.out_dir.empty()) p.out_dir = p.wd;
     if (!is_dir(p.db_dir)) return fail(ctx, PANTAX_HIP_E_IO, "Specified PanTax database directory '%s' is not a valid directory path", p.db_dir.c_str());
@@ -84,6 +84,8 @@ void rs_skipped(const RunPlan &p) {
         if (p.rep.want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.path[i].c_str());
     for (int i = 0; i < N_PAIR_REPORTS; ++i)
         if (p.rep.pair_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.pair_path[i].c_str());
+    for (int i = 0; i < N_EXT_REPORTS; ++i)
+        if (p.rep.ext_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.ext_path[i].c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
 // ALL species ranges (ranges-only db), counters on the device
@@ -550,9 +552,9 @@ int strain_tables(Run &run, const Ingest &in, const Selection &sn, const ShardRe
 }
 // The phases in order.  `rc` is this rank's status since the last collective (RankComm's rule): PTX_TRY where a phase has ended in the collective
 // that carried it, an assignment where the next collective carries it.
-int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
+int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg, const pantax_hip_profile_ext *ext) {
     PTX_ENTER(ctx);
-    Run run{ctx, cfg, RunPlan(), RankComm{ctx, cfg}, Lap()};
+    Run run{ctx, cfg, ext, RunPlan(), RankComm{ctx, cfg}, Lap()};
     const RunPlan &p = run.p;
     PTX_TRY(check_args(run));
     PTX_TRY(decide_resume(run));                                                             // all-reduce: rank 0's decision
@@ -598,10 +600,10 @@ int profile_impl(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
 }  // namespace
 
 // nothing throws across the boundary: an allocation failure or a parser exception becomes a status + message
-extern "C" int pantax_hip_profile(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) {
+extern "C" int pantax_hip_profile_with_ext(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg, const pantax_hip_profile_ext *ext) {
     if (!ctx || !cfg) return PANTAX_HIP_E_INVALID;
     try {
-        return profile_impl(ctx, cfg);
+        return profile_impl(ctx, cfg, ext);
     } catch (const std::bad_alloc &) {
         return fail(ctx, PANTAX_HIP_E_LIMIT, "profile: out of host memory");
     } catch (const std::exception &e) {
@@ -610,3 +612,4 @@ extern "C" int pantax_hip_profile(pantax_hip_ctx *ctx, const pantax_hip_profilin
         return fail(ctx, PANTAX_HIP_E_STATE, "profile: unknown exception");
     }
 }
+extern "C" int pantax_hip_profile(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg) { return pantax_hip_profile_with_ext(ctx, cfg, nullptr); }

@@ -590,6 +590,21 @@ int pantax_hip_strain_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pan
     return evidence_launch(ctx, db, sel->sel_off, sel->sel_hap, hap_out, species_out);
 }
 
+int pantax_hip_strain_fit(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_fit_set *sel, uint64_t *hap_out, uint64_t *species_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_fit: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_fit", sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_fit", sel->sel_off, sel->sel_hap));
+    const uint64_t C = sel->sel_off[db->S];
+    if (C && !sel->sel_w) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_fit: null sel_w");
+    for (uint64_t c = 0; c < C; ++c)
+        if (!std::isfinite(sel->sel_w[c]) || sel->sel_w[c] < 0.0) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_fit: the weight of selection entry %llu is %g (finite and >= 0)", (unsigned long long)c, sel->sel_w[c]);
+    if ((C && !hap_out) || (db->S && !species_out)) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_fit: null output array");
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_fit"));
+    return fit_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->sel_w, hap_out, species_out);
+}
+
 int pantax_hip_db_hap_pairs(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out,
                             uint64_t *species_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;

@@ -1,6 +1,6 @@
 // pantax-hip -- command-line front end of the pipeline seam.  Takes the profiling flags of the
 // reference CLI (cli.rs:114-164, 222-240; defaults resolved as in main.rs:102-171) and calls
-// pantax_hip_profile, i.e. it stands where `pantax ... --species --strain` calls profile::profile.
+// pantax_hip_profile_with_ext, i.e. it stands where `pantax ... --species --strain` calls profile::profile.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -40,6 +40,11 @@ static void usage() {
             "  --strain-pair-evidence F   pairwise strain evidence: for every two rows of strain_abundance.txt of a species the nodes both walk (class shared)\n"
             "                     and the nodes only the one, only the other walks (only): n_nodes, len, covered, bases, depth, breadth, and whether the\n"
             "                     two are identical, nested or distinct on the graph (one rank only)\n"
+            "  --strain-fit F   model fit: for every row of strain_abundance.txt over the nodes it walks (class all) and the nodes no other reported strain of\n"
+            "                     its species walks (private) the aligned bases, the bases its predicted coverages put there (expected), what the sample has\n"
+            "                     beyond them (excess), what it lacks (deficit) and the part of that on nodes without any coverage (blind), with\n"
+            "                     fit = 1 - (excess + deficit) / (bases + expected); then per species every node (total), the nodes some reported strain walks\n"
+            "                     (explained) and the nodes none walks (orphan) (one rank only)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -65,6 +70,9 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
+    pantax_hip_profile_ext ext;   // the outputs added behind the config's last field
+    memset(&ext, 0, sizeof(ext));
+    ext.struct_size = sizeof(ext);
     pantax_hip_db_pairs_config pairs;
     memset(&pairs, 0, sizeof(pairs));
     pairs.max_distance = -1;
@@ -126,6 +134,7 @@ int main(int argc, char **argv) {
         else if (a == "--strain-near-miss") c.strain_near_miss_file = next();
         else if (a == "--strain-near-miss-top") c.strain_near_miss_top = atoi(next());
         else if (a == "--strain-pair-evidence") c.strain_pair_evidence_file = next();
+        else if (a == "--strain-fit") ext.strain_fit_file = next();
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;
@@ -200,7 +209,7 @@ int main(int argc, char **argv) {
         if (use_rccl && RcclComm::allreduce_sum(&comm, &failed, 1) != 0) { fprintf(stderr, "pantax-hip: rank %d: the exchange behind --filter-gaf failed\n", rank); failed = 1.0; }
         if (failed != 0.0) { if (use_rccl) comm.destroy(id_file); pantax_hip_destroy(ctx); return 1; }
     }
-    rc = pantax_hip_profile(ctx, &c);
+    rc = pantax_hip_profile_with_ext(ctx, &c, &ext);
     if (rc != 0) fprintf(stderr, "pantax-hip: %serror %d: %s\n", use_rccl ? ("rank " + std::to_string(rank) + ": ").c_str() : "", rc, pantax_hip_last_error(ctx));
     if (use_rccl) comm.destroy(id_file);
     pantax_hip_destroy(ctx);

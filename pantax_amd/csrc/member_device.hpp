@@ -9,8 +9,8 @@
 namespace ptx {
 
 // Route 2: node membership in chosen walks as a compact arena -- member_words(K) words per node of a species over its K chosen haplotypes only (bit k = the
-// k-th of them), filled by read_strain_mask_kernel (walk_masks.hip).  Its six users: read_strains_launch and read_support_launch (through rs_table_build),
-// evidence_launch, depth_launch, near_miss_launch (over Sel ++ Cand), hap_pairs_launch.  The object owns the device buffers: it outlives the kernels that read d_mask.
+// k-th of them), filled by read_strain_mask_kernel (walk_masks.hip).  Its seven users: read_strains_launch and read_support_launch (through rs_table_build),
+// evidence_launch, depth_launch, near_miss_launch (over Sel ++ Cand), hap_pairs_launch, fit_launch.  The object owns the device buffers: it outlives the kernels that read d_mask.
 constexpr uint64_t WALK_MASK_TILE = 4096;   // walk positions per tile of the mask pass (one wave)
 struct WalkMaskTile { uint64_t p0, p1, word0; uint32_t nw, k; };   // walk positions [p0, p1) of chosen walk k; its words start at word0 (+ local node * nw)
 struct WalkMasks {
@@ -22,7 +22,7 @@ struct WalkMasks {
     uint64_t add_species(const Db *db, uint32_t s, const uint32_t *haps, uint64_t K);          // -> first word of the species' node masks
     int build(Ctx *ctx, const Db *db);   // after the last row / add_species: zero fill + the pass over the tiles, on ctx->stream
 };
-// What the launchers of the four node passes (evidence, depth, near miss, hap pairs) hold on the device around their kernel: the masks, and one output block [a | b]
+// What the launchers of the five node passes (evidence, depth, near miss, hap pairs, fit) hold on the device around their kernel: the masks, and one output block [a | b]
 struct MemberPass {
     WalkMasks wm;
     DevBuf<unsigned long long> d_out;
@@ -31,6 +31,14 @@ struct MemberPass {
 };
 // first mask word of global node v of the row's species (the row by value: by reference the node kernels' register allocation comes out differently)
 __device__ __forceinline__ uint64_t member_mask_row(const MemberRow r, uint32_t v) { return r.mask_base + (uint64_t)(v - r.node_base) * r.nw; }
+
+// The per-wave LDS counters of the evidence and fit node passes change hands between the wave's lanes (lane 0 adds, every lane zeroes and flushes its own
+// bit): order the accesses inside the wave
+__device__ __forceinline__ void member_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
 
 struct MemberQ { unsigned long long n, len, cov, bases; };
 __device__ __forceinline__ void mq_add(MemberQ &a, bool on, uint32_t len, uint32_t cov, unsigned long long bases) {

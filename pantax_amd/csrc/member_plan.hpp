@@ -1,10 +1,10 @@
-// member_plan.hpp -- "which of the chosen haplotypes of this species walk node v?", the question of the five strain reports (read strains, read support,
-// node evidence, depth, near miss) and of the db's pair sums (hap pairs: six users), decided once on the host as pure functions of plain values:
+// member_plan.hpp -- "which of the chosen haplotypes of this species walk node v?", the question of the six strain reports (read strains, read support,
+// node evidence, depth, near miss, model fit) and of the db's pair sums (hap pairs: seven users), decided once on the host as pure functions of plain values:
 //   route 0 -- nothing chosen;
 //   route 1 -- a species of <= 64 haplotypes whose node -> haplotype words were built at upload (Db::d_node_haps), the call's *_route option not "walk":
 //              word(v) = node_haps[v] & bits, bit = haplotype index; no array of its own;
 //   route 2 -- every other species: ceil(K / 64) words per node over the K chosen haplotypes only, bit = position in the chosen list (WalkMasks, member_device.hpp).
-// The launchers of the six users follow it; nothing else decodes a *_route option, spells the route predicate or sizes a node's words.  Standard
+// The launchers of the seven users follow it; nothing else decodes a *_route option, spells the route predicate or sizes a node's words.  Standard
 // headers only: tests/native/member_plan_check.cpp compiles this with the host compiler alone; MemberRow is also what the kernels read.
 #pragma once
 #include <cstdint>
@@ -24,7 +24,7 @@ struct MemberRow {
     uint32_t K;                // chosen haplotypes
 };
 template <class T> constexpr T member_words(T K) { return (K + 63) / 64; }   // words that hold K bits
-// route 1 is open: `route_opt` is the call's read_strain_route / evidence_route / depth_route / near_miss_route / hap_pairs_route (any value but "walk":
+// route 1 is open: `route_opt` is the call's read_strain_route / evidence_route / depth_route / near_miss_route / hap_pairs_route / fit_route (any value but "walk":
 // the default)
 bool member_by_node(bool nh_built, const std::string &route_opt);
 unsigned long long member_bits(const uint32_t *haps, uint64_t K);   // bit haps[k] for every k (haplotype indices < 64)
@@ -32,7 +32,7 @@ unsigned long long member_bits(const uint32_t *haps, uint64_t K);   // bit haps[
 MemberRow member_row(bool by_node, uint64_t nh, uint32_t node_base, const uint32_t *haps, uint64_t K);
 
 // Bit -> entry filing: per_bit(bit, k) for the k-th chosen haplotype, which sits at bit haps[k] on route 1 and at bit first + k on route 2 (`first`: the bits
-// of the row ahead of the list).  The per-bit arrays of the read passes and of node evidence hold H + C + 1 entries, a species' bits from member_bit_base on.
+// of the row ahead of the list).  The per-bit arrays of the read passes, of node evidence and of the model fit hold H + C + 1 entries, a species' bits from member_bit_base on.
 template <class PerBit> inline void member_file_bits(uint32_t route, const uint32_t *haps, uint64_t K, uint64_t first, PerBit &&per_bit) {
     for (uint64_t k = 0; k < K; ++k) per_bit(route == 1u ? (uint64_t)haps[k] : first + k, k);
 }

@@ -1,7 +1,8 @@
 // profile_reports.cpp -- the per-strain reports of the file seam (profile_reports.hpp): per group of species, behind its strain step, the group's rows of
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
-// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way.
+// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so is the model fit report, whose file is named in
+// the seam's sized extension (EXT_REPORTS).
 #include <algorithm>
 #include <fstream>
 #include <unordered_map>
@@ -11,7 +12,8 @@
 namespace ptx {
 namespace {
 constexpr size_t EVIDENCE_N = 4, DEPTH_N = 2 * PANTAX_HIP_DEPTH_BINS;   // u64 per class: {n_nodes, len, covered, bases}; a histogram of [96]{n_nodes, len}
-// The group's rows of strain_abundance.txt, decided in the group's own turn (the a15 filter is row-local) and read by all six reports: `pass` as bits over
+constexpr size_t FIT_N = 8;   // {n_nodes, len, bases, expected, excess, deficit, blind_nodes, blind_expected}
+// The group's rows of strain_abundance.txt, decided in the group's own turn (the a15 filter is row-local) and read by every report: `pass` as bits over
 // the shard's haplotypes; per species of the group [off[k - k0], off[k - k0 + 1]) the species-local haplotypes `hap` in ascending order with their
 // second_sol weights `w`; the i-th of them is entry entry0 + i of ReportData
 struct GroupSel { std::vector<uint8_t> pass; std::vector<uint64_t> off; std::vector<uint32_t> hap; std::vector<double> w; size_t entry0 = 0; };
@@ -74,6 +76,15 @@ int group_node_sums(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const
     out.hap.resize(n_hap * (g.entry0 + g.hap.size()));
     PTX_TRY(call(run.ctx, db, &set, out.hap.data() + n_hap * g.entry0, out.species.data() + n_species * (size_t)k0));
     run.lap(lap);
+    return 0;
+}
+// --strain-fit, on the same coverage result: Sel_s = the group's rows, their weights the unrounded second_sol
+int group_fit(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &ft = sh.rep.ft;
+    const pantax_hip_fit_set set{k1 - k0, g.off.data(), g.hap.data(), g.w.data()};
+    ft.hap.resize(2 * FIT_N * (g.entry0 + g.hap.size()));
+    PTX_TRY(pantax_hip_strain_fit(run.ctx, db, &set, ft.hap.data() + 2 * FIT_N * g.entry0, ft.species.data() + 3 * FIT_N * (size_t)k0));
+    run.lap("  strain fit");
     return 0;
 }
 // --strain-pair-evidence, on the same coverage result: Sel_s = the group's rows, but for a species of more rows than the call serves, which gets no block
@@ -166,7 +177,7 @@ int group_near_miss(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const
     return 0;
 }
 
-// ---- the files: what every writer is handed, what the writers share, the six writers
+// ---- the files: what every writer is handed, what the writers share, the writers
 struct Writer {
     Run &run; const Ingest &in; const Selection &sn; const ShardResult &sh; const std::vector<GenomeRow> &genomes;
     const std::vector<TrackRow> &rows;                      // the rows of strain_abundance.txt, in its order
@@ -267,6 +278,39 @@ struct Writer {
                 else f << "-\t-";
                 f << '\t' << pc << '\n';
             });
+        });
+    }
+    // --strain-fit: the sums {n_nodes, len, bases, expected, excess, deficit, blind_nodes, blind_expected} of every class, with fit = 1 - (excess + deficit) /
+    // (bases + expected): {all, private} of every row of strain_abundance.txt, in its order, then {total, explained, orphan} of every species of the shard in the
+    // order it went through the device; explained only where the species has rows, with the f64 sum of their weights in ascending haplotype index
+    int fit() const {
+        return file(run.p.rep.ext_path[XREP_FIT], "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_nodes\tlen\tbases\texpected\texcess\tdeficit\tblind_nodes\tblind_expected\tfit\tpredicted_coverage\n",
+                    "strain fit report", [&](std::ofstream &f) {
+            const auto put = [&f](const std::string &head, const char *cls, const uint64_t *q, const std::string &pc) {
+                f << head << '\t' << cls;
+                for (size_t i = 0; i < FIT_N; ++i) f << '\t' << q[i];
+                const uint64_t off = q[4] + q[5], of = q[2] + q[3];
+                f << '\t' << (of ? fmt_f64(1.0 - (double)off / (double)of) : std::string("-")) << '\t' << pc << '\n';
+            };
+            const auto &d = rep.ft;
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "model fit", &e));
+                const std::string head = strain_head(r), pc = fmt_f64(sh.met[r.hap].second_sol);
+                put(head, "all", d.hap.data() + 2 * FIT_N * e, pc);
+                put(head, "private", d.hap.data() + 2 * FIT_N * e + FIT_N, pc);
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const std::string head = species_head(k);
+                const uint64_t *q = d.species.data() + 3 * FIT_N * k;
+                double pc = 0.0;
+                bool any = false;
+                for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1]; ++h)
+                    if (rep.entry[h] >= 0) { pc += sh.met[h].second_sol; any = true; }
+                put(head, "total", q, "-");
+                if (any) put(head, "explained", q + FIT_N, fmt_f64(pc));
+                put(head, "orphan", q + 2 * FIT_N, "-");
+            }
+            return 0;
         });
     }
     // --strain-read-support: {compatible, unique, assigned} of every row of strain_abundance.txt, in its order; {counted, unexplained, ambiguous, uninformative}
@@ -405,6 +449,7 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.run[REP_DEPTH]) rep.dp.species.assign(2 * DEPTH_N * (size_t)Su, 0);
     if (plan.run[REP_NEAR_MISS]) { rep.nm.species.assign(12 * (size_t)Su, 0); rep.nm.row_off.assign(Su + 1, 0); }
     if (plan.pair_run[PREP_EVIDENCE]) { rep.pe.pair_off.assign(Su, 0); rep.pe.K.assign(Su, 0); }
+    if (plan.ext_run[XREP_FIT]) rep.ft.species.assign(3 * FIT_N * (size_t)Su, 0);
 }
 int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
     const ReportPlan &plan = run.p.rep;
@@ -414,6 +459,7 @@ int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, ui
     if (plan.run[REP_READ_STRAINS]) PTX_TRY(group_read_strains(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_COVERAGE]) PTX_TRY(group_cov_track(run, db, k0, k1, g, sh));
     if (plan.run[REP_EVIDENCE]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_evidence, 2 * EVIDENCE_N, 3 * EVIDENCE_N, sh.rep.ev, "  strain evidence"));
+    if (plan.ext_run[XREP_FIT]) PTX_TRY(group_fit(run, db, k0, k1, g, sh));
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(group_pair_evidence(run, db, k0, k1, g, sh));
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
@@ -433,6 +479,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.run[REP_DEPTH]) PTX_TRY(w.depth());
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(w.near_miss());
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(w.pair_evidence());
+    if (plan.ext_run[XREP_FIT]) PTX_TRY(w.fit());
     return 0;
 }
 }  // namespace reports

@@ -1,6 +1,7 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
-// while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a row
-// of REPORTS (or of PAIR_REPORTS), a sub-struct here, and a line in each of begin / collect_group / write (profile_reports.cpp).
+// while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
+// of pantax_hip_profile_ext with its row of EXT_REPORTS (REPORTS and PAIR_REPORTS are closed: the config they point into keeps its size), a sub-struct
+// here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
 #include <string>
@@ -27,6 +28,8 @@ struct ReportData {
     struct NodeSums { std::vector<uint64_t> hap, species; };
     NodeSums ev;   // --strain-evidence: n = 4 {n_nodes, len, covered, bases}, three species classes
     NodeSums dp;   // --strain-depth: n = 192, a depth histogram of [96]{n_nodes, len}, two species classes
+    // --strain-fit: n = 8 {n_nodes, len, bases, expected, excess, deficit, blind_nodes, blind_expected}, three species classes {total, explained, orphan}
+    NodeSums ft;
     // --strain-read-support: hap[9e ..) = {compatible, unique, assigned}; species[12k ..) = {counted, unexplained, ambiguous, uninformative}; a species of
     // K[k] = 1..64 rows owns the K x K block of shared reads pair[pair_off[k] ..) over its entries in ascending order
     struct { std::vector<uint64_t> hap, species, pair, pair_off; std::vector<uint32_t> K; } sup;

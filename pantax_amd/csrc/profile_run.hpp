@@ -26,8 +26,8 @@ struct RunPlan {
     ReportPlan rep;                                                     // the per-strain reports: wanted, run by this call, their two parameters (report_plan.hpp)
     std::string db_dir, wd, out_dir, zip, species_file, strain_file, report, gaf_path;
 };
-// what every phase is handed: the two handles, the plan, the ranks, the trace clock
-struct Run { pantax_hip_ctx *ctx; const pantax_hip_profiling_config *cfg; RunPlan p; RankComm comm; Lap lap; };
+// what every phase is handed: the two handles, the sized extension of cfg (or null), the plan, the ranks, the trace clock
+struct Run { pantax_hip_ctx *ctx; const pantax_hip_profiling_config *cfg; const pantax_hip_profile_ext *ext; RunPlan p; RankComm comm; Lap lap; };
 // a1 - a3: depends on the sample (and the ranges of the DB)
 struct Ingest {
     std::vector<RangeRow> ranges; uint32_t S = 0;

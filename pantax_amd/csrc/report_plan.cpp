@@ -1,12 +1,12 @@
 // report_plan.cpp -- see report_plan.hpp
 #include "report_plan.hpp"
+#include <cstring>
 
 namespace ptx {
 
 namespace {
-// the one rule of a row of either table: its path, whether it is wanted, and the refusal of a wanted report on several ranks or a sharded ingest
-bool plan_row(const ReportRow &row, const pantax_hip_profiling_config *cfg, int W, bool sharded, std::string &path_out, bool &want, std::string &err) {
-    const char *path = cfg->*row.field;
+// the one rule of a row of any of the three tables: its path, whether it is wanted, and the refusal of a wanted report on several ranks or a sharded ingest
+template <class Row> bool plan_path(const Row &row, const char *path, int W, bool sharded, std::string &path_out, bool &want, std::string &err) {
     path_out = path ? path : "";
     want = !path_out.empty() && path_out != "None";
     if (want && (W > 1 || sharded)) {
@@ -14,6 +14,20 @@ bool plan_row(const ReportRow &row, const pantax_hip_profiling_config *cfg, int 
         return false;
     }
     return true;
+}
+bool plan_row(const ReportRow &row, const pantax_hip_profiling_config *cfg, int W, bool sharded, std::string &path_out, bool &want, std::string &err) {
+    return plan_path(row, cfg->*row.field, W, sharded, path_out, want, err);
+}
+// a field of the sized extension, read only where the caller's struct holds all of it (the caller's object may be shorter than this header's struct: the
+// offset comes from an object of our own, the value through a copy of its bytes)
+const char *ext_field(const pantax_hip_profile_ext *ext, const char *pantax_hip_profile_ext::*field) {
+    if (!ext) return nullptr;
+    static const pantax_hip_profile_ext layout{};
+    const size_t at = (size_t)(reinterpret_cast<const char *>(&(layout.*field)) - reinterpret_cast<const char *>(&layout));
+    if (at + sizeof(const char *) > ext->struct_size) return nullptr;
+    const char *value = nullptr;
+    std::memcpy(&value, reinterpret_cast<const char *>(ext) + at, sizeof(value));
+    return value;
 }
 // ... and when a wanted report runs
 bool runs(bool want, bool strain, bool full_path, bool strain_done) { return want && strain && !(full_path && strain_done); }
@@ -38,9 +52,21 @@ bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, R
     return true;
 }
 
+bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, ReportPlan &plan, std::string &err) {
+    for (int i = 0; i < N_EXT_REPORTS; ++i) { plan.ext_path[i].clear(); plan.ext_want[i] = plan.ext_run[i] = false; }
+    if (ext && (ext->struct_size < 8 || ext->struct_size % 8 != 0)) {
+        err = "profile: pantax_hip_profile_ext.struct_size " + std::to_string((unsigned long long)ext->struct_size) + " (a multiple of 8, at least 8)";
+        return false;
+    }
+    for (int i = 0; i < N_EXT_REPORTS; ++i)
+        if (!plan_path(EXT_REPORTS[i], ext_field(ext, EXT_REPORTS[i].field), W, sharded, plan.ext_path[i], plan.ext_want[i], err)) return false;
+    return true;
+}
+
 void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_done) {
     for (int i = 0; i < N_REPORTS; ++i) plan.run[i] = runs(plan.want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_PAIR_REPORTS; ++i) plan.pair_run[i] = runs(plan.pair_want[i], strain, full_path, strain_done);
+    for (int i = 0; i < N_EXT_REPORTS; ++i) plan.ext_run[i] = runs(plan.ext_want[i], strain, full_path, strain_done);
 }
 
 }  // namespace ptx

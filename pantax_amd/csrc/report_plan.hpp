@@ -1,7 +1,7 @@
 // report_plan.hpp -- the per-strain reports of the file seam (pantax_hip_profile) as one table: which config field switches a report on, what its refusal
 // calls it, whether it follows the rows of strain_abundance.txt.  plan_reports / resume_reports decide from plain values which reports this call wants
 // and runs; nothing else in the seam spells a report's field name or repeats the rule.  pantax_hip.h and standard headers only:
-// tests/native/report_plan_check.cpp and pair_report_plan_check.cpp compile this with the host compiler alone.
+// tests/native/report_plan_check.cpp, pair_report_plan_check.cpp and fit_report_plan_check.cpp compile this with the host compiler alone.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -31,16 +31,36 @@ enum PairReportId { PREP_EVIDENCE, N_PAIR_REPORTS };
 constexpr ReportRow PAIR_REPORTS[N_PAIR_REPORTS] = {
     {&pantax_hip_profiling_config::strain_pair_evidence_file, "strain_pair_evidence_file", "pairwise strain evidence report", true},
 };
+// A third id space: the reports whose file is named in the sized extension of the seam (pantax_hip_profile_ext; pantax_hip_profiling_config keeps its
+// size, and the two tables above their rows).  Same columns but for the struct the member pointer goes into, same rule (plan_ext_reports); checked after
+// the two tables above.  A later report is a field appended to pantax_hip_profile_ext and a row here.
+enum ExtReportId { XREP_FIT, N_EXT_REPORTS };
+struct ExtReportRow {
+    const char *pantax_hip_profile_ext::*field;
+    const char *name;
+    const char *what;
+    bool rows;
+};
+constexpr ExtReportRow EXT_REPORTS[N_EXT_REPORTS] = {
+    {&pantax_hip_profile_ext::strain_fit_file, "strain_fit_file", "model fit report", true},
+};
 struct ReportPlan {
-    std::string path[N_REPORTS], pair_path[N_PAIR_REPORTS];
+    std::string path[N_REPORTS], pair_path[N_PAIR_REPORTS], ext_path[N_EXT_REPORTS];
     bool want[N_REPORTS] = {}, run[N_REPORTS] = {};   // want: the caller named a file; run: this call runs a strain step and writes it
     bool pair_want[N_PAIR_REPORTS] = {}, pair_run[N_PAIR_REPORTS] = {};
+    bool ext_want[N_EXT_REPORTS] = {}, ext_run[N_EXT_REPORTS] = {};
     uint64_t ct_window = 10000;                       // window of the coverage track in bases
     uint32_t nm_top = 5;                              // candidates the near-miss report prints per species
-    bool any_run() const { for (const bool r : run) if (r) return true; for (const bool r : pair_run) if (r) return true; return false; }
+    bool any_run() const {
+        for (const bool r : run) if (r) return true;
+        for (const bool r : pair_run) if (r) return true;
+        for (const bool r : ext_run) if (r) return true;
+        return false;
+    }
     bool rows_run() const {
         for (int i = 0; i < N_REPORTS; ++i) if (run[i] && REPORTS[i].rows) return true;
         for (int i = 0; i < N_PAIR_REPORTS; ++i) if (pair_run[i] && PAIR_REPORTS[i].rows) return true;
+        for (int i = 0; i < N_EXT_REPORTS; ++i) if (ext_run[i] && EXT_REPORTS[i].rows) return true;
         return false;
     }
 };
@@ -48,6 +68,9 @@ struct ReportPlan {
 // rows of the GAF on the rank of their byte range -- not joined here.  false: the first failing check in table order (REPORTS, then
 // PAIR_REPORTS), its message in err (E_INVALID)
 bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, ReportPlan &plan, std::string &err);
+// behind plan_reports, on the same plan: ext -> ext_path and ext_want, by the same rule and with the same refusal wording.  ext == null: all off; a field
+// that does not lie wholly inside ext->struct_size reads as off; false also for a struct_size below 8 or not a multiple of 8
+bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, ReportPlan &plan, std::string &err);
 // run[] from want[]: a wanted report is written by a call that runs a strain step
 void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_done);
 

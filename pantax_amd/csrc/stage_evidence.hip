@@ -36,13 +36,6 @@ constexpr uint32_t EV_TILE = 256;     // nodes the wave holds in registers at a 
 
 struct EvSpecies { MemberRow m; uint32_t bit_base, pad; };   // bit_base: first entry of the species in bit_entry
 
-// the wave's LDS counters change hands between its lanes (lane 0 adds, every lane zeroes and flushes its own bit): order the accesses inside the wave
-__device__ __forceinline__ void ev_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, const MemberChunk *__restrict__ chunks, const EvSpecies *__restrict__ tab,
                                                             const uint32_t *__restrict__ node_len, const uint32_t *__restrict__ cov,
                                                             const unsigned long long *__restrict__ bases, const unsigned long long *__restrict__ node_haps,
@@ -62,7 +55,7 @@ __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, c
             const unsigned long long live = st.m.route == 1u ? st.m.bits : (st.m.route == 2u ? (left >= 64u ? ~0ull : (1ull << left) - 1ull) : 0ull);
 #pragma unroll
             for (int q = 0; q < 8; ++q) cnt[q * 64 + lane] = 0ull;
-            ev_wave_sync();
+            member_wave_sync();
             for (uint32_t t0 = 0; t0 < ch.n; t0 += EV_TILE) {
                 uint32_t ln[4], cv[4];
                 unsigned long long bs[4], wd[4];
@@ -111,7 +104,7 @@ __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, c
                     }
                 }
             }
-            ev_wave_sync();
+            member_wave_sync();
             if ((live >> lane) & 1ull) {   // lane b owns bit b of this word
                 const uint32_t e = bit_entry[st.bit_base + 64u * w + (uint32_t)lane];
                 if (e != MEMBER_NO_ENTRY) {
@@ -122,7 +115,7 @@ __global__ void __launch_bounds__(256) evidence_node_kernel(uint32_t n_chunks, c
                     }
                 }
             }
-            ev_wave_sync();   // (the counters are zeroed again by the next pass or chunk)
+            member_wave_sync();   // (the counters are zeroed again by the next pass or chunk)
         }
         tot = mq_wave_sum(tot); orp = mq_wave_sum(orp); cor = mq_wave_sum(cor);
         if (lane == 0) {

@@ -378,6 +378,22 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_evidence(self.ctx, self.db, C.byref(cs), p(hap) if len(sh) else None, p(species) if self.S else None))
         return hap, species
 
+    def strain_fit(self, sel_off, sel_hap, sel_w):
+        """Model fit per strain (pantax_hip_strain_fit) of the coverage result get_node_abundances left on the device.  sel_off [S+1], sel_hap as for
+        strain_evidence, sel_w float64 [C]: the predicted coverage of every selection entry (finite, >= 0) -> (hap uint64 [C, 2, 8]: all / private of
+        every selection entry, species uint64 [S, 3, 8]: total / explained / orphan), the last axis {n_nodes, len, bases, expected, excess, deficit,
+        blind_nodes, blind_expected}."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        sw = as_c(sel_w, np.float64)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]) or len(sw) != len(sh):
+            raise ValueError("strain_fit: sel_off needs S + 1 entries, sel_hap and sel_w sel_off[-1]")
+        cs = _ffi.FitSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, sw.ctypes.data if len(sh) else None)
+        hap = np.zeros((len(sh), 2, 8), dtype=np.uint64)
+        species = np.zeros((self.S, 3, 8), dtype=np.uint64)
+        self._check(self.lib.pantax_hip_strain_fit(self.ctx, self.db, C.byref(cs), p(hap) if len(sh) else None, p(species) if self.S else None))
+        return hap, species
+
     def strain_depth(self, sel_off, sel_hap, species=True):
         """Per-strain depth distribution (pantax_hip_strain_depth) of the coverage result get_node_abundances left on the device.
         sel_off [S+1], sel_hap as for strain_evidence -> (hap uint64 [C, 2, 96, 2]: the histograms all / private of every selection entry,
@@ -603,7 +619,7 @@ class Engine:
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
                 strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
-                strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None):
+                strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None, strain_fit_file=None):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -612,7 +628,8 @@ class Engine:
         (--strain-evidence; one rank only).  strain_read_support_file: path of the per-strain read support report (--strain-read-support; one rank only).
         strain_depth_file: path of the per-strain depth distribution report (--strain-depth; one rank only).  strain_near_miss_file: path of the
         unreported-strain near-miss report (--strain-near-miss; one rank only), strain_near_miss_top the candidates it prints per species (0: 5).
-        strain_pair_evidence_file: path of the pairwise strain evidence report (--strain-pair-evidence; one rank only)."""
+        strain_pair_evidence_file: path of the pairwise strain evidence report (--strain-pair-evidence; one rank only).  strain_fit_file: path of the
+        model fit report (--strain-fit; one rank only); given, the call goes through pantax_hip_profile_with_ext."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -655,7 +672,11 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
+        if strain_fit_file is None:
+            self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
+        else:   # the outputs behind the config's last field travel in the sized extension
+            ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file))
+            self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
         """pantax_hip_db_pairs (the --db-pairs mode): the pairwise distinguishability table of a db directory -> out_file.  species: taxids (a list or a
