@@ -461,6 +461,50 @@ typedef struct {
 int pantax_hip_strain_fit(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_fit_set *sel,
                           uint64_t *hap_out /*[C][2][8]: all, private*/, uint64_t *species_out /*[S][3][8]: total, explained, orphan*/);
 
+/* ---- bootstrap of the strain fit (the --strain-bootstrap report; not a stage of the reference): strain_abundance.txt gives one number per strain, the
+ * x_h of one L1 fit; a least-absolute-deviation fit is a weighted median and can jump between vertices when a handful of rows change.  This call says how
+ * far the number moves when the rows are drawn again: it refits the LP of the selected strains on the sample's rows (replicate 0) and on n_replicates
+ * Poisson-bootstrap resamples of them, all on the device.  Selection, Sel_s, K_s and M(v) are those of pantax_hip_strain_evidence; the inputs are node_len
+ * and bases_per_node as pantax_hip_node_coverage leaves them.  Selection entry c of species s is COLUMN k = c - sel_off[s] of the species' LP.
+ *   Rows of species s: every node v with a_v = (double)(long long)bases[v] / (double)node_len[v] > 0 and mask_v = sum over k of [sel_hap k in M(v)] << k != 0 is
+ *   the row (mask_v, a_v).  No min_depth, no --sample cut, no first or second filter: the LP of profile.rs:1333-1451 restricted to the selected columns,
+ *   0 <= x_k <= 1.05 max a (the box of profile.rs:1327, from the replicate's own rows) and no column pinned.  A node with a_v > 0 and mask_v = 0 gives no row
+ *   and is no part of the objective here.
+ *   Weight of row v in replicate b: 1 for b = 0 (the plain refit).  For b >= 1, with sm(x) = splitmix64's output function (x += 0x9E3779B97F4A7C15;
+ *   x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31, in u64):
+ *       r = sm(sm(seed ^ sm(sp_key[s])) + ((uint64_t)b << 40) + v_local),   v_local = the node's index inside its species,
+ *       w = #{ j in 0..15 : r >= T[j] },   T[j] = floor(2^64 * sum_{i <= j} e^-1 / i!):   a Poisson(1) weight capped at 16.
+ *   sp_key is the caller's name of the species (the file seam passes the taxid): the weights do not depend on where the species sits in the db.
+ *   Replicate LP: minimise sum_v w_v |a_v - sum_k x_k bit_k(mask_v)| -- the LAD of the multiset in which row v occurs w_v times; amax, the pattern tables
+ *   and the solver's scratch are formed from the replicate's own rows, and a pattern whose rows all drew 0 does not exist in it.
+ * Outputs, replicate-major, R = n_replicates + 1:  x_out [R][C] the solution;  obj_out [R][S] the weighted objective above at x (a sum, not a mean);
+ * rows_out [R][S] = sum of the weights;  status_out [R][S]:  0 solved;  1 nothing to solve (K_s = 0 or no row: x = 0, obj = 0);  PANTAX_HIP_E_LIMIT
+ * K_s > 64 (x = 0, obj = 0, rows = 0; the other species are served);  PANTAX_HIP_E_SOLVER that LP failed, the others stand.
+ * The call fails as a whole only on invalid arguments, a HIP error or PANTAX_HIP_E_LIMIT of its own (32-bit row positions; a replicate that does not fit
+ * the option bootstrap_rows_max, the cap on the expanded rows in flight on the device, 0 = from the free device memory); on an error the outputs are left
+ * as given.  State rules of pantax_hip_strain_evidence: PANTAX_HIP_E_STATE behind a resident step and before any coverage pass; PANTAX_HIP_E_INVALID as in
+ * the evidence call, and for a null sp_key with S > 0.  Determinism: the same inputs give the same bits, whatever the chunking of the replicates
+ * (bootstrap_rows_max), the membership route (option bootstrap_route=walk takes every species' membership from its selected walks) and the position of the
+ * species in the db; the objective is summed in an order that is a function of the replicate's rows alone. */
+typedef struct {
+    uint32_t n_species;       /* must equal the db's */
+    const uint64_t *sel_off;  /* [S+1] as pantax_hip_evidence_set */
+    const uint32_t *sel_hap;  /* [C] species-local haplotype index, any order, no repeats within a species */
+    const uint64_t *sp_key;   /* [S] the species' key of the weight hash */
+    uint64_t seed;
+    uint32_t n_replicates;    /* 0: the refit only */
+} pantax_hip_bootstrap_set;
+int pantax_hip_strain_bootstrap(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_bootstrap_set *sel, double *x_out /*[R][C]*/, double *obj_out /*[R][S]*/,
+                                uint64_t *rows_out /*[R][S]*/, int32_t *status_out /*[R][S]*/);
+/* host helpers, no ctx and no GPU.  The weight w of the contract above (replicate 0: 1): */
+uint32_t pantax_hip_bootstrap_weight(uint64_t seed, uint64_t sp_key, uint32_t replicate, uint64_t v_local);
+/* The summary of one quantity over the replicates b >= 1: x and status hold its n values and the LPs' statuses in ascending b (status NULL: all solved);
+ * only the entries with status 0 count, m of them.  out[10] = { n_solved = m;  mean = the f64 sum in ascending b divided by m;  sd = sqrt(sum of
+ * (x - mean)^2 in ascending b / (m - 1)), 0 for m < 2;  q025, q25, q50, q75, q975 = the sorted value at index floor(p (m - 1) / 1000), p = 25, 250, 500,
+ * 750, 975 in integer arithmetic;  zero_fraction = the share of the m values with x == 0.0;  min }.  m = 0: n_solved = 0 and nine zeros.
+ * PANTAX_HIP_E_INVALID for a null out, or a null x with n > 0. */
+int pantax_hip_bootstrap_summary(uint64_t n, const double *x, const int32_t *status, double *out /*[10]*/);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -737,7 +781,8 @@ int pantax_hip_profile(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *c
  * strain_pair_evidence_file are appended HERE, one field each, and reach the seam through pantax_hip_profile_with_ext.  struct_size is
  * sizeof(pantax_hip_profile_ext) as the caller's header has it: a field that does not lie wholly inside struct_size reads as off, so a caller built
  * against an older header keeps working against a newer library; struct_size below 8 or not a multiple of 8 is PANTAX_HIP_E_INVALID.  ext == NULL:
- * everything here is off, and pantax_hip_profile(ctx, cfg) is pantax_hip_profile_with_ext(ctx, cfg, NULL). */
+ * everything here is off, and pantax_hip_profile(ctx, cfg) is pantax_hip_profile_with_ext(ctx, cfg, NULL).  This struct is closed at strain_fit_file: later outputs are
+ * fields of pantax_hip_profile_ext2 below. */
 typedef struct {
     uint64_t struct_size;         /* sizeof(pantax_hip_profile_ext) as the caller's header has it */
     /* --strain-fit: path of the model fit report (pantax_hip_strain_fit over every group of species, right behind the group's evidence sums, on the same
@@ -753,6 +798,25 @@ typedef struct {
     const char *strain_fit_file;
 } pantax_hip_profile_ext;
 int pantax_hip_profile_with_ext(pantax_hip_ctx *ctx, const pantax_hip_profiling_config *cfg, const pantax_hip_profile_ext *ext);
+/* The extension as it grows.  pantax_hip_profile_ext above is its first version and keeps ITS size too (compiled callers and a committed host check hold
+ * its 16 bytes); the outputs behind strain_fit_file are the fields of the longer struct below, which BEGINS with the first version.  A caller fills
+ * v1.struct_size = sizeof(pantax_hip_profile_ext2) and passes &ext2.v1 to pantax_hip_profile_with_ext: by the rule above the library reads every field
+ * that lies wholly inside struct_size, so a caller with the 16-byte struct runs with the fields below off.  A later output is a field appended here. */
+typedef struct {
+    pantax_hip_profile_ext v1;    /* v1.struct_size = sizeof(pantax_hip_profile_ext2) */
+    /* --strain-bootstrap: path of the bootstrap report (pantax_hip_strain_bootstrap over every group of species, right behind the group's model fit, on the
+     * same coverage result; NULL, "" or "None" = off).  Sel_s = the species' rows of strain_abundance.txt, sp_key = the species taxid as a number (a taxid that
+     * is no number: FNV-1a of its text).  TSV with a header: species_taxid, strain_taxid, genome_ID, class, predicted_coverage, refit, n_solved, mean, sd, q025,
+     * q25, q50, q75, q975, min, zero_fraction, share, share_q025, share_q975, n_rows, objective; f64 in shortest round-trip digits, "-" where a column does not
+     * apply or nothing was solved.  First the strains in the order of strain_abundance.txt, class "strain": predicted_coverage = the unrounded second_sol,
+     * refit = x of replicate 0, n_solved .. zero_fraction = pantax_hip_bootstrap_summary over the replicates' x, share = refit / sum of the species' refits,
+     * share_q025 / share_q975 from the same summary over x_k / sum_k x_k per solved replicate (a sum of 0 counts as 0).  Then every species that went
+     * through a strain step and has rows in the table, in the order the run took them, class "species" ("skipped" for more than 64 rows): n_rows and
+     * objective of replicate 0, n_solved, mean, sd, the quantiles and min over the replicates' objectives.  Same rules as strain_fit_file. */
+    const char *strain_bootstrap_file;
+    uint64_t strain_bootstrap_replicates;   /* 0 reads as 100; beyond 2^32 - 2: PANTAX_HIP_E_INVALID */
+    uint64_t strain_bootstrap_seed;         /* a struct that does not hold the field reads as 42, the seed of the row sampler; the front ends default to 42 */
+} pantax_hip_profile_ext2;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

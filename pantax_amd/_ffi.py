@@ -26,6 +26,7 @@ SYMBOLS = [
     "pantax_hip_read_strains", "pantax_hip_strain_cov_track", "pantax_hip_strain_evidence", "pantax_hip_strain_read_support", "pantax_hip_strain_depth",
     "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_strain_near_miss", "pantax_hip_near_miss_rank",
     "pantax_hip_db_hap_pairs", "pantax_hip_db_pairs", "pantax_hip_strain_pair_evidence", "pantax_hip_strain_fit", "pantax_hip_profile_with_ext",
+    "pantax_hip_strain_bootstrap", "pantax_hip_bootstrap_weight", "pantax_hip_bootstrap_summary",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -133,8 +134,15 @@ class FitSet(C.Structure):
 
 
 class ProfileExt(C.Structure):
-    """pantax_hip_profile_ext: the sized extension of ProfilingConfig; struct_size = ctypes.sizeof(ProfileExt)"""
-    _fields_ = [("struct_size", C.c_uint64), ("strain_fit_file", C.c_char_p)]
+    """pantax_hip_profile_ext2 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file) and the fields behind it;
+    struct_size = ctypes.sizeof(ProfileExt)"""
+    _fields_ = [("struct_size", C.c_uint64), ("strain_fit_file", C.c_char_p), ("strain_bootstrap_file", C.c_char_p),
+                ("strain_bootstrap_replicates", C.c_uint64), ("strain_bootstrap_seed", C.c_uint64)]
+
+
+class BootstrapSet(C.Structure):
+    _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p), ("sp_key", C.c_void_p), ("seed", C.c_uint64),
+                ("n_replicates", C.c_uint32)]
 
 
 class NearMissSet(C.Structure):
@@ -193,6 +201,12 @@ def load():
         _lib.pantax_hip_strain_pair_evidence.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(EvidenceSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         _lib.pantax_hip_strain_fit.restype = C.c_int
         _lib.pantax_hip_strain_fit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FitSet), C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_strain_bootstrap.restype = C.c_int
+        _lib.pantax_hip_strain_bootstrap.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BootstrapSet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_bootstrap_weight.restype = C.c_uint32
+        _lib.pantax_hip_bootstrap_weight.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64]
+        _lib.pantax_hip_bootstrap_summary.restype = C.c_int
+        _lib.pantax_hip_bootstrap_summary.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.pantax_hip_profile_with_ext.restype = C.c_int
         _lib.pantax_hip_profile_with_ext.argtypes = [C.c_void_p, C.POINTER(ProfilingConfig), C.POINTER(ProfileExt)]
         _lib.pantax_hip_db_pairs.restype = C.c_int

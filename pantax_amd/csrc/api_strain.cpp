@@ -605,6 +605,24 @@ int pantax_hip_strain_fit(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_h
     return fit_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->sel_w, hap_out, species_out);
 }
 
+int pantax_hip_strain_bootstrap(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_bootstrap_set *sel, double *x_out, double *obj_out, uint64_t *rows_out,
+                                int32_t *status_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_bootstrap: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_bootstrap", sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_bootstrap", sel->sel_off, sel->sel_hap));
+    if (db->S && !sel->sp_key) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_bootstrap: null sp_key");
+    if (sel->n_replicates == 0xFFFFFFFFu) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_bootstrap: %u replicates (at most 2^32 - 2)", sel->n_replicates);
+    if ((sel->sel_off[db->S] && !x_out) || (db->S && (!obj_out || !rows_out || !status_out))) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_bootstrap: null output array");
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_bootstrap"));
+    try {
+        return bootstrap_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->sp_key, sel->seed, sel->n_replicates, x_out, obj_out, rows_out, status_out);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_bootstrap: out of host memory");
+    }
+}
+
 int pantax_hip_db_hap_pairs(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out,
                             uint64_t *species_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;

@@ -45,6 +45,10 @@ static void usage() {
             "                     beyond them (excess), what it lacks (deficit) and the part of that on nodes without any coverage (blind), with\n"
             "                     fit = 1 - (excess + deficit) / (bases + expected); then per species every node (total), the nodes some reported strain walks\n"
             "                     (explained) and the nodes none walks (orphan) (one rank only)\n"
+            "  --strain-bootstrap F   bootstrap of the strain fit: for every row of strain_abundance.txt the coverage a refit of the reported strains gives it and\n"
+            "                     its mean, sd, quantiles and zero fraction over N Poisson resamples of the LP's rows, its share of the species and the share's\n"
+            "                     0.025 and 0.975 quantiles; per species the rows and the objective (one rank only)\n"
+            "  --strain-bootstrap-replicates N   resamples (default 100)     --strain-bootstrap-seed N   their seed (default 42)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -70,9 +74,10 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
-    pantax_hip_profile_ext ext;   // the outputs added behind the config's last field
+    pantax_hip_profile_ext2 ext;   // the outputs added behind the config's last field
     memset(&ext, 0, sizeof(ext));
-    ext.struct_size = sizeof(ext);
+    ext.v1.struct_size = sizeof(ext);
+    ext.strain_bootstrap_seed = 42;
     pantax_hip_db_pairs_config pairs;
     memset(&pairs, 0, sizeof(pairs));
     pairs.max_distance = -1;
@@ -134,7 +139,10 @@ int main(int argc, char **argv) {
         else if (a == "--strain-near-miss") c.strain_near_miss_file = next();
         else if (a == "--strain-near-miss-top") c.strain_near_miss_top = atoi(next());
         else if (a == "--strain-pair-evidence") c.strain_pair_evidence_file = next();
-        else if (a == "--strain-fit") ext.strain_fit_file = next();
+        else if (a == "--strain-fit") ext.v1.strain_fit_file = next();
+        else if (a == "--strain-bootstrap") ext.strain_bootstrap_file = next();
+        else if (a == "--strain-bootstrap-replicates") ext.strain_bootstrap_replicates = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-bootstrap-seed") ext.strain_bootstrap_seed = strtoull(next(), nullptr, 10);
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;
@@ -209,7 +217,7 @@ int main(int argc, char **argv) {
         if (use_rccl && RcclComm::allreduce_sum(&comm, &failed, 1) != 0) { fprintf(stderr, "pantax-hip: rank %d: the exchange behind --filter-gaf failed\n", rank); failed = 1.0; }
         if (failed != 0.0) { if (use_rccl) comm.destroy(id_file); pantax_hip_destroy(ctx); return 1; }
     }
-    rc = pantax_hip_profile_with_ext(ctx, &c, &ext);
+    rc = pantax_hip_profile_with_ext(ctx, &c, &ext.v1);
     if (rc != 0) fprintf(stderr, "pantax-hip: %serror %d: %s\n", use_rccl ? ("rank " + std::to_string(rank) + ": ").c_str() : "", rc, pantax_hip_last_error(ctx));
     if (use_rccl) comm.destroy(id_file);
     pantax_hip_destroy(ctx);

@@ -1,8 +1,8 @@
 // profile_reports.cpp -- the per-strain reports of the file seam (profile_reports.hpp): per group of species, behind its strain step, the group's rows of
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
-// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so is the model fit report, whose file is named in
-// the seam's sized extension (EXT_REPORTS).
+// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report and the bootstrap report, whose files are
+// named in the seam's sized extension (EXT_REPORTS, EXT2_REPORTS).
 #include <algorithm>
 #include <fstream>
 #include <unordered_map>
@@ -85,6 +85,37 @@ int group_fit(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const Group
     ft.hap.resize(2 * FIT_N * (g.entry0 + g.hap.size()));
     PTX_TRY(pantax_hip_strain_fit(run.ctx, db, &set, ft.hap.data() + 2 * FIT_N * g.entry0, ft.species.data() + 3 * FIT_N * (size_t)k0));
     run.lap("  strain fit");
+    return 0;
+}
+// --strain-bootstrap, on the same coverage result: Sel_s = the group's rows (column = position: ascending haplotype), sp_key = the species taxid
+uint64_t taxid_key(const std::string &taxid) {
+    uint64_t v = 0;
+    bool number = !taxid.empty() && taxid.size() <= 19;
+    for (const char c : taxid) { if (c < '0' || c > '9') { number = false; break; } v = v * 10 + (uint64_t)(c - '0'); }
+    if (number) return v;
+    uint64_t h = 0xCBF29CE484222325ull;   // a taxid that is no number: FNV-1a of its text
+    for (const char c : taxid) { h ^= (unsigned char)c; h *= 0x100000001B3ull; }
+    return h;
+}
+int group_bootstrap(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &bs = sh.rep.bs;
+    const uint32_t Sg = k1 - k0;
+    const uint64_t R = bs.R, Cg = g.hap.size();
+    std::vector<uint64_t> key(Sg);
+    for (uint32_t k = k0; k < k1; ++k) key[k - k0] = taxid_key(in.ranges[sn.sel[sh.use[k]]].species);
+    const pantax_hip_bootstrap_set set{Sg, g.off.data(), g.hap.data(), key.data(), run.p.rep.bs_seed, run.p.rep.bs_replicates};
+    std::vector<double> x(R * Cg), obj(R * Sg);
+    std::vector<uint64_t> rows(R * Sg);
+    std::vector<int32_t> status(R * Sg);
+    PTX_TRY(pantax_hip_strain_bootstrap(run.ctx, db, &set, x.data(), obj.data(), rows.data(), status.data()));
+    bs.x.resize(R * (g.entry0 + Cg));
+    for (uint64_t b = 0; b < R; ++b) {   // replicate-major -> the R values of an entry, of a species side by side
+        for (uint64_t c = 0; c < Cg; ++c) bs.x[R * (g.entry0 + c) + b] = x[b * Cg + c];
+        for (uint32_t k = 0; k < Sg; ++k) {
+            bs.obj[R * (k0 + k) + b] = obj[b * Sg + k]; bs.rows[R * (k0 + k) + b] = rows[b * Sg + k]; bs.status[R * (k0 + k) + b] = status[b * Sg + k];
+        }
+    }
+    run.lap("  strain bootstrap");
     return 0;
 }
 // --strain-pair-evidence, on the same coverage result: Sel_s = the group's rows, but for a species of more rows than the call serves, which gets no block
@@ -313,6 +344,62 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-bootstrap: per row of strain_abundance.txt, in its order, the refit and the summary of its x over the replicates, its share of the species'
+    // refit and the 2.5 % / 97.5 % quantiles of its share per replicate; then per species of the shard in the order it went through the device the rows and
+    // the objective of the refit and the summary of the replicates' objectives ("skipped": more rows than the call serves)
+    int bootstrap() const {
+        return file(run.p.rep.ext2_path[X2REP_BOOTSTRAP],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tclass\tpredicted_coverage\trefit\tn_solved\tmean\tsd\tq025\tq25\tq50\tq75\tq975\tmin\tzero_fraction\tshare\tshare_q025\tshare_q975\tn_rows\tobjective\n",
+                    "strain bootstrap report", [&](std::ofstream &f) {
+            const auto &d = rep.bs;
+            const uint64_t R = d.R, n = R - 1;
+            // {n_solved, mean, sd, q025 .. q975, min, zero_fraction} of one summary in the file's order; "-" but for n_solved where nothing was solved
+            const auto stats = [&f](const double *o, bool zero_fraction) {
+                f << '\t' << (uint64_t)o[0];
+                static const int order[9] = {1, 2, 3, 4, 5, 6, 7, 9, 8};
+                for (const int i : order) f << '\t' << (o[0] > 0 && (i != 8 || zero_fraction) ? fmt_f64(o[i]) : std::string("-"));
+            };
+            std::vector<double> share(n);
+            double o[10], os[10];
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "bootstrap", &e));
+                const int32_t *st = d.status.data() + R * r.k;
+                f << strain_head(r) << "\tstrain\t" << fmt_f64(sh.met[r.hap].second_sol);
+                if (st[0] != 0 && st[0] != 1) {   // the species was not served
+                    f << "\t-\t0";
+                    for (int i = 0; i < 14; ++i) f << "\t-";
+                    f << '\n';
+                    continue;
+                }
+                const double *x = d.x.data() + R * e;
+                // the species' entries, in column order
+                double refit_sum = 0.0;
+                std::fill(share.begin(), share.end(), 0.0);
+                for (uint64_t h = sh.hap_off[r.k]; h < sh.hap_off[r.k + 1]; ++h)
+                    if (rep.entry[h] >= 0) {
+                        const double *xe = d.x.data() + R * (uint64_t)rep.entry[h];
+                        refit_sum += xe[0];
+                        for (uint64_t b = 0; b < n; ++b) share[b] += xe[1 + b];
+                    }
+                for (uint64_t b = 0; b < n; ++b) share[b] = share[b] == 0.0 ? 0.0 : x[1 + b] / share[b];
+                PTX_TRY(pantax_hip_bootstrap_summary(n, x + 1, st + 1, o));
+                PTX_TRY(pantax_hip_bootstrap_summary(n, share.data(), st + 1, os));
+                f << '\t' << fmt_f64(x[0]);
+                stats(o, true);
+                f << '\t' << fmt_f64(refit_sum == 0.0 ? 0.0 : x[0] / refit_sum) << '\t' << (os[0] > 0 ? fmt_f64(os[3]) : std::string("-")) << '\t'
+                  << (os[0] > 0 ? fmt_f64(os[7]) : std::string("-")) << "\t-\t-\n";
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const int32_t *st = d.status.data() + R * k;
+                const bool skipped = st[0] != 0 && st[0] != 1;
+                PTX_TRY(pantax_hip_bootstrap_summary(n, d.obj.data() + R * k + 1, st + 1, o));
+                f << species_head(k) << '\t' << (skipped ? "skipped" : "species") << "\t-\t-";
+                stats(o, false);
+                f << "\t-\t-\t-\t" << d.rows[R * k] << '\t' << (skipped ? std::string("-") : fmt_f64(d.obj[R * k])) << '\n';
+            }
+            return 0;
+        });
+    }
     // --strain-read-support: {compatible, unique, assigned} of every row of strain_abundance.txt, in its order; {counted, unexplained, ambiguous, uninformative}
     // of every species of the shard in the order it went through the device (a species without rows: counted only); the shared reads of every pair of rows
     int read_support() const {
@@ -450,8 +537,12 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.run[REP_NEAR_MISS]) { rep.nm.species.assign(12 * (size_t)Su, 0); rep.nm.row_off.assign(Su + 1, 0); }
     if (plan.pair_run[PREP_EVIDENCE]) { rep.pe.pair_off.assign(Su, 0); rep.pe.K.assign(Su, 0); }
     if (plan.ext_run[XREP_FIT]) rep.ft.species.assign(3 * FIT_N * (size_t)Su, 0);
+    if (plan.ext2_run[X2REP_BOOTSTRAP]) {
+        rep.bs.R = (uint64_t)plan.bs_replicates + 1;
+        rep.bs.obj.assign(rep.bs.R * Su, 0.0); rep.bs.rows.assign(rep.bs.R * Su, 0); rep.bs.status.assign(rep.bs.R * Su, 1);
+    }
 }
-int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
+int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
     const ReportPlan &plan = run.p.rep;
     if (!plan.any_run()) return 0;
     GroupSel g;
@@ -460,6 +551,7 @@ int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, ui
     if (plan.run[REP_COVERAGE]) PTX_TRY(group_cov_track(run, db, k0, k1, g, sh));
     if (plan.run[REP_EVIDENCE]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_evidence, 2 * EVIDENCE_N, 3 * EVIDENCE_N, sh.rep.ev, "  strain evidence"));
     if (plan.ext_run[XREP_FIT]) PTX_TRY(group_fit(run, db, k0, k1, g, sh));
+    if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(group_bootstrap(run, in, sn, db, k0, k1, g, sh));
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(group_pair_evidence(run, db, k0, k1, g, sh));
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
@@ -480,6 +572,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(w.near_miss());
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(w.pair_evidence());
     if (plan.ext_run[XREP_FIT]) PTX_TRY(w.fit());
+    if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(w.bootstrap());
     return 0;
 }
 }  // namespace reports

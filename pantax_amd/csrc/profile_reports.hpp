@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
-// of pantax_hip_profile_ext with its row of EXT_REPORTS (REPORTS and PAIR_REPORTS are closed: the config they point into keeps its size), a sub-struct
+// of pantax_hip_profile_ext2 with its row of EXT2_REPORTS (REPORTS, PAIR_REPORTS and EXT_REPORTS are closed: the structs they point into keep their size), a sub-struct
 // here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
@@ -30,6 +30,8 @@ struct ReportData {
     NodeSums dp;   // --strain-depth: n = 192, a depth histogram of [96]{n_nodes, len}, two species classes
     // --strain-fit: n = 8 {n_nodes, len, bases, expected, excess, deficit, blind_nodes, blind_expected}, three species classes {total, explained, orphan}
     NodeSums ft;
+    // --strain-bootstrap: R = replicates + 1 values a quantity, replicate 0 first: x[R e ..) of entry e; obj[R k ..), rows[R k ..), status[R k ..) of species k
+    struct { uint64_t R = 0; std::vector<double> x, obj; std::vector<uint64_t> rows; std::vector<int32_t> status; } bs;
     // --strain-read-support: hap[9e ..) = {compatible, unique, assigned}; species[12k ..) = {counted, unexplained, ambiguous, uninformative}; a species of
     // K[k] = 1..64 rows owns the K x K block of shared reads pair[pair_off[k] ..) over its entries in ascending order
     struct { std::vector<uint64_t> hap, species, pair, pair_off; std::vector<uint32_t> K; } sup;
@@ -46,7 +48,7 @@ namespace reports {
 // sizes what the running reports index by read (R), haplotype (H) and species (Su) of the shard
 void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportData &rep);
 // the species [k0, k1) of the db that has just gone through its strain step: the group's rows of the strain table selected once, then each running report
-int collect_group(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh);
+int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh);
 // behind the tables: the files of the running reports; `rows` come from strain_tables and are put into the table's order here
 int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, const std::vector<GenomeRow> &genomes, std::vector<TrackRow> &rows);
 }  // namespace reports

@@ -199,7 +199,7 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
                                     run.cfg->sample_test ? 500 : run.cfg->sample_nodes, run.cfg->solver_semantics};
         PTX_TRY(pantax_hip_strain_profile(run.ctx, db, &sc, nullptr, cov.data() + k0, sh.met.data() + sh.hap_off[k0], sh.info.data() + k0));
         run.lap("strain step");
-        PTX_TRY(reports::collect_group(run, in, db, k0, k1, sh));   // the per-strain reports take what they need while the group is resident
+        PTX_TRY(reports::collect_group(run, in, sn, db, k0, k1, sh));   // the per-strain reports take what they need while the group is resident
         if (run.cfg->image_cache == 2) {   // leave images behind for the next run
             for (uint32_t k = k0; k < k1; ++k)
                 if (src[sh.use[k]].kind != 1) {

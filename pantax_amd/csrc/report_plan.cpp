@@ -20,14 +20,18 @@ bool plan_row(const ReportRow &row, const pantax_hip_profiling_config *cfg, int 
 }
 // a field of the sized extension, read only where the caller's struct holds all of it (the caller's object may be shorter than this header's struct: the
 // offset comes from an object of our own, the value through a copy of its bytes)
-const char *ext_field(const pantax_hip_profile_ext *ext, const char *pantax_hip_profile_ext::*field) {
-    if (!ext) return nullptr;
-    static const pantax_hip_profile_ext layout{};
+template <class Ext, class T> bool ext_value(const pantax_hip_profile_ext *ext, T Ext::*field, T &value) {
+    if (!ext) return false;
+    static const Ext layout{};
     const size_t at = (size_t)(reinterpret_cast<const char *>(&(layout.*field)) - reinterpret_cast<const char *>(&layout));
-    if (at + sizeof(const char *) > ext->struct_size) return nullptr;
-    const char *value = nullptr;
+    if (at + sizeof(T) > ext->struct_size) return false;
     std::memcpy(&value, reinterpret_cast<const char *>(ext) + at, sizeof(value));
-    return value;
+    return true;
+}
+// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2, which begins with it)
+template <class Ext> const char *ext_field(const pantax_hip_profile_ext *ext, const char *Ext::*field) {
+    const char *value = nullptr;
+    return ext_value(ext, field, value) ? value : nullptr;
 }
 // ... and when a wanted report runs
 bool runs(bool want, bool strain, bool full_path, bool strain_done) { return want && strain && !(full_path && strain_done); }
@@ -54,12 +58,25 @@ bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, R
 
 bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, ReportPlan &plan, std::string &err) {
     for (int i = 0; i < N_EXT_REPORTS; ++i) { plan.ext_path[i].clear(); plan.ext_want[i] = plan.ext_run[i] = false; }
+    for (int i = 0; i < N_EXT2_REPORTS; ++i) { plan.ext2_path[i].clear(); plan.ext2_want[i] = plan.ext2_run[i] = false; }
     if (ext && (ext->struct_size < 8 || ext->struct_size % 8 != 0)) {
         err = "profile: pantax_hip_profile_ext.struct_size " + std::to_string((unsigned long long)ext->struct_size) + " (a multiple of 8, at least 8)";
         return false;
     }
     for (int i = 0; i < N_EXT_REPORTS; ++i)
         if (!plan_path(EXT_REPORTS[i], ext_field(ext, EXT_REPORTS[i].field), W, sharded, plan.ext_path[i], plan.ext_want[i], err)) return false;
+    for (int i = 0; i < N_EXT2_REPORTS; ++i)
+        if (!plan_path(EXT2_REPORTS[i], ext_field(ext, EXT2_REPORTS[i].field), W, sharded, plan.ext2_path[i], plan.ext2_want[i], err)) return false;
+    plan.bs_replicates = 100; plan.bs_seed = 42;
+    if (plan.ext2_want[X2REP_BOOTSTRAP]) {
+        uint64_t n = 0, seed = 42;
+        if (ext_value(ext, &pantax_hip_profile_ext2::strain_bootstrap_replicates, n) && n > 0xFFFFFFFEull) {
+            err = "profile: strain_bootstrap_replicates " + std::to_string((unsigned long long)n) + " (at most 2^32 - 2)";
+            return false;
+        }
+        if (n) plan.bs_replicates = (uint32_t)n;
+        if (ext_value(ext, &pantax_hip_profile_ext2::strain_bootstrap_seed, seed)) plan.bs_seed = seed;
+    }
     return true;
 }
 
@@ -67,6 +84,7 @@ void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_d
     for (int i = 0; i < N_REPORTS; ++i) plan.run[i] = runs(plan.want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_PAIR_REPORTS; ++i) plan.pair_run[i] = runs(plan.pair_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT_REPORTS; ++i) plan.ext_run[i] = runs(plan.ext_want[i], strain, full_path, strain_done);
+    for (int i = 0; i < N_EXT2_REPORTS; ++i) plan.ext2_run[i] = runs(plan.ext2_want[i], strain, full_path, strain_done);
 }
 
 }  // namespace ptx

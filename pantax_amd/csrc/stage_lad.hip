@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <vector>
 #include "lad.hpp"
+#include "lad_args.hpp"
 #include "lad_device.hpp"
 #include "second_filter.hpp"
 #include "primitives.hpp"
@@ -133,35 +134,6 @@ enum { C_LB = 0, C_UB = 1, C_PAT = 2, C_FIXED = 3 };
 #else
 #define LAD_TICK(ph) do { } while (0)
 #endif
-struct LadArgs {
-    unsigned long long *prof;   // LAD_PROFILE builds only (null otherwise)
-    const double *row_a;
-    const uint64_t *pat_mask;
-    const uint32_t *pat_start;
-    const uint32_t *sp_pat_off;
-    double *pat_eps, *sc_s, *sc_rho;
-    uint32_t *sc_lo, *sc_up, *ls_lo, *ls_hi, *ls_mid;
-    const int32_t *sp_p;
-    const uint8_t *need;    // [S] or null: solve only species with need[s] != 0
-    const uint8_t *fixed;   // [H] at col_off[s] + k, or null: variables pinned to zero
-    const double *amax;
-    double *x_out;          // [H] at col_off[s] + k
-    int32_t *status, *iters;
-    const uint64_t *col_off;   // [S+1] first column slot of every species (= its first haplotype)
-    // wide species (more than LAD_MAXP columns): the mask words of pattern k of species s are
-    // pat_or[(wide_off[s] + k - sp_pat_off[s]) * NW ..]; W / G live in global scratch, slot wide_slot[s]
-    const uint32_t *wide_list, *wide_off, *wide_slot;
-    const uint64_t *pat_or, *pat_and;
-    double *wide_W, *wide_G;
-    // wide_off counts groups of LAD_WIDE_NW words; a species of more than LAD_WIDEP haplotypes ("huge") has wide_nw[s] > LAD_WIDE_NW
-    // words per node and per pattern.  W of wide slot i starts at wide_woff[i] (G at twice that), rows of 64 * wide_nw doubles;
-    // the column state of a huge species (x, c, d, ub, ... of lad_solve_body) at wide_coff[i] columns into huge_f64 (x 8) / huge_i32 (x 5);
-    // pat_act[k] = the basis slot that holds pattern k, or -1 (huge species only)
-    const uint32_t *wide_nw;
-    const uint64_t *wide_woff, *wide_coff;
-    double *huge_f64;
-    int *huge_i32, *pat_act;
-};
 
 template <int PS>
 struct LadShared {
@@ -1167,6 +1139,21 @@ int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const
     PTX_TRY(lad_prof_end(ctx, S, prof, d_iters));
 #endif
     return objective_launch(ctx, db, lb, nullptr, d_x, nullptr, d_obj, nullptr);
+}
+
+// The solver on plain arrays (lad_args.hpp): one workgroup per entry of A.sp_p, n_lps of them, every one with at most LAD_MAXP columns -- the caller's
+// tables stand where a LadBatch's do (pantax_hip_strain_bootstrap: a (replicate, species) pair is one entry).  The two one-word instances only; no
+// objective pass behind it.
+int lad_args_launch(Ctx *ctx, const LadArgs &A, uint32_t n_lps, int pmax_bound, const char *timer_name) {
+    if (n_lps == 0) return 0;
+    if (pmax_bound > LAD_MAXP) return fail(ctx, PANTAX_HIP_E_LIMIT, "lad solver: %d columns through the plain-array entry (at most %d)", pmax_bound, LAD_MAXP);
+    {
+        KTimer t(ctx, timer_name);
+        if (pmax_bound <= 16) hipLaunchKernelGGL((lad_solve_kernel<16, 1>), dim3(n_lps), dim3(LAD_BLOCK), 0, ctx->stream, A);
+        else hipLaunchKernelGGL((lad_solve_kernel<LAD_MAXP, 1>), dim3(n_lps), dim3(LAD_BLOCK), 0, ctx->stream, A);
+    }
+    PTX_HIP(ctx, hipGetLastError());
+    return 0;
 }
 
 }  // namespace ptx

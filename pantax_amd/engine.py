@@ -394,6 +394,25 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_fit(self.ctx, self.db, C.byref(cs), p(hap) if len(sh) else None, p(species) if self.S else None))
         return hap, species
 
+    def strain_bootstrap(self, sel_off, sel_hap, sp_key, seed=42, n_replicates=100):
+        """Bootstrap of the strain fit (pantax_hip_strain_bootstrap) on the coverage result get_node_abundances left on the device.  sel_off [S+1], sel_hap as
+        for strain_evidence (entry c of species s is column c - sel_off[s] of its LP), sp_key uint64 [S]: the species' key of the weight hash -> (x float64
+        [R, C], obj float64 [R, S], rows uint64 [R, S], status int32 [R, S]) with R = n_replicates + 1; replicate 0 is the plain refit."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        sk = as_c(sp_key, np.uint64)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]) or len(sk) != self.S:
+            raise ValueError("strain_bootstrap: sel_off needs S + 1 entries, sel_hap sel_off[-1], sp_key S")
+        R = int(n_replicates) + 1
+        cs = _ffi.BootstrapSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, sk.ctypes.data if self.S else None, int(seed), int(n_replicates))
+        x = np.zeros((R, len(sh)), dtype=np.float64)
+        obj = np.zeros((R, self.S), dtype=np.float64)
+        rows = np.zeros((R, self.S), dtype=np.uint64)
+        status = np.zeros((R, self.S), dtype=np.int32)
+        self._check(self.lib.pantax_hip_strain_bootstrap(self.ctx, self.db, C.byref(cs), p(x) if len(sh) else None, p(obj) if self.S else None,
+                                                         p(rows) if self.S else None, p(status) if self.S else None))
+        return x, obj, rows, status
+
     def strain_depth(self, sel_off, sel_hap, species=True):
         """Per-strain depth distribution (pantax_hip_strain_depth) of the coverage result get_node_abundances left on the device.
         sel_off [S+1], sel_hap as for strain_evidence -> (hap uint64 [C, 2, 96, 2]: the histograms all / private of every selection entry,
@@ -619,7 +638,8 @@ class Engine:
                 reads_binning_file=None, range_file=None, species_len_file=None, image_cache=0, rank=0, world_size=1,
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
                 strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
-                strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None, strain_fit_file=None):
+                strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None, strain_fit_file=None,
+                strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -629,7 +649,8 @@ class Engine:
         strain_depth_file: path of the per-strain depth distribution report (--strain-depth; one rank only).  strain_near_miss_file: path of the
         unreported-strain near-miss report (--strain-near-miss; one rank only), strain_near_miss_top the candidates it prints per species (0: 5).
         strain_pair_evidence_file: path of the pairwise strain evidence report (--strain-pair-evidence; one rank only).  strain_fit_file: path of the
-        model fit report (--strain-fit; one rank only); given, the call goes through pantax_hip_profile_with_ext."""
+        model fit report (--strain-fit; one rank only); given, the call goes through pantax_hip_profile_with_ext.  strain_bootstrap_file: path of the
+        bootstrap report (--strain-bootstrap; one rank only), strain_bootstrap_replicates the resamples (0: 100), strain_bootstrap_seed their seed."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -672,10 +693,11 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
-            ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file))
+            ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
+                                  strain_bootstrap_replicates=int(strain_bootstrap_replicates), strain_bootstrap_seed=int(strain_bootstrap_seed))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -818,6 +840,25 @@ class Engine:
 def depth_bin(d):
     """pantax_hip_depth_bin: the histogram bin (0 .. 95) of a node depth (any integer 0 <= d < 2^64).  Host only: no Engine is needed."""
     return int(_ffi.load().pantax_hip_depth_bin(int(d)))
+
+
+def bootstrap_weight(seed, sp_key, replicate, v_local):
+    """pantax_hip_bootstrap_weight: the weight (0 .. 16) of node v_local of the species with key sp_key in bootstrap replicate `replicate` (0: always 1).
+    Host only: no Engine is needed."""
+    return int(_ffi.load().pantax_hip_bootstrap_weight(int(seed), int(sp_key), int(replicate), int(v_local)))
+
+
+def bootstrap_summary(x, status=None):
+    """pantax_hip_bootstrap_summary over the replicates b >= 1: x their values, status their LP statuses (None: all solved) -> float64 [10] = {n_solved, mean,
+    sd, q025, q25, q50, q75, q975, zero_fraction, min}.  Host only."""
+    xv = as_c(x, np.float64)
+    st = None if status is None else as_c(status, np.int32)
+    if xv.ndim != 1 or (st is not None and st.shape != xv.shape):
+        raise ValueError("bootstrap_summary: x and status are one-dimensional and of one length")
+    out = np.zeros(10, dtype=np.float64)
+    if _ffi.load().pantax_hip_bootstrap_summary(len(xv), p(xv) if len(xv) else None, p(st) if st is not None and len(st) else None, p(out)) != 0:
+        raise ValueError("bootstrap_summary: refused")
+    return out
 
 
 def depth_bin_range(b):
