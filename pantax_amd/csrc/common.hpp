@@ -163,7 +163,7 @@ struct CtxConfig {
     bool ncs_no_prefix = false;      // node statistics of long-node graphs through the per-lane word loop (round 5's kernel; tests compare, measurements)
     bool cov_arena_verify = false;   // tests: a coverage pass that skips its zero fill first checks that the arena IS zero (fails with PANTAX_HIP_E_STATE)
     // measurement shapes
-    int cov_item_groups = 0;         // groups of 64 steps per work item of the short-read coverage kernel (0: 64)
+    int cov_item_groups = 0;         // groups of 64 steps per work item of the short-read coverage kernel (0: COV_ITEM_GROUPS = 128; clamped to [1, 256] by build_step_read)
     int tv_u = 4, tv_rounds = 4, tf_u = 8, tf_rounds = 1, rows_u = 1, tb_slots = 256, trio_xcd = 3, cov_shape = -1, covf_shape = -1, cov_xcd = 0, group_bucket_bits = 0;
     uint32_t tv_ablate = 0, cov_ablate = 0, ssn_ablate = 0;
     bool trio_two_pass = false;      // every build through records + prefix + rows kernel, as a db's first build (tests, measurements)

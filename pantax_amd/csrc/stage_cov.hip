@@ -342,6 +342,8 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
             const uint32_t off = v[u] - wlo;                                  // unsigned wrap: nodes below the window are out of range too
             const bool inw = off < win_n;
             if (live[u] & !earlier & (aln != 0u) && !ABL(2u)) {               // :881 / :828
+                // (the 32-bit LDS sum of a work item: build_step_read cuts items of at most 256 groups, 16384 steps x (2^18 - 1) < 2^32; LONG's cuts
+                // of the stream are covl_shape's chunk_groups, which nothing bounds this way)
                 if (inw & (aln < (1u << 18))) atomicAdd(&S_WIN(off), aln);
                 else atomicAdd(&bases[v[u]], (unsigned long long)aln);
             }

@@ -328,7 +328,8 @@ int build_step_read(Ctx *ctx, Reads *rd, uint32_t max_node_id) {
         fg[0] = 0;                                                  // groups in front of the first live one (pads) belong to the first block
         std::vector<uint2> items;
         rd->h_item_block.clear();
-        const uint32_t cap = ctx->cfg.cov_item_groups > 0 ? (uint32_t)ctx->cfg.cov_item_groups : COV_ITEM_GROUPS;
+        // at most 256 groups: the LDS `bases` window sums an item's 32-bit lengths, 256 x 64 steps x (2^18 - 1) < 2^32 (S_WIN in coverage_fast_kernel, stage_cov.hip)
+        const uint32_t cap = ctx->cfg.cov_item_groups > 0 ? (uint32_t)std::min(ctx->cfg.cov_item_groups, 256) : COV_ITEM_GROUPS;
         if (monotone)
             for (uint32_t b = 0; b < NBLK; ++b)
             {   // a block's groups in EQUAL items of at most `cap` groups (81 groups: 41 + 40, not 64 + 17 -- a workgroup zeroes and flushes its LDS windows once per item)

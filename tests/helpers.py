@@ -575,3 +575,16 @@ def gaf_id_edge_text():
     rest = b"\t150\t0\t150\t+\t>3>4\t400\t3\t153\t150\t150\t60\n"
     return (b"\t150\t0\t150\t+\t>1\t400\t3\t153\t150\t150\t60\n" + b"a" + rest + b"abcdefg" + rest + b"abcdefgh" + rest + b"abcdefghi" + rest
             + b"notab\n" + b"\t\n" + b"crlf_no_tab\r\n" + b"x\t1\r\n" + b"@c\n" + b"lastline_without_tab")
+
+
+def oracle_coverage(species, reads, sp, keep=None):
+    """per species of a db: (trio table, bases, cov, trio_bases, aborts) of the C oracle over the reads binned to it (sp: the species of every read;
+    keep: a mask of the reads that count)"""
+    from oracle import oracle as orc
+    out = []
+    for si, g in enumerate(species):
+        G = orc.Graph(g.node_len, g.path_off, g.path_nodes)
+        T = orc.TrioTable(G)
+        so, nid, ps, pe = select_reads(reads, np.nonzero((sp == si) if keep is None else (sp == si) & keep)[0])
+        out.append((T,) + orc.node_coverage(G, T, g.range_start, so, nid, ps, pe))
+    return out
