@@ -505,6 +505,34 @@ uint32_t pantax_hip_bootstrap_weight(uint64_t seed, uint64_t sp_key, uint32_t re
  * PANTAX_HIP_E_INVALID for a null out, or a null x with n > 0. */
 int pantax_hip_bootstrap_summary(uint64_t n, const double *x, const int32_t *status, double *out /*[10]*/);
 
+/* ---- leave-one-out test of the strain fit (the --strain-dropout report; not a stage of the reference): does the sample need a reported strain at all, or
+ * is the L1 fit as good without it?  The bootstrap cannot say: a strain whose coverage another strain absorbs at no cost is as stable as a well-founded one.
+ * Selection, Sel_s, K_s, M(v), the inputs, the state rules and the argument errors are those of pantax_hip_strain_bootstrap without sp_key, seed and
+ * replicates; the rows of species s are the rows of its replicate 0 (every node with a_v > 0 and mask_v != 0, column k = selection entry sel_off[s] + k).
+ *   Species s has E_s = K_s + 1 entries.  Entry 0 is the plain refit; entry k + 1 is the same LP with column k pinned to zero: 0 <= x_j <= 1.05 max a for
+ *   j != k (max a over the species' rows, the same in every entry), x_k = 0; the rows and their masks stay, so a row with mask_v = {k} stays in the objective
+ *   with prediction 0 and costs a_v.  (profile.rs:1333-1451 on the selected columns with one column's upper bound at zero.)
+ * Outputs, sized by the caller; entry (s, e) has index q = sel_off[s] + s + e, Q = C + S entries exist:
+ *   x_out      per species a block of E_s x K_s doubles at x_off[s] = sum over t < s of E_t K_t, entry-major; x[e][k] of entry e = k + 1 is exactly 0.0;
+ *   obj_out    [Q] sum over the rows of |a_v - sum_j x_j bit_j(mask_v)| at the entry's x (a sum, as in the bootstrap);
+ *   status_out [Q] 0 solved;  1 nothing to solve (no row, or K_s = 0: x = 0, obj = 0);  PANTAX_HIP_E_LIMIT K_s > 64 (the other species are served);
+ *              PANTAX_HIP_E_SOLVER that LP alone failed;
+ *   rows_out   [S] the species' rows;
+ *   count_out  [Q][4] = { n_member, n_only, n_worse, n_better } of entry k + 1: rows with bit k; rows with mask == 1 << k; rows whose absolute residual
+ *              under entry k + 1 is strictly larger / strictly smaller than under entry 0.  Entry 0 holds { rows, 0, 0, 0 }.  The residual of a row is
+ *              fabs(s - a), s the f64 sum of the entry's x_j over the set bits in ascending j: the counts are a function of the delivered x.
+ * The call fails as a whole only on invalid arguments, a HIP error or PANTAX_HIP_E_LIMIT of its own (32-bit row positions; one round of LPs -- entry e of
+ * every species over one copy of the pattern tables -- that does not fit the option dropout_patterns_max, the cap on the replicated patterns in flight,
+ * 0 = from the free device memory); on an error the outputs are left as given.  Determinism: the same inputs give the same bits, whatever the chunking
+ * of the rounds (dropout_patterns_max), the membership route (option dropout_route=walk) and the position of the species in the db; the objective is summed
+ * in an order that is a function of the species' sorted rows alone. */
+int pantax_hip_strain_dropout(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, double *x_out, double *obj_out /*[Q]*/,
+                              int32_t *status_out /*[Q]*/, uint64_t *rows_out /*[S]*/, uint64_t *count_out /*[Q][4]*/);
+/* host helper, no ctx and no GPU: who takes over when column k of K is dropped.  x_full / x_drop [K]: the x of entry 0 and of entry k + 1.
+ * out[3] = { the column j != k with the largest x_drop[j] - x_full[j] (ties: the lowest j), -1 when no difference is positive;  that gain (0 when none);
+ * sum over j != k of |x_drop[j] - x_full[j]| in ascending j }.  PANTAX_HIP_E_INVALID for a null argument or k >= K. */
+int pantax_hip_dropout_substitute(uint32_t K, uint32_t k, const double *x_full, const double *x_drop, double *out /*[3]*/);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -817,6 +845,23 @@ typedef struct {
     uint64_t strain_bootstrap_replicates;   /* 0 reads as 100; beyond 2^32 - 2: PANTAX_HIP_E_INVALID */
     uint64_t strain_bootstrap_seed;         /* a struct that does not hold the field reads as 42, the seed of the row sampler; the front ends default to 42 */
 } pantax_hip_profile_ext2;
+/* ... and once more: pantax_hip_profile_ext2 is closed at strain_bootstrap_seed (a committed host check holds its 40 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the second version.  A caller fills v2.v1.struct_size = sizeof(pantax_hip_profile_ext3) and passes
+ * &ext3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16- or 40-byte struct runs with the fields below off.  A later output is a field appended here. */
+typedef struct {
+    pantax_hip_profile_ext2 v2;   /* v2.v1.struct_size = sizeof(pantax_hip_profile_ext3) */
+    /* --strain-dropout: path of the leave-one-out report (pantax_hip_strain_dropout over every group of species, right behind the group's bootstrap, on the
+     * same coverage result; NULL, "" or "None" = off).  Sel_s = the species' rows of strain_abundance.txt in ascending haplotype index.  TSV with a header:
+     * species_taxid, strain_taxid, genome_ID, class, predicted_coverage, refit, n_rows, objective, objective_without, delta, delta_fraction, n_member,
+     * n_only, n_worse, n_better, substitute_strain_taxid, substitute_genome_ID, substitute_gain, shift; f64 in shortest round-trip digits, "-" where a
+     * column does not apply.  First the strains in the order of strain_abundance.txt, class "strain": predicted_coverage = the unrounded second_sol,
+     * refit = x of entry 0, n_rows and objective of entry 0, objective_without = the objective of the strain's entry k + 1, delta = objective_without -
+     * objective, delta_fraction = delta / objective_without ("-" when that is 0), the four counts of entry k + 1, the substitute columns and shift from
+     * pantax_hip_dropout_substitute ("-" when there is none; refit .. shift are "-" where entry 0 or entry k + 1 is not solved).  Then every species that went
+     * through a strain step and has rows in the table, in the order the run took them, class "species" ("skipped" for more than 64 rows): n_rows and
+     * objective, the rest "-".  Same rules as strain_fit_file. */
+    const char *strain_dropout_file;
+} pantax_hip_profile_ext3;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

@@ -623,6 +623,22 @@ int pantax_hip_strain_bootstrap(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
     }
 }
 
+int pantax_hip_strain_dropout(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, double *x_out, double *obj_out, int32_t *status_out,
+                              uint64_t *rows_out, uint64_t *count_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_dropout: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_dropout", sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_dropout", sel->sel_off, sel->sel_hap));
+    if ((sel->sel_off[db->S] && !x_out) || (db->S && (!obj_out || !status_out || !rows_out || !count_out))) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_dropout: null output array");
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_dropout"));
+    try {
+        return dropout_launch(ctx, db, sel->sel_off, sel->sel_hap, x_out, obj_out, status_out, rows_out, count_out);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_dropout: out of host memory");
+    }
+}
+
 int pantax_hip_db_hap_pairs(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out,
                             uint64_t *species_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;

@@ -49,6 +49,9 @@ static void usage() {
             "                     its mean, sd, quantiles and zero fraction over N Poisson resamples of the LP's rows, its share of the species and the share's\n"
             "                     0.025 and 0.975 quantiles; per species the rows and the objective (one rank only)\n"
             "  --strain-bootstrap-replicates N   resamples (default 100)     --strain-bootstrap-seed N   their seed (default 42)\n"
+            "  --strain-dropout F   leave-one-out test of the strain fit: for every row of strain_abundance.txt the objective of a refit of the reported strains\n"
+            "                     with and without it (delta), the rows it walks, walks alone, that fit worse and better without it, and the strain that takes\n"
+            "                     over its coverage (substitute); per species the rows and the objective (one rank only)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -74,9 +77,10 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
-    pantax_hip_profile_ext2 ext;   // the outputs added behind the config's last field
-    memset(&ext, 0, sizeof(ext));
-    ext.v1.struct_size = sizeof(ext);
+    pantax_hip_profile_ext3 ext3;   // the outputs added behind the config's last field
+    memset(&ext3, 0, sizeof(ext3));
+    pantax_hip_profile_ext2 &ext = ext3.v2;
+    ext.v1.struct_size = sizeof(ext3);
     ext.strain_bootstrap_seed = 42;
     pantax_hip_db_pairs_config pairs;
     memset(&pairs, 0, sizeof(pairs));
@@ -143,6 +147,7 @@ int main(int argc, char **argv) {
         else if (a == "--strain-bootstrap") ext.strain_bootstrap_file = next();
         else if (a == "--strain-bootstrap-replicates") ext.strain_bootstrap_replicates = strtoull(next(), nullptr, 10);
         else if (a == "--strain-bootstrap-seed") ext.strain_bootstrap_seed = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-dropout") ext3.strain_dropout_file = next();
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

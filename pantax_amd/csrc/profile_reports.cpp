@@ -1,8 +1,8 @@
 // profile_reports.cpp -- the per-strain reports of the file seam (profile_reports.hpp): per group of species, behind its strain step, the group's rows of
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
-// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report and the bootstrap report, whose files are
-// named in the seam's sized extension (EXT_REPORTS, EXT2_REPORTS).
+// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report and the leave-one-out
+// report, whose files are named in the seam's sized extension (EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS).
 #include <algorithm>
 #include <fstream>
 #include <unordered_map>
@@ -116,6 +116,38 @@ int group_bootstrap(Run &run, const Ingest &in, const Selection &sn, pantax_hip_
         }
     }
     run.lap("  strain bootstrap");
+    return 0;
+}
+// --strain-dropout, on the same coverage result: Sel_s = the group's rows (column = position: ascending haplotype)
+int group_dropout(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &dr = sh.rep.dr;
+    const uint32_t Sg = k1 - k0;
+    const uint64_t Cg = g.hap.size(), Q = Cg + Sg;
+    uint64_t X = 0;
+    for (uint32_t k = 0; k < Sg; ++k) { const uint64_t K = g.off[k + 1] - g.off[k]; X += (K + 1) * K; }
+    const pantax_hip_evidence_set set{Sg, g.off.data(), g.hap.data()};
+    std::vector<double> x(X ? X : 1), obj(Q);
+    std::vector<int32_t> status(Q);
+    std::vector<uint64_t> rows(Sg), cnt(4 * Q);
+    PTX_TRY(pantax_hip_strain_dropout(run.ctx, db, &set, x.data(), obj.data(), status.data(), rows.data(), cnt.data()));
+    const size_t n = g.entry0 + Cg;
+    dr.refit.resize(n); dr.obj_without.resize(n); dr.gain.resize(n); dr.shift.resize(n); dr.cnt.resize(4 * n); dr.st.resize(n); dr.sub.resize(n);
+    uint64_t x0 = 0;
+    for (uint32_t k = 0; k < Sg; ++k) {
+        const uint64_t c0 = g.off[k], K = g.off[k + 1] - c0, q0 = c0 + k;
+        dr.rows[k0 + k] = rows[k]; dr.obj[k0 + k] = obj[q0]; dr.status[k0 + k] = status[q0]; dr.K[k0 + k] = (uint32_t)K;
+        for (uint64_t j = 0; j < K; ++j) {
+            const size_t e = g.entry0 + c0 + j;
+            const double *xf = x.data() + x0, *xd = xf + (j + 1) * K;
+            double o[3] = {-1.0, 0.0, 0.0};
+            if (K <= 64) PTX_TRY(pantax_hip_dropout_substitute((uint32_t)K, (uint32_t)j, xf, xd, o));
+            dr.refit[e] = xf[j]; dr.obj_without[e] = obj[q0 + 1 + j]; dr.st[e] = status[q0 + 1 + j];
+            std::copy(cnt.begin() + 4 * (q0 + 1 + j), cnt.begin() + 4 * (q0 + 1 + j) + 4, dr.cnt.begin() + 4 * e);
+            dr.sub[e] = o[0] < 0 ? -1 : (int64_t)(g.entry0 + c0 + (uint64_t)o[0]); dr.gain[e] = o[1]; dr.shift[e] = o[2];
+        }
+        x0 += (K + 1) * K;
+    }
+    run.lap("  strain dropout");
     return 0;
 }
 // --strain-pair-evidence, on the same coverage result: Sel_s = the group's rows, but for a species of more rows than the call serves, which gets no block
@@ -400,6 +432,45 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-dropout: per row of strain_abundance.txt, in its order, the refit and what the fit loses without the strain; then per species of the shard
+    // with rows in the table, in the order it went through the device, the rows and the objective of the refit ("skipped": more rows than the call serves)
+    int dropout() const {
+        return file(run.p.rep.ext3_path[X3REP_DROPOUT],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tclass\tpredicted_coverage\trefit\tn_rows\tobjective\tobjective_without\tdelta\tdelta_fraction\tn_member\tn_only\tn_worse\tn_better\tsubstitute_strain_taxid\tsubstitute_genome_ID\tsubstitute_gain\tshift\n",
+                    "strain dropout report", [&](std::ofstream &f) {
+            const auto &d = rep.dr;
+            std::vector<const TrackRow *> row_of(d.refit.size(), nullptr);   // entry -> its first row of the table
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "leave-one-out test", &e));
+                if (!row_of[e]) row_of[e] = &r;
+            }
+            for (const TrackRow &r : rows) {
+                const int64_t e = rep.entry[r.hap];
+                f << strain_head(r) << "\tstrain\t" << fmt_f64(sh.met[r.hap].second_sol);
+                if (d.status[r.k] != 0 || d.st[e] != 0) {   // the species was not served, has no row, or one of the two LPs failed
+                    for (int i = 0; i < 14; ++i) f << "\t-";
+                    f << '\n';
+                    continue;
+                }
+                const double delta = d.obj_without[e] - d.obj[r.k];
+                f << '\t' << fmt_f64(d.refit[e]) << '\t' << d.rows[r.k] << '\t' << fmt_f64(d.obj[r.k]) << '\t' << fmt_f64(d.obj_without[e]) << '\t' << fmt_f64(delta) << '\t'
+                  << (d.obj_without[e] != 0.0 ? fmt_f64(delta / d.obj_without[e]) : std::string("-"));
+                for (int c = 0; c < 4; ++c) f << '\t' << d.cnt[4 * e + c];
+                const TrackRow *sub = d.sub[e] >= 0 ? row_of[d.sub[e]] : nullptr;
+                if (sub) f << '\t' << (sub->gr ? sub->gr->strain_taxid : "") << '\t' << (sub->gr ? sub->gr->genome_id : "") << '\t' << fmt_f64(d.gain[e]);
+                else f << "\t-\t-\t-";
+                f << '\t' << fmt_f64(d.shift[e]) << '\n';
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                if (d.K[k] == 0) continue;
+                const bool skipped = d.status[k] != 0 && d.status[k] != 1;
+                f << species_head(k) << '\t' << (skipped ? "skipped" : "species") << "\t-\t-\t" << d.rows[k] << '\t' << (skipped ? std::string("-") : fmt_f64(d.obj[k]));
+                for (int i = 0; i < 11; ++i) f << "\t-";
+                f << '\n';
+            }
+            return 0;
+        });
+    }
     // --strain-read-support: {compatible, unique, assigned} of every row of strain_abundance.txt, in its order; {counted, unexplained, ambiguous, uninformative}
     // of every species of the shard in the order it went through the device (a species without rows: counted only); the shared reads of every pair of rows
     int read_support() const {
@@ -541,6 +612,7 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
         rep.bs.R = (uint64_t)plan.bs_replicates + 1;
         rep.bs.obj.assign(rep.bs.R * Su, 0.0); rep.bs.rows.assign(rep.bs.R * Su, 0); rep.bs.status.assign(rep.bs.R * Su, 1);
     }
+    if (plan.ext3_run[X3REP_DROPOUT]) { rep.dr.rows.assign(Su, 0); rep.dr.obj.assign(Su, 0.0); rep.dr.status.assign(Su, 1); rep.dr.K.assign(Su, 0); }
 }
 int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
     const ReportPlan &plan = run.p.rep;
@@ -552,6 +624,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.run[REP_EVIDENCE]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_evidence, 2 * EVIDENCE_N, 3 * EVIDENCE_N, sh.rep.ev, "  strain evidence"));
     if (plan.ext_run[XREP_FIT]) PTX_TRY(group_fit(run, db, k0, k1, g, sh));
     if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(group_bootstrap(run, in, sn, db, k0, k1, g, sh));
+    if (plan.ext3_run[X3REP_DROPOUT]) PTX_TRY(group_dropout(run, db, k0, k1, g, sh));
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(group_pair_evidence(run, db, k0, k1, g, sh));
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
@@ -573,6 +646,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(w.pair_evidence());
     if (plan.ext_run[XREP_FIT]) PTX_TRY(w.fit());
     if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(w.bootstrap());
+    if (plan.ext3_run[X3REP_DROPOUT]) PTX_TRY(w.dropout());
     return 0;
 }
 }  // namespace reports

@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
-// of pantax_hip_profile_ext2 with its row of EXT2_REPORTS (REPORTS, PAIR_REPORTS and EXT_REPORTS are closed: the structs they point into keep their size), a sub-struct
+// of pantax_hip_profile_ext3 with its row of EXT3_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS and EXT2_REPORTS are closed: the structs they point into keep their size), a sub-struct
 // here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
@@ -32,6 +32,10 @@ struct ReportData {
     NodeSums ft;
     // --strain-bootstrap: R = replicates + 1 values a quantity, replicate 0 first: x[R e ..) of entry e; obj[R k ..), rows[R k ..), status[R k ..) of species k
     struct { uint64_t R = 0; std::vector<double> x, obj; std::vector<uint64_t> rows; std::vector<int32_t> status; } bs;
+    // --strain-dropout: per entry e the refit x, the objective without it, its four counts, the status of its LP, the entry of its substitute (-1: none) with
+    // its gain, and the shift; per species k the rows, the objective and the status of the refit and K[k] = its rows of the table
+    struct { std::vector<double> refit, obj_without, gain, shift, obj; std::vector<uint64_t> cnt, rows; std::vector<int32_t> st, status; std::vector<int64_t> sub;
+             std::vector<uint32_t> K; } dr;
     // --strain-read-support: hap[9e ..) = {compatible, unique, assigned}; species[12k ..) = {counted, unexplained, ambiguous, uninformative}; a species of
     // K[k] = 1..64 rows owns the K x K block of shared reads pair[pair_off[k] ..) over its entries in ascending order
     struct { std::vector<uint64_t> hap, species, pair, pair_off; std::vector<uint32_t> K; } sup;

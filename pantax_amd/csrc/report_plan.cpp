@@ -5,7 +5,7 @@
 namespace ptx {
 
 namespace {
-// the one rule of a row of any of the three tables: its path, whether it is wanted, and the refusal of a wanted report on several ranks or a sharded ingest
+// the one rule of a row of any of the tables: its path, whether it is wanted, and the refusal of a wanted report on several ranks or a sharded ingest
 template <class Row> bool plan_path(const Row &row, const char *path, int W, bool sharded, std::string &path_out, bool &want, std::string &err) {
     path_out = path ? path : "";
     want = !path_out.empty() && path_out != "None";
@@ -28,7 +28,7 @@ template <class Ext, class T> bool ext_value(const pantax_hip_profile_ext *ext, 
     std::memcpy(&value, reinterpret_cast<const char *>(ext) + at, sizeof(value));
     return true;
 }
-// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2, which begins with it)
+// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2 / _ext3, which begin with it)
 template <class Ext> const char *ext_field(const pantax_hip_profile_ext *ext, const char *Ext::*field) {
     const char *value = nullptr;
     return ext_value(ext, field, value) ? value : nullptr;
@@ -59,6 +59,7 @@ bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, R
 bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, ReportPlan &plan, std::string &err) {
     for (int i = 0; i < N_EXT_REPORTS; ++i) { plan.ext_path[i].clear(); plan.ext_want[i] = plan.ext_run[i] = false; }
     for (int i = 0; i < N_EXT2_REPORTS; ++i) { plan.ext2_path[i].clear(); plan.ext2_want[i] = plan.ext2_run[i] = false; }
+    for (int i = 0; i < N_EXT3_REPORTS; ++i) { plan.ext3_path[i].clear(); plan.ext3_want[i] = plan.ext3_run[i] = false; }
     if (ext && (ext->struct_size < 8 || ext->struct_size % 8 != 0)) {
         err = "profile: pantax_hip_profile_ext.struct_size " + std::to_string((unsigned long long)ext->struct_size) + " (a multiple of 8, at least 8)";
         return false;
@@ -67,6 +68,8 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
         if (!plan_path(EXT_REPORTS[i], ext_field(ext, EXT_REPORTS[i].field), W, sharded, plan.ext_path[i], plan.ext_want[i], err)) return false;
     for (int i = 0; i < N_EXT2_REPORTS; ++i)
         if (!plan_path(EXT2_REPORTS[i], ext_field(ext, EXT2_REPORTS[i].field), W, sharded, plan.ext2_path[i], plan.ext2_want[i], err)) return false;
+    for (int i = 0; i < N_EXT3_REPORTS; ++i)
+        if (!plan_path(EXT3_REPORTS[i], ext_field(ext, EXT3_REPORTS[i].field), W, sharded, plan.ext3_path[i], plan.ext3_want[i], err)) return false;
     plan.bs_replicates = 100; plan.bs_seed = 42;
     if (plan.ext2_want[X2REP_BOOTSTRAP]) {
         uint64_t n = 0, seed = 42;
@@ -85,6 +88,7 @@ void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_d
     for (int i = 0; i < N_PAIR_REPORTS; ++i) plan.pair_run[i] = runs(plan.pair_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT_REPORTS; ++i) plan.ext_run[i] = runs(plan.ext_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT2_REPORTS; ++i) plan.ext2_run[i] = runs(plan.ext2_want[i], strain, full_path, strain_done);
+    for (int i = 0; i < N_EXT3_REPORTS; ++i) plan.ext3_run[i] = runs(plan.ext3_want[i], strain, full_path, strain_done);
 }
 
 }  // namespace ptx

@@ -5,7 +5,7 @@
 // mask over the selected haplotypes (column k = position in the species' selection); replicate b repeats row v w_v times, w_v a Poisson(1) weight capped at 16
 // from a hash of (seed, sp_key, b, v_local) (bootstrap_weight.hpp), replicate 0 every row once; every replicate is solved as a LAD of its own rows.
 //
-// Once per call:
+// Once per call -- boot_front_build below, the front half this stage shares with the leave-one-out test of stage_dropout.hip (boot_front.hpp):
 //   boot rows      one chained scan over the nodes: head flag "is a row", the store writes {species, mask, a} and the payload v_local at the prefix (no atomics:
 //                  the same rows in the same places every run).  Membership: the two routes of member_plan.hpp (option bootstrap_route); on route 1 the
 //                  bits of the node's haplotype word are moved to their columns through a 64-entry table per species;
@@ -29,6 +29,7 @@
 #include <cmath>
 #include <vector>
 #include "common.hpp"
+#include "boot_front.hpp"
 #include "bootstrap_plan.hpp"
 #include "bootstrap_weight.hpp"
 #include "lad_args.hpp"
@@ -40,10 +41,6 @@
 namespace ptx {
 
 namespace {
-
-constexpr int32_t BOOT_PENDING = 0x7FFFFFFF;   // pre-status of an entry the solver decides
-
-struct BootSpecies { MemberRow m; uint64_t hash; };   // hash: boot_species_hash(seed, sp_key[s])
 
 // ---- the rows of the call
 struct BootRowSrc {
@@ -237,6 +234,98 @@ __global__ void __launch_bounds__(256) boot_objective_kernel(const int32_t *__re
 
 }  // namespace
 
+// the front half of the bootstrap and of the leave-one-out test (boot_front.hpp)
+int boot_front_build(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed, const std::string &route_opt,
+                     const char *what, const std::function<int(uint64_t)> &sized, BootFront &F) {
+    const uint32_t S = db->S;
+    const uint64_t V = db->V;
+    F.N = 0; F.P = 0; F.k_max = 0;
+    if (V >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "%s: %llu nodes exceed 32-bit positions", what, (unsigned long long)V);
+    const bool by_node = member_by_node(db->nh_built, route_opt);
+    // ---- host tables
+    std::vector<BootSpecies> tab(S);
+    std::vector<uint8_t> bit_col((size_t)S * 64, 0);
+    std::vector<uint32_t> node_off(S + 1);
+    F.pre_host.assign(S, 0);   // per species: E_LIMIT, 1 (nothing selected) or pending
+    WalkMasks &wm = F.wm;
+    uint64_t k_max = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        const uint64_t K = sel_off[s + 1] - sel_off[s];
+        const bool served = K <= 64;
+        tab[s].m = wm.row(db, s, by_node, sel_hap + sel_off[s], served ? K : 0);   // a species beyond the limit has no rows
+        tab[s].hash = sp_key ? boot_species_hash(seed, sp_key[s]) : 0ull;
+        if (tab[s].m.route == 1u) for (uint64_t k = 0; k < K; ++k) bit_col[(size_t)s * 64 + sel_hap[sel_off[s] + k]] = (uint8_t)k;
+        if (served) k_max = std::max(k_max, K);
+        node_off[s] = (uint32_t)db->h_node_off[s];
+        F.pre_host[s] = K > 64 ? PANTAX_HIP_E_LIMIT : (K == 0 ? 1 : BOOT_PENDING);
+    }
+    node_off[S] = (uint32_t)db->h_node_off[S];
+    F.k_max = k_max;
+    if (V == 0 || k_max == 0) return 0;
+    // ---- rows: {species, mask, a} + v_local, compacted by one scan over the nodes
+    PTX_TRY(wm.build(ctx, db));
+    PTX_TRY(upload(ctx, F.d_tab, tab.data(), tab.size()));
+    PTX_TRY(upload(ctx, F.d_bit_col, bit_col.data(), bit_col.size()));
+    PTX_TRY(upload(ctx, F.d_node_off, node_off.data(), node_off.size()));
+    PTX_TRY(upload(ctx, F.d_sel_off, sel_off, (size_t)S + 1));
+    PTX_HIP(ctx, F.d_counts.alloc(4));
+    PTX_HIP(ctx, hipMemsetAsync(F.d_counts.p, 0, 4 * sizeof(uint32_t), ctx->stream));
+    for (int w = 0; w < 3; ++w) PTX_HIP(ctx, F.ka[w].alloc(V));
+    PTX_HIP(ctx, F.d_va.alloc(V));
+    const BootRowSrc src{F.d_node_off.p, S, F.d_tab.p, F.d_bit_col.p, db->d_node_len.p, (const unsigned long long *)db->d_bases.p,
+                         by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, wm.d_mask.p};
+    PTX_TRY(exclusive_scan_fn(ctx, BootRowLoad{src}, BootRowStore{src, F.ka[0].p, F.ka[1].p, F.ka[2].p, F.d_va.p}, V, F.d_counts.p, "scan_chained_kernel<BootRows>"));
+    uint32_t n_rows32 = 0;
+    PTX_TRY(download(ctx, &n_rows32, F.d_counts.p, 1));
+    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t N = n_rows32;
+    if (N == 0) return 0;
+    // ---- the caller's plan, before anything is sized by it
+    PTX_TRY(sized(N));
+    // ---- sort by (species, mask, a), v_local as payload
+    for (int w = 0; w < 3; ++w) PTX_HIP(ctx, F.kb[w].alloc(N));
+    PTX_HIP(ctx, F.d_vb.alloc(N));
+    PTX_HIP(ctx, F.d_table.alloc(sort_table_elems(N)));
+    PTX_HIP(ctx, F.d_scan_tmp.alloc(scan_tmp_elems(std::max<uint64_t>(N, 256ull * 2048))));
+    SortBufs A, B;
+    A.nw = B.nw = 3;
+    for (int w = 0; w < 3; ++w) { A.k[w] = F.ka[w].p; B.k[w] = F.kb[w].p; }
+    A.v = F.d_va.p; B.v = F.d_vb.p;
+    std::vector<SortPass> passes;
+    add_passes(passes, 2, 0, 63);                       // a > 0: sign bit clear
+    add_passes(passes, 1, 0, (int)k_max);
+    if (S > 1) add_passes(passes, 0, 0, bits_for(S - 1));
+    bool in_b = false;
+    PTX_TRY(radix_sort(ctx, A, B, N, passes.data(), (int)passes.size(), F.d_table.p, F.d_scan_tmp.p, &in_b));
+    const SortBufs &Sd = in_b ? B : A;
+    F.row_sp = Sd.k[0]; F.row_mask = Sd.k[1];
+    F.base_a = reinterpret_cast<const double *>(Sd.k[2]);
+    F.vloc = Sd.v;
+    // ---- base patterns
+    PTX_HIP(ctx, F.d_bpat_mask.alloc(N)); PTX_HIP(ctx, F.d_bpat_start.alloc(N + 1)); PTX_HIP(ctx, F.d_bpat_species.alloc(N)); PTX_HIP(ctx, F.d_bsp_pat_off.alloc((size_t)S + 1));
+    PTX_TRY(exclusive_scan_fn(ctx, BootPatLoad{Sd.k[0], Sd.k[1]}, BootPatStore{Sd.k[0], Sd.k[1], F.d_bpat_mask.p, F.d_bpat_start.p, F.d_bpat_species.p}, N, F.d_counts.p + 1,
+                              "scan_chained_kernel<BootPat>"));
+    uint32_t P = 0;
+    PTX_TRY(download(ctx, &P, F.d_counts.p + 1, 1));
+    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (P == 0 || P > N) return fail(ctx, PANTAX_HIP_E_STATE, "%s: internal (%u patterns of %llu rows)", what, P, (unsigned long long)N);
+    hipLaunchKernelGGL(boot_sp_pat_off_kernel, dim3((S + 1 + 255) / 256), dim3(256), 0, ctx->stream, S, P, (uint32_t)N, F.d_bpat_species.p, F.d_bpat_start.p, F.d_bsp_pat_off.p);
+    PTX_HIP(ctx, hipGetLastError());
+    F.N = N; F.P = P;
+    return 0;
+}
+
+int boot_objective_launch(Ctx *ctx, uint32_t nq, const int32_t *sp_p, const uint32_t *sp_pat_off, const uint64_t *pat_mask, const uint32_t *pat_start, const double *row_a,
+                          const uint64_t *col_off, const double *x, double *part, double *obj, const char *timer_name) {
+    if (nq == 0) return 0;
+    {
+        KTimer tm(ctx, timer_name);
+        hipLaunchKernelGGL(boot_objective_kernel, dim3(nq), dim3(256), 0, ctx->stream, sp_p, sp_pat_off, pat_mask, pat_start, row_a, col_off, x, part, obj);
+    }
+    PTX_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 // selection and sp_key validated by the caller
 int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed, uint32_t n_replicates, double *x_out,
                      double *obj_out, uint64_t *rows_out, int32_t *status_out) {
@@ -245,25 +334,26 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
     if (S == 0) return 0;
     if (V >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_bootstrap: %llu nodes exceed 32-bit positions", (unsigned long long)V);
     if (R * std::max<uint64_t>(C, S) >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_bootstrap: %llu replicates of %llu selection entries and %u species exceed 32-bit positions", (unsigned long long)R, (unsigned long long)C, S);
-    const bool by_node = member_by_node(db->nh_built, ctx->cfg.bootstrap_route);
-    // ---- host tables
-    std::vector<BootSpecies> tab(S);
-    std::vector<uint8_t> bit_col((size_t)S * 64, 0);
-    std::vector<uint32_t> node_off(S + 1);
-    std::vector<int32_t> pre_host(S);   // per species: E_LIMIT, 1 (nothing selected) or pending
-    WalkMasks wm;
-    uint64_t k_max = 0;
-    for (uint32_t s = 0; s < S; ++s) {
-        const uint64_t K = sel_off[s + 1] - sel_off[s];
-        const bool served = K <= 64;
-        tab[s].m = wm.row(db, s, by_node, sel_hap + sel_off[s], served ? K : 0);   // a species beyond the limit has no rows
-        tab[s].hash = boot_species_hash(seed, sp_key[s]);
-        if (tab[s].m.route == 1u) for (uint64_t k = 0; k < K; ++k) bit_col[(size_t)s * 64 + sel_hap[sel_off[s] + k]] = (uint8_t)k;
-        if (served) k_max = std::max(k_max, K);
-        node_off[s] = (uint32_t)db->h_node_off[s];
-        pre_host[s] = K > 64 ? PANTAX_HIP_E_LIMIT : (K == 0 ? 1 : BOOT_PENDING);
+    // ---- the plan of the chunks, once the rows are counted
+    BootstrapPlan plan;
+    const auto sized = [&](uint64_t n_rows) {
+        uint64_t cap = ctx->cfg.bootstrap_rows_max;
+        if (cap == 0) {
+            size_t free_b = 0, total_b = 0;
+            PTX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+            cap = bootstrap_default_cap(free_b);
+        }
+        std::string why;
+        if (!bootstrap_plan(n_rows, R, cap, plan, why)) return fail(ctx, PANTAX_HIP_E_LIMIT, "%s", why.c_str());
+        return 0;
+    };
+    // ---- host tables, rows, sort, base patterns (boot_front.hpp)
+    BootFront F;
+    {
+        const int rc = boot_front_build(ctx, db, sel_off, sel_hap, sp_key, seed, ctx->cfg.bootstrap_route, "strain_bootstrap", sized, F);
+        if (rc != 0) return rc;
     }
-    node_off[S] = (uint32_t)db->h_node_off[S];
+    const std::vector<int32_t> &pre_host = F.pre_host;
     // results on the host; the caller's arrays are written at the very end
     std::vector<double> hx((size_t)(R * C)), hobj((size_t)(R * S), 0.0);
     std::vector<uint64_t> hrows((size_t)(R * S), 0);
@@ -275,69 +365,14 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
         std::copy(hrows.begin(), hrows.end(), rows_out); std::copy(hstatus.begin(), hstatus.end(), status_out);
         return 0;
     };
-    if (V == 0 || k_max == 0) return deliver();
-    // ---- rows: {species, mask, a} + v_local, compacted by one scan over the nodes
-    DevBuf<BootSpecies> d_tab;
-    DevBuf<uint8_t> d_bit_col;
-    DevBuf<uint32_t> d_node_off, d_counts, d_va, d_vb, d_table, d_scan_tmp;
-    DevBuf<uint64_t> d_sel_off, ka[3], kb[3];
-    PTX_TRY(wm.build(ctx, db));
-    PTX_TRY(upload(ctx, d_tab, tab.data(), tab.size()));
-    PTX_TRY(upload(ctx, d_bit_col, bit_col.data(), bit_col.size()));
-    PTX_TRY(upload(ctx, d_node_off, node_off.data(), node_off.size()));
-    PTX_TRY(upload(ctx, d_sel_off, sel_off, (size_t)S + 1));
-    PTX_HIP(ctx, d_counts.alloc(4));
-    PTX_HIP(ctx, hipMemsetAsync(d_counts.p, 0, 4 * sizeof(uint32_t), ctx->stream));
-    for (int w = 0; w < 3; ++w) PTX_HIP(ctx, ka[w].alloc(V));
-    PTX_HIP(ctx, d_va.alloc(V));
-    const BootRowSrc src{d_node_off.p, S, d_tab.p, d_bit_col.p, db->d_node_len.p, (const unsigned long long *)db->d_bases.p,
-                         by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, wm.d_mask.p};
-    PTX_TRY(exclusive_scan_fn(ctx, BootRowLoad{src}, BootRowStore{src, ka[0].p, ka[1].p, ka[2].p, d_va.p}, V, d_counts.p, "scan_chained_kernel<BootRows>"));
-    uint32_t n_rows32 = 0;
-    PTX_TRY(download(ctx, &n_rows32, d_counts.p, 1));
-    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const uint64_t N = n_rows32;
-    if (N == 0) return deliver();
-    // ---- the plan of the chunks, before anything is sized by it
-    uint64_t cap = ctx->cfg.bootstrap_rows_max;
-    if (cap == 0) {
-        size_t free_b = 0, total_b = 0;
-        PTX_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-        cap = bootstrap_default_cap(free_b);
-    }
-    BootstrapPlan plan;
-    std::string why;
-    if (!bootstrap_plan(N, R, cap, plan, why)) return fail(ctx, PANTAX_HIP_E_LIMIT, "%s", why.c_str());
-    // ---- sort by (species, mask, a), v_local as payload
-    for (int w = 0; w < 3; ++w) PTX_HIP(ctx, kb[w].alloc(N));
-    PTX_HIP(ctx, d_vb.alloc(N));
-    PTX_HIP(ctx, d_table.alloc(sort_table_elems(N)));
-    PTX_HIP(ctx, d_scan_tmp.alloc(scan_tmp_elems(std::max<uint64_t>(N, 256ull * 2048))));
-    SortBufs A, B;
-    A.nw = B.nw = 3;
-    for (int w = 0; w < 3; ++w) { A.k[w] = ka[w].p; B.k[w] = kb[w].p; }
-    A.v = d_va.p; B.v = d_vb.p;
-    std::vector<SortPass> passes;
-    add_passes(passes, 2, 0, 63);                       // a > 0: sign bit clear
-    add_passes(passes, 1, 0, (int)k_max);
-    if (S > 1) add_passes(passes, 0, 0, bits_for(S - 1));
-    bool in_b = false;
-    PTX_TRY(radix_sort(ctx, A, B, N, passes.data(), (int)passes.size(), d_table.p, d_scan_tmp.p, &in_b));
-    const SortBufs &Sd = in_b ? B : A;
-    const uint64_t *row_sp = Sd.k[0];
-    const double *base_a = reinterpret_cast<const double *>(Sd.k[2]);
-    // ---- base patterns
-    DevBuf<uint64_t> d_bpat_mask;
-    DevBuf<uint32_t> d_bpat_start, d_bpat_species, d_bsp_pat_off;
-    PTX_HIP(ctx, d_bpat_mask.alloc(N)); PTX_HIP(ctx, d_bpat_start.alloc(N + 1)); PTX_HIP(ctx, d_bpat_species.alloc(N)); PTX_HIP(ctx, d_bsp_pat_off.alloc((size_t)S + 1));
-    PTX_TRY(exclusive_scan_fn(ctx, BootPatLoad{Sd.k[0], Sd.k[1]}, BootPatStore{Sd.k[0], Sd.k[1], d_bpat_mask.p, d_bpat_start.p, d_bpat_species.p}, N, d_counts.p + 1,
-                              "scan_chained_kernel<BootPat>"));
-    uint32_t P = 0;
-    PTX_TRY(download(ctx, &P, d_counts.p + 1, 1));
-    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (P == 0 || P > N) return fail(ctx, PANTAX_HIP_E_STATE, "strain_bootstrap: internal (%u patterns of %llu rows)", P, (unsigned long long)N);
-    hipLaunchKernelGGL(boot_sp_pat_off_kernel, dim3((S + 1 + 255) / 256), dim3(256), 0, ctx->stream, S, P, (uint32_t)N, d_bpat_species.p, d_bpat_start.p, d_bsp_pat_off.p);
-    PTX_HIP(ctx, hipGetLastError());
+    if (F.N == 0) return deliver();
+    const uint64_t N = F.N, k_max = F.k_max;
+    const uint32_t P = F.P;
+    const uint64_t *row_sp = F.row_sp;
+    const double *base_a = F.base_a;
+    DevBuf<BootSpecies> &d_tab = F.d_tab;
+    DevBuf<uint32_t> &d_counts = F.d_counts, &d_bpat_start = F.d_bpat_start, &d_bsp_pat_off = F.d_bsp_pat_off;
+    DevBuf<uint64_t> &d_sel_off = F.d_sel_off, &d_bpat_mask = F.d_bpat_mask;
     // ---- the chunk's scratch, once (DevBuf: the ctx's device cache); nothing is allocated inside the loop
     const uint64_t per = plan.per_chunk, nq_max = per * S, np_max = per * P, ni_max = per * N;
     DevBuf<uint32_t> d_off, d_prefix, d_pat_start, d_sp_pat_off, d_flags, d_sc_lo, d_sc_up, d_ls_lo, d_ls_hi, d_ls_mid;
@@ -359,7 +394,7 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
     for (uint64_t b0 = 0; b0 < R; b0 += per) {
         const uint32_t nb = (uint32_t)std::min<uint64_t>(per, R - b0), n_items = nb * (uint32_t)N, n_pat = nb * P, nq = nb * S;
         // weights -> first expanded row of every item; the total closes the offsets
-        PTX_TRY(exclusive_scan_fn(ctx, BootWeightLoad{row_sp, Sd.v, d_tab.p, (uint32_t)N, (uint32_t)b0}, BootWeightStore{d_off.p}, n_items, d_counts.p + 2, "scan_chained_kernel<BootWeights>"));
+        PTX_TRY(exclusive_scan_fn(ctx, BootWeightLoad{row_sp, F.vloc, d_tab.p, (uint32_t)N, (uint32_t)b0}, BootWeightStore{d_off.p}, n_items, d_counts.p + 2, "scan_chained_kernel<BootWeights>"));
         PTX_HIP(ctx, hipMemcpyAsync(d_off.p + n_items, d_counts.p + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
         {
             KTimer tm(ctx, "boot_expand_kernel");
@@ -388,12 +423,7 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
         LA.ls_lo = d_ls_lo.p; LA.ls_hi = d_ls_hi.p; LA.ls_mid = d_ls_mid.p;
         LA.sp_p = d_sp_p.p; LA.amax = d_amax.p; LA.x_out = d_x.p; LA.status = d_status.p; LA.iters = d_iters.p; LA.col_off = d_col_off.p;
         PTX_TRY(lad_args_launch(ctx, LA, nq, (int)k_max, "lad_solve_kernel<bootstrap>"));
-        {
-            KTimer tm(ctx, "boot_objective_kernel");
-            hipLaunchKernelGGL(boot_objective_kernel, dim3(nq), dim3(256), 0, ctx->stream, d_sp_p.p, d_sp_pat_off.p, d_pat_mask.p, d_pat_start.p, d_exp_a.p, d_col_off.p, d_x.p,
-                               d_sc_s.p, d_obj.p);
-        }
-        PTX_HIP(ctx, hipGetLastError());
+        PTX_TRY(boot_objective_launch(ctx, nq, d_sp_p.p, d_sp_pat_off.p, d_pat_mask.p, d_pat_start.p, d_exp_a.p, d_col_off.p, d_x.p, d_sc_s.p, d_obj.p, "boot_objective_kernel"));
         if (C) PTX_TRY(download(ctx, hx.data() + b0 * C, d_x.p, (size_t)nb * C));
         PTX_TRY(download(ctx, hobj.data() + b0 * S, d_obj.p, (size_t)nq));
         PTX_TRY(download(ctx, (unsigned long long *)hrows.data() + b0 * S, (const unsigned long long *)d_rows.p, (size_t)nq));

@@ -413,6 +413,30 @@ class Engine:
                                                          p(rows) if self.S else None, p(status) if self.S else None))
         return x, obj, rows, status
 
+    def strain_dropout(self, sel_off, sel_hap):
+        """Leave-one-out test of the strain fit (pantax_hip_strain_dropout) on the coverage result get_node_abundances left on the device.  sel_off [S+1],
+        sel_hap as for strain_bootstrap.  Species s of K_s columns has K_s + 1 entries: 0 the plain refit, k + 1 the fit without column k; entry (s, e) is
+        q = sel_off[s] + s + e -> (x: list of S float64 [K_s + 1, K_s] blocks (views of one array, x[0].base), obj float64 [Q], status int32 [Q],
+        rows uint64 [S], count uint64 [Q, 4] = n_member, n_only, n_worse, n_better) with Q = sel_off[-1] + S."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("strain_dropout: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        K = np.diff(so.astype(np.int64))
+        x_off = np.concatenate([[0], np.cumsum((K + 1) * K)]).astype(np.int64)
+        Q = len(sh) + self.S
+        cs = _ffi.EvidenceSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None)
+        flat = np.zeros(max(int(x_off[-1]), 1), dtype=np.float64)
+        obj = np.zeros(Q, dtype=np.float64)
+        status = np.zeros(Q, dtype=np.int32)
+        rows = np.zeros(self.S, dtype=np.uint64)
+        count = np.zeros((Q, 4), dtype=np.uint64)
+        self._check(self.lib.pantax_hip_strain_dropout(self.ctx, self.db, C.byref(cs), p(flat), p(obj) if self.S else None, p(status) if self.S else None,
+                                                       p(rows) if self.S else None, p(count) if self.S else None))
+        flat = flat[:int(x_off[-1])]
+        x = [flat[int(x_off[s]):int(x_off[s + 1])].reshape(int(K[s]) + 1, int(K[s])) for s in range(self.S)]
+        return x, obj, status, rows, count
+
     def strain_depth(self, sel_off, sel_hap, species=True):
         """Per-strain depth distribution (pantax_hip_strain_depth) of the coverage result get_node_abundances left on the device.
         sel_off [S+1], sel_hap as for strain_evidence -> (hap uint64 [C, 2, 96, 2]: the histograms all / private of every selection entry,
@@ -639,7 +663,7 @@ class Engine:
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
                 strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
                 strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None, strain_fit_file=None,
-                strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42):
+                strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42, strain_dropout_file=None):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -650,7 +674,8 @@ class Engine:
         unreported-strain near-miss report (--strain-near-miss; one rank only), strain_near_miss_top the candidates it prints per species (0: 5).
         strain_pair_evidence_file: path of the pairwise strain evidence report (--strain-pair-evidence; one rank only).  strain_fit_file: path of the
         model fit report (--strain-fit; one rank only); given, the call goes through pantax_hip_profile_with_ext.  strain_bootstrap_file: path of the
-        bootstrap report (--strain-bootstrap; one rank only), strain_bootstrap_replicates the resamples (0: 100), strain_bootstrap_seed their seed."""
+        bootstrap report (--strain-bootstrap; one rank only), strain_bootstrap_replicates the resamples (0: 100), strain_bootstrap_seed their seed.  strain_dropout_file: path of
+        the leave-one-out report (--strain-dropout; one rank only)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -693,11 +718,12 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
-                                  strain_bootstrap_replicates=int(strain_bootstrap_replicates), strain_bootstrap_seed=int(strain_bootstrap_seed))
+                                  strain_bootstrap_replicates=int(strain_bootstrap_replicates), strain_bootstrap_seed=int(strain_bootstrap_seed),
+                                  strain_dropout_file=enc(strain_dropout_file))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -846,6 +872,18 @@ def bootstrap_weight(seed, sp_key, replicate, v_local):
     """pantax_hip_bootstrap_weight: the weight (0 .. 16) of node v_local of the species with key sp_key in bootstrap replicate `replicate` (0: always 1).
     Host only: no Engine is needed."""
     return int(_ffi.load().pantax_hip_bootstrap_weight(int(seed), int(sp_key), int(replicate), int(v_local)))
+
+
+def dropout_substitute(k, x_full, x_drop):
+    """pantax_hip_dropout_substitute: who takes over when column k is dropped.  x_full / x_drop float64 [K]: the x of the plain refit and of the fit without
+    column k -> (substitute column or -1, its gain, shift = the L1 distance of the two solutions over the other columns)."""
+    xf, xd = as_c(x_full, np.float64), as_c(x_drop, np.float64)
+    if xf.ndim != 1 or xf.shape != xd.shape:
+        raise ValueError("dropout_substitute: x_full and x_drop are one-dimensional and of one length")
+    out = np.zeros(3, dtype=np.float64)
+    if _ffi.load().pantax_hip_dropout_substitute(len(xf), int(k), p(xf), p(xd), p(out)) != 0:
+        raise ValueError("dropout_substitute: refused")
+    return int(out[0]), float(out[1]), float(out[2])
 
 
 def bootstrap_summary(x, status=None):
