@@ -168,6 +168,8 @@ struct CtxConfig {
     int cov_item_groups = 0;         // groups of 64 steps per work item of the short-read coverage kernel (0: COV_ITEM_GROUPS = 128; clamped to [1, 256] by build_step_read)
     int tv_u = 4, tv_rounds = 4, tf_u = 8, tf_rounds = 1, rows_u = 1, tb_slots = 256, trio_xcd = 3, cov_shape = -1, covf_shape = -1, cov_xcd = 0, group_bucket_bits = 0;
     uint32_t tv_ablate = 0, cov_ablate = 0, ssn_ablate = 0;
+    std::string cov_spec;            // short-read coverage kernel, the node record requested a round ahead at the item's species guess: "" / "on"; "miss": the guess matches no
+                                     // read, so every wave checks and takes the fallback loads (tests compare: the results are the same)
     bool trio_two_pass = false;      // every build through records + prefix + rows kernel, as a db's first build (tests, measurements)
     std::string bin_route;           // "walk": the binning pass of resident reads finds a walk's smallest and largest id by reading the walk (bin_slots_kernel) where it would take
                                      // them from the record filed at upload (bin_mm_kernel; "minmax" or empty) (tests compare, measurements)

@@ -56,7 +56,9 @@ namespace ptx {
 // from exec-mask branches): loads are unconditional with a safe index on dead lanes, per-lane cases are selects, and only
 // the LDS / memory updates sit under a mask.  Groups that hold a step of a longer walk are left to coverage_step_kernel.
 // Levels: {code, node id} + group_slot (scalar) -> {read record 16 B, slot record 8 B} -> {node record 16 B, active byte}
-// -> two unique-trio entries.
+// -> two unique-trio entries.  Off the chain: level 1 since round 5 and level 2 since round 6 (requested one / two rounds ahead), level 3 since round 25
+// (the node record requested a round ahead at the delta of the item's species guess, checked against the lane's species when the slot record is
+// there: PF3 in the body).  Level 4 is paid every round.
 // Workgroup = one ITEM of the read layout (build_step_read): up to COV_ITEM_GROUPS consecutive groups whose reads all START inside one
 // block of 2048 node ids.  (Round 3 gave every workgroup a fixed number of groups: where a species is thinly covered -- most species of a
 // Dirichlet-distributed sample -- 4096 steps span more nodes than the LDS windows hold, and every update outside them is a memory-side
@@ -73,6 +75,9 @@ namespace ptx {
 //     step: gathers with the read record / the node record, for every lane (the lanes of one walk share the address);
 // and every per-lane case is a select.  only_long != 0: groups without a step of a longer walk are the plain instantiation's.
 template <bool WITH_TRIO, int U, int PASSES, int WIN, bool LONG = false>
+#if !defined(COV_NO_PF3) && !defined(COV_NO_PF2) && !defined(COV_NO_PREFETCH)
+__attribute__((amdgpu_waves_per_eu((U <= 2 && !LONG) ? 6 : 1)))      // (the short-read shapes of two groups in flight: 80 vector registers, six waves -- no scratch, profiles/r25)
+#endif
 __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
     const uint2 *__restrict__ items, const uint32_t *__restrict__ group_slot, const uint4 *__restrict__ read_rec, const uint2 *__restrict__ slot_rec,
     const uint32_t *__restrict__ node_id, const uint8_t *__restrict__ step_code, const uint8_t *__restrict__ active,
@@ -80,9 +85,14 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
     uint32_t *__restrict__ bitmap, uint32_t *__restrict__ full, const uint2 *__restrict__ trio_ent, unsigned long long *__restrict__ trio_bases,
     unsigned long long *__restrict__ n_abort, uint32_t ablate, int blk_shift,
     const uint32_t *__restrict__ long_sum = nullptr, const uint32_t *__restrict__ long_len0 = nullptr, uint32_t only_long = 0u,
-    uint32_t chunk_groups = 0u, uint32_t total_groups = 0u, uint32_t win_back = 0u, const uint32_t *__restrict__ item_sel = nullptr) {
+    uint32_t chunk_groups = 0u, uint32_t total_groups = 0u, uint32_t win_back = 0u, const uint32_t *__restrict__ item_sel = nullptr,
+    uint32_t spec_miss = 0u) {
     constexpr int WAVES = COV_BLOCK / 64;
+#if !defined(COV_NO_PF3) && !defined(COV_NO_PF2) && !defined(COV_NO_PREFETCH)
+    const int lane = threadIdx.x & 63, wave = LONG ? (int)(threadIdx.x >> 6) : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (a scalar: group indices stay out of the vector registers)
+#else
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#endif
     // this workgroup's groups [g0, n_groups): an item of the read layout -- or, LONG, a plain cut of the stream: a long walk begins anywhere in a group,
     // so hardly any group starts with the first step of a read and the layout's items are arbitrary cuts anyway; the windows then begin `win_back` nodes
     // in front of the first live step's node (a reverse-strand walk runs DOWN from its first node, the key the stream is ordered by)
@@ -93,12 +103,16 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
     // window base: the node of the first step of the first group that has a live one (workgroup-uniform scalar loads)
     uint32_t wlo = 0, win_n = 0, mark_n = 0, bit0_lo = 0, bwn = 0;
     uint64_t bw0 = 0;
+    // ... and the item's guess (PF3 below): species and delta of that group's first slot -- an ACTIVE species, the loop requires it.  No live group: a
+    // species no read has
+    uint32_t s0 = 0xFFFFFFFFu, dlt0 = 0;
 #pragma unroll 1
     for (uint32_t g = g0; g < n_groups && win_n == 0; ++g) {
         const uint32_t gs = group_slot[g];
         if (gs == NO_SLOT) continue;
         const uint2 sr0 = slot_rec[gs];
         if ((int)sr0.x < 0 || !active[sr0.x]) continue;
+        s0 = sr0.x; dlt0 = sr0.y;
         // the window starts at the item's NODE BLOCK, not at its first read: the reads of a bucket of the layout (512 ids wide at 3e8 nodes)
         // are in no particular order, so later reads of the item may start hundreds of nodes in front of the first one -- every read of
         // the item starts inside the block (build_step_read), and ids and node indices run in step inside a species
@@ -113,8 +127,10 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
         // every node of the window has its bits inside the LDS bit window: a partial range is marked in 32-bit positions relative to it
         mark_n = (b_hi - (bw0 << 5) <= (uint64_t)COV_BWIN * 32) ? (uint32_t)min((uint64_t)WIN, V - wlo) : 0u;
     }
+    if (spec_miss) s0 = 0xFFFFFFFFu;       // option cov_spec=miss (tests): no read matches the guess, every wave takes the fallback loads
     // the barrier orders the LDS zero-fill only (a workgroup fence on the local address space): the window probes above are
-    // still in flight and are first needed by the updates of the first pass, behind that pass's own three levels of loads
+    // still in flight and are first needed by the updates of the first pass, behind that pass's own three levels of loads (PF3: `wlo`, the safe
+    // index of the speculative node records, by the prologue's requests)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
@@ -141,9 +157,27 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
 #else
     constexpr bool PF2 = false;
 #endif
+    // ... and takes level 3's NODE RECORD off the chain as well (round 25).  Level 3 waited for level 2 only because v = id + slot_rec.y; every read of an
+    // item starts inside one block of 2048 ids and a species has hundreds of thousands, so the reads of an item are one species' in all but the item at a
+    // species border -- and that species' delta is a scalar since the window probe (dlt0).  The record is requested from the id alone, with the
+    // coming round's read / slot records; level 3 checks every ok lane's species against the guess (species, not delta: contiguous ranges give every
+    // species the same delta, and a hit wave also skips the `active` gather -- s0 is active), and the rare wave with a lane of another species does
+    // the old two loads instead (wave-uniform).  The exposed chain per round: trio entries alone.  -DCOV_NO_PF3: round 6's body.
+    // Registers decide whether it pays: the plain way (four more per group in flight) is 86 VGPRs = FIVE waves per SIMD and 5.12 -> 5.47 ms, slower than
+    // round 6's body.  Kept at 80 = six waves, without scratch: the slot record travels as its species alone (a hit wave's delta is dlt0; the
+    // fallback loads the record again), `active` is folded into ok where it is loaded, the wave index is a scalar (group indices and the groups'
+    // first slots live in SGPRs) and the two-group shapes ask for six waves: 5.12 -> 5.00 ms (profiles/r25_*; the kernel is no latency chain alone)
+#if !defined(COV_NO_PF3)
+    constexpr bool PF3 = PF2;
+#else
+    constexpr bool PF3 = false;
+#endif
+    // the speculative index: always inside the table -- dead lanes, pads and reads of no species request SOME record they never use
+    const auto guess_v = [&](uint32_t id) { const uint32_t vg = id + dlt0; return vg < V ? vg : wlo; };
     uint32_t c_code[U], c_id[U], c_gs[U];      // PF2: this round's level 1 ...
     uint4 c_rr[U];                             // ... and level 2, requested a round ago
-    uint2 c_sr[U];
+    uint2 c_sr[U];                             // (PF3: the species alone)
+    uint4 c_nr[U];                             // PF3: ... and the node record at the item's delta
     bool c_run[U];                             // ... and whether the group is this kernel's at all (wave-uniform: decided once, when its records are requested)
 #pragma unroll
     for (int u = 0; u < U; ++u) c_run[u] = false;
@@ -159,9 +193,12 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
             const bool run0 = (gw0 + (uint32_t)u < n_groups) & any1(!pad0) & none1(!pad0 & ((c_code[u] & STEP_LONG) != 0u));
             const uint32_t sl = slot_in_group(c_gs[u], c_code[u], lane);
             const uint32_t slot = (pad0 | !run0) ? (c_gs[u] == NO_SLOT ? 0u : c_gs[u]) : sl;
-            c_rr[u] = read_rec[slot]; c_sr[u] = slot_rec[slot];
+            c_rr[u] = read_rec[slot];
+            if constexpr (PF3) c_sr[u] = make_uint2(slot_rec[slot].x, 0u); else c_sr[u] = slot_rec[slot];
+            if constexpr (PF3) c_nr[u] = node_rec[guess_v(c_id[u])];
             c_run[u] = run0;
         }
+        if constexpr (PF3) __builtin_amdgcn_sched_barrier(0);      // (the requests stay where they are written: in front of the first round)
     }
 #pragma unroll 1
     for (int pass = 0;; ++pass) {
@@ -172,6 +209,7 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
         bool run[U];                                                          // wave-uniform: the group is this kernel's
         uint4 rr[U];
         uint2 sr[U];
+        uint4 nrg[U];                                                         // PF3: the node record at the item's delta
 #ifndef COV_NO_PREFETCH
         if constexpr (PF2) {
             const uint32_t gn = gw + (uint32_t)(WAVES * U), g2 = gn + (uint32_t)(WAVES * U);   // the coming round's groups, and the one behind it
@@ -180,6 +218,7 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
             for (int u = 0; u < U; ++u) {
                 run[u] = c_run[u];
                 code[u] = c_code[u]; id[u] = c_id[u]; gs[u] = c_gs[u]; rr[u] = c_rr[u]; sr[u] = c_sr[u];
+                if constexpr (PF3) nrg[u] = c_nr[u];
                 const uint32_t g = g2 + (uint32_t)u < n_groups ? g2 + (uint32_t)u : gw;
                 const uint64_t t = (uint64_t)g * 64 + lane;
                 m_code[u] = step_code[t]; m_id[u] = node_id[t]; m_gs[u] = group_slot[g];
@@ -188,11 +227,14 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
                 const bool runn = (gn + (uint32_t)u < n_groups) & any1(!padn) & none1(!padn & ((n_code[u] & STEP_LONG) != 0u));
                 const uint32_t sl = slot_in_group(n_gs[u], n_code[u], lane);
                 const uint32_t slot = (padn | !runn) ? (n_gs[u] == NO_SLOT ? 0u : n_gs[u]) : sl;
-                c_rr[u] = read_rec[slot]; c_sr[u] = slot_rec[slot];
+                c_rr[u] = read_rec[slot];
+                if constexpr (PF3) c_sr[u] = make_uint2(slot_rec[slot].x, 0u); else c_sr[u] = slot_rec[slot];
+                if constexpr (PF3) c_nr[u] = node_rec[guess_v(n_id[u])];       // level 3's node record of the coming round, from the id alone
                 c_run[u] = runn;
                 c_code[u] = n_code[u]; c_id[u] = n_id[u]; c_gs[u] = n_gs[u];
                 n_code[u] = m_code[u]; n_id[u] = m_id[u]; n_gs[u] = m_gs[u];
             }
+            if constexpr (PF3) __builtin_amdgcn_sched_barrier(0);             // (the requests leave here, with level 2's, not behind this round's waits)
         } else
         {
             const uint32_t gn = gw + (uint32_t)(WAVES * U);                    // the coming round's groups
@@ -217,6 +259,7 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
 #endif
         // ---- level 2 (dead lanes read the group's first record: in range, and on a line that is fetched anyway)
         bool pad[U];
+        uint32_t slot_[U];
         uint32_t ll0[U], lsum[U];                                             // LONG: first node length / sum of the lengths before the last step, by slot
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -230,6 +273,7 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
             const uint32_t slot = (pad[u] | !run[u]) ? (gs[u] == NO_SLOT ? 0u : gs[u]) : sl;
             if constexpr (!PF2) { rr[u] = read_rec[slot]; sr[u] = slot_rec[slot]; }     // (PF2: requested a round ago)
             if constexpr (LONG) { ll0[u] = long_len0[slot]; lsum[u] = long_sum[slot]; }
+            slot_[u] = slot;
         }
         // LONG: the two steps in front of the wave's group (wave-uniform addresses: position of the group - 1, - 2; the dword of step codes in front of it)
         uint32_t h_id1[U], h_id2[U], h_codes[U];
@@ -249,10 +293,30 @@ __global__ void __launch_bounds__(COV_BLOCK) coverage_fast_kernel(
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             ok[u] = run[u] & !pad[u] & ((int)sr[u].x >= 0);
+            if constexpr (PF3) {
+                // every ok lane is of the guessed species: its delta is dlt0, its record is the one requested a round ago (v < V for an id of its species)
+                // and its species is active -- no `active` gather.  Lanes that are not ok hold SOME in-range record and never use it: `nl`, the marks and
+                // the trio head shifted up from the lane below all sit under ok / live of the same read.
+                // (each side waits for ITS record inside the branch -- the empty asm is a use: behind the join the compiler's one wait would be the
+                // fallback's, for everything in flight with the coming round's requests among it, on the hit side too)
+                if (none1(ok[u] & (sr[u].x != s0))) {
+                    v[u] = ok[u] ? id[u] + dlt0 : wlo;
+                    nr[u] = nrg[u];
+                    asm volatile("" : "+v"(nr[u].x), "+v"(nr[u].y), "+v"(nr[u].z), "+v"(nr[u].w));
+                } else {                                                      // a wave at a species border: the slot record's delta again, then round 6's two loads
+                    v[u] = ok[u] ? id[u] + slot_rec[slot_[u]].y : wlo;
+                    nr[u] = node_rec[v[u]];
+                    const uint32_t a = active[ok[u] ? sr[u].x : 0u];
+                    asm volatile("" : "+v"(nr[u].x), "+v"(nr[u].y), "+v"(nr[u].z), "+v"(nr[u].w));
+                    ok[u] = ok[u] & (a != 0u);
+                }
+                act[u] = 1u;                                                  // (folded into ok where it was loaded)
+            } else {
             v[u] = ok[u] ? id[u] + sr[u].y : wlo;
             nr[u] = node_rec[v[u]];
             act[u] = active[ok[u] ? sr[u].x : 0u];      // never null here (the launcher passes all-ones when no species is deselected): an unconditional load
                                                         // travels beside the node record; under a pointer test the compiler waited for it first
+            }
         }
         // LONG: id of the walk's first step (one address per walk) and the node records of the two steps in front of the wave (wave-uniform: the
         // walk of lane 0, when it began one / two steps or more before this group)
@@ -699,7 +763,8 @@ static void fast_launch_as(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_act, bo
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(COV_BLOCK), cov_lds_bytes(WIN), ctx->stream, t.items, rd->d_g_group_slot.p, rd->d_g_read_rec.p,
                        rd->d_g_slot_rec.p, rd->d_g_node_id.p, rd->d_g_step_dup.p, d_act, db->d_node_rec.p, db->d_bit_off.p, db->V, db->d_bases.p,
                        db->d_bitmap.p, db->d_full.p, db->d_trio_ent.p, db->d_trio_bases.p, db->d_abort, ctx->cfg.cov_ablate /* -DCOV_ABLATE builds only */,
-                       t.blk_shift, t.long_sum, t.long_len0, t.only_long, t.chunk_groups, t.total_groups, t.win_back, t.item_sel);
+                       t.blk_shift, t.long_sum, t.long_len0, t.only_long, t.chunk_groups, t.total_groups, t.win_back, t.item_sel,
+                       ctx->cfg.cov_spec == "miss" ? 1u : 0u /* tests: every wave of the short-read kernel takes the fallback loads */);
 }
 
 // Walks of <= 64 steps: the short-read kernel, one wave per 64-step group, PASSES groups per wave and workgroup (the LDS windows are zeroed and flushed
