@@ -129,6 +129,33 @@ __device__ __forceinline__ uint32_t tree_node(uint32_t rank) {
     return (1u << ((uint32_t)SN_LEVELS - 1u - tz)) + ((q >> tz) >> 1);
 }
 
+// Bucket ids of N keys {km, ka} at once, level by level: at every level the N tree nodes are read from LDS together, one wait covers them, then the N
+// compares follow -- SN_LEVELS + 1 dependent LDS round trips for the N keys where a descent per key makes N times as many.  Branch-free: every lane
+// descends with whatever key it holds (any key stays inside the tree: node k of level l lies in [2^l, 2^(l+1)), so every read is of tree[1 .. SN_NLEAF - 1]),
+// and a lane without a row discards its id.  The id is the serial loop's: lo = the splitters less than the key, 2 lo + 1 when the key equals splitter
+// lo ("equal to splitter j" is its own bucket), the probe of a key above every splitter (lo = SN_NSPLIT: no such splitter) reads splitter 0 and is ignored.
+template <int N>
+__device__ __forceinline__ void sn_bucket_ids(const ulonglong2 *tree, const uint64_t (&km)[N], const uint64_t (&ka)[N], uint32_t (&id)[N]) {
+    uint32_t k[N];                                               // 16 k through the levels: the node's byte offset, one shift a level saved
+    ulonglong2 nd[N];
+#pragma unroll
+    for (int r = 0; r < N; ++r) k[r] = 16u;
+#pragma unroll
+    for (int l = 0; l < SN_LEVELS; ++l) {
+#pragma unroll
+        for (int r = 0; r < N; ++r) nd[r] = *reinterpret_cast<const ulonglong2 *>(reinterpret_cast<const char *>(tree) + k[r]);
+#pragma unroll
+        for (int r = 0; r < N; ++r) k[r] = (k[r] << 1) | (less2(Key2{nd[r].x, nd[r].y}, Key2{km[r], ka[r]}) ? 16u : 0u);
+    }
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+        k[r] = (k[r] >> 4) - (uint32_t)SN_NLEAF;                 // splitters less than the key
+        nd[r] = tree[tree_node(k[r] < (uint32_t)SN_NSPLIT ? k[r] : 0u)];
+    }
+#pragma unroll
+    for (int r = 0; r < N; ++r) id[r] = 2u * k[r] + (((k[r] < (uint32_t)SN_NSPLIT) & eq2(Key2{nd[r].x, nd[r].y}, Key2{km[r], ka[r]})) ? 1u : 0u);
+}
+
 // Bucket pair j (the even bucket 2j: the rows between splitters j - 1 and j; the tie bucket 2j + 1: the copies of splitter j) is MIXED when its even bucket
 // may hold rows of more than one mask: the two splitters differ in their mask, or one of them does not exist (pair 0, the last pair).  Otherwise every row
 // of bucket 2j has the mask of splitter j (*mv): the local sorts move `a` alone through their networks and store no key words for it (Sn::keys_all == 0),

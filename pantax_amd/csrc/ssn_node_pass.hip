@@ -2,9 +2,16 @@
 // own bucket 2j+1), one LDS histogram per workgroup stored as a row of the segment's count matrix, the rows of the even buckets staged.
 //
 // EDIT TOGETHER.  This file holds two kernels and nothing else: ssn_hist_kernel<HAPS> (the stage calls and fallbacks) and node_rows_kernel (the
-// resident step, fused with the node statistics; node_rows_final_kernel folds its partials).  From "haplotype word -> columns" down to the staging of
-// the row, and the three epilogues (count matrix row, c0 partial, column sums), node_rows_kernel and ssn_hist_kernel<true> are the SAME statements: a
-// change to one is a change to the other.  They stay two kernels -- one shared body cost ssn_hist_kernel<true> 115 -> 127 VGPRs (see below).
+// resident step, fused with the node statistics; node_rows_final_kernel folds its partials).  They stay two kernels -- one shared body cost
+// ssn_hist_kernel<true> 115 -> 127 VGPRs (see below).  What the two have in common, statement for statement, and has to be edited in both:
+//   * the columns' sums of a node (c8 / l8 in registers, the columns beyond 8 by LDS atomics), the c0 sum, the row test (a > 0 and a mask), the
+//     histogram atomic, the ballot and the staging of the row;
+//   * the three epilogues (count matrix row, c0 partial, column sums).
+// What differs since the bucket ids of node_rows_kernel are formed level by level for a half's four items (sn_bucket_ids, ssn_device.hpp):
+//   * ssn_hist_kernel descends the tree per row, inside the row test (ten dependent LDS reads an item) -- the loop -DNODE_ROWS_SERIAL_DESCENT puts back
+//     into node_rows_kernel for A/B builds.  Both spell the same bucket id: lo = the splitters less than the key, 2 lo + 1 for a copy of splitter lo;
+//   * node_rows_kernel looks its column tables up four bytes at a time (its register peak), ssn_hist_kernel as the compiler unrolls them.
+#include <type_traits>
 #include "ssn_device.hpp"
 
 namespace ptx {
@@ -171,13 +178,16 @@ __global__ void __launch_bounds__(256) ssn_hist_kernel(Sn sn) {
 // kernel wrote and this one read back, and the second read of the lengths, are gone.
 // A kernel of its own, not a third instantiation of ssn_hist_kernel: one shared body changed the register allocation of ssn_hist_kernel<true>
 // (115 -> 127 VGPRs, node_pass=split 0.6 ms a step slower than the parent at cfg4), and the two-kernel path of the stage calls and fallbacks has to stay
-// what it was.  The price: from "haplotype word -> columns" down to the staging of the row, and the three epilogues (count matrix row, c0 partial,
-// column sums), this kernel and ssn_hist_kernel<true> are the SAME statements and have to be edited together.
+// what it was.  The price: the statements the two share (listed at the head of this file) have to be edited together.
 // A wave's item is 64 consecutive nodes: their first bit comes from ONE wave-uniform load of bit_off plus a DPP prefix sum of the lengths (no running
 // offset: a workgroup's tiles are not consecutive for a wave).  A tile is walked in two halves of four items -- the statistics kernel's depth: eight
 // items' lengths, bases, flag, haplotype and bit-vector words beside the sixteen column sums do not fit the registers of four waves per SIMD (153 VGPRs)
 // -- and a half's streams are all requested before its first dependent bit-vector load.  The covered bases of a node have ONE consumer here, the column
 // sums of path_cov_ratio: a node without a column (empty mask), or one a step covered whole (flag), does not fetch its bit-vector words at all.
+// Instruction issue (round 26: the kernel is bound by VALU / SALU issue and the serial LDS chain of the descent, not by bytes): the tiles that lie
+// wholly inside the segment -- all but a segment's last -- take a body without any `i < n` select or exec region, with the streams at a wave-uniform
+// base of the half plus the lane's offset; the last tile alone takes the guarded body.  The bucket ids of a half's four items come from ONE level-major
+// descent after the streams' registers are free.
 constexpr int SN_HALF = SN_ITEMS >= 8 ? SN_ITEMS / 2 : SN_ITEMS;
 static_assert(SN_ITEMS % SN_HALF == 0, "whole halves");
 // NB (options node_bits / node_bits_words; ssn_node_bits(), ssn_plan.hpp): where a node's bit-vector words come from.
@@ -263,10 +273,14 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
     const uint32_t stage0 = o + t0 * SN_TILE;                    // (the staged rows: see ssn_hist_kernel)
     double cacc = 0.0;                                           // abundances of this thread's nodes with an empty mask
     NodeAcc nacc;                                                // statistics of this thread's nodes
-    for (uint32_t t = t0; t < t1; ++t) {
-#pragma unroll
-      for (int hb = 0; hb < SN_ITEMS; hb += HALF) {
-        const uint32_t base = t * SN_TILE + (uint32_t)hb * 256u + threadIdx.x;
+    // One half of tile t (items hb .. hb + HALF - 1).  GUARD = false: the tile lies wholly inside the segment (workgroup-uniform) -- no lane is behind the
+    // segment's end, the streams are loaded from a wave-uniform 64-bit base of the half plus the lane's 32-bit offset inside it, nothing is selected.
+    // GUARD = true, a segment's last tile: a lane behind the end loads the segment's last node and takes zeros afterwards.
+    static_assert((uint64_t)SN_TILE * sizeof(unsigned long long) < (1ull << 20), "a lane's byte offset from the half's base: 32 bits with room to spare");
+    auto half = [&](auto guard, const uint32_t t, const int hb) __attribute__((always_inline)) {
+        constexpr bool GUARD = decltype(guard)::value;
+        __builtin_amdgcn_sched_barrier(0);                       // (a half's requests stay behind the half before it: the registers are one half's)
+        const uint32_t hbase = t * SN_TILE + (uint32_t)hb * 256u, base = hbase + threadIdx.x;   // (hbase < n: the half's first node in the segment, unless GUARD)
         double av[HALF];
         uint64_t mv[HALF];
         uint32_t cv[HALF], lv[HALF];
@@ -274,7 +288,6 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
             unsigned long long bs[HALF];
             uint32_t fw[HALF];
             uint64_t gb[HALF];                                   // first bit of the wave's 64 nodes (wave-uniform)
-            uint32_t ex[HALF];                                   // ... and of every node, from there
             uint32_t bw0[HALF], bw1[HALF];                       // NB, an item that fits: words lane and 64 + lane of its stretch; otherwise a node's first and last word
             bool fits[HALF];                                     // NB: the stretch was loaded (wave-uniform)
             uint32_t nwv[HALF], tbv[HALF];                       // NB: words and bits of the item's stretch (wave-uniform)
@@ -298,12 +311,20 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
             }
 #pragma unroll
             for (int r = 0; r < HALF; ++r) {                     // the four streams of the half
-                const uint32_t i = base + (uint32_t)r * 256u;
-                const bool in = i < n;
-                lv[r] = in ? sn.hp.node_len[o + i] : 0u;
-                bs[r] = in ? sn.fz.bases[o + i] : 0ull;
-                fw[r] = in ? sn.fz.full[(o + i) >> 5] : 0u;
-                mv[r] = in ? sn.hp.node_haps[o + i] : 0ull;
+                if constexpr (GUARD) {                           // (n > 0: a lane behind the end loads node n - 1)
+                    const uint32_t i = base + (uint32_t)r * 256u;
+                    const bool in = i < n;
+                    const uint32_t v = o + (in ? i : n - 1u);
+                    const uint32_t l = sn.hp.node_len[v], f = sn.fz.full[v >> 5];
+                    const unsigned long long b = sn.fz.bases[v], h = sn.hp.node_haps[v];
+                    lv[r] = in ? l : 0u; bs[r] = in ? b : 0ull; fw[r] = in ? f : 0u; mv[r] = in ? h : 0ull;
+                } else {                                         // node v0 + j: the 64-bit part of the address is the half's (scalar), j < SN_TILE
+                    const uint32_t v0 = o + hbase, j = threadIdx.x + (uint32_t)r * 256u;
+                    lv[r] = (sn.hp.node_len + v0)[j];
+                    bs[r] = (sn.fz.bases + v0)[j];
+                    fw[r] = (sn.fz.full + (v0 >> 5))[((v0 & 31u) + j) >> 5];
+                    mv[r] = (sn.hp.node_haps + v0)[j];
+                }
             }
             if (!NB) {
 #pragma unroll
@@ -313,8 +334,6 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
                     fits[r] = false; nwv[r] = tbv[r] = 0u;
                 }
             }
-#pragma unroll
-            for (int r = 0; r < HALF; ++r) ex[r] = wave_incl_scan_dpp(lv[r]) - lv[r];   // ... then of every node (a species' bases fit 32 bits: checked at upload)
             if (NB) {                                            // (the streams have arrived, and the ends requested before them)
 #pragma unroll
                 for (int k = 0; k < 2 * HALF; ++k) eb[k] = lane_get(endv, k);
@@ -324,7 +343,8 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
             for (int r = 0; r < HALF; ++r) {                     // haplotype word -> columns
                 const unsigned long long hm = mv[r];
                 unsigned long long m = 0ull;
-                for (int b = 0; b < nbyte; ++b) m |= s_dyn_tab[b * 256 + (int)((hm >> (8 * b)) & 255ull)];
+#pragma unroll 4
+                for (int b = 0; b < nbyte; ++b) m |= s_dyn_tab[b * 256 + (int)((hm >> (8 * b)) & 255ull)];   // (four lookups in flight: eight were the kernel's register peak)
                 mv[r] = m;
                 whole[r] = (fw[r] >> ((o + base + (uint32_t)r * 256u) & 31u)) & 1u;   // a step covered the whole node: a flag instead of marked bits
             }
@@ -332,7 +352,7 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
             for (int r = 0; r < HALF; ++r) {                     // gather: first and last bit-vector word of every node that has a consumer for its count: independent loads, issued together
                 if (NB && fits[r]) continue;                     // (wave-uniform)
                 const bool count = lv[r] != 0u && mv[r] != 0ull && !whole[r] && !NRK_ABL(1u);   // (l = 0 behind the segment's end)
-                const uint64_t g0 = gb[r] + ex[r];
+                const uint64_t g0 = gb[r] + (wave_incl_scan_dpp(lv[r]) - lv[r]);
                 bw0[r] = count ? sn.fz.bitmap[g0 >> 5] : 0u;
                 bw1[r] = count ? sn.fz.bitmap[(g0 + lv[r] - 1) >> 5] : 0u;
             }
@@ -340,6 +360,11 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
             for (int r = 0; r < HALF; ++r) {
                 const uint32_t i = base + (uint32_t)r * 256u;
                 const bool count = lv[r] != 0u && mv[r] != 0ull && !whole[r] && !NRK_ABL(1u);
+                // the node's first bit from the item's (a species' bases fit 32 bits: checked at upload).  Formed where it is used: four items' worth held from the
+                // streams' arrival on cost four registers at the kernel's peak.  Every lane of the wave is active HERE, at the top of an item: the per-lane arms
+                // further down (`else if (count)` with its interior-word loop, `i < n`) have closed again before the next item begins -- no scan or shuffle may move
+                // into them.  An item that takes the gather fallback forms this scan twice (once for its loads above): six VALU on the rare path
+                const uint32_t exr = wave_incl_scan_dpp(lv[r]) - lv[r];
                 uint32_t c = whole[r] ? lv[r] : 0u;
                 if (NB && fits[r]) {                             // (wave-uniform: every lane takes part in the shuffles)
                     // E = the set bits of the stretch below the node's first bit, from the words' prefix of set bits (DPP scan) and the word the bit lies in, both
@@ -349,7 +374,7 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
                     const uint32_t q0 = (uint32_t)lane < nw ? __popc(bw0[r]) : 0u, s0 = wave_incl_scan_dpp(q0);
                     uint32_t q1 = 0u, s1 = 0u;
                     if (NB > 1) { q1 = (uint32_t)lane + 64u < nw ? __popc(bw1[r]) : 0u; s1 = wave_incl_scan_dpp(q1) + lane_get(s0, 63); }
-                    const uint32_t f0 = ((uint32_t)gb[r] & 31u) + ex[r], j0 = f0 >> 5;   // bits from the stretch's first word on
+                    const uint32_t f0 = ((uint32_t)gb[r] & 31u) + exr, j0 = f0 >> 5;   // bits from the stretch's first word on
                     uint32_t x = (uint32_t)__shfl((int)bw0[r], (int)(j0 & 63u)), px = (uint32_t)__shfl((int)(s0 - q0), (int)(j0 & 63u));
                     if (NB > 1) {
                         const uint32_t y = (uint32_t)__shfl((int)bw1[r], (int)(j0 & 63u)), py = (uint32_t)__shfl((int)(s1 - q1), (int)(j0 & 63u));
@@ -364,20 +389,34 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
                     const uint32_t cc = wave_shl1(e, ce) - e;
                     if (count) c = cc;
                 } else if (count) {
-                    const uint64_t g0 = gb[r] + ex[r], g1 = g0 + lv[r], w0 = g0 >> 5, w1 = (g1 - 1) >> 5;
+                    const uint64_t g0 = gb[r] + exr, g1 = g0 + lv[r], w0 = g0 >> 5, w1 = (g1 - 1) >> 5;
                     const uint32_t m0 = 0xFFFFFFFFu << (g0 & 31), m1 = 0xFFFFFFFFu >> (31 - (uint32_t)((g1 - 1) & 31));
                     c = w0 == w1 ? __popc(bw0[r] & m0 & m1) : __popc(bw0[r] & m0) + __popc(bw1[r] & m1);
                     for (uint64_t ww = w0 + 1; ww < w1; ++ww) c += __popc(sn.fz.bitmap[ww]);   // nodes of more than 33 bases
                 }
                 cv[r] = c;
                 av[r] = 0.0;
-                if (i < n) {
+                if (!GUARD || i < n) {
                     av[r] = (double)(long long)bs[r] / (double)lv[r];   // profile.rs:987-988, as node_cov_stats_kernel forms it
                     nacc.add(av[r], sn.fz.min_depth);
                 }
+                if constexpr (!GUARD) __builtin_amdgcn_sched_barrier(0);   // (one item's shuffles at a time: four items' temporaries do not fit beside the sums)
             }
         }
-        // ---- from here to the end of the kernel: ssn_hist_kernel<true>'s statements (edit both)
+        [[maybe_unused]] uint32_t idv[HALF];
+#ifndef NODE_ROWS_SERIAL_DESCENT
+        {                                                        // the bucket ids of the half's items, level by level (sn_bucket_ids): the streams' registers are free here
+            uint64_t ka[HALF];
+#pragma unroll
+            for (int r = 0; r < HALF; ++r) ka[r] = (uint64_t)__double_as_longlong(av[r]);
+            if (NRK_ABL(2u)) {
+#pragma unroll
+                for (int r = 0; r < HALF; ++r) idv[r] = 2u * ((uint32_t)(ka[r] >> 30) & (uint32_t)(SN_NLEAF - 1));
+            } else sn_bucket_ids<HALF>(tree, mv, ka, idv);
+        }
+#endif
+        // ---- from here on the statements this kernel shares with ssn_hist_kernel<true> (edit both): the list at the head of this file says which.  The bucket id
+        // is not among them: it is idv[r] from above, or -- -DNODE_ROWS_SERIAL_DESCENT, A/B builds only -- ssn_hist_kernel's descent per row
 #pragma unroll
         for (int r = 0; r < HALF; ++r) {
             {                                                     // the columns' sums
@@ -400,6 +439,7 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
             const uint64_t abits = (uint64_t)__double_as_longlong(av[r]);
             if (av[r] > 0.0 && mv[r] == 0ull) cacc += av[r];
             if (av[r] > 0.0 && mv[r] != 0ull) {                  // (nodes behind the segment's end were loaded as zeros)
+#ifdef NODE_ROWS_SERIAL_DESCENT
                 const Key2 key{mv[r], abits};
                 uint32_t k = 1;
                 if (NRK_ABL(2u)) k = (uint32_t)SN_NLEAF + ((uint32_t)(abits >> 30) & (uint32_t)(SN_NLEAF - 1));
@@ -410,6 +450,9 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
                 uint32_t eq = 0;
                 if (lo < (uint32_t)SN_NSPLIT && !NRK_ABL(2u)) { const ulonglong2 nd = tree[tree_node(lo)]; eq = eq2(Key2{nd.x, nd.y}, key) ? 1u : 0u; }
                 id = 2u * lo + eq;
+#else
+                id = idv[r];
+#endif
                 atomicAdd(&s_hist[id], 1u);
             }
             const bool travels = id != SN_NO_ROW && !(id & 1u);
@@ -425,7 +468,15 @@ __global__ void __launch_bounds__(256) node_rows_kernel(Sn sn) {
                 }
             }
         }
-      }
+    };
+    const uint32_t tf = n / SN_TILE < t1 ? n / SN_TILE : t1;     // (workgroup-uniform) the tiles before tf lie wholly inside the segment; only a segment's last tile may not
+    for (uint32_t t = t0; t < tf; ++t) {
+#pragma unroll
+        for (int hb = 0; hb < SN_ITEMS; hb += HALF) half(std::false_type{}, t, hb);
+    }
+    if (t0 < t1 && tf < t1) {                                    // the segment's last tile (tf = t1 - 1 >= t0: t1 is at most the segment's tiles, n / SN_TILE one less at least)
+#pragma unroll
+        for (int hb = 0; hb < SN_ITEMS; hb += HALF) half(std::true_type{}, tf, hb);
     }
     __syncthreads();
     sn_block_partial<4>(nacc, sn.npart + (size_t)s * sn.G + g);
