@@ -433,7 +433,7 @@ int pantax_hip_node_coverage(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_
     if (!ctx || !db || !reads) return PANTAX_HIP_E_INVALID;
     PTX_ENTER(ctx);
     if (!reads->binned) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: call pantax_hip_bin_reads on these reads first");
-    if (trio_bases_out && !db->trio_built) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: trio_bases requested but pantax_hip_trio_index has not run");
+    if (trio_bases_out && !db->trio.built()) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: trio_bases requested but pantax_hip_trio_index has not run");
     const uint8_t *d_active = nullptr;
     if (species_active) {
         PTX_TRY(upload_small(ctx, db->d_active, species_active, db->S));
@@ -442,8 +442,8 @@ int pantax_hip_node_coverage(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_
     // trio_bases are handed out in the table's export order, (species, hap, position) -- the order of pantax_hip_trio_get --, not in the order
     // the rows are filed in: the permutation is made before the pass (it may rebuild the index with the window starts: same rows)
     if (trio_bases_out && db->U) PTX_TRY(trio_export_ensure(ctx, db));
-    PTX_TRY(coverage_launch(ctx, db, reads, d_active, db->trio_built));
-    db->cov_stage = true;
+    PTX_TRY(coverage_launch(ctx, db, reads, d_active, db->trio.built()));
+    db->cov.stage_marked();
     unsigned long long *d_abort = db->d_abort;
     unsigned long long h_abort = 0;
     std::vector<uint32_t> cov32;

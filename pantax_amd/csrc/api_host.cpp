@@ -71,9 +71,7 @@ extern "C" {
 int pantax_hip_db_reset(pantax_hip_ctx *ctx, pantax_hip_db *db) {
     if (!ctx || !db) return PANTAX_HIP_E_INVALID;
     std::lock_guard<std::recursive_mutex> ptx_lock__(ctx->mu);
-    db->trio_built = false;
-    db->cov_done = false;
-    db->U = 0;
+    db->index_invalidate();
     return 0;
 }
 

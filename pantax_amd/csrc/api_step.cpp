@@ -25,6 +25,29 @@ void copy_species_out(void *arg) {   // runs right after the step's single wait
     std::memcpy(o->keep, o->db->h_sp_out[o->slot].p + sizeof(double) * S, S);
 }
 
+// The index build of a step on the side stream: ordered behind the last reader of the index it replaces -- the previous step reads it up to its first
+// filter (strain_enqueue records ev_trio_free behind it; what follows there -- masks, row sort, LPs, objective -- runs beside the rebuild); without such an
+// event (stage calls in between, option trio_after_step) behind everything enqueued so far -- and ev_fork recorded behind it for the main stream to wait
+// for.  A failure leaves no index: the side stream is drained and the tables count as empty.
+int trio_build_forked(pantax_hip_ctx *ctx, pantax_hip_db *db) {
+    if (db->trio.free_event_valid() && !ctx->cfg.trio_after_step) PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, db->ev_trio_free, 0));
+    else {
+        PTX_HIP(ctx, hipEventRecord(ctx->ev_seq, ctx->stream));
+        PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_seq, 0));
+    }
+    int rc; hipError_t e;
+    {
+        SideStream side(ctx);
+        if (!side) return fail(ctx, PANTAX_HIP_E_STATE, "trio index build: the ctx is already on its side stream");
+        rc = trio_index_build(ctx, db, false);
+        e = hipEventRecord(ctx->ev_fork, ctx->stream2);
+    }
+    if (rc != 0 || e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream2); db->index_invalidate(); }
+    if (rc != 0) return rc;
+    PTX_HIP(ctx, e);
+    return 0;
+}
+
 // Everything of one step enqueued on the device, nothing waited for.  The device runs steps strictly one after the other:
 // the side stream (unique-trio build) first waits for all the main-stream work enqueued so far, i.e. for the previous step.
 int step_enqueue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const double *avg_len, const pantax_hip_step_config *cfg) {
@@ -47,32 +70,15 @@ int step_enqueue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads
         } } } slow_report{marks, &n_marks, ctx->cfg.trace};
     // a7 first, on the side stream: the unique-trio index depends on the graphs only (the reference rebuilds it every
     // run, profile.rs:2936), so it is built while the main stream bins the reads and takes the species decision
-    bool forked = false;
-    if (cfg->rebuild_trio && !(db->trio_prefetched && db->trio_built)) { db->trio_built = false; db->cov_done = false; db->U = 0; }
-    db->trio_prefetched = false;   // (a prefetched index serves ONE step: the run it was started for)
-    if (!db->trio_built) {
-        // the previous step still reads the index this build replaces -- up to its first filter (strain_enqueue records the event
-        // behind it); what follows there (masks, row sort, LPs, objective) runs beside the rebuild.  Without such an event
-        // (stage calls in between) the side stream waits for everything enqueued so far.
-        if (db->trio_free_valid && !ctx->cfg.trio_after_step) PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, db->ev_trio_free, 0));
-        else {
-            PTX_HIP(ctx, hipEventRecord(ctx->ev_seq, ctx->stream));
-            PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_seq, 0));
-        }
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream_main = main_stream; ctx->stream = ctx->stream2;
-        const int rc = trio_index_build(ctx, db, false);   // without the row-order export copies: no stage of the step reads them
-        const hipError_t e = hipEventRecord(ctx->ev_fork, ctx->stream2);
-        ctx->stream = main_stream; ctx->stream_main = nullptr;
-        if (rc != 0) return rc;
-        PTX_HIP(ctx, e);
-        forked = true;
-    }
-    // a failure between the fork and the join must not leave the index half built behind a `trio_built` flag: the next
-    // call would read it with no ordering against the side stream
+    if (cfg->rebuild_trio && !db->trio.serves_coming_step()) db->index_invalidate();
+    db->trio.prefetch_consumed();
+    const bool forked = !db->trio.built();
+    if (forked) PTX_TRY(trio_build_forked(ctx, db));   // without the row-order export copies: no stage of the step reads them
+    // a failure between the fork and the join must not leave the index claimed as built: the next call would read it with no
+    // ordering against the side stream
     struct ForkGuard {
         Ctx *c; Db *d; bool armed;
-        ~ForkGuard() { if (armed) { (void)hipStreamSynchronize(c->stream2); d->trio_built = false; d->cov_done = false; } }
+        ~ForkGuard() { if (armed) { (void)hipStreamSynchronize(c->stream2); d->index_invalidate(); } }
     } fork_guard{ctx, db, forked};
     mark();
     // a2 + a3 counters
@@ -90,7 +96,7 @@ int step_enqueue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads
     PTX_TRY(strain_prezero(ctx, db));   // zero-fills of the strain step, while this stream would wait for the trio index anyway
     struct PreZeroGuard { LadBatch &lb; ~PreZeroGuard() { lb.prezeroed = false; } } prezero_guard{db->lad};   // never outlives this call
     PTX_TRY(coverage_prepare(ctx, db, reads, true));   // arena zero-fill + walk sums of long reads: need the binning, not the trio index
-    struct CovPrepGuard { Db *d; ~CovPrepGuard() { d->cov_prepared = false; } } covprep_guard{db};
+    struct CovPrepGuard { Db *d; ~CovPrepGuard() { d->cov.prepare_dropped(); } } covprep_guard{db};   // (no-op once the coverage pass has begun)
     mark();
     // a8 needs both
     if (forked) PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0));
@@ -137,20 +143,11 @@ extern "C" int pantax_hip_trio_index_prefetch(pantax_hip_ctx *ctx, pantax_hip_db
     if (!ctx || !db) return PANTAX_HIP_E_INVALID;
     PTX_ENTER(ctx);
     if (db->d_node_rec.p == nullptr) return fail(ctx, PANTAX_HIP_E_STATE, "trio_index_prefetch: the db was uploaded without graphs (ranges only)");
-    db->trio_built = false; db->cov_done = false; db->U = 0; db->trio_prefetched = false;
-    if (db->trio_free_valid && !ctx->cfg.trio_after_step) PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, db->ev_trio_free, 0));
-    else {
-        PTX_HIP(ctx, hipEventRecord(ctx->ev_seq, ctx->stream));
-        PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_seq, 0));
-    }
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream_main = main_stream; ctx->stream = ctx->stream2;
-    const int rc = trio_index_build(ctx, db, false);
-    const hipError_t e = hipEventRecord(ctx->ev_fork, ctx->stream2);
-    ctx->stream = main_stream; ctx->stream_main = nullptr;
-    if (rc != 0 || e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream2); db->trio_built = false; if (rc != 0) return rc; PTX_HIP(ctx, e); }
+    db->index_invalidate();
+    db->trio.prefetch_consumed();
+    PTX_TRY(trio_build_forked(ctx, db));
     PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_fork, 0));
-    db->trio_prefetched = true;
+    db->trio.prefetched();
     return 0;
 }
 

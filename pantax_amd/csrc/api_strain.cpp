@@ -118,8 +118,8 @@ int strain_prezero(Ctx *ctx, Db *db) {
 // Enqueues the whole strain step and the download of its result arena; nothing waits for the host.
 // d_active: device [S] or null.
 int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const uint8_t *d_active, int slot) {
-    if (!db->cov_done) return fail(ctx, PANTAX_HIP_E_STATE, "strain_profile: call pantax_hip_node_coverage first");
-    if (!db->trio_built) return fail(ctx, PANTAX_HIP_E_STATE, "strain_profile: call pantax_hip_trio_index first");
+    if (!db->cov.strain_may_run()) return fail(ctx, PANTAX_HIP_E_STATE, "strain_profile: call pantax_hip_node_coverage first");
+    if (!db->trio.built()) return fail(ctx, PANTAX_HIP_E_STATE, "strain_profile: call pantax_hip_trio_index first");
     if (cfg->sample_nodes < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_profile: sample_nodes %d", cfg->sample_nodes);
     if (cfg->solver_semantics != PANTAX_HIP_SEMANTICS_GUROBI && cfg->solver_semantics != PANTAX_HIP_SEMANTICS_HIGHS)
         return fail(ctx, PANTAX_HIP_E_INVALID, "strain_profile: solver_semantics %d", cfg->solver_semantics);
@@ -142,27 +142,27 @@ int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const 
         PTX_HIP(ctx, hipMemcpyAsync(lb.d_counts.p + 3, db->trio_scratch.d_tot.p + 2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     mark();
     // the resident step (the coverage pass left its counts to node_stats_launch): this call's two statistics passes are the only readers of the coverage
-    // arena, once -- they zero it for the next step's coverage pass.  A stage caller may read bases / trio_bases again, so nothing is cleaned for it.
-    // cov_clean_async: the fill goes onto the side stream instead, in front of the LPs (below) -- not while every kernel is being clocked (a bracket on the side
-    // stream measures the overlap, and the per-kernel table wants the fill's own time).  -1: from 1 GiB of arena on (cfg4: 4.8 GB, 17.73 -> 17.42 ms a step; the reference-DB shape 27.7 -> 27.3; at 0.4 GB the
-    // two events cost more than the 0.07 ms fill)
+    // arena, once.  How it gets back to zero for the next step's coverage pass is cov_clean_plan's (cov_state.hpp): they zero what they read, a fill goes
+    // onto the side stream in front of the LPs (below), or the next pass fills in front of itself.  A stage caller may read bases / trio_bases again, so
+    // nothing is cleaned for it.
+    const bool resident = db->cov.count_pending();
     const bool clocked = ctx->timing && ctx->timing_filter.empty();     // (named launches only: the fill overlaps, unbracketed)
-    const bool clean_async = db->cov_count_pending && !ctx->cfg.cov_self_clean && !clocked &&
-                             (ctx->cfg.cov_clean_async > 0 || (ctx->cfg.cov_clean_async < 0 && db->cov_arena_total >= ((size_t)1 << 30)));
-    // the species flags the coverage pass of THIS step masked its reads with (the resident step: cov_count_pending): the two statistics passes skip what it skipped
-    const uint8_t *skip_absent = db->cov_count_pending ? d_active : nullptr;
-    db->cov_self_clean = db->cov_count_pending && ctx->cfg.cov_self_clean && db->U != 0;
-    PTX_TRY(hap_trio_stats_launch(ctx, db, db->d_hap_nnz, db->d_hap_mean, skip_absent));                 // a9 statistics
+    const CovClean clean = cov_clean_plan(resident, ctx->cfg.cov_readers_clean, ctx->cfg.cov_clean_async, clocked, db->cov.arena_bytes(), db->U);
+    const bool readers_clean = clean == CovClean::readers_clean;
+    struct CleanGuard { Db *d; bool armed; ~CleanGuard() { if (armed) d->cov.invalidated(); } } clean_guard{db, readers_clean};   // (a failure among the cleaning readers: neither a result nor zero)
+    // the species flags the coverage pass of THIS step masked its reads with: the two statistics passes skip what it skipped
+    const uint8_t *skip_absent = resident ? d_active : nullptr;
+    PTX_TRY(hap_trio_stats_launch(ctx, db, db->d_hap_nnz, db->d_hap_mean, skip_absent, readers_clean));                 // a9 statistics
     mark();
     // ONE pass over the nodes where the step is eligible (node_rows_kernel, inside lad_prepare's row sort): the first filter reads the unique-trio statistics
     // alone, so the LP columns are known before any node is looked at, and the statistics below are first needed by lad_pair_launch
-    lb.node_pass_fused = node_pass_fused_eligible(ctx, db, cfg);
+    lb.node_pass_fused = node_pass_fused_eligible(ctx, db, cfg, readers_clean);
     lb.fused_min_depth = (double)cfg->min_depth;
     lb.fused_active = ctx->cfg.no_absent_skip ? nullptr : skip_absent;
     if (lb.node_pass_fused) lb.S = S;
     else
-    PTX_TRY(node_stats_launch(ctx, db, &lb, cfg->min_depth, skip_absent));                               // abundances + per-species stats
-    if (db->cov_self_clean) { db->cov_arena_clean = true; db->cov_done = false; db->cov_self_clean = false; }   // (cov_done: the arena no longer holds a coverage result)
+    PTX_TRY(node_stats_launch(ctx, db, &lb, cfg->min_depth, skip_absent, readers_clean));                              // abundances + per-species stats
+    if (readers_clean) { db->cov.readers_cleaned(); clean_guard.armed = false; }   // (the arena no longer holds a coverage result)
     mark();
     PTX_TRY(row_sample_apply(ctx, db, &lb, cfg->sample_nodes));
     mark();                             // a11 (no-op unless a species is larger than --sample)
@@ -174,21 +174,21 @@ int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const 
     // ... by default from behind the ROW COMPACTION (lad_prepare records the event there): the compaction is a chained scan whose tiles
     // spin on their predecessors, and beside the rebuild's kernels its 3 ms stretched to 9-13 (round 4); PANTAX_TRIO_FREE=filter: from here
     const bool free_at_filter = ctx->cfg.trio_free_at_filter;
-    db->trio_free_pending = !free_at_filter;
-    if (free_at_filter) { PTX_HIP(ctx, hipEventRecord(db->ev_trio_free, ctx->stream)); db->trio_free_valid = true; }
+    if (free_at_filter) { PTX_HIP(ctx, hipEventRecord(db->ev_trio_free, ctx->stream)); db->trio.free_event_recorded(); }
+    else db->trio.free_event_awaited();
     mark();
     int pmax_bound = 1;                                                                     // mask bits of a row key: min(#haps, 64) (wide species: a 64-bit hash)
     for (uint32_t s = 0; s < S; ++s) pmax_bound = std::max<int>(pmax_bound, (int)std::min<uint64_t>(db->h_hap_off[s + 1] - db->h_hap_off[s], LAD_MAXP));
     {
         const int rc_prep = lad_prepare(ctx, db, &lb, true, pmax_bound);                   // a10 + row grouping
         if (rc_prep != 0) {   // failed before it recorded the event: no stale event may order the next step's rebuild (it falls back to ev_seq)
-            db->trio_free_pending = false; db->trio_free_valid = false;
+            db->trio.free_event_void();
             return rc_prep;
         }
     }
-    if (db->trio_free_pending) { PTX_HIP(ctx, hipEventRecord(db->ev_trio_free, ctx->stream)); db->trio_free_valid = true; db->trio_free_pending = false; }
+    if (db->trio.free_event_pending()) { PTX_HIP(ctx, hipEventRecord(db->ev_trio_free, ctx->stream)); db->trio.free_event_recorded(); }
     mark();
-    if (clean_async) PTX_TRY(coverage_arena_clean_async(ctx, db));   // beside the LPs: one workgroup per species, most of the memory system idle
+    if (clean == CovClean::side_fill) PTX_TRY(coverage_arena_clean_async(ctx, db));   // beside the LPs: one workgroup per species, most of the memory system idle
     PTX_TRY(lad_pair_launch(ctx, db, &lb, pmax_bound, fc));                                 // LP 1 -> a13 decision -> LP 2, objectives
     mark();
     PTX_TRY(fetch_arena_enqueue(ctx, db, L, slot));
@@ -387,7 +387,6 @@ int pantax_hip_pao_solve_batch(pantax_hip_ctx *ctx, const pantax_hip_species_bat
     std::vector<uint32_t> cov32(V ? V : 1, 0);
     if (in->node_base_cov) for (uint64_t v = 0; v < V; ++v) cov32[v] = (uint32_t)in->node_base_cov[v];
     PTX_TRY(upload(ctx, db->d_cov, cov32.data(), V));
-    db->cov_count_pending = false;
     PTX_TRY(upload(ctx, lb.d_ab, in->node_abundance, V));
     std::vector<double> amax(S);
     std::vector<uint32_t> nvalid(S);
@@ -560,10 +559,9 @@ static int check_hap_selection(pantax_hip_ctx *ctx, const pantax_hip_db *db, con
 // ... and what their kernels read: bases_per_node in the coverage arena, node_base_cov in d_cov -- as the STAGE call leaves them
 static int check_stage_coverage(pantax_hip_ctx *ctx, const pantax_hip_db *db, const char *what) {
     if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "%s: %d enqueued step(s) of this db have not been collected", what, db->step_inflight);
-    const bool arena_gone = db->cov_arena_clean || db->cov_clean_pending;
-    if (!db->cov_done || !db->cov_stage || db->cov_count_pending || arena_gone || db->d_cov.n < db->V || (db->V && (!db->d_cov.p || !db->d_bases.p)))
+    if (!db->cov.stage_report_may_run() || db->d_cov.n < db->V || (db->V && (!db->d_cov.p || !db->d_bases.p)))
         return fail(ctx, PANTAX_HIP_E_STATE, "%s: the db holds no coverage result of pantax_hip_node_coverage%s; call pantax_hip_node_coverage first", what,
-                    db->cov_done || arena_gone ? " (a resident step counts the covered bases in its own passes, keeps no node_base_cov and may have zeroed the coverage arena)" : "");
+                    db->cov.resident_used_it() ? " (a resident step counts the covered bases in its own passes, keeps no node_base_cov and may have zeroed the coverage arena)" : "");
     return 0;
 }
 

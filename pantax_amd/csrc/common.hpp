@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "../../include/pantax_hip.h"
+#include "cov_state.hpp"
 
 #ifndef TRIO_LH_PACK
 #define TRIO_LH_PACK 0   // 1: length and owner of a row in ONE 8-byte record (measurement builds)
@@ -156,7 +157,7 @@ struct CtxConfig {
     int covl_shape = -1;             // shape of the long-walk kernel: <U><groups per workgroup / 8><window / 1024><back / 256> (default 2834)
     bool cov_count = false;          // resident step: popcount_kernel as in the stage call
     int cov_clean_async = -1;        // resident step: the coverage arena's zero fill goes onto the side stream, beside the LPs (1; -1: arenas of 1 GiB and more); 0: in front of the coverage pass
-    bool cov_self_clean = false;     // resident step: the last readers of the coverage arena zero it instead of a zero fill in front of every coverage pass.  OFF: measured
+    bool cov_readers_clean = false;  // (option cov_self_clean) resident step: the last readers of the coverage arena zero it instead of a zero fill in front of every coverage pass.  OFF: measured
                                      // slower (node_cov_stats_kernel 2.5 -> 6.9 ms with the stores among its loads against 1.5 ms of zero fill at 1e4 strains)
     bool walk_sum_in_bin = false;    // the walk sums of long reads inside the binning pass instead of by walk_sum_kernel.  OFF: measured -- the row of 16 lanes that streams a
                                      // long walk in bin_slots_kernel adds 0.63 ms there at the cfg5 share where walk_sum_kernel takes 0.38 (cfg5 at full size: +2.7 against 2.9);
@@ -207,7 +208,7 @@ struct Ctx {
     NumaInfo numa;
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream_main = nullptr;   // the main stream while `stream` is swapped to the side stream (api_step.cpp), else null
+    hipStream_t stream_main = nullptr;   // the main stream while `stream` is swapped to the side stream (SideStream below), else null
     hipStream_t stream2 = nullptr;   // side stream of the resident step (the trio index does not depend on the reads)
     hipStream_t stream_up = nullptr; // copy stream of the file seam's graph loader thread (round 6; created on first use): the next group of species travels while this one's tables are built
     hipEvent_t ev_fork = nullptr;
@@ -233,6 +234,17 @@ struct Ctx {
     size_t pin_up_off = 0;       // on its last lap have run (an event per stream, recorded when the ring leaves the half) -- steps enqueued
     hipEvent_t pin_up_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // back to back share it without a host wait in between
     bool pin_up_ev_set[2] = {false, false};
+};
+
+// While one lives, whatever enqueues on ctx->stream goes onto the side stream (ctx->stream2) and ctx->stream_main names the main stream; both are put
+// back when it goes out of scope, whichever way.  It does not nest: on a ctx that is already on its side stream it swaps nothing and tests false.
+struct SideStream {
+    Ctx *c;
+    explicit SideStream(Ctx *ctx) : c(ctx->stream_main ? nullptr : ctx) { if (c) { c->stream_main = c->stream; c->stream = c->stream2; } }
+    ~SideStream() { if (c) { c->stream = c->stream_main; c->stream_main = nullptr; } }
+    SideStream(const SideStream &) = delete;
+    SideStream &operator=(const SideStream &) = delete;
+    explicit operator bool() const { return c != nullptr; }
 };
 
 // RAII-less timing scope: records events around a launch when ctx->timing is on
@@ -407,23 +419,11 @@ struct Db {
     // canonical order.  A row IS its lookup entry: d_trio_ent[r], d_trio_len[r], d_trio_hap[r], d_trio_bases[r] belong together, the lookup head
     // of a node {first row, #rows} rides in its node record.  The (species, hap, position) order the C ABI hands out (pantax_hip_trio_get,
     // trio_bases of pantax_hip_node_coverage) is a permutation made on request (trio_export_ensure): it costs nothing on the step's path.
-    bool trio_built = false;
-    bool trio_prefetched = false;   // pantax_hip_trio_index_prefetch built the index of the COMING step: that step's rebuild_trio is served by it
-    bool trio_keys_built = false;   // d_trio_q (window start of every row: what the export order is made from) was written by the last build
-    bool trio_perm_valid = false;   // d_trio_perm holds the export order of the last build
-    uint64_t U = 0;
-    bool cov_prepared = false;       // coverage_prepare ran for the coming coverage_launch
-    bool cov_count_pending = false;  // d_cov of the last coverage pass is still to be counted from the bitmap (node_stats_launch does it, or the fused node pass, which needs no d_cov)
-    // round 6: in the resident step the last readers of the coverage arena (hap_rows_pass_kernel<0>: trio_bases; node_cov_stats_kernel: bases, bit vector,
-    // full-node flags) zero what they read, and the next coverage pass skips its zero fill.  cov_self_clean: this step's readers clean (set by
-    // strain_enqueue); cov_arena_clean + its signature: the arena is all zero in exactly this layout (reset by whatever dirties it).
-    bool cov_self_clean = false, cov_arena_clean = false;
-    uint64_t cov_arena_sig = 0;
-    // ... or (cov_clean_async) the arena is zero-filled on the SIDE stream from behind those readers, beside the step's row sort and LPs: the next coverage
-    // pass waits for ev_cov_clean instead of filling in front of itself
-    size_t cov_arena_total = 0;
-    hipEvent_t ev_cov_read = nullptr, ev_cov_clean = nullptr;
-    bool cov_clean_pending = false;
+    TrioState trio;                 // how far the index is built, prefetched, exported (cov_state.hpp)
+    uint64_t U = 0;                 // rows of the index; 0 while there is none (reset by TrioState::invalidate alone)
+    CovState cov;                   // what the coverage arena holds (cov_state.hpp; DESIGN.md, "Lifecycle of the coverage arena and of the unique-trio index")
+    hipEvent_t ev_cov_read = nullptr, ev_cov_clean = nullptr;   // the side-stream fill of the arena: behind its last readers / over
+    void index_invalidate() { trio.invalidate(U); cov.invalidated(); }   // a coverage result counts trio_bases by the rows of ITS index
     bool trio_sizes_known = false;   // U, the rows per haplotype and per species depend on the graphs only: kept across db_reset
     uint64_t U_known = 0;
     bool trio_layout_fast = false;   // the sizes were learnt by a build that filed the visit table's species from its records (else: every species by the pass over the walks)
@@ -452,9 +452,7 @@ struct Db {
     uint32_t stat_lds_haps = 0;      // most haplotypes of a species whose chunk accumulators live in LDS (65 .. 1024; up to 64: lane registers)
     bool stat_global_rows = false;   // a species of more than 1024 haplotypes accumulates in its chunks' own (zero-filled) rows of partials
     DevBuf<uint32_t> d_sp_chunk_off; // [S+1] first chunk of every species (species without rows: empty range)
-    // coverage state (a8), resident for the strain step
-    bool cov_done = false;
-    bool cov_stage = false;          // ... left by the stage call pantax_hip_node_coverage (node_base_cov counted into d_cov), not by a resident step: what pantax_hip_strain_cov_track reads
+    // coverage (a8), resident for the strain step
     // d_bases, d_trio_bases, the abort counter and d_bitmap are windows of one arena: one memset per coverage pass
     DevBuf<uint8_t> d_cov_arena;
     unsigned long long *d_abort = nullptr;
@@ -485,9 +483,8 @@ struct Db {
     pantax_hip_step_config step_cfg[2];
     int stats_slot = -1;             // h_arena slot of the step collected last (pantax_hip_strain_node_stats), -1: none yet
     int step_enq = 0, step_col = 0, step_inflight = 0;   // slot of the next enqueue / the next collect; steps enqueued and not yet collected
-    hipEvent_t ev_trio_free = nullptr;   // recorded behind the last reader of the unique-trio tables in a step: the next step's rebuild waits
-    bool trio_free_valid = false;        // for this, not for the whole previous step (its row sort and LPs run beside the rebuild)
-    bool trio_free_pending = false;      // the event is still to be recorded by lad_prepare, behind the row compaction
+    hipEvent_t ev_trio_free = nullptr;   // recorded behind the last reader of the unique-trio tables in a step: the next step's rebuild waits for this (TrioState::free_event_valid),
+                                         // not for the whole previous step (its row sort and LPs run beside the rebuild)
     ~Db() { for (hipEvent_t e : ev_step) if (e) (void)hipEventDestroy(e); if (ev_trio_free) (void)hipEventDestroy(ev_trio_free);
             if (ev_cov_read) (void)hipEventDestroy(ev_cov_read); if (ev_cov_clean) (void)hipEventDestroy(ev_cov_clean); }
     // LP-row staging (lad_prepare)
@@ -678,7 +675,7 @@ int bin_reads_launch(Ctx *ctx, const Db *db, Reads *rd, unsigned long long *d_co
 int species_ensure(Ctx *ctx, Reads *rd);   // d_species in file order (resident reads keep the species per slot)
 int coverage_arena_clean_async(Ctx *ctx, Db *db);   // resident step: the arena's zero fill on the side stream (option cov_clean_async)
 int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio);   // optional, ahead of coverage_launch (needs the binning and db->U only)
-// defer_count: leave node_base_cov (popcount_kernel) to the node statistics pass that follows in the resident step (db->cov_count_pending)
+// defer_count: leave node_base_cov (popcount_kernel) to the node statistics pass that follows in the resident step (CovState::count_pending)
 int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool with_trio, bool defer_count = false);
 // stage_cov_step.hip: round 5's kernel for the groups of longer walks (option cov_long=step), in the shape the pass's plan names (cov_plan.hpp)
 struct CovPlan;

@@ -8,9 +8,10 @@ namespace ptx {
 
 // a9: per-hap unique-trio statistics (zscore_filter profile.rs:1028-1051; :1114-1147)
 int hap_trio_stats_launch(Ctx *ctx, Db *db, DevBuf<uint32_t> &d_ntrio_nz /*[H]*/, DevBuf<double> &d_mean /*[H]*/,
-                          const uint8_t *d_active = nullptr /* device [S] or null: species the coverage pass skipped are not read */);
+                          const uint8_t *d_active /* device [S] or null: species the coverage pass skipped are not read */,
+                          bool readers_clean /* the pass zeroes the trio_bases it reads (cov_clean_plan, cov_state.hpp) */);
 // node abundance + per-species stats
-int node_stats_launch(Ctx *ctx, Db *db, LadBatch *lb, int64_t min_depth, const uint8_t *d_active = nullptr);
+int node_stats_launch(Ctx *ctx, Db *db, LadBatch *lb, int64_t min_depth, const uint8_t *d_active, bool readers_clean /* ... bases, bit vector, full-node flags */);
 // Which route the LP rows take: a pure function of the options and of the db's host-side tables (h_node_off, h_hap_off, the node -> haplotype state).
 // node_pass_fused_eligible (before the step's first kernel) and lad_prepare (later) both decide from it.
 struct RowRoute {
@@ -26,7 +27,7 @@ struct RowRoute {
 RowRoute row_route(const Ctx *ctx, const Db *db);
 int row_pack_shift(const RowRoute &rt, uint32_t S, int pmax_bound);   // >= 0: two-word rows {species << shift | mask, a}; -1: three words
 // the resident step's fused node pass (node_rows_kernel in place of node_cov_stats_kernel + ssn_hist_kernel<true>): can THIS step take it?  Host-known only.
-bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg);
+bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg, bool readers_clean);
 // Which LDS shape the <= 16-column LAD solver launches with (stage_lad.hip: LadRoomy / LadCompact): a pure function of the option lad_shape ("" / "auto",
 // "roomy", "compact"), the number of solver workgroups of the launch (one per species), the device's CU count and the launch's column bound.
 //   auto: compact when the batch has more workgroups than the device has CUs -- they would queue for a CU one at a time under the roomy shape, while four

@@ -117,13 +117,14 @@ int sample_sort_nodes(Ctx *ctx, const double *ab, const uint64_t *mask, const ui
         if (!ctx->ev_ssn_join) PTX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_ssn_join, hipEventDisableTiming));
         PTX_HIP(ctx, hipEventRecord(ctx->ev_ssn_fork, ctx->stream));
         PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_ssn_fork, 0));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream_main = main_stream; ctx->stream = ctx->stream2;
-        tie_join.armed = true;
-        { KTimer t(ctx, "ssn_ties_kernel");
-          ssn_ties_launch(ctx, sn, S, pl.tie_grid); }
-        const hipError_t e = hipEventRecord(ctx->ev_ssn_join, ctx->stream2);
-        ctx->stream = main_stream; ctx->stream_main = nullptr;
+        hipError_t e;
+        {
+            SideStream side(ctx);   // (never refused: the plan above keeps the fill in line on a ctx that is on its side stream already)
+            tie_join.armed = true;
+            { KTimer t(ctx, "ssn_ties_kernel");
+              ssn_ties_launch(ctx, sn, S, pl.tie_grid); }
+            e = hipEventRecord(ctx->ev_ssn_join, ctx->stream2);
+        }
         PTX_HIP(ctx, e);
     }
     { KTimer t(ctx, "ssn_scatter_kernel");

@@ -640,14 +640,12 @@ int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio) {
     db->d_bitmap.view(base + off_bm, a.words);
     db->d_full.view(base + off_full, a.fwords);
     // (d_cov is allocated by the pass that writes it -- popcount_kernel below, node_stats_launch: a resident step on the fused node pass has none)
-    // the resident step's last readers left the arena zeroed (cov_arena_clean) unless its layout or place changed since: only the abort counter is reset
+    // the resident step's last readers, or its fill on the side stream, left the arena zeroed unless its layout or place changed since (the signature):
+    // only the abort counter is reset
     const uint64_t sig = (uint64_t)(uintptr_t)base ^ ((uint64_t)total * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)off_bm << 1) ^ ((uint64_t)off_full << 2) ^ (uint64_t)off_trio;
-    db->cov_arena_total = total;
-    if (db->cov_clean_pending) {   // a fill on the side stream (coverage_arena_clean_async): over before anything here touches the arena
-        PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, db->ev_cov_clean, 0));
-        db->cov_clean_pending = false;
-    }
-    if (db->cov_arena_clean && db->cov_arena_sig == sig) {
+    const CovPrepare todo = db->cov.prepare_begun(sig, total);
+    if (todo.wait_side_fill) PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, db->ev_cov_clean, 0));   // (coverage_arena_clean_async): over before anything here touches the arena
+    if (todo.skip_fill) {
         if (ctx->cfg.cov_arena_verify) {
             DevBuf<unsigned long long> d_nz;
             PTX_HIP(ctx, d_nz.alloc(1));
@@ -664,8 +662,6 @@ int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio) {
         KTimer t(ctx, "zero_fill_kernel");   // (the arena's fill is a kernel of the step like any other: timed with them)
         PTX_TRY(zero_fill(ctx, base, total));
     }
-    db->cov_arena_clean = false;   // the coming pass writes it
-    db->cov_arena_sig = sig;
     if (rd->R && rd->T_pad && rd->n_long && rd->long_sums_db != 0 && rd->long_sums_db == db->uid) {
         // the binning pass of these reads against THIS db took the walk sums on its way (bin_slots_kernel, round 6)
     } else if (rd->R && rd->T_pad && rd->n_long) {
@@ -677,7 +673,7 @@ int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio) {
                            rd->d_long_len0.p);
     }
     PTX_HIP(ctx, hipGetLastError());
-    db->cov_prepared = true;
+    db->cov.prepare_finished();
     return 0;
 }
 
@@ -688,23 +684,25 @@ int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio) {
 // pass, which waits for gathers at 0.3 of the HBM rate: the same 0.3 ms as here -- a streaming fill slows a latency-bound neighbour by what it takes).  The next coverage_prepare waits for
 // ev_cov_clean.
 int coverage_arena_clean_async(Ctx *ctx, Db *db) {
-    if (!db->d_cov_arena.p || !db->cov_arena_total || !ctx->stream2) return 0;
+    if (!db->d_cov_arena.p || !db->cov.arena_bytes() || !ctx->stream2) return 0;
     uint8_t *f_ptr = db->d_cov_arena.p;
-    const size_t f_n = db->cov_arena_total;
+    const size_t f_n = db->cov.arena_bytes();
     if (!db->ev_cov_read) PTX_HIP(ctx, hipEventCreateWithFlags(&db->ev_cov_read, hipEventDisableTiming));
     if (!db->ev_cov_clean) PTX_HIP(ctx, hipEventCreateWithFlags(&db->ev_cov_clean, hipEventDisableTiming));
     PTX_HIP(ctx, hipEventRecord(db->ev_cov_read, ctx->stream));
     PTX_HIP(ctx, hipStreamWaitEvent(ctx->stream2, db->ev_cov_read, 0));
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream_main = main_stream; ctx->stream = ctx->stream2;
     int rc;
-    rc = zero_fill(ctx, f_ptr, f_n);
-    const hipError_t e = hipEventRecord(db->ev_cov_clean, ctx->stream2);
-    ctx->stream = main_stream; ctx->stream_main = nullptr;
+    hipError_t e;
+    {
+        SideStream side(ctx);
+        if (!side) return fail(ctx, PANTAX_HIP_E_STATE, "coverage arena fill: the ctx is already on its side stream");
+        rc = zero_fill(ctx, f_ptr, f_n);
+        e = hipEventRecord(db->ev_cov_clean, ctx->stream2);
+    }
+    db->cov.invalidated();          // the arena no longer holds a coverage result, whether the fill went out whole or not
     if (rc != 0) return rc;
     PTX_HIP(ctx, e);
-    db->cov_done = false;          // the arena no longer holds a coverage result
-    db->cov_arena_clean = true; db->cov_clean_pending = true;
+    db->cov.side_fill_enqueued();
     return 0;
 }
 
@@ -832,11 +830,10 @@ int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool w
     if (!rd->grouped) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: these reads are a slice kept as plain columns (to be routed to their owner), not resident reads");
     const bool trace = ctx->cfg.trace && !defer_count;
     CovLap lap{ctx, trace};
-    if (!db->cov_prepared) PTX_TRY(coverage_prepare(ctx, db, rd, with_trio));
+    if (db->cov.launch_needs_prepare()) PTX_TRY(coverage_prepare(ctx, db, rd, with_trio));
     lap("arena + zero fill");
-    db->cov_prepared = false;
-    db->cov_stage = false;         // (pantax_hip_node_coverage sets it behind its own pass)
-    db->trio_free_valid = false;   // a reader of the unique-trio tables goes onto the stream: the event of an earlier strain step no longer covers them
+    db->cov.launch_begun();
+    db->trio.free_event_void();    // a reader of the unique-trio tables goes onto the stream: the event of an earlier strain step no longer covers them
     const bool trio = with_trio && db->U;
     const uint8_t *d_act_fast = d_active;
     if (rd->R && rd->T_pad) PTX_TRY(active_flags(ctx, db, d_active, &d_act_fast));
@@ -860,11 +857,10 @@ int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool w
     }
     PTX_HIP(ctx, hipGetLastError());
     lap("coverage kernels");
-    db->cov_count_pending = defer_count && db->V != 0;   // the resident step: node_stats_launch counts the covered bases in its own pass
     if (db->V && !defer_count) PTX_TRY(count_launch(ctx, db));
     PTX_HIP(ctx, hipGetLastError());
     lap("popcount");
-    db->cov_done = true;
+    db->cov.launch_finished(defer_count && db->V != 0);   // (deferred, the resident step: node_stats_launch counts the covered bases in its own pass, or the fused node pass)
     return 0;
 }
 

@@ -338,7 +338,7 @@ int hap_stats_layout(Ctx *ctx, Db *db, const uint64_t *sp_first_row, const uint6
     return 0;
 }
 
-int hap_trio_stats_launch(Ctx *ctx, Db *db, DevBuf<uint32_t> &d_nnz, DevBuf<double> &d_mean, const uint8_t *d_active) {
+int hap_trio_stats_launch(Ctx *ctx, Db *db, DevBuf<uint32_t> &d_nnz, DevBuf<double> &d_mean, const uint8_t *d_active, bool readers_clean) {
     if (ctx->cfg.no_absent_skip) d_active = nullptr;
     PTX_HIP(ctx, d_nnz.alloc(db->H));
     PTX_HIP(ctx, d_mean.alloc(db->H));
@@ -358,7 +358,7 @@ int hap_trio_stats_launch(Ctx *ctx, Db *db, DevBuf<uint32_t> &d_nnz, DevBuf<doub
     if (db->stat_global_rows) { KTimer tz(ctx, "hap_partials_zero_fill"); PTX_TRY(zero_fill(ctx, part, NP * (sizeof(HapAcc) + (PP == 0 ? sizeof(HapBits) : 0)))); }   /* (the bits lie behind the partials) */ \
     if (NC) hipLaunchKernelGGL(hap_rows_pass_kernel<PP>, dim3(NC), dim3(64), lds_acc + (PP == 0 ? lds_bits : 0), ctx->stream, (const uint4 *)db->d_stat_chunks.p, (const uint64_t *)db->d_hap_off.p, \
                                TRIO_HAP_PTR(db), (unsigned long long *)db->d_trio_bases.p, (const trio_len_t *)db->d_trio_len.p,          \
-                               (const double *)mean0, (const double *)sd, part, pbits, db->d_hs_x.p, db->d_hs_h.p, db->d_hs_n.p, db->cov_self_clean ? 1u : 0u, d_active);  \
+                               (const double *)mean0, (const double *)sd, part, pbits, db->d_hs_x.p, db->d_hs_h.p, db->d_hs_n.p, readers_clean ? 1u : 0u, d_active);  \
     hipLaunchKernelGGL(hap_combine_kernel<PP>, dim3(S), dim3(256), 0, ctx->stream, (const uint32_t *)db->d_sp_chunk_off.p, (const uint4 *)db->d_stat_chunks.p,  \
                        (const uint64_t *)db->d_hap_off.p, (const HapAcc *)part, (const HapBits *)pbits, d_nnz.p, mean0, sd, d_mean.p);
     HS_PASS(0) HS_PASS(1) HS_PASS(2)

@@ -546,13 +546,13 @@ LadShape lad_shape(const std::string &option, uint32_t n_workgroups, int n_cu, i
 }
 const char *lad_shape_name(LadShape s) { return s == LadShape::compact ? "compact" : "roomy"; }
 
-// The fused node pass serves the resident step (the coverage pass left its counts: cov_count_pending) whose masks are formed in the sort, without a11 (it
+// The fused node pass serves the resident step (the coverage pass left its counts: CovState::count_pending) whose masks are formed in the sort, without a11 (it
 // needs nvalid on the host and edits the abundances in front of the sort), without the self-cleaning readers, and not the long-node variant of the
 // statistics kernel (the reference-DB shape: its per-stretch prefix in LDS does not fit beside the histogram pass's tree and tables -- it stays on the
 // two kernels).  Nothing hands `cov` or `ab` out after a resident step, so no output asks for the split path.  Option node_pass=split: never.
-bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg) {
-    if (ctx->cfg.node_pass == "split" || !db->cov_count_pending || db->V == 0) return false;
-    if (cfg->sample_nodes != 0 || ctx->cfg.cov_self_clean || db->cov_self_clean) return false;
+bool node_pass_fused_eligible(const Ctx *ctx, const Db *db, const pantax_hip_strain_config *cfg, bool readers_clean) {
+    if (ctx->cfg.node_pass == "split" || !db->cov.count_pending() || db->V == 0) return false;
+    if (cfg->sample_nodes != 0 || ctx->cfg.cov_readers_clean || readers_clean) return false;
     if (long_node_shape(db->L, db->V, ctx->cfg.ncs_prefix_min, ctx->cfg.ncs_no_prefix)) return false;
     return row_route(ctx, db).masks_in_sort;
 }
@@ -668,9 +668,9 @@ static int sort_rows(Ctx *ctx, Db *db, LadBatch *lb, const RowRoute &rt, int pma
         hipLaunchKernelGGL(row_emit_kernel, dim3(grid_rows ? grid_rows : 1), dim3(256), 0, ctx->stream, V, S, db->d_node_base.p, lb->d_ab.p,
                            (unsigned long long *)lb->d_mask.p, d_n, ka[0].p, ka[1].p, ka[2].p, pack_shift);
     }
-    if (db->trio_free_pending && db->ev_trio_free) {   // the next step's index rebuild may start from here (api_strain.cpp)
+    if (db->trio.free_event_pending() && db->ev_trio_free) {   // the next step's index rebuild may start from here (api_strain.cpp)
         PTX_HIP(ctx, hipEventRecord(db->ev_trio_free, ctx->stream));
-        db->trio_free_valid = true; db->trio_free_pending = false;
+        db->trio.free_event_recorded();
     }
     SortBufs A, B;
     A.nw = B.nw = pack_shift >= 0 ? 2 : 3;
@@ -701,7 +701,7 @@ static int sort_rows(Ctx *ctx, Db *db, LadBatch *lb, const RowRoute &rt, int pma
         }
         PTX_TRY(sample_sort_nodes(ctx, fused ? (const double *)nullptr : lb->d_ab.p, lb->d_mask.p, db->d_node_base.p, S, rt.max_vs, V, db->d_row16.p, A.k, pack_shift, db->d_ss_ws.p, d_n, &pat,
                                   rt.masks_in_sort ? &hp : nullptr, fused ? &fz : nullptr));
-        if (fused) db->cov_count_pending = false;             // the covered bases were counted (and used) inside the sort
+        if (fused) db->cov.counted();           // the covered bases were counted (and used) inside the sort
     } else if (rt.use_sample) {   // few rows: sample sort (6 launches) instead of 10+ radix passes of 3 launches each
         PTX_HIP(ctx, db->d_ss_ws.alloc(sample_sort_ws_elems(V)));
         PTX_TRY(sample_sort3(ctx, A, B, V, db->d_ss_ws.p, d_n));

@@ -235,7 +235,7 @@ __global__ void __launch_bounds__(64) node_stats_final_kernel(uint32_t S, const 
     if (threadIdx.x == 0) { amax_out[s] = mx; nvalid_out[s] = (uint32_t)nv; nzsum_out[s] = zs; nzcnt_out[s] = (uint32_t)zc; }
 }
 
-int node_stats_launch(Ctx *ctx, Db *db, LadBatch *lb, int64_t min_depth, const uint8_t *d_active) {
+int node_stats_launch(Ctx *ctx, Db *db, LadBatch *lb, int64_t min_depth, const uint8_t *d_active, bool readers_clean) {
     if (ctx->cfg.no_absent_skip) d_active = nullptr;     // (tests compare, measurements)
     uint32_t S = db->S;
     lb->S = S;
@@ -243,7 +243,7 @@ int node_stats_launch(Ctx *ctx, Db *db, LadBatch *lb, int64_t min_depth, const u
     PTX_HIP(ctx, lb->d_amax.alloc(S)); PTX_HIP(ctx, lb->d_nvalid.alloc(S));
     PTX_HIP(ctx, lb->d_nzsum.alloc(S)); PTX_HIP(ctx, lb->d_nzcnt.alloc(S));
     PTX_HIP(ctx, lb->d_partial.alloc((size_t)S * STAT_CHUNKS * 4));
-    const bool with_cov = db->cov_count_pending;                 // the resident step left the covered-base counts to this pass
+    const bool with_cov = db->cov.count_pending();               // the resident step left the covered-base counts to this pass
     if (with_cov) PTX_HIP(ctx, db->d_cov.alloc(db->V));
     // the chunk table of this db (made once per variant): ~8192 workgroups in all for the fused kernel (it holds fewer workgroups per CU: shorter ones, so
     // that the last round is short), ~2048 for the plain one; every species at least one chunk and at most STAT_CHUNKS, in proportion to its nodes
@@ -264,7 +264,7 @@ int node_stats_launch(Ctx *ctx, Db *db, LadBatch *lb, int64_t min_depth, const u
     }
     KTimer t(ctx, with_cov ? "node_cov_stats_kernel" : "node_stats_kernel");
     if (with_cov) {
-        if (db->cov_self_clean)
+        if (readers_clean)
         hipLaunchKernelGGL(node_cov_stats_kernel<true>, dim3(nc.n), dim3(256), 0, ctx->stream, db->d_node_base.p, db->d_node_len.p, db->d_bases.p, db->d_bit_off.p,
                            db->d_full.p, db->d_bitmap.p, (double)min_depth, db->d_cov.p, lb->d_ab.p, (NodePartial *)lb->d_partial.p, (const uint32_t *)nc.d_chunk_sp.p, (const uint32_t *)nc.d_sp_off.p, d_active);
         else if (long_node_shape(db->L, db->V, ctx->cfg.ncs_prefix_min, ctx->cfg.ncs_no_prefix))   // long nodes on average (chunk graphs of single-genome species among them): counts from a per-stretch prefix in LDS
@@ -273,7 +273,7 @@ int node_stats_launch(Ctx *ctx, Db *db, LadBatch *lb, int64_t min_depth, const u
         else
         hipLaunchKernelGGL(node_cov_stats_kernel<false>, dim3(nc.n), dim3(256), 0, ctx->stream, db->d_node_base.p, db->d_node_len.p, db->d_bases.p, db->d_bit_off.p,
                            db->d_full.p, db->d_bitmap.p, (double)min_depth, db->d_cov.p, lb->d_ab.p, (NodePartial *)lb->d_partial.p, (const uint32_t *)nc.d_chunk_sp.p, (const uint32_t *)nc.d_sp_off.p, d_active);
-        db->cov_count_pending = false;
+        db->cov.counted();
     } else
     hipLaunchKernelGGL(node_stats_kernel, dim3(nc.n), dim3(256), 0, ctx->stream, db->d_node_base.p, db->d_node_len.p, db->d_bases.p,
                        (double)min_depth, lb->d_ab.p, (NodePartial *)lb->d_partial.p, (const uint32_t *)nc.d_chunk_sp.p, (const uint32_t *)nc.d_sp_off.p);

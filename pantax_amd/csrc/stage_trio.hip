@@ -182,8 +182,8 @@ static int trio_first_build_epilogue(Ctx *ctx, Db *db, const TrioPlan &pl) {
 // route, path route, or the one-pass rebuild).  Which of it runs is the plan's; the order below is the order on the stream.
 // with_keys: the window start of every row is kept as well (d_trio_q): what the exporters build the (species, hap, position) order from.
 int trio_index_build(Ctx *ctx, Db *db, bool with_keys) {
-    db->trio_keys_built = false;
-    db->trio_perm_valid = false;
+    const bool same_rows = db->trio.built();   // (the exporters' rebuild with the window starts: a row keeps its number, a coverage result stays valid)
+    db->trio.build_begun();
     if (db->P >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "trio_index: %llu path steps exceed 32-bit positions", (unsigned long long)db->P);
     TrioPlanIn in = trio_plan_in(ctx, db, with_keys);
     TrioPlan pl = trio_plan(in);
@@ -206,15 +206,14 @@ int trio_index_build(Ctx *ctx, Db *db, bool with_keys) {
     if (pl.path_route) PTX_TRY(trio_path_rows_launch(ctx, db, pl, ro));
     PTX_HIP(ctx, hipGetLastError());
     if (pl.first_build) PTX_TRY(trio_first_build_epilogue(ctx, db, pl));           // 8. first-build epilogue
-    db->trio_built = true;
-    db->trio_keys_built = with_keys;
-    db->cov_done = false;
+    db->trio.build_finished(with_keys);
+    if (!same_rows) db->cov.invalidated();
     return 0;
 }
 
 // the window start of every row is wanted (the exporters): rebuild with it unless it is there
 int trio_keys_ensure(Ctx *ctx, Db *db) {
-    if (db->trio_built && db->trio_keys_built) return 0;
+    if (db->trio.has_keys()) return 0;
     if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "trio tables: %d enqueued step(s) of this db have not been collected", db->step_inflight);
     PTX_HIP(ctx, hipStreamSynchronize(ctx->stream2));   // a step's rebuild on the side stream is over before the tables are replaced
     return trio_index_build(ctx, db, true);
@@ -224,7 +223,7 @@ int trio_keys_ensure(Ctx *ctx, Db *db) {
 // haplotypes are one CSR in that order).  Off the step's path: only pantax_hip_trio_get and the trio_bases of pantax_hip_node_coverage ask.
 int trio_export_ensure(Ctx *ctx, Db *db) {
     PTX_TRY(trio_keys_ensure(ctx, db));
-    if (db->trio_perm_valid) return 0;
+    if (db->trio.export_order_valid()) return 0;
     const uint64_t U = db->U;
     PTX_HIP(ctx, db->d_trio_perm.alloc(U ? U : 1));
     if (U) {
@@ -242,7 +241,7 @@ int trio_export_ensure(Ctx *ctx, Db *db) {
         if (in_b) PTX_HIP(ctx, hipMemcpyAsync(db->d_trio_perm.p, vb.p, U * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
         PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the sort's buffers go out of scope
     }
-    db->trio_perm_valid = true;
+    db->trio.export_order_made();
     return 0;
 }
 
@@ -262,7 +261,7 @@ extern "C" {
 int pantax_hip_trio_index(pantax_hip_ctx *ctx, pantax_hip_db *db, uint64_t *n_unique_total_out) {
     if (!ctx || !db) return PANTAX_HIP_E_INVALID;
     PTX_ENTER(ctx);
-    if (!db->trio_built) {
+    if (!db->trio.built()) {
         const bool rebuild = db->trio_sizes_known;
         PTX_TRY(trio_index_build(ctx, db));
         // a db's FIRST build reads the error word of its kernels itself; a rebuild (after pantax_hip_db_reset) leaves it for the pipelined step to
@@ -272,7 +271,7 @@ int pantax_hip_trio_index(pantax_hip_ctx *ctx, pantax_hip_db *db, uint64_t *n_un
             PTX_TRY(download(ctx, &err, db->trio_scratch.d_tot.p + 2, 1));
             PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
             if (err) {
-                db->trio_built = false;
+                db->index_invalidate();
                 return fail(ctx, PANTAX_HIP_E_LIMIT, "trio_index: %u problems in the rebuild's kernels: visit groups out of order / offsets that are not this table's, or a node "
                                                      "that heads 2^16 or more unique-trio rows", err);
             }
@@ -286,15 +285,13 @@ int pantax_hip_trio_get(pantax_hip_ctx *ctx, const pantax_hip_db *cdb, uint32_t 
                         uint64_t *hap_trio_off_out) {
     if (!ctx || !cdb) return PANTAX_HIP_E_INVALID;
     pantax_hip_db *db = const_cast<pantax_hip_db *>(cdb);
-    if (!db->trio_built) return fail(ctx, PANTAX_HIP_E_STATE, "trio_get: call pantax_hip_trio_index first");
+    if (!db->trio.built()) return fail(ctx, PANTAX_HIP_E_STATE, "trio_get: call pantax_hip_trio_index first");
     PTX_ENTER(ctx);
     const uint64_t U = db->U;
     if ((abc_out || hap_out || len_out) && U) {
         // the table in (species, hap, position) order is an export: the rows are permuted on the device (the last build may have been a
-        // step's, without the window starts: the same index is built again with them -- coverage results stay valid, a row keeps its number)
-        const bool cov_done = db->cov_done;
+        // step's, without the window starts: the same index is built again with them)
         PTX_TRY(trio_export_ensure(ctx, db));
-        db->cov_done = cov_done;
         DevBuf<uint32_t> d_abc, d_hap, d_len;
         if (abc_out) PTX_HIP(ctx, d_abc.alloc(3 * U));
         if (hap_out) PTX_HIP(ctx, d_hap.alloc(U));

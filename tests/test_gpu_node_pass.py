@@ -217,3 +217,40 @@ def test_pipelined_steps_with_the_side_stream_arena_fill(eng, corner_set, set_op
         assert "node_rows_kernel" in eng.timing_get()
     finally:
         eng.timing_enable(False)
+
+
+def test_pipelined_steps_with_the_last_readers_cleaning_the_arena(eng, corner_set, set_opt):
+    """Three resident steps in flight behind each other with option cov_self_clean=1: the last readers of the coverage arena (the haplotype statistics
+    and the node statistics pass) zero what they read, every coverage pass after the first skips its zero fill, and cov_arena_verify counts the arena's
+    non-zero words before each such pass.  The results are those of the same three steps under the default options, array by array."""
+    from pantax_amd.pipeline import StepConfig, profile_step, profile_steps_pipelined
+    sset = corner_set
+    set_opt(eng, "row_sort", "nodes")
+    eng.upload_db(sset.species)
+    rd = sset.reads
+    names = [g.name for g in sset.species]
+    haps = [h for g in sset.species for h in g.hap_names]
+    avg = _avg(sset)
+    rng = np.random.default_rng(5)
+    flag_sets = [None] + [(rng.random(rd.n_reads) < f).astype(np.uint8) for f in (0.4, 0.7)]   # three different samples of the same reads
+    single = []
+    for fl in flag_sets:                         # (the default options: a zero fill in front of every coverage pass or beside the LPs, nothing verified)
+        eng.upload_packed(rd, fl)
+        single.append(profile_step(eng, names, haps, avg, StepConfig()))
+    set_opt(eng, "cov_self_clean", "1")
+    set_opt(eng, "cov_arena_verify", "1")
+    got = profile_steps_pipelined(eng, names, haps, avg, len(flag_sets), StepConfig(), next_input=lambda i: eng.upload_packed(rd, flag_sets[i]))
+    assert len(got) == len(single)
+    for a, b in zip(got, single):
+        assert a[0] == b[0] and a[1] == b[1] and a[2]["n_active"] == b[2]["n_active"] and a[2]["n_rows"] == b[2]["n_rows"] and a[2]["iters"] == b[2]["iters"]
+        assert a[2]["n_cand"] == b[2]["n_cand"] and a[2]["n_patterns"] == b[2]["n_patterns"]
+        assert np.array_equal(np.array(a[2]["obj"], dtype=float), np.array(b[2]["obj"], dtype=float), equal_nan=True)
+    assert single[1][1] != single[0][1]
+    eng.timing_enable(True)                      # (the path the pipelined steps took: one more step, which finds the arena clean; its launches named)
+    eng.timing_reset()
+    try:
+        profile_step(eng, names, haps, avg, StepConfig())
+        ran = set(eng.timing_get())
+        assert "node_cov_stats_kernel" in ran and "node_rows_kernel" not in ran and "zero_fill_kernel" not in ran, sorted(ran)
+    finally:
+        eng.timing_enable(False)
