@@ -168,8 +168,19 @@ int db_upload_begin(Ctx *ctx, uint32_t S, const int64_t *range_start, const int6
 int db_upload_arrays(Ctx *ctx, pantax_hip_db *db, const GraphPart *parts, const std::string *files, hipStream_t stream_arg) {
     const uint32_t S = db->S;
     const hipStream_t stream = stream_arg ? stream_arg : ctx->stream;
-    // small tables go through plain asynchronous copies from vectors that live until the closing wait (not through the ctx's staging buffers:
-    // this may be a loader thread beside the thread that owns them)
+    // The scratch of the packed sections and the host tables copied from, declared in front of the wait that every exit takes: a failure part-way
+    // must not hand scratch back to the device cache, or free a table, that a copy or a kernel queued on `stream` still uses -- on the loader
+    // thread `stream` is a copy stream the cache does not wait for (dev_cache_alloc)
+    DevBuf<uint16_t> d_len16;
+    DevBuf<WidenSpecies> d_wt;
+    DevBuf<uint32_t> d_pk_first, d_pk_off;
+    DevBuf<uint8_t> d_pk_payload;
+    DevBuf<UnpackSpecies> d_ut;
+    std::vector<WidenSpecies> wt;
+    std::vector<UnpackSpecies> ut;
+    struct StreamWait { hipStream_t st; ~StreamWait() { (void)hipStreamSynchronize(st); } } wait_on_exit{stream};
+    // small tables go through plain asynchronous copies from vectors that live until the closing wait (not through the ctx's small-upload ring:
+    // this may be a loader thread beside the thread that owns it)
     auto put = [&](void *dst, const void *src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
     {   // the two big arrays: every species' stretch of them, back to back, through ONE chunk pipeline each.  Species that come PACKED (image
         // format 4: 16-bit lengths, walks as blocks of deltas) send their packed sections through pipelines of their own into scratch, and
@@ -191,10 +202,7 @@ int db_upload_arrays(Ctx *ctx, pantax_hip_db *db, const GraphPart *parts, const 
             if (bad >= 0) return fail(ctx, PANTAX_HIP_E_LIMIT, "db_upload: species %u holds a node of negative length or longer than 2^32 - 1 (reference asserts > 0, profile.rs:494)", seg_species[bad]);
             segs.clear(); seg_species.clear();
         }
-        DevBuf<uint16_t> d_len16;
-        DevBuf<WidenSpecies> d_wt;
         if (n_len16) {
-            std::vector<WidenSpecies> wt;
             uint64_t at = 0;
             for (uint32_t s = 0; s < S; ++s) {
                 if (!parts[s].len16) continue;
@@ -208,14 +216,10 @@ int db_upload_arrays(Ctx *ctx, pantax_hip_db *db, const GraphPart *parts, const 
             PTX_HIP(ctx, put(d_wt.p, wt.data(), wt.size() * sizeof(WidenSpecies)));
             PTX_TRY(upload_segments(ctx, d_len16.p, segs.data(), segs.size(), files, nullptr, stream));
             PTX_TRY(lens_widen_launch(ctx, d_wt.p, (uint32_t)wt.size(), at, d_len16.p, db->d_node_len.p, stream_arg));
-            PTX_HIP(ctx, hipStreamSynchronize(stream));   // the scratch and its table go out of scope
+            PTX_HIP(ctx, hipStreamSynchronize(stream));   // the lengths are in place; `segs` is reused
             segs.clear();
         }
         // ---- walks
-        DevBuf<uint32_t> d_pk_first, d_pk_off;
-        DevBuf<uint8_t> d_pk_payload;
-        DevBuf<UnpackSpecies> d_ut;
-        std::vector<UnpackSpecies> ut;
         uint64_t nb_tot = 0, noff_tot = 0, pay_units = 0;
         if (n_packed) {
             std::vector<UploadSeg> s_first, s_off, s_pay;
@@ -252,7 +256,7 @@ int db_upload_arrays(Ctx *ctx, pantax_hip_db *db, const GraphPart *parts, const 
         }
         if (n_packed) {   // (behind the plain pipeline: the holes' garbage is overwritten)
             PTX_TRY(walks_unpack_launch(ctx, d_ut.p, (uint32_t)ut.size(), (uint32_t)nb_tot, d_pk_first.p, d_pk_off.p, d_pk_payload.p, db->d_path_nodes.p, stream_arg));
-            PTX_HIP(ctx, hipStreamSynchronize(stream));   // the scratch goes out of scope
+            PTX_HIP(ctx, hipStreamSynchronize(stream));
         }
     }
     PTX_HIP(ctx, hipStreamSynchronize(stream));

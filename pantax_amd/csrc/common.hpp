@@ -13,6 +13,7 @@
 #include <vector>
 #include "../../include/pantax_hip.h"
 #include "cov_state.hpp"
+#include "upload_host.hpp"
 
 #ifndef TRIO_LH_PACK
 #define TRIO_LH_PACK 0   // 1: length and owner of a row in ONE 8-byte record (measurement builds)
@@ -60,7 +61,7 @@ hipError_t dev_cache_alloc(void **p, size_t bytes, size_t *cap_out, int *dev_out
 void dev_cache_free(void *p, size_t cap, int dev);   // dev: the device the block was allocated on (the caller's current device may differ)
 void dev_cache_trim();   // really free everything cached for the current device (pantax_hip_destroy)
 void dev_cache_register_stream(int dev, hipStream_t st, bool add);   // a ctx's compute streams: what a released block may still be in use on
-struct DevCacheIdleFrees { DevCacheIdleFrees(); ~DevCacheIdleFrees(); };   // scope: blocks released by this thread are idle already (see ctx.cpp)
+struct DevCacheIdleFrees { DevCacheIdleFrees(); ~DevCacheIdleFrees(); };   // scope: blocks released by this thread are idle already (see dev_cache.cpp)
 
 template <class T>
 struct DevBuf {
@@ -193,15 +194,6 @@ struct CtxConfig {
 };
 int ctx_set_option(CtxConfig &cfg, const char *name, const char *value);   // 0, or PANTAX_HIP_E_INVALID for an unknown name / unparsable value
 
-// The host side of the big uploads (GAF text, graph arrays) is a crew of threads that pread into a pinned ring while the DMA engine empties
-// it: both want the memory of the GPU's own NUMA node -- a filler on the far socket writes the ring across the inter-socket link, and the DMA
-// reads it back the same way (round 4: 0.365 .. 0.49 s for the same 15-GB load from box to box).  pantax_hip_init looks the node up
-// (/sys/bus/pci/devices/<gpu>/numa_node); the crew's threads are bound to its CPUs and the ring is allocated from it (option numa_bind=0: off).
-struct NumaInfo {
-    int node = -1;                   // -1: unknown / a single node: nothing is bound
-    std::vector<int> cpus;           // the node's CPUs
-};
-
 struct Ctx {
     std::recursive_mutex mu;         // one call at a time per ctx (PTX_ENTER)
     CtxConfig cfg;
@@ -229,7 +221,8 @@ struct Ctx {
     DevBuf<uint32_t> d_scan_ws2; // the same for scans enqueued on the side stream (they may run beside scans of the main stream)
     uint32_t scan_epoch2 = 0;
     PinBuf pin_down;             // staging of small downloads (valid until the next download through it)
-    PinBuf pin_text;             // ring of pinned chunks of the large uploads (upload_staged: GAF text, graph arrays)
+    PinBuf pin_text;             // ring of pinned chunks of the large uploads (upload.cpp: GAF text, graph arrays); named by upload.cpp alone
+    RingGate ring_gate;          // ... which holds a RingLease on this for the duration of a pipeline: one upload at a time, a second is refused
     PinBuf pin_up;               // ring of small uploads, in two halves: a half is re-entered only after the copies issued from it
     size_t pin_up_off = 0;       // on its last lap have run (an event per stream, recorded when the ring leaves the half) -- steps enqueued
     hipEvent_t pin_up_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // back to back share it without a host wait in between
@@ -556,17 +549,6 @@ int upload(Ctx *ctx, DevBuf<T> &dst, const T *src, size_t n) {
     if (n) PTX_HIP(ctx, hipMemcpyAsync(dst.p, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     return 0;
 }
-// A stretch of a 32-bit device array as it lies on the host: in memory (`src`) or in a file (`file` = index into the paths the
-// upload is given, bytes from `file_off`); `narrow`: the source holds 64-bit little-endian integers (bincode's i64 lengths / usize
-// node ids, zip.rs:171-190) that become 32-bit ones on the way -- a value beyond 2^32 - 1 (or negative) fails the upload.
-struct UploadSeg {
-    const void *src = nullptr;
-    int32_t file = -1;
-    uint64_t file_off = 0;
-    uint64_t out_bytes = 0;   // bytes this stretch occupies on the device (a multiple of 4); the source holds twice as many when narrow
-    bool narrow = false;
-    bool hole = false;        // nothing is filled (the bytes travel as they lie in the ring): a stretch another pass writes on the device
-};
 // segments back to back -> d_dst, as ONE chunk pipeline through the pinned ring (a crew of host threads fills a chunk -- pread /
 // memcpy / narrowing -- while the chunks before it travel).  *bad_seg (optional) = first segment that held a value beyond 32 bits, or -1.
 int upload_segments(Ctx *ctx, void *d_dst, const UploadSeg *segs, size_t n_segs, const std::string *files, int64_t *bad_seg, hipStream_t stream = nullptr /* null: ctx->stream */);
@@ -605,13 +587,16 @@ int db_upload_parts(Ctx *ctx, uint32_t S, const int64_t *range_start, const int6
                     pantax_hip_db **out);
 // the same in three steps (round 6: the file seam loads the NEXT group of species on a thread of its own while this group's tables are built):
 // begin -- host tables, small uploads, the big arrays allocated (calling thread, ctx->stream); arrays -- node lengths and walks from their files into
-// HBM, unpacked where they come packed (any thread that has made the ctx's device current; `stream`: its copy stream, waited for before it returns;
-// touches neither ctx->stream nor the ctx's staging buffers); finish -- node tables, checks, tiles, visit table, node -> haplotypes (ctx->stream)
+// HBM, unpacked where they come packed; finish -- node tables, checks, tiles, visit table, node -> haplotypes (ctx->stream).
+// db_upload_arrays may run on a thread of its own (one that has made the ctx's device current) with a copy stream of its own (`stream`), which it
+// waits for before it returns, whichever way it returns; it does not touch ctx->stream.  It SHARES the ctx's staging ring with the owning thread:
+// the owning thread must not start a staged upload (upload_big, upload_file, upload_text_pieces, upload_segments) until the loader has been joined.
+// A violation is refused (PANTAX_HIP_E_STATE from whichever upload comes second: the ring is leased, upload_host.hpp), not raced.
 int db_upload_begin(Ctx *ctx, uint32_t S, const int64_t *range_start, const int64_t *range_end, const GraphPart *parts, pantax_hip_db **out);
 int db_upload_arrays(Ctx *ctx, pantax_hip_db *db, const GraphPart *parts, const std::string *files, hipStream_t stream);
 int db_upload_finish(Ctx *ctx, pantax_hip_db *db);
-// large pageable host buffers (mmapped text, graph arrays) -> HBM through two pinned chunks: a few threads copy the next
-// chunk into pinned memory while the previous one is on its way over PCIe (a plain copy from pageable memory is staged
+// large pageable host buffers (mmapped text, graph arrays) -> HBM through a ring of three pinned chunks: a crew of threads copies the
+// next two chunks into pinned memory while the previous one is on its way over PCIe (a plain copy from pageable memory is staged
 // by one runtime thread at ~10 GB/s).  Returns after the last chunk has arrived.
 int upload_big(Ctx *ctx, void *d_dst, const void *src, uint64_t bytes);
 // the same from an open file (pread straight into the pinned chunks: no page of the file is mapped or faulted in)
@@ -621,8 +606,6 @@ int upload_file(Ctx *ctx, void *d_dst, int fd, uint64_t file_off, uint64_t bytes
 // chunk of piece k has been enqueued (record an event there).  fd >= 0: pread from the file at file_base + offset, else from `text`.
 int upload_text_pieces(Ctx *ctx, size_t n_pieces, void *const *d_dst, const char *text, int fd, uint64_t file_base, const uint64_t *piece_off, const uint64_t *piece_end,
                        hipStream_t stream, const std::function<bool(size_t)> &before_piece, const std::function<int(size_t)> &after_piece);
-// fn(begin, end) over [0, n) split across up to n_threads host threads (the calling thread takes the first slice)
-void parallel_for(uint64_t n, int n_threads, const std::function<void(uint64_t, uint64_t)> &fn);
 // small host -> device copies go through the pinned ring (the source may be reused as soon as this returns)
 constexpr size_t PIN_UP_RING = 1u << 20, PIN_UP_MAX = 1u << 16;
 template <class T>

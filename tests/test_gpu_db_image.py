@@ -282,6 +282,24 @@ def test_offset_guard_host(eng, canon, tmp_path):
     _aftermath(eng, canon, tmp_path / "after")
 
 
+def test_good_load_behind_each_host_refusal(eng, tmp_path):
+    """test_offset_guard_host looks at the engine once, behind both of its refusals (every other refusal of this file is followed by _aftermath at
+    once).  Here the undamaged pair of the same two species is loaded directly behind EACH refused load, on the same engine: the staging ring is free
+    again (no lease is left behind by a refused call), and the arrays the device then holds are the codec's, byte for byte."""
+    db = _guard_db()
+    d = tmp_path / "good"
+    d.mkdir()
+    good = _write(db, d)
+    for k, off in enumerate(([0, 1, 2, 3, 3], [1, 1, 2, 3, 4])):
+        b = tmp_path / ("b%d" % k)
+        b.mkdir()
+        paths = _write(db, b, per_species=lambda i, g: dict(blk_off=off) if i == 0 else dict())
+        _refused(eng, E_IO, "block offsets do not span its payload", lambda: _load(eng, db, paths))
+        _load(eng, db, good)
+        for p, q in zip(good, _save(eng, db, tmp_path / ("out%d" % k))):
+            assert open(p, "rb").read() == open(q, "rb").read(), (k, p)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the file seam
 @pytest.fixture(scope="module")
 def world(tmp_path_factory, eng):
