@@ -114,7 +114,7 @@ int pantax_hip_bin_reads(pantax_hip_ctx *ctx, const pantax_hip_db *db, pantax_hi
  * with species != "U" (:312-319), the MAPQ filter when `filtered` (:239-245), absolute =
  * base_count / avg_len (:336), abundance = absolute / sum (:341).  avg_len[s] <= 0 = species missing
  * from species_genomes_stats.txt.  Outputs [n_species]; rows are in db order (callers sort by
- * abundance, :344).  Requires bin_reads on `reads`. */
+ * abundance, :344).  Requires bin_reads of `reads` against `db` (else PANTAX_HIP_E_STATE). */
 int pantax_hip_species_profile(pantax_hip_ctx *ctx, const pantax_hip_db *db, pantax_hip_reads *reads,
                                const int64_t *read_count, const int64_t *base_sum, const int64_t *less_multi,
                                const int64_t *uniq_count, const double *avg_len, int filtered,
@@ -132,8 +132,8 @@ int pantax_hip_trio_index(pantax_hip_ctx *ctx, pantax_hip_db *db, uint64_t *n_un
 int pantax_hip_trio_get(pantax_hip_ctx *ctx, const pantax_hip_db *db, uint32_t *abc_out, uint32_t *hap_out,
                         int64_t *len_out, uint64_t *hap_trio_off_out);
 
-/* ---- a8: get_node_abundances integer part (profile.rs:743-1026).  Requires bin_reads
- * (and trio_index if trio_bases_out != NULL).  species_active: [S] 0/1 or NULL = all
+/* ---- a8: get_node_abundances integer part (profile.rs:743-1026).  Requires bin_reads of `reads` against `db`
+ * (else PANTAX_HIP_E_STATE: the slot records of binned reads hold species indices and node bases of ONE db; and trio_index if trio_bases_out != NULL).  species_active: [S] 0/1 or NULL = all
  * (the species load_species_range keeps, profile.rs:553-656).  Outputs: [V], [V], [U].
  * n_abort_out counts reads on which the reference would abort (assert profile.rs:854 /
  * index panic :849); they contribute nothing. */

@@ -388,8 +388,8 @@ int pantax_hip_reads_upload(pantax_hip_ctx *ctx, const pantax_hip_packed_reads *
     PTX_TRY(upload(ctx, rd->d_pend, r->pend, r->n_reads));
     PTX_TRY(upload(ctx, rd->d_qlen, r->qlen, r->n_reads));
     PTX_TRY(upload(ctx, rd->d_mapq, r->mapq, r->n_reads));
-    rd->has_flags = r->flags != nullptr;
-    if (rd->has_flags) PTX_TRY(upload(ctx, rd->d_flags, r->flags, r->n_reads));
+    if (r->flags) PTX_TRY(upload(ctx, rd->d_flags, r->flags, r->n_reads));
+    rd->state.columns_replaced(r->flags != nullptr);
     uint32_t max_id = 0;
     for (uint64_t i = 0; i < r->n_steps; ++i) max_id = std::max(max_id, r->node_id[i]);
     PTX_TRY(build_step_read(ctx, rd.get(), max_id));
@@ -436,7 +436,8 @@ int pantax_hip_node_coverage(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_
                              uint64_t *n_abort_out) {
     if (!ctx || !db || !reads) return PANTAX_HIP_E_INVALID;
     PTX_ENTER(ctx);
-    if (!reads->binned) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: call pantax_hip_bin_reads on these reads first");
+    if (!reads->state.binned_against(db->uid))
+        return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: call pantax_hip_bin_reads on these reads against this db first (they are not binned, or binned against another db)");
     if (trio_bases_out && !db->trio.built()) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: trio_bases requested but pantax_hip_trio_index has not run");
     const uint8_t *d_active = nullptr;
     if (species_active) {

@@ -15,7 +15,8 @@ int pantax_hip_species_profile(pantax_hip_ctx *ctx, const pantax_hip_db *db, pan
                                int filtered, uint8_t *keep_out, double *absolute_out, double *abundance_out) {
     if (!ctx || !db || !reads || !read_count || !base_sum || !less_multi || !uniq_count || !avg_len || !keep_out || !absolute_out || !abundance_out)
         return PANTAX_HIP_E_INVALID;
-    if (!reads->binned) return fail(ctx, PANTAX_HIP_E_STATE, "species_profile: call pantax_hip_bin_reads first");
+    if (!reads->state.binned_against(db->uid))
+        return fail(ctx, PANTAX_HIP_E_STATE, "species_profile: call pantax_hip_bin_reads on these reads against this db first (they are not binned, or binned against another db)");
     PTX_ENTER(ctx);
     // profile.rs:312-319: distinct read_len among the first 1000 rows of the frame without "U" reads
     std::vector<uint32_t> head;

@@ -406,8 +406,7 @@ int route_reads(Run &run, Ingest &in, const Selection &sn, int *unpack_rc) {
         std::vector<int32_t> owner_all(in.S, -1);
         for (size_t i = 0; i < sn.sel.size(); ++i) owner_all[sn.sel[i]] = sn.owner[i];
         if (in.R) PTX_TRY(upload(run.ctx, in.reads.rd->d_flags, sn.flags.data(), in.R));
-        in.reads.rd->has_flags = in.R != 0;
-        in.reads.rd->g_flags_valid = false;
+        in.reads.rd->state.flags_replaced(in.R != 0);   // plain columns: the flags travel beside the species array, the binning stands (the rule: reads_state.hpp)
         PTX_TRY(route_pack(run.ctx, in.bin_db.db, in.reads.rd, owner_all.data(), W, rt));
         for (int j = 0; j <= W; ++j) send_off[j] = rt.word_off[j] * 4;
         return 0;

@@ -93,8 +93,8 @@ int step_enqueue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads
     for (int k = 0; k < 2; ++k) PTX_HIP(ctx, db->h_sp_out[k].reserve(sizeof(double) * S + S));
     PTX_HIP(ctx, hipMemcpyAsync(db->h_sp_out[slot].p, db->d_sp_out.p, sizeof(double) * S + S, hipMemcpyDeviceToHost, ctx->stream));
     mark();
-    PTX_TRY(strain_prezero(ctx, db));   // zero-fills of the strain step, while this stream would wait for the trio index anyway
-    struct PreZeroGuard { LadBatch &lb; ~PreZeroGuard() { lb.prezeroed = false; } } prezero_guard{db->lad};   // never outlives this call
+    bool strain_zeroed = false;
+    PTX_TRY(strain_prezero(ctx, db, &strain_zeroed));   // zero-fills of the strain step, while this stream would wait for the trio index anyway
     PTX_TRY(coverage_prepare(ctx, db, reads, true));   // arena zero-fill + walk sums of long reads: need the binning, not the trio index
     struct CovPrepGuard { Db *d; ~CovPrepGuard() { d->cov.prepare_dropped(); } } covprep_guard{db};   // (no-op once the coverage pass has begun)
     mark();
@@ -106,7 +106,7 @@ int step_enqueue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads
     // a9 .. a14
     pantax_hip_strain_config sc{cfg->unique_trio_nodes_fraction, cfg->unique_trio_nodes_mean_count_f, cfg->single_cov_ratio, cfg->min_depth,
                                 cfg->shift, cfg->sample_nodes, cfg->solver_semantics};
-    PTX_TRY(strain_enqueue(ctx, db, &sc, db->d_active.p, slot));
+    PTX_TRY(strain_enqueue(ctx, db, &sc, db->d_active.p, slot, strain_zeroed));
     mark();
     db->step_cfg[slot] = *cfg;
     db->step_enq ^= 1;

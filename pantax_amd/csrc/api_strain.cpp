@@ -52,12 +52,12 @@ struct ArenaLayout {
     }
 };
 
-int bind_arena(Ctx *ctx, Db *db, LadBatch &lb, const ArenaLayout &L) {
+int bind_arena(Ctx *ctx, Db *db, LadBatch &lb, const ArenaLayout &L, bool zeroed) {
     const uint32_t S = db->S;
     const size_t Hn = db->H ? db->H : 1;
     PTX_HIP(ctx, db->d_arena.alloc(L.total));
     uint8_t *b = db->d_arena.p;
-    if (!lb.prezeroed) PTX_HIP(ctx, hipMemsetAsync(b, 0, L.total, ctx->stream));   // unsolved species read back as x = 0, status 0, 0 pivots
+    if (!zeroed) PTX_HIP(ctx, hipMemsetAsync(b, 0, L.total, ctx->stream));   // unsolved species read back as x = 0, status 0, 0 pivots
     lb.d_amax.view(b + L.amax, S); lb.d_nzsum.view(b + L.nzsum, S); lb.d_obj.view(b + L.obj1, S); lb.d_obj2.view(b + L.obj2, S);
     lb.d_x.view(b + L.x1, Hn); lb.d_x2.view(b + L.x2, Hn);
     lb.d_ratio.view(b + L.ratio, Hn * 2);
@@ -103,21 +103,21 @@ namespace ptx {
 
 // The two zero-fills of the strain step (result arena, membership masks) issued ahead of time: in the resident step the
 // main stream idles before the coverage kernel while the trio index is built on the side stream, so they cost nothing
-// there instead of ~10 us between coverage and the first strain kernel.  strain_enqueue consumes the flag.
-int strain_prezero(Ctx *ctx, Db *db) {
+// there instead of ~10 us between coverage and the first strain kernel.  *zeroed goes to strain_enqueue of the same call, and nowhere else.
+int strain_prezero(Ctx *ctx, Db *db, bool *zeroed) {
     LadBatch &lb = db->lad;
     const ArenaLayout L(db->S, db->H);
-    lb.prezeroed = false;
-    PTX_TRY(bind_arena(ctx, db, lb, L));
+    *zeroed = false;
+    PTX_TRY(bind_arena(ctx, db, lb, L, false));
     PTX_HIP(ctx, lb.d_mask.alloc(db->V));
     if (!use_node_haps(ctx, db)) PTX_TRY(zero_fill(ctx, lb.d_mask.p, db->V * sizeof(uint64_t)));   // (the by-node mask kernel writes every word)
-    lb.prezeroed = true;
+    *zeroed = true;
     return 0;
 }
 
 // Enqueues the whole strain step and the download of its result arena; nothing waits for the host.
 // d_active: device [S] or null.
-int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const uint8_t *d_active, int slot) {
+int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const uint8_t *d_active, int slot, bool zeroed) {
     if (!db->cov.strain_may_run()) return fail(ctx, PANTAX_HIP_E_STATE, "strain_profile: call pantax_hip_node_coverage first");
     if (!db->trio.built()) return fail(ctx, PANTAX_HIP_E_STATE, "strain_profile: call pantax_hip_trio_index first");
     if (cfg->sample_nodes < 0) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_profile: sample_nodes %d", cfg->sample_nodes);
@@ -135,7 +135,7 @@ int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const 
             for (int i = 0; i < *n; ++i) std::fprintf(stderr, " %.2f", m[i]);
             std::fprintf(stderr, "\n");
         } } } slow_report{marks, &n_marks, ctx->cfg.trace};
-    PTX_TRY(bind_arena(ctx, db, lb, L));
+    PTX_TRY(bind_arena(ctx, db, lb, L, zeroed));
     // the error word of the index build this step reads (a REBUILD does not wait for the host: its kernels' complaints -- a visit group out of order,
     // group offsets that are not this table's -- come back with the step's results); taken here, before the next step's rebuild may clear it
     if (db->trio_scratch.d_tot.p)
@@ -156,10 +156,9 @@ int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const 
     mark();
     // ONE pass over the nodes where the step is eligible (node_rows_kernel, inside lad_prepare's row sort): the first filter reads the unique-trio statistics
     // alone, so the LP columns are known before any node is looked at, and the statistics below are first needed by lad_pair_launch
-    lb.node_pass_fused = node_pass_fused_eligible(ctx, db, cfg, readers_clean);
-    lb.fused_min_depth = (double)cfg->min_depth;
-    lb.fused_active = ctx->cfg.no_absent_skip ? nullptr : skip_absent;
-    if (lb.node_pass_fused) lb.S = S;
+    const bool fused = node_pass_fused_eligible(ctx, db, cfg, readers_clean);
+    const FusedNodePass fused_pass{(double)cfg->min_depth, ctx->cfg.no_absent_skip ? nullptr : skip_absent};
+    if (fused) lb.S = S;
     else
     PTX_TRY(node_stats_launch(ctx, db, &lb, cfg->min_depth, skip_absent, readers_clean));                              // abundances + per-species stats
     if (readers_clean) { db->cov.readers_cleaned(); clean_guard.armed = false; }   // (the arena no longer holds a coverage result)
@@ -179,8 +178,10 @@ int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const 
     mark();
     int pmax_bound = 1;                                                                     // mask bits of a row key: min(#haps, 64) (wide species: a 64-bit hash)
     for (uint32_t s = 0; s < S; ++s) pmax_bound = std::max<int>(pmax_bound, (int)std::min<uint64_t>(db->h_hap_off[s + 1] - db->h_hap_off[s], LAD_MAXP));
+    LadRows rows;
     {
-        const int rc_prep = lad_prepare(ctx, db, &lb, true, pmax_bound);                   // a10 + row grouping
+        const LadRequest rq{/*cand_on_device=*/true, pmax_bound, zeroed, fused ? &fused_pass : nullptr};
+        const int rc_prep = lad_prepare(ctx, db, &lb, rq, &rows);                           // a10 + row grouping
         if (rc_prep != 0) {   // failed before it recorded the event: no stale event may order the next step's rebuild (it falls back to ev_seq)
             db->trio.free_event_void();
             return rc_prep;
@@ -189,11 +190,10 @@ int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const 
     if (db->trio.free_event_pending()) { PTX_HIP(ctx, hipEventRecord(db->ev_trio_free, ctx->stream)); db->trio.free_event_recorded(); }
     mark();
     if (clean == CovClean::side_fill) PTX_TRY(coverage_arena_clean_async(ctx, db));   // beside the LPs: one workgroup per species, most of the memory system idle
-    PTX_TRY(lad_pair_launch(ctx, db, &lb, pmax_bound, fc));                                 // LP 1 -> a13 decision -> LP 2, objectives
+    PTX_TRY(lad_pair_launch(ctx, db, &lb, rows, pmax_bound, fc));                           // LP 1 -> a13 decision -> LP 2, objectives
     mark();
     PTX_TRY(fetch_arena_enqueue(ctx, db, L, slot));
     mark();
-    lb.prezeroed = false;
     return 0;
 }
 
@@ -383,7 +383,7 @@ int pantax_hip_pao_solve_batch(pantax_hip_ctx *ctx, const pantax_hip_species_bat
     LadBatch &lb = db->lad;
     lb.S = S;
     const ArenaLayout L(S, H);
-    PTX_TRY(bind_arena(ctx, db, lb, L));
+    PTX_TRY(bind_arena(ctx, db, lb, L, false));
     std::vector<uint32_t> cov32(V ? V : 1, 0);
     if (in->node_base_cov) for (uint64_t v = 0; v < V; ++v) cov32[v] = (uint32_t)in->node_base_cov[v];
     PTX_TRY(upload(ctx, db->d_cov, cov32.data(), V));
@@ -411,9 +411,10 @@ int pantax_hip_pao_solve_batch(pantax_hip_ctx *ctx, const pantax_hip_species_bat
     }
     PTX_TRY(upload(ctx, lb.d_amax, amax.data(), S));
     PTX_TRY(upload(ctx, lb.d_nvalid, nvalid.data(), S));
-    PTX_TRY(lad_prepare(ctx, db, &lb, false, pmax));
+    LadRows rows;
+    PTX_TRY(lad_prepare(ctx, db, &lb, LadRequest{/*cand_on_device=*/false, pmax, /*zeroed=*/false, /*fused=*/nullptr}, &rows));
     PTX_TRY(upload(ctx, lb.d_fixed2, fixed.data(), fixed.size()));
-    PTX_TRY(lad_solve_launch(ctx, db, &lb, pmax, nullptr, lb.d_fixed2.p, lb.d_x.p, lb.d_obj.p, lb.d_status.p, lb.d_iters.p));
+    PTX_TRY(lad_solve_launch(ctx, db, &lb, rows, pmax, nullptr, lb.d_fixed2.p, lb.d_x.p, lb.d_obj.p, lb.d_status.p, lb.d_iters.p));
     std::vector<double> x(H ? H : 1), obj(S);
     std::vector<unsigned long long> ratio((H ? H : 1) * 2);
     std::vector<int32_t> st(S), it(S);
@@ -464,7 +465,7 @@ static int check_read_strain_set(pantax_hip_ctx *ctx, const pantax_hip_db *db, c
                                  const char *what, std::vector<uint32_t> &hap, std::vector<double> &w, std::vector<uint64_t> &ord_all) {
     const uint32_t S = db->S;
     if (cand->n_species != S) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: the candidate set has %u species, the db %u", what, cand->n_species, S);
-    if (!reads->binned || reads->binned_db != db->uid || !reads->grouped)
+    if (!reads->state.binned_against(db->uid) || !reads->state.grouped())
         return fail(ctx, PANTAX_HIP_E_STATE, "%s: call pantax_hip_bin_reads on these reads against this db first", what);
     if (db->d_path_nodes.p == nullptr || db->h_path_off.size() != db->H + 1)
         return fail(ctx, PANTAX_HIP_E_STATE, "%s: the db was uploaded without graphs (ranges only)", what);

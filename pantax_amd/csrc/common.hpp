@@ -13,6 +13,7 @@
 #include <vector>
 #include "../../include/pantax_hip.h"
 #include "cov_state.hpp"
+#include "reads_state.hpp"
 #include "upload_host.hpp"
 
 #ifndef TRIO_LH_PACK
@@ -271,8 +272,7 @@ constexpr int LAD_WIDEP = 64 * LAD_WIDE_NW;   // candidate paths up to which a s
 struct LadBatch {
     uint32_t S = 0;
     // per species (host mirrors + device)
-    bool prezeroed = false;             // the result arena and d_mask were zeroed ahead of strain_enqueue (strain_prezero)
-    std::vector<int32_t> h_p;           // [S] number of candidates (0 = not solved)
+    std::vector<int32_t> h_p;          // [S] number of candidates (0 = not solved)
     std::vector<uint32_t> h_cand;       // [H] at hap_off[s] + k: candidate k -> hap index within species
     DevBuf<int32_t> d_p;
     DevBuf<int32_t> d_hap_bit;          // [H] bit index of hap in its species' candidate list, -1 if none
@@ -281,16 +281,12 @@ struct LadBatch {
     DevBuf<uint64_t> d_mask;            // [V] candidate membership mask per node (the 0/1 coeff matrix, row-wise)
     DevBuf<double> d_ab;                // [V] node_abundance = bases / len  (profile.rs:980-990)
     DevBuf<double> d_c0;                // [S] sum of ab over the nodes with ab > 0 and no column (the row sort straight from the nodes sums it): the objective's part without rows
-    bool rows_c0_valid = false;         // ... is there for the rows lad_prepare has just sorted
-    bool masks_in_sort = false;         // the last lad_prepare formed the masks inside the row sort: d_mask holds nothing
-    bool node_pass_fused = false;       // this step's lad_prepare also forms abundances, covered bases and the node statistics inside the row sort (node_rows_kernel):
-    double fused_min_depth = 0.0;       //   d_ab and the db's d_cov hold nothing; strain_enqueue decides (node_pass_fused_eligible, stage_lp_rows.hip: the row route) and hands over min_depth and the
-    const uint8_t *fused_active = nullptr;   // species flags the coverage pass skipped by
+                                        //     (whether it is there for the rows just sorted, and whether d_mask / d_ab hold anything: LadRows, lad.hpp -- lad_prepare's result, not kept here)
     DevBuf<unsigned long long> d_ratio; // [H*2] at 2 * (hap_off[s] + k): sum cov, sum len of candidate k (exact integers)
     // species that can have more than 64 candidates (more than 64 haplotypes): LAD_WIDE_NW mask words per node in a side
     // array, d_mask then holds a 64-bit hash of those words (rows are grouped by it; the words of every pattern are
     // collected after the grouping, and a hash collision is detected there, not assumed away)
-    const void *wide_for = nullptr;     // the Db the wide tables below were laid out for
+    bool wide_laid_out = false;         // the wide tables below are laid out (once: a batch serves the one db that owns it)
     uint32_t n_wide = 0;                // species with more than LAD_MAXP haplotypes
     uint32_t n_huge = 0;                // ... of them with more than LAD_WIDEP: mask words, W / G and the column state sized at run time
     uint64_t Vw = 0;                    // their four-word mask groups (nodes x words per node / 4)
@@ -353,7 +349,7 @@ struct TrioScratch {
 // ---- resident DB -----------------------------------------------------------------------------
 inline uint64_t next_db_uid() { static std::atomic<uint64_t> n{1}; return n.fetch_add(1); }
 struct Db {
-    const uint64_t uid = next_db_uid();   // never reused: what resident reads remember a db by (Reads::long_sums_db)
+    const uint64_t uid = next_db_uid();   // never reused: what resident reads remember a db by (ReadsState::binned_against)
     uint32_t S = 0;
     uint64_t V = 0, H = 0, P = 0, L = 0;
     std::vector<int64_t> h_range_start, h_range_end;
@@ -491,7 +487,6 @@ struct Reads {
     DevBuf<uint32_t> d_step_off, d_node_id, d_pstart, d_pend, d_qlen;
     DevBuf<uint8_t> d_mapq, d_flags;
     DevBuf<uint64_t> d_id_hash;      // 64-bit hash of every read id (device tokenizer; the duplicate-id rule, profile.rs:361-437): fetched by the host only when two reads share one
-    bool has_flags = false;
     DevBuf<int32_t> d_species;
     std::vector<int32_t> h_pre_species;   // first rows of species/qlen, fetched with the counters (equal-length test)
     std::vector<uint32_t> h_pre_qlen;
@@ -510,18 +505,13 @@ struct Reads {
     DevBuf<uint2> d_g_qm;            // [R'] {read length, MAPQ} in slot order (the binning pass runs over the slots)
     DevBuf<uint2> d_g_mm;            // [R'] {smallest node id of the walk, largest} in slot order: with d_g_qm all the binning pass needs of a read (bin_mm_kernel); they depend
                                      //      on the reads alone and are filed by the fill kernels of the upload, which hold every step of every walk anyway
-    DevBuf<uint8_t> d_g_flag;        // [R'] drop flags in slot order, refreshed when the flags changed (g_flags_valid)
+    DevBuf<uint8_t> d_g_flag;        // [R'] drop flags in slot order, refreshed when the flags changed (ReadsState::slot_flags_current)
     uint32_t n_slots = 0;            // reads that own a slot (non-empty walk)
     DevBuf<uint2> d_g_items;         // [n_items] work items of the short-read coverage kernel: groups [x, y) whose reads start inside one block of 2048 node ids
     uint32_t n_items = 0;
     int item_blk_shift = 0;          // log2 of the node-block size the items were cut at (0: plain cuts of the stream)
-    bool g_flags_valid = false;
-    bool species_valid = false;      // d_species (file order) reflects the last binning pass; species_ensure() gathers it from the slots
-    bool binned = false;
-    uint64_t binned_db = 0;          // Db::uid of the db the last binning pass ran against (its species indices are in the slot records)
-    bool grouped = true;             // false: columns only (a slice that will be routed away, stage_route.hip; the file seam until its graphs travel): no locus-grouped copy, no coverage pass
+    ReadsState state;                // flags, locus-grouped copy, binning, species array, walk sums: what of them holds (reads_state.hpp; DESIGN.md, "Lifecycle of resident reads")
     uint64_t layout_id = 0;          // a new number for every locus-grouped copy built (build_step_read)
-    uint64_t long_sums_db = 0;       // Db::uid of the db whose binning pass filled d_long_sum / d_long_len0 (0: nobody: walk_sum_kernel does it)
     std::vector<uint32_t> h_item_block;   // node block (first node id >> item_blk_shift) of every work item of the short-read coverage kernel, ascending (host)
     uint32_t max_node_id = 0;        // largest node id of the walks (the device tokenizer notes it: what a later reads_group() sizes its buckets by)
 };

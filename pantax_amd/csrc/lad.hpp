@@ -38,24 +38,40 @@ LadShape lad_shape(const std::string &option, uint32_t n_workgroups, int n_cu, i
 const char *lad_shape_name(LadShape s);
 // a11: species with more valid rows than sample_nodes keep the rows rand 0.9.2's choose_multiple(seed 42) would keep
 int row_sample_apply(Ctx *ctx, const Db *db, LadBatch *lb, int64_t sample_nodes);
-// a10: masks, ratios; then LP rows sorted and grouped into patterns
-int lad_prepare(Ctx *ctx, Db *db, LadBatch *lb, bool cand_on_device, int pmax_bound);
+// a10: masks, ratios; then LP rows sorted and grouped into patterns.  What the caller has decided goes in as LadRequest, what the solver and the objective
+// have to know about the rows comes back as LadRows -- nothing of either is kept in the LadBatch.
+struct FusedNodePass { double min_depth; const uint8_t *active; };   // active: the species flags the coverage pass skipped by (device [S] or null)
+struct LadRequest {
+    bool cand_on_device;         // lb->d_hap_bit / d_p were written by first_filter_kernel; else they are uploaded from lb->h_p / h_cand (solver seam)
+    int pmax_bound;              // upper bound of the candidates per species
+    bool zeroed;                 // the result arena and d_mask were zeroed ahead of the step (strain_prezero)
+    const FusedNodePass *fused;  // the row sort also forms abundances, covered bases and node statistics (node_rows_kernel): d_ab and the db's d_cov hold nothing.
+                                 // strain_enqueue decides (node_pass_fused_eligible); null: the two-kernel path has run
+};
+struct LadRows {
+    bool c0_valid;       // lb->d_c0 (the objective's part without rows) is there for the rows just sorted
+    bool masks_in_sort;  // the masks were formed inside the row sort: lb->d_mask holds nothing
+    bool fused;          // ... and so were the abundances: lb->d_ab holds nothing
+};
+int lad_prepare(Ctx *ctx, Db *db, LadBatch *lb, const LadRequest &rq, LadRows *rows);
 // a12: one workgroup per species (those with d_p[s] > 0 and need[s], when given); variables with fixed[s*64+k]
 // are pinned to 0.  Writes x, obj, status, iters for the solved species.  Nothing is read back.
-int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const uint8_t *d_need, const uint8_t *d_fixed, double *d_x,
+int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, const LadRows &rows, int pmax_bound, const uint8_t *d_need, const uint8_t *d_fixed, double *d_x,
                      double *d_obj, int32_t *d_status, int32_t *d_iters);
 // the strain step's LP1 -> second filter -> LP2 (+ both objectives) as two launches
 struct FilterCfg;
-int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const FilterCfg &fc);
+int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, const LadRows &rows, int pmax_bound, const FilterCfg &fc);
 // both objectives of the solved species (x2 / need2 null: one solution), from the sorted rows or from the nodes
-int objective_launch(Ctx *ctx, const Db *db, LadBatch *lb, const uint8_t *d_need2, const double *d_x1, const double *d_x2, double *d_obj1, double *d_obj2);
+int objective_launch(Ctx *ctx, const Db *db, LadBatch *lb, const LadRows &rows, const uint8_t *d_need2, const double *d_x1, const double *d_x2, double *d_obj1,
+                     double *d_obj2);
 // a9 / a13 decisions on the device (the host redoes only the reporting arithmetic at the end of the step)
 struct FilterCfg { double fr, fc, sr; int shift; };
 int first_filter_launch(Ctx *ctx, const Db *db, LadBatch *lb, const uint8_t *d_active, const FilterCfg &fc);
 
 // the strain step in two halves (api_strain.cpp): everything enqueued / the one wait + host reporting
-int strain_prezero(Ctx *ctx, Db *db);   // optional, ahead of strain_enqueue: its two zero-fills, issued where the stream has slack
-int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const uint8_t *d_active, int slot);   // slot: which pinned result buffer / event (0 or 1)
+int strain_prezero(Ctx *ctx, Db *db, bool *zeroed);   // optional, ahead of strain_enqueue: its two zero-fills, issued where the stream has slack; the caller hands *zeroed on
+// slot: which pinned result buffer / event (0 or 1); zeroed: strain_prezero has run in this call, behind everything that wrote the arena and the masks
+int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const uint8_t *d_active, int slot, bool zeroed = false);
 int strain_finish(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const uint8_t *species_active, const double *species_coverage,
                   pantax_hip_hap_metrics *met, pantax_hip_solve_info *info_out, void (*after_wait)(void *), void *after_wait_arg, int slot);
 

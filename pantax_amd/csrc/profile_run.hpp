@@ -36,7 +36,7 @@ struct Ingest {
     DbHolder bin_db;                   // ranges-only db of ALL species
     uint64_t R = 0, text_begin = 0;
     std::vector<int32_t> sp_idx;       // species of every read (file order), with the host columns of hr: fetched once, on request (host_cols)
-    bool have_cols = false, reads_grouped = false;   // reads_grouped: the locus-grouped copy of the resident reads exists (built once, beside the first graph load)
+    bool have_cols = false;
     std::vector<int64_t> rc, bs, lm, uq, rs, re;   // the four counters per species (merged over the ranks when sharded); range starts / ends
     std::vector<uint32_t> head;        // read lengths of the first (up to 1000) binned rows of the file
     uint64_t read_base = 0, R_all = 0; // this rank's first read in file order; reads of the whole file

@@ -161,7 +161,7 @@ int shard_pass(Run &run, Ingest &in, const Selection &sn, bool use_images, Shard
     bool flags_set = false;
     std::unique_ptr<Loader> cur(new Loader(run.ctx)), next;
     PTX_TRY(start_load(run.ctx, g_rs.data(), g_re.data(), files.data(), groups[0], piped, *cur));
-    if (!run.p.sharded && !in.reads_grouped) { PTX_TRY(reads_group(run.ctx, in.reads.rd)); in.reads_grouped = true; run.lap("locus-grouped copy of the reads"); }   // (sharded: reads_from_routed grouped what arrived)
+    if (!in.reads.rd->state.grouped()) { PTX_TRY(reads_group(run.ctx, in.reads.rd)); run.lap("locus-grouped copy of the reads"); }   // built once, beside the first graph load (sharded: reads_from_routed grouped what arrived)
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         const uint32_t k0 = groups[gi].k0, k1 = groups[gi].k1, Sg = k1 - k0;
         cur->join();

@@ -566,6 +566,12 @@ __global__ void __launch_bounds__(256) bin_reduce_kernel(int n, const unsigned l
 size_t bin_counter_words(uint32_t S) { return (size_t)(BIN_REPL + 1) * 4 * S + BIN_PREFIX; }
 size_t bin_result_words(uint32_t S) { return (size_t)4 * S + BIN_PREFIX; }
 
+// the instance of a binning kernel for (ranges sorted and disjoint) x (per-species tables in LDS); the four share one signature
+template <class K>
+static K bin_instance(bool sorted, bool lds, K sorted_lds, K sorted_global, K any_lds, K any_global) {
+    return sorted ? (lds ? sorted_lds : sorted_global) : (lds ? any_lds : any_global);
+}
+
 // d_counters: bin_counter_words(S) u64 = [4*S sums][prefix block][BIN_REPL replicas of 4*S]
 int bin_reads_launch(Ctx *ctx, const Db *db, Reads *rd, unsigned long long *d_counters) {
     int S = (int)db->S;
@@ -573,90 +579,68 @@ int bin_reads_launch(Ctx *ctx, const Db *db, Reads *rd, unsigned long long *d_co
     const std::string &route = ctx->cfg.bin_route;
     if (!route.empty() && route != "minmax" && route != "walk") return fail(ctx, PANTAX_HIP_E_INVALID, "bin_reads: option bin_route is \"minmax\" or \"walk\", not \"%s\"", route.c_str());
     const bool walk = route == "walk";
-    rd->species_valid = false;
-    rd->binned_db = db->uid;
-    if (rd->R == 0) { rd->binned = true; return 0; }
+    const bool grouped = rd->state.grouped();
+    rd->state.bin_begun();   // until bin_finished below nothing is claimed: a pass that fails part-way leaves reads that are not binned
+    if (rd->R == 0) { rd->state.bin_finished(db->uid, false, false); return 0; }
     unsigned long long *d_final = d_counters;
     d_counters = d_counters + bin_result_words(S);   // replicas
-    const bool lds = S <= BIN_LDS_SPECIES;
-    const size_t dyn = (size_t)S * (rd->grouped ? 40 : 32);   // LDS tables per species: 8 + 12 (counters) + 12 (ranges) + 8 ({first id, node base}; slot order only)
-    if (rd->grouped) {
+    const bool sorted = db->ranges_sorted_disjoint, lds = S <= BIN_LDS_SPECIES;
+    const size_t dyn = lds ? (size_t)S * (grouped ? 40 : 32) : 0;   // LDS tables per species: 8 + 12 (counters) + 12 (ranges) + 8 ({first id, node base}; slot order only)
+    bool sums = false;
+    if (grouped) {
         // resident reads: slot order (coalesced slot records); drop flags reach the slots once per change
         const uint8_t *g_flag = nullptr;
-        if (rd->has_flags) {
-            if (!rd->g_flags_valid) {
+        if (rd->state.has_flags()) {
+            if (!rd->state.slot_flags_current()) {
                 PTX_HIP(ctx, rd->d_g_flag.alloc(rd->R));
                 hipLaunchKernelGGL(flags_to_slots_kernel, dim3(grid_for(rd->R, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, rd->R, rd->d_flags.p,
                                    rd->d_slot_of.p, rd->d_g_flag.p);
-                rd->g_flags_valid = true;
+                rd->state.slot_flags_filed();
             }
             g_flag = rd->d_g_flag.p;
         }
         // (option walk_sum_in_bin: walk sums of long walks on the way -- a db with graphs, reads that hold walks of more than 64 steps)
-        const bool sums = rd->n_long && db->d_node_len.p && db->d_sp_first_id.p && rd->d_long_sum.p && rd->d_long_len0.p && ctx->cfg.walk_sum_in_bin;
-        rd->long_sums_db = sums ? db->uid : 0;
+        sums = rd->n_long && db->d_node_len.p && db->d_sp_first_id.p && rd->d_long_sum.p && rd->d_long_len0.p && ctx->cfg.walk_sum_in_bin;
         const int grid = grid_for(rd->n_slots, BIN_BLOCK, ctx->n_cu * 8);
         // {min id, max id} of every walk were filed at upload: bin_mm_kernel; the pass that reads the walks stays for the walk sums and for bin_route=walk
         if (rd->n_slots && !walk && !sums) {
             KTimer t(ctx, "bin_mm_kernel");
-#define BIN_ARGS rd->n_slots, rd->d_g_mm.p, rd->d_g_qm.p, g_flag, db->d_rng_start.p, db->d_rng_end.p, db->d_rng_idx.p, S, rd->d_g_slot_rec.p, db->d_sp_first_id.p, \
-                 db->d_node_base.p, d_counters
-            if (db->ranges_sorted_disjoint) {
-                if (lds) hipLaunchKernelGGL((bin_mm_kernel<true, true>), dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, BIN_ARGS);
-                else hipLaunchKernelGGL((bin_mm_kernel<true, false>), dim3(grid), dim3(BIN_BLOCK), 0, ctx->stream, BIN_ARGS);
-            } else {
-                if (lds) hipLaunchKernelGGL((bin_mm_kernel<false, true>), dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, BIN_ARGS);
-                else hipLaunchKernelGGL((bin_mm_kernel<false, false>), dim3(grid), dim3(BIN_BLOCK), 0, ctx->stream, BIN_ARGS);
-            }
-#undef BIN_ARGS
+            hipLaunchKernelGGL(bin_instance(sorted, lds, bin_mm_kernel<true, true>, bin_mm_kernel<true, false>, bin_mm_kernel<false, true>, bin_mm_kernel<false, false>),
+                               dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, rd->n_slots, rd->d_g_mm.p, rd->d_g_qm.p, g_flag, db->d_rng_start.p, db->d_rng_end.p,
+                               db->d_rng_idx.p, S, rd->d_g_slot_rec.p, db->d_sp_first_id.p, db->d_node_base.p, d_counters);
         } else if (rd->n_slots) {
             KTimer t(ctx, "bin_slots_kernel");
-#define BIN_ARGS rd->n_slots, rd->d_g_read_rec.p, rd->d_g_node_id.p, rd->d_g_qm.p, g_flag, db->d_rng_start.p, db->d_rng_end.p, db->d_rng_idx.p, S, \
-                 rd->d_g_slot_rec.p, db->d_sp_first_id.p, db->d_node_base.p, d_counters, sums ? (const uint32_t *)db->d_node_len.p : (const uint32_t *)nullptr, \
-                 rd->d_long_sum.p, rd->d_long_len0.p
-            if (db->ranges_sorted_disjoint) {
-                if (lds) hipLaunchKernelGGL((bin_slots_kernel<true, true>), dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, BIN_ARGS);
-                else hipLaunchKernelGGL((bin_slots_kernel<true, false>), dim3(grid), dim3(BIN_BLOCK), 0, ctx->stream, BIN_ARGS);
-            } else {
-                if (lds) hipLaunchKernelGGL((bin_slots_kernel<false, true>), dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, BIN_ARGS);
-                else hipLaunchKernelGGL((bin_slots_kernel<false, false>), dim3(grid), dim3(BIN_BLOCK), 0, ctx->stream, BIN_ARGS);
-            }
-#undef BIN_ARGS
+            hipLaunchKernelGGL(bin_instance(sorted, lds, bin_slots_kernel<true, true>, bin_slots_kernel<true, false>, bin_slots_kernel<false, true>, bin_slots_kernel<false, false>),
+                               dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, rd->n_slots, rd->d_g_read_rec.p, rd->d_g_node_id.p, rd->d_g_qm.p, g_flag, db->d_rng_start.p,
+                               db->d_rng_end.p, db->d_rng_idx.p, S, rd->d_g_slot_rec.p, db->d_sp_first_id.p, db->d_node_base.p, d_counters,
+                               sums ? (const uint32_t *)db->d_node_len.p : (const uint32_t *)nullptr, rd->d_long_sum.p, rd->d_long_len0.p);
         }
     } else {
         // a slice kept as plain columns (to be routed away): read order, the species array is the product
         PTX_HIP(ctx, rd->d_species.alloc(rd->R));
         int grid = grid_for(rd->R, BIN_BLOCK, ctx->n_cu * 8);
         KTimer t(ctx, "bin_reads_kernel");
-#define BIN_ARGS rd->R, rd->d_step_off.p, rd->d_node_id.p, rd->d_qlen.p, rd->d_mapq.p, db->d_rng_start.p, db->d_rng_end.p, \
-                 db->d_rng_idx.p, S, rd->d_species.p, d_counters
-        if (db->ranges_sorted_disjoint) {
-            if (lds) hipLaunchKernelGGL((bin_reads_lds_kernel<true>), dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, BIN_ARGS);
-            else hipLaunchKernelGGL((bin_reads_kernel<true, false>), dim3(grid), dim3(BIN_BLOCK), 0, ctx->stream, BIN_ARGS);
-        } else {
-            if (lds) hipLaunchKernelGGL((bin_reads_lds_kernel<false>), dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, BIN_ARGS);
-            else hipLaunchKernelGGL((bin_reads_kernel<false, false>), dim3(grid), dim3(BIN_BLOCK), 0, ctx->stream, BIN_ARGS);
-        }
-#undef BIN_ARGS
-        rd->species_valid = true;
+        hipLaunchKernelGGL(bin_instance(sorted, lds, bin_reads_lds_kernel<true>, bin_reads_kernel<true, false>, bin_reads_lds_kernel<false>, bin_reads_kernel<false, false>),
+                           dim3(grid), dim3(BIN_BLOCK), dyn, ctx->stream, rd->R, rd->d_step_off.p, rd->d_node_id.p, rd->d_qlen.p, rd->d_mapq.p, db->d_rng_start.p,
+                           db->d_rng_end.p, db->d_rng_idx.p, S, rd->d_species.p, d_counters);
     }
     const uint32_t npre = (uint32_t)std::min<uint64_t>(rd->R, BIN_PREFIX);
     hipLaunchKernelGGL(bin_reduce_kernel, dim3((std::max<uint32_t>(4 * S, npre) + 255) / 256), dim3(256), 0, ctx->stream, 4 * S, d_counters, d_final,
-                       npre, rd->grouped ? nullptr : rd->d_species.p, rd->d_qlen.p, rd->d_slot_of.p, rd->d_g_slot_rec.p);
+                       npre, grouped ? nullptr : rd->d_species.p, rd->d_qlen.p, rd->d_slot_of.p, rd->d_g_slot_rec.p);
     PTX_HIP(ctx, hipGetLastError());
-    rd->binned = true;
+    rd->state.bin_finished(db->uid, /*species_in_file_order=*/!grouped, sums);
     return 0;
 }
 
 // the per-read species array in file order (report, routing, host-side equal-length test): resident reads keep the species
 // per SLOT; this gathers them on request
 int species_ensure(Ctx *ctx, Reads *rd) {
-    if (rd->species_valid || rd->R == 0) return 0;
+    if (rd->state.species_in_file_order() || rd->R == 0) return 0;
     PTX_HIP(ctx, rd->d_species.alloc(rd->R));
     hipLaunchKernelGGL(species_gather_kernel, dim3(grid_for(rd->R, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, rd->R, rd->d_slot_of.p, rd->d_g_slot_rec.p,
                        rd->d_species.p);
     PTX_HIP(ctx, hipGetLastError());
-    rd->species_valid = true;
+    rd->state.species_gathered();
     return 0;
 }
 
@@ -725,7 +709,7 @@ __global__ void __launch_bounds__(64) species_profile_kernel(uint64_t R, const i
 
 int species_profile_launch(Ctx *ctx, const Db *db, const Reads *rd, const unsigned long long *d_counters, const double *d_avg_len, int filtered,
                            uint8_t *d_keep, double *d_absolute) {
-    hipLaunchKernelGGL(species_profile_kernel, dim3(1), dim3(64), 0, ctx->stream, rd->R, rd->grouped ? nullptr : rd->d_species.p, rd->d_slot_of.p,
+    hipLaunchKernelGGL(species_profile_kernel, dim3(1), dim3(64), 0, ctx->stream, rd->R, rd->state.grouped() ? nullptr : rd->d_species.p, rd->d_slot_of.p,
                        rd->d_g_slot_rec.p, rd->d_qlen.p, db->S, d_counters, d_avg_len,
                        filtered, d_keep, d_absolute);
     PTX_HIP(ctx, hipGetLastError());

@@ -662,7 +662,7 @@ int coverage_prepare(Ctx *ctx, Db *db, Reads *rd, bool with_trio) {
         KTimer t(ctx, "zero_fill_kernel");   // (the arena's fill is a kernel of the step like any other: timed with them)
         PTX_TRY(zero_fill(ctx, base, total));
     }
-    if (rd->R && rd->T_pad && rd->n_long && rd->long_sums_db != 0 && rd->long_sums_db == db->uid) {
+    if (rd->R && rd->T_pad && rd->n_long && rd->state.long_sums_from(db->uid)) {
         // the binning pass of these reads against THIS db took the walk sums on its way (bin_slots_kernel, round 6)
     } else if (rd->R && rd->T_pad && rd->n_long) {
         PTX_HIP(ctx, hipMemsetAsync(rd->d_long_sum.p, 0, rd->R * sizeof(uint32_t), ctx->stream));
@@ -827,7 +827,7 @@ static int count_launch(Ctx *ctx, Db *db) {
 }
 
 int coverage_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_active, bool with_trio, bool defer_count) {
-    if (!rd->grouped) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: these reads are a slice kept as plain columns (to be routed to their owner), not resident reads");
+    if (!rd->state.grouped()) return fail(ctx, PANTAX_HIP_E_STATE, "node_coverage: these reads are a slice kept as plain columns (to be routed to their owner), not resident reads");
     const bool trace = ctx->cfg.trace && !defer_count;
     CovLap lap{ctx, trace};
     if (db->cov.launch_needs_prepare()) PTX_TRY(coverage_prepare(ctx, db, rd, with_trio));

@@ -393,7 +393,6 @@ __global__ void __launch_bounds__(256) add_u32_offset_kernel(uint64_t n, uint32_
 int gaf_tokenize_device(Ctx *ctx, const char *text, uint64_t size, HostReads &out, Reads *resident, int fd, uint64_t file_base, bool group,
                         bool want_id_spans, bool want_host_columns) {
     out = HostReads();
-    if (resident) resident->grouped = group;
     // PANTAX_HIP_TRACE=1: where the load spends its time (stderr)
     const bool trace = ctx->cfg.trace;
     const auto t_enter = std::chrono::steady_clock::now();
@@ -410,6 +409,7 @@ int gaf_tokenize_device(Ctx *ctx, const char *text, uint64_t size, HostReads &ou
             static const uint32_t zero = 0;
             resident->R = resident->T = 0;
             PTX_TRY(upload(ctx, resident->d_step_off, &zero, 1));
+            resident->state.columns_replaced(false);
             if (group) PTX_TRY(build_step_read(ctx, resident, 0));
             PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
@@ -601,7 +601,7 @@ int gaf_tokenize_device(Ctx *ctx, const char *text, uint64_t size, HostReads &ou
         resident->R = R; resident->T = T;
         resident->d_step_off.take(o32[0]); resident->d_node_id.take(o32[1]); resident->d_pstart.take(o32[2]); resident->d_pend.take(o32[3]);
         resident->d_qlen.take(o32[4]); resident->d_mapq.take(o8[0]); resident->d_flags.take(o8[1]); resident->d_id_hash.take(o_hash);
-        resident->has_flags = true;
+        resident->state.columns_replaced(true);
         resident->max_node_id = max_id;
         if (group) PTX_TRY(build_step_read(ctx, resident, max_id));
         PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -663,9 +663,7 @@ extern "C" int pantax_hip_reads_load_gaf(pantax_hip_ctx *ctx, const char *path, 
 extern "C" int pantax_hip_reads_set_flags(pantax_hip_ctx *ctx, pantax_hip_reads *reads, const uint8_t *flags) {
     if (!ctx || !reads) return PANTAX_HIP_E_INVALID;
     PTX_ENTER(ctx);
-    reads->has_flags = flags != nullptr;
+    reads->state.flags_replaced(flags != nullptr);   // the per-slot species carry the drop flags: bin again (the rule: reads_state.hpp)
     if (flags) { PTX_TRY(upload(ctx, reads->d_flags, flags, reads->R)); PTX_HIP(ctx, hipStreamSynchronize(ctx->stream)); }
-    reads->g_flags_valid = false;
-    reads->binned = false;   // the per-slot species carry the drop flags: bin again
     return 0;
 }

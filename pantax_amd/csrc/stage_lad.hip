@@ -1090,7 +1090,7 @@ static int lad_prof_end(Ctx *ctx, uint32_t S, DevBuf<unsigned long long> &buf, c
 #endif
 
 // the strain step's two solves + second filter + both objectives: two launches
-int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const FilterCfg &fc) {
+int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, const LadRows &rows, int pmax_bound, const FilterCfg &fc) {
     const uint32_t S = db->S;
     LadShape shape;
     PTX_TRY(lad_shape_checked(ctx, S, pmax_bound, &shape));
@@ -1113,10 +1113,10 @@ int lad_pair_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const 
 #ifdef LAD_PROFILE
     PTX_TRY(lad_prof_end(ctx, S, prof, lb->d_iters.p));
 #endif
-    return objective_launch(ctx, db, lb, lb->d_need2.p, lb->d_x.p, lb->d_x2.p, lb->d_obj.p, lb->d_obj2.p);
+    return objective_launch(ctx, db, lb, rows, lb->d_need2.p, lb->d_x.p, lb->d_x2.p, lb->d_obj.p, lb->d_obj2.p);
 }
 
-int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const uint8_t *d_need, const uint8_t *d_fixed, double *d_x,
+int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, const LadRows &rows, int pmax_bound, const uint8_t *d_need, const uint8_t *d_fixed, double *d_x,
                      double *d_obj, int32_t *d_status, int32_t *d_iters) {
     const uint32_t S = db->S;
     LadShape shape;
@@ -1138,7 +1138,7 @@ int lad_solve_launch(Ctx *ctx, const Db *db, LadBatch *lb, int pmax_bound, const
 #ifdef LAD_PROFILE
     PTX_TRY(lad_prof_end(ctx, S, prof, d_iters));
 #endif
-    return objective_launch(ctx, db, lb, nullptr, d_x, nullptr, d_obj, nullptr);
+    return objective_launch(ctx, db, lb, rows, nullptr, d_x, nullptr, d_obj, nullptr);
 }
 
 // The solver on plain arrays (lad_args.hpp): one workgroup per entry of A.sp_p, n_lps of them, every one with at most LAD_MAXP columns -- the caller's

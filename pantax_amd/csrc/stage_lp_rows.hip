@@ -575,7 +575,7 @@ static int upload_candidates(Ctx *ctx, const Db *db, LadBatch *lb) {
 // has this path; what grows is the scratch (W and G: 3 x (64 nw)^2 doubles per such species) and the time of one workgroup.
 static int wide_layout(Ctx *ctx, const Db *db, LadBatch *lb, const RowRoute &rt) {
     const uint32_t S = db->S;
-    if (lb->wide_for != (const void *)db) {
+    if (!lb->wide_laid_out) {   // (the batch is its db's own: Db::lad)
         std::vector<uint32_t> off(S ? S : 1, 0xFFFFFFFFu), slot(S ? S : 1, 0xFFFFFFFFu), nwv(S ? S : 1, 0u), list;
         std::vector<uint64_t> woff, coff;
         uint64_t vw = 0, wtot = 0, ctot = 0;
@@ -612,7 +612,7 @@ static int wide_layout(Ctx *ctx, const Db *db, LadBatch *lb, const RowRoute &rt)
             }
             if (n_huge) { PTX_HIP(ctx, lb->d_huge_f64.alloc(ctot * 8)); PTX_HIP(ctx, lb->d_huge_i32.alloc(ctot * 5)); }
         }
-        lb->wide_for = (const void *)db;
+        lb->wide_laid_out = true;
     }
     if (rt.wide != (lb->n_wide != 0)) return fail(ctx, PANTAX_HIP_E_STATE, "lad_prepare: internal (the row route and the wide tables disagree about species of more than %d haplotypes)", LAD_MAXP);
     if (rt.wide) {
@@ -650,7 +650,7 @@ static void mask_ratio_passes(Ctx *ctx, const Db *db, LadBatch *lb, const RowRou
 }
 // 4. rows: compact (the routes that do not read the node arrays) -> sort by (species, mask, a); *sorted: where the sorted rows are.  The staging buffers
 // live in the db so that repeated steps do not hipMalloc; the node sort writes the pattern tables itself (from its splitters), so they are allocated here.
-static int sort_rows(Ctx *ctx, Db *db, LadBatch *lb, const RowRoute &rt, int pmax_bound, int pack_shift, SortBufs *sorted) {
+static int sort_rows(Ctx *ctx, Db *db, LadBatch *lb, const RowRoute &rt, const FusedNodePass *fused_pass, int pmax_bound, int pack_shift, SortBufs *sorted, bool *c0_valid) {
     const uint32_t S = db->S;
     const uint64_t V = db->V;
     DevBuf<uint32_t> &scan_tmp = db->d_scan_tmp, &table = db->d_sort_table;
@@ -682,17 +682,17 @@ static int sort_rows(Ctx *ctx, Db *db, LadBatch *lb, const RowRoute &rt, int pma
     PTX_HIP(ctx, lb->d_pat_mask.alloc(k_cap)); PTX_HIP(ctx, lb->d_pat_start.alloc(k_cap + 1)); PTX_HIP(ctx, lb->d_pat_species.alloc(k_cap));
     PTX_HIP(ctx, lb->d_sp_pat_off.alloc(S + 1));
     if (rt.use_nodes) {   // no compaction: the sort's passes read the node arrays and skip the nodes that are no rows; the patterns come from its splitters
-        const bool fused = lb->node_pass_fused;
+        const bool fused = fused_pass != nullptr;
         PTX_HIP(ctx, db->d_ss_ws.alloc(sample_sort_nodes_ws_elems(S, rt.max_vs, V)));
         PTX_HIP(ctx, db->d_row16.alloc(4 * V));
         PTX_HIP(ctx, lb->d_c0.alloc(S));
         const RowPatterns pat{lb->d_pat_mask.p, lb->d_pat_start.p, lb->d_pat_species.p, lb->d_sp_pat_off.p, d_K, lb->d_c0.p};
-        lb->rows_c0_valid = true;
+        *c0_valid = true;
         RowMaskSource hp;
         NodeCovSource fz;
         if (fused) {
             fz.bases = (const unsigned long long *)db->d_bases.p; fz.bit_off = db->d_bit_off.p; fz.full = db->d_full.p; fz.bitmap = db->d_bitmap.p;
-            fz.active = lb->fused_active; fz.min_depth = lb->fused_min_depth;
+            fz.active = fused_pass->active; fz.min_depth = fused_pass->min_depth;
             fz.amax = lb->d_amax.p; fz.nzsum = lb->d_nzsum.p; fz.nvalid = lb->d_nvalid.p; fz.nzcnt = lb->d_nzcnt.p;
         }
         if (rt.masks_in_sort) {
@@ -752,27 +752,25 @@ static int solver_scratch(Ctx *ctx, LadBatch *lb) {
 
 // All of it is enqueued without a host round trip: the row count n and the pattern count K stay on the
 // device (lb->d_counts = {n_rows, K, overflow}); buffers are sized by their host-known bounds (n <= V,
-// K <= k_cap).  cand_on_device: lb->d_hap_bit / d_p were written by first_filter_kernel; otherwise they are
-// uploaded from lb->h_p / h_cand (solver seam).  pmax_bound = upper bound of candidates per species.
-int lad_prepare(Ctx *ctx, Db *db, LadBatch *lb, bool cand_on_device, int pmax_bound) {
+// K <= k_cap).  The request and what comes back in *rows: lad.hpp.
+int lad_prepare(Ctx *ctx, Db *db, LadBatch *lb, const LadRequest &rq, LadRows *rows) {
     const uint64_t V = db->V, H = db->H;
     const RowRoute rt = row_route(ctx, db);
-    const int pack_shift = row_pack_shift(rt, db->S, pmax_bound);
-    lb->rows_c0_valid = false;
-    if (!cand_on_device) PTX_TRY(upload_candidates(ctx, db, lb));
+    const int pack_shift = row_pack_shift(rt, db->S, rq.pmax_bound);
+    *rows = LadRows{false, rt.masks_in_sort, rq.fused != nullptr};
+    if (!rq.cand_on_device) PTX_TRY(upload_candidates(ctx, db, lb));
     PTX_HIP(ctx, lb->d_mask.alloc(V));
     PTX_HIP(ctx, lb->d_ratio.alloc((size_t)(H ? H : 1) * 2));
-    if (!lb->prezeroed && !rt.by_node) PTX_TRY(zero_fill(ctx, lb->d_mask.p, V * sizeof(uint64_t)));   // (mask_nodes_kernel writes every word)
+    if (!rq.zeroed && !rt.by_node) PTX_TRY(zero_fill(ctx, lb->d_mask.p, V * sizeof(uint64_t)));   // (mask_nodes_kernel writes every word)
     PTX_TRY(wide_layout(ctx, db, lb, rt));
     // d_ratio and d_counts live in the step's result arena, which the caller has just zeroed
-    lb->masks_in_sort = rt.masks_in_sort;
     // the fused node pass was decided before the step's first kernel (strain_enqueue): no abundance array and no covered-base counts exist, so every reader
-    // of them below (mask_nodes_kernel, ratio_kernel, row_emit_kernel, wide_pattern_kernel; objective_kernel in objective_launch) is excluded by this flag
-    if (lb->node_pass_fused && (!rt.masks_in_sort || rt.wide || !cand_on_device))
+    // of them below (mask_nodes_kernel, ratio_kernel, row_emit_kernel, wide_pattern_kernel; objective_kernel in objective_launch) is excluded by it
+    if (rq.fused && (!rt.masks_in_sort || rt.wide || !rq.cand_on_device))
         return fail(ctx, PANTAX_HIP_E_STATE, "lad_prepare: internal (the fused node pass without masks formed in the row sort)");
     mask_ratio_passes(ctx, db, lb, rt);
     SortBufs sorted;
-    PTX_TRY(sort_rows(ctx, db, lb, rt, pmax_bound, pack_shift, &sorted));
+    PTX_TRY(sort_rows(ctx, db, lb, rt, rq.fused, rq.pmax_bound, pack_shift, &sorted, &rows->c0_valid));
     PTX_TRY(pattern_tables(ctx, db, lb, rt, pack_shift, sorted));
     PTX_TRY(solver_scratch(ctx, lb));
     PTX_HIP(ctx, hipGetLastError());

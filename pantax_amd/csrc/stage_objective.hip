@@ -178,11 +178,11 @@ __global__ void __launch_bounds__(256) objective_rows_kernel(const int32_t *__re
     done[s] = 0;
 }
 
-int objective_launch(Ctx *ctx, const Db *db, LadBatch *lb, const uint8_t *d_need2, const double *d_x1, const double *d_x2, double *d_obj1,
-                            double *d_obj2) {
+int objective_launch(Ctx *ctx, const Db *db, LadBatch *lb, const LadRows &rows, const uint8_t *d_need2, const double *d_x1, const double *d_x2, double *d_obj1,
+                     double *d_obj2) {
     const uint32_t S = db->S;
     const bool by_nodes = ctx->cfg.objective == "nodes";   // measurements / tests: the pass over the nodes
-    if (lb->rows_c0_valid && lb->n_wide == 0 && (!by_nodes || lb->masks_in_sort)) {
+    if (rows.c0_valid && lb->n_wide == 0 && (!by_nodes || rows.masks_in_sort)) {
         KTimer t(ctx, "objective_rows_kernel");
         PTX_HIP(ctx, lb->d_partial.alloc((size_t)S * STAT_CHUNKS * 4));
         if (lb->d_obj_done.n < S) {
@@ -199,7 +199,7 @@ int objective_launch(Ctx *ctx, const Db *db, LadBatch *lb, const uint8_t *d_need
         PTX_HIP(ctx, hipGetLastError());
         return 0;
     }
-    if (lb->node_pass_fused) return fail(ctx, PANTAX_HIP_E_STATE, "objective: internal (the pass over the nodes after a fused node pass: no abundance array)");
+    if (rows.fused) return fail(ctx, PANTAX_HIP_E_STATE, "objective: internal (the pass over the nodes after a fused node pass: no abundance array)");
     KTimer t(ctx, "objective_kernel");
     PTX_HIP(ctx, lb->d_partial.alloc((size_t)S * STAT_CHUNKS * 4));
     if (lb->d_obj_done.n < S) {

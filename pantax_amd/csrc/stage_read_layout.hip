@@ -237,15 +237,13 @@ __global__ void __launch_bounds__(256) group_block_kernel(uint32_t n_groups, con
     }
 }
 
-int build_step_read(Ctx *ctx, Reads *rd, uint32_t max_node_id) {
+static int step_read_layout(Ctx *ctx, Reads *rd, uint32_t max_node_id) {
     static std::atomic<uint64_t> next_layout{1};
     rd->layout_id = next_layout.fetch_add(1);       // (what a db's list of work items is made for)
     rd->T_pad = 0;
     rd->n_long = 0;
     rd->n_slots = 0;
     rd->n_items = 0;
-    rd->g_flags_valid = false;
-    rd->species_valid = false;
     PTX_HIP(ctx, rd->d_slot_of.alloc(rd->R ? rd->R : 1));
     PTX_HIP(ctx, rd->d_g_slot_rec.alloc(rd->R ? rd->R : 1));
     PTX_HIP(ctx, rd->d_g_qm.alloc(rd->R ? rd->R : 1));
@@ -349,12 +347,18 @@ int build_step_read(Ctx *ctx, Reads *rd, uint32_t max_node_id) {
     return 0;
 }
 
-int reads_group(Ctx *ctx, Reads *rd) {
-    if (rd->grouped) return 0;
-    PTX_TRY(build_step_read(ctx, rd, rd->max_node_id));
-    rd->grouped = true;
-    rd->binned = false;          // the species of a read now live in its slot record: the next binning pass writes them
+// "grouped" holds only from the finished build on; the build voids the binning (the species of a read now live in its slot record: the next binning pass
+// writes them), the file-order species array and the slot-order flags
+int build_step_read(Ctx *ctx, Reads *rd, uint32_t max_node_id) {
+    rd->state.layout_begun();
+    PTX_TRY(step_read_layout(ctx, rd, max_node_id));
+    rd->state.layout_finished();
     return 0;
+}
+
+int reads_group(Ctx *ctx, Reads *rd) {
+    if (rd->state.grouped()) return 0;
+    return build_step_read(ctx, rd, rd->max_node_id);
 }
 
 }  // namespace ptx

@@ -135,7 +135,8 @@ __global__ void __launch_bounds__(256) route_max_kernel(uint64_t n, const uint32
 // reads (binned against `db`) -> one message per owner.  owner_of_species[s] = rank that owns species s of `db`, or < 0.
 int route_pack(Ctx *ctx, const Db *db, const Reads *rd, const int32_t *owner_of_species, int W, Route &rt) {
     if (W < 1 || W > ROUTE_MAXW) return fail(ctx, PANTAX_HIP_E_LIMIT, "route_pack: %d owners (at most %d)", W, ROUTE_MAXW);
-    if (!rd->binned) return fail(ctx, PANTAX_HIP_E_STATE, "route_pack: call pantax_hip_bin_reads on these reads first");
+    if (!rd->state.binned_against(db->uid))
+        return fail(ctx, PANTAX_HIP_E_STATE, "route_pack: call pantax_hip_bin_reads on these reads against this db first (they are not binned, or binned against another db)");
     PTX_TRY(species_ensure(ctx, const_cast<Reads *>(rd)));   // resident (grouped) reads keep the species per slot
     for (uint32_t s = 0; s < db->S; ++s)
         if (owner_of_species[s] >= W) return fail(ctx, PANTAX_HIP_E_INVALID, "route_pack: species %u is owned by rank %d of %d", s, owner_of_species[s], W);
@@ -151,7 +152,7 @@ int route_pack(Ctx *ctx, const Db *db, const Reads *rd, const int32_t *owner_of_
     PTX_TRY(upload_small(ctx, d_owner, owner_of_species, db->S));
     PTX_HIP(ctx, table.alloc(n_tab)); PTX_HIP(ctx, scanned.alloc(n_tab)); PTX_HIP(ctx, scan_tmp.alloc(scan_tmp_elems(n_tab)));
     PTX_HIP(ctx, totals.alloc(2 * W + 1));
-    const uint8_t *flags = rd->has_flags ? rd->d_flags.p : nullptr;
+    const uint8_t *flags = rd->state.has_flags() ? rd->d_flags.p : nullptr;
     {
         KTimer t(ctx, "route_count_kernel");
         hipLaunchKernelGGL(route_count_kernel, dim3(n_tiles), dim3(ROUTE_TILE), 0, ctx->stream, rd->R, rd->d_species.p, d_owner.p, flags, rd->d_step_off.p, W,
@@ -192,8 +193,7 @@ int reads_from_routed(Ctx *ctx, const uint32_t *d_recv, int W, const uint64_t *n
     PTX_HIP(ctx, rd->d_step_off.alloc(R + 1)); PTX_HIP(ctx, rd->d_node_id.alloc(T ? T : 1));
     PTX_HIP(ctx, rd->d_pstart.alloc(R ? R : 1)); PTX_HIP(ctx, rd->d_pend.alloc(R ? R : 1)); PTX_HIP(ctx, rd->d_qlen.alloc(R ? R : 1));
     PTX_HIP(ctx, rd->d_mapq.alloc(R ? R : 1));
-    rd->has_flags = false;
-    rd->binned = false;
+    rd->state.columns_replaced(false);
     DevBuf<uint32_t> nst, mq, scan_tmp, d_max;
     PTX_HIP(ctx, nst.alloc(R + 1)); PTX_HIP(ctx, mq.alloc(R ? R : 1)); PTX_HIP(ctx, scan_tmp.alloc(scan_tmp_elems(R + 1))); PTX_HIP(ctx, d_max.alloc(1));
     auto d2d = [&](void *dst, const void *src, uint64_t words) {
