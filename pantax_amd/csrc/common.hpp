@@ -266,6 +266,17 @@ constexpr int LAD_MAXP = 64;     // candidate paths of a species on the one-word
 constexpr int LAD_WIDE_NW = 4;   // mask words of a "wide" species (65 .. 256 haplotypes); more haplotypes ("huge"): whole groups of four words
 constexpr int LAD_WIDEP = 64 * LAD_WIDE_NW;   // candidate paths up to which a species' solver state is sized at compile time
 
+// The LAD solver's scratch per pattern (stage_lad.hip; LadArgs in lad_args.hpp names the same eight arrays): the perturbation, position, rate and row
+// brackets of every pattern and the crossed-count brackets of its line search.  One owner: the strain step's LadBatch, the bootstrap's and the
+// dropout's chunk each hold one.
+struct LadArgs;
+struct LadPatScratch {
+    DevBuf<double> pat_eps, sc_s, sc_rho;
+    DevBuf<uint32_t> sc_lo, sc_up, ls_lo, ls_hi, ls_mid;
+    int alloc(Ctx *ctx, uint64_t n_patterns);   // (lad_args.hpp)
+    void bind(LadArgs &A) const;
+};
+
 // One batch = every species that has at least one candidate path, solved concurrently
 // (one workgroup per species; the LPs are block-diagonal: profile.rs:3297-3319 runs them as
 // independent rayon tasks).
@@ -319,9 +330,7 @@ struct LadBatch {
     DevBuf<uint32_t> d_pat_species;     // [K]
     DevBuf<uint32_t> d_sp_pat_off;      // [S+1]
     std::vector<uint32_t> h_sp_pat_off;
-    // solver scratch per pattern
-    DevBuf<double> d_pat_eps, d_sc_s, d_sc_rho;
-    DevBuf<uint32_t> d_sc_lo, d_sc_up, d_ls_lo, d_ls_hi, d_ls_mid;
+    LadPatScratch pat_scratch;          // solver scratch per pattern (between two solves the objective pass keeps its predictions in sc_s / sc_rho)
     // solver in/out per species
     DevBuf<double> d_x, d_x2, d_obj, d_obj2;      // [H] x of solve 1 / 2 at hap_off[s] + k, [S] objectives
     DevBuf<int32_t> d_status, d_iters, d_status2, d_iters2;   // [S]

@@ -375,18 +375,18 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
     DevBuf<uint64_t> &d_sel_off = F.d_sel_off, &d_bpat_mask = F.d_bpat_mask;
     // ---- the chunk's scratch, once (DevBuf: the ctx's device cache); nothing is allocated inside the loop
     const uint64_t per = plan.per_chunk, nq_max = per * S, np_max = per * P, ni_max = per * N;
-    DevBuf<uint32_t> d_off, d_prefix, d_pat_start, d_sp_pat_off, d_flags, d_sc_lo, d_sc_up, d_ls_lo, d_ls_hi, d_ls_mid;
+    DevBuf<uint32_t> d_off, d_prefix, d_pat_start, d_sp_pat_off, d_flags;
     DevBuf<uint64_t> d_pat_mask, d_col_off, d_rows;
-    DevBuf<double> d_exp_a, d_amax, d_x, d_obj, d_pat_eps, d_sc_s, d_sc_rho;
+    DevBuf<double> d_exp_a, d_amax, d_x, d_obj;
     DevBuf<int32_t> d_sp_p, d_pre, d_status, d_iters;
+    LadPatScratch pat_scratch;
     PTX_HIP(ctx, d_off.alloc(ni_max + 1)); PTX_HIP(ctx, d_exp_a.alloc(plan.chunk_rows));
     PTX_HIP(ctx, d_prefix.alloc(np_max + 1)); PTX_HIP(ctx, d_pat_start.alloc(np_max + 1)); PTX_HIP(ctx, d_pat_mask.alloc(np_max));
     PTX_HIP(ctx, d_sp_pat_off.alloc(nq_max + 1)); PTX_HIP(ctx, d_flags.alloc(1));
     PTX_HIP(ctx, d_col_off.alloc(nq_max)); PTX_HIP(ctx, d_rows.alloc(nq_max)); PTX_HIP(ctx, d_amax.alloc(nq_max)); PTX_HIP(ctx, d_obj.alloc(nq_max));
     PTX_HIP(ctx, d_sp_p.alloc(nq_max)); PTX_HIP(ctx, d_pre.alloc(nq_max)); PTX_HIP(ctx, d_status.alloc(nq_max)); PTX_HIP(ctx, d_iters.alloc(nq_max));
     PTX_HIP(ctx, d_x.alloc(per * std::max<uint64_t>(C, 1)));
-    PTX_HIP(ctx, d_pat_eps.alloc(np_max)); PTX_HIP(ctx, d_sc_s.alloc(np_max)); PTX_HIP(ctx, d_sc_rho.alloc(np_max));
-    PTX_HIP(ctx, d_sc_lo.alloc(np_max)); PTX_HIP(ctx, d_sc_up.alloc(np_max)); PTX_HIP(ctx, d_ls_lo.alloc(np_max)); PTX_HIP(ctx, d_ls_hi.alloc(np_max)); PTX_HIP(ctx, d_ls_mid.alloc(np_max));
+    PTX_TRY(pat_scratch.alloc(ctx, np_max));
     PTX_HIP(ctx, hipMemsetAsync(d_flags.p, 0, sizeof(uint32_t), ctx->stream));
     std::vector<int32_t> c_pre(nq_max), c_status(nq_max);
     uint32_t h_flag = 0;
@@ -417,13 +417,10 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
         PTX_HIP(ctx, hipGetLastError());
         if (C) PTX_HIP(ctx, hipMemsetAsync(d_x.p, 0, (size_t)nb * C * sizeof(double), ctx->stream));
         PTX_HIP(ctx, hipMemsetAsync(d_status.p, 0, (size_t)nq * sizeof(int32_t), ctx->stream));
-        LadArgs LA = {};
-        LA.row_a = d_exp_a.p; LA.pat_mask = d_pat_mask.p; LA.pat_start = d_pat_start.p; LA.sp_pat_off = d_sp_pat_off.p;
-        LA.pat_eps = d_pat_eps.p; LA.sc_s = d_sc_s.p; LA.sc_rho = d_sc_rho.p; LA.sc_lo = d_sc_lo.p; LA.sc_up = d_sc_up.p;
-        LA.ls_lo = d_ls_lo.p; LA.ls_hi = d_ls_hi.p; LA.ls_mid = d_ls_mid.p;
-        LA.sp_p = d_sp_p.p; LA.amax = d_amax.p; LA.x_out = d_x.p; LA.status = d_status.p; LA.iters = d_iters.p; LA.col_off = d_col_off.p;
+        const LadArgs LA = lad_plain_args(LadRowTables{d_exp_a.p, d_pat_mask.p, d_pat_start.p, d_sp_pat_off.p}, LadLpTables{d_sp_p.p, d_amax.p, d_col_off.p, nullptr, nullptr},
+                                          LadOutputs{d_x.p, d_status.p, d_iters.p}, pat_scratch);
         PTX_TRY(lad_args_launch(ctx, LA, nq, (int)k_max, "lad_solve_kernel<bootstrap>"));
-        PTX_TRY(boot_objective_launch(ctx, nq, d_sp_p.p, d_sp_pat_off.p, d_pat_mask.p, d_pat_start.p, d_exp_a.p, d_col_off.p, d_x.p, d_sc_s.p, d_obj.p, "boot_objective_kernel"));
+        PTX_TRY(boot_objective_launch(ctx, nq, d_sp_p.p, d_sp_pat_off.p, d_pat_mask.p, d_pat_start.p, d_exp_a.p, d_col_off.p, d_x.p, pat_scratch.sc_s.p, d_obj.p, "boot_objective_kernel"));
         if (C) PTX_TRY(download(ctx, hx.data() + b0 * C, d_x.p, (size_t)nb * C));
         PTX_TRY(download(ctx, hobj.data() + b0 * S, d_obj.p, (size_t)nq));
         PTX_TRY(download(ctx, (unsigned long long *)hrows.data() + b0 * S, (const unsigned long long *)d_rows.p, (size_t)nq));

@@ -308,15 +308,15 @@ int dropout_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *se
     const uint32_t n_slices = (uint32_t)sl_sp.size();
     // ---- all scratch, once; nothing is allocated inside the loop
     const uint64_t cp = plan.chunk_patterns, ce = plan.chunk_entries;
-    DevBuf<uint32_t> d_pat_start, d_sp_pat_off, d_sc_lo, d_sc_up, d_ls_lo, d_ls_hi, d_ls_mid, d_sl_sp, d_sl_row0, d_sp_sl_off, d_part_cnt;
+    DevBuf<uint32_t> d_pat_start, d_sp_pat_off, d_sl_sp, d_sl_row0, d_sp_sl_off, d_part_cnt;
     DevBuf<uint64_t> d_pat_mask, d_col_off, d_x_off, d_sl_part;
     DevBuf<unsigned long long> d_cnt;
-    DevBuf<double> d_amax, d_x, d_obj, d_pat_eps, d_sc_s, d_sc_rho, d_part_obj;
+    DevBuf<double> d_amax, d_x, d_obj, d_part_obj;
     DevBuf<int32_t> d_sp_p, d_status, d_iters;
     DevBuf<uint8_t> d_fixed;
+    LadPatScratch pat_scratch;
     PTX_HIP(ctx, d_pat_start.alloc(cp + 1)); PTX_HIP(ctx, d_pat_mask.alloc(cp)); PTX_HIP(ctx, d_sp_pat_off.alloc(ce + 1));
-    PTX_HIP(ctx, d_pat_eps.alloc(cp)); PTX_HIP(ctx, d_sc_s.alloc(cp)); PTX_HIP(ctx, d_sc_rho.alloc(cp));
-    PTX_HIP(ctx, d_sc_lo.alloc(cp)); PTX_HIP(ctx, d_sc_up.alloc(cp)); PTX_HIP(ctx, d_ls_lo.alloc(cp)); PTX_HIP(ctx, d_ls_hi.alloc(cp)); PTX_HIP(ctx, d_ls_mid.alloc(cp));
+    PTX_TRY(pat_scratch.alloc(ctx, cp));
     PTX_HIP(ctx, d_sp_p.alloc(ce)); PTX_HIP(ctx, d_amax.alloc(ce)); PTX_HIP(ctx, d_col_off.alloc(ce)); PTX_HIP(ctx, d_status.alloc(ce)); PTX_HIP(ctx, d_iters.alloc(ce));
     PTX_HIP(ctx, d_x.alloc(std::max<uint64_t>(X, 1))); PTX_HIP(ctx, d_fixed.alloc(std::max<uint64_t>(X, 1)));
     PTX_HIP(ctx, d_obj.alloc(Q)); PTX_HIP(ctx, d_cnt.alloc(Q * 4));
@@ -344,15 +344,12 @@ int dropout_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *se
         }
         PTX_HIP(ctx, hipGetLastError());
         PTX_HIP(ctx, hipMemsetAsync(d_status.p, 0, (size_t)nq * sizeof(int32_t), ctx->stream));
-        LadArgs LA = {};
-        LA.row_a = F.base_a; LA.pat_mask = d_pat_mask.p; LA.pat_start = d_pat_start.p; LA.sp_pat_off = d_sp_pat_off.p;
-        LA.pat_eps = d_pat_eps.p; LA.sc_s = d_sc_s.p; LA.sc_rho = d_sc_rho.p; LA.sc_lo = d_sc_lo.p; LA.sc_up = d_sc_up.p;
-        LA.ls_lo = d_ls_lo.p; LA.ls_hi = d_ls_hi.p; LA.ls_mid = d_ls_mid.p;
-        LA.sp_p = d_sp_p.p; LA.fixed = d_fixed.p; LA.amax = d_amax.p; LA.x_out = d_x.p; LA.status = d_status.p; LA.iters = d_iters.p; LA.col_off = d_col_off.p;
+        const LadArgs LA = lad_plain_args(LadRowTables{F.base_a, d_pat_mask.p, d_pat_start.p, d_sp_pat_off.p}, LadLpTables{d_sp_p.p, d_amax.p, d_col_off.p, nullptr, d_fixed.p},
+                                          LadOutputs{d_x.p, d_status.p, d_iters.p}, pat_scratch);
         PTX_TRY(lad_args_launch(ctx, LA, nq, (int)F.k_max, "lad_solve_kernel<dropout>"));
         // measurement only (option dropout_yardstick): the bootstrap's objective pass over the same rows, a pass per round; its sums are not delivered
         if (ctx->cfg.dropout_yardstick)
-            PTX_TRY(boot_objective_launch(ctx, nq, d_sp_p.p, d_sp_pat_off.p, d_pat_mask.p, d_pat_start.p, F.base_a, d_col_off.p, d_x.p, d_sc_s.p, d_yard.p, "boot_objective_kernel<dropout>"));
+            PTX_TRY(boot_objective_launch(ctx, nq, d_sp_p.p, d_sp_pat_off.p, d_pat_mask.p, d_pat_start.p, F.base_a, d_col_off.p, d_x.p, pat_scratch.sc_s.p, d_yard.p, "boot_objective_kernel<dropout>"));
         PTX_TRY(download(ctx, c_status.data(), d_status.p, (size_t)nq));
         PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         for (uint32_t rl = 0; rl < nr; ++rl)

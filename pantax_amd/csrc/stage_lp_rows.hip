@@ -743,9 +743,7 @@ static int pattern_tables(Ctx *ctx, const Db *db, LadBatch *lb, const RowRoute &
 // 6. the solver's per-pattern scratch
 static int solver_scratch(Ctx *ctx, LadBatch *lb) {
     const uint64_t k_cap = lb->k_cap;
-    PTX_HIP(ctx, lb->d_pat_eps.alloc(k_cap)); PTX_HIP(ctx, lb->d_sc_s.alloc(k_cap)); PTX_HIP(ctx, lb->d_sc_rho.alloc(k_cap));
-    PTX_HIP(ctx, lb->d_sc_lo.alloc(k_cap)); PTX_HIP(ctx, lb->d_sc_up.alloc(k_cap)); PTX_HIP(ctx, lb->d_ls_lo.alloc(k_cap));
-    PTX_HIP(ctx, lb->d_ls_hi.alloc(k_cap)); PTX_HIP(ctx, lb->d_ls_mid.alloc(k_cap));
+    PTX_TRY(lb->pat_scratch.alloc(ctx, k_cap));
     if (lb->n_huge) PTX_HIP(ctx, lb->d_pat_act.alloc(k_cap));
     return 0;
 }

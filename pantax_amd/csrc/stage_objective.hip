@@ -192,9 +192,9 @@ int objective_launch(Ctx *ctx, const Db *db, LadBatch *lb, const LadRows &rows, 
         const uint32_t nch = stat_chunks(S);
         // (the solver's per-pattern scratch is free again: the predictions of both solutions go there)
         hipLaunchKernelGGL(pattern_pred_kernel, dim3(S), dim3(256), 0, ctx->stream, lb->d_p.p, d_need2, lb->d_sp_pat_off.p, lb->d_pat_mask.p, db->d_hap_off.p, d_x1, d_x2,
-                           lb->d_sc_s.p, lb->d_sc_rho.p);
+                           lb->pat_scratch.sc_s.p, lb->pat_scratch.sc_rho.p);
         hipLaunchKernelGGL(objective_rows_kernel, dim3(S * nch), dim3(256), 0, ctx->stream, lb->d_p.p, d_need2, lb->d_sp_pat_off.p, lb->d_pat_start.p, lb->row_a,
-                           (const double *)lb->d_sc_s.p, (const double *)lb->d_sc_rho.p, (const double *)lb->d_c0.p, lb->d_partial.p, lb->d_obj_done.p, lb->d_nvalid.p,
+                           (const double *)lb->pat_scratch.sc_s.p, (const double *)lb->pat_scratch.sc_rho.p, (const double *)lb->d_c0.p, lb->d_partial.p, lb->d_obj_done.p, lb->d_nvalid.p,
                            d_obj1, d_obj2, nch, d_x2 != nullptr);
         PTX_HIP(ctx, hipGetLastError());
         return 0;
