@@ -533,6 +533,41 @@ int pantax_hip_strain_dropout(pantax_hip_ctx *ctx, pantax_hip_db *db, const pant
  * sum over j != k of |x_drop[j] - x_full[j]| in ascending j }.  PANTAX_HIP_E_INVALID for a null argument or k >= K. */
 int pantax_hip_dropout_substitute(uint32_t K, uint32_t k, const double *x_full, const double *x_drop, double *out /*[3]*/);
 
+/* ---- add-one test of the strain fit (not a stage of the reference): the false-negative test beside the leave-one-out test.  For a haplotype that a filter
+ * dropped: how much better would the L1 fit of this sample be with it in the LP, what coverage would it get, and which reported strain would it take that
+ * coverage from?  The near-miss call counts bases; only the LP can say this.
+ * Selection type, Sel_s, Cand_s, M(v), N(v), the state rules and the argument errors are those of pantax_hip_strain_near_miss (PANTAX_HIP_E_INVALID also for
+ * a haplotype twice within Sel_s or within Cand_s, and for one in both); the inputs are those of pantax_hip_strain_bootstrap.
+ *   Columns: species s has K_s reported and J_s candidate haplotypes, W_s = K_s + J_s columns.  Column k < K_s is selection entry sel_off[s] + k, column
+ *   K_s + c is candidate entry cand_off[s] + c.
+ *   Rows: the bootstrap's replicate-0 rows for the selection Sel_s ++ Cand_s: every node with a_v = (double)(long long)bases / (double)len > 0 and a non-empty
+ *   mask over the W_s columns.  No min_depth, no sample cut, no filter.  The row set is the same in every entry of a species: the objectives are comparable.
+ *   Entries: E_s = J_s + 1.  Entry 0 pins every candidate column to zero: the refit of the reported strains over these rows, in which a row that only
+ *   candidates walk costs a_v.  Entry c + 1 frees candidate c and pins the other candidates; the reported columns are free in every entry.  Box:
+ *   0 <= x <= 1.05 max a, max a over the species' rows, the same in every entry.  A pinned column is delivered as exactly +0.0.  K_s = 0 makes entry 0
+ *   all-pinned: no LP is launched, x = 0, obj = sum of a, status 0 (the rule of the leave-one-out call's entry 1 at K_s = 1).
+ * Outputs, sized by the caller; entry (s, e) has index q = cand_off[s] + s + e, Q = J + S entries exist:
+ *   x_out      per species a block of E_s x W_s doubles at x_off[s] = sum over t < s of E_t W_t, entry-major;
+ *   obj_out    [Q] the SUM over the rows of |a_v - sum_j x_j bit_j(mask_v)| at the entry's x;
+ *   status_out [Q] 0 solved;  1 nothing to solve (no row, or W_s = 0: x = 0, obj = 0);  PANTAX_HIP_E_LIMIT W_s > 64 (the other species are served);
+ *              PANTAX_HIP_E_SOLVER that LP alone failed;
+ *   rows_out   [S] the species' rows;
+ *   count_out  [Q][4] = { n_member, n_novel, n_better, n_worse } of entry c + 1: rows with bit K_s + c; rows with bit K_s + c and no bit below K_s; rows whose
+ *              absolute residual under entry c + 1 is strictly smaller / strictly larger than under entry 0.  Entry 0 holds { rows, rows with no bit below
+ *              K_s, 0, 0 }.  The residual of a row is fabs(s - a), s the f64 sum of the entry's x_j over the set bits in ascending j: the counts are a function
+ *              of the delivered x.
+ * The call fails as a whole only on invalid arguments, a HIP error or PANTAX_HIP_E_LIMIT of its own (32-bit row positions; one round of LPs -- entry e of
+ * every species over one copy of the pattern tables -- that does not fit the option addin_patterns_max, the cap on the replicated patterns in flight,
+ * 0 = from the free device memory); on an error the outputs are left as given.  Determinism: the same inputs give the same bits, whatever the chunking of
+ * the rounds (addin_patterns_max), the membership route (option addin_route=walk) and the position of the species in the db; the objective is summed in an
+ * order that is a function of the species' sorted rows and its column counts alone. */
+int pantax_hip_strain_addin(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_near_miss_set *sel, double *x_out, double *obj_out /*[Q]*/,
+                            int32_t *status_out /*[Q]*/, uint64_t *rows_out /*[S]*/, uint64_t *count_out /*[Q][4]*/);
+/* host helper, no ctx and no GPU: which reported strain gives coverage up when a candidate enters.  x_base / x_add [W]: the x of entry 0 and of entry c + 1;
+ * the first K columns are the reported ones.  out[3] = { the column j < K with the largest x_base[j] - x_add[j] (ties: the lowest j), -1 when no difference
+ * is positive;  that loss (0 when none);  sum over j < K of |x_add[j] - x_base[j]| in ascending j }.  PANTAX_HIP_E_INVALID for a null argument or K > W. */
+int pantax_hip_addin_donor(uint32_t W, uint32_t K, const double *x_base, const double *x_add, double *out /*[3]*/);
+
 /* ---- SURVEY 8e, reads over N GPUs: bin where tokenised, route to the owner of the species ------------------------
  * The reference groups the reads by species in one process (group_reads_by_species, profile.rs:439-463) and hands each
  * species' records to its rayon task.  With one process per GPU every rank holds a 1/N slice of the reads (its byte range
@@ -862,6 +897,29 @@ typedef struct {
      * objective, the rest "-".  Same rules as strain_fit_file. */
     const char *strain_dropout_file;
 } pantax_hip_profile_ext3;
+/* ... and once more: pantax_hip_profile_ext3 is closed at strain_dropout_file (a committed host check holds its 48 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the third version.  A caller fills v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext4) and passes
+ * &ext4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40- or 48-byte struct runs with the fields below off.  A later output is a field
+ * appended here. */
+typedef struct {
+    pantax_hip_profile_ext3 v3;   /* v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext4) */
+    /* --strain-addin: path of the add-one report (pantax_hip_strain_addin over every group of species, right behind the group's leave-one-out test, on the
+     * same coverage result; NULL, "" or "None" = off).  Sel_s = the species' rows of strain_abundance.txt in ascending haplotype index; Cand_s = the
+     * candidates of the near-miss report (every haplotype of the species without a row), ranked by pantax_hip_near_miss_rank with top = strain_addin_top and
+     * cut in rank order to 64 - K_s: a candidate without novel bases is not tested.  TSV with a header: species_taxid, strain_taxid, genome_ID, rank, class,
+     * n_rows, objective, objective_with, gain, gain_fraction, coverage, n_member, n_novel, n_better, n_worse, donor_strain_taxid, donor_genome_ID,
+     * donor_loss, shift, stage, unique_trio_nodes_fraction; f64 in shortest round-trip digits, "-" where a column does not apply.  Per species in the
+     * order it went through the device its tested candidates in rank order, class "candidate": n_rows and objective of entry 0, objective_with = the
+     * objective of the candidate's entry c + 1, gain = objective - objective_with, gain_fraction = gain / objective ("-" when that is 0), coverage = the
+     * candidate's x under its own entry, the four counts of entry c + 1, the donor columns and shift from pantax_hip_addin_donor (strain_taxid and genome_ID of a
+     * candidate and of a donor are those of the haplotype's first row of genomes_info.txt, as in the near-miss report; "-" when there is no donor;
+     * n_rows .. shift are "-" where entry 0 or entry c + 1 is not solved), stage and unique_trio_nodes_fraction as the near-miss report prints them.
+     * Then one row per species that has rows in the strain table or a tested candidate, in the same order, class "species" ("skipped" for more than 64
+     * rows in the table): n_rows, objective and, in n_novel, the rows no reported strain walks (entry 0's second count); the rest "-".  Same rules as
+     * strain_fit_file. */
+    const char *strain_addin_file;
+    uint64_t strain_addin_top;   /* candidates tested per species: 0 reads as 5, and so does a struct that does not hold the field */
+} pantax_hip_profile_ext4;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

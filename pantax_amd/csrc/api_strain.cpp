@@ -685,23 +685,46 @@ int pantax_hip_strain_depth(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax
     return depth_launch(ctx, db, sel->sel_off, sel->sel_hap, hap_out, species_out);
 }
 
+// the argument checks that pantax_hip_strain_near_miss and pantax_hip_strain_addin share: both sets in range and free of repeats, and disjoint
+static int check_near_miss_set(pantax_hip_ctx *ctx, const pantax_hip_db *db, const char *what, const pantax_hip_near_miss_set *sel) {
+    PTX_TRY(check_species_count(ctx, db, what, sel->n_species));
+    PTX_TRY(check_hap_selection(ctx, db, what, sel->sel_off, sel->sel_hap));
+    PTX_TRY(check_hap_selection(ctx, db, (std::string(what) + " (candidates)").c_str(), sel->cand_off, sel->cand_hap));
+    std::vector<uint8_t> reported;
+    for (uint32_t s = 0; s < db->S; ++s) {
+        reported.assign(db->h_hap_off[s + 1] - db->h_hap_off[s], 0);
+        for (uint64_t c = sel->sel_off[s]; c < sel->sel_off[s + 1]; ++c) reported[sel->sel_hap[c]] = 1;
+        for (uint64_t c = sel->cand_off[s]; c < sel->cand_off[s + 1]; ++c)
+            if (reported[sel->cand_hap[c]]) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: haplotype %u of species %u is reported and a candidate", what, sel->cand_hap[c], s);
+    }
+    return 0;
+}
+
 int pantax_hip_strain_near_miss(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_near_miss_set *sel, uint64_t *cand_out, uint64_t *species_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;
     if (!db || !sel || !sel->sel_off || !sel->cand_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_near_miss: null argument");
     PTX_ENTER(ctx);
-    PTX_TRY(check_species_count(ctx, db, "strain_near_miss", sel->n_species));
-    PTX_TRY(check_hap_selection(ctx, db, "strain_near_miss", sel->sel_off, sel->sel_hap));
-    PTX_TRY(check_hap_selection(ctx, db, "strain_near_miss (candidates)", sel->cand_off, sel->cand_hap));
-    std::vector<uint8_t> reported;
-    for (uint32_t s = 0; s < db->S; ++s) {   // both sets are in range and free of repeats: are they disjoint?
-        reported.assign(db->h_hap_off[s + 1] - db->h_hap_off[s], 0);
-        for (uint64_t c = sel->sel_off[s]; c < sel->sel_off[s + 1]; ++c) reported[sel->sel_hap[c]] = 1;
-        for (uint64_t c = sel->cand_off[s]; c < sel->cand_off[s + 1]; ++c)
-            if (reported[sel->cand_hap[c]]) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_near_miss: haplotype %u of species %u is reported and a candidate", sel->cand_hap[c], s);
-    }
+    PTX_TRY(check_near_miss_set(ctx, db, "strain_near_miss", sel));
     if ((sel->cand_off[db->S] && !cand_out) || (db->S && !species_out)) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_near_miss: null output array");
     PTX_TRY(check_stage_coverage(ctx, db, "strain_near_miss"));
     return near_miss_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->cand_off, sel->cand_hap, cand_out, species_out);
+}
+
+int pantax_hip_strain_addin(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_near_miss_set *sel, double *x_out, double *obj_out, int32_t *status_out,
+                            uint64_t *rows_out, uint64_t *count_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off || !sel->cand_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_addin: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_near_miss_set(ctx, db, "strain_addin", sel));
+    // (x_out holds (J_s + 1) (K_s + J_s) doubles a species: none only when nothing is reported anywhere and there is no candidate)
+    if (((sel->sel_off[db->S] || sel->cand_off[db->S]) && !x_out) || (db->S && (!obj_out || !status_out || !rows_out || !count_out)))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_addin: null output array");
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_addin"));
+    try {
+        return addin_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->cand_off, sel->cand_hap, x_out, obj_out, status_out, rows_out, count_out);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_addin: out of host memory");
+    }
 }
 
 }  // extern "C"

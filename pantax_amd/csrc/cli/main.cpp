@@ -52,6 +52,11 @@ static void usage() {
             "  --strain-dropout F   leave-one-out test of the strain fit: for every row of strain_abundance.txt the objective of a refit of the reported strains\n"
             "                     with and without it (delta), the rows it walks, walks alone, that fit worse and better without it, and the strain that takes\n"
             "                     over its coverage (substitute); per species the rows and the objective (one rank only)\n"
+            "  --strain-addin F   add-one test of the strain fit: for the unreported haplotypes of a species that rank highest in the near-miss report the\n"
+            "                     objective of a refit of the reported strains with the candidate in the LP (gain), the coverage it gets, the rows it walks,\n"
+            "                     walks without a reported strain, that fit better and worse with it, and the reported strain it takes coverage from (donor);\n"
+            "                     per species the rows, the objective and the rows no reported strain walks (one rank only)\n"
+            "  --strain-addin-top N   candidates tested per species (default 5)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -77,10 +82,11 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
-    pantax_hip_profile_ext3 ext3;   // the outputs added behind the config's last field
-    memset(&ext3, 0, sizeof(ext3));
+    pantax_hip_profile_ext4 ext4;   // the outputs added behind the config's last field
+    memset(&ext4, 0, sizeof(ext4));
+    pantax_hip_profile_ext3 &ext3 = ext4.v3;
     pantax_hip_profile_ext2 &ext = ext3.v2;
-    ext.v1.struct_size = sizeof(ext3);
+    ext.v1.struct_size = sizeof(ext4);
     ext.strain_bootstrap_seed = 42;
     pantax_hip_db_pairs_config pairs;
     memset(&pairs, 0, sizeof(pairs));
@@ -148,6 +154,8 @@ int main(int argc, char **argv) {
         else if (a == "--strain-bootstrap-replicates") ext.strain_bootstrap_replicates = strtoull(next(), nullptr, 10);
         else if (a == "--strain-bootstrap-seed") ext.strain_bootstrap_seed = strtoull(next(), nullptr, 10);
         else if (a == "--strain-dropout") ext3.strain_dropout_file = next();
+        else if (a == "--strain-addin") ext4.strain_addin_file = next();
+        else if (a == "--strain-addin-top") ext4.strain_addin_top = strtoull(next(), nullptr, 10);
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

@@ -147,10 +147,12 @@ struct CtxConfig {
     std::string row_sort;            // "radix" / "nodes"
     std::string objective;           // "nodes": the LP objective summed over the nodes
     // "walk": the strain report takes the membership of every species from the chosen walks (the compact masks, route 2 of member_plan.hpp), not from the node -> haplotype words
-    std::string read_strain_route, evidence_route, depth_route, near_miss_route, hap_pairs_route, fit_route, bootstrap_route, dropout_route;
+    std::string read_strain_route, evidence_route, depth_route, near_miss_route, hap_pairs_route, fit_route, bootstrap_route, dropout_route, addin_route;
     uint64_t bootstrap_rows_max = 0; // expanded rows of the bootstrap replicates in flight on the device (0: from the free device memory, bootstrap_plan.hpp; tests lower it to cut the replicates into chunks)
     uint64_t dropout_patterns_max = 0; // replicated patterns of the leave-one-out rounds in flight on the device (0: from the free device memory, dropout_plan.hpp; tests lower it to cut the rounds into chunks)
     bool dropout_yardstick = false;   // measurement (tools/dropout_probe.py): pantax_hip_strain_dropout also runs boot_objective_kernel over every round's entries; nothing of it is delivered
+    uint64_t addin_patterns_max = 0;  // replicated patterns of the add-one rounds in flight on the device (0: from the free device memory, addin_plan.hpp; tests lower it to cut the rounds into chunks)
+    bool addin_yardstick = false;     // measurement (tools/addin_probe.py): pantax_hip_strain_addin also runs boot_objective_kernel over every round's entries; nothing of it is delivered
     int hap_pairs_chunk = 0;         // > 0: nodes per chunk of the pair-sum pass, in whole waves (0: by the block pair, hap_pairs_plan.hpp; tests: 64 puts a chunk border every wave)
     int depth_grid = 0;              // > 0: at most this many workgroups in the depth distribution pass (tests: 1 sends every item, and every change of species and tile, through one workgroup)
     int near_miss_words = 0;         // 1 .. 4: candidate mask words a wave of the near-miss pass counts in one pass over its nodes (0 = 4; tests: 1 sends a species of 200 haplotypes through the tiled passes)
@@ -698,6 +700,10 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
 // E_s x K_s at dropout_x_offsets, obj_out / status_out [Q], rows_out [S], count_out [Q][4]
 int dropout_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, double *x_out, double *obj_out, int32_t *status_out, uint64_t *rows_out,
                    uint64_t *count_out);
+// stage_addin.hip (pantax_hip_strain_addin): both sets validated by the caller; Q = J + S entries, entry (s, e) at cand_off[s] + s + e; x_out in blocks of
+// E_s x W_s at addin_x_offsets, obj_out / status_out [Q], rows_out [S], count_out [Q][4]
+int addin_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *cand_off, const uint32_t *cand_hap, double *x_out, double *obj_out,
+                 int32_t *status_out, uint64_t *rows_out, uint64_t *count_out);
 // stage_hap_pairs.hip: pantax_hip_db_hap_pairs behind its checks; pair_off [S+1] from hap_pairs_offsets
 int hap_pairs_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *pair_off, uint64_t *pair_out, uint64_t *species_out);
 // ... and pantax_hip_strain_pair_evidence behind its checks (coverage result resident): pair_out [..][4], species_out [S][3][4]

@@ -1,8 +1,8 @@
 // profile_reports.cpp -- the per-strain reports of the file seam (profile_reports.hpp): per group of species, behind its strain step, the group's rows of
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
-// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report and the leave-one-out
-// report, whose files are named in the seam's sized extension (EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS).
+// (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
+// report and the add-one report, whose files are named in the seam's sized extension (EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS).
 #include <algorithm>
 #include <fstream>
 #include <unordered_map>
@@ -189,30 +189,90 @@ int group_read_support(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k
     run.lap("  strain read support");
     return 0;
 }
-// --strain-near-miss, on the same coverage result: Sel_s = the group's rows; Cand_s = every other haplotype of a species of <= 64 haplotypes, of a wider
-// one the unreported haplotypes that have a unique_trio_nodes_fraction, the 256 largest (ties: lower index first) -- the cap bounds the node-mask arena
-// of the walk route at four words a node.  The candidates pantax_hip_near_miss_rank keeps are the ones printed; their `all` comes from one evidence
-// call of the group over them alone
-int group_near_miss(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+// The candidates of a group and their near-miss sums, for the near-miss report and the add-one report: Sel_s = the group's rows; Cand_s = every other
+// haplotype of a species of <= 64 haplotypes, of a wider one the unreported haplotypes that have a unique_trio_nodes_fraction, the 256 largest (ties: lower
+// index first) -- the cap bounds the node-mask arena of the walk route at four words a node.  One stage call a group, by whichever report asks first
+struct GroupCand { bool done = false; std::vector<uint64_t> off; std::vector<uint32_t> hap; std::vector<uint64_t> out /*[J][2][4]*/, species /*[Sg][3][4]*/; };
+int group_candidates(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, const ShardResult &sh, GroupCand &gc) {
     constexpr uint64_t WIDE_CAP = 256;
-    auto &nm = sh.rep.nm;
+    if (gc.done) return 0;
     const uint32_t Sg = k1 - k0;
-    std::vector<uint64_t> c_off(Sg + 1, 0);
-    std::vector<uint32_t> c_hap;
+    gc.off.assign(Sg + 1, 0);
+    gc.hap.clear();
     for (uint32_t k = k0; k < k1; ++k) {
         const uint64_t h0 = sh.hap_off[k], nh = sh.hap_off[k + 1] - h0;
-        const size_t at = c_hap.size();
+        const size_t at = gc.hap.size();
         for (uint64_t h = h0; h < h0 + nh; ++h)
-            if (!g.pass[h] && (nh <= 64 || (sh.met[h].has & PANTAX_HIP_HAS_FRACTION))) c_hap.push_back((uint32_t)(h - h0));
+            if (!g.pass[h] && (nh <= 64 || (sh.met[h].has & PANTAX_HIP_HAS_FRACTION))) gc.hap.push_back((uint32_t)(h - h0));
         if (nh > 64) {
-            std::stable_sort(c_hap.begin() + at, c_hap.end(), [&](uint32_t a, uint32_t b) { return sh.met[h0 + a].unique_trio_nodes_fraction > sh.met[h0 + b].unique_trio_nodes_fraction; });
-            if (c_hap.size() - at > WIDE_CAP) c_hap.resize(at + WIDE_CAP);
+            std::stable_sort(gc.hap.begin() + at, gc.hap.end(), [&](uint32_t a, uint32_t b) { return sh.met[h0 + a].unique_trio_nodes_fraction > sh.met[h0 + b].unique_trio_nodes_fraction; });
+            if (gc.hap.size() - at > WIDE_CAP) gc.hap.resize(at + WIDE_CAP);
         }
-        c_off[k - k0 + 1] = c_hap.size();
+        gc.off[k - k0 + 1] = gc.hap.size();
     }
-    const pantax_hip_near_miss_set set{Sg, g.off.data(), g.hap.data(), c_off.data(), c_hap.data()};
-    std::vector<uint64_t> c_out(8 * c_hap.size());
-    PTX_TRY(pantax_hip_strain_near_miss(run.ctx, db, &set, c_out.data(), nm.species.data() + 12 * (size_t)k0));
+    const pantax_hip_near_miss_set set{Sg, g.off.data(), g.hap.data(), gc.off.data(), gc.hap.data()};
+    gc.out.assign(8 * gc.hap.size(), 0);
+    gc.species.assign(12 * (size_t)Sg, 0);
+    PTX_TRY(pantax_hip_strain_near_miss(run.ctx, db, &set, gc.out.data(), gc.species.data()));
+    gc.done = true;
+    return 0;
+}
+// --strain-addin, on the same coverage result, behind the leave-one-out test: Sel_s = the group's rows (column = position: ascending haplotype); Cand_s = the
+// group's candidates in the rank order of pantax_hip_near_miss_rank, top = strain_addin_top, cut to 64 - K_s (a candidate without novel bases has no rank
+// and is not tested; a species of more than 64 rows gets no candidate and comes back beyond the limit)
+int group_addin(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh, GroupCand &gc) {
+    auto &ai = sh.rep.ai;
+    const uint32_t Sg = k1 - k0;
+    PTX_TRY(group_candidates(run, db, k0, k1, g, sh, gc));
+    std::vector<uint64_t> a_off(Sg + 1, 0);
+    std::vector<uint32_t> a_hap, rank;
+    for (uint32_t k = 0; k < Sg; ++k) {
+        const uint64_t c0 = gc.off[k], n = gc.off[k + 1] - c0, K = g.off[k + 1] - g.off[k];
+        uint32_t kept = 0;
+        rank.assign(n ? n : 1, 0);
+        if (n && K < 64) PTX_TRY(pantax_hip_near_miss_rank((uint32_t)n, gc.hap.data() + c0, gc.out.data() + 8 * c0, run.p.rep.ai_top, rank.data(), &kept));
+        kept = (uint32_t)std::min<uint64_t>(kept, K < 64 ? 64 - K : 0);
+        for (uint32_t i = 0; i < kept; ++i) a_hap.push_back(gc.hap[c0 + rank[i]]);
+        a_off[k + 1] = a_hap.size();
+    }
+    const uint64_t Q = a_hap.size() + Sg;
+    uint64_t X = 0;
+    for (uint32_t k = 0; k < Sg; ++k) { const uint64_t K = g.off[k + 1] - g.off[k], J = a_off[k + 1] - a_off[k]; X += (J + 1) * (K + J); }
+    const pantax_hip_near_miss_set set{Sg, g.off.data(), g.hap.data(), a_off.data(), a_hap.data()};
+    std::vector<double> x(X ? X : 1), obj(Q);
+    std::vector<int32_t> status(Q);
+    std::vector<uint64_t> rows(Sg), cnt(4 * Q);
+    PTX_TRY(pantax_hip_strain_addin(run.ctx, db, &set, x.data(), obj.data(), status.data(), rows.data(), cnt.data()));
+    uint64_t x0 = 0;
+    for (uint32_t k = 0; k < Sg; ++k) {
+        const uint64_t s0 = g.off[k], K = g.off[k + 1] - s0, J = a_off[k + 1] - a_off[k], W = K + J, q0 = a_off[k] + k;
+        ai.rows[k0 + k] = rows[k]; ai.obj[k0 + k] = obj[q0]; ai.status[k0 + k] = status[q0]; ai.novel[k0 + k] = cnt[4 * q0 + 1]; ai.K[k0 + k] = (uint32_t)K;
+        for (uint64_t c = 0; c < J; ++c) {
+            ReportData::AddinRow r{};
+            const double *xb = x.data() + x0, *xa = xb + (c + 1) * W;
+            double o[3] = {-1.0, 0.0, 0.0};
+            PTX_TRY(pantax_hip_addin_donor((uint32_t)W, (uint32_t)K, xb, xa, o));
+            r.hap = sh.hap_off[k0 + k] + a_hap[a_off[k] + c];
+            r.obj_with = obj[q0 + 1 + c]; r.st = status[q0 + 1 + c]; r.coverage = xa[K + c];
+            std::copy(cnt.begin() + 4 * (q0 + 1 + c), cnt.begin() + 4 * (q0 + 1 + c) + 4, r.cnt);
+            r.donor = o[0] < 0 ? -1 : (int64_t)(sh.hap_off[k0 + k] + g.hap[s0 + (uint64_t)o[0]]); r.loss = o[1]; r.shift = o[2];
+            ai.cand.push_back(r);
+        }
+        ai.row_off[k0 + k + 1] = ai.cand.size();
+        x0 += (J + 1) * W;
+    }
+    run.lap("  strain add-one");
+    return 0;
+}
+// --strain-near-miss, on the same coverage result: the candidates pantax_hip_near_miss_rank keeps are the ones printed; their `all` comes from one evidence
+// call of the group over them alone
+int group_near_miss(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh, GroupCand &gc) {
+    auto &nm = sh.rep.nm;
+    const uint32_t Sg = k1 - k0;
+    PTX_TRY(group_candidates(run, db, k0, k1, g, sh, gc));
+    const std::vector<uint64_t> &c_off = gc.off, &c_out = gc.out;
+    const std::vector<uint32_t> &c_hap = gc.hap;
+    std::copy(gc.species.begin(), gc.species.end(), nm.species.begin() + 12 * (size_t)k0);
     // the printed candidates of every species, in rank order
     std::vector<uint64_t> p_off(Sg + 1, 0);
     std::vector<uint32_t> p_hap, rank;
@@ -471,6 +531,45 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-addin (strain_taxid / genome_ID: the first genomes_info.txt row of the haplotype, of candidates and donors alike): per species of the shard, in
+    // the order it went through the device, its tested candidates in rank order: what the fit gains with the
+    // candidate, the coverage it gets and the reported strain it takes it from; then per species with rows in the table or a tested candidate the rows,
+    // the objective of the reported strains alone and the rows none of them walks ("skipped": more rows in the table than the call serves)
+    int addin() const {
+        return file(run.p.rep.ext4_path[X4REP_ADDIN],
+                    "species_taxid\tstrain_taxid\tgenome_ID\trank\tclass\tn_rows\tobjective\tobjective_with\tgain\tgain_fraction\tcoverage\tn_member\tn_novel\tn_better\tn_worse\tdonor_strain_taxid\tdonor_genome_ID\tdonor_loss\tshift\tstage\tunique_trio_nodes_fraction\n",
+                    "strain add-one report", [&](std::ofstream &f) {
+            const auto &d = rep.ai;
+            for (uint32_t k = 0; k < Su; ++k)
+                for (uint64_t i = d.row_off[k]; i < d.row_off[k + 1]; ++i) {
+                    const ReportData::AddinRow &r = d.cand[i];
+                    const GenomeRow *gr = genome_of(r.hap);
+                    const pantax_hip_hap_metrics &m = sh.met[r.hap];
+                    f << species(k) << '\t' << (gr ? gr->strain_taxid : "") << '\t' << (gr ? gr->genome_id : "") << '\t' << (i - d.row_off[k]) + 1 << "\tcandidate";
+                    if (d.status[k] != 0 || r.st != 0) {   // one of the two LPs did not solve
+                        for (int c = 0; c < 14; ++c) f << "\t-";
+                    } else {
+                        const double gain = d.obj[k] - r.obj_with;
+                        f << '\t' << d.rows[k] << '\t' << fmt_f64(d.obj[k]) << '\t' << fmt_f64(r.obj_with) << '\t' << fmt_f64(gain) << '\t'
+                          << (d.obj[k] != 0.0 ? fmt_f64(gain / d.obj[k]) : std::string("-")) << '\t' << fmt_f64(r.coverage);
+                        for (int c = 0; c < 4; ++c) f << '\t' << r.cnt[c];
+                        if (r.donor >= 0) {   // (named as the candidates are: the report does not follow the rows of the table)
+                            const GenomeRow *don = genome_of((uint64_t)r.donor);
+                            f << '\t' << (don ? don->strain_taxid : "") << '\t' << (don ? don->genome_id : "") << '\t' << fmt_f64(r.loss);
+                        } else f << "\t-\t-\t-";
+                        f << '\t' << fmt_f64(r.shift);
+                    }
+                    f << '\t' << near_miss_stage(m) << '\t' << ((m.has & PANTAX_HIP_HAS_FRACTION) ? fmt_f64(m.unique_trio_nodes_fraction) : std::string("-")) << '\n';
+                }
+            for (uint32_t k = 0; k < Su; ++k) {
+                if (d.K[k] == 0 && d.row_off[k + 1] == d.row_off[k]) continue;
+                const bool skipped = d.status[k] != 0 && d.status[k] != 1;
+                f << species_head(k) << "\t-\t" << (skipped ? "skipped" : "species") << '\t' << d.rows[k] << '\t' << (skipped ? std::string("-") : fmt_f64(d.obj[k])) << "\t-\t-\t-\t-\t-\t"
+                  << (skipped ? std::string("-") : std::to_string(d.novel[k])) << "\t-\t-\t-\t-\t-\t-\t-\t-\n";
+            }
+            return 0;
+        });
+    }
     // --strain-read-support: {compatible, unique, assigned} of every row of strain_abundance.txt, in its order; {counted, unexplained, ambiguous, uninformative}
     // of every species of the shard in the order it went through the device (a species without rows: counted only); the shared reads of every pair of rows
     int read_support() const {
@@ -613,11 +712,15 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
         rep.bs.obj.assign(rep.bs.R * Su, 0.0); rep.bs.rows.assign(rep.bs.R * Su, 0); rep.bs.status.assign(rep.bs.R * Su, 1);
     }
     if (plan.ext3_run[X3REP_DROPOUT]) { rep.dr.rows.assign(Su, 0); rep.dr.obj.assign(Su, 0.0); rep.dr.status.assign(Su, 1); rep.dr.K.assign(Su, 0); }
+    if (plan.ext4_run[X4REP_ADDIN]) {
+        rep.ai.rows.assign(Su, 0); rep.ai.novel.assign(Su, 0); rep.ai.obj.assign(Su, 0.0); rep.ai.status.assign(Su, 1); rep.ai.K.assign(Su, 0); rep.ai.row_off.assign(Su + 1, 0);
+    }
 }
 int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
     const ReportPlan &plan = run.p.rep;
     if (!plan.any_run()) return 0;
     GroupSel g;
+    GroupCand gc;
     PTX_TRY(group_select(run, k0, k1, sh, g));
     if (plan.run[REP_READ_STRAINS]) PTX_TRY(group_read_strains(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_COVERAGE]) PTX_TRY(group_cov_track(run, db, k0, k1, g, sh));
@@ -625,10 +728,11 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.ext_run[XREP_FIT]) PTX_TRY(group_fit(run, db, k0, k1, g, sh));
     if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(group_bootstrap(run, in, sn, db, k0, k1, g, sh));
     if (plan.ext3_run[X3REP_DROPOUT]) PTX_TRY(group_dropout(run, db, k0, k1, g, sh));
+    if (plan.ext4_run[X4REP_ADDIN]) PTX_TRY(group_addin(run, db, k0, k1, g, sh, gc));
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(group_pair_evidence(run, db, k0, k1, g, sh));
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
-    if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh));
+    if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh, gc));
     return 0;
 }
 int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh, const std::vector<GenomeRow> &genomes, std::vector<TrackRow> &rows) {
@@ -647,6 +751,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext_run[XREP_FIT]) PTX_TRY(w.fit());
     if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(w.bootstrap());
     if (plan.ext3_run[X3REP_DROPOUT]) PTX_TRY(w.dropout());
+    if (plan.ext4_run[X4REP_ADDIN]) PTX_TRY(w.addin());
     return 0;
 }
 }  // namespace reports

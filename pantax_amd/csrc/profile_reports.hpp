@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
-// of pantax_hip_profile_ext3 with its row of EXT3_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS and EXT2_REPORTS are closed: the structs they point into keep their size), a sub-struct
+// of pantax_hip_profile_ext4 with its row of EXT4_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS and EXT3_REPORTS are closed: the structs they point into keep their size), a sub-struct
 // here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
@@ -36,6 +36,11 @@ struct ReportData {
     // its gain, and the shift; per species k the rows, the objective and the status of the refit and K[k] = its rows of the table
     struct { std::vector<double> refit, obj_without, gain, shift, obj; std::vector<uint64_t> cnt, rows; std::vector<int32_t> st, status; std::vector<int64_t> sub;
              std::vector<uint32_t> K; } dr;
+    // --strain-addin: the tested candidates rows[row_off[k] .. row_off[k + 1]) of species k in rank order: the haplotype ([hap_names]), the objective with it,
+    // the status of its LP, its coverage, its four counts, the haplotype of its donor (-1: none) with its loss, and the shift; per species k the rows, the
+    // objective and the status of entry 0, the rows no reported strain walks and K[k] = its rows of the table
+    struct AddinRow { uint64_t hap; double obj_with, coverage, loss, shift; uint64_t cnt[4]; int32_t st; int64_t donor; };
+    struct { std::vector<AddinRow> cand; std::vector<uint64_t> row_off, rows, novel; std::vector<double> obj; std::vector<int32_t> status; std::vector<uint32_t> K; } ai;
     // --strain-read-support: hap[9e ..) = {compatible, unique, assigned}; species[12k ..) = {counted, unexplained, ambiguous, uninformative}; a species of
     // K[k] = 1..64 rows owns the K x K block of shared reads pair[pair_off[k] ..) over its entries in ascending order
     struct { std::vector<uint64_t> hap, species, pair, pair_off; std::vector<uint32_t> K; } sup;

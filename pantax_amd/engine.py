@@ -467,6 +467,31 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_near_miss(self.ctx, self.db, C.byref(cs), p(cand) if len(ch) else None, p(species) if self.S else None))
         return cand, species
 
+    def strain_addin(self, sel_off, sel_hap, cand_off, cand_hap):
+        """Add-one test of the strain fit (pantax_hip_strain_addin) on the coverage result get_node_abundances left on the device.  sel_off / sel_hap and
+        cand_off / cand_hap as for strain_near_miss.  Species s of K_s reported and J_s candidate haplotypes has W_s = K_s + J_s columns (the reported ones
+        first) and J_s + 1 entries: 0 the refit with every candidate pinned to zero, c + 1 the fit with candidate c free; entry (s, e) is
+        q = cand_off[s] + s + e -> (x: list of S float64 [J_s + 1, W_s] blocks (views of one array, x[0].base), obj float64 [Q], status int32 [Q],
+        rows uint64 [S], count uint64 [Q, 4] = n_member, n_novel, n_better, n_worse) with Q = cand_off[-1] + S."""
+        so, sh = as_c(sel_off, np.uint64), as_c(sel_hap, np.uint32)
+        co, ch = as_c(cand_off, np.uint64), as_c(cand_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]) or len(co) != self.S + 1 or len(ch) != int(co[-1]):
+            raise ValueError("strain_addin: sel_off / cand_off need S + 1 entries, sel_hap sel_off[-1] and cand_hap cand_off[-1]")
+        K, J = np.diff(so.astype(np.int64)), np.diff(co.astype(np.int64))
+        x_off = np.concatenate([[0], np.cumsum((J + 1) * (K + J))]).astype(np.int64)
+        Q = len(ch) + self.S
+        cs = _ffi.NearMissSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, co.ctypes.data, ch.ctypes.data if len(ch) else None)
+        flat = np.zeros(max(int(x_off[-1]), 1), dtype=np.float64)
+        obj = np.zeros(Q, dtype=np.float64)
+        status = np.zeros(Q, dtype=np.int32)
+        rows = np.zeros(self.S, dtype=np.uint64)
+        count = np.zeros((Q, 4), dtype=np.uint64)
+        self._check(self.lib.pantax_hip_strain_addin(self.ctx, self.db, C.byref(cs), p(flat), p(obj) if self.S else None, p(status) if self.S else None,
+                                                     p(rows) if self.S else None, p(count) if self.S else None))
+        flat = flat[:int(x_off[-1])]
+        x = [flat[int(x_off[s]):int(x_off[s + 1])].reshape(int(J[s]) + 1, int(K[s] + J[s])) for s in range(self.S)]
+        return x, obj, status, rows, count
+
     def hap_pairs(self, sel_off, sel_hap, species=True):
         """Pairwise strain distinguishability (pantax_hip_db_hap_pairs) of the resident db: no reads, no coverage pass.  sel_off [S+1], sel_hap as for
         strain_evidence (at most 256 haplotypes a species) -> (pair_off uint64 [S+1], pair uint64 [pair_off[-1], 2]: the K_s x K_s block of species s
@@ -663,7 +688,8 @@ class Engine:
                 allreduce=None, alltoallv=None, sample_test=False, solver_semantics=0, minimization_min_cov=0.0, read_strain_file=None,
                 strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
                 strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None, strain_fit_file=None,
-                strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42, strain_dropout_file=None):
+                strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42, strain_dropout_file=None,
+                strain_addin_file=None, strain_addin_top=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -675,7 +701,8 @@ class Engine:
         strain_pair_evidence_file: path of the pairwise strain evidence report (--strain-pair-evidence; one rank only).  strain_fit_file: path of the
         model fit report (--strain-fit; one rank only); given, the call goes through pantax_hip_profile_with_ext.  strain_bootstrap_file: path of the
         bootstrap report (--strain-bootstrap; one rank only), strain_bootstrap_replicates the resamples (0: 100), strain_bootstrap_seed their seed.  strain_dropout_file: path of
-        the leave-one-out report (--strain-dropout; one rank only)."""
+        the leave-one-out report (--strain-dropout; one rank only).  strain_addin_file: path of the add-one report (--strain-addin; one rank only),
+        strain_addin_top the candidates it tests per species (0: 5)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -718,12 +745,12 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
                                   strain_bootstrap_replicates=int(strain_bootstrap_replicates), strain_bootstrap_seed=int(strain_bootstrap_seed),
-                                  strain_dropout_file=enc(strain_dropout_file))
+                                  strain_dropout_file=enc(strain_dropout_file), strain_addin_file=enc(strain_addin_file), strain_addin_top=int(strain_addin_top))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -883,6 +910,19 @@ def dropout_substitute(k, x_full, x_drop):
     out = np.zeros(3, dtype=np.float64)
     if _ffi.load().pantax_hip_dropout_substitute(len(xf), int(k), p(xf), p(xd), p(out)) != 0:
         raise ValueError("dropout_substitute: refused")
+    return int(out[0]), float(out[1]), float(out[2])
+
+
+def addin_donor(K, x_base, x_add):
+    """pantax_hip_addin_donor: which reported strain gives coverage up when a candidate enters.  x_base / x_add float64 [W]: the x of entry 0 and of the
+    candidate's entry, the first K columns the reported ones -> (donor column or -1, its loss, shift = the L1 distance of the two solutions over the
+    reported columns)."""
+    xb, xa = as_c(x_base, np.float64), as_c(x_add, np.float64)
+    if xb.ndim != 1 or xb.shape != xa.shape:
+        raise ValueError("addin_donor: x_base and x_add are one-dimensional and of one length")
+    out = np.zeros(3, dtype=np.float64)
+    if _ffi.load().pantax_hip_addin_donor(len(xb), int(K), p(xb), p(xa), p(out)) != 0:
+        raise ValueError("addin_donor: refused")
     return int(out[0]), float(out[1]), float(out[2])
 
 
