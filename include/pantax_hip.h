@@ -243,6 +243,52 @@ int pantax_hip_strain_read_support(pantax_hip_ctx *ctx, pantax_hip_db *db, panta
                                    uint64_t *species_out /*[S][4][3]: counted, unexplained, ambiguous, uninformative*/,
                                    uint64_t *pair_off_out /*[S+1]*/, uint64_t pair_cap /* entries pair_out holds */, uint64_t *pair_out);
 
+/* ---- read classes and the read-based estimate (the --strain-em report; not a stage of the reference): the reads of a species grouped by the set of
+ * candidate strains they are compatible with, and a depth per candidate from EM over those groups -- an estimate that does not come from the LP.  A counted
+ * read, N(r), C(r), Q(r) = (1, n_steps, span) and the state rules are exactly those of pantax_hip_strain_read_support above.  The candidate set is a
+ * pantax_hip_read_strain_set with cand_len (the graph bases G of the candidate, u64) in place of the weights, max_iter >= 1 and tol >= 0, finite (else
+ * PANTAX_HIP_E_INVALID).
+ *   Canonical order: the candidates of a species are taken in ascending haplotype index, whatever the caller's order; bit i of a class mask is the candidate
+ *   with the i-th smallest haplotype index.  The caller's order decides only where a candidate's x lands in x_out.
+ *   Read classes, for a species of 1 <= K_s <= 64: a class is a distinct non-zero mask m = C(r) with the u64 sums of Q(r) over its reads; classes are listed
+ *   in ascending mask (unsigned), species after species.  species_out [S][2][3] = counted and unexplained (C(r) empty) as in read support, both also written
+ *   for K_s = 0 (unexplained = 0 there).  Integers only: exact and independent of any order.  K_s > 64: the species is skipped -- no classes, no estimate,
+ *   x = 0; the call still succeeds and counted is still written.
+ *   Sizing: cls_off_out [S+1] is always written.  cls_mask_out [cls_off[S]] and cls_q_out [cls_off[S]][3] are written when cls_cap holds them; cls_cap > 0
+ *   but too small: PANTAX_HIP_E_LIMIT with nothing else touched; cls_cap = 0 (the arrays may be null) is fine: a caller that only wants the estimate, or
+ *   wants to size the arrays, calls it this way.
+ *   The estimate, per species over its classes j = 0 .. J-1 in that order, b_j = span of class j, G_k = cand_len of the candidate at bit k, in f64 with IEEE
+ *   add, mul, div and u64 -> f64 conversion only (no contraction, no reassociation):
+ *     x_k = 1.0 if G_k > 0 else 0.0
+ *     for t = 1 .. max_iter:
+ *       D_j = sum of x_k over the set bits k of m_j, ascending k, from 0.0;      r_j = (double)b_j / D_j if D_j > 0.0, else 0.0
+ *       R_k = sum of r_j over the classes j with bit k set, ascending j, from 0.0
+ *       y_k = (x_k * R_k) / (double)G_k;  0.0 if G_k == 0;  0.0 if y_k < 1e-200
+ *       delta = max_k |y_k - x_k|;  top = max_k y_k;  x = y;  n_iter = t;  if delta <= tol * top: converged = 1, stop
+ *   This is the EM of the Poisson model "class j collects bases at rate sum_{k in m_j} x_k, strain k spreads over G_k bases"; its fixed point maximises
+ *   sum_j b_j log D_j - sum_k G_k x_k, and identical strains get equal depth.  The 1e-200 floor keeps the iteration out of denormals; it is part of the
+ *   contract.  x_out [C] in the caller's order, iter_out / converged_out / delta_out [S]; a species of K_s = 0, a skipped one or one without classes gets
+ *   zeros and n_iter = 0.  The same inputs give the same bits, whatever the membership route (option read_strain_route=walk), the table size (option
+ *   read_class_slots) and where the classes are kept (option read_em_lds_classes). */
+typedef struct {
+    uint32_t n_species;         /* must equal the db's */
+    const uint64_t *cand_off;   /* [S+1] */
+    const uint32_t *cand_hap;   /* [C] species-local haplotype index (any order, no repeats) */
+    const uint64_t *cand_len;   /* [C] graph bases of the candidate, G */
+    uint32_t max_iter;          /* >= 1 */
+    double tol;                 /* >= 0, finite */
+} pantax_hip_read_em_set;
+int pantax_hip_strain_read_em(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_em_set *cand,
+                              uint64_t *species_out /*[S][2][3]: counted, unexplained*/, uint64_t *cls_off_out /*[S+1]*/,
+                              uint64_t cls_cap /* classes cls_mask_out and cls_q_out hold */, uint64_t *cls_mask_out, uint64_t *cls_q_out /*[][3]*/,
+                              double *x_out /*[C]*/, uint32_t *iter_out /*[S]*/, int32_t *converged_out /*[S]*/, double *delta_out /*[S]*/);
+/* host helper, no ctx and no GPU: the estimate above for one species.  mask / b [J] in ascending mask, len [K] in canonical order, K <= 64, every mask over
+ * the K low bits; x_out [K].  The same arithmetic, compiled with contraction off: equal to the device bit for bit.  It follows the iteration as written also
+ * for J = 0 (zeros after two iterations).  PANTAX_HIP_E_INVALID for a null argument, K > 64, max_iter = 0, a tol that is negative or not finite, a mask bit
+ * at or above K. */
+int pantax_hip_read_em(uint32_t K, uint64_t J, const uint64_t *mask, const uint64_t *b, const uint64_t *len, uint32_t max_iter, double tol, double *x_out,
+                       uint32_t *n_iter_out, int32_t *converged_out, double *delta_out);
+
 /* ---- per-strain coverage track (the --strain-coverage report; not a stage of the reference): coverage along the genome of selected haplotypes,
  * in windows of W bases, from what pantax_hip_node_coverage leaves on the device.  For a species s, a species-local haplotype h and W >= 1:
  *   v_0 .. v_{n-1} = the walk of h as global node indices (a node visited twice counts at both visits);
@@ -920,6 +966,28 @@ typedef struct {
     const char *strain_addin_file;
     uint64_t strain_addin_top;   /* candidates tested per species: 0 reads as 5, and so does a struct that does not hold the field */
 } pantax_hip_profile_ext4;
+/* ... and once more: pantax_hip_profile_ext4 is closed at strain_addin_top (a committed host check holds its 64 bytes); the outputs behind it are the fields
+ * of the struct below, which begins with the fourth version.  A caller fills v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext5) and passes
+ * &ext5.v4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40-, 48- or 64-byte struct runs with the fields below off.  A later output is a
+ * field appended here. */
+typedef struct {
+    pantax_hip_profile_ext4 v4;   /* v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext5) */
+    /* --strain-em: path of the read class report (pantax_hip_strain_read_em over every group of species, right behind the group's read support call; NULL,
+     * "" or "None" = off).  Candidates = the species' rows of strain_abundance.txt; G = the len of the strain's `all` class of pantax_hip_strain_evidence
+     * (the distinct nodes it walks; the seam makes that call for this report too when strain_evidence_file is off); max_iter = strain_em_iterations,
+     * tol = 1e-6.  TSV with a header: species_taxid, strain_taxid, genome_ID, class, rank, n_members, members, n_reads, n_steps, span, share, len,
+     * em_coverage, em_bases, em_share, predicted_coverage, n_classes, n_iter, converged, delta; f64 in shortest round-trip digits, "-" where a column does
+     * not apply.  First the strains in the order of strain_abundance.txt, class "strain": n_reads, n_steps, span summed over the classes that hold the
+     * strain (= compatible of read support), len = G, em_coverage = x, em_bases = x * G, em_share = em_bases / the sum of em_bases over the species'
+     * strains in ascending haplotype index ("-" when that is 0), predicted_coverage unrounded.  Then per species in the order it went through the device:
+     * class "read_class", the first strain_em_classes classes by span descending, ties by mask ascending: rank from 1, n_members = the popcount, members =
+     * the genome_IDs joined by "," in ascending haplotype index, share = span / the counted span ("-" when that is 0);  class "other", one row when the
+     * species has more classes than printed, holding their sums (n_members = how many);  class "unexplained";  class "species" ("skipped" for more than 64
+     * rows in the table): counted, n_classes, n_iter, converged, delta.  Same rules as strain_fit_file. */
+    const char *strain_em_file;
+    uint64_t strain_em_classes;      /* classes printed per species: 0 reads as 10, and so does a struct that does not hold the field */
+    uint64_t strain_em_iterations;   /* max_iter: 0 reads as 1000, and so does a struct that does not hold the field; cut to 2^32 - 1 */
+} pantax_hip_profile_ext5;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

@@ -27,7 +27,7 @@ SYMBOLS = [
     "pantax_hip_depth_bin", "pantax_hip_depth_bin_range", "pantax_hip_depth_quantile", "pantax_hip_strain_near_miss", "pantax_hip_near_miss_rank",
     "pantax_hip_db_hap_pairs", "pantax_hip_db_pairs", "pantax_hip_strain_pair_evidence", "pantax_hip_strain_fit", "pantax_hip_profile_with_ext",
     "pantax_hip_strain_bootstrap", "pantax_hip_bootstrap_weight", "pantax_hip_bootstrap_summary", "pantax_hip_strain_dropout", "pantax_hip_dropout_substitute",
-    "pantax_hip_strain_addin", "pantax_hip_addin_donor",
+    "pantax_hip_strain_addin", "pantax_hip_addin_donor", "pantax_hip_strain_read_em", "pantax_hip_read_em",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -122,6 +122,11 @@ class ReadStrainSet(C.Structure):
     _fields_ = [("n_species", C.c_uint32), ("cand_off", C.c_void_p), ("cand_hap", C.c_void_p), ("cand_w", C.c_void_p)]
 
 
+class ReadEmSet(C.Structure):
+    _fields_ = [("n_species", C.c_uint32), ("cand_off", C.c_void_p), ("cand_hap", C.c_void_p), ("cand_len", C.c_void_p), ("max_iter", C.c_uint32),
+                ("tol", C.c_double)]
+
+
 class CovTrackSet(C.Structure):
     _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p), ("window", C.c_uint64)]
 
@@ -135,11 +140,13 @@ class FitSet(C.Structure):
 
 
 class ProfileExt(C.Structure):
-    """pantax_hip_profile_ext4 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
-    behind it (40 bytes), strain_dropout_file (48) and the two fields of pantax_hip_profile_ext4 (64); struct_size = ctypes.sizeof(ProfileExt)"""
+    """pantax_hip_profile_ext5 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
+    behind it (40 bytes), strain_dropout_file (48), the two fields of pantax_hip_profile_ext4 (64) and the three of pantax_hip_profile_ext5 (88);
+    struct_size = ctypes.sizeof(ProfileExt)"""
     _fields_ = [("struct_size", C.c_uint64), ("strain_fit_file", C.c_char_p), ("strain_bootstrap_file", C.c_char_p),
                 ("strain_bootstrap_replicates", C.c_uint64), ("strain_bootstrap_seed", C.c_uint64), ("strain_dropout_file", C.c_char_p),
-                ("strain_addin_file", C.c_char_p), ("strain_addin_top", C.c_uint64)]
+                ("strain_addin_file", C.c_char_p), ("strain_addin_top", C.c_uint64),
+                ("strain_em_file", C.c_char_p), ("strain_em_classes", C.c_uint64), ("strain_em_iterations", C.c_uint64)]
 
 
 class BootstrapSet(C.Structure):
@@ -217,6 +224,12 @@ def load():
         _lib.pantax_hip_strain_addin.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(NearMissSet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.pantax_hip_addin_donor.restype = C.c_int
         _lib.pantax_hip_addin_donor.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_strain_read_em.restype = C.c_int
+        _lib.pantax_hip_strain_read_em.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReadEmSet), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_read_em.restype = C.c_int
+        _lib.pantax_hip_read_em.argtypes = [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_double)]
         _lib.pantax_hip_profile_with_ext.restype = C.c_int
         _lib.pantax_hip_profile_with_ext.argtypes = [C.c_void_p, C.POINTER(ProfilingConfig), C.POINTER(ProfileExt)]
         _lib.pantax_hip_db_pairs.restype = C.c_int

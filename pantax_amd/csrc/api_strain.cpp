@@ -459,10 +459,10 @@ int pantax_hip_pao_solve(pantax_hip_ctx *ctx, uint32_t n_nodes, const int64_t *n
     return 0;
 }
 
-// what the two passes over the reads' candidate masks share: the state they need, a candidate set in range and without repeats -> every species'
+// what the three passes over the reads' candidate masks (read strains, read support, read classes) share: the state they need, a candidate set in range and without repeats -> every species'
 // candidates in ascending haplotype order (bit order = the order of the sum and of the tie rule), ord[c] = the caller's entry of sorted candidate c
 static int check_read_strain_set(pantax_hip_ctx *ctx, const pantax_hip_db *db, const pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
-                                 const char *what, std::vector<uint32_t> &hap, std::vector<double> &w, std::vector<uint64_t> &ord_all) {
+                                 const char *what, std::vector<uint32_t> &hap, std::vector<double> &w, std::vector<uint64_t> &ord_all, bool need_w = true) {
     const uint32_t S = db->S;
     if (cand->n_species != S) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: the candidate set has %u species, the db %u", what, cand->n_species, S);
     if (!reads->state.binned_against(db->uid) || !reads->state.grouped())
@@ -474,7 +474,7 @@ static int check_read_strain_set(pantax_hip_ctx *ctx, const pantax_hip_db *db, c
     for (uint32_t s = 0; s < S; ++s)
         if (cand->cand_off[s + 1] < cand->cand_off[s]) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: cand_off decreases at species %u", what, s);
     const uint64_t C = cand->cand_off[S];
-    if (C && (!cand->cand_hap || !cand->cand_w)) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: null cand_hap / cand_w", what);
+    if (C && (!cand->cand_hap || (need_w && !cand->cand_w))) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: null cand_hap / cand_w", what);
     hap.resize(C); w.resize(C); ord_all.resize(C);
     std::vector<uint64_t> ord;
     for (uint32_t s = 0; s < S; ++s) {
@@ -489,7 +489,7 @@ static int check_read_strain_set(pantax_hip_ctx *ctx, const pantax_hip_db *db, c
             if (i && cand->cand_hap[ord[i]] == cand->cand_hap[ord[i - 1]])
                 return fail(ctx, PANTAX_HIP_E_INVALID, "%s: haplotype %u of species %u is a candidate twice", what, cand->cand_hap[ord[i]], s);
             hap[c0 + i] = cand->cand_hap[ord[i]];
-            w[c0 + i] = cand->cand_w[ord[i]];
+            w[c0 + i] = cand->cand_w ? cand->cand_w[ord[i]] : 0.0;   // (the read classes take a set without weights)
             ord_all[c0 + i] = ord[i];
         }
     }
@@ -529,6 +529,31 @@ int pantax_hip_strain_read_support(pantax_hip_ctx *ctx, pantax_hip_db *db, panta
     if ((cand->cand_off[S] && !hap_out) || (S && !species_out) || (pair_off_out[S] && !pair_out))
         return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_support: null output array");
     return read_support_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), ord.data(), pair_off_out, hap_out, species_out, pair_out);
+}
+
+int pantax_hip_strain_read_em(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_em_set *cand, uint64_t *species_out,
+                              uint64_t *cls_off_out, uint64_t cls_cap, uint64_t *cls_mask_out, uint64_t *cls_q_out, double *x_out, uint32_t *iter_out,
+                              int32_t *converged_out, double *delta_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !reads || !cand || !cand->cand_off || !cls_off_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_em: null argument");
+    PTX_ENTER(ctx);
+    if (cand->max_iter == 0 || !(cand->tol >= 0.0) || !std::isfinite(cand->tol))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_em: max_iter %u, tol %g (at least one iteration; tol finite and >= 0)", cand->max_iter, cand->tol);
+    // the set of the read passes with lengths in place of the weights: the same checks, the same canonical order
+    const pantax_hip_read_strain_set set{cand->n_species, cand->cand_off, cand->cand_hap, nullptr};
+    std::vector<uint32_t> hap;
+    std::vector<double> w;
+    std::vector<uint64_t> ord;
+    PTX_TRY(check_read_strain_set(ctx, db, reads, &set, "strain_read_em", hap, w, ord, /*need_w=*/false));
+    const uint32_t S = db->S;
+    const uint64_t C = cand->cand_off[S];
+    if (C && !cand->cand_len) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_em: null cand_len");
+    if ((C && !x_out) || (S && (!species_out || !iter_out || !converged_out || !delta_out)) || (cls_cap && (!cls_mask_out || !cls_q_out)))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_em: null output array");
+    std::vector<uint64_t> len(C ? C : 1);
+    for (uint64_t c = 0; c < C; ++c) len[c] = cand->cand_len[ord[c]];
+    return read_em_launch(ctx, db, reads, cand->cand_off, hap.data(), len.data(), ord.data(), cand->max_iter, cand->tol, species_out, cls_off_out, cls_cap, cls_mask_out,
+                          cls_q_out, x_out, iter_out, converged_out, delta_out);
 }
 
 // what the two node reports behind the coverage pass share: the db's species count (checked first, as before the window of the track), a selection of

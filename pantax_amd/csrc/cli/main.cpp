@@ -57,6 +57,10 @@ static void usage() {
             "                     walks without a reported strain, that fit better and worse with it, and the reported strain it takes coverage from (donor);\n"
             "                     per species the rows, the objective and the rows no reported strain walks (one rank only)\n"
             "  --strain-addin-top N   candidates tested per species (default 5)\n"
+            "  --strain-em F      read classes and a read-based estimate: the reads of a species grouped by the set of reported strains they are compatible\n"
+            "                     with (reads, steps and aligned bases per set), and per row of strain_abundance.txt the depth that EM over those sets gives\n"
+            "                     it, beside predicted_coverage; per species the unexplained reads and the iterations (one rank only)\n"
+            "  --strain-em-classes N   sets printed per species, by bases (default 10)     --strain-em-iterations N   EM iterations at most (default 1000)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -82,11 +86,12 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
-    pantax_hip_profile_ext4 ext4;   // the outputs added behind the config's last field
-    memset(&ext4, 0, sizeof(ext4));
+    pantax_hip_profile_ext5 ext5;   // the outputs added behind the config's last field
+    memset(&ext5, 0, sizeof(ext5));
+    pantax_hip_profile_ext4 &ext4 = ext5.v4;
     pantax_hip_profile_ext3 &ext3 = ext4.v3;
     pantax_hip_profile_ext2 &ext = ext3.v2;
-    ext.v1.struct_size = sizeof(ext4);
+    ext.v1.struct_size = sizeof(ext5);
     ext.strain_bootstrap_seed = 42;
     pantax_hip_db_pairs_config pairs;
     memset(&pairs, 0, sizeof(pairs));
@@ -156,6 +161,9 @@ int main(int argc, char **argv) {
         else if (a == "--strain-dropout") ext3.strain_dropout_file = next();
         else if (a == "--strain-addin") ext4.strain_addin_file = next();
         else if (a == "--strain-addin-top") ext4.strain_addin_top = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-em") ext5.strain_em_file = next();
+        else if (a == "--strain-em-classes") ext5.strain_em_classes = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-em-iterations") ext5.strain_em_iterations = strtoull(next(), nullptr, 10);
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

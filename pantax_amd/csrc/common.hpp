@@ -153,6 +153,8 @@ struct CtxConfig {
     bool dropout_yardstick = false;   // measurement (tools/dropout_probe.py): pantax_hip_strain_dropout also runs boot_objective_kernel over every round's entries; nothing of it is delivered
     uint64_t addin_patterns_max = 0;  // replicated patterns of the add-one rounds in flight on the device (0: from the free device memory, addin_plan.hpp; tests lower it to cut the rounds into chunks)
     bool addin_yardstick = false;     // measurement (tools/addin_probe.py): pantax_hip_strain_addin also runs boot_objective_kernel over every round's entries; nothing of it is delivered
+    uint64_t read_class_slots = 0;    // pantax_hip_strain_read_em: the cap in "slots of a species' class table = the power of two >= 2 min(2^K - 1, cap)" on the first pass (0: 2048, read_em_plan.hpp; tests lower it to force growth reruns)
+    int read_em_lds_classes = 0;      // > 0: classes of a species whose (mask, r) the estimate keeps in LDS, at most 2048 (0 = 2048; tests lower it to send a species through global memory)
     int hap_pairs_chunk = 0;         // > 0: nodes per chunk of the pair-sum pass, in whole waves (0: by the block pair, hap_pairs_plan.hpp; tests: 64 puts a chunk border every wave)
     int depth_grid = 0;              // > 0: at most this many workgroups in the depth distribution pass (tests: 1 sends every item, and every change of species and tile, through one workgroup)
     int near_miss_words = 0;         // 1 .. 4: candidate mask words a wave of the near-miss pass counts in one pass over its nodes (0 = 4; tests: 1 sends a species of 200 haplotypes through the tiled passes)
@@ -689,6 +691,11 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
 // sorted candidate c, pair_off [S+1]; all validated by the caller.  hap_out [C][3][3] in the caller's order, species_out [S][4][3], pair_out [pair_off[S]]
 int read_support_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, const uint64_t *entry_of,
                         const uint64_t *pair_off, uint64_t *hap_out, uint64_t *species_out, uint64_t *pair_out);
+// stage_read_em.hip (pantax_hip_strain_read_em): candidates of every species in ascending haplotype order with their lengths, entry_of[c] = the caller's entry
+// of sorted candidate c; all validated by the caller.  Outputs as the stage call's; they are written only when the call succeeds (cls_off_out: also on E_LIMIT)
+int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const uint64_t *cand_len, const uint64_t *entry_of, uint32_t max_iter,
+                   double tol, uint64_t *species_out, uint64_t *cls_off_out, uint64_t cls_cap, uint64_t *cls_mask_out, uint64_t *cls_q_out, double *x_out, uint32_t *iter_out,
+                   int32_t *converged_out, double *delta_out);
 // stage_evidence.hip (pantax_hip_strain_evidence): selection validated by the caller; hap_out [C][2][4], species_out [S][3][4]
 int evidence_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t *hap_out, uint64_t *species_out);
 // stage_fit.hip (pantax_hip_strain_fit): selection and weights validated by the caller; hap_out [C][2][8], species_out [S][3][8]

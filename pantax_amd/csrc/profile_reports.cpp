@@ -2,12 +2,13 @@
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
 // (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
-// report and the add-one report, whose files are named in the seam's sized extension (EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS).
+// report, the add-one report and the read class report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT5_REPORTS).
 #include <algorithm>
 #include <fstream>
 #include <unordered_map>
 #include "hap_pairs_plan.hpp"
 #include "profile_run.hpp"
+#include "read_em_plan.hpp"
 
 namespace ptx {
 namespace {
@@ -187,6 +188,42 @@ int group_read_support(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k
                                            sup.pair.data() + pair0));
     for (uint32_t k = 0; k < Sg; ++k) sup.pair_off[k0 + k] = pair0 + p_off[k];
     run.lap("  strain read support");
+    return 0;
+}
+// --strain-em, right behind the read support call: the candidates of group_read_strains with G = the len of the strain's `all` class of the node evidence
+// (the evidence report's when it runs, else a call of its own) in place of the weights; max_iter from the plan, tol 1e-6
+int group_read_em(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &em = sh.rep.em;
+    const uint32_t Sg = k1 - k0;
+    const size_t C = g.hap.size();
+    std::vector<uint64_t> own_hap, own_species;
+    const uint64_t *ev = nullptr;                                          // [C][2][4] of this group's entries
+    if (run.p.rep.run[REP_EVIDENCE]) ev = sh.rep.ev.hap.data() + 2 * EVIDENCE_N * g.entry0;
+    else {
+        const pantax_hip_evidence_set set{Sg, g.off.data(), g.hap.data()};
+        own_hap.assign(2 * EVIDENCE_N * (C ? C : 1), 0); own_species.assign(3 * EVIDENCE_N * (size_t)Sg, 0);
+        PTX_TRY(pantax_hip_strain_evidence(run.ctx, db, &set, own_hap.data(), own_species.data()));
+        ev = own_hap.data();
+    }
+    em.len.resize(g.entry0 + C); em.x.resize(g.entry0 + C, 0.0);
+    for (size_t c = 0; c < C; ++c) em.len[g.entry0 + c] = ev[2 * EVIDENCE_N * c + 1];
+    const pantax_hip_read_em_set cs{Sg, g.off.data(), g.hap.data(), em.len.data() + g.entry0, run.p.rep.em_iterations, 1e-6};
+    std::vector<uint64_t> c_off(Sg + 1, 0), c_mask, c_q;
+    uint64_t cap = 4096;
+    for (;;) {   // a second call only when the group has more classes than the first guess holds: c_off then says how many
+        c_mask.assign(cap, 0); c_q.assign(3 * cap, 0);
+        const int rc = pantax_hip_strain_read_em(run.ctx, db, in.reads.rd, &cs, em.species.data() + 6 * (size_t)k0, c_off.data(), cap, c_mask.data(), c_q.data(),
+                                                 em.x.data() + g.entry0, em.iter.data() + k0, em.conv.data() + k0, em.delta.data() + k0);
+        if (rc == PANTAX_HIP_E_LIMIT && c_off[Sg] > cap) { cap = c_off[Sg]; continue; }
+        if (rc != 0) return rc;
+        break;
+    }
+    for (uint32_t k = 0; k < Sg; ++k) {
+        em.K[k0 + k] = (uint32_t)(g.off[k + 1] - g.off[k]);
+        for (uint64_t j = c_off[k]; j < c_off[k + 1]; ++j) em.cls.push_back(ReportData::EmClass{c_mask[j], {c_q[3 * j], c_q[3 * j + 1], c_q[3 * j + 2]}});
+        em.cls_off[k0 + k + 1] = em.cls.size();
+    }
+    run.lap("  strain read classes");
     return 0;
 }
 // The candidates of a group and their near-miss sums, for the near-miss report and the add-one report: Sel_s = the group's rows; Cand_s = every other
@@ -610,6 +647,73 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-em: the estimate beside predicted_coverage for every row of strain_abundance.txt, in its order; then per species of the shard in the order it
+    // went through the device its largest classes, the rest of them in one row, the unexplained reads and the species row
+    int read_em() const {
+        const auto &em = rep.em;
+        return file(run.p.rep.ext5_path[X5REP_EM],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tclass\trank\tn_members\tmembers\tn_reads\tn_steps\tspan\tshare\tlen\tem_coverage\tem_bases\tem_share\tpredicted_coverage\tn_classes\tn_iter\tconverged\tdelta\n",
+                    "strain read class report", [&](std::ofstream &f) {
+            std::vector<const TrackRow *> row_of(em.x.size(), nullptr);   // entry -> its first row of the table
+            std::vector<int64_t> e0(Su, -1);                              // the species' entries are consecutive, in ascending haplotype index: bit i = entry e0 + i
+            std::vector<double> total(Su, 0.0);                           // the sum of em_bases over the species' strains, in that order
+            for (uint32_t k = 0; k < Su; ++k) {
+                for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1] && e0[k] < 0; ++h) e0[k] = rep.entry[h];
+                for (uint32_t i = 0; e0[k] >= 0 && i < em.K[k]; ++i) total[k] += em.x[e0[k] + i] * (double)em.len[e0[k] + i];
+            }
+            const auto served = [&](uint32_t k) { return em.K[k] >= 1 && em.K[k] <= READ_EM_MAX_K; };
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "read classes", &e));
+                if (!row_of[e]) row_of[e] = &r;
+                f << strain_head(r) << "\tstrain\t-\t-\t-";
+                if (served(r.k)) {
+                    uint64_t q[3] = {0, 0, 0};
+                    const uint64_t bit = (uint64_t)(e - e0[r.k]);
+                    for (uint64_t j = em.cls_off[r.k]; j < em.cls_off[r.k + 1]; ++j)
+                        if ((em.cls[j].mask >> bit) & 1ull) for (int c = 0; c < 3; ++c) q[c] += em.cls[j].q[c];
+                    const double bases = em.x[e] * (double)em.len[e];
+                    f << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << "\t-\t" << em.len[e] << '\t' << fmt_f64(em.x[e]) << '\t' << fmt_f64(bases) << '\t'
+                      << (total[r.k] != 0.0 ? fmt_f64(bases / total[r.k]) : std::string("-"));
+                } else f << "\t-\t-\t-\t-\t" << em.len[e] << "\t-\t-\t-";
+                f << '\t' << fmt_f64(sh.met[r.hap].second_sol) << "\t-\t-\t-\t-\n";
+            }
+            const auto frac = [](uint64_t n, uint64_t of) { return of ? fmt_f64((double)n / (double)of) : std::string("-"); };
+            for (uint32_t k = 0; k < Su; ++k) {
+                const std::string head = species_head(k);
+                const uint64_t *sp = em.species.data() + 6 * (size_t)k;
+                const uint64_t J = em.cls_off[k + 1] - em.cls_off[k];
+                const ReportData::EmClass *cls = em.cls.data() + em.cls_off[k];
+                std::vector<uint64_t> mask(J), span(J);
+                for (uint64_t j = 0; j < J; ++j) { mask[j] = cls[j].mask; span[j] = cls[j].q[2]; }
+                const std::vector<uint64_t> top = read_class_rank(J, mask.data(), span.data(), run.p.rep.em_classes);
+                std::vector<uint8_t> printed(J, 0);
+                for (size_t i = 0; i < top.size(); ++i) {
+                    const ReportData::EmClass &c = cls[top[i]];
+                    printed[top[i]] = 1;
+                    f << head << "\tread_class\t" << i + 1 << '\t' << __builtin_popcountll(c.mask) << '\t';
+                    bool first = true;
+                    for (uint64_t m = c.mask; m; m &= m - 1ull) {
+                        const int64_t e = e0[k] + __builtin_ctzll(m);
+                        if (!first) f << ',';
+                        first = false;
+                        if (e0[k] >= 0 && (size_t)e < row_of.size() && row_of[e] && row_of[e]->gr) f << row_of[e]->gr->genome_id;
+                    }
+                    f << '\t' << c.q[0] << '\t' << c.q[1] << '\t' << c.q[2] << '\t' << frac(c.q[2], sp[2]) << "\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+                }
+                if (J > top.size()) {
+                    uint64_t q[3] = {0, 0, 0};
+                    for (uint64_t j = 0; j < J; ++j)
+                        if (!printed[j]) for (int c = 0; c < 3; ++c) q[c] += cls[j].q[c];
+                    f << head << "\tother\t-\t" << J - top.size() << "\t-\t" << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << frac(q[2], sp[2]) << "\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+                }
+                f << head << "\tunexplained\t-\t-\t-\t" << sp[3] << '\t' << sp[4] << '\t' << sp[5] << '\t' << frac(sp[5], sp[2]) << "\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+                f << head << '\t' << (em.K[k] > READ_EM_MAX_K ? "skipped" : "species") << "\t-\t-\t-\t" << sp[0] << '\t' << sp[1] << '\t' << sp[2] << "\t-\t-\t-\t-\t-\t-";
+                if (em.K[k] > READ_EM_MAX_K) f << "\t-\t-\t-\t-\n";
+                else f << '\t' << J << '\t' << em.iter[k] << '\t' << em.conv[k] << '\t' << fmt_f64(em.delta[k]) << '\n';
+            }
+            return 0;
+        });
+    }
     // --strain-depth: per histogram of every class its node count, its length, the length at depth 0 and the length-weighted quantiles
     int depth() const {
         return file(REP_DEPTH, "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_nodes\tlen\tlen_zero\tq05\tq25\tq50\tq75\tq95\tq50_hi\tpredicted_coverage\n", "strain depth report", [&](std::ofstream &f) {
@@ -715,6 +819,9 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.ext4_run[X4REP_ADDIN]) {
         rep.ai.rows.assign(Su, 0); rep.ai.novel.assign(Su, 0); rep.ai.obj.assign(Su, 0.0); rep.ai.status.assign(Su, 1); rep.ai.K.assign(Su, 0); rep.ai.row_off.assign(Su + 1, 0);
     }
+    if (plan.ext5_run[X5REP_EM]) {
+        rep.em.species.assign(6 * (size_t)Su, 0); rep.em.cls_off.assign(Su + 1, 0); rep.em.K.assign(Su, 0); rep.em.iter.assign(Su, 0); rep.em.conv.assign(Su, 0); rep.em.delta.assign(Su, 0.0);
+    }
 }
 int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
     const ReportPlan &plan = run.p.rep;
@@ -731,6 +838,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.ext4_run[X4REP_ADDIN]) PTX_TRY(group_addin(run, db, k0, k1, g, sh, gc));
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(group_pair_evidence(run, db, k0, k1, g, sh));
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
+    if (plan.ext5_run[X5REP_EM]) PTX_TRY(group_read_em(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh, gc));
     return 0;
@@ -752,6 +860,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(w.bootstrap());
     if (plan.ext3_run[X3REP_DROPOUT]) PTX_TRY(w.dropout());
     if (plan.ext4_run[X4REP_ADDIN]) PTX_TRY(w.addin());
+    if (plan.ext5_run[X5REP_EM]) PTX_TRY(w.read_em());
     return 0;
 }
 }  // namespace reports

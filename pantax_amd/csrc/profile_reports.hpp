@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
-// of pantax_hip_profile_ext4 with its row of EXT4_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS and EXT3_REPORTS are closed: the structs they point into keep their size), a sub-struct
+// of pantax_hip_profile_ext5 with its row of EXT5_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS and EXT4_REPORTS are closed: the structs they point into keep their size), a sub-struct
 // here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
@@ -44,6 +44,10 @@ struct ReportData {
     // --strain-read-support: hap[9e ..) = {compatible, unique, assigned}; species[12k ..) = {counted, unexplained, ambiguous, uninformative}; a species of
     // K[k] = 1..64 rows owns the K x K block of shared reads pair[pair_off[k] ..) over its entries in ascending order
     struct { std::vector<uint64_t> hap, species, pair, pair_off; std::vector<uint32_t> K; } sup;
+    // --strain-em: per entry e its G and its x; per species k {counted, unexplained} in species[6k ..), its classes cls[cls_off[k] .. cls_off[k + 1]) in ascending
+    // mask (bit i = the species' i-th entry), the iterations, converged and delta of its estimate and K[k] = its rows of the table
+    struct EmClass { uint64_t mask, q[3]; };
+    struct { std::vector<uint64_t> len, species, cls_off; std::vector<double> x, delta; std::vector<EmClass> cls; std::vector<uint32_t> K, iter; std::vector<int32_t> conv; } em;
     // --strain-near-miss: species[12k ..) = {orphan, claimed, contested}; the printed candidates rows[row_off[k] .. row_off[k + 1]) in rank order: the
     // haplotype ([hap_names]) and q = {novel, exclusive, all} x {n_nodes, len, covered, bases}
     struct NearMissRow { uint64_t hap; uint64_t q[12]; };

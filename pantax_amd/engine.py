@@ -344,6 +344,39 @@ class Engine:
                                                             p(species) if self.S else None, p(pair_off), len(pair), p(pair) if len(pair) else None))
         return hap, species, pair_off, pair
 
+    def strain_read_em(self, cand_off, cand_hap, cand_len, max_iter=1000, tol=1e-6):
+        """Read classes and the read-based estimate (pantax_hip_strain_read_em) of the resident reads, binned against the resident db.  The candidate set
+        of read_strains with cand_len (uint64 graph bases of every candidate) in place of the weights -> (species uint64 [S, 2, 3]: counted /
+        unexplained, cls_off uint64 [S+1], cls_mask uint64 [J], cls_q uint64 [J, 3]: the classes of every species of 1 .. 64 candidates in ascending
+        mask, bit i = the candidate with the i-th smallest haplotype index, x float64 [C] in the caller's order, n_iter uint32 [S], converged int32 [S],
+        delta float64 [S]); the last axis of species and cls_q is {n_reads, n_steps, span}."""
+        co = as_c(cand_off, np.uint64)
+        ch = as_c(cand_hap, np.uint32)
+        cl = as_c(cand_len, np.uint64)
+        if len(co) != self.S + 1 or len(ch) != int(co[-1]) or len(cl) != len(ch):
+            raise ValueError("strain_read_em: cand_off needs S + 1 entries and cand_hap / cand_len cand_off[-1] each")
+        cs = _ffi.ReadEmSet(self.S, co.ctypes.data, ch.ctypes.data if len(ch) else None, cl.ctypes.data if len(cl) else None, int(max_iter), float(tol))
+        species = np.zeros((self.S, 2, 3), dtype=np.uint64)
+        cls_off = np.zeros(self.S + 1, dtype=np.uint64)
+        x = np.zeros(len(ch), dtype=np.float64)
+        n_iter = np.zeros(self.S, dtype=np.uint32)
+        converged = np.zeros(self.S, dtype=np.int32)
+        delta = np.zeros(self.S, dtype=np.float64)
+        cap = 4096
+        while True:   # a second call only when a species set has more classes than the first guess holds: cls_off then says how many
+            cls_mask = np.zeros(cap, dtype=np.uint64)
+            cls_q = np.zeros((cap, 3), dtype=np.uint64)
+            rc = self.lib.pantax_hip_strain_read_em(self.ctx, self.db, self.reads, C.byref(cs), p(species) if self.S else None, p(cls_off), cap, p(cls_mask),
+                                                    p(cls_q), p(x) if len(ch) else None, p(n_iter) if self.S else None,
+                                                    p(converged) if self.S else None, p(delta) if self.S else None)
+            if rc == _ffi.E_LIMIT and int(cls_off[-1]) > cap:
+                cap = int(cls_off[-1])
+                continue
+            self._check(rc)
+            break
+        n = int(cls_off[-1])
+        return species, cls_off, cls_mask[:n].copy(), cls_q[:n].copy(), x, n_iter, converged, delta
+
     def strain_cov_track(self, sel_off, sel_hap, window):
         """Per-strain windowed coverage track (pantax_hip_strain_cov_track) of the coverage result get_node_abundances left on the device.
         sel_off [S+1], sel_hap (species-local haplotype indices, no repeats within a species), window W >= 1 in bases ->
@@ -689,7 +722,7 @@ class Engine:
                 strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
                 strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None, strain_fit_file=None,
                 strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42, strain_dropout_file=None,
-                strain_addin_file=None, strain_addin_top=0):
+                strain_addin_file=None, strain_addin_top=0, strain_em_file=None, strain_em_classes=0, strain_em_iterations=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -702,7 +735,8 @@ class Engine:
         model fit report (--strain-fit; one rank only); given, the call goes through pantax_hip_profile_with_ext.  strain_bootstrap_file: path of the
         bootstrap report (--strain-bootstrap; one rank only), strain_bootstrap_replicates the resamples (0: 100), strain_bootstrap_seed their seed.  strain_dropout_file: path of
         the leave-one-out report (--strain-dropout; one rank only).  strain_addin_file: path of the add-one report (--strain-addin; one rank only),
-        strain_addin_top the candidates it tests per species (0: 5)."""
+        strain_addin_top the candidates it tests per species (0: 5).  strain_em_file: path of the read class report (--strain-em; one rank only),
+        strain_em_classes the classes it prints per species (0: 10), strain_em_iterations the iterations of its estimate at most (0: 1000)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -745,12 +779,13 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
                                   strain_bootstrap_replicates=int(strain_bootstrap_replicates), strain_bootstrap_seed=int(strain_bootstrap_seed),
-                                  strain_dropout_file=enc(strain_dropout_file), strain_addin_file=enc(strain_addin_file), strain_addin_top=int(strain_addin_top))
+                                  strain_dropout_file=enc(strain_dropout_file), strain_addin_file=enc(strain_addin_file), strain_addin_top=int(strain_addin_top),
+                                  strain_em_file=enc(strain_em_file), strain_em_classes=int(strain_em_classes), strain_em_iterations=int(strain_em_iterations))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -911,6 +946,21 @@ def dropout_substitute(k, x_full, x_drop):
     if _ffi.load().pantax_hip_dropout_substitute(len(xf), int(k), p(xf), p(xd), p(out)) != 0:
         raise ValueError("dropout_substitute: refused")
     return int(out[0]), float(out[1]), float(out[2])
+
+
+def read_em(mask, b, length, max_iter=1000, tol=1e-6):
+    """pantax_hip_read_em: the read-based estimate of one species on the host.  mask / b uint64 [J]: the classes in ascending mask and their spans;
+    length uint64 [K]: the graph bases of the candidates in ascending haplotype index (bit k of a mask) -> (x float64 [K], n_iter, converged, delta)."""
+    m = as_c(mask, np.uint64)
+    bb = as_c(b, np.uint64)
+    ln = as_c(length, np.uint64)
+    if m.ndim != 1 or bb.shape != m.shape or ln.ndim != 1:
+        raise ValueError("read_em: mask and b are one-dimensional and of one length, length is one-dimensional")
+    x = np.zeros(len(ln), dtype=np.float64)
+    n_iter, conv, delta = C.c_uint32(0), C.c_int32(0), C.c_double(0.0)
+    if _ffi.load().pantax_hip_read_em(len(ln), len(m), p(m), p(bb), p(ln), int(max_iter), float(tol), p(x), C.byref(n_iter), C.byref(conv), C.byref(delta)) != 0:
+        raise ValueError("read_em: refused")
+    return x, int(n_iter.value), int(conv.value), float(delta.value)
 
 
 def addin_donor(K, x_base, x_add):
