@@ -316,6 +316,48 @@ int pantax_hip_strain_cov_track(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
                                 uint64_t *win_off_out /*[C+1]*/, uint64_t cap /* windows the four arrays hold */,
                                 uint32_t *n_nodes_out, uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out);
 
+/* ---- absent and amplified segments along a strain (the --strain-segments report; not a stage of the reference): the exact stretches of the genome of
+ * selected haplotypes that the sample does not cover at all, and those far deeper than a given depth, from what pantax_hip_node_coverage leaves on the
+ * device.  Walk, o_i and G_h as for the coverage track above.  With min_len >= 1 and one peak_depth[c] <= 2^31 per selection entry c (0: no peak class
+ * for that entry), step i of entry c has the class
+ *     1 (PANTAX_HIP_SEGMENT_GAP)   if node_base_cov[v_i] == 0;
+ *     2 (PANTAX_HIP_SEGMENT_PEAK)  else if peak_depth[c] > 0 and bases_per_node[v_i] >= peak_depth[c] * node_len[v_i] (u64 product);
+ *     0                            else.
+ * A segment is a maximal run [i, j) of consecutive steps of one walk with the same non-zero class (a gap directly followed by a peak is two segments);
+ * it carries class (u8), step = i (u64, walk-local), n_steps = j - i (u32), start = o_i, len = sum of node_len, bases = sum of bases_per_node (u64).
+ * Per selection entry, always written: hap_len [C] = G_h; and for the classes k = gap, peak over ALL runs of the class whatever their length,
+ * n_runs [2C], run_len [2C] (the sum of len) and run_max [2C] (the longest len), entry c's gap at 2c and its peak at 2c + 1.
+ * seg_off_out [C+1] = the prefix, in the order of sel_hap, of the number of segments with len >= min_len; it is ALWAYS written.  The six segment arrays
+ * hold exactly those segments, per entry in ascending start.  The cap protocol is that of pantax_hip_strain_cov_track: with more than `cap` segments the
+ * call returns PANTAX_HIP_E_LIMIT with seg_off_out and the per-entry summaries filled and the segment arrays untouched; a caller sizes them by calling
+ * once with cap = 0.  Integers only: results are exact and independent of any order.
+ * Validation and state rules of pantax_hip_strain_cov_track.  PANTAX_HIP_E_INVALID also for min_len = 0 and a peak_depth above 2^31. */
+#define PANTAX_HIP_SEGMENT_GAP 1
+#define PANTAX_HIP_SEGMENT_PEAK 2
+typedef struct {
+    uint32_t n_species;          /* must equal the db's */
+    const uint64_t *sel_off;     /* [S+1] */
+    const uint32_t *sel_hap;     /* [C] species-local haplotype index, any order, no repeats within a species */
+    const uint64_t *peak_depth;  /* [C] 0 = no peak class for the entry; at most 2^31 */
+    uint64_t min_len;            /* >= 1: segments shorter than this are counted in the summaries only */
+} pantax_hip_segment_set;
+int pantax_hip_strain_segments(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_segment_set *sel,
+                               uint64_t *seg_off_out /*[C+1]*/, uint64_t cap /* segments the six arrays hold */,
+                               uint64_t *hap_len_out /*[C]*/, uint64_t *n_runs_out /*[2C]*/, uint64_t *run_len_out /*[2C]*/, uint64_t *run_max_out /*[2C]*/,
+                               uint8_t *seg_class_out, uint64_t *seg_step_out, uint32_t *seg_n_steps_out, uint64_t *seg_start_out, uint64_t *seg_len_out,
+                               uint64_t *seg_bases_out);
+/* host helper, no ctx and no GPU: chains of the segments of ONE haplotype, given in ascending start (disjoint: start[i] >= start[i-1] + len[i-1]; class 1
+ * or 2).  Per class separately, ignoring the segments of the other class: consecutive segments with start_next - (start_prev + len_prev) <= bridge form
+ * one chain (a stretch of at most `bridge` bases decides nothing, in either direction; a peak between two gaps does not break their chain).  Chain m with
+ * span >= min_span is returned, in ascending start: chain_class [n], chain_first / chain_last [n] = the index of its first and last member in the input,
+ * chain_q [n][PANTAX_HIP_SEGMENT_CHAIN_N] = { start, end, span = end - start, in_class = the sum of its members' len, n_segments, n_steps, bases }.  The
+ * output arrays hold n entries (there are at most n chains); *n_chains_out = how many were written.  PANTAX_HIP_E_INVALID: a null argument with n > 0, a
+ * class other than 1 or 2, segments that are not ascending and disjoint. */
+#define PANTAX_HIP_SEGMENT_CHAIN_N 7
+int pantax_hip_segment_chain(uint64_t n, const uint8_t *seg_class, const uint64_t *seg_start, const uint64_t *seg_len, const uint32_t *seg_n_steps,
+                             const uint64_t *seg_bases, uint64_t bridge, uint64_t min_span, uint64_t *n_chains_out, uint8_t *chain_class,
+                             uint64_t *chain_first, uint64_t *chain_last, uint64_t *chain_q);
+
 /* ---- per-strain node evidence (the --strain-evidence report; not a stage of the reference): what in the sample separates a selected haplotype from
  * the other selected haplotypes of its species, and the coverage of the species that no selected haplotype explains, from what pantax_hip_node_coverage
  * leaves on the device.  For a species s of the db, Sel_s = its selected species-local haplotype indices, K_s = |Sel_s|.  Every node v of s is counted
@@ -988,6 +1030,28 @@ typedef struct {
     uint64_t strain_em_classes;      /* classes printed per species: 0 reads as 10, and so does a struct that does not hold the field */
     uint64_t strain_em_iterations;   /* max_iter: 0 reads as 1000, and so does a struct that does not hold the field; cut to 2^32 - 1 */
 } pantax_hip_profile_ext5;
+/* ... and once more: pantax_hip_profile_ext5 is closed at strain_em_iterations (a committed host check holds its 88 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the fifth version.  A caller fills v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext6) and passes
+ * &ext6.v5.v4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40-, 48-, 64- or 88-byte struct runs with the fields below off.  A later output
+ * is a field appended here. */
+#define PANTAX_HIP_SEGMENTS_PEAK_OFF 0xFFFFFFFFFFFFFFFFull
+typedef struct {
+    pantax_hip_profile_ext5 v5;   /* v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext6) */
+    /* --strain-segments: path of the segment report (pantax_hip_strain_segments over every group of species, right behind the group's strain step, beside
+     * the coverage track and on the same selected haplotypes; NULL, "" or "None" = off).  Per row of strain_abundance.txt peak_depth = max(2, ceil(F x the
+     * unrounded predicted_coverage)), clamped at 2^31 (F = strain_segments_peak; 0 when peaks are off).  The device is asked for the segments of at least
+     * min(strain_segments_min, bridge + 1) bases and pantax_hip_segment_chain joins them per strain with `bridge` and min_span = strain_segments_min.  TSV
+     * with a header: species_taxid, strain_taxid, genome_ID, class, rank, start, end, span, in_class, n_segments, n_nodes, bases, depth, fraction, threshold,
+     * predicted_coverage; f64 in shortest round-trip digits, "-" where a column does not apply.  Per strain in the order of strain_abundance.txt: class
+     * "strain" (span = G_h); "gap_total" and "peak_total" over ALL runs of the class (n_segments = n_runs, in_class = run_len, span = run_max, fraction =
+     * run_len / G_h, "-" when G_h = 0; threshold = peak_depth on peak_total); then the kept chains in ascending start, class "gap" or "peak" with rank from 1
+     * per class: start, end, span, in_class, n_segments, n_nodes = the steps, bases, depth = bases / in_class, fraction = in_class / span, threshold =
+     * peak_depth on peak rows.  Same rules as strain_fit_file. */
+    const char *strain_segments_file;
+    uint64_t strain_segments_min;     /* min_span in bases: 0 reads as 1000, and so does a struct that does not hold the field */
+    uint64_t strain_segments_bridge;  /* bridge + 1: 0 reads as a bridge of 100 bases, and so does a struct that does not hold the field; 1 = a bridge of 0 */
+    uint64_t strain_segments_peak;    /* F: 0 reads as 10, and so does a struct that does not hold the field; PANTAX_HIP_SEGMENTS_PEAK_OFF = no peak class */
+} pantax_hip_profile_ext6;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

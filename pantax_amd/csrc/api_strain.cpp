@@ -603,6 +603,26 @@ int pantax_hip_strain_cov_track(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
     return cov_track_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->window, win_off_out, cap, n_nodes_out, len_out, covered_out, bases_out);
 }
 
+int pantax_hip_strain_segments(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_segment_set *sel, uint64_t *seg_off_out, uint64_t cap, uint64_t *hap_len_out,
+                               uint64_t *n_runs_out, uint64_t *run_len_out, uint64_t *run_max_out, uint8_t *seg_class_out, uint64_t *seg_step_out,
+                               uint32_t *seg_n_steps_out, uint64_t *seg_start_out, uint64_t *seg_len_out, uint64_t *seg_bases_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off || !seg_off_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_segments: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_segments", sel->n_species));
+    if (sel->min_len == 0) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_segments: min_len of 0 bases");
+    PTX_TRY(check_hap_selection(ctx, db, "strain_segments", sel->sel_off, sel->sel_hap));
+    const uint64_t C = sel->sel_off[db->S];
+    if (C && (!sel->peak_depth || !hap_len_out || !n_runs_out || !run_len_out || !run_max_out))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_segments: null peak_depth or summary array");
+    for (uint64_t c = 0; c < C; ++c)
+        if (sel->peak_depth[c] > (1ull << 31))
+            return fail(ctx, PANTAX_HIP_E_INVALID, "strain_segments: peak_depth %llu of entry %llu (at most 2^31)", (unsigned long long)sel->peak_depth[c], (unsigned long long)c);
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_segments"));
+    return segments_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->peak_depth, sel->min_len, seg_off_out, cap, hap_len_out, n_runs_out, run_len_out, run_max_out,
+                           seg_class_out, seg_step_out, seg_n_steps_out, seg_start_out, seg_len_out, seg_bases_out);
+}
+
 int pantax_hip_strain_evidence(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_evidence_set *sel, uint64_t *hap_out, uint64_t *species_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;
     if (!db || !sel || !sel->sel_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_evidence: null argument");

@@ -724,6 +724,11 @@ int near_miss_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
 // windows fit `cap`
 int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, uint32_t *n_nodes_out,
                      uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out);
+// stage_segments.hip (pantax_hip_strain_segments): selection, peak depths and min_len validated by the caller; seg_off_out [C+1] and the four summaries are
+// always written, the six segment arrays only when the segments fit `cap`
+int segments_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *peak_depth, uint64_t min_len, uint64_t *seg_off_out,
+                    uint64_t cap, uint64_t *hap_len_out, uint64_t *n_runs_out, uint64_t *run_len_out, uint64_t *run_max_out, uint8_t *seg_class_out,
+                    uint64_t *seg_step_out, uint32_t *seg_n_steps_out, uint64_t *seg_start_out, uint64_t *seg_len_out, uint64_t *seg_bases_out);
 struct HostReads;
 // stage_gaf.hip: text -> host columns (+ walks unless `resident` is given, which then owns the packed reads in HBM)
 int gaf_tokenize_device(Ctx *ctx, const char *text, uint64_t size, HostReads &out, Reads *resident = nullptr, int fd = -1, uint64_t file_base = 0, bool group = true,

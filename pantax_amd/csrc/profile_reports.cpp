@@ -2,8 +2,9 @@
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
 // (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
-// report, the add-one report and the read class report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT5_REPORTS).
+// report, the add-one report, the read class report and the segment report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT6_REPORTS).
 #include <algorithm>
+#include <cmath>
 #include <fstream>
 #include <unordered_map>
 #include "hap_pairs_plan.hpp"
@@ -69,6 +70,32 @@ int group_cov_track(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const
     if (n) PTX_TRY(pantax_hip_strain_cov_track(run.ctx, db, &set, w_off.data(), n, ct.n_nodes.data() + at, ct.len.data() + at, ct.covered.data() + at, ct.bases.data() + at));
     for (size_t e = 0; e < g.hap.size(); ++e) ct.win_off.push_back(at + w_off[e + 1]);
     run.lap("  strain coverage track");
+    return 0;
+}
+// --strain-segments, beside the coverage track and on the same rows: peak_depth = max(2, ceil(F x second_sol)) clamped at 2^31 (0 with peaks off); the device
+// is asked for the seeds of min(min_span, bridge + 1) bases, which the writer chains
+int group_segments(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &sg = sh.rep.sg;
+    const ReportPlan &plan = run.p.rep;
+    const size_t C = g.hap.size(), e0 = g.entry0;
+    sg.peak.resize(e0 + C); sg.hap_len.resize(e0 + C); sg.n_runs.resize(2 * (e0 + C)); sg.run_len.resize(2 * (e0 + C)); sg.run_max.resize(2 * (e0 + C));
+    for (size_t c = 0; c < C; ++c) {
+        const double v = std::ceil((double)plan.sg_peak * g.w[c]);
+        sg.peak[e0 + c] = plan.sg_peak == 0 ? 0 : !(v >= 2.0) ? 2 : v >= 2147483648.0 ? 1ull << 31 : (uint64_t)v;
+    }
+    const uint64_t seed = plan.sg_bridge == ~0ull ? plan.sg_min : std::min(plan.sg_min, plan.sg_bridge + 1);
+    const pantax_hip_segment_set set{k1 - k0, g.off.data(), g.hap.data(), sg.peak.data() + e0, seed};
+    std::vector<uint64_t> s_off(C + 1, 0);
+    const int rc_size = pantax_hip_strain_segments(run.ctx, db, &set, s_off.data(), 0, sg.hap_len.data() + e0, sg.n_runs.data() + 2 * e0, sg.run_len.data() + 2 * e0,
+                                                   sg.run_max.data() + 2 * e0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);   // sizes: E_LIMIT unless there is no segment
+    if (rc_size != 0 && rc_size != PANTAX_HIP_E_LIMIT) return rc_size;
+    const uint64_t n = s_off[C], at = sg.len.size();
+    sg.cls.resize(at + n); sg.step.resize(at + n); sg.n_steps.resize(at + n); sg.start.resize(at + n); sg.len.resize(at + n); sg.bases.resize(at + n);
+    if (n) PTX_TRY(pantax_hip_strain_segments(run.ctx, db, &set, s_off.data(), n, sg.hap_len.data() + e0, sg.n_runs.data() + 2 * e0, sg.run_len.data() + 2 * e0,
+                                              sg.run_max.data() + 2 * e0, sg.cls.data() + at, sg.step.data() + at, sg.n_steps.data() + at, sg.start.data() + at,
+                                              sg.len.data() + at, sg.bases.data() + at));
+    for (size_t e = 0; e < C; ++e) sg.seg_off.push_back(at + s_off[e + 1]);
+    run.lap("  strain segments");
     return 0;
 }
 // --strain-evidence and --strain-depth, on the same coverage result: Sel_s = the group's rows; `call` writes n_hap u64 per entry and n_species per species
@@ -424,6 +451,43 @@ struct Writer {
                     const uint64_t start = (i - w0) * W, end = i + 1 == w1 ? G : start + W;   // (only the last window can be cut short: start + W <= G before it)
                     f << head << '\t' << start << '\t' << end << '\t' << ct.n_nodes[i] << '\t' << ct.len[i] << '\t' << ct.covered[i] << '\t' << ct.bases[i] << '\t'
                       << fmt_f64((double)ct.bases[i] / (double)ct.len[i]) << '\t' << fmt_f64((double)ct.covered[i] / (double)ct.len[i]) << '\n';
+                }
+            }
+            return 0;
+        });
+    }
+    // --strain-segments: per row of strain_abundance.txt, in its order, the strain, the totals of either class over all runs, and the chains of its kept
+    // segments (pantax_hip_segment_chain with the plan's bridge and min_span) in ascending start, ranked per class
+    int segments() const {
+        const auto &sg = rep.sg;
+        const ReportPlan &plan = run.p.rep;
+        return file(plan.ext6_path[X6REP_SEGMENTS],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tclass\trank\tstart\tend\tspan\tin_class\tn_segments\tn_nodes\tbases\tdepth\tfraction\tthreshold\tpredicted_coverage\n",
+                    "strain segment report", [&](std::ofstream &f) {
+            std::vector<uint8_t> c_cls;
+            std::vector<uint64_t> c_first, c_last, c_q;
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "segments", &e));
+                const std::string head = strain_head(r), pc = fmt_f64(sh.met[r.hap].second_sol);
+                const uint64_t G = sg.hap_len[e], pd = sg.peak[e];
+                const std::string thr = pd ? std::to_string((unsigned long long)pd) : std::string("-");
+                f << head << "\tstrain\t-\t0\t" << G << '\t' << G << "\t-\t-\t-\t-\t-\t-\t" << thr << '\t' << pc << '\n';
+                for (int k = 0; k < 2; ++k)
+                    f << head << '\t' << (k ? "peak_total" : "gap_total") << "\t-\t-\t-\t" << sg.run_max[2 * e + k] << '\t' << sg.run_len[2 * e + k] << '\t' << sg.n_runs[2 * e + k]
+                      << "\t-\t-\t-\t" << (G ? fmt_f64((double)sg.run_len[2 * e + k] / (double)G) : std::string("-")) << '\t' << (k ? thr : std::string("-")) << '\t' << pc << '\n';
+                const uint64_t s0 = sg.seg_off[e], n = sg.seg_off[e + 1] - s0;
+                uint64_t m = 0;
+                c_cls.resize(n); c_first.resize(n); c_last.resize(n); c_q.resize(PANTAX_HIP_SEGMENT_CHAIN_N * n);
+                if (pantax_hip_segment_chain(n, sg.cls.data() + s0, sg.start.data() + s0, sg.len.data() + s0, sg.n_steps.data() + s0, sg.bases.data() + s0, plan.sg_bridge,
+                                             plan.sg_min, &m, c_cls.data(), c_first.data(), c_last.data(), c_q.data()) != 0)
+                    return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: the segments of a strain are not ascending and disjoint");
+                uint64_t rank[2] = {0, 0};
+                for (uint64_t i = 0; i < m; ++i) {
+                    const uint64_t *q = c_q.data() + PANTAX_HIP_SEGMENT_CHAIN_N * i;
+                    const bool peak = c_cls[i] == PANTAX_HIP_SEGMENT_PEAK;
+                    f << head << '\t' << (peak ? "peak" : "gap") << '\t' << ++rank[peak ? 1 : 0] << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << q[3] << '\t' << q[4] << '\t'
+                      << q[5] << '\t' << q[6] << '\t' << fmt_f64((double)q[6] / (double)q[3]) << '\t' << fmt_f64((double)q[3] / (double)q[2]) << '\t' << (peak ? thr : std::string("-"))
+                      << '\t' << pc << '\n';
                 }
             }
             return 0;
@@ -831,6 +895,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     PTX_TRY(group_select(run, k0, k1, sh, g));
     if (plan.run[REP_READ_STRAINS]) PTX_TRY(group_read_strains(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_COVERAGE]) PTX_TRY(group_cov_track(run, db, k0, k1, g, sh));
+    if (plan.ext6_run[X6REP_SEGMENTS]) PTX_TRY(group_segments(run, db, k0, k1, g, sh));
     if (plan.run[REP_EVIDENCE]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_evidence, 2 * EVIDENCE_N, 3 * EVIDENCE_N, sh.rep.ev, "  strain evidence"));
     if (plan.ext_run[XREP_FIT]) PTX_TRY(group_fit(run, db, k0, k1, g, sh));
     if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(group_bootstrap(run, in, sn, db, k0, k1, g, sh));
@@ -861,6 +926,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext3_run[X3REP_DROPOUT]) PTX_TRY(w.dropout());
     if (plan.ext4_run[X4REP_ADDIN]) PTX_TRY(w.addin());
     if (plan.ext5_run[X5REP_EM]) PTX_TRY(w.read_em());
+    if (plan.ext6_run[X6REP_SEGMENTS]) PTX_TRY(w.segments());
     return 0;
 }
 }  // namespace reports

@@ -397,6 +397,35 @@ class Engine:
             self._check(self.lib.pantax_hip_strain_cov_track(self.ctx, self.db, C.byref(cs), p(win_off), n, p(n_nodes), p(ln), p(covered), p(bases)))
         return win_off, n_nodes, ln, covered, bases
 
+    def strain_segments(self, sel_off, sel_hap, peak_depth, min_len):
+        """Absent and amplified segments along selected haplotypes (pantax_hip_strain_segments) of the coverage result get_node_abundances left on the
+        device.  sel_off [S+1], sel_hap (species-local haplotype indices, no repeats within a species), peak_depth (one uint64 per entry, or one number
+        for all; 0: no peak class), min_len >= 1 in bases -> (seg_off uint64 [C+1], hap_len uint64 [C], n_runs, run_len, run_max uint64 [C, 2]: gap /
+        peak over all runs, seg_class uint8, seg_step uint64, seg_n_steps uint32, seg_start, seg_len, seg_bases uint64): the segments of at least
+        min_len bases of selection entry c are [seg_off[c], seg_off[c+1]), in ascending start."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("strain_segments: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        pd = as_c(np.broadcast_to(np.asarray(peak_depth, dtype=np.uint64), (len(sh),)), np.uint64)
+        cs = _ffi.SegmentSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, pd.ctypes.data if len(sh) else None, int(min_len))
+        seg_off = np.zeros(len(sh) + 1, dtype=np.uint64)
+        hap_len = np.zeros(len(sh), dtype=np.uint64)
+        n_runs, run_len, run_max = (np.zeros((len(sh), 2), dtype=np.uint64) for _ in range(3))
+        q = lambda a: p(a) if len(a) else None
+        rc = self.lib.pantax_hip_strain_segments(self.ctx, self.db, C.byref(cs), p(seg_off), 0, q(hap_len), q(n_runs), q(run_len), q(run_max),
+                                                 None, None, None, None, None, None)   # sizes the arrays
+        if rc != _ffi.E_LIMIT:
+            self._check(rc)
+        n = int(seg_off[-1])
+        cls = np.zeros(n, dtype=np.uint8)
+        n_steps = np.zeros(n, dtype=np.uint32)
+        step, start, ln, bases = (np.zeros(n, dtype=np.uint64) for _ in range(4))
+        if n:
+            self._check(self.lib.pantax_hip_strain_segments(self.ctx, self.db, C.byref(cs), p(seg_off), n, q(hap_len), q(n_runs), q(run_len), q(run_max),
+                                                            p(cls), p(step), p(n_steps), p(start), p(ln), p(bases)))
+        return seg_off, hap_len, n_runs, run_len, run_max, cls, step, n_steps, start, ln, bases
+
     def strain_evidence(self, sel_off, sel_hap):
         """Per-strain node evidence (pantax_hip_strain_evidence) of the coverage result get_node_abundances left on the device.
         sel_off [S+1], sel_hap (species-local haplotype indices, no repeats within a species) -> (hap uint64 [C, 2, 4]: all / private of every
@@ -722,7 +751,8 @@ class Engine:
                 strain_coverage_file=None, strain_coverage_window=0, strain_evidence_file=None, strain_read_support_file=None,
                 strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None, strain_fit_file=None,
                 strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42, strain_dropout_file=None,
-                strain_addin_file=None, strain_addin_top=0, strain_em_file=None, strain_em_classes=0, strain_em_iterations=0):
+                strain_addin_file=None, strain_addin_top=0, strain_em_file=None, strain_em_classes=0, strain_em_iterations=0,
+                strain_segments_file=None, strain_segments_min=0, strain_segments_bridge=None, strain_segments_peak=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -736,7 +766,10 @@ class Engine:
         bootstrap report (--strain-bootstrap; one rank only), strain_bootstrap_replicates the resamples (0: 100), strain_bootstrap_seed their seed.  strain_dropout_file: path of
         the leave-one-out report (--strain-dropout; one rank only).  strain_addin_file: path of the add-one report (--strain-addin; one rank only),
         strain_addin_top the candidates it tests per species (0: 5).  strain_em_file: path of the read class report (--strain-em; one rank only),
-        strain_em_classes the classes it prints per species (0: 10), strain_em_iterations the iterations of its estimate at most (0: 1000)."""
+        strain_em_classes the classes it prints per species (0: 10), strain_em_iterations the iterations of its estimate at most (0: 1000).
+        strain_segments_file: path of the segment report (--strain-segments; one rank only), strain_segments_min the bases a chain spans at least
+        (0: 1000), strain_segments_bridge the bases between two segments of a chain at most (None: 100; 0 is a bridge of 0 -- the struct holds
+        bridge + 1), strain_segments_peak the integer factor F of peak_depth = max(2, ceil(F x predicted_coverage)) (0: 10; "off": no peak class)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -779,13 +812,16 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
                                   strain_bootstrap_replicates=int(strain_bootstrap_replicates), strain_bootstrap_seed=int(strain_bootstrap_seed),
                                   strain_dropout_file=enc(strain_dropout_file), strain_addin_file=enc(strain_addin_file), strain_addin_top=int(strain_addin_top),
-                                  strain_em_file=enc(strain_em_file), strain_em_classes=int(strain_em_classes), strain_em_iterations=int(strain_em_iterations))
+                                  strain_em_file=enc(strain_em_file), strain_em_classes=int(strain_em_classes), strain_em_iterations=int(strain_em_iterations),
+                                  strain_segments_file=enc(strain_segments_file), strain_segments_min=int(strain_segments_min),
+                                  strain_segments_bridge=0 if strain_segments_bridge is None else int(strain_segments_bridge) + 1,
+                                  strain_segments_peak=_ffi.SEGMENTS_PEAK_OFF if strain_segments_peak == "off" else int(strain_segments_peak))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -961,6 +997,29 @@ def read_em(mask, b, length, max_iter=1000, tol=1e-6):
     if _ffi.load().pantax_hip_read_em(len(ln), len(m), p(m), p(bb), p(ln), int(max_iter), float(tol), p(x), C.byref(n_iter), C.byref(conv), C.byref(delta)) != 0:
         raise ValueError("read_em: refused")
     return x, int(n_iter.value), int(conv.value), float(delta.value)
+
+
+def segment_chain(seg_class, seg_start, seg_len, seg_n_steps, seg_bases, bridge, min_span):
+    """pantax_hip_segment_chain: chains of the segments of ONE haplotype (ascending start, disjoint).  Per class separately, consecutive segments at most
+    `bridge` bases apart form a chain; those of span >= min_span are returned in ascending start -> (chain_class uint8 [M], first uint64 [M], last uint64
+    [M]: its first and last member, q uint64 [M, 7]: start, end, span, in_class, n_segments, n_steps, bases)."""
+    cl = as_c(seg_class, np.uint8)
+    st = as_c(seg_start, np.uint64)
+    ln = as_c(seg_len, np.uint64)
+    ns = as_c(seg_n_steps, np.uint32)
+    bs = as_c(seg_bases, np.uint64)
+    n = len(cl)
+    if not (len(st) == len(ln) == len(ns) == len(bs) == n):
+        raise ValueError("segment_chain: the five arrays are of one length")
+    c_cls = np.zeros(n, dtype=np.uint8)
+    first, last = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    q = np.zeros((n, _ffi.SEGMENT_CHAIN_N), dtype=np.uint64)
+    m = C.c_uint64(0)
+    a = lambda x: p(x) if n else None
+    if _ffi.load().pantax_hip_segment_chain(n, a(cl), a(st), a(ln), a(ns), a(bs), int(bridge), int(min_span), C.byref(m), a(c_cls), a(first), a(last), a(q)) != 0:
+        raise ValueError("segment_chain: refused")
+    m = int(m.value)
+    return c_cls[:m].copy(), first[:m].copy(), last[:m].copy(), q[:m].copy()
 
 
 def addin_donor(K, x_base, x_add):
