@@ -289,6 +289,51 @@ int pantax_hip_strain_read_em(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip
 int pantax_hip_read_em(uint32_t K, uint64_t J, const uint64_t *mask, const uint64_t *b, const uint64_t *len, uint32_t max_iter, double tol, double *x_out,
                        uint32_t *n_iter_out, int32_t *converged_out, double *delta_out);
 
+/* ---- mosaic reads (the --strain-mosaic report; not a stage of the reference): which candidate strains a read that fits no single candidate switches
+ * between, and where.  Inputs, state rules, PANTAX_HIP_E_INVALID cases, a counted read, Q(r) = (1, n_steps, span), K_s and the rule "argmax of w, ties to
+ * the smallest species-local haplotype index" are those of pantax_hip_strain_read_support above.  For a counted read r of a species with 1 <= K_s <= 64:
+ *   v_1 .. v_n = its steps in walk order (a node visited twice is two steps);  M(v) = the species' candidates whose walk visits v.
+ *   r is FOREIGN if some M(v_i) is empty: it is not cut and gives no segments, switches or junctions; foreign_steps sums its steps with empty M.
+ *   Otherwise r is cut greedily from the left: a segment grows while the intersection of its steps' M stays non-empty, the step that would empty it opens
+ *   the next segment.  k(r) = the number of segments, A_j = the intersection over segment j, and segment j is ASSIGNED the argmax of w over A_j.  k(r) is
+ *   the smallest number of stretches that each fit one candidate (a stretch of a compatible stretch is compatible), the same in either walk direction, and
+ *   k(r) = 1 exactly when C(r) is not empty.  A read of k >= 2 is MOSAIC.  Two consecutive segments never share their assigned strain.
+ * Outputs, u64 unless stated, exact integers independent of any order:
+ *   species_out [S][6][3] = the sums of Q over { counted, compatible (k = 1), mosaic1 (k = 2), mosaic2 (k = 3), mosaic3plus (k >= 4), foreign }; a species
+ *     of K_s = 0 or K_s > 64 gets counted only (a candidate word is one u64, as in pantax_hip_strain_read_em);
+ *   extra_out [S][3] = { n_segments = sum of k over the mosaic reads, n_breaks = sum of k - 1, foreign_steps };
+ *   hap_out [C][2] in the order of cand_hap = { the segments of mosaic reads assigned to the candidate, the steps in those segments };
+ *   pair_out[pair_off[s] + a * K_s + b] = the breaks whose left segment is assigned to the candidate at position a of the species' list and whose right
+ *     segment to the one at position b: in walk order, NOT mirrored, zero diagonal.  pair_off_out [S+1] and pair_cap as in read support;
+ *   junctions: a break between the last step a of its left segment and the first step b of its right segment is the junction (species, node_a, node_b),
+ *     nodes as species-local indices.  junction_out [junction_cap][3] (u32) and junction_count_out [junction_cap] hold the DISTINCT junctions with their
+ *     numbers of breaks in ascending (species, node_a, node_b); *n_junctions_out = how many; *n_breaks_total_out = the breaks of the call, always
+ *     written.  junction_cap = 0: junctions are not collected (the two arrays may be null, *n_junctions_out = 0).  junction_cap > 0 but below the breaks
+ *     of the call: PANTAX_HIP_E_LIMIT with *n_breaks_total_out and pair_off_out written and nothing else touched; size by it and repeat.
+ *     The greedy cut puts a break as LATE in walk order as it can, so reads of the two strands that cross one recombination point report junctions that
+ *     bracket the point from either side, not one junction.
+ * For every species of 1 <= K_s <= 64: counted = compatible + mosaic1 + mosaic2 + mosaic3plus + foreign (all three numbers); compatible = counted -
+ * unexplained and mosaic* + foreign = unexplained of pantax_hip_strain_read_support on the same candidates; sum of hap_out.segments = n_segments; sum of
+ * hap_out.steps = the n_steps of the three mosaic classes; sum of the species' pair block = n_breaks = the sum of its junction counts = n_segments - the
+ * n_reads of the three mosaic classes; K_s = 1 gives no mosaic read. */
+#define PANTAX_HIP_MOSAIC_CLASSES 6
+int pantax_hip_strain_mosaic(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
+                             uint64_t *species_out /*[S][6][3]*/, uint64_t *extra_out /*[S][3]*/, uint64_t *hap_out /*[C][2]*/,
+                             uint64_t *pair_off_out /*[S+1]*/, uint64_t pair_cap /* entries pair_out holds */, uint64_t *pair_out,
+                             uint64_t junction_cap /* junctions the two arrays hold; 0 = do not collect */, uint32_t *junction_out /*[][3]*/,
+                             uint64_t *junction_count_out, uint64_t *n_junctions_out, uint64_t *n_breaks_total_out);
+/* host helper, no ctx and no GPU: the greedy cut above for ONE walk.  masks [n]: bit p of masks[i] = the candidate at position p walks step i (bits at and
+ * above K are ignored); w, hap [K] = weight and species-local haplotype index of position p (no repeats), 1 <= K <= 64.  *k_out = k (0 for a foreign or an
+ * empty walk), *foreign_steps_out = the steps with an empty mask; segment j < min(k, cap) is the steps [seg_end_out[j-1], seg_end_out[j]) (seg_end_out[-1]
+ * = 0) and is assigned position seg_pos_out[j].  PANTAX_HIP_E_LIMIT when k > cap (k, foreign_steps and the first cap segments are written);
+ * PANTAX_HIP_E_INVALID for a null argument, K = 0, K > 64 or a haplotype twice. */
+int pantax_hip_mosaic_walk(uint64_t n, const uint64_t *masks, uint32_t K, const double *w, const uint32_t *hap, uint64_t *seg_end_out,
+                           uint32_t *seg_pos_out, uint64_t cap, uint64_t *k_out, uint64_t *foreign_steps_out);
+/* host helper, no ctx and no GPU: the junctions a report prints -- idx_out [min(n, top)] = the indices of the first `top` of n junctions in the order
+ * count descending, then node_a, then node_b ascending; *n_out = how many.  PANTAX_HIP_E_INVALID for a null argument with n > 0. */
+int pantax_hip_mosaic_top(uint64_t n, const uint32_t *node_a, const uint32_t *node_b, const uint64_t *count, uint64_t top, uint64_t *idx_out,
+                          uint64_t *n_out);
+
 /* ---- per-strain coverage track (the --strain-coverage report; not a stage of the reference): coverage along the genome of selected haplotypes,
  * in windows of W bases, from what pantax_hip_node_coverage leaves on the device.  For a species s, a species-local haplotype h and W >= 1:
  *   v_0 .. v_{n-1} = the walk of h as global node indices (a node visited twice counts at both visits);
@@ -1052,6 +1097,27 @@ typedef struct {
     uint64_t strain_segments_bridge;  /* bridge + 1: 0 reads as a bridge of 100 bases, and so does a struct that does not hold the field; 1 = a bridge of 0 */
     uint64_t strain_segments_peak;    /* F: 0 reads as 10, and so does a struct that does not hold the field; PANTAX_HIP_SEGMENTS_PEAK_OFF = no peak class */
 } pantax_hip_profile_ext6;
+/* ... and once more: pantax_hip_profile_ext6 is closed at strain_segments_peak (a committed host check holds its 120 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the sixth version.  A caller fills v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext7) and
+ * passes &ext7.v6.v5.v4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40-, 48-, 64-, 88- or 120-byte struct runs with the fields below off.
+ * A later output is a field appended here. */
+#define PANTAX_HIP_MOSAIC_TOP_OFF 0xFFFFFFFFFFFFFFFFull
+typedef struct {
+    pantax_hip_profile_ext6 v6;   /* v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext7) */
+    /* --strain-mosaic: path of the mosaic read report (pantax_hip_strain_mosaic over every group of species, right behind the group's strain step, with
+     * exactly the candidates and weights of read_strain_file; NULL, "" or "None" = off).  TSV with a header: species_taxid, strain_taxid, genome_ID, class,
+     * n_reads, n_steps, span, n_segments, fraction, other_strain_taxid, other_genome_ID, node_a, node_b; f64 in shortest round-trip digits, "-" where a
+     * column does not apply or a fraction has no denominator.  (1) per row of strain_abundance.txt, in its order, class "donor": n_segments and n_steps =
+     * the segments of mosaic reads assigned to the strain and their steps, fraction = those steps / the steps of the species' mosaic reads.  (2) per
+     * species in shard order: "counted", "compatible", "mosaic1", "mosaic2", "mosaic3plus", "foreign" with Q and fraction = n_reads / counted.n_reads
+     * (foreign carries foreign_steps in n_segments), then "mosaic_total" = Q over the three mosaic classes with n_segments; a species without rows:
+     * counted only; one of more than 64 rows: counted and "skipped".  (3) per pair of rows a < b (haplotype index) of a species with a break between
+     * them, class "switch": a's strain columns, b in other_*, n_segments = pair[a][b] + pair[b][a], fraction = that / the species' n_breaks.  (4) per
+     * species its strain_mosaic_top junctions by count (then node_a, node_b ascending), class "junction": node_a and node_b as the node ids of the GAF,
+     * n_segments = the count, fraction = count / n_breaks.  Same rules as strain_fit_file. */
+    const char *strain_mosaic_file;
+    uint64_t strain_mosaic_top;   /* junctions printed per species: 0 reads as 10, and so does a struct that does not hold the field; PANTAX_HIP_MOSAIC_TOP_OFF = no junction rows, none collected */
+} pantax_hip_profile_ext7;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

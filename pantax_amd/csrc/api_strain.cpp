@@ -509,6 +509,22 @@ int pantax_hip_read_strains(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_r
     return read_strains_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), hap_out, n_out, post_out);
 }
 
+// the one argument check of pantax_hip_strain_read_support and pantax_hip_strain_mosaic: the set check above, then pair_off_out (always written from here
+// on) and the pair_cap rule
+static int check_read_pair_set(pantax_hip_ctx *ctx, const pantax_hip_db *db, const pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand, const char *what,
+                               uint64_t *pair_off_out, uint64_t pair_cap, std::vector<uint32_t> &hap, std::vector<double> &w, std::vector<uint64_t> &ord) {
+    PTX_TRY(check_read_strain_set(ctx, db, reads, cand, what, hap, w, ord));
+    const uint32_t S = db->S;
+    pair_off_out[0] = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        const uint64_t K = cand->cand_off[s + 1] - cand->cand_off[s];
+        pair_off_out[s + 1] = pair_off_out[s] + (K <= 64 ? K * K : 0);
+    }
+    if (pair_off_out[S] > pair_cap)
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "%s: %llu pair entries, the caller's array holds %llu", what, (unsigned long long)pair_off_out[S], (unsigned long long)pair_cap);
+    return 0;
+}
+
 int pantax_hip_strain_read_support(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
                                    uint64_t *hap_out, uint64_t *species_out, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;
@@ -517,18 +533,29 @@ int pantax_hip_strain_read_support(pantax_hip_ctx *ctx, pantax_hip_db *db, panta
     std::vector<uint32_t> hap;
     std::vector<double> w;
     std::vector<uint64_t> ord;
-    PTX_TRY(check_read_strain_set(ctx, db, reads, cand, "strain_read_support", hap, w, ord));
+    PTX_TRY(check_read_pair_set(ctx, db, reads, cand, "strain_read_support", pair_off_out, pair_cap, hap, w, ord));
     const uint32_t S = db->S;
-    pair_off_out[0] = 0;
-    for (uint32_t s = 0; s < S; ++s) {
-        const uint64_t K = cand->cand_off[s + 1] - cand->cand_off[s];
-        pair_off_out[s + 1] = pair_off_out[s] + (K <= 64 ? K * K : 0);
-    }
-    if (pair_off_out[S] > pair_cap)
-        return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_read_support: %llu pair entries, the caller's array holds %llu", (unsigned long long)pair_off_out[S], (unsigned long long)pair_cap);
     if ((cand->cand_off[S] && !hap_out) || (S && !species_out) || (pair_off_out[S] && !pair_out))
         return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_support: null output array");
     return read_support_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), ord.data(), pair_off_out, hap_out, species_out, pair_out);
+}
+
+int pantax_hip_strain_mosaic(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand, uint64_t *species_out,
+                             uint64_t *extra_out, uint64_t *hap_out, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out, uint64_t junction_cap,
+                             uint32_t *junction_out, uint64_t *junction_count_out, uint64_t *n_junctions_out, uint64_t *n_breaks_total_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !reads || !cand || !cand->cand_off || !pair_off_out || !n_junctions_out || !n_breaks_total_out)
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_mosaic: null argument");
+    PTX_ENTER(ctx);
+    std::vector<uint32_t> hap;
+    std::vector<double> w;
+    std::vector<uint64_t> ord;
+    PTX_TRY(check_read_pair_set(ctx, db, reads, cand, "strain_mosaic", pair_off_out, pair_cap, hap, w, ord));
+    const uint32_t S = db->S;
+    if ((cand->cand_off[S] && !hap_out) || (S && (!species_out || !extra_out)) || (pair_off_out[S] && !pair_out) || (junction_cap && (!junction_out || !junction_count_out)))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_mosaic: null output array");
+    return mosaic_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), ord.data(), pair_off_out, species_out, extra_out, hap_out, pair_out, junction_cap,
+                         junction_out, junction_count_out, n_junctions_out, n_breaks_total_out);
 }
 
 int pantax_hip_strain_read_em(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_em_set *cand, uint64_t *species_out,

@@ -691,6 +691,11 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
 // sorted candidate c, pair_off [S+1]; all validated by the caller.  hap_out [C][3][3] in the caller's order, species_out [S][4][3], pair_out [pair_off[S]]
 int read_support_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, const uint64_t *entry_of,
                         const uint64_t *pair_off, uint64_t *hap_out, uint64_t *species_out, uint64_t *pair_out);
+// stage_mosaic.hip (pantax_hip_strain_mosaic): the arguments of read_support_launch; species_out [S][6][3], extra_out [S][3], hap_out [C][2] in the caller's
+// order, pair_out [pair_off[S]]; junction_cap = 0 collects no junctions, more breaks than a non-zero junction_cap is E_LIMIT with *n_breaks_total_out alone written
+int mosaic_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, const uint64_t *entry_of,
+                  const uint64_t *pair_off, uint64_t *species_out, uint64_t *extra_out, uint64_t *hap_out, uint64_t *pair_out, uint64_t junction_cap,
+                  uint32_t *junction_out, uint64_t *junction_count_out, uint64_t *n_junctions_out, uint64_t *n_breaks_total_out);
 // stage_read_em.hip (pantax_hip_strain_read_em): candidates of every species in ascending haplotype order with their lengths, entry_of[c] = the caller's entry
 // of sorted candidate c; all validated by the caller.  Outputs as the stage call's; they are written only when the call succeeds (cls_off_out: also on E_LIMIT)
 int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const uint64_t *cand_len, const uint64_t *entry_of, uint32_t max_iter,

@@ -2,12 +2,13 @@
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
 // (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
-// report, the add-one report, the read class report and the segment report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT6_REPORTS).
+// report, the add-one report, the read class report, the segment report and the mosaic read report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT7_REPORTS).
 #include <algorithm>
 #include <cmath>
 #include <fstream>
 #include <unordered_map>
 #include "hap_pairs_plan.hpp"
+#include "mosaic_plan.hpp"
 #include "profile_run.hpp"
 #include "read_em_plan.hpp"
 
@@ -215,6 +216,39 @@ int group_read_support(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k
                                            sup.pair.data() + pair0));
     for (uint32_t k = 0; k < Sg; ++k) sup.pair_off[k0 + k] = pair0 + p_off[k];
     run.lap("  strain read support");
+    return 0;
+}
+// --strain-mosaic, beside the read support call and with its candidates and weights: the cut reads summed on the device.  Junctions (unless the plan's top
+// is off) with a first guess of their number; a second call only when the group has more breaks than that: n_breaks then says how many
+int group_mosaic(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &mo = sh.rep.mo;
+    const uint32_t Sg = k1 - k0;
+    std::vector<uint64_t> p_off(Sg + 1, 0);
+    const pantax_hip_read_strain_set cs{Sg, g.off.data(), g.hap.data(), g.w.data()};
+    mo.hap.resize(2 * (g.entry0 + g.hap.size()));
+    uint64_t n_pair = 0;
+    for (uint32_t k = 0; k < Sg; ++k) { const uint64_t K = g.off[k + 1] - g.off[k]; mo.K[k0 + k] = (uint32_t)K; n_pair += K <= 64 ? K * K : 0; }
+    const size_t pair0 = mo.pair.size();
+    mo.pair.resize(pair0 + n_pair);
+    uint64_t cap = run.p.rep.mo_top ? 4096 : 0, n_junctions = 0, n_breaks = 0;
+    std::vector<uint32_t> jn;
+    std::vector<uint64_t> jc;
+    for (;;) {
+        jn.assign(3 * cap, 0); jc.assign(cap, 0);
+        const int rc = pantax_hip_strain_mosaic(run.ctx, db, in.reads.rd, &cs, mo.species.data() + 3 * MOS_N_CLASSES * (size_t)k0, mo.extra.data() + 3 * (size_t)k0,
+                                                mo.hap.data() + 2 * g.entry0, p_off.data(), n_pair, mo.pair.data() + pair0, cap, cap ? jn.data() : nullptr,
+                                                cap ? jc.data() : nullptr, &n_junctions, &n_breaks);
+        if (rc == PANTAX_HIP_E_LIMIT && cap && n_breaks > cap) { cap = n_breaks; continue; }
+        if (rc != 0) return rc;
+        break;
+    }
+    uint64_t j = 0;
+    for (uint32_t k = 0; k < Sg; ++k) {
+        mo.pair_off[k0 + k] = pair0 + p_off[k];
+        for (; j < n_junctions && jn[3 * j] == k; ++j) { mo.jn_a.push_back(jn[3 * j + 1]); mo.jn_b.push_back(jn[3 * j + 2]); mo.jn_count.push_back(jc[j]); }
+        mo.jn_off[k0 + k + 1] = mo.jn_count.size();
+    }
+    run.lap("  strain mosaic reads");
     return 0;
 }
 // --strain-em, right behind the read support call: the candidates of group_read_strains with G = the len of the strain's `all` class of the node evidence
@@ -711,6 +745,74 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-mosaic: the donor row of every row of strain_abundance.txt, in its order; the classes of every species of the shard in the order it went
+    // through the device; the switches between every two rows of a species; the plan's top junctions of every species
+    int mosaic() const {
+        const auto &mo = rep.mo;
+        return file(run.p.rep.ext7_path[X7REP_MOSAIC],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_reads\tn_steps\tspan\tn_segments\tfraction\tother_strain_taxid\tother_genome_ID\tnode_a\tnode_b\n",
+                    "strain mosaic read report", [&](std::ofstream &f) {
+            const auto frac = [](uint64_t n, uint64_t of) { return of ? fmt_f64((double)n / (double)of) : std::string("-"); };
+            const auto served = [&](uint32_t k) { return mo.K[k] >= 1 && mo.K[k] <= MOSAIC_MAX_K; };
+            const auto sp = [&](uint32_t k, int cls) { return mo.species.data() + 3 * MOS_N_CLASSES * (size_t)k + 3 * cls; };
+            std::vector<const TrackRow *> row_of(mo.hap.size() / 2, nullptr);   // entry -> its first row of the table
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "mosaic reads", &e));
+                if (!row_of[e]) row_of[e] = &r;
+                f << strain_head(r) << "\tdonor\t-\t";
+                if (served(r.k)) {
+                    const uint64_t steps = sp(r.k, MOS_MOSAIC1)[1] + sp(r.k, MOS_MOSAIC2)[1] + sp(r.k, MOS_MOSAIC3PLUS)[1];
+                    f << mo.hap[2 * e + 1] << "\t-\t" << mo.hap[2 * e] << '\t' << frac(mo.hap[2 * e + 1], steps);
+                } else f << "-\t-\t-\t-";
+                f << "\t-\t-\t-\t-\n";
+            }
+            const char *const of_species[MOS_N_CLASSES] = {"counted", "compatible", "mosaic1", "mosaic2", "mosaic3plus", "foreign"};
+            for (uint32_t k = 0; k < Su; ++k) {
+                const std::string head = species_head(k);
+                const uint64_t *ex = mo.extra.data() + 3 * (size_t)k;
+                for (int c = 0; c < (served(k) ? (int)MOS_N_CLASSES : 1); ++c) {   // a species without rows, or of more than 64: counted only
+                    const uint64_t *q = sp(k, c);
+                    f << head << '\t' << of_species[c] << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t';
+                    if (c == MOS_FOREIGN) f << ex[2]; else f << '-';
+                    f << '\t' << frac(q[0], sp(k, MOS_COUNTED)[0]) << "\t-\t-\t-\t-\n";
+                }
+                if (served(k)) {
+                    uint64_t q[3];
+                    for (int i = 0; i < 3; ++i) q[i] = sp(k, MOS_MOSAIC1)[i] + sp(k, MOS_MOSAIC2)[i] + sp(k, MOS_MOSAIC3PLUS)[i];
+                    f << head << "\tmosaic_total\t" << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << ex[0] << '\t' << frac(q[0], sp(k, MOS_COUNTED)[0]) << "\t-\t-\t-\t-\n";
+                } else if (mo.K[k] > MOSAIC_MAX_K) f << head << "\tskipped\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const uint64_t K = mo.K[k];
+                if (K < 2 || K > MOSAIC_MAX_K) continue;
+                int64_t e0 = -1;                                                        // the species' entries are consecutive, in ascending haplotype index
+                for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1] && e0 < 0; ++h) e0 = rep.entry[h];
+                const uint64_t *pm = mo.pair.data() + mo.pair_off[k];
+                for (uint64_t a = 0; a < K; ++a)
+                    for (uint64_t b = a + 1; b < K; ++b) {
+                        const uint64_t n = pm[a * K + b] + pm[b * K + a];
+                        if (!n || e0 < 0 || !row_of[e0 + a] || !row_of[e0 + b]) continue;
+                        const TrackRow &ra = *row_of[e0 + a], &rb = *row_of[e0 + b];
+                        f << strain_head(ra) << "\tswitch\t-\t-\t-\t" << n << '\t' << frac(n, mo.extra[3 * (size_t)k + 1]) << '\t' << (rb.gr ? rb.gr->strain_taxid : std::string()) << '\t'
+                          << (rb.gr ? rb.gr->genome_id : std::string()) << "\t-\t-\n";
+                    }
+            }
+            std::vector<uint64_t> top;
+            for (uint32_t k = 0; k < Su && run.p.rep.mo_top; ++k) {
+                const uint64_t j0 = mo.jn_off[k], n = mo.jn_off[k + 1] - j0;
+                uint64_t m = 0;
+                top.resize(n);
+                if (pantax_hip_mosaic_top(n, mo.jn_a.data() + j0, mo.jn_b.data() + j0, mo.jn_count.data() + j0, run.p.rep.mo_top, top.data(), &m) != 0) continue;   // (n = 0)
+                const int64_t first = in.ranges[sn.sel[sh.use[k]]].start;              // the node ids of the GAF: the species' first node id + the local index
+                for (uint64_t i = 0; i < m; ++i) {
+                    const uint64_t j = j0 + top[i];
+                    f << species_head(k) << "\tjunction\t-\t-\t-\t" << mo.jn_count[j] << '\t' << frac(mo.jn_count[j], mo.extra[3 * (size_t)k + 1]) << "\t-\t-\t" << first + (int64_t)mo.jn_a[j]
+                      << '\t' << first + (int64_t)mo.jn_b[j] << '\n';
+                }
+            }
+            return 0;
+        });
+    }
     // --strain-em: the estimate beside predicted_coverage for every row of strain_abundance.txt, in its order; then per species of the shard in the order it
     // went through the device its largest classes, the rest of them in one row, the unexplained reads and the species row
     int read_em() const {
@@ -886,6 +988,9 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.ext5_run[X5REP_EM]) {
         rep.em.species.assign(6 * (size_t)Su, 0); rep.em.cls_off.assign(Su + 1, 0); rep.em.K.assign(Su, 0); rep.em.iter.assign(Su, 0); rep.em.conv.assign(Su, 0); rep.em.delta.assign(Su, 0.0);
     }
+    if (plan.ext7_run[X7REP_MOSAIC]) {
+        rep.mo.species.assign(3 * MOS_N_CLASSES * (size_t)Su, 0); rep.mo.extra.assign(3 * (size_t)Su, 0); rep.mo.pair_off.assign(Su, 0); rep.mo.K.assign(Su, 0); rep.mo.jn_off.assign(Su + 1, 0);
+    }
 }
 int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db *db, uint32_t k0, uint32_t k1, ShardResult &sh) {
     const ReportPlan &plan = run.p.rep;
@@ -904,6 +1009,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.pair_run[PREP_EVIDENCE]) PTX_TRY(group_pair_evidence(run, db, k0, k1, g, sh));
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
     if (plan.ext5_run[X5REP_EM]) PTX_TRY(group_read_em(run, in, db, k0, k1, g, sh));
+    if (plan.ext7_run[X7REP_MOSAIC]) PTX_TRY(group_mosaic(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh, gc));
     return 0;
@@ -927,6 +1033,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext4_run[X4REP_ADDIN]) PTX_TRY(w.addin());
     if (plan.ext5_run[X5REP_EM]) PTX_TRY(w.read_em());
     if (plan.ext6_run[X6REP_SEGMENTS]) PTX_TRY(w.segments());
+    if (plan.ext7_run[X7REP_MOSAIC]) PTX_TRY(w.mosaic());
     return 0;
 }
 }  // namespace reports

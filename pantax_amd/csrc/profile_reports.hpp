@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
-// of pantax_hip_profile_ext6 with its row of EXT6_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS and EXT5_REPORTS are closed: the structs they point into keep their size), a sub-struct
+// of pantax_hip_profile_ext7 with its row of EXT7_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS, EXT5_REPORTS and EXT6_REPORTS are closed: the structs they point into keep their size), a sub-struct
 // here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
@@ -50,6 +50,10 @@ struct ReportData {
     struct { std::vector<uint64_t> len, species, cls_off; std::vector<double> x, delta; std::vector<EmClass> cls; std::vector<uint32_t> K, iter; std::vector<int32_t> conv; } em;
     // --strain-segments: per entry e its peak_depth, G_h and the run totals {gap, peak} at [2e ..); its kept segments [seg_off[e], seg_off[e + 1]) in ascending start
     struct { std::vector<uint64_t> peak, hap_len, n_runs, run_len, run_max, seg_off{0}, step, start, len, bases; std::vector<uint32_t> n_steps; std::vector<uint8_t> cls; } sg;
+    // --strain-mosaic: species[18k ..) = the six classes of Q, extra[3k ..) = {n_segments, n_breaks, foreign_steps}, hap[2e ..) = {segments, steps}; K[k] = the
+    // species' rows of the table and its K x K switch counts from pair[pair_off[k]] on; its distinct junctions [jn_off[k], jn_off[k + 1]) as species-local
+    // {node_a, node_b} with their counts, in ascending (node_a, node_b)
+    struct { std::vector<uint64_t> species, extra, hap, pair, pair_off, jn_off, jn_count; std::vector<uint32_t> K, jn_a, jn_b; } mo;
     // --strain-near-miss: species[12k ..) = {orphan, claimed, contested}; the printed candidates rows[row_off[k] .. row_off[k + 1]) in rank order: the
     // haplotype ([hap_names]) and q = {novel, exclusive, all} x {n_nodes, len, covered, bases}
     struct NearMissRow { uint64_t hap; uint64_t q[12]; };

@@ -344,6 +344,42 @@ class Engine:
                                                             p(species) if self.S else None, p(pair_off), len(pair), p(pair) if len(pair) else None))
         return hap, species, pair_off, pair
 
+    def strain_mosaic(self, cand_off, cand_hap, cand_w, junction_cap=None):
+        """Mosaic reads (pantax_hip_strain_mosaic) of the resident reads, binned against the resident db: every counted read of a species of 1 .. 64
+        candidates cut into the fewest stretches that each fit one candidate.  The candidate set of read_strains -> (species uint64 [S, 6, 3]: counted /
+        compatible / mosaic1 / mosaic2 / mosaic3plus / foreign, extra uint64 [S, 3]: n_segments / n_breaks / foreign_steps, hap uint64 [C, 2]: segments /
+        steps of every candidate entry, pair_off uint64 [S+1], pair uint64 [pair_off[-1]]: the K_s x K_s switch counts [left][right], junction uint32
+        [J, 3]: species / node_a / node_b (species-local) in ascending order, junction_count uint64 [J], n_breaks_total); the last axis of species is
+        {n_reads, n_steps, span}.  junction_cap None: sized inside (a second call when the first guess is short); 0: junctions are not collected; a
+        number that is too small raises PantaxHipError with code E_LIMIT."""
+        co = as_c(cand_off, np.uint64)
+        ch = as_c(cand_hap, np.uint32)
+        cw = as_c(cand_w, np.float64)
+        if len(co) != self.S + 1 or len(ch) != int(co[-1]) or len(cw) != len(ch):
+            raise ValueError("strain_mosaic: cand_off needs S + 1 entries and cand_hap / cand_w cand_off[-1] each")
+        cs = _ffi.ReadStrainSet(self.S, co.ctypes.data, ch.ctypes.data if len(ch) else None, cw.ctypes.data if len(cw) else None)
+        species = np.zeros((self.S, _ffi.MOSAIC_CLASSES, 3), dtype=np.uint64)
+        extra = np.zeros((self.S, 3), dtype=np.uint64)
+        hap = np.zeros((len(ch), 2), dtype=np.uint64)
+        pair_off = np.zeros(self.S + 1, dtype=np.uint64)
+        k = np.diff(co.astype(np.int64))
+        pair = np.zeros(int((k[k <= 64] ** 2).sum()), dtype=np.uint64)
+        q = lambda a: p(a) if len(a) else None
+        cap = 1024 if junction_cap is None else int(junction_cap)
+        while True:
+            jn = np.zeros((cap, 3), dtype=np.uint32)
+            jc = np.zeros(cap, dtype=np.uint64)
+            n_j, n_b = C.c_uint64(0), C.c_uint64(0)
+            rc = self.lib.pantax_hip_strain_mosaic(self.ctx, self.db, self.reads, C.byref(cs), q(species), q(extra), q(hap), p(pair_off), len(pair), q(pair),
+                                                   cap, q(jn), q(jc), C.byref(n_j), C.byref(n_b))
+            if rc == _ffi.E_LIMIT and junction_cap is None and cap and int(n_b.value) > cap:
+                cap = int(n_b.value)
+                continue
+            self._check(rc)
+            break
+        n = int(n_j.value)
+        return species, extra, hap, pair_off, pair, jn[:n].copy(), jc[:n].copy(), int(n_b.value)
+
     def strain_read_em(self, cand_off, cand_hap, cand_len, max_iter=1000, tol=1e-6):
         """Read classes and the read-based estimate (pantax_hip_strain_read_em) of the resident reads, binned against the resident db.  The candidate set
         of read_strains with cand_len (uint64 graph bases of every candidate) in place of the weights -> (species uint64 [S, 2, 3]: counted /
@@ -752,7 +788,8 @@ class Engine:
                 strain_depth_file=None, strain_near_miss_file=None, strain_near_miss_top=0, strain_pair_evidence_file=None, strain_fit_file=None,
                 strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42, strain_dropout_file=None,
                 strain_addin_file=None, strain_addin_top=0, strain_em_file=None, strain_em_classes=0, strain_em_iterations=0,
-                strain_segments_file=None, strain_segments_min=0, strain_segments_bridge=None, strain_segments_peak=0):
+                strain_segments_file=None, strain_segments_min=0, strain_segments_bridge=None, strain_segments_peak=0,
+                strain_mosaic_file=None, strain_mosaic_top=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -769,7 +806,9 @@ class Engine:
         strain_em_classes the classes it prints per species (0: 10), strain_em_iterations the iterations of its estimate at most (0: 1000).
         strain_segments_file: path of the segment report (--strain-segments; one rank only), strain_segments_min the bases a chain spans at least
         (0: 1000), strain_segments_bridge the bases between two segments of a chain at most (None: 100; 0 is a bridge of 0 -- the struct holds
-        bridge + 1), strain_segments_peak the integer factor F of peak_depth = max(2, ceil(F x predicted_coverage)) (0: 10; "off": no peak class)."""
+        bridge + 1), strain_segments_peak the integer factor F of peak_depth = max(2, ceil(F x predicted_coverage)) (0: 10; "off": no peak class).
+        strain_mosaic_file: path of the mosaic read report (--strain-mosaic; one rank only), strain_mosaic_top the junctions it prints per species
+        (0: 10; "off": none, and none are collected)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -812,7 +851,7 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
@@ -821,7 +860,9 @@ class Engine:
                                   strain_em_file=enc(strain_em_file), strain_em_classes=int(strain_em_classes), strain_em_iterations=int(strain_em_iterations),
                                   strain_segments_file=enc(strain_segments_file), strain_segments_min=int(strain_segments_min),
                                   strain_segments_bridge=0 if strain_segments_bridge is None else int(strain_segments_bridge) + 1,
-                                  strain_segments_peak=_ffi.SEGMENTS_PEAK_OFF if strain_segments_peak == "off" else int(strain_segments_peak))
+                                  strain_segments_peak=_ffi.SEGMENTS_PEAK_OFF if strain_segments_peak == "off" else int(strain_segments_peak),
+                                  strain_mosaic_file=enc(strain_mosaic_file),
+                                  strain_mosaic_top=_ffi.MOSAIC_TOP_OFF if strain_mosaic_top == "off" else int(strain_mosaic_top))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -1020,6 +1061,45 @@ def segment_chain(seg_class, seg_start, seg_len, seg_n_steps, seg_bases, bridge,
         raise ValueError("segment_chain: refused")
     m = int(m.value)
     return c_cls[:m].copy(), first[:m].copy(), last[:m].copy(), q[:m].copy()
+
+
+def mosaic_walk(masks, w, hap, cap=None):
+    """pantax_hip_mosaic_walk: the greedy cut of ONE walk.  masks uint64 [n]: bit p of masks[i] = the candidate at position p walks step i; w float64 [K],
+    hap uint32 [K]: weight and haplotype index of position p, 1 <= K <= 64 -> (k, foreign_steps, seg_end uint64 [k]: segment j is the steps
+    [seg_end[j-1], seg_end[j]), seg_pos uint32 [k]: the position it is assigned).  A foreign or empty walk has k = 0.  cap: the segments the arrays
+    hold (None: n); a cap below k raises ValueError."""
+    mk = as_c(masks, np.uint64)
+    ww = as_c(w, np.float64)
+    hh = as_c(hap, np.uint32)
+    if len(ww) != len(hh):
+        raise ValueError("mosaic_walk: w and hap are of one length")
+    n = len(mk)
+    cap = n if cap is None else int(cap)
+    seg_end = np.zeros(cap, dtype=np.uint64)
+    seg_pos = np.zeros(cap, dtype=np.uint32)
+    k, fs = C.c_uint64(0), C.c_uint64(0)
+    a = lambda x: p(x) if len(x) else None
+    rc = _ffi.load().pantax_hip_mosaic_walk(n, a(mk), len(ww), a(ww), a(hh), a(seg_end), a(seg_pos), cap, C.byref(k), C.byref(fs))
+    if rc != 0:
+        raise ValueError("mosaic_walk: refused (%d)" % rc)
+    k = int(k.value)
+    return k, int(fs.value), seg_end[:k].copy(), seg_pos[:k].copy()
+
+
+def mosaic_top(node_a, node_b, count, top):
+    """pantax_hip_mosaic_top: the indices of the first `top` junctions in the order count descending, then node_a, then node_b ascending."""
+    na = as_c(node_a, np.uint32)
+    nb = as_c(node_b, np.uint32)
+    ct = as_c(count, np.uint64)
+    n = len(ct)
+    if not (len(na) == len(nb) == n):
+        raise ValueError("mosaic_top: the three arrays are of one length")
+    idx = np.zeros(min(n, int(top)), dtype=np.uint64)
+    m = C.c_uint64(0)
+    a = lambda x: p(x) if len(x) else None
+    if _ffi.load().pantax_hip_mosaic_top(n, a(na), a(nb), a(ct), int(top), a(idx), C.byref(m)) != 0:
+        raise ValueError("mosaic_top: refused")
+    return idx[:int(m.value)].copy()
 
 
 def addin_donor(K, x_base, x_add):
