@@ -1212,6 +1212,13 @@ int pantax_hip_strain_node_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, double 
  * the first filter dropped included; zeros for the haplotypes of a species the step skipped.  [H] each; either output may be NULL. */
 int pantax_hip_strain_hap_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, uint32_t *nnz_out, double *mean_filtered_out);
 
+/* The per-node results of the same step when it went through the split node pass (option node_pass=split, or a step that is not eligible for the
+ * fused pass): the covered bases of every node (node_base_cov) and the node abundances bases / length, [V] each, as the device holds them.  When the
+ * step sampled rows (sample_nodes), a11 has edited `ab`: the nodes it did not choose read 0.  The call synchronises and copies; it launches nothing.
+ * PANTAX_HIP_E_STATE before the first collected step, while enqueued steps are not yet collected, when the step collected last took the fused node
+ * pass (which stores neither array), and once a later pantax_hip_node_coverage has counted the covered bases itself.  Either output may be NULL. */
+int pantax_hip_strain_node_cov(pantax_hip_ctx *ctx, pantax_hip_db *db, uint32_t *cov_out, double *ab_out);
+
 /* ---- measurement: HIP-event timings of kernels launched on the ctx stream ---------------- */
 int pantax_hip_timing_enable(pantax_hip_ctx *ctx, int on);
 int pantax_hip_timing_reset(pantax_hip_ctx *ctx);

@@ -18,7 +18,7 @@ SYMBOLS = [
     "pantax_hip_db_upload", "pantax_hip_db_upload_parts", "pantax_hip_db_free", "pantax_hip_reads_upload", "pantax_hip_reads_free",
     "pantax_hip_bin_reads", "pantax_hip_species_profile", "pantax_hip_db_reset", "pantax_hip_abundance_filter",
     "pantax_hip_trio_index", "pantax_hip_trio_get", "pantax_hip_node_coverage",
-    "pantax_hip_strain_profile", "pantax_hip_strain_node_stats", "pantax_hip_strain_hap_stats", "pantax_hip_pao_solve", "pantax_hip_pao_solve_batch", "pantax_hip_profile", "pantax_hip_profile_step", "pantax_hip_profile_step_enqueue", "pantax_hip_profile_step_collect", "pantax_hip_trio_index_prefetch", "pantax_hip_sort_rows",
+    "pantax_hip_strain_profile", "pantax_hip_strain_node_stats", "pantax_hip_strain_hap_stats", "pantax_hip_strain_node_cov", "pantax_hip_pao_solve", "pantax_hip_pao_solve_batch", "pantax_hip_profile", "pantax_hip_profile_step", "pantax_hip_profile_step_enqueue", "pantax_hip_profile_step_collect", "pantax_hip_trio_index_prefetch", "pantax_hip_sort_rows",
     "pantax_hip_scan", "pantax_hip_radix_sort", "pantax_hip_fill",
     "pantax_hip_sample_ranks", "pantax_hip_chacha_block", "pantax_hip_gaf_filter", "pantax_hip_db_save_images", "pantax_hip_db_load_images",
     "pantax_hip_gaf_load", "pantax_hip_gaf_load_device", "pantax_hip_reads_load_gaf", "pantax_hip_reads_set_flags", "pantax_hip_gaf_view", "pantax_hip_gaf_ids", "pantax_hip_gaf_free",

@@ -161,6 +161,7 @@ int strain_enqueue(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const 
     if (fused) lb.S = S;
     else
     PTX_TRY(node_stats_launch(ctx, db, &lb, cfg->min_depth, skip_absent, readers_clean));                              // abundances + per-species stats
+    db->node_cov_enq[slot] = fused ? Db::NodeCov::fused : resident ? Db::NodeCov::split : Db::NodeCov::replaced;   // (a stage caller's d_cov is count_launch's)
     if (readers_clean) { db->cov.readers_cleaned(); clean_guard.armed = false; }   // (the arena no longer holds a coverage result)
     mark();
     PTX_TRY(row_sample_apply(ctx, db, &lb, cfg->sample_nodes));
@@ -214,6 +215,7 @@ int strain_finish(Ctx *ctx, Db *db, const pantax_hip_strain_config *cfg, const u
     PTX_TRY(fetch_arena_wait(ctx, db, lb, L, r, slot));                                         // the one host round trip
     if (after_wait) after_wait(after_wait_arg);
     db->stats_slot = slot;
+    db->node_cov = db->node_cov_enq[slot];
     lb.n_rows = r.counts[0]; lb.K = r.counts[1];
     lb.h_sp_pat_off.assign(r.sp_pat_off, r.sp_pat_off + S + 1);
 
@@ -359,6 +361,20 @@ int pantax_hip_strain_hap_stats(pantax_hip_ctx *ctx, pantax_hip_db *db, uint32_t
     const uint8_t *b = db->h_arena[db->stats_slot].p;   // (nothing in flight: no download is writing either slot)
     if (nnz_out) std::memcpy(nnz_out, b + L.nnz, sizeof(uint32_t) * db->H);
     if (mean_filtered_out) std::memcpy(mean_filtered_out, b + L.meanf, sizeof(double) * db->H);
+    return 0;
+}
+
+int pantax_hip_strain_node_cov(pantax_hip_ctx *ctx, pantax_hip_db *db, uint32_t *cov_out, double *ab_out) {
+    if (!ctx || !db) return PANTAX_HIP_E_INVALID;
+    PTX_ENTER(ctx);
+    if (db->stats_slot < 0 || db->node_cov == Db::NodeCov::none) return fail(ctx, PANTAX_HIP_E_STATE, "strain_node_cov: no strain step of this db has been collected");
+    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "strain_node_cov: %d enqueued step(s) of this db have not been collected (their node pass rewrites the arrays)", db->step_inflight);
+    if (db->node_cov == Db::NodeCov::fused) return fail(ctx, PANTAX_HIP_E_STATE, "strain_node_cov: the step collected last took the fused node pass, which stores neither array (option node_pass=split)");
+    if (db->node_cov == Db::NodeCov::replaced) return fail(ctx, PANTAX_HIP_E_STATE, "strain_node_cov: a stage call has counted the covered bases since (pantax_hip_node_coverage returns them)");
+    if (db->d_cov.n < db->V || db->lad.d_ab.n < db->V) return fail(ctx, PANTAX_HIP_E_STATE, "strain_node_cov: the per-node arrays of the step are gone");
+    if (cov_out) PTX_TRY(download(ctx, cov_out, db->d_cov.p, db->V));
+    if (ab_out) PTX_TRY(download(ctx, ab_out, db->lad.d_ab.p, db->V));
+    PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }
 

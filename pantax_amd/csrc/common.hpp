@@ -484,6 +484,11 @@ struct Db {
     hipEvent_t ev_step[2] = {nullptr, nullptr};   // recorded behind the last download of the step that uses the slot
     pantax_hip_step_config step_cfg[2];
     int stats_slot = -1;             // h_arena slot of the step collected last (pantax_hip_strain_node_stats), -1: none yet
+    // what d_cov and the step's d_ab hold (pantax_hip_strain_node_cov): nothing, the per-node results of a step on the split node pass (node_stats_launch
+    // with the covered-base counts folded in), nothing because the step took the fused pass, or the counts of a later stage call (count_launch)
+    enum class NodeCov : uint8_t { none, split, fused, replaced };
+    NodeCov node_cov_enq[2] = {NodeCov::none, NodeCov::none};   // per result slot: the pass the enqueued step took
+    NodeCov node_cov = NodeCov::none;                            // ... of the step collected last, set beside stats_slot
     int step_enq = 0, step_col = 0, step_inflight = 0;   // slot of the next enqueue / the next collect; steps enqueued and not yet collected
     hipEvent_t ev_trio_free = nullptr;   // recorded behind the last reader of the unique-trio tables in a step: the next step's rebuild waits for this (TrioState::free_event_valid),
                                          // not for the whole previous step (its row sort and LPs run beside the rebuild)

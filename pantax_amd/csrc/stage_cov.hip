@@ -816,6 +816,7 @@ static int long_launch(Ctx *ctx, Db *db, Reads *rd, const uint8_t *d_act, bool t
 // node_base_cov of the stage call (the resident step leaves it to the node statistics pass: defer_count)
 static int count_launch(Ctx *ctx, Db *db) {
     PTX_HIP(ctx, db->d_cov.alloc(db->V));
+    db->node_cov = Db::NodeCov::replaced;                        // (no longer the counts of a resident step: pantax_hip_strain_node_cov)
     KTimer t(ctx, "popcount_kernel");
     if (long_node_shape(db->L, db->V, ctx->cfg.ncs_prefix_min, ctx->cfg.ncs_no_prefix))
         hipLaunchKernelGGL(popcount_long_kernel, dim3(grid_for((db->V + 63) / 64, 4, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, db->V,

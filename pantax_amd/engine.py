@@ -982,6 +982,12 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_hap_stats(self.ctx, self.db, p(nnz), p(meanf)))
         return nnz[: self.H], meanf[: self.H]
 
+    def strain_node_cov(self):
+        """pantax_hip_strain_node_cov: (cov [V] uint32, ab [V] float64) of the strain step collected last, when it took the split node pass"""
+        cov, ab = np.zeros(max(self.V, 1), dtype=np.uint32), np.zeros(max(self.V, 1))
+        self._check(self.lib.pantax_hip_strain_node_cov(self.ctx, self.db, p(cov), p(ab)))
+        return cov[: self.V], ab[: self.V]
+
     def timing_enable(self, on=True):
         self._check(self.lib.pantax_hip_timing_enable(self.ctx, int(on)))
 
