@@ -504,6 +504,59 @@ int pantax_hip_strain_near_miss(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
 int pantax_hip_near_miss_rank(uint32_t n_cand, const uint32_t *cand_hap, const uint64_t *cand_out /*[n_cand][2][4]*/, uint32_t top,
                               uint32_t *rank_out /*[n_cand]*/, uint32_t *n_out);
 
+/* ---- read rescue (the --strain-rescue report; not a stage of the reference): for every read that fits no reported strain, whether a single unreported
+ * candidate of the db walks all of its nodes, and which one.  Sel_s, Cand_s, K_s, J_s and the PANTAX_HIP_E_INVALID cases are those of
+ * pantax_hip_strain_near_miss above; the state rule (reads binned against db, else PANTAX_HIP_E_STATE), a counted read and Q(r) = (1, n_steps, span) are
+ * those of pantax_hip_strain_read_support.  On any error the outputs are left as given.
+ * A species is OPEN when K_s + J_s <= 64 (K_s = 0 and J_s = 0 are both allowed); a wider species is SKIPPED: only `counted` is written for it.
+ * For a counted read r of an open species with steps v_1 .. v_n in walk order (a node visited twice is two steps):
+ *   M(v) = the members of Sel_s whose walk visits v,  N(v) = the same over Cand_s (containment over node sets, as everywhere else);
+ *   C(r) = the intersection of M(v_i),  D(r) = the intersection of N(v_i).
+ * Every counted read of an open species is exactly one of
+ *   compatible  C(r) is not empty;
+ *   foreign     some M(v_i) is empty (with K_s = 0: every counted read);
+ *   mosaic      C(r) is empty and no M(v_i) is: the k >= 2 of pantax_hip_strain_mosaic.
+ * Unexplained = foreign or mosaic.  An unexplained read is RESCUED when D(r) is not empty and also CONTESTED when |D(r)| >= 2.  A foreign read that is
+ * not rescued is foreign_novel when some step has M(v_i) and N(v_i) both empty (a node nobody of either list walks), else foreign_patchwork (every node
+ * is walked by a reported strain or a candidate, but no single haplotype walks them all).
+ * Outputs, all u64, exact integers independent of any order, Q in the order { n_reads, n_steps, span }:
+ *   species_out [S][9][3] = the sums of Q over { counted, compatible, foreign, foreign_rescued, foreign_patchwork, foreign_novel, mosaic, mosaic_rescued,
+ *     contested };
+ *   step_out [S][3] = { foreign_steps = the steps with M empty, claimed_steps = those of them with N not empty, novel_steps = those with N empty };
+ *   cand_out [J][3][3] in the order of cand_hap = { rescued[c] = the sum of Q over unexplained reads with c in D(r), alone[c] = over D(r) = {c},
+ *     from_foreign[c] = over foreign reads with c in D(r) };
+ *   cand_steps_out [J] = the steps with M(v) empty and c in N(v).
+ * For every open species: counted = compatible + foreign + mosaic; foreign = foreign_rescued + foreign_patchwork + foreign_novel; the sum of alone over
+ * the species' candidates + contested = foreign_rescued + mosaic_rescued (all three numbers of Q); alone <= rescued and from_foreign <= rescued;
+ * foreign_steps = claimed_steps + novel_steps; the sum of cand_steps >= claimed_steps, equal when J_s = 1; J_s = 0 gives foreign = foreign_novel and no
+ * rescue; novel_steps > 0 exactly when foreign_novel.n_reads > 0.  On the same Sel: counted, compatible, foreign and foreign_steps are those of
+ * pantax_hip_strain_mosaic with cand = Sel (whatever the weights), mosaic = its mosaic1 + mosaic2 + mosaic3plus; compatible + foreign_rescued +
+ * mosaic_rescued = counted - unexplained of pantax_hip_strain_read_support over the list Sel ++ Cand.
+ * The option read_strain_route=walk takes every species' membership from the walks of Sel_s ++ Cand_s. */
+#define PANTAX_HIP_RESCUE_CLASSES 9
+int pantax_hip_strain_read_rescue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_near_miss_set *sel,
+                                  uint64_t *species_out /*[S][9][3]*/, uint64_t *step_out /*[S][3]*/, uint64_t *cand_out /*[J][3][3]*/,
+                                  uint64_t *cand_steps_out /*[J]*/);
+/* host helper, no ctx and no GPU: the classes above for ONE walk of n steps.  Bit p of sel_masks[i] = the member at position p of Sel walks step i, bit p
+ * of cand_masks[i] the same over Cand; bits at and above K or J are ignored.  *class_out = one of the six values below, *d_out = D(r) (bit p = position
+ * p of Cand), steps_out [3] = { foreign_steps, claimed_steps, novel_steps } of the walk.  PANTAX_HIP_E_INVALID for a null argument, n = 0 or K + J > 64. */
+enum {
+    PANTAX_HIP_RESCUE_COMPATIBLE = 0,
+    PANTAX_HIP_RESCUE_FOREIGN_RESCUED = 1,
+    PANTAX_HIP_RESCUE_FOREIGN_PATCHWORK = 2,
+    PANTAX_HIP_RESCUE_FOREIGN_NOVEL = 3,
+    PANTAX_HIP_RESCUE_MOSAIC_RESCUED = 4,
+    PANTAX_HIP_RESCUE_MOSAIC_UNRESCUED = 5
+};
+int pantax_hip_rescue_walk(uint64_t n, const uint64_t *sel_masks, const uint64_t *cand_masks, uint32_t K, uint32_t J, uint32_t *class_out, uint64_t *d_out,
+                           uint64_t *steps_out /*[3]*/);
+/* host helper, no ctx and no GPU: the order in which one species' candidates are printed.  cand_hap [n_cand] and cand_out [n_cand][3][3] are the species'
+ * stretch of pantax_hip_strain_read_rescue.  rank_out [n_cand] receives candidate positions ordered by rescued.span descending, then rescued.n_reads
+ * descending, then haplotype index ascending; candidates with rescued.n_reads = 0 are left out; only the first `top` are kept (0 keeps all); *n_out =
+ * the number written.  A null pointer among the four (whatever n_cand): PANTAX_HIP_E_INVALID, nothing written. */
+int pantax_hip_rescue_rank(uint32_t n_cand, const uint32_t *cand_hap, const uint64_t *cand_out /*[n_cand][3][3]*/, uint32_t top,
+                           uint32_t *rank_out /*[n_cand]*/, uint32_t *n_out);
+
 /* ---- pairwise strain distinguishability of a db (the --db-pairs mode; not a stage of the reference): the strain step's LP has one 0/1 column per haplotype
  * over the nodes of its species (profile.rs:1333-1342); two haplotypes with equal columns cannot be told apart by it, and two whose columns differ on 300
  * bases of nodes only where those 300 bases are covered.  This call says, before any sample, which selected haplotypes of the db can be separated and by how
@@ -1118,6 +1171,26 @@ typedef struct {
     const char *strain_mosaic_file;
     uint64_t strain_mosaic_top;   /* junctions printed per species: 0 reads as 10, and so does a struct that does not hold the field; PANTAX_HIP_MOSAIC_TOP_OFF = no junction rows, none collected */
 } pantax_hip_profile_ext7;
+/* ... and once more: pantax_hip_profile_ext7 is closed at strain_mosaic_top (a committed host check holds its 136 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the seventh version.  A caller fills v7.v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext8) and
+ * passes &ext8.v7.v6.v5.v4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40-, 48-, 64-, 88-, 120- or 136-byte struct runs with the fields
+ * below off.  A later output is a field appended here. */
+typedef struct {
+    pantax_hip_profile_ext7 v7;   /* v7.v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext8) */
+    /* --strain-rescue: path of the read rescue report (pantax_hip_strain_read_rescue over every group of species, right behind the group's strain step;
+     * NULL, "" or "None" = off).  Sel_s = the species' rows of strain_abundance.txt; Cand_s = the candidates of the near-miss report, first in the order
+     * of pantax_hip_near_miss_rank with top = 0, then the remaining ones in ascending haplotype index (a candidate without novel bases can still rescue a
+     * mosaic read), cut to 64 - K_s; a species of more than 64 rows is skipped.  TSV with a header: species_taxid, strain_taxid, genome_ID, rank, class,
+     * n_reads, n_steps, span, fraction, alone_reads, foreign_reads, foreign_steps, claimed_steps, stage, unique_trio_nodes_fraction; f64 in shortest
+     * round-trip digits, "-" where a column does not apply or a fraction has no denominator.  (1) per species in shard order its candidates in the order
+     * of pantax_hip_rescue_rank with top = strain_rescue_top, rank from 1, class "candidate": Q of rescued, fraction = rescued.n_reads / (foreign +
+     * mosaic).n_reads, alone.n_reads, from_foreign.n_reads, claimed_steps = cand_steps; strain_taxid, genome_ID, stage and unique_trio_nodes_fraction as
+     * the near-miss report prints them.  (2) per species in shard order: "counted", "compatible", "foreign", "foreign_rescued", "foreign_patchwork",
+     * "foreign_novel", "mosaic", "mosaic_rescued", "contested" with Q and fraction = n_reads / counted.n_reads; the foreign row carries foreign_steps and
+     * claimed_steps, the foreign_novel row novel_steps in foreign_steps; a skipped species: "counted" and "skipped".  Same rules as strain_fit_file. */
+    const char *strain_rescue_file;
+    uint64_t strain_rescue_top;   /* candidates printed per species: 0 reads as 5, and so does a struct that does not hold the field */
+} pantax_hip_profile_ext8;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

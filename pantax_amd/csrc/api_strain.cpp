@@ -475,17 +475,24 @@ int pantax_hip_pao_solve(pantax_hip_ctx *ctx, uint32_t n_nodes, const int64_t *n
     return 0;
 }
 
+// the state every pass over the reads' candidate masks needs (read strains, read support, read classes, mosaic reads, read rescue): reads binned and grouped
+// against this db, a db with graphs, no step in flight
+static int check_read_pass_state(pantax_hip_ctx *ctx, const pantax_hip_db *db, const pantax_hip_reads *reads, const char *what) {
+    if (!reads->state.binned_against(db->uid) || !reads->state.grouped())
+        return fail(ctx, PANTAX_HIP_E_STATE, "%s: call pantax_hip_bin_reads on these reads against this db first", what);
+    if (db->d_path_nodes.p == nullptr || db->h_path_off.size() != db->H + 1)
+        return fail(ctx, PANTAX_HIP_E_STATE, "%s: the db was uploaded without graphs (ranges only)", what);
+    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "%s: %d enqueued step(s) of this db have not been collected", what, db->step_inflight);
+    return 0;
+}
+
 // what the three passes over the reads' candidate masks (read strains, read support, read classes) share: the state they need, a candidate set in range and without repeats -> every species'
 // candidates in ascending haplotype order (bit order = the order of the sum and of the tie rule), ord[c] = the caller's entry of sorted candidate c
 static int check_read_strain_set(pantax_hip_ctx *ctx, const pantax_hip_db *db, const pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
                                  const char *what, std::vector<uint32_t> &hap, std::vector<double> &w, std::vector<uint64_t> &ord_all, bool need_w = true) {
     const uint32_t S = db->S;
     if (cand->n_species != S) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: the candidate set has %u species, the db %u", what, cand->n_species, S);
-    if (!reads->state.binned_against(db->uid) || !reads->state.grouped())
-        return fail(ctx, PANTAX_HIP_E_STATE, "%s: call pantax_hip_bin_reads on these reads against this db first", what);
-    if (db->d_path_nodes.p == nullptr || db->h_path_off.size() != db->H + 1)
-        return fail(ctx, PANTAX_HIP_E_STATE, "%s: the db was uploaded without graphs (ranges only)", what);
-    if (db->step_inflight) return fail(ctx, PANTAX_HIP_E_STATE, "%s: %d enqueued step(s) of this db have not been collected", what, db->step_inflight);
+    PTX_TRY(check_read_pass_state(ctx, db, reads, what));
     if (cand->cand_off[0] != 0) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: cand_off[0] = %llu", what, (unsigned long long)cand->cand_off[0]);
     for (uint32_t s = 0; s < S; ++s)
         if (cand->cand_off[s + 1] < cand->cand_off[s]) return fail(ctx, PANTAX_HIP_E_INVALID, "%s: cand_off decreases at species %u", what, s);
@@ -796,6 +803,18 @@ int pantax_hip_strain_near_miss(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
     if ((sel->cand_off[db->S] && !cand_out) || (db->S && !species_out)) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_near_miss: null output array");
     PTX_TRY(check_stage_coverage(ctx, db, "strain_near_miss"));
     return near_miss_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->cand_off, sel->cand_hap, cand_out, species_out);
+}
+
+int pantax_hip_strain_read_rescue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_near_miss_set *sel, uint64_t *species_out,
+                                  uint64_t *step_out, uint64_t *cand_out, uint64_t *cand_steps_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !reads || !sel || !sel->sel_off || !sel->cand_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_rescue: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_near_miss_set(ctx, db, "strain_read_rescue", sel));
+    PTX_TRY(check_read_pass_state(ctx, db, reads, "strain_read_rescue"));
+    if ((sel->cand_off[db->S] && (!cand_out || !cand_steps_out)) || (db->S && (!species_out || !step_out)))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_read_rescue: null output array");
+    return rescue_launch(ctx, db, reads, sel->sel_off, sel->sel_hap, sel->cand_off, sel->cand_hap, species_out, step_out, cand_out, cand_steps_out);
 }
 
 int pantax_hip_strain_addin(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_near_miss_set *sel, double *x_out, double *obj_out, int32_t *status_out,

@@ -701,6 +701,10 @@ int read_support_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
 int mosaic_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, const uint64_t *entry_of,
                   const uint64_t *pair_off, uint64_t *species_out, uint64_t *extra_out, uint64_t *hap_out, uint64_t *pair_out, uint64_t junction_cap,
                   uint32_t *junction_out, uint64_t *junction_count_out, uint64_t *n_junctions_out, uint64_t *n_breaks_total_out);
+// stage_rescue.hip (pantax_hip_strain_read_rescue): both sets validated by the caller; species_out [S][9][3], step_out [S][3], cand_out [J][3][3] and
+// cand_steps_out [J] in the caller's order of cand_hap
+int rescue_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *cand_off, const uint32_t *cand_hap,
+                  uint64_t *species_out, uint64_t *step_out, uint64_t *cand_out, uint64_t *cand_steps_out);
 // stage_read_em.hip (pantax_hip_strain_read_em): candidates of every species in ascending haplotype order with their lengths, entry_of[c] = the caller's entry
 // of sorted candidate c; all validated by the caller.  Outputs as the stage call's; they are written only when the call succeeds (cls_off_out: also on E_LIMIT)
 int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const uint64_t *cand_len, const uint64_t *entry_of, uint32_t max_iter,

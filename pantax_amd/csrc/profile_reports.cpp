@@ -2,7 +2,7 @@
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
 // (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
-// report, the add-one report, the read class report, the segment report and the mosaic read report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT7_REPORTS).
+// report, the add-one report, the read class report, the segment report, the mosaic read report and the read rescue report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT8_REPORTS).
 #include <algorithm>
 #include <cmath>
 #include <fstream>
@@ -11,6 +11,7 @@
 #include "mosaic_plan.hpp"
 #include "profile_run.hpp"
 #include "read_em_plan.hpp"
+#include "rescue_plan.hpp"
 
 namespace ptx {
 namespace {
@@ -395,6 +396,45 @@ int group_near_miss(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const
     PTX_TRY(pantax_hip_strain_evidence(run.ctx, db, &printed, e_hap.data(), e_species.data()));
     for (size_t i = 0; i < p_hap.size(); ++i) std::copy(e_hap.begin() + 8 * i, e_hap.begin() + 8 * i + 4, nm.rows[row0 + i].q + 8);   // all
     run.lap("  strain near misses");
+    return 0;
+}
+// --strain-rescue, beside the mosaic call: Sel_s = the group's rows; Cand_s = the group's candidates (rescue_candidates: the rank order of
+// pantax_hip_near_miss_rank with top = 0, then the rest in ascending haplotype index, cut to 64 - K_s; a species of more than 64 rows goes in with its rows
+// alone and comes back skipped).  The candidates pantax_hip_rescue_rank keeps are the ones printed
+int group_rescue(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh, GroupCand &gc) {
+    auto &rc = sh.rep.rc;
+    const uint32_t Sg = k1 - k0;
+    PTX_TRY(group_candidates(run, db, k0, k1, g, sh, gc));
+    std::vector<uint64_t> c_off(Sg + 1, 0);
+    std::vector<uint32_t> c_hap, rank;
+    for (uint32_t k = 0; k < Sg; ++k) {
+        const uint64_t c0 = gc.off[k], n = gc.off[k + 1] - c0, K = g.off[k + 1] - g.off[k];
+        uint32_t kept = 0;
+        rank.assign(n ? n : 1, 0);
+        if (n && K < RESCUE_MAX_LIST) PTX_TRY(pantax_hip_near_miss_rank((uint32_t)n, gc.hap.data() + c0, gc.out.data() + 8 * c0, 0, rank.data(), &kept));
+        for (const uint32_t c : rescue_candidates(K, (uint32_t)n, gc.hap.data() + c0, rank.data(), kept)) c_hap.push_back(gc.hap[c0 + c]);
+        c_off[k + 1] = c_hap.size();
+        rc.open[k0 + k] = K + (c_off[k + 1] - c_off[k]) <= RESCUE_MAX_LIST ? 1 : 0;
+    }
+    const pantax_hip_near_miss_set set{Sg, g.off.data(), g.hap.data(), c_off.data(), c_hap.data()};
+    std::vector<uint64_t> out(9 * c_hap.size()), steps(c_hap.size());
+    PTX_TRY(pantax_hip_strain_read_rescue(run.ctx, db, in.reads.rd, &set, rc.species.data() + 3 * RES_N_CLASSES * (size_t)k0, rc.step.data() + 3 * (size_t)k0,
+                                          out.data(), steps.data()));
+    for (uint32_t k = 0; k < Sg; ++k) {
+        const uint64_t c0 = c_off[k], n = c_off[k + 1] - c0;
+        uint32_t kept = 0;
+        rank.assign(n ? n : 1, 0);
+        if (n) PTX_TRY(pantax_hip_rescue_rank((uint32_t)n, c_hap.data() + c0, out.data() + 9 * c0, run.p.rep.rs_top, rank.data(), &kept));
+        for (uint32_t i = 0; i < kept; ++i) {
+            ReportData::RescueRow r{};
+            r.hap = sh.hap_off[k0 + k] + c_hap[c0 + rank[i]];
+            std::copy(out.begin() + 9 * (c0 + rank[i]), out.begin() + 9 * (c0 + rank[i]) + 9, r.q);
+            r.steps = steps[c0 + rank[i]];
+            rc.rows.push_back(r);
+        }
+        rc.row_off[k0 + k + 1] = rc.rows.size();
+    }
+    run.lap("  strain read rescue");
     return 0;
 }
 
@@ -921,6 +961,41 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-rescue: per species of the shard, in the order it went through the device, the candidates group_rescue kept, in rank order; then the nine
+    // classes of every species.  strain_taxid / genome_ID / stage / unique_trio_nodes_fraction as the near-miss report prints them
+    int rescue() const {
+        const auto &rc = rep.rc;
+        return file(run.p.rep.ext8_path[X8REP_RESCUE],
+                    "species_taxid\tstrain_taxid\tgenome_ID\trank\tclass\tn_reads\tn_steps\tspan\tfraction\talone_reads\tforeign_reads\tforeign_steps\tclaimed_steps\tstage\tunique_trio_nodes_fraction\n",
+                    "strain read rescue report", [&](std::ofstream &f) {
+            const auto frac = [](uint64_t n, uint64_t of) { return of ? fmt_f64((double)n / (double)of) : std::string("-"); };
+            const auto sp = [&](uint32_t k, int cls) { return rc.species.data() + 3 * RES_N_CLASSES * (size_t)k + 3 * cls; };
+            for (uint32_t k = 0; k < Su; ++k)
+                for (uint64_t i = rc.row_off[k]; i < rc.row_off[k + 1]; ++i) {
+                    const ReportData::RescueRow &r = rc.rows[i];
+                    const GenomeRow *gr = genome_of(r.hap);
+                    const pantax_hip_hap_metrics &m = sh.met[r.hap];
+                    f << species(k) << '\t' << (gr ? gr->strain_taxid : std::string()) << '\t' << (gr ? gr->genome_id : std::string()) << '\t' << (i - rc.row_off[k]) + 1 << "\tcandidate\t"
+                      << r.q[0] << '\t' << r.q[1] << '\t' << r.q[2] << '\t' << frac(r.q[0], sp(k, RES_FOREIGN)[0] + sp(k, RES_MOSAIC)[0]) << '\t' << r.q[3] << '\t' << r.q[6] << "\t-\t"
+                      << r.steps << '\t' << near_miss_stage(m) << '\t' << ((m.has & PANTAX_HIP_HAS_FRACTION) ? fmt_f64(m.unique_trio_nodes_fraction) : std::string("-")) << '\n';
+                }
+            const char *const of_species[RES_N_CLASSES] = {"counted", "compatible", "foreign", "foreign_rescued", "foreign_patchwork", "foreign_novel", "mosaic", "mosaic_rescued", "contested"};
+            for (uint32_t k = 0; k < Su; ++k) {
+                const std::string head = species_head(k) + "\t-\t";
+                const uint64_t *st = rc.step.data() + 3 * (size_t)k;
+                for (int c = 0; c < (rc.open[k] ? (int)RES_N_CLASSES : 1); ++c) {   // a skipped species: counted only
+                    const uint64_t *q = sp(k, c);
+                    f << head << of_species[c] << '\t' << q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << frac(q[0], sp(k, RES_COUNTED)[0]) << "\t-\t-\t";
+                    if (c == RES_FOREIGN) f << st[0] << '\t' << st[1];
+                    else if (c == RES_FOREIGN_NOVEL) f << st[2] << "\t-";
+                    else f << "-\t-";
+                    f << "\t-\t-\n";
+                }
+                if (!rc.open[k]) f << head << "skipped\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+            }
+            return 0;
+        });
+    }
     // --strain-pair-evidence: per species of the shard, in the order it went through the device, for every two of its rows a < b (ascending haplotype index)
     // what both walk (shared) and what only a, only b walks, as {n_nodes, len, covered, bases} with depth and breadth
     int pair_evidence() const {
@@ -988,6 +1063,9 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.ext5_run[X5REP_EM]) {
         rep.em.species.assign(6 * (size_t)Su, 0); rep.em.cls_off.assign(Su + 1, 0); rep.em.K.assign(Su, 0); rep.em.iter.assign(Su, 0); rep.em.conv.assign(Su, 0); rep.em.delta.assign(Su, 0.0);
     }
+    if (plan.ext8_run[X8REP_RESCUE]) {
+        rep.rc.species.assign(3 * RES_N_CLASSES * (size_t)Su, 0); rep.rc.step.assign(3 * (size_t)Su, 0); rep.rc.row_off.assign(Su + 1, 0); rep.rc.open.assign(Su, 0);
+    }
     if (plan.ext7_run[X7REP_MOSAIC]) {
         rep.mo.species.assign(3 * MOS_N_CLASSES * (size_t)Su, 0); rep.mo.extra.assign(3 * (size_t)Su, 0); rep.mo.pair_off.assign(Su, 0); rep.mo.K.assign(Su, 0); rep.mo.jn_off.assign(Su + 1, 0);
     }
@@ -1010,6 +1088,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.run[REP_READ_SUPPORT]) PTX_TRY(group_read_support(run, in, db, k0, k1, g, sh));
     if (plan.ext5_run[X5REP_EM]) PTX_TRY(group_read_em(run, in, db, k0, k1, g, sh));
     if (plan.ext7_run[X7REP_MOSAIC]) PTX_TRY(group_mosaic(run, in, db, k0, k1, g, sh));
+    if (plan.ext8_run[X8REP_RESCUE]) PTX_TRY(group_rescue(run, in, db, k0, k1, g, sh, gc));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh, gc));
     return 0;
@@ -1034,6 +1113,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext5_run[X5REP_EM]) PTX_TRY(w.read_em());
     if (plan.ext6_run[X6REP_SEGMENTS]) PTX_TRY(w.segments());
     if (plan.ext7_run[X7REP_MOSAIC]) PTX_TRY(w.mosaic());
+    if (plan.ext8_run[X8REP_RESCUE]) PTX_TRY(w.rescue());
     return 0;
 }
 }  // namespace reports

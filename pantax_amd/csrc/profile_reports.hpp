@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
-// of pantax_hip_profile_ext7 with its row of EXT7_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS, EXT5_REPORTS and EXT6_REPORTS are closed: the structs they point into keep their size), a sub-struct
+// of pantax_hip_profile_ext8 with its row of EXT8_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS, EXT5_REPORTS, EXT6_REPORTS and EXT7_REPORTS are closed: the structs they point into keep their size), a sub-struct
 // here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
@@ -54,6 +54,11 @@ struct ReportData {
     // species' rows of the table and its K x K switch counts from pair[pair_off[k]] on; its distinct junctions [jn_off[k], jn_off[k + 1]) as species-local
     // {node_a, node_b} with their counts, in ascending (node_a, node_b)
     struct { std::vector<uint64_t> species, extra, hap, pair, pair_off, jn_off, jn_count; std::vector<uint32_t> K, jn_a, jn_b; } mo;
+    // --strain-rescue: species[27k ..) = the nine classes of Q, step[3k ..) = {foreign_steps, claimed_steps, novel_steps}, open[k] = the species went through
+    // the call with K_s + J_s <= 64; the printed candidates rows[row_off[k] .. row_off[k + 1]) in rank order: the haplotype ([hap_names]), q = {rescued,
+    // alone, from_foreign} x Q and its steps
+    struct RescueRow { uint64_t hap; uint64_t q[9]; uint64_t steps; };
+    struct { std::vector<uint64_t> species, step, row_off; std::vector<uint8_t> open; std::vector<RescueRow> rows; } rc;
     // --strain-near-miss: species[12k ..) = {orphan, claimed, contested}; the printed candidates rows[row_off[k] .. row_off[k + 1]) in rank order: the
     // haplotype ([hap_names]) and q = {novel, exclusive, all} x {n_nodes, len, covered, bases}
     struct NearMissRow { uint64_t hap; uint64_t q[12]; };

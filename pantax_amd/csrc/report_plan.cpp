@@ -29,7 +29,7 @@ template <class Ext, class T> bool ext_value(const pantax_hip_profile_ext *ext, 
     std::memcpy(&value, reinterpret_cast<const char *>(ext) + at, sizeof(value));
     return true;
 }
-// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2 / _ext3 / _ext4 / _ext5 / _ext6 / _ext7, which begin with it)
+// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2 / _ext3 / _ext4 / _ext5 / _ext6 / _ext7 / _ext8, which begin with it)
 template <class Ext> const char *ext_field(const pantax_hip_profile_ext *ext, const char *Ext::*field) {
     const char *value = nullptr;
     return ext_value(ext, field, value) ? value : nullptr;
@@ -65,6 +65,7 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
     for (int i = 0; i < N_EXT5_REPORTS; ++i) { plan.ext5_path[i].clear(); plan.ext5_want[i] = plan.ext5_run[i] = false; }
     for (int i = 0; i < N_EXT6_REPORTS; ++i) { plan.ext6_path[i].clear(); plan.ext6_want[i] = plan.ext6_run[i] = false; }
     for (int i = 0; i < N_EXT7_REPORTS; ++i) { plan.ext7_path[i].clear(); plan.ext7_want[i] = plan.ext7_run[i] = false; }
+    for (int i = 0; i < N_EXT8_REPORTS; ++i) { plan.ext8_path[i].clear(); plan.ext8_want[i] = plan.ext8_run[i] = false; }
     if (ext && (ext->struct_size < 8 || ext->struct_size % 8 != 0)) {
         err = "profile: pantax_hip_profile_ext.struct_size " + std::to_string((unsigned long long)ext->struct_size) + " (a multiple of 8, at least 8)";
         return false;
@@ -83,8 +84,10 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
         if (!plan_path(EXT6_REPORTS[i], ext_field(ext, EXT6_REPORTS[i].field), W, sharded, plan.ext6_path[i], plan.ext6_want[i], err)) return false;
     for (int i = 0; i < N_EXT7_REPORTS; ++i)
         if (!plan_path(EXT7_REPORTS[i], ext_field(ext, EXT7_REPORTS[i].field), W, sharded, plan.ext7_path[i], plan.ext7_want[i], err)) return false;
+    for (int i = 0; i < N_EXT8_REPORTS; ++i)
+        if (!plan_path(EXT8_REPORTS[i], ext_field(ext, EXT8_REPORTS[i].field), W, sharded, plan.ext8_path[i], plan.ext8_want[i], err)) return false;
     plan.bs_replicates = 100; plan.bs_seed = 42; plan.ai_top = 5; plan.em_classes = 10; plan.em_iterations = 1000;
-    plan.sg_min = 1000; plan.sg_bridge = 100; plan.sg_peak = 10; plan.mo_top = 10;
+    plan.sg_min = 1000; plan.sg_bridge = 100; plan.sg_peak = 10; plan.mo_top = 10; plan.rs_top = 5;
     if (plan.ext2_want[X2REP_BOOTSTRAP]) {
         uint64_t n = 0, seed = 42;
         if (ext_value(ext, &pantax_hip_profile_ext2::strain_bootstrap_replicates, n) && n > 0xFFFFFFFEull) {
@@ -113,6 +116,10 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
         uint64_t top = 0;
         if (ext_value(ext, &pantax_hip_profile_ext7::strain_mosaic_top, top) && top) plan.mo_top = top == PANTAX_HIP_MOSAIC_TOP_OFF ? 0 : top;
     }
+    if (plan.ext8_want[X8REP_RESCUE]) {
+        uint64_t top = 0;
+        if (ext_value(ext, &pantax_hip_profile_ext8::strain_rescue_top, top) && top) plan.rs_top = (uint32_t)std::min<uint64_t>(top, 0xFFFFFFFFull);
+    }
     return true;
 }
 
@@ -126,6 +133,7 @@ void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_d
     for (int i = 0; i < N_EXT5_REPORTS; ++i) plan.ext5_run[i] = runs(plan.ext5_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT6_REPORTS; ++i) plan.ext6_run[i] = runs(plan.ext6_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT7_REPORTS; ++i) plan.ext7_run[i] = runs(plan.ext7_want[i], strain, full_path, strain_done);
+    for (int i = 0; i < N_EXT8_REPORTS; ++i) plan.ext8_run[i] = runs(plan.ext8_want[i], strain, full_path, strain_done);
 }
 
 }  // namespace ptx

@@ -565,6 +565,25 @@ class Engine:
         self._check(self.lib.pantax_hip_strain_near_miss(self.ctx, self.db, C.byref(cs), p(cand) if len(ch) else None, p(species) if self.S else None))
         return cand, species
 
+    def strain_read_rescue(self, sel_off, sel_hap, cand_off, cand_hap):
+        """Read rescue (pantax_hip_strain_read_rescue) of the resident reads, binned against the resident db: for every read that fits no reported strain,
+        whether a single candidate walks all of its nodes.  sel_off / sel_hap and cand_off / cand_hap as for strain_near_miss; a species of K_s + J_s > 64
+        is skipped (counted only) -> (species uint64 [S, 9, 3]: counted / compatible / foreign / foreign_rescued / foreign_patchwork / foreign_novel /
+        mosaic / mosaic_rescued / contested, step uint64 [S, 3]: foreign_steps / claimed_steps / novel_steps, cand uint64 [J, 3, 3]: rescued / alone /
+        from_foreign of every candidate entry, cand_steps uint64 [J]); the last axis of species and cand is {n_reads, n_steps, span}."""
+        so, sh = as_c(sel_off, np.uint64), as_c(sel_hap, np.uint32)
+        co, ch = as_c(cand_off, np.uint64), as_c(cand_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]) or len(co) != self.S + 1 or len(ch) != int(co[-1]):
+            raise ValueError("strain_read_rescue: sel_off / cand_off need S + 1 entries, sel_hap sel_off[-1] and cand_hap cand_off[-1]")
+        cs = _ffi.NearMissSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, co.ctypes.data, ch.ctypes.data if len(ch) else None)
+        species = np.zeros((self.S, _ffi.RESCUE_CLASSES, 3), dtype=np.uint64)
+        step = np.zeros((self.S, 3), dtype=np.uint64)
+        cand = np.zeros((len(ch), 3, 3), dtype=np.uint64)
+        cand_steps = np.zeros(len(ch), dtype=np.uint64)
+        self._check(self.lib.pantax_hip_strain_read_rescue(self.ctx, self.db, self.reads, C.byref(cs), p(species) if self.S else None, p(step) if self.S else None,
+                                                           p(cand) if len(ch) else None, p(cand_steps) if len(ch) else None))
+        return species, step, cand, cand_steps
+
     def strain_addin(self, sel_off, sel_hap, cand_off, cand_hap):
         """Add-one test of the strain fit (pantax_hip_strain_addin) on the coverage result get_node_abundances left on the device.  sel_off / sel_hap and
         cand_off / cand_hap as for strain_near_miss.  Species s of K_s reported and J_s candidate haplotypes has W_s = K_s + J_s columns (the reported ones
@@ -789,7 +808,7 @@ class Engine:
                 strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42, strain_dropout_file=None,
                 strain_addin_file=None, strain_addin_top=0, strain_em_file=None, strain_em_classes=0, strain_em_iterations=0,
                 strain_segments_file=None, strain_segments_min=0, strain_segments_bridge=None, strain_segments_peak=0,
-                strain_mosaic_file=None, strain_mosaic_top=0):
+                strain_mosaic_file=None, strain_mosaic_top=0, strain_rescue_file=None, strain_rescue_top=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -808,7 +827,8 @@ class Engine:
         (0: 1000), strain_segments_bridge the bases between two segments of a chain at most (None: 100; 0 is a bridge of 0 -- the struct holds
         bridge + 1), strain_segments_peak the integer factor F of peak_depth = max(2, ceil(F x predicted_coverage)) (0: 10; "off": no peak class).
         strain_mosaic_file: path of the mosaic read report (--strain-mosaic; one rank only), strain_mosaic_top the junctions it prints per species
-        (0: 10; "off": none, and none are collected)."""
+        (0: 10; "off": none, and none are collected).
+        strain_rescue_file: path of the read rescue report (--strain-rescue; one rank only), strain_rescue_top the candidates it prints per species (0: 5)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -851,7 +871,7 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
@@ -862,7 +882,8 @@ class Engine:
                                   strain_segments_bridge=0 if strain_segments_bridge is None else int(strain_segments_bridge) + 1,
                                   strain_segments_peak=_ffi.SEGMENTS_PEAK_OFF if strain_segments_peak == "off" else int(strain_segments_peak),
                                   strain_mosaic_file=enc(strain_mosaic_file),
-                                  strain_mosaic_top=_ffi.MOSAIC_TOP_OFF if strain_mosaic_top == "off" else int(strain_mosaic_top))
+                                  strain_mosaic_top=_ffi.MOSAIC_TOP_OFF if strain_mosaic_top == "off" else int(strain_mosaic_top),
+                                  strain_rescue_file=enc(strain_rescue_file), strain_rescue_top=int(strain_rescue_top))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -1171,6 +1192,40 @@ def near_miss_rank(cand_hap, cand_out, top=0):
     rc = _ffi.load().pantax_hip_near_miss_rank(len(ch), p(ch) if len(ch) else p(out), p(co) if len(ch) else p(one), int(top), p(out), C.byref(n))
     if rc != 0:
         raise ValueError("near_miss_rank: refused (%d)" % rc)
+    return out[:n.value].copy()
+
+
+def rescue_walk(sel_masks, cand_masks, K, J):
+    """pantax_hip_rescue_walk: the read rescue classes of ONE walk.  sel_masks / cand_masks uint64 [n]: bit p = the member at position p of Sel / Cand walks
+    step i (bits at and above K / J are ignored), K + J <= 64 -> (class: 0 compatible, 1 foreign_rescued, 2 foreign_patchwork, 3 foreign_novel,
+    4 mosaic_rescued, 5 mosaic_unrescued; D(r) as a mask over Cand; steps uint64 [3] = foreign_steps, claimed_steps, novel_steps).  Host only."""
+    sm = as_c(sel_masks, np.uint64)
+    cm = as_c(cand_masks, np.uint64)
+    if len(sm) != len(cm):
+        raise ValueError("rescue_walk: sel_masks and cand_masks are of one length")
+    cls, d = C.c_uint32(0), C.c_uint64(0)
+    steps = np.zeros(3, dtype=np.uint64)
+    a = lambda x: p(x) if len(x) else None
+    rc = _ffi.load().pantax_hip_rescue_walk(len(sm), a(sm), a(cm), int(K), int(J), C.byref(cls), C.byref(d), p(steps))
+    if rc != 0:
+        raise ValueError("rescue_walk: refused (%d)" % rc)
+    return int(cls.value), int(d.value), steps
+
+
+def rescue_rank(cand_hap, cand_out, top=0):
+    """pantax_hip_rescue_rank: the positions of one species' candidates (cand_hap [n], cand_out [n, 3, 3] of strain_read_rescue) in the order of the
+    report -- rescued span descending, then rescued reads descending, then haplotype index ascending; candidates that rescue no read are left out; the
+    first `top` (0: all).  Host only: no Engine is needed."""
+    ch = as_c(cand_hap, np.uint32)
+    co = as_c(cand_out, np.uint64)
+    if co.shape != (len(ch), 3, 3):
+        raise ValueError("rescue_rank: cand_out is [len(cand_hap), 3, 3]")
+    out = np.zeros(max(len(ch), 1), dtype=np.uint32)
+    n = C.c_uint32(0)
+    one = np.zeros(9, dtype=np.uint64)   # (a zero-length array has no address to hand over)
+    rc = _ffi.load().pantax_hip_rescue_rank(len(ch), p(ch) if len(ch) else p(out), p(co) if len(ch) else p(one), int(top), p(out), C.byref(n))
+    if rc != 0:
+        raise ValueError("rescue_rank: refused (%d)" % rc)
     return out[:n.value].copy()
 
 
