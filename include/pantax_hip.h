@@ -557,6 +557,54 @@ int pantax_hip_rescue_walk(uint64_t n, const uint64_t *sel_masks, const uint64_t
 int pantax_hip_rescue_rank(uint32_t n_cand, const uint32_t *cand_hap, const uint64_t *cand_out /*[n_cand][3][3]*/, uint32_t top,
                            uint32_t *rank_out /*[n_cand]*/, uint32_t *n_out);
 
+/* ---- link support (the --strain-links report; not a stage of the reference): which adjacencies of a reported strain the reads cross.  Every other
+ * report treats a read and a strain as sets of nodes; this one looks at which node follows which.  The selection is a pantax_hip_read_strain_set: Sel_s
+ * with K_s entries per species, the weights unused (a null cand_w is fine).  State rules of pantax_hip_strain_read_support (reads binned against db, else
+ * PANTAX_HIP_E_STATE) and, for the coverage result, of pantax_hip_strain_segments (PANTAX_HIP_E_STATE behind a resident step and before any coverage
+ * pass); PANTAX_HIP_E_INVALID cases of pantax_hip_read_strains.  On any error the outputs are left as given.
+ * A species is OPEN when K_s <= 64: a link mask is one u64, bit p = position p of the species' list (the caller's order).  A wider one is SKIPPED.
+ *   Links.  Entry c at position p of species s has the walk w_0 .. w_{n-1}; position i in [0, n-1) carries the link e_i = {w_i, w_{i+1}}, an UNORDERED pair
+ *   of species-local nodes (walks carry no orientation; {u, u} is a link).  L(e) = the list positions whose walk has e at some position.
+ *   Crossings.  A counted read with steps v_1 .. v_n in walk order (repeats count) makes n - 1 crossings {v_i, v_{i+1}}; support[e] = the crossings equal
+ *   to e over the species' counted reads.  With M(v) as in pantax_hip_strain_mosaic a crossing is exactly one of
+ *     known    L is not empty;
+ *     skip     not known, and M(v_i) and M(v_{i+1}) meet: a reported strain walks both nodes, never one after the other;
+ *     switch   not known, both M non-empty, and the two are disjoint;
+ *     foreign  an M is empty (K_s = 0: every crossing).
+ *   Position classes.  With bases[] = bases_per_node of the coverage pass, position i of entry c is exactly one of
+ *     crossed  support[e_i] > 0;
+ *     broken   not crossed, bases[w_i] > 0 and bases[w_{i+1}] > 0: reads reach both sides and none goes across;
+ *     open     the rest;
+ *   and it is also PRIVATE when L(e_i) is the single bit p.
+ * Outputs, u64 unless stated, exact integers independent of any order:
+ *   species_out [S][6] = { counted_reads, crossings, known, skip, switch, foreign }; a skipped species gets the first two only;
+ *   link_out [S][4] = { distinct links, distinct links crossed, core links (L = all K_s bits), core links crossed };
+ *   hap_out [C][8] in the order of cand_hap = { links, crossed, open, broken, private, private_crossed, private_broken, support = the sum of
+ *     support[e_i] over the positions }; an entry of a skipped species gets zeros;
+ *   break records, one per broken position, per entry in ascending step, under the cap protocol of pantax_hip_strain_segments: brk_off_out [C+1] is
+ *     ALWAYS written; more than `cap` records: PANTAX_HIP_E_LIMIT with brk_off_out, species_out, link_out and hap_out filled and the record arrays
+ *     untouched.  brk_step (i), brk_start (o_{i+1}, the junction in path coordinates, o as in the coverage track), brk_node_a / brk_node_b (u32: w_i and
+ *     w_{i+1}, in walk order, species-local), brk_flank (min(bases[w_i] / node_len[w_i], bases[w_{i+1}] / node_len[w_{i+1}]), integer division; a node of
+ *     length 0 counts as depth 0), brk_mask (L(e_i)).
+ * For every open species: crossings = known + skip + switch + foreign = counted.n_steps - counted.n_reads of pantax_hip_strain_read_support on the same
+ * selection; known = the sum of support over the distinct links; per entry links = (steps of the walk) - 1 = crossed + open + broken, private_* <= its
+ * class, brk_off[c+1] - brk_off[c] = broken[c]; K_s = 1 gives private = links, switch = 0 and core = distinct.
+ * The option read_strain_route=walk takes every species' membership from the walks of Sel_s. */
+#define PANTAX_HIP_LINK_SPECIES_N 6
+#define PANTAX_HIP_LINK_HAP_N 8
+int pantax_hip_strain_links(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *sel,
+                            uint64_t *species_out /*[S][6]*/, uint64_t *link_out /*[S][4]*/, uint64_t *hap_out /*[C][8]*/, uint64_t *brk_off_out /*[C+1]*/,
+                            uint64_t cap /* records the six arrays hold */, uint64_t *brk_step_out, uint64_t *brk_start_out, uint32_t *brk_node_a_out,
+                            uint32_t *brk_node_b_out, uint64_t *brk_flank_out, uint64_t *brk_mask_out);
+/* host helper, no ctx and no GPU: the classes above for the crossings of ONE walk of n steps.  Bit p of masks[i] = the member at position p of Sel walks
+ * step i (bits at and above K are ignored); known[i] != 0: the crossing {step i, step i+1} is a link of some member (known may be null when n = 1).
+ * out [4] = { known, skip, switch, foreign }.  PANTAX_HIP_E_INVALID for a null argument, n = 0 or K > 64. */
+int pantax_hip_link_crossings(uint64_t n, const uint64_t *masks /*[n]*/, const uint8_t *known /*[n-1]*/, uint32_t K, uint64_t *out /*[4]*/);
+/* host helper, no ctx and no GPU: the breaks a report prints -- idx_out [min(n, top)] = the indices of the first `top` (0 keeps all) of n breaks in the
+ * order flank descending, then start ascending (then index ascending); *n_out = how many.  PANTAX_HIP_E_INVALID for a null idx_out / n_out, or a null
+ * flank / start with n > 0. */
+int pantax_hip_link_top(uint64_t n, const uint64_t *flank, const uint64_t *start, uint64_t top, uint64_t *idx_out, uint64_t *n_out);
+
 /* ---- pairwise strain distinguishability of a db (the --db-pairs mode; not a stage of the reference): the strain step's LP has one 0/1 column per haplotype
  * over the nodes of its species (profile.rs:1333-1342); two haplotypes with equal columns cannot be told apart by it, and two whose columns differ on 300
  * bases of nodes only where those 300 bases are covered.  This call says, before any sample, which selected haplotypes of the db can be separated and by how
@@ -1191,6 +1239,24 @@ typedef struct {
     const char *strain_rescue_file;
     uint64_t strain_rescue_top;   /* candidates printed per species: 0 reads as 5, and so does a struct that does not hold the field */
 } pantax_hip_profile_ext8;
+/* ... and once more: pantax_hip_profile_ext8 is closed at strain_rescue_top (a committed host check holds its 152 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the eighth version.  A caller fills v8.v7.v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext9)
+ * and passes &ext9.v8.v7.v6.v5.v4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40-, 48-, 64-, 88-, 120-, 136- or 152-byte struct runs
+ * with the fields below off.  A later output is a field appended here. */
+typedef struct {
+    pantax_hip_profile_ext8 v8;   /* v8.v7.v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext9) */
+    /* --strain-links: path of the link support report (pantax_hip_strain_links over every group of species, right behind the group's strain step, beside
+     * the read rescue call; NULL, "" or "None" = off).  Sel_s = the species' rows of strain_abundance.txt; a species of more than 64 rows is skipped.  TSV
+     * with a header: species_taxid, strain_taxid, genome_ID, class, rank, n_links, crossed, open, broken, private, private_crossed, private_broken,
+     * support, crossed_fraction, start, node_a, node_b, flank_depth, shared_with, predicted_coverage; f64 in shortest round-trip digits, "-" where a
+     * column does not apply or a fraction has no denominator.  (1) per row of strain_abundance.txt, in its order, a "strain" row with the eight numbers of
+     * hap_out and crossed_fraction = crossed / links, then that strain's first strain_links_top breaks in the order of pantax_hip_link_top: class "break",
+     * rank from 1, start, node_a and node_b (node ids as in the GAF), flank_depth, shared_with = popcount(brk_mask).  (2) per species in shard order:
+     * "links" and "core" with n_links and crossed from link_out; then "crossings", "known", "skip", "switch", "foreign" with the count in support and its
+     * share of crossings in crossed_fraction; a skipped species: "crossings" and "skipped".  Same rules as strain_fit_file. */
+    const char *strain_links_file;
+    uint64_t strain_links_top;   /* breaks printed per strain: 0 reads as 10, and so does a struct that does not hold the field */
+} pantax_hip_profile_ext9;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

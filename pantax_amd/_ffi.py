@@ -31,6 +31,7 @@ SYMBOLS = [
     "pantax_hip_strain_segments", "pantax_hip_segment_chain",
     "pantax_hip_strain_mosaic", "pantax_hip_mosaic_walk", "pantax_hip_mosaic_top",
     "pantax_hip_strain_read_rescue", "pantax_hip_rescue_walk", "pantax_hip_rescue_rank",
+    "pantax_hip_strain_links", "pantax_hip_link_crossings", "pantax_hip_link_top",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -42,6 +43,8 @@ SEGMENT_CHAIN_N = 7   # PANTAX_HIP_SEGMENT_CHAIN_N
 MOSAIC_TOP_OFF = 0xFFFFFFFFFFFFFFFF   # PANTAX_HIP_MOSAIC_TOP_OFF
 MOSAIC_CLASSES = 6   # PANTAX_HIP_MOSAIC_CLASSES
 RESCUE_CLASSES = 9   # PANTAX_HIP_RESCUE_CLASSES
+LINK_SPECIES_N = 6   # PANTAX_HIP_LINK_SPECIES_N
+LINK_HAP_N = 8       # PANTAX_HIP_LINK_HAP_N
 DEPTH_BINS = 96   # PANTAX_HIP_DEPTH_BINS
 DEPTH_NONE = 1    # PANTAX_HIP_DEPTH_NONE: pantax_hip_depth_quantile of a histogram without length
 
@@ -152,16 +155,17 @@ class FitSet(C.Structure):
 
 
 class ProfileExt(C.Structure):
-    """pantax_hip_profile_ext8 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
+    """pantax_hip_profile_ext9 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
     behind it (40 bytes), strain_dropout_file (48), the two fields of pantax_hip_profile_ext4 (64), the three of pantax_hip_profile_ext5 (88), the four
-    of pantax_hip_profile_ext6 (120), the two of pantax_hip_profile_ext7 (136) and the two of pantax_hip_profile_ext8 (152); struct_size = ctypes.sizeof(ProfileExt)"""
+    of pantax_hip_profile_ext6 (120), the two of pantax_hip_profile_ext7 (136), the two of pantax_hip_profile_ext8 (152) and the two of pantax_hip_profile_ext9 (168); struct_size = ctypes.sizeof(ProfileExt)"""
     _fields_ = [("struct_size", C.c_uint64), ("strain_fit_file", C.c_char_p), ("strain_bootstrap_file", C.c_char_p),
                 ("strain_bootstrap_replicates", C.c_uint64), ("strain_bootstrap_seed", C.c_uint64), ("strain_dropout_file", C.c_char_p),
                 ("strain_addin_file", C.c_char_p), ("strain_addin_top", C.c_uint64),
                 ("strain_em_file", C.c_char_p), ("strain_em_classes", C.c_uint64), ("strain_em_iterations", C.c_uint64),
                 ("strain_segments_file", C.c_char_p), ("strain_segments_min", C.c_uint64), ("strain_segments_bridge", C.c_uint64),
                 ("strain_segments_peak", C.c_uint64), ("strain_mosaic_file", C.c_char_p), ("strain_mosaic_top", C.c_uint64),
-                ("strain_rescue_file", C.c_char_p), ("strain_rescue_top", C.c_uint64)]
+                ("strain_rescue_file", C.c_char_p), ("strain_rescue_top", C.c_uint64),
+                ("strain_links_file", C.c_char_p), ("strain_links_top", C.c_uint64)]
 
 
 class BootstrapSet(C.Structure):
@@ -263,6 +267,12 @@ def load():
         _lib.pantax_hip_rescue_walk.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p]
         _lib.pantax_hip_rescue_rank.restype = C.c_int
         _lib.pantax_hip_rescue_rank.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+        _lib.pantax_hip_strain_links.restype = C.c_int
+        _lib.pantax_hip_strain_links.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReadStrainSet)] + [C.c_void_p] * 4 + [C.c_uint64] + [C.c_void_p] * 6
+        _lib.pantax_hip_link_crossings.restype = C.c_int
+        _lib.pantax_hip_link_crossings.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        _lib.pantax_hip_link_top.restype = C.c_int
+        _lib.pantax_hip_link_top.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
         _lib.pantax_hip_profile_with_ext.restype = C.c_int
         _lib.pantax_hip_profile_with_ext.argtypes = [C.c_void_p, C.POINTER(ProfilingConfig), C.POINTER(ProfileExt)]
         _lib.pantax_hip_db_pairs.restype = C.c_int

@@ -817,6 +817,23 @@ int pantax_hip_strain_read_rescue(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax
     return rescue_launch(ctx, db, reads, sel->sel_off, sel->sel_hap, sel->cand_off, sel->cand_hap, species_out, step_out, cand_out, cand_steps_out);
 }
 
+int pantax_hip_strain_links(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *sel, uint64_t *species_out,
+                            uint64_t *link_out, uint64_t *hap_out, uint64_t *brk_off_out, uint64_t cap, uint64_t *brk_step_out, uint64_t *brk_start_out,
+                            uint32_t *brk_node_a_out, uint32_t *brk_node_b_out, uint64_t *brk_flank_out, uint64_t *brk_mask_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !reads || !sel || !sel->cand_off || !brk_off_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_links: null argument");
+    PTX_ENTER(ctx);
+    std::vector<uint32_t> hap;
+    std::vector<double> w;
+    std::vector<uint64_t> ord;
+    PTX_TRY(check_read_strain_set(ctx, db, reads, sel, "strain_links", hap, w, ord, /*need_w=*/false));   // (the caller's order is kept: bit p = position p)
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_links"));
+    const uint32_t S = db->S;
+    if ((sel->cand_off[S] && !hap_out) || (S && (!species_out || !link_out))) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_links: null output array");
+    return links_launch(ctx, db, reads, sel->cand_off, sel->cand_hap, species_out, link_out, hap_out, brk_off_out, cap, brk_step_out, brk_start_out,
+                        brk_node_a_out, brk_node_b_out, brk_flank_out, brk_mask_out);
+}
+
 int pantax_hip_strain_addin(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_near_miss_set *sel, double *x_out, double *obj_out, int32_t *status_out,
                             uint64_t *rows_out, uint64_t *count_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;

@@ -73,6 +73,10 @@ static void usage() {
             "  --strain-rescue F   read rescue: for the reads of a species that fit no row of strain_abundance.txt, whether a single unreported haplotype of\n"
             "                     the db walks all of a read's nodes -- per candidate the reads it rescues, per species the reads by class (one rank only)\n"
             "  --strain-rescue-top N   candidates printed per species, by rescued span (default 5)\n"
+            "  --strain-links F    link support: which adjacencies (node u followed by node v) of every row of strain_abundance.txt the reads cross -- per\n"
+            "                     strain its links crossed, open and broken (reads reach both sides, none goes across) and its deepest breaks, per species\n"
+            "                     the read crossings that are a link of a reported strain, skip within one, switch between two or are foreign (one rank only)\n"
+            "  --strain-links-top N   breaks printed per strain, by flank depth (default 10)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -98,15 +102,16 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
-    pantax_hip_profile_ext8 ext8;   // the outputs added behind the config's last field
-    memset(&ext8, 0, sizeof(ext8));
+    pantax_hip_profile_ext9 ext9;   // the outputs added behind the config's last field
+    memset(&ext9, 0, sizeof(ext9));
+    pantax_hip_profile_ext8 &ext8 = ext9.v8;
     pantax_hip_profile_ext7 &ext7 = ext8.v7;
     pantax_hip_profile_ext6 &ext6 = ext7.v6;
     pantax_hip_profile_ext5 &ext5 = ext6.v5;
     pantax_hip_profile_ext4 &ext4 = ext5.v4;
     pantax_hip_profile_ext3 &ext3 = ext4.v3;
     pantax_hip_profile_ext2 &ext = ext3.v2;
-    ext.v1.struct_size = sizeof(ext8);
+    ext.v1.struct_size = sizeof(ext9);
     ext.strain_bootstrap_seed = 42;
     pantax_hip_db_pairs_config pairs;
     memset(&pairs, 0, sizeof(pairs));
@@ -187,6 +192,8 @@ int main(int argc, char **argv) {
         else if (a == "--strain-mosaic-top") { const std::string v = next(); ext7.strain_mosaic_top = v == "off" ? PANTAX_HIP_MOSAIC_TOP_OFF : strtoull(v.c_str(), nullptr, 10); }
         else if (a == "--strain-rescue") ext8.strain_rescue_file = next();
         else if (a == "--strain-rescue-top") ext8.strain_rescue_top = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-links") ext9.strain_links_file = next();
+        else if (a == "--strain-links-top") ext9.strain_links_top = strtoull(next(), nullptr, 10);
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

@@ -705,6 +705,12 @@ int mosaic_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const u
 // cand_steps_out [J] in the caller's order of cand_hap
 int rescue_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *cand_off, const uint32_t *cand_hap,
                   uint64_t *species_out, uint64_t *step_out, uint64_t *cand_out, uint64_t *cand_steps_out);
+// stage_links.hip (pantax_hip_strain_links): the selection validated by the caller, in the caller's order (bit p of a link mask = position p of the
+// species' list).  brk_off_out [C+1], species_out [S][6], link_out [S][4] and hap_out [C][8] are always written; more than `cap` break records:
+// PANTAX_HIP_E_LIMIT and the six record arrays are not touched
+int links_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t *species_out, uint64_t *link_out, uint64_t *hap_out,
+                 uint64_t *brk_off_out, uint64_t cap, uint64_t *brk_step_out, uint64_t *brk_start_out, uint32_t *brk_node_a_out, uint32_t *brk_node_b_out,
+                 uint64_t *brk_flank_out, uint64_t *brk_mask_out);
 // stage_read_em.hip (pantax_hip_strain_read_em): candidates of every species in ascending haplotype order with their lengths, entry_of[c] = the caller's entry
 // of sorted candidate c; all validated by the caller.  Outputs as the stage call's; they are written only when the call succeeds (cls_off_out: also on E_LIMIT)
 int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const uint64_t *cand_len, const uint64_t *entry_of, uint32_t max_iter,

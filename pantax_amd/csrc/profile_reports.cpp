@@ -2,12 +2,13 @@
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
 // (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
-// report, the add-one report, the read class report, the segment report, the mosaic read report and the read rescue report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT8_REPORTS).
+// report, the add-one report, the read class report, the segment report, the mosaic read report, the read rescue report and the link support report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT9_REPORTS).
 #include <algorithm>
 #include <cmath>
 #include <fstream>
 #include <unordered_map>
 #include "hap_pairs_plan.hpp"
+#include "links_plan.hpp"
 #include "mosaic_plan.hpp"
 #include "profile_run.hpp"
 #include "read_em_plan.hpp"
@@ -435,6 +436,26 @@ int group_rescue(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uin
         rc.row_off[k0 + k + 1] = rc.rows.size();
     }
     run.lap("  strain read rescue");
+    return 0;
+}
+// --strain-links, beside the read rescue call: Sel_s = the group's rows; the two calls of the cap protocol.  A species of more than 64 rows comes back skipped
+int group_links(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &lk = sh.rep.lk;
+    const size_t C = g.hap.size(), e0 = g.entry0;
+    const pantax_hip_read_strain_set set{k1 - k0, g.off.data(), g.hap.data(), nullptr};
+    lk.hap.resize(LNK_N_HAP * (e0 + C));
+    for (uint32_t k = k0; k < k1; ++k) lk.open[k] = g.off[k - k0 + 1] - g.off[k - k0] <= LINKS_MAX_LIST ? 1 : 0;
+    uint64_t *const sp = lk.species.data() + LNK_N_SPECIES * (size_t)k0, *const lt = lk.link.data() + LNK_N_TABLE * (size_t)k0, *const hp = lk.hap.data() + LNK_N_HAP * e0;
+    std::vector<uint64_t> b_off(C + 1, 0);
+    const int rc_size = pantax_hip_strain_links(run.ctx, db, in.reads.rd, &set, sp, lt, hp, b_off.data(), 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);   // sizes: E_LIMIT unless there is no break
+    if (rc_size != 0 && rc_size != PANTAX_HIP_E_LIMIT) return rc_size;
+    const uint64_t n = b_off[C], at = lk.start.size();
+    std::vector<uint64_t> step(n);
+    lk.start.resize(at + n); lk.flank.resize(at + n); lk.mask.resize(at + n); lk.node_a.resize(at + n); lk.node_b.resize(at + n);
+    if (n) PTX_TRY(pantax_hip_strain_links(run.ctx, db, in.reads.rd, &set, sp, lt, hp, b_off.data(), n, step.data(), lk.start.data() + at, lk.node_a.data() + at,
+                                           lk.node_b.data() + at, lk.flank.data() + at, lk.mask.data() + at));
+    for (size_t e = 0; e < C; ++e) lk.brk_off.push_back(at + b_off[e + 1]);
+    run.lap("  strain link support");
     return 0;
 }
 
@@ -996,6 +1017,51 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-links: per row of strain_abundance.txt, in its order, the strain's eight counters and its first lk_top breaks in the order of
+    // pantax_hip_link_top; then per species of the shard, in the order it went through the device, its link table and its crossings by class
+    int links() const {
+        const auto &lk = rep.lk;
+        return file(run.p.rep.ext9_path[X9REP_LINKS],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tclass\trank\tn_links\tcrossed\topen\tbroken\tprivate\tprivate_crossed\tprivate_broken\tsupport\tcrossed_fraction\tstart\tnode_a\tnode_b\tflank_depth\tshared_with\tpredicted_coverage\n",
+                    "link support report", [&](std::ofstream &f) {
+            const auto frac = [](uint64_t n, uint64_t of) { return of ? fmt_f64((double)n / (double)of) : std::string("-"); };
+            std::vector<uint64_t> top;
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "link support", &e));
+                const std::string head = strain_head(r), pc = fmt_f64(sh.met[r.hap].second_sol);
+                const uint64_t *q = lk.hap.data() + LNK_N_HAP * (size_t)e;
+                f << head << "\tstrain\t-";
+                if (lk.open[r.k]) {
+                    for (int i = 0; i < (int)LNK_N_HAP; ++i) f << '\t' << q[i];
+                    f << '\t' << frac(q[LNK_CROSSED], q[LNK_LINKS]);
+                } else f << "\t-\t-\t-\t-\t-\t-\t-\t-\t-";
+                f << "\t-\t-\t-\t-\t-\t" << pc << '\n';
+                const uint64_t b0 = lk.brk_off[e], n = lk.brk_off[e + 1] - b0;
+                uint64_t m = 0;
+                top.resize(n ? n : 1);
+                if (pantax_hip_link_top(n, lk.flank.data() + b0, lk.start.data() + b0, run.p.rep.lk_top, top.data(), &m) != 0) continue;
+                const int64_t first = in.ranges[sn.sel[sh.use[r.k]]].start;              // the node ids of the GAF: the species' first node id + the local index
+                for (uint64_t i = 0; i < m; ++i) {
+                    const uint64_t j = b0 + top[i];
+                    f << head << "\tbreak\t" << i + 1 << "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t" << lk.start[j] << '\t' << first + (int64_t)lk.node_a[j] << '\t' << first + (int64_t)lk.node_b[j]
+                      << '\t' << lk.flank[j] << '\t' << __builtin_popcountll(lk.mask[j]) << '\t' << pc << '\n';
+                }
+            }
+            const char *const of_species[LNK_N_SPECIES] = {"", "crossings", "known", "skip", "switch", "foreign"};
+            for (uint32_t k = 0; k < Su; ++k) {
+                const std::string head = species_head(k);
+                const uint64_t *sp = lk.species.data() + LNK_N_SPECIES * (size_t)k, *lt = lk.link.data() + LNK_N_TABLE * (size_t)k;
+                if (lk.open[k])
+                    for (int c = 0; c < 2; ++c)
+                        f << head << '\t' << (c ? "core" : "links") << "\t-\t" << lt[2 * c] << '\t' << lt[2 * c + 1] << "\t-\t-\t-\t-\t-\t-\t" << frac(lt[2 * c + 1], lt[2 * c])
+                          << "\t-\t-\t-\t-\t-\t-\n";
+                for (int c = LNK_CROSSINGS; c < (lk.open[k] ? (int)LNK_N_SPECIES : (int)LNK_CROSSINGS + 1); ++c)   // a skipped species: crossings only
+                    f << head << '\t' << of_species[c] << "\t-\t-\t-\t-\t-\t-\t-\t-\t" << sp[c] << '\t' << frac(sp[c], sp[LNK_CROSSINGS]) << "\t-\t-\t-\t-\t-\t-\n";
+                if (!lk.open[k]) f << head << "\tskipped\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+            }
+            return 0;
+        });
+    }
     // --strain-pair-evidence: per species of the shard, in the order it went through the device, for every two of its rows a < b (ascending haplotype index)
     // what both walk (shared) and what only a, only b walks, as {n_nodes, len, covered, bases} with depth and breadth
     int pair_evidence() const {
@@ -1066,6 +1132,9 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.ext8_run[X8REP_RESCUE]) {
         rep.rc.species.assign(3 * RES_N_CLASSES * (size_t)Su, 0); rep.rc.step.assign(3 * (size_t)Su, 0); rep.rc.row_off.assign(Su + 1, 0); rep.rc.open.assign(Su, 0);
     }
+    if (plan.ext9_run[X9REP_LINKS]) {
+        rep.lk.species.assign(LNK_N_SPECIES * (size_t)Su, 0); rep.lk.link.assign(LNK_N_TABLE * (size_t)Su, 0); rep.lk.open.assign(Su, 0);
+    }
     if (plan.ext7_run[X7REP_MOSAIC]) {
         rep.mo.species.assign(3 * MOS_N_CLASSES * (size_t)Su, 0); rep.mo.extra.assign(3 * (size_t)Su, 0); rep.mo.pair_off.assign(Su, 0); rep.mo.K.assign(Su, 0); rep.mo.jn_off.assign(Su + 1, 0);
     }
@@ -1089,6 +1158,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.ext5_run[X5REP_EM]) PTX_TRY(group_read_em(run, in, db, k0, k1, g, sh));
     if (plan.ext7_run[X7REP_MOSAIC]) PTX_TRY(group_mosaic(run, in, db, k0, k1, g, sh));
     if (plan.ext8_run[X8REP_RESCUE]) PTX_TRY(group_rescue(run, in, db, k0, k1, g, sh, gc));
+    if (plan.ext9_run[X9REP_LINKS]) PTX_TRY(group_links(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh, gc));
     return 0;
@@ -1114,6 +1184,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext6_run[X6REP_SEGMENTS]) PTX_TRY(w.segments());
     if (plan.ext7_run[X7REP_MOSAIC]) PTX_TRY(w.mosaic());
     if (plan.ext8_run[X8REP_RESCUE]) PTX_TRY(w.rescue());
+    if (plan.ext9_run[X9REP_LINKS]) PTX_TRY(w.links());
     return 0;
 }
 }  // namespace reports

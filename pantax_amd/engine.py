@@ -584,6 +584,35 @@ class Engine:
                                                            p(cand) if len(ch) else None, p(cand_steps) if len(ch) else None))
         return species, step, cand, cand_steps
 
+    def strain_links(self, sel_off, sel_hap):
+        """Link support (pantax_hip_strain_links) of the resident reads, binned against the resident db, on the coverage result get_node_abundances left on
+        the device: which adjacencies of the selected haplotypes the reads cross.  sel_off [S+1], sel_hap (species-local haplotype indices, no repeats
+        within a species; bit p of a link mask = position p of the species' list); a species of K_s > 64 is skipped -> (species uint64 [S, 6]: counted_reads /
+        crossings / known / skip / switch / foreign, link uint64 [S, 4]: distinct / distinct crossed / core / core crossed, hap uint64 [C, 8]: links /
+        crossed / open / broken / private / private_crossed / private_broken / support, brk_off uint64 [C+1], brk_step, brk_start uint64, brk_node_a,
+        brk_node_b uint32 (species-local, in walk order), brk_flank, brk_mask uint64): the break records of entry c are [brk_off[c], brk_off[c+1]), in
+        ascending step.  Makes the two calls of the cap protocol."""
+        so, sh = as_c(sel_off, np.uint64), as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("strain_links: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        cs = _ffi.ReadStrainSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, None)
+        species = np.zeros((self.S, _ffi.LINK_SPECIES_N), dtype=np.uint64)
+        link = np.zeros((self.S, 4), dtype=np.uint64)
+        hap = np.zeros((len(sh), _ffi.LINK_HAP_N), dtype=np.uint64)
+        brk_off = np.zeros(len(sh) + 1, dtype=np.uint64)
+        q = lambda a: p(a) if a.size else None
+        rc = self.lib.pantax_hip_strain_links(self.ctx, self.db, self.reads, C.byref(cs), q(species), q(link), q(hap), p(brk_off), 0,
+                                              None, None, None, None, None, None)   # sizes the arrays
+        if rc != _ffi.E_LIMIT:
+            self._check(rc)
+        n = int(brk_off[-1])
+        step, start, flank, mask = (np.zeros(n, dtype=np.uint64) for _ in range(4))
+        node_a, node_b = (np.zeros(n, dtype=np.uint32) for _ in range(2))
+        if n:
+            self._check(self.lib.pantax_hip_strain_links(self.ctx, self.db, self.reads, C.byref(cs), q(species), q(link), q(hap), p(brk_off), n,
+                                                         p(step), p(start), p(node_a), p(node_b), p(flank), p(mask)))
+        return species, link, hap, brk_off, step, start, node_a, node_b, flank, mask
+
     def strain_addin(self, sel_off, sel_hap, cand_off, cand_hap):
         """Add-one test of the strain fit (pantax_hip_strain_addin) on the coverage result get_node_abundances left on the device.  sel_off / sel_hap and
         cand_off / cand_hap as for strain_near_miss.  Species s of K_s reported and J_s candidate haplotypes has W_s = K_s + J_s columns (the reported ones
@@ -808,7 +837,8 @@ class Engine:
                 strain_bootstrap_file=None, strain_bootstrap_replicates=0, strain_bootstrap_seed=42, strain_dropout_file=None,
                 strain_addin_file=None, strain_addin_top=0, strain_em_file=None, strain_em_classes=0, strain_em_iterations=0,
                 strain_segments_file=None, strain_segments_min=0, strain_segments_bridge=None, strain_segments_peak=0,
-                strain_mosaic_file=None, strain_mosaic_top=0, strain_rescue_file=None, strain_rescue_top=0):
+                strain_mosaic_file=None, strain_mosaic_top=0, strain_rescue_file=None, strain_rescue_top=0,
+                strain_links_file=None, strain_links_top=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -828,7 +858,8 @@ class Engine:
         bridge + 1), strain_segments_peak the integer factor F of peak_depth = max(2, ceil(F x predicted_coverage)) (0: 10; "off": no peak class).
         strain_mosaic_file: path of the mosaic read report (--strain-mosaic; one rank only), strain_mosaic_top the junctions it prints per species
         (0: 10; "off": none, and none are collected).
-        strain_rescue_file: path of the read rescue report (--strain-rescue; one rank only), strain_rescue_top the candidates it prints per species (0: 5)."""
+        strain_rescue_file: path of the read rescue report (--strain-rescue; one rank only), strain_rescue_top the candidates it prints per species (0: 5).
+        strain_links_file: path of the link support report (--strain-links; one rank only), strain_links_top the breaks it prints per strain (0: 10)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -871,7 +902,7 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None and strain_links_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
@@ -883,7 +914,8 @@ class Engine:
                                   strain_segments_peak=_ffi.SEGMENTS_PEAK_OFF if strain_segments_peak == "off" else int(strain_segments_peak),
                                   strain_mosaic_file=enc(strain_mosaic_file),
                                   strain_mosaic_top=_ffi.MOSAIC_TOP_OFF if strain_mosaic_top == "off" else int(strain_mosaic_top),
-                                  strain_rescue_file=enc(strain_rescue_file), strain_rescue_top=int(strain_rescue_top))
+                                  strain_rescue_file=enc(strain_rescue_file), strain_rescue_top=int(strain_rescue_top),
+                                  strain_links_file=enc(strain_links_file), strain_links_top=int(strain_links_top))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -1226,6 +1258,36 @@ def rescue_rank(cand_hap, cand_out, top=0):
     rc = _ffi.load().pantax_hip_rescue_rank(len(ch), p(ch) if len(ch) else p(out), p(co) if len(ch) else p(one), int(top), p(out), C.byref(n))
     if rc != 0:
         raise ValueError("rescue_rank: refused (%d)" % rc)
+    return out[:n.value].copy()
+
+
+def link_crossings(masks, known, K):
+    """pantax_hip_link_crossings: the classes of the crossings of ONE walk.  masks uint64 [n]: bit p = the member at position p of the list walks step i
+    (bits at and above K are ignored); known [n - 1]: non-zero where the crossing {step i, step i + 1} is a link of some member; K <= 64 ->
+    uint64 [4] = known, skip, switch, foreign.  Host only."""
+    m = as_c(masks, np.uint64)
+    kn = as_c(known, np.uint8)
+    if len(m) == 0 or len(kn) != len(m) - 1:
+        raise ValueError("link_crossings: masks holds n >= 1 steps and known n - 1 crossings")
+    out = np.zeros(4, dtype=np.uint64)
+    rc = _ffi.load().pantax_hip_link_crossings(len(m), p(m), p(kn) if len(kn) else None, int(K), p(out))
+    if rc != 0:
+        raise ValueError("link_crossings: refused (%d)" % rc)
+    return out
+
+
+def link_top(flank, start, top=0):
+    """pantax_hip_link_top: the indices of the first `top` (0: all) breaks in the order of the report -- flank descending, then start ascending.
+    Host only: no Engine is needed."""
+    fl = as_c(flank, np.uint64)
+    st = as_c(start, np.uint64)
+    if len(fl) != len(st):
+        raise ValueError("link_top: flank and start are of one length")
+    out = np.zeros(max(len(fl), 1), dtype=np.uint64)
+    n = C.c_uint64(0)
+    rc = _ffi.load().pantax_hip_link_top(len(fl), p(fl) if len(fl) else None, p(st) if len(fl) else None, int(top), p(out), C.byref(n))
+    if rc != 0:
+        raise ValueError("link_top: refused (%d)" % rc)
     return out[:n.value].copy()
 
 
