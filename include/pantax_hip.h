@@ -605,6 +605,47 @@ int pantax_hip_link_crossings(uint64_t n, const uint64_t *masks /*[n]*/, const u
  * flank / start with n > 0. */
 int pantax_hip_link_top(uint64_t n, const uint64_t *flank, const uint64_t *start, uint64_t top, uint64_t *idx_out, uint64_t *n_out);
 
+/* ---- rarefaction of the strain fit (the --strain-rarefy report; not a stage of the reference): would a strain still be there with half the reads?  Every
+ * other diagnostic is conditioned on the depth the sample has; the bootstrap redraws the LP's rows (nodes) at that depth.  This call thins the READS -- one
+ * read feeds several nodes, and the LP's rows move together when it goes -- and refits the LP of pantax_hip_strain_bootstrap on every nested subsample.
+ *   The thinning rule.  With sm = splitmix64's output function as in the bootstrap, replicate b >= 1 and r = the read's index in the uploaded columns
+ *   (the order of the outputs of pantax_hip_read_strains):  h = sm(sm(seed ^ sm(b)) + r),  depth(b, r) = min(63, leading zero bits of h).  Read r belongs
+ *   to level l of replicate b iff depth(b, r) >= l: level 0 is every read, level l keeps a read with probability 2^-l, and the levels of one replicate are
+ *   nested.  pantax_hip_rarefy_depth is the rule as a host helper.
+ *   bases_l[v] of a level = bases_per_node of pantax_hip_node_coverage over the level's reads alone: the counted reads (binned to a species of the db, no
+ *   drop flag), the aligned length of every step as in get_node_abundances, only the first occurrence of a node in a read, nothing from a read that
+ *   aborts there.  Exact integers.
+ *   Entries.  E = 1 + n_replicates x n_levels.  Entry 0 is the full sample: its rows come from the bases_per_node the coverage pass left on the device, and
+ *   its x, obj, rows and status are the bits of pantax_hip_strain_bootstrap with n_replicates = 0 on the same selection.  Entry 1 + (b - 1) n_levels + (l - 1)
+ *   is level l in 1 .. n_levels of replicate b in 1 .. n_replicates: the LP of the bootstrap's contract on bases_l -- rows a_v = bases_l[v] / len > 0 with a
+ *   non-empty mask, the box 1.05 max a of the entry's own rows, no column pinned.
+ * Outputs, entry-major:  x_out [E][C];  obj_out [E][S] (a sum over the rows);  rows_out [E][S];  status_out [E][S] as in the bootstrap: 0 solved, 1 nothing
+ * to solve, PANTAX_HIP_E_LIMIT for K_s > 64 (the other species are served), PANTAX_HIP_E_SOLVER for that LP alone;  reads_out [E][S][2] = { counted reads
+ * of the species in the entry's level, bases they added }, entry 0's from the first pass over the reads;  member_out [E][C][2] = { n_member, n_only } of
+ * the selected strain in the entry's LP as pantax_hip_strain_dropout defines them for its entry 0: the rows with its bit, the rows with mask == 1 << k.
+ * Only the species with 1 <= K_s <= 64 are thinned: the others get zeros in reads_out.
+ * State rules of pantax_hip_strain_links: resident reads binned against this db and a coverage result of pantax_hip_node_coverage, PANTAX_HIP_E_STATE
+ * otherwise.  PANTAX_HIP_E_INVALID for n_levels outside 1 .. 16, n_replicates = 0 and the argument errors of pantax_hip_strain_evidence.  On an error the
+ * outputs are left as given.  Determinism: the same inputs give the same bits, whatever the number of levels a pass over the reads serves (option
+ * rarefy_levels_max, 0 = from the free device memory), the membership route (option rarefy_route=walk) and the position of a species in the db. */
+typedef struct {
+    uint32_t n_species;       /* must equal the db's */
+    const uint64_t *sel_off;  /* [S+1] as pantax_hip_evidence_set */
+    const uint32_t *sel_hap;  /* [C] species-local haplotype index, any order, no repeats within a species */
+    uint64_t seed;
+    uint32_t n_levels;        /* the thinned levels 1 .. n_levels; 1 .. 16 */
+    uint32_t n_replicates;    /* >= 1 */
+} pantax_hip_rarefy_set;
+int pantax_hip_strain_rarefy(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_rarefy_set *sel, double *x_out /*[E][C]*/,
+                             double *obj_out /*[E][S]*/, uint64_t *rows_out /*[E][S]*/, int32_t *status_out /*[E][S]*/, uint64_t *reads_out /*[E][S][2]*/,
+                             uint64_t *member_out /*[E][C][2]*/);
+/* the test seam of the pass over the reads: bases_l of ONE level (0 .. 63; level 0 and replicate 0 are allowed) over every species of the db, bases_out [V].
+ * State rules as above. */
+int pantax_hip_rarefy_node_bases(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, uint64_t seed, uint32_t replicate, uint32_t level,
+                                 uint64_t *bases_out /*[V]*/);
+/* host helper, no ctx and no GPU: depth(replicate, read) of the rule above */
+uint32_t pantax_hip_rarefy_depth(uint64_t seed, uint32_t replicate, uint64_t read);
+
 /* ---- pairwise strain distinguishability of a db (the --db-pairs mode; not a stage of the reference): the strain step's LP has one 0/1 column per haplotype
  * over the nodes of its species (profile.rs:1333-1342); two haplotypes with equal columns cannot be told apart by it, and two whose columns differ on 300
  * bases of nodes only where those 300 bases are covered.  This call says, before any sample, which selected haplotypes of the db can be separated and by how
@@ -1257,6 +1298,28 @@ typedef struct {
     const char *strain_links_file;
     uint64_t strain_links_top;   /* breaks printed per strain: 0 reads as 10, and so does a struct that does not hold the field */
 } pantax_hip_profile_ext9;
+/* ... and once more: pantax_hip_profile_ext9 is closed at strain_links_top (a committed host check holds its 168 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the ninth version.  A caller fills v9.v8.v7.v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext10)
+ * and passes &ext10.v9.v8.v7.v6.v5.v4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40-, 48-, 64-, 88-, 120-, 136-, 152- or 168-byte struct
+ * runs with the fields below off.  A later output is a field appended here. */
+typedef struct {
+    pantax_hip_profile_ext9 v9;   /* v9.v8.v7.v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext10) */
+    /* --strain-rarefy: path of the rarefaction report (pantax_hip_strain_rarefy over every group of species, right behind the group's strain step, beside
+     * the link support call; NULL, "" or "None" = off).  Sel_s = the species' rows of strain_abundance.txt in ascending haplotype index; a species of more
+     * than 64 rows is skipped.  TSV with a header: species_taxid, strain_taxid, genome_ID, class, level, fraction, n_solved, predicted_coverage, refit, mean,
+     * sd, min, max, scaled_mean, zero_fraction, n_member, n_only, n_reads, bases, n_rows, objective; f64 in shortest round-trip digits, "-" where a column
+     * does not apply.  (1) per row of strain_abundance.txt, in its order, a "strain" row per level 0 .. strain_rarefy_levels: fraction = 2^-level; refit = x
+     * of entry 0; n_solved, mean, sd, min and zero_fraction = pantax_hip_bootstrap_summary over the level's x of the replicates (level 0: the one value of
+     * entry 0, n_solved = 1, sd = 0), max over the same solved LPs; scaled_mean = mean x 2^level, the number to read beside refit; n_member and n_only =
+     * the means over the replicates, as f64.  (2) per species in shard order a "species" row per level: n_solved, n_reads and bases (means over the
+     * replicates, as f64), n_rows (the mean over the replicates) and the mean objective of the solved LPs; a species of more than 64 rows: one "skipped" row
+     * and no strain rows.  Same rules as
+     * strain_fit_file. */
+    const char *strain_rarefy_file;
+    uint64_t strain_rarefy_levels;       /* thinned levels 1 .. N (fractions 1/2 .. 2^-N), at most 16: 0 reads as 5, and so does a struct that does not hold the field */
+    uint64_t strain_rarefy_replicates;   /* replicates per level: 0 reads as 5, and so does a struct that does not hold the field */
+    uint64_t strain_rarefy_seed;         /* a struct that does not hold the field reads as 42; 0 passed explicitly is 0 */
+} pantax_hip_profile_ext10;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

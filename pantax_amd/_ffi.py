@@ -32,6 +32,7 @@ SYMBOLS = [
     "pantax_hip_strain_mosaic", "pantax_hip_mosaic_walk", "pantax_hip_mosaic_top",
     "pantax_hip_strain_read_rescue", "pantax_hip_rescue_walk", "pantax_hip_rescue_rank",
     "pantax_hip_strain_links", "pantax_hip_link_crossings", "pantax_hip_link_top",
+    "pantax_hip_strain_rarefy", "pantax_hip_rarefy_node_bases", "pantax_hip_rarefy_depth",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -155,9 +156,9 @@ class FitSet(C.Structure):
 
 
 class ProfileExt(C.Structure):
-    """pantax_hip_profile_ext9 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
+    """pantax_hip_profile_ext10 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
     behind it (40 bytes), strain_dropout_file (48), the two fields of pantax_hip_profile_ext4 (64), the three of pantax_hip_profile_ext5 (88), the four
-    of pantax_hip_profile_ext6 (120), the two of pantax_hip_profile_ext7 (136), the two of pantax_hip_profile_ext8 (152) and the two of pantax_hip_profile_ext9 (168); struct_size = ctypes.sizeof(ProfileExt)"""
+    of pantax_hip_profile_ext6 (120), the two of pantax_hip_profile_ext7 (136), the two of pantax_hip_profile_ext8 (152), the two of pantax_hip_profile_ext9 (168) and the four of pantax_hip_profile_ext10 (200); struct_size = ctypes.sizeof(ProfileExt)"""
     _fields_ = [("struct_size", C.c_uint64), ("strain_fit_file", C.c_char_p), ("strain_bootstrap_file", C.c_char_p),
                 ("strain_bootstrap_replicates", C.c_uint64), ("strain_bootstrap_seed", C.c_uint64), ("strain_dropout_file", C.c_char_p),
                 ("strain_addin_file", C.c_char_p), ("strain_addin_top", C.c_uint64),
@@ -165,7 +166,15 @@ class ProfileExt(C.Structure):
                 ("strain_segments_file", C.c_char_p), ("strain_segments_min", C.c_uint64), ("strain_segments_bridge", C.c_uint64),
                 ("strain_segments_peak", C.c_uint64), ("strain_mosaic_file", C.c_char_p), ("strain_mosaic_top", C.c_uint64),
                 ("strain_rescue_file", C.c_char_p), ("strain_rescue_top", C.c_uint64),
-                ("strain_links_file", C.c_char_p), ("strain_links_top", C.c_uint64)]
+                ("strain_links_file", C.c_char_p), ("strain_links_top", C.c_uint64),
+                ("strain_rarefy_file", C.c_char_p), ("strain_rarefy_levels", C.c_uint64), ("strain_rarefy_replicates", C.c_uint64),
+                ("strain_rarefy_seed", C.c_uint64)]
+
+
+class RarefySet(C.Structure):
+    """pantax_hip_rarefy_set"""
+    _fields_ = [("n_species", C.c_uint32), ("sel_off", C.c_void_p), ("sel_hap", C.c_void_p), ("seed", C.c_uint64), ("n_levels", C.c_uint32),
+                ("n_replicates", C.c_uint32)]
 
 
 class BootstrapSet(C.Structure):
@@ -273,6 +282,12 @@ def load():
         _lib.pantax_hip_link_crossings.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         _lib.pantax_hip_link_top.restype = C.c_int
         _lib.pantax_hip_link_top.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]
+        _lib.pantax_hip_strain_rarefy.restype = C.c_int
+        _lib.pantax_hip_strain_rarefy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RarefySet)] + [C.c_void_p] * 6
+        _lib.pantax_hip_rarefy_node_bases.restype = C.c_int
+        _lib.pantax_hip_rarefy_node_bases.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+        _lib.pantax_hip_rarefy_depth.restype = C.c_uint32
+        _lib.pantax_hip_rarefy_depth.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
         _lib.pantax_hip_profile_with_ext.restype = C.c_int
         _lib.pantax_hip_profile_with_ext.argtypes = [C.c_void_p, C.POINTER(ProfilingConfig), C.POINTER(ProfileExt)]
         _lib.pantax_hip_db_pairs.restype = C.c_int

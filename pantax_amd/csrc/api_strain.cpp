@@ -834,6 +834,38 @@ int pantax_hip_strain_links(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_r
                         brk_node_a_out, brk_node_b_out, brk_flank_out, brk_mask_out);
 }
 
+int pantax_hip_strain_rarefy(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_rarefy_set *sel, double *x_out, double *obj_out,
+                             uint64_t *rows_out, int32_t *status_out, uint64_t *reads_out, uint64_t *member_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !reads || !sel || !sel->sel_off) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_rarefy: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_rarefy", sel->n_species));
+    if (sel->n_levels == 0 || sel->n_levels > 16) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_rarefy: %u levels (1 .. 16)", sel->n_levels);
+    if (sel->n_replicates == 0) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_rarefy: 0 replicates (at least one)");
+    PTX_TRY(check_read_pass_state(ctx, db, reads, "strain_rarefy"));
+    PTX_TRY(check_hap_selection(ctx, db, "strain_rarefy", sel->sel_off, sel->sel_hap));
+    if ((sel->sel_off[db->S] && (!x_out || !member_out)) || (db->S && (!obj_out || !rows_out || !status_out || !reads_out)))
+        return fail(ctx, PANTAX_HIP_E_INVALID, "strain_rarefy: null output array");
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_rarefy"));
+    try {
+        return rarefy_launch(ctx, db, reads, sel->sel_off, sel->sel_hap, sel->seed, sel->n_levels, sel->n_replicates, x_out, obj_out, rows_out, status_out, reads_out,
+                             member_out);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_rarefy: out of host memory");
+    }
+}
+
+int pantax_hip_rarefy_node_bases(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, uint64_t seed, uint32_t replicate, uint32_t level,
+                                 uint64_t *bases_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !reads || (db->V && !bases_out)) return fail(ctx, PANTAX_HIP_E_INVALID, "rarefy_node_bases: null argument");
+    PTX_ENTER(ctx);
+    if (level > 63) return fail(ctx, PANTAX_HIP_E_INVALID, "rarefy_node_bases: level %u (0 .. 63)", level);
+    PTX_TRY(check_read_pass_state(ctx, db, reads, "rarefy_node_bases"));
+    PTX_TRY(check_stage_coverage(ctx, db, "rarefy_node_bases"));
+    return rarefy_node_bases_launch(ctx, db, reads, seed, replicate, level, bases_out);
+}
+
 int pantax_hip_strain_addin(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_near_miss_set *sel, double *x_out, double *obj_out, int32_t *status_out,
                             uint64_t *rows_out, uint64_t *count_out) {
     if (!ctx) return PANTAX_HIP_E_INVALID;

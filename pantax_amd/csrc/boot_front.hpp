@@ -35,10 +35,18 @@ struct BootFront {
     DevBuf<uint32_t> d_bpat_start /*[P + 1], the last = N*/, d_bpat_species /*[P]*/, d_bsp_pat_off /*[S + 1]*/;
 };
 
-// sp_key null: no weight hash (seed unread).  route_opt: the caller's membership route option.  `sized` is called once with N > 0, behind the row scan and
+// d_bases [V]: the per-node bases the row source reads -- the db's own (Db::d_bases) for the bootstrap, the leave-one-out and the add-one test, a thinned
+// level's for the rarefaction.  sp_key null: no weight hash (seed unread).  route_opt: the caller's membership route option.  `sized` is called once with N > 0, behind the row scan and
 // ahead of everything that is sized by N: the caller's plan; a non-zero return ends the call with it.  `what` heads the messages.
-int boot_front_build(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed, const std::string &route_opt,
-                     const char *what, const std::function<int(uint64_t)> &sized, BootFront &F);
+int boot_front_build(Ctx *ctx, Db *db, const unsigned long long *d_bases, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed,
+                     const std::string &route_opt, const char *what, const std::function<int(uint64_t)> &sized, BootFront &F);
+
+// bootstrap_launch (common.hpp) on the per-node bases array d_bases [V] instead of the db's own, under the membership route option route_opt, `what` heading
+// the messages.  front_built (may be null) is called once with the front half when it holds rows (F.N > 0), ahead of the replicates: a caller's own pass
+// over the base patterns.  Outputs as bootstrap_launch's, written only on success.
+int bootstrap_launch_on(Ctx *ctx, Db *db, const unsigned long long *d_bases, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed,
+                        uint32_t n_replicates, const std::string &route_opt, const char *what, const std::function<int(const BootFront &)> *front_built, double *x_out,
+                        double *obj_out, uint64_t *rows_out, int32_t *status_out);
 
 // boot_objective_kernel over the entries [0, nq) of plain solver tables (lad_args.hpp): obj[q] = the sum over the entry's rows of |m . x - a|, a workgroup per
 // entry, a wave per pattern; part [patterns] is scratch.  The bootstrap's objective pass, and the yardstick the leave-one-out pass is measured against.

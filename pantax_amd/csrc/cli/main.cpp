@@ -77,6 +77,11 @@ static void usage() {
             "                     strain its links crossed, open and broken (reads reach both sides, none goes across) and its deepest breaks, per species\n"
             "                     the read crossings that are a link of a reported strain, skip within one, switch between two or are foreign (one rank only)\n"
             "  --strain-links-top N   breaks printed per strain, by flank depth (default 10)\n"
+            "  --strain-rarefy F   rarefaction: the strain fit again on nested subsamples of the READS (1/2, 1/4, ..) -- per row of strain_abundance.txt and level\n"
+            "                     the refitted coverage over the replicates, scaled back to full depth, and how often it drops to 0 (one rank only)\n"
+            "  --strain-rarefy-levels N   thinned levels 1/2 .. 2^-N (default 5, at most 16)\n"
+            "  --strain-rarefy-replicates N   replicates per level (default 5)\n"
+            "  --strain-rarefy-seed N   seed of the thinning rule (default 42)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -102,8 +107,9 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
-    pantax_hip_profile_ext9 ext9;   // the outputs added behind the config's last field
-    memset(&ext9, 0, sizeof(ext9));
+    pantax_hip_profile_ext10 ext10;   // the outputs added behind the config's last field
+    memset(&ext10, 0, sizeof(ext10));
+    pantax_hip_profile_ext9 &ext9 = ext10.v9;
     pantax_hip_profile_ext8 &ext8 = ext9.v8;
     pantax_hip_profile_ext7 &ext7 = ext8.v7;
     pantax_hip_profile_ext6 &ext6 = ext7.v6;
@@ -111,8 +117,9 @@ int main(int argc, char **argv) {
     pantax_hip_profile_ext4 &ext4 = ext5.v4;
     pantax_hip_profile_ext3 &ext3 = ext4.v3;
     pantax_hip_profile_ext2 &ext = ext3.v2;
-    ext.v1.struct_size = sizeof(ext9);
+    ext.v1.struct_size = sizeof(ext10);
     ext.strain_bootstrap_seed = 42;
+    ext10.strain_rarefy_seed = 42;
     pantax_hip_db_pairs_config pairs;
     memset(&pairs, 0, sizeof(pairs));
     pairs.max_distance = -1;
@@ -194,6 +201,10 @@ int main(int argc, char **argv) {
         else if (a == "--strain-rescue-top") ext8.strain_rescue_top = strtoull(next(), nullptr, 10);
         else if (a == "--strain-links") ext9.strain_links_file = next();
         else if (a == "--strain-links-top") ext9.strain_links_top = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-rarefy") ext10.strain_rarefy_file = next();
+        else if (a == "--strain-rarefy-levels") ext10.strain_rarefy_levels = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-rarefy-replicates") ext10.strain_rarefy_replicates = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-rarefy-seed") ext10.strain_rarefy_seed = strtoull(next(), nullptr, 10);
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

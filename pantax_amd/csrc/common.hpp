@@ -147,7 +147,8 @@ struct CtxConfig {
     std::string row_sort;            // "radix" / "nodes"
     std::string objective;           // "nodes": the LP objective summed over the nodes
     // "walk": the strain report takes the membership of every species from the chosen walks (the compact masks, route 2 of member_plan.hpp), not from the node -> haplotype words
-    std::string read_strain_route, evidence_route, depth_route, near_miss_route, hap_pairs_route, fit_route, bootstrap_route, dropout_route, addin_route;
+    std::string read_strain_route, evidence_route, depth_route, near_miss_route, hap_pairs_route, fit_route, bootstrap_route, dropout_route, addin_route, rarefy_route;
+    uint64_t rarefy_levels_max = 0;  // levels of a replicate one pass of pantax_hip_strain_rarefy over the reads serves (0: from the free device memory, rarefy_plan.hpp; tests lower it to cut a replicate into passes)
     uint64_t bootstrap_rows_max = 0; // expanded rows of the bootstrap replicates in flight on the device (0: from the free device memory, bootstrap_plan.hpp; tests lower it to cut the replicates into chunks)
     uint64_t dropout_patterns_max = 0; // replicated patterns of the leave-one-out rounds in flight on the device (0: from the free device memory, dropout_plan.hpp; tests lower it to cut the rounds into chunks)
     bool dropout_yardstick = false;   // measurement (tools/dropout_probe.py): pantax_hip_strain_dropout also runs boot_objective_kernel over every round's entries; nothing of it is delivered
@@ -723,6 +724,12 @@ int fit_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_ha
 // stage_bootstrap.hip (pantax_hip_strain_bootstrap): selection and sp_key validated by the caller; x_out [R][C], obj_out / rows_out / status_out [R][S], R = n_replicates + 1
 int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed, uint32_t n_replicates, double *x_out,
                      double *obj_out, uint64_t *rows_out, int32_t *status_out);
+// stage_rarefy.hip (pantax_hip_strain_rarefy): selection, n_levels and n_replicates validated by the caller; E = 1 + n_replicates * n_levels entries, x_out [E][C],
+// obj_out / rows_out / status_out [E][S], reads_out [E][S][2], member_out [E][C][2]; written only on success
+int rarefy_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t seed, uint32_t n_levels, uint32_t n_replicates,
+                  double *x_out, double *obj_out, uint64_t *rows_out, int32_t *status_out, uint64_t *reads_out, uint64_t *member_out);
+// ... and its test seam (pantax_hip_rarefy_node_bases): the depth and the bases kernel for one level over every species, bases_out [V]
+int rarefy_node_bases_launch(Ctx *ctx, Db *db, Reads *rd, uint64_t seed, uint32_t replicate, uint32_t level, uint64_t *bases_out);
 // stage_dropout.hip (pantax_hip_strain_dropout): selection validated by the caller; Q = C + S entries, entry (s, e) at sel_off[s] + s + e; x_out in blocks of
 // E_s x K_s at dropout_x_offsets, obj_out / status_out [Q], rows_out [S], count_out [Q][4]
 int dropout_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, double *x_out, double *obj_out, int32_t *status_out, uint64_t *rows_out,

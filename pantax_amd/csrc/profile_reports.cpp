@@ -2,7 +2,7 @@
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
 // (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
-// report, the add-one report, the read class report, the segment report, the mosaic read report, the read rescue report and the link support report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT9_REPORTS).
+// report, the add-one report, the read class report, the segment report, the mosaic read report, the read rescue report, the link support report and the rarefaction report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT10_REPORTS).
 #include <algorithm>
 #include <cmath>
 #include <fstream>
@@ -147,6 +147,31 @@ int group_bootstrap(Run &run, const Ingest &in, const Selection &sn, pantax_hip_
         }
     }
     run.lap("  strain bootstrap");
+    return 0;
+}
+// --strain-rarefy, on the same coverage result and the resident reads: Sel_s = the group's rows (column = position: ascending haplotype)
+int group_rarefy(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &rf = sh.rep.rf;
+    const uint32_t Sg = k1 - k0;
+    const uint64_t E = rf.E, Cg = g.hap.size();
+    const pantax_hip_rarefy_set set{Sg, g.off.data(), g.hap.data(), run.p.rep.rf_seed, run.p.rep.rf_levels, run.p.rep.rf_replicates};
+    std::vector<double> x(E * Cg), obj(E * Sg);
+    std::vector<uint64_t> rows(E * Sg), reads(2 * E * Sg), member(2 * E * Cg);
+    std::vector<int32_t> status(E * Sg);
+    PTX_TRY(pantax_hip_strain_rarefy(run.ctx, db, in.reads.rd, &set, x.data(), obj.data(), rows.data(), status.data(), reads.data(), member.data()));
+    rf.x.resize(E * (g.entry0 + Cg)); rf.member.resize(2 * E * (g.entry0 + Cg));
+    for (uint64_t e = 0; e < E; ++e) {   // entry-major -> the E values of a selection entry, of a species side by side
+        for (uint64_t c = 0; c < Cg; ++c) {
+            rf.x[E * (g.entry0 + c) + e] = x[e * Cg + c];
+            for (int j = 0; j < 2; ++j) rf.member[2 * (E * (g.entry0 + c) + e) + j] = member[2 * (e * Cg + c) + j];
+        }
+        for (uint32_t k = 0; k < Sg; ++k) {
+            const uint64_t at = E * (k0 + k) + e;
+            rf.obj[at] = obj[e * Sg + k]; rf.rows[at] = rows[e * Sg + k]; rf.status[at] = status[e * Sg + k];
+            for (int j = 0; j < 2; ++j) rf.reads[2 * at + j] = reads[2 * (e * Sg + k) + j];
+        }
+    }
+    run.lap("  strain rarefaction");
     return 0;
 }
 // --strain-dropout, on the same coverage result: Sel_s = the group's rows (column = position: ascending haplotype)
@@ -1062,6 +1087,65 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-rarefy: per row of strain_abundance.txt, in its order, a row per level 0 .. L: the summary of its x over the level's replicates
+    // (pantax_hip_bootstrap_summary; level 0 = entry 0 alone), the mean scaled back by 2^level, the means of n_member and n_only; then per species of the
+    // shard, in the order it went through the device, per level the means of its counted reads, added bases and rows and the mean objective of the solved LPs
+    int rarefy() const {
+        return file(run.p.rep.ext10_path[X10REP_RAREFY],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tclass\tlevel\tfraction\tn_solved\tpredicted_coverage\trefit\tmean\tsd\tmin\tmax\tscaled_mean\tzero_fraction\tn_member\tn_only\tn_reads\tbases\tn_rows\tobjective\n",
+                    "rarefaction report", [&](std::ofstream &f) {
+            const auto &d = rep.rf;
+            const uint64_t E = d.E, L = run.p.rep.rf_levels, B = run.p.rep.rf_replicates;
+            // the entries of a level: entry 0 alone, or one per replicate
+            const auto n_of = [&](uint64_t l) { return l == 0 ? (uint64_t)1 : B; };
+            const auto entry = [&](uint64_t l, uint64_t i) { return l == 0 ? (uint64_t)0 : 1 + i * L + (l - 1); };
+            const auto mean_u64 = [&](const uint64_t *v, size_t stride, uint64_t l) {   // the f64 sum in ascending replicate, divided by their number
+                double s = 0.0;
+                for (uint64_t i = 0; i < n_of(l); ++i) s += (double)v[stride * entry(l, i)];
+                return s / (double)n_of(l);
+            };
+            std::vector<double> val(B ? B : 1);
+            std::vector<int32_t> st(B ? B : 1);
+            double o[10];
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "rarefaction", &e));
+                const int32_t *sk = d.status.data() + E * r.k;
+                const std::string head = strain_head(r), pc = fmt_f64(sh.met[r.hap].second_sol);
+                if (sk[0] != 0 && sk[0] != 1) continue;   // the species was not served: its "skipped" row says so
+                const double *x = d.x.data() + E * (uint64_t)e;
+                const uint64_t *m = d.member.data() + 2 * E * (uint64_t)e;
+                for (uint64_t l = 0; l <= L; ++l) {
+                    const uint64_t n = n_of(l);
+                    double mx = 0.0;
+                    bool any = false;
+                    for (uint64_t i = 0; i < n; ++i) {
+                        val[i] = x[entry(l, i)]; st[i] = sk[entry(l, i)];
+                        if (st[i] == 0 && (!any || val[i] > mx)) { mx = val[i]; any = true; }
+                    }
+                    PTX_TRY(pantax_hip_bootstrap_summary(n, val.data(), st.data(), o));
+                    const double scale = std::ldexp(1.0, (int)l);
+                    f << head << "\tstrain\t" << l << '\t' << fmt_f64(1.0 / scale) << '\t' << (uint64_t)o[0] << '\t' << pc << '\t' << fmt_f64(x[0]);
+                    if (o[0] > 0) f << '\t' << fmt_f64(o[1]) << '\t' << fmt_f64(o[2]) << '\t' << fmt_f64(o[9]) << '\t' << fmt_f64(mx) << '\t' << fmt_f64(o[1] * scale) << '\t' << fmt_f64(o[8]);
+                    else f << "\t-\t-\t-\t-\t-\t-";
+                    f << '\t' << fmt_f64(mean_u64(m, 2, l)) << '\t' << fmt_f64(mean_u64(m + 1, 2, l)) << "\t-\t-\t-\t-\n";
+                }
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const int32_t *sk = d.status.data() + E * k;
+                const std::string head = species_head(k);
+                if (sk[0] != 0 && sk[0] != 1) { f << head << "\tskipped\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n"; continue; }
+                for (uint64_t l = 0; l <= L; ++l) {
+                    const uint64_t n = n_of(l);
+                    for (uint64_t i = 0; i < n; ++i) { val[i] = d.obj[E * k + entry(l, i)]; st[i] = sk[entry(l, i)]; }
+                    PTX_TRY(pantax_hip_bootstrap_summary(n, val.data(), st.data(), o));
+                    f << head << "\tspecies\t" << l << '\t' << fmt_f64(1.0 / std::ldexp(1.0, (int)l)) << '\t' << (uint64_t)o[0] << "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t"
+                      << fmt_f64(mean_u64(d.reads.data() + 2 * E * k, 2, l)) << '\t' << fmt_f64(mean_u64(d.reads.data() + 2 * E * k + 1, 2, l)) << '\t'
+                      << fmt_f64(mean_u64(d.rows.data() + E * k, 1, l)) << '\t' << (o[0] > 0 ? fmt_f64(o[1]) : std::string("-")) << '\n';
+                }
+            }
+            return 0;
+        });
+    }
     // --strain-pair-evidence: per species of the shard, in the order it went through the device, for every two of its rows a < b (ascending haplotype index)
     // what both walk (shared) and what only a, only b walks, as {n_nodes, len, covered, bases} with depth and breadth
     int pair_evidence() const {
@@ -1132,6 +1216,10 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.ext8_run[X8REP_RESCUE]) {
         rep.rc.species.assign(3 * RES_N_CLASSES * (size_t)Su, 0); rep.rc.step.assign(3 * (size_t)Su, 0); rep.rc.row_off.assign(Su + 1, 0); rep.rc.open.assign(Su, 0);
     }
+    if (plan.ext10_run[X10REP_RAREFY]) {
+        rep.rf.E = 1 + (uint64_t)plan.rf_replicates * plan.rf_levels;
+        rep.rf.obj.assign(rep.rf.E * Su, 0.0); rep.rf.rows.assign(rep.rf.E * Su, 0); rep.rf.status.assign(rep.rf.E * Su, 1); rep.rf.reads.assign(2 * rep.rf.E * Su, 0);
+    }
     if (plan.ext9_run[X9REP_LINKS]) {
         rep.lk.species.assign(LNK_N_SPECIES * (size_t)Su, 0); rep.lk.link.assign(LNK_N_TABLE * (size_t)Su, 0); rep.lk.open.assign(Su, 0);
     }
@@ -1159,6 +1247,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.ext7_run[X7REP_MOSAIC]) PTX_TRY(group_mosaic(run, in, db, k0, k1, g, sh));
     if (plan.ext8_run[X8REP_RESCUE]) PTX_TRY(group_rescue(run, in, db, k0, k1, g, sh, gc));
     if (plan.ext9_run[X9REP_LINKS]) PTX_TRY(group_links(run, in, db, k0, k1, g, sh));
+    if (plan.ext10_run[X10REP_RAREFY]) PTX_TRY(group_rarefy(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh, gc));
     return 0;
@@ -1185,6 +1274,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext7_run[X7REP_MOSAIC]) PTX_TRY(w.mosaic());
     if (plan.ext8_run[X8REP_RESCUE]) PTX_TRY(w.rescue());
     if (plan.ext9_run[X9REP_LINKS]) PTX_TRY(w.links());
+    if (plan.ext10_run[X10REP_RAREFY]) PTX_TRY(w.rarefy());
     return 0;
 }
 }  // namespace reports

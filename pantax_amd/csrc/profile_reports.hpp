@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
-// of pantax_hip_profile_ext9 with its row of EXT9_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS, EXT5_REPORTS, EXT6_REPORTS, EXT7_REPORTS and EXT8_REPORTS are closed: the structs they point into keep their size), a sub-struct
+// of pantax_hip_profile_ext10 with its row of EXT10_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS, EXT5_REPORTS, EXT6_REPORTS, EXT7_REPORTS, EXT8_REPORTS and EXT9_REPORTS are closed: the structs they point into keep their size), a sub-struct
 // here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
@@ -62,6 +62,10 @@ struct ReportData {
     // --strain-links: species[6k ..) and link[4k ..) as pantax_hip_strain_links writes them, open[k] = the species went through the call with K_s <= 64;
     // per entry e its eight counters hap[8e ..) and its break records [brk_off[e], brk_off[e + 1]) in ascending step (node_a / node_b species-local)
     struct { std::vector<uint64_t> species, link, hap, brk_off{0}, start, flank, mask; std::vector<uint32_t> node_a, node_b; std::vector<uint8_t> open; } lk;
+    // --strain-rarefy: E = 1 + replicates x levels entries (entry 0 the full sample, 1 + (b - 1) levels + (l - 1) level l of replicate b); per selection
+    // entry e its E values x[E e ..) and member[2 E e ..) = {n_member, n_only}; per species k obj / rows / status [E k ..) and reads[2 E k ..) = {counted
+    // reads, bases added}
+    struct { uint64_t E = 1; std::vector<double> x, obj; std::vector<uint64_t> rows, reads, member; std::vector<int32_t> status; } rf;
     // --strain-near-miss: species[12k ..) = {orphan, claimed, contested}; the printed candidates rows[row_off[k] .. row_off[k + 1]) in rank order: the
     // haplotype ([hap_names]) and q = {novel, exclusive, all} x {n_nodes, len, covered, bases}
     struct NearMissRow { uint64_t hap; uint64_t q[12]; };

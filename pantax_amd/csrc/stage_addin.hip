@@ -285,7 +285,7 @@ int addin_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_
         w_off[s + 1] = w_hap.size();
     }
     BootFront F;
-    PTX_TRY(boot_front_build(ctx, db, w_off.data(), w_hap.data(), nullptr, 0, ctx->cfg.addin_route, "strain_addin", [](uint64_t) { return 0; }, F));
+    PTX_TRY(boot_front_build(ctx, db, (const unsigned long long *)db->d_bases.p, w_off.data(), w_hap.data(), nullptr, 0, ctx->cfg.addin_route, "strain_addin", [](uint64_t) { return 0; }, F));
     // results on the host; the caller's arrays are written at the very end
     std::vector<double> hx((size_t)X, 0.0), hobj((size_t)Q, 0.0);
     std::vector<int32_t> hstatus((size_t)Q, 1);

@@ -235,8 +235,8 @@ __global__ void __launch_bounds__(256) boot_objective_kernel(const int32_t *__re
 }  // namespace
 
 // the front half of the bootstrap and of the leave-one-out test (boot_front.hpp)
-int boot_front_build(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed, const std::string &route_opt,
-                     const char *what, const std::function<int(uint64_t)> &sized, BootFront &F) {
+int boot_front_build(Ctx *ctx, Db *db, const unsigned long long *d_bases, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed,
+                     const std::string &route_opt, const char *what, const std::function<int(uint64_t)> &sized, BootFront &F) {
     const uint32_t S = db->S;
     const uint64_t V = db->V;
     F.N = 0; F.P = 0; F.k_max = 0;
@@ -272,7 +272,7 @@ int boot_front_build(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
     PTX_HIP(ctx, hipMemsetAsync(F.d_counts.p, 0, 4 * sizeof(uint32_t), ctx->stream));
     for (int w = 0; w < 3; ++w) PTX_HIP(ctx, F.ka[w].alloc(V));
     PTX_HIP(ctx, F.d_va.alloc(V));
-    const BootRowSrc src{F.d_node_off.p, S, F.d_tab.p, F.d_bit_col.p, db->d_node_len.p, (const unsigned long long *)db->d_bases.p,
+    const BootRowSrc src{F.d_node_off.p, S, F.d_tab.p, F.d_bit_col.p, db->d_node_len.p, d_bases,
                          by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, wm.d_mask.p};
     PTX_TRY(exclusive_scan_fn(ctx, BootRowLoad{src}, BootRowStore{src, F.ka[0].p, F.ka[1].p, F.ka[2].p, F.d_va.p}, V, F.d_counts.p, "scan_chained_kernel<BootRows>"));
     uint32_t n_rows32 = 0;
@@ -329,11 +329,19 @@ int boot_objective_launch(Ctx *ctx, uint32_t nq, const int32_t *sp_p, const uint
 // selection and sp_key validated by the caller
 int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed, uint32_t n_replicates, double *x_out,
                      double *obj_out, uint64_t *rows_out, int32_t *status_out) {
+    return bootstrap_launch_on(ctx, db, (const unsigned long long *)db->d_bases.p, sel_off, sel_hap, sp_key, seed, n_replicates, ctx->cfg.bootstrap_route, "strain_bootstrap",
+                               nullptr, x_out, obj_out, rows_out, status_out);
+}
+
+// the same on any per-node bases array of the db's V nodes (boot_front.hpp): the rarefaction's refit of a thinned level is this with n_replicates = 0
+int bootstrap_launch_on(Ctx *ctx, Db *db, const unsigned long long *d_bases, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *sp_key, uint64_t seed,
+                        uint32_t n_replicates, const std::string &route_opt, const char *what, const std::function<int(const BootFront &)> *front_built, double *x_out,
+                        double *obj_out, uint64_t *rows_out, int32_t *status_out) {
     const uint32_t S = db->S;
     const uint64_t C = sel_off[S], V = db->V, R = (uint64_t)n_replicates + 1;
     if (S == 0) return 0;
-    if (V >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_bootstrap: %llu nodes exceed 32-bit positions", (unsigned long long)V);
-    if (R * std::max<uint64_t>(C, S) >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_bootstrap: %llu replicates of %llu selection entries and %u species exceed 32-bit positions", (unsigned long long)R, (unsigned long long)C, S);
+    if (V >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "%s: %llu nodes exceed 32-bit positions", what, (unsigned long long)V);
+    if (R * std::max<uint64_t>(C, S) >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "%s: %llu replicates of %llu selection entries and %u species exceed 32-bit positions", what, (unsigned long long)R, (unsigned long long)C, S);
     // ---- the plan of the chunks, once the rows are counted
     BootstrapPlan plan;
     const auto sized = [&](uint64_t n_rows) {
@@ -350,9 +358,10 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
     // ---- host tables, rows, sort, base patterns (boot_front.hpp)
     BootFront F;
     {
-        const int rc = boot_front_build(ctx, db, sel_off, sel_hap, sp_key, seed, ctx->cfg.bootstrap_route, "strain_bootstrap", sized, F);
+        const int rc = boot_front_build(ctx, db, d_bases, sel_off, sel_hap, sp_key, seed, route_opt, what, sized, F);
         if (rc != 0) return rc;
     }
+    if (front_built && F.N) PTX_TRY((*front_built)(F));
     const std::vector<int32_t> &pre_host = F.pre_host;
     // results on the host; the caller's arrays are written at the very end
     std::vector<double> hx((size_t)(R * C)), hobj((size_t)(R * S), 0.0);
@@ -429,7 +438,7 @@ int bootstrap_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
         PTX_TRY(download(ctx, &h_flag, d_flags.p, 1));
         PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (h_flag)
-            return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_bootstrap: the replicates %llu .. %llu drew more than the %u expanded rows their chunk is sized for (bootstrap_plan.hpp)",
+            return fail(ctx, PANTAX_HIP_E_LIMIT, "%s: the replicates %llu .. %llu drew more than the %u expanded rows their chunk is sized for (bootstrap_plan.hpp)", what,
                         (unsigned long long)b0, (unsigned long long)(b0 + nb - 1), cap_rows);
         for (uint32_t q = 0; q < nq; ++q)
             hstatus[b0 * S + q] = c_pre[q] != BOOT_PENDING ? c_pre[q] : (c_status[q] == 0 ? 0 : PANTAX_HIP_E_SOLVER);

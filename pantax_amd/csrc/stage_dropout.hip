@@ -250,7 +250,7 @@ int dropout_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *se
     if (!dropout_x_offsets(S, sel_off, x_off.data())) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_dropout: the x blocks of %llu selection entries exceed 64-bit positions", (unsigned long long)C);
     const uint64_t X = x_off[S];
     BootFront F;
-    PTX_TRY(boot_front_build(ctx, db, sel_off, sel_hap, nullptr, 0, ctx->cfg.dropout_route, "strain_dropout", [](uint64_t) { return 0; }, F));
+    PTX_TRY(boot_front_build(ctx, db, (const unsigned long long *)db->d_bases.p, sel_off, sel_hap, nullptr, 0, ctx->cfg.dropout_route, "strain_dropout", [](uint64_t) { return 0; }, F));
     // results on the host; the caller's arrays are written at the very end
     std::vector<double> hx((size_t)X, 0.0), hobj((size_t)Q, 0.0);
     std::vector<int32_t> hstatus((size_t)Q, 1);

@@ -613,6 +613,33 @@ class Engine:
                                                          p(step), p(start), p(node_a), p(node_b), p(flank), p(mask)))
         return species, link, hap, brk_off, step, start, node_a, node_b, flank, mask
 
+    def strain_rarefy(self, sel_off, sel_hap, seed=42, n_levels=5, n_replicates=5):
+        """Rarefaction of the strain fit (pantax_hip_strain_rarefy) of the resident reads, binned against the resident db, on the coverage result
+        get_node_abundances left on the device: the LP of strain_bootstrap refitted on nested subsamples of the reads.  sel_off [S+1], sel_hap as for
+        strain_bootstrap.  E = 1 + n_replicates * n_levels entries: 0 the full sample, 1 + (b - 1) n_levels + (l - 1) level l (reads kept with probability
+        2^-l) of replicate b -> (x float64 [E, C], obj float64 [E, S], rows uint64 [E, S], status int32 [E, S], reads uint64 [E, S, 2] = counted reads /
+        bases added, member uint64 [E, C, 2] = n_member / n_only)."""
+        so, sh = as_c(sel_off, np.uint64), as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("strain_rarefy: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        E = 1 + max(int(n_replicates), 0) * max(int(n_levels), 0)
+        cs = _ffi.RarefySet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, int(seed), int(n_levels), int(n_replicates))
+        x = np.zeros((E, len(sh)), dtype=np.float64)
+        obj = np.zeros((E, self.S), dtype=np.float64)
+        rows = np.zeros((E, self.S), dtype=np.uint64)
+        status = np.zeros((E, self.S), dtype=np.int32)
+        reads = np.zeros((E, self.S, 2), dtype=np.uint64)
+        member = np.zeros((E, len(sh), 2), dtype=np.uint64)
+        q = lambda a: p(a) if a.size else None
+        self._check(self.lib.pantax_hip_strain_rarefy(self.ctx, self.db, self.reads, C.byref(cs), q(x), q(obj), q(rows), q(status), q(reads), q(member)))
+        return x, obj, rows, status, reads, member
+
+    def rarefy_node_bases(self, seed, replicate, level):
+        """pantax_hip_rarefy_node_bases: bases_per_node of the reads of ONE level (0: every read) of a replicate, over every species -> uint64 [V]"""
+        out = np.zeros(max(self.V, 1), dtype=np.uint64)
+        self._check(self.lib.pantax_hip_rarefy_node_bases(self.ctx, self.db, self.reads, int(seed), int(replicate), int(level), p(out)))
+        return out[:self.V]
+
     def strain_addin(self, sel_off, sel_hap, cand_off, cand_hap):
         """Add-one test of the strain fit (pantax_hip_strain_addin) on the coverage result get_node_abundances left on the device.  sel_off / sel_hap and
         cand_off / cand_hap as for strain_near_miss.  Species s of K_s reported and J_s candidate haplotypes has W_s = K_s + J_s columns (the reported ones
@@ -838,7 +865,8 @@ class Engine:
                 strain_addin_file=None, strain_addin_top=0, strain_em_file=None, strain_em_classes=0, strain_em_iterations=0,
                 strain_segments_file=None, strain_segments_min=0, strain_segments_bridge=None, strain_segments_peak=0,
                 strain_mosaic_file=None, strain_mosaic_top=0, strain_rescue_file=None, strain_rescue_top=0,
-                strain_links_file=None, strain_links_top=0):
+                strain_links_file=None, strain_links_top=0,
+                strain_rarefy_file=None, strain_rarefy_levels=0, strain_rarefy_replicates=0, strain_rarefy_seed=42):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -859,7 +887,9 @@ class Engine:
         strain_mosaic_file: path of the mosaic read report (--strain-mosaic; one rank only), strain_mosaic_top the junctions it prints per species
         (0: 10; "off": none, and none are collected).
         strain_rescue_file: path of the read rescue report (--strain-rescue; one rank only), strain_rescue_top the candidates it prints per species (0: 5).
-        strain_links_file: path of the link support report (--strain-links; one rank only), strain_links_top the breaks it prints per strain (0: 10)."""
+        strain_links_file: path of the link support report (--strain-links; one rank only), strain_links_top the breaks it prints per strain (0: 10).
+        strain_rarefy_file: path of the rarefaction report (--strain-rarefy; one rank only), strain_rarefy_levels the thinned levels 1/2 .. 2^-N (0: 5; at
+        most 16), strain_rarefy_replicates the replicates per level (0: 5), strain_rarefy_seed the seed of the thinning rule."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -902,7 +932,7 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None and strain_links_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None and strain_links_file is None and strain_rarefy_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
@@ -915,7 +945,9 @@ class Engine:
                                   strain_mosaic_file=enc(strain_mosaic_file),
                                   strain_mosaic_top=_ffi.MOSAIC_TOP_OFF if strain_mosaic_top == "off" else int(strain_mosaic_top),
                                   strain_rescue_file=enc(strain_rescue_file), strain_rescue_top=int(strain_rescue_top),
-                                  strain_links_file=enc(strain_links_file), strain_links_top=int(strain_links_top))
+                                  strain_links_file=enc(strain_links_file), strain_links_top=int(strain_links_top),
+                                  strain_rarefy_file=enc(strain_rarefy_file), strain_rarefy_levels=int(strain_rarefy_levels),
+                                  strain_rarefy_replicates=int(strain_rarefy_replicates), strain_rarefy_seed=int(strain_rarefy_seed))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -1259,6 +1291,12 @@ def rescue_rank(cand_hap, cand_out, top=0):
     if rc != 0:
         raise ValueError("rescue_rank: refused (%d)" % rc)
     return out[:n.value].copy()
+
+
+def rarefy_depth(seed, replicate, read):
+    """pantax_hip_rarefy_depth: the depth (0 .. 63) of read `read` (its index in the uploaded columns) in replicate `replicate` of the rarefaction: the read
+    belongs to level l iff depth >= l.  Host only: no Engine is needed."""
+    return int(_ffi.load().pantax_hip_rarefy_depth(int(seed), int(replicate), int(read)))
 
 
 def link_crossings(masks, known, K):
