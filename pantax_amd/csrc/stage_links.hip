@@ -9,7 +9,7 @@
 // distinct links, files {larger node, smaller node, species} of a link at its head and ORs every key's payload bit into L[link].  links_off_kernel
 // files the links at their smaller node: link_off[u] = the first link whose smaller node is >= u, a binary search per node over the distinct smaller
 // nodes, so that a lookup is one offset pair and a scan over the node's few larger neighbours.
-// Read pass.  links_read_kernel walks the locus-grouped step stream (read_strain_device.hpp: a wave per 64-step group, a lane per step).  A step's
+// Read pass.  links_read_kernel walks the locus-grouped step stream (read_pass_device.hpp: a wave per 64-step group, a lane per step).  A step's
 // successor in its walk is the next lane; lane 63 reads the first node of the next group, which is the walk's next step also for walks of more than 64
 // steps.  A crossing that is a link adds one to support[link]; any other crossing takes the membership words of its two nodes (either route of
 // member_plan.hpp) and adds to its class per lane -- these are rare.  counted_reads, crossings and known are reduced per species of the wave: three
@@ -28,16 +28,12 @@
 #include "common.hpp"
 #include "cov_track_tile.hpp"
 #include "links_plan.hpp"
-#include "primitives.hpp"
-#include "read_strain_device.hpp"
+#include "read_pass_device.hpp"
 #include "scan_chained.hpp"
-#include "wave.hpp"
 
 namespace ptx {
 
 namespace {
-
-constexpr uint32_t LK_NONE = 0xFFFFFFFFu;
 
 struct LkSpecies {
     unsigned long long all;   // the K_s low bits: L of a core link
@@ -66,13 +62,7 @@ __device__ __forceinline__ uint32_t lk_find(const LkTable &tb, uint32_t u, uint3
     const uint32_t d1 = tb.off[a + 1];
     for (uint32_t d = tb.off[a]; d < d1; ++d)
         if (tb.hi[d] == b) return d;
-    return LK_NONE;
-}
-// the word of global node v over the species' list (an open species: one word; an empty list: nobody walks anything)
-__device__ __forceinline__ unsigned long long lk_word(const RsSpecies &st, uint32_t v, const unsigned long long *__restrict__ node_haps,
-                                                      const unsigned long long *__restrict__ mask) {
-    if (st.m.route == 0u) return 0ull;
-    return st.m.route == 1u ? (node_haps[v] & st.m.bits) : mask[member_mask_row(st.m, v)];
+    return MEMBER_NO_ENTRY;
 }
 
 // ---- the link table ----
@@ -134,12 +124,9 @@ __global__ void __launch_bounds__(256) links_count_kernel(uint64_t n_bound, cons
         uint32_t s = 0u;
         bool crossed = false, core = false;
         if (in) { s = sp[d]; crossed = support[d] != 0ull; core = L[d] == lks[s].all; }
-        for (unsigned long long rem = __builtin_amdgcn_ballot_w64(in); rem;) {
-            const uint32_t s0 = lane_get(s, __builtin_ctzll(rem));
-            const bool mine = in && s == s0;
-            const unsigned long long mb = __builtin_amdgcn_ballot_w64(mine), xb = __builtin_amdgcn_ballot_w64(mine && crossed);
+        rs_species_rounds(in, s, [&](uint32_t s0, bool mine, unsigned long long mb) {
+            const unsigned long long xb = __builtin_amdgcn_ballot_w64(mine && crossed);
             const unsigned long long cb = __builtin_amdgcn_ballot_w64(mine && core), cxb = __builtin_amdgcn_ballot_w64(mine && core && crossed);
-            rem &= ~mb;
             if (lane == 0) {
                 unsigned long long *const o = link_out + (uint64_t)s0 * LNK_N_TABLE;
                 atomicAdd(o + LNK_DISTINCT, (unsigned long long)__popcll(mb));
@@ -147,16 +134,17 @@ __global__ void __launch_bounds__(256) links_count_kernel(uint64_t n_bound, cons
                 if (cb) atomicAdd(o + LNK_CORE, (unsigned long long)__popcll(cb));
                 if (cxb) atomicAdd(o + LNK_CORE_CROSSED, (unsigned long long)__popcll(cxb));
             }
-        }
+        });
     }
 }
 
 // ---- the read pass ----
-__global__ void __launch_bounds__(256) links_read_kernel(uint32_t n_groups, uint32_t n_slots, uint64_t T_pad, const uint32_t *__restrict__ group_slot,
+__global__ void __launch_bounds__(256) links_read_kernel(uint32_t n_groups, uint32_t n_slots, const uint32_t *__restrict__ group_slot,
                                                          const uint8_t *__restrict__ step_code, const uint32_t *__restrict__ g_node_id,
-                                                         const uint4 *__restrict__ read_rec, const uint2 *__restrict__ slot_rec, const RsSpecies *__restrict__ tab,
-                                                         const LkSpecies *__restrict__ lks, const unsigned long long *__restrict__ node_haps,
-                                                         const unsigned long long *__restrict__ mask, LkTable tb, unsigned long long *__restrict__ sp_out) {
+                                                         const uint4 *__restrict__ read_rec, const uint2 *__restrict__ slot_rec, uint64_t T_pad,
+                                                         const RsSpecies *__restrict__ tab, const LkSpecies *__restrict__ lks,
+                                                         const unsigned long long *__restrict__ node_haps, const unsigned long long *__restrict__ mask, LkTable tb,
+                                                         unsigned long long *__restrict__ sp_out) {
     const int lane = threadIdx.x & 63;
     for (uint32_t g = blockIdx.x * 4 + (threadIdx.x >> 6); g < n_groups; g += gridDim.x * 4) {
         const uint32_t gs = group_slot[g];                                   // (wave-uniform) NO_SLOT: a group of pads only
@@ -169,28 +157,25 @@ __global__ void __launch_bounds__(256) links_read_kernel(uint32_t n_groups, uint
         LkSpecies ls{0ull, 0u, 0u};
         if (cross) ls = lks[L.sr.x];
         const bool open = cross && ls.open != 0u;
-        uint32_t d = LK_NONE;
+        uint32_t d = MEMBER_NO_ENTRY;
         if (open) d = lk_find(tb, L.v, nxt);
-        const bool known = open && d != LK_NONE;
+        const bool known = open && d != MEMBER_NO_ENTRY;
         if (known) atomicAdd(&tb.support[d], 1ull);
         if (open && !known) {                                                // rare: per lane
-            const int cls = link_unknown_class(lk_word(L.st, L.v, node_haps, mask), lk_word(L.st, nxt, node_haps, mask));
+            const int cls = link_unknown_class(rs_word1(L.st, L.v, node_haps, mask), rs_word1(L.st, nxt, node_haps, mask));
             atomicAdd(sp_out + (uint64_t)L.sr.x * LNK_N_SPECIES + (uint32_t)cls, 1ull);
         }
         // counted_reads, crossings and known take nearly every step: per species of the wave
-        for (unsigned long long rem = __builtin_amdgcn_ballot_w64(L.counted); rem;) {
-            const uint32_t s0 = lane_get(L.sr.x, __builtin_ctzll(rem));
-            const bool mine = L.counted && L.sr.x == s0;
-            const unsigned long long mb = __builtin_amdgcn_ballot_w64(mine), rb = __builtin_amdgcn_ballot_w64(mine && L.last);
+        rs_species_rounds(L.counted, L.sr.x, [&](uint32_t s0, bool mine, unsigned long long) {
+            const unsigned long long rb = __builtin_amdgcn_ballot_w64(mine && L.last);
             const unsigned long long xb = __builtin_amdgcn_ballot_w64(mine && cross), kb = __builtin_amdgcn_ballot_w64(mine && known);
-            rem &= ~mb;
             if (lane == 0) {
                 unsigned long long *const o = sp_out + (uint64_t)s0 * LNK_N_SPECIES;
                 if (rb) atomicAdd(o + LNK_COUNTED, (unsigned long long)__popcll(rb));
                 if (xb) atomicAdd(o + LNK_CROSSINGS, (unsigned long long)__popcll(xb));
                 if (kb) atomicAdd(o + LNK_KNOWN, (unsigned long long)__popcll(kb));
             }
-        }
+        });
     }
 }
 
@@ -223,7 +208,7 @@ __global__ void __launch_bounds__(256) links_walk_kernel(uint32_t n_tiles, const
             const uint32_t w = j < 15 ? v[j < 15 ? j + 1 : 15] : after;
             const uint32_t d = lk_find(tb, v[j], w);
             unsigned long long sup = 0ull, lm = 0ull;
-            if (d != LK_NONE) { sup = tb.support[d]; lm = tb.L[d]; }   // (always: the table was built from these positions)
+            if (d != MEMBER_NO_ENTRY) { sup = tb.support[d]; lm = tb.L[d]; }   // (always: the table was built from these positions)
             const bool crossed = sup != 0ull;
             const bool broken = !crossed && bases[v[j]] != 0ull && bases[w] != 0ull;
             const bool priv = lm == me;
@@ -257,7 +242,7 @@ __global__ void __launch_bounds__(256) links_walk_kernel(uint32_t n_tiles, const
                     out.node_a[slot] = v[j] - tl.node_base;
                     out.node_b[slot] = w - tl.node_base;
                     out.flank[slot] = fa < fb ? fa : fb;
-                    out.mask[slot] = d != LK_NONE ? tb.L[d] : 0ull;
+                    out.mask[slot] = d != MEMBER_NO_ENTRY ? tb.L[d] : 0ull;
                 }
                 ++slot;
             }
@@ -363,14 +348,7 @@ int links_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *sel_off, const uin
             hipLaunchKernelGGL(links_off_kernel, dim3(grid_for(V + 1, 256, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, V, d_lo, d_D.p, d_off.p);
         }
     }
-    const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
-    const unsigned long long *node_haps = rt.by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr;
-    if (n_slots && n_groups) {
-        KTimer tm(ctx, "links_read_kernel");
-        hipLaunchKernelGGL(links_read_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->T_pad,
-                           rd->d_g_group_slot.p, rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p, d_lks.p, node_haps,
-                           rt.wm.d_mask.p, tb, d_sp_out);
-    }
+    rs_launch_groups(ctx, rd, "links_read_kernel", links_read_kernel, rd->T_pad, d_tab.p, d_lks.p, rs_node_haps(rt, db), rt.wm.d_mask.p, tb, d_sp_out);
     DevBuf<LkTileSum> d_sums;
     std::vector<LkTileSum> sums(n_tiles);
     if (n_keys) {

@@ -5,7 +5,7 @@
 // pass (stage_read_support.hip).  M(v) = the candidates of the species that walk node v, one u64 (species of 1 <= K_s <= 64).  A read with an empty M(v) is
 // foreign; every other read is cut greedily from the left: a segment grows while the AND of its steps' M stays non-zero.  Integers only: no order matters.
 //
-// mosaic_kernel walks the locus-grouped step stream as the other read passes do (read_strain_device.hpp: a wave per 64-step group, a lane per step).
+// mosaic_kernel walks the locus-grouped step stream as the other read passes do (read_pass_device.hpp: a wave per 64-step group, a lane per step).
 // Walks of at most 64 steps lie inside their group:
 //   foreign     one ballot of the lanes with M = 0; a lane ANDs it with its walk's lanes.  Foreign walks leave the cut (their lanes carry all ones);
 //   cut         rounds of the segmented AND (seg_and).  After a round the first lane of a walk whose prefix is zero is a break: the lowest bit of the ballot
@@ -16,7 +16,7 @@
 //               segment from the lane below and the strain of its own segment from that segment's last lane (the ballot of such lanes, ctz at and above
 //               the own lane), both through ds_bpermute;
 //   counters    counted and compatible take nearly every read: per species of the wave one ballot, two DPP reductions and one 64-bit atomicAdd per
-//               non-zero sum from lane 0, as in read_support_kernel.  The rare classes (mosaic, foreign), the per-candidate segments, the switches and
+//               non-zero sum from lane 0 (rs_species_rounds, rs_reduce_add).  The rare classes (mosaic, foreign), the per-candidate segments, the switches and
 //               the junction records add per lane; the break lanes of a wave share one returning atomic on the break counter.
 // A walk of more than 64 steps cannot be cut group by group in any order: the cut is sequential.  The wave that meets its first step takes the whole
 // walk: a pass over its groups for the foreign steps, then chunk by chunk the words into the lanes and a wave-uniform loop over the chunk's lanes that
@@ -28,15 +28,11 @@
 #include <cmath>
 #include "common.hpp"
 #include "mosaic_plan.hpp"
-#include "primitives.hpp"
-#include "read_strain_device.hpp"
-#include "wave.hpp"
+#include "read_pass_device.hpp"
 
 namespace ptx {
 
 namespace {
-
-constexpr uint32_t MOS_NO_ENTRY = 0xFFFFFFFFu;
 
 struct MosSpecies {
     uint64_t pair_base;   // first entry of the species' K x K block of the switch counts
@@ -53,21 +49,6 @@ struct MosOut {
     unsigned long long cap;
 };
 
-__device__ __forceinline__ unsigned long long lanes_from(int a) { return ~0ull << a; }          // lanes a .. 63
-__device__ __forceinline__ unsigned long long lanes_upto(int b) { return ~0ull >> (63 - b); }   // lanes 0 .. b
-
-__device__ __forceinline__ void mos_add3(unsigned long long *__restrict__ dst, unsigned long long n, unsigned long long steps, unsigned long long span) {
-    if (n) atomicAdd(dst, n);
-    if (steps) atomicAdd(dst + 1, steps);
-    if (span) atomicAdd(dst + 2, span);
-}
-// sum of Q over the lanes of `on` (its ballot is `b`, not empty) -> dst; all 64 lanes call it
-__device__ __forceinline__ void mos_reduce_add(int lane, bool on, unsigned long long b, uint32_t steps, uint32_t span, unsigned long long *__restrict__ dst) {
-    const auto add = [](unsigned long long x, unsigned long long y) { return x + y; };
-    const unsigned long long qs = wave_reduce(on ? (unsigned long long)steps : 0ull, add);
-    const unsigned long long qp = wave_reduce(on ? (unsigned long long)span : 0ull, add);
-    if (lane == 0) mos_add3(dst, (unsigned long long)__popcll(b), qs, qp);
-}
 // the candidate entry a segment with the non-zero word `a` is assigned: bits ascend with the haplotype index, the first of equal weights wins (a set whose
 // weights are all NaN or -inf keeps its lowest bit)
 __device__ __forceinline__ uint32_t mos_assigned(unsigned long long a, const RsSpecies &st, const double *__restrict__ bit_w, const uint32_t *__restrict__ bit_entry) {
@@ -81,23 +62,18 @@ __device__ __forceinline__ uint32_t mos_assigned(unsigned long long a, const RsS
     }
     return bit_entry[st.bit_base + besti];
 }
-__device__ __forceinline__ uint32_t mos_span(const uint4 &rr) { return rr.w >= rr.z ? rr.w - rr.z : 0u; }
 __device__ __forceinline__ bool mos_served(const RsSpecies &st) { return st.m.route != 0u && st.m.nw == 1u; }   // 1 <= K_s <= 64
-__device__ __forceinline__ unsigned long long mos_word(const RsSpecies &st, uint32_t v, const unsigned long long *__restrict__ node_haps,
-                                                       const unsigned long long *__restrict__ mask) {
-    return st.m.route == 1u ? (node_haps[v] & st.m.bits) : mask[member_mask_row(st.m, v)];
-}
 __device__ __forceinline__ void mos_file_junction(const MosOut &out, unsigned long long at, uint32_t species, uint32_t node_a, uint32_t node_b) {
     if (at >= out.cap) return;   // (cap = 0: not collected; beyond the cap the counter goes on counting and nothing is written)
     uint32_t *const j = out.junction + at * 3ull;
     j[0] = species; j[1] = node_a; j[2] = node_b;
 }
 __device__ __forceinline__ void mos_add_switch(const MosOut &out, const MosSpecies &ms, uint32_t e_left, uint32_t e_right) {
-    if (e_left == MOS_NO_ENTRY || e_right == MOS_NO_ENTRY) return;
+    if (e_left == MEMBER_NO_ENTRY || e_right == MEMBER_NO_ENTRY) return;
     atomicAdd(out.pair + ms.pair_base + (uint64_t)(e_left - ms.ent0) * ms.K + (e_right - ms.ent0), 1ull);
 }
 __device__ __forceinline__ void mos_add_segment(const MosOut &out, uint32_t e, uint32_t steps) {
-    if (e == MOS_NO_ENTRY) return;
+    if (e == MEMBER_NO_ENTRY) return;
     atomicAdd(out.hap + (uint64_t)e * 2u, 1ull);
     atomicAdd(out.hap + (uint64_t)e * 2u + 1u, (unsigned long long)steps);
 }
@@ -112,31 +88,31 @@ __device__ __forceinline__ void mos_long_walk(int lane, int l0, const RsLane &L,
     const uint32_t sp = lane_get(L.sr.x, l0), node_off = lane_get(L.sr.y, l0);
     if ((int32_t)sp < 0) return;                                              // not counted
     const RsSpecies st = tab[sp];
-    const uint32_t steps = rr.y, span = mos_span(rr);
+    const uint32_t steps = rr.y, span = rs_span(rr);
     unsigned long long *const so = out.sp + (uint64_t)sp * (3u * MOS_N_CLASSES);
-    if (lane == 0) mos_add3(so + 3u * MOS_COUNTED, 1ull, steps, span);
+    if (lane == 0) rs_add3(so + 3u * MOS_COUNTED, 1ull, steps, span);
     if (!mos_served(st)) return;
     const uint64_t t0 = rr.x, t1 = (uint64_t)rr.x + rr.y;
     unsigned long long foreign_steps = 0;
     for (uint64_t base = t0 & ~63ull; base < t1; base += 64u) {              // (wave-uniform)
         const uint64_t t = base + (uint64_t)lane;
         const bool in = t >= t0 && t < t1;
-        const unsigned long long m = in ? mos_word(st, g_node_id[t] + node_off, node_haps, mask) : ~0ull;
+        const unsigned long long m = in ? rs_word1(st, g_node_id[t] + node_off, node_haps, mask) : ~0ull;
         foreign_steps += (unsigned long long)__popcll(__builtin_amdgcn_ballot_w64(in && m == 0ull));
     }
     if (foreign_steps) {
-        if (lane == 0) { mos_add3(so + 3u * MOS_FOREIGN, 1ull, steps, span); atomicAdd(out.extra + (uint64_t)sp * 3u + 2u, foreign_steps); }
+        if (lane == 0) { rs_add3(so + 3u * MOS_FOREIGN, 1ull, steps, span); atomicAdd(out.extra + (uint64_t)sp * 3u + 2u, foreign_steps); }
         return;
     }
     const MosSpecies ms = mos[sp];
     unsigned long long run = ~0ull, k = 1;
-    uint32_t run_steps = 0, e_left = MOS_NO_ENTRY, v_prev = 0;
+    uint32_t run_steps = 0, e_left = MEMBER_NO_ENTRY, v_prev = 0;
     bool have_left = false;
     for (uint64_t base = t0 & ~63ull; base < t1; base += 64u) {
         const uint64_t t = base + (uint64_t)lane;
         const bool in = t >= t0 && t < t1;
         const uint32_t v = in ? g_node_id[t] + node_off : 0u;
-        const unsigned long long m = in ? mos_word(st, v, node_haps, mask) : ~0ull;
+        const unsigned long long m = in ? rs_word1(st, v, node_haps, mask) : ~0ull;
         const int lo = base < t0 ? (int)(t0 - base) : 0, hi = t1 - base < 64u ? (int)(t1 - base) : 64;
         for (int l = lo; l < hi; ++l) {                                       // (wave-uniform)
             const unsigned long long ml = lane_get(m, l);
@@ -155,7 +131,7 @@ __device__ __forceinline__ void mos_long_walk(int lane, int l0, const RsLane &L,
         }
     }
     if (lane != 0) return;
-    mos_add3(so + 3u * mosaic_class_of(k), 1ull, steps, span);
+    rs_add3(so + 3u * mosaic_class_of(k), 1ull, steps, span);
     if (k < 2) return;
     const uint32_t e = mos_assigned(run, st, bit_w, bit_entry);
     mos_add_segment(out, e, run_steps);
@@ -178,10 +154,10 @@ __global__ void __launch_bounds__(256) mosaic_kernel(uint32_t n_groups, uint32_t
         const bool served = L.counted && mos_served(L.st);
         const bool cut = served && !L.is_long;                               // a step of a walk that lies inside this group
         const bool decide = L.last && L.counted && !L.is_long;
-        const uint32_t steps = L.rr.y, span = mos_span(L.rr);
+        const uint32_t steps = L.rr.y, span = rs_span(L.rr);
         const int end = cut ? min(L.seg + (int)L.rr.y - 1, 63) : lane;       // my walk's last lane (the layout keeps such a walk inside its group)
-        const unsigned long long walk = lanes_from(L.seg) & lanes_upto(end);
-        const unsigned long long m = cut ? mos_word(L.st, L.v, node_haps, mask) : ~0ull;
+        const unsigned long long walk = rs_lanes(L.seg, end);
+        const unsigned long long m = cut ? rs_word1(L.st, L.v, node_haps, mask) : ~0ull;
         // foreign walks are voted out before the first round
         const unsigned long long fz = __builtin_amdgcn_ballot_w64(cut && m == 0ull) & walk;
         const bool foreign = cut && fz != 0ull, active = cut && !foreign;
@@ -192,7 +168,7 @@ __global__ void __launch_bounds__(256) mosaic_kernel(uint32_t n_groups, uint32_t
             a = seg_and(word, lane, seg);
             const unsigned long long zero = __builtin_amdgcn_ballot_w64(active && a == 0ull);
             if (zero == 0ull) break;
-            const unsigned long long mine = zero & lanes_from(seg) & walk;   // (the lanes of my segment read non-zero below its first zero lane)
+            const unsigned long long mine = zero & rs_lanes(seg, 63) & walk; // (the lanes of my segment read non-zero below its first zero lane)
             if (active && mine) { const int b = __builtin_ctzll(mine); if (lane >= b) seg = b; }
         }
         const bool brk = active && seg != L.seg && lane == seg;              // the first step of a segment that is not the walk's first
@@ -201,10 +177,10 @@ __global__ void __launch_bounds__(256) mosaic_kernel(uint32_t n_groups, uint32_t
         const bool mosaic = active && k >= 2u;
         const bool seg_end = mosaic && (L.last || (lane < 63 && ((brk_b >> (lane + 1)) & 1ull) != 0ull));
         const unsigned long long end_b = __builtin_amdgcn_ballot_w64(seg_end);
-        uint32_t e = MOS_NO_ENTRY;
+        uint32_t e = MEMBER_NO_ENTRY;
         if (seg_end) { e = mos_assigned(a, L.st, bit_w, bit_entry); mos_add_segment(out, e, (uint32_t)(lane - seg) + 1u); }
         if (brk_b) {                                                         // (wave-uniform)
-            const int my_end = brk ? __builtin_ctzll(end_b & lanes_from(lane)) : lane;
+            const int my_end = brk ? __builtin_ctzll(end_b & rs_lanes(lane, 63)) : lane;
             const uint32_t e_left = (uint32_t)__shfl((int)e, (lane + 63) & 63), e_right = (uint32_t)__shfl((int)e, my_end);
             const uint32_t v_left = (uint32_t)__shfl((int)L.v, (lane + 63) & 63);
             unsigned long long base = 0;
@@ -217,23 +193,18 @@ __global__ void __launch_bounds__(256) mosaic_kernel(uint32_t n_groups, uint32_t
             }
         }
         // the classes: counted and compatible per species of the wave, the rare ones per lane
-        unsigned long long rem = __builtin_amdgcn_ballot_w64(decide);
-        while (rem) {
-            const uint32_t s0 = lane_get(L.sr.x, __builtin_ctzll(rem));      // the species of the first deciding lane left
-            const bool mine = decide && L.sr.x == s0;
-            const unsigned long long mb = __builtin_amdgcn_ballot_w64(mine);
-            rem &= ~mb;
+        rs_species_rounds(decide, L.sr.x, [&](uint32_t s0, bool mine, unsigned long long mb) {
             unsigned long long *const so = out.sp + (uint64_t)s0 * (3u * MOS_N_CLASSES);
-            mos_reduce_add(lane, mine, mb, steps, span, so + 3u * MOS_COUNTED);
+            rs_reduce_add(lane, mine, mb, steps, span, so + 3u * MOS_COUNTED);
             const bool comp = mine && active && k == 1u;
             const unsigned long long cb = __builtin_amdgcn_ballot_w64(comp);
-            if (cb) mos_reduce_add(lane, comp, cb, steps, span, so + 3u * MOS_COMPATIBLE);
-        }
+            if (cb) rs_reduce_add(lane, comp, cb, steps, span, so + 3u * MOS_COMPATIBLE);
+        });
         if (decide && (foreign || mosaic)) {
             unsigned long long *const so = out.sp + (uint64_t)L.sr.x * (3u * MOS_N_CLASSES);
             unsigned long long *const ex = out.extra + (uint64_t)L.sr.x * 3u;
-            if (foreign) { mos_add3(so + 3u * MOS_FOREIGN, 1ull, steps, span); atomicAdd(ex + 2, (unsigned long long)__popcll(fz)); }
-            else { mos_add3(so + 3u * mosaic_class_of(k), 1ull, steps, span); atomicAdd(ex, (unsigned long long)k); atomicAdd(ex + 1, (unsigned long long)(k - 1u)); }
+            if (foreign) { rs_add3(so + 3u * MOS_FOREIGN, 1ull, steps, span); atomicAdd(ex + 2, (unsigned long long)__popcll(fz)); }
+            else { rs_add3(so + 3u * mosaic_class_of(k), 1ull, steps, span); atomicAdd(ex, (unsigned long long)k); atomicAdd(ex + 1, (unsigned long long)(k - 1u)); }
         }
         // a walk of more than 64 steps begins in this group (at most one does: it fills the group's remaining lanes): this wave takes all of it
         const unsigned long long long_b = __builtin_amdgcn_ballot_w64(L.live && L.is_long && (uint32_t)((uint64_t)g * 64u + (uint64_t)lane) == L.rr.x);
@@ -251,22 +222,20 @@ int mosaic_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const u
                   uint32_t *junction_out, uint64_t *junction_count_out, uint64_t *n_junctions_out, uint64_t *n_breaks_total_out) {
     const uint32_t S = db->S;
     const uint64_t H = db->H, C = cand_off[S], P = pair_off[S];
-    if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_mosaic: %llu haplotypes + candidates exceed 32-bit positions", (unsigned long long)(H + C));
+    PTX_TRY(rs_check_bits(ctx, "strain_mosaic", H, C));
     std::vector<double> bit_w(H + C + 1, 0.0);
-    std::vector<uint32_t> bit_entry(H + C + 1, MOS_NO_ENTRY);
+    std::vector<uint32_t> bit_entry(H + C + 1, MEMBER_NO_ENTRY);
     RsTable rt;
     rs_table_build(ctx, db, cand_off, cand_hap, rt, [&](uint64_t at, uint64_t c) { bit_w[at] = cand_w[c]; bit_entry[at] = (uint32_t)entry_of[c]; });
     std::vector<MosSpecies> mos(S ? S : 1, MosSpecies{0ull, 0u, 0u});
     for (uint32_t s = 0; s < S; ++s) mos[s] = MosSpecies{pair_off[s], (uint32_t)(cand_off[s + 1] - cand_off[s]), (uint32_t)cand_off[s]};
-    // one device block, zero-filled once: [hap C x 2][species S x 18][extra S x 3][pair P][breaks 1]
-    const size_t n_sp = (size_t)S * 3 * MOS_N_CLASSES, n_out = (size_t)C * 2 + n_sp + (size_t)S * 3 + (size_t)P + 1;
-    DevBuf<unsigned long long> d_out;
+    const size_t n_sp = (size_t)S * 3 * MOS_N_CLASSES;
+    RsCounters cnt;
     DevBuf<uint32_t> d_junction, d_bit_entry;
     DevBuf<RsSpecies> d_tab;
     DevBuf<MosSpecies> d_mos;
     DevBuf<double> d_bit_w;
-    PTX_HIP(ctx, d_out.alloc(n_out));
-    PTX_TRY(zero_fill(ctx, d_out.p, n_out * sizeof(unsigned long long)));
+    PTX_TRY(cnt.init(ctx, (size_t)C * 2 + n_sp + (size_t)S * 3 + (size_t)P + 1));
     const uint64_t rec_cap = std::min<uint64_t>(junction_cap, rd->T_pad);   // (a break is a step of the stream: there are fewer than T_pad)
     if (rec_cap) PTX_HIP(ctx, d_junction.alloc((size_t)rec_cap * 3));
     PTX_TRY(upload(ctx, d_tab, rt.tab.data(), rt.tab.size()));
@@ -274,17 +243,8 @@ int mosaic_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const u
     PTX_TRY(upload(ctx, d_bit_w, bit_w.data(), bit_w.size()));
     PTX_TRY(upload(ctx, d_bit_entry, bit_entry.data(), bit_entry.size()));
     PTX_TRY(rt.wm.build(ctx, db));
-    const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
-    MosOut out;
-    out.hap = d_out.p; out.sp = out.hap + (size_t)C * 2; out.extra = out.sp + n_sp; out.pair = out.extra + (size_t)S * 3; out.n_breaks = out.pair + (size_t)P;
-    out.junction = rec_cap ? d_junction.p : nullptr; out.cap = rec_cap;
-    const unsigned long long *node_haps = rt.by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr;
-    if (n_slots && n_groups) {
-        KTimer tm(ctx, "mosaic_kernel");
-        hipLaunchKernelGGL(mosaic_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->d_g_group_slot.p,
-                           rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p, d_mos.p, node_haps, rt.wm.d_mask.p, d_bit_w.p,
-                           d_bit_entry.p, out);
-    }
+    const MosOut out{cnt.take((size_t)C * 2), cnt.take(n_sp), cnt.take((size_t)S * 3), cnt.take((size_t)P), cnt.take(1), rec_cap ? d_junction.p : nullptr, rec_cap};
+    rs_launch_groups(ctx, rd, "mosaic_kernel", mosaic_kernel, d_tab.p, d_mos.p, rs_node_haps(rt, db), rt.wm.d_mask.p, d_bit_w.p, d_bit_entry.p, out);
     PTX_HIP(ctx, hipGetLastError());
     unsigned long long n_breaks = 0;
     PTX_TRY(download(ctx, &n_breaks, out.n_breaks, 1));

@@ -9,7 +9,7 @@
 //   rarefy_depth_kernel   over the reads: min(depth, 255) as one byte per slot of the locus-grouped copy (d_slot_of) -- the main pass runs in slot order and
 //                         never sees a read index.  5 bytes per read (4 read, 1 written at a scattered place);
 // per pass (rarefy_plan.hpp: the levels [l0, l1) whose arrays of V u64 the device holds at once):
-//   rarefy_bases_kernel   over the locus-grouped stream, a wave per 64-step group as the read passes of read_strain_device.hpp: the per-step aligned length
+//   rarefy_bases_kernel   over the locus-grouped stream, a wave per 64-step group as the read passes of read_pass_device.hpp: the per-step aligned length
 //                         of the coverage pass (coverage_fast_kernel, stage_cov.hip: the first-occurrence codes of d_g_step_dup, the wave's segmented
 //                         prefix of node lengths, d_long_sum / d_long_len0 for walks of more than 64 steps) -- `bases` alone: no bit vector, no trio sums,
 //                         no arena.  A step with aln > 0 adds it to bases[l][v] for l0 <= l < l1, l <= depth(slot): u64 atomics, the same bits in every
@@ -26,12 +26,9 @@
 #include <vector>
 #include "common.hpp"
 #include "boot_front.hpp"
-#include "cov_device.hpp"
-#include "primitives.hpp"
 #include "rarefy_depth.hpp"
 #include "rarefy_plan.hpp"
-#include "read_strain_device.hpp"
-#include "wave.hpp"
+#include "read_pass_device.hpp"
 
 namespace ptx {
 
@@ -69,7 +66,7 @@ __global__ void __launch_bounds__(256) rarefy_bases_kernel(uint32_t n_groups, ui
         if (gs == RS_NO_SLOT) continue;
         const uint64_t t = (uint64_t)g * 64u + (uint64_t)lane;
         const uint32_t code = step_code[t];
-        const uint32_t slot = rs_slot_in_group(gs, code, lane);
+        const uint32_t slot = slot_in_group(gs, code, lane);
         const bool live = code != STEP_PAD && slot < n_slots;
         uint4 rr = make_uint4(0u, 0u, 0u, 0u);
         uint2 sr = make_uint2(0xFFFFFFFFu, 0u);
@@ -104,10 +101,7 @@ __global__ void __launch_bounds__(256) rarefy_bases_kernel(uint32_t n_groups, ui
         if (adds)
             for (uint32_t l = P.lb0; l < P.lb1 && l <= depth; ++l) atomicAdd(&P.bases[(uint64_t)(l - P.lb0) * P.V + v], (unsigned long long)aln);
         // per (level, species): the counted reads (their first steps) and the bases added, species by species of the wave
-        for (unsigned long long rem = __builtin_amdgcn_ballot_w64(counted); rem;) {
-            const uint32_t s0 = lane_get(sr.x, __builtin_ctzll(rem));
-            const bool mine = counted && sr.x == s0;
-            rem &= ~__builtin_amdgcn_ballot_w64(mine);
+        rs_species_rounds(counted, sr.x, [&](uint32_t s0, bool mine, unsigned long long) {
             for (uint32_t l = P.lc0; l < P.lb1; ++l) {                       // (wave-uniform)
                 const bool in = mine && depth >= l;
                 if (__builtin_amdgcn_ballot_w64(in) == 0ull) break;          // nested: nothing at the levels above either
@@ -119,7 +113,7 @@ __global__ void __launch_bounds__(256) rarefy_bases_kernel(uint32_t n_groups, ui
                     if (sum) atomicAdd(o + 1, sum);
                 }
             }
-        }
+        });
     }
 }
 
@@ -161,13 +155,8 @@ struct RfyReads {
     int pass(uint32_t lb0, uint32_t lb1, uint32_t lc0, unsigned long long *bases, unsigned long long *sp) {
         if (!db->V) return 0;
         PTX_TRY(zero_fill(ctx, bases, (size_t)(lb1 - lb0) * db->V * sizeof(unsigned long long)));
-        const uint32_t n_groups = (uint32_t)(rd->T_pad / 64);
-        if (!rd->n_slots || !n_groups) return 0;
         const RfyPass P{lb0, lb1, lc0, db->S, db->V, bases, sp, d_serve.p};
-        KTimer tm(ctx, "rarefy_bases_kernel");
-        hipLaunchKernelGGL(rarefy_bases_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, rd->n_slots, rd->d_g_group_slot.p,
-                           rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, db->d_node_len.p, rd->d_long_sum.p, rd->d_long_len0.p,
-                           d_depth.p, P);
+        rs_launch_groups(ctx, rd, "rarefy_bases_kernel", rarefy_bases_kernel, db->d_node_len.p, rd->d_long_sum.p, rd->d_long_len0.p, d_depth.p, P);
         PTX_HIP(ctx, hipGetLastError());
         return 0;
     }

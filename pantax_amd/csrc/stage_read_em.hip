@@ -5,7 +5,7 @@
 // the per-strain read support (stage_read_support.hip).  A class is a distinct non-zero mask over the candidates of a species of 1 <= K_s <= 64 in ascending
 // haplotype index, with the u64 sums of Q over its reads; the estimate is the fixed f64 iteration of the header over a species' classes in ascending mask.
 //
-// read_class_kernel forms C(r) exactly as read_support_kernel does (read_strain_device.hpp: a wave per 64-step group, a lane per step, the segmented AND
+// read_class_kernel forms C(r) exactly as read_support_kernel does (read_pass_device.hpp: a wave per 64-step group, a lane per step, the segmented AND
 // on the DPP path; the lane of a walk's last step decides); on route 1 the word's haplotype bits are compressed to candidate ranks.  The WAVE reduces before
 // it touches memory: it takes the species of its first deciding lane left (counted: one reduction), then within the species the mask of the first lane
 // left, ballots the lanes that carry the same mask, reduces their Q and lane 0 files ONE class -- core reads share one mask, so the hot class costs one set
@@ -26,10 +26,8 @@
 #include <algorithm>
 #include <cmath>
 #include "common.hpp"
-#include "primitives.hpp"
 #include "read_em_plan.hpp"
-#include "read_strain_device.hpp"
-#include "wave.hpp"
+#include "read_pass_device.hpp"
 
 namespace ptx {
 
@@ -49,11 +47,6 @@ struct RcOut {
     uint32_t *overflow;        // [S]
 };
 
-__device__ __forceinline__ void rc_add3(unsigned long long *__restrict__ dst, unsigned long long n, unsigned long long steps, unsigned long long span) {
-    if (n) atomicAdd(dst, n);
-    if (steps) atomicAdd(dst + 1, steps);
-    if (span) atomicAdd(dst + 2, span);
-}
 // route 1: haplotype bits -> candidate ranks (monotone: the compressed word sorts as the raw one)
 __device__ __forceinline__ unsigned long long rc_rank_bits(unsigned long long m, unsigned long long bits) {
     if ((bits & (bits + 1ull)) == 0ull) return m;   // the chosen haplotypes are 0 .. K-1: rank = index
@@ -70,35 +63,21 @@ __device__ __forceinline__ void rc_file(const RcSpecies &su, uint32_t s0, unsign
         unsigned long long old = __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (a key never changes once set)
         if (old == 0ull) old = atomicCAS(k, 0ull, m0);
         if (old == 0ull || old == m0) {
-            rc_add3(out.cnt + (su.slot_base + i) * 3u, n, steps, span);
+            rs_add3(out.cnt + (su.slot_base + i) * 3u, n, steps, span);
             return;
         }
         i = (i + 1u) & su.slot_mask;
     }
     atomicOr(out.overflow + s0, 1u);
 }
-// sum of Q over the lanes of `on` (its ballot is `b`, not empty); all 64 lanes call it, lane 0 holds the result
-struct RcQ { unsigned long long n, steps, span; };
-__device__ __forceinline__ RcQ rc_reduce(bool on, unsigned long long b, uint32_t steps, uint32_t span) {
-    const auto add = [](unsigned long long x, unsigned long long y) { return x + y; };
-    return RcQ{(unsigned long long)__popcll(b), wave_reduce(on ? (unsigned long long)steps : 0ull, add), wave_reduce(on ? (unsigned long long)span : 0ull, add)};
-}
 // the deciding lanes of the wave -> the counters and the tables, species by species, mask by mask.  All 64 lanes call it.
 __device__ __forceinline__ void rc_wave_reduce(int lane, bool decide, uint32_t sp, unsigned long long m, uint32_t steps, uint32_t span,
                                                const RcSpecies *__restrict__ rc, const RcOut &out) {
-    unsigned long long rem = __builtin_amdgcn_ballot_w64(decide);
-    while (rem) {
-        const uint32_t s0 = lane_get(sp, __builtin_ctzll(rem));              // the species of the first deciding lane left
-        const bool mine = decide && sp == s0;
-        const unsigned long long sb = __builtin_amdgcn_ballot_w64(mine);
-        rem &= ~sb;
+    rs_species_rounds(decide, sp, [&](uint32_t s0, bool mine, unsigned long long sb) {
         const RcSpecies su = rc[s0];
-        if (su.mode == RC_OFF) continue;
-        if (su.mode != RC_RERUN) {
-            const RcQ q = rc_reduce(mine, sb, steps, span);
-            if (lane == 0) rc_add3(out.sp + (uint64_t)s0 * 6u, q.n, q.steps, q.span);   // counted
-        }
-        if (su.mode == RC_COUNT) continue;
+        if (su.mode == RC_OFF) return;
+        if (su.mode != RC_RERUN) rs_reduce_add(lane, mine, sb, steps, span, out.sp + (uint64_t)s0 * 6u);   // counted
+        if (su.mode == RC_COUNT) return;
         unsigned long long left = sb;
         while (left) {
             const unsigned long long m0 = lane_get(m, __builtin_ctzll(left));   // the mask of the first lane left
@@ -106,16 +85,14 @@ __device__ __forceinline__ void rc_wave_reduce(int lane, bool decide, uint32_t s
             const unsigned long long cb = __builtin_amdgcn_ballot_w64(same);
             left &= ~cb;
             if (m0 == 0ull && su.mode == RC_RERUN) continue;                 // (unexplained was counted by the first pass)
-            const RcQ q = rc_reduce(same, cb, steps, span);
+            const RsQ q = rs_reduce(same, cb, steps, span);
             if (lane == 0) {
-                if (m0 == 0ull) rc_add3(out.sp + (uint64_t)s0 * 6u + 3u, q.n, q.steps, q.span);
+                if (m0 == 0ull) rs_add3(out.sp + (uint64_t)s0 * 6u + 3u, q.n, q.steps, q.span);
                 else rc_file(su, s0, m0, q.n, q.steps, q.span, out);
             }
         }
-    }
+    });
 }
-
-__device__ __forceinline__ uint32_t rc_span(const uint4 &rr) { return rr.w >= rr.z ? rr.w - rr.z : 0u; }
 
 // every species of the table has at most one mask word (a species of more than 64 candidates is in it without candidates)
 __global__ void __launch_bounds__(256) read_class_kernel(uint32_t n_groups, uint32_t n_slots, const uint32_t *__restrict__ group_slot,
@@ -136,7 +113,7 @@ __global__ void __launch_bounds__(256) read_class_kernel(uint32_t n_groups, uint
             if (L.is_long) rs_long_partial(long_acc, 1u, L.slot, 0u, w);
             else if (L.last) cm = L.st.m.route == 1u ? rc_rank_bits(w, L.st.m.bits) : w;
         }
-        rc_wave_reduce(lane, decide, L.sr.x, cm, L.rr.y, rc_span(L.rr), rc, out);
+        rc_wave_reduce(lane, decide, L.sr.x, cm, L.rr.y, rs_span(L.rr), rc, out);
     }
 }
 
@@ -146,18 +123,13 @@ __global__ void __launch_bounds__(256) read_class_long_kernel(uint32_t n_slots, 
                                                               const unsigned long long *__restrict__ long_acc, RcOut out) {
     const int lane = threadIdx.x & 63;
     for (uint64_t base = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64u; base < n_slots; base += (uint64_t)gridDim.x * 256u) {   // (wave-uniform)
-        const uint64_t s = base + (uint64_t)lane;
-        const bool in = s < n_slots;
-        uint4 rr = make_uint4(0u, 0u, 0u, 0u);
-        uint32_t sp = 0xFFFFFFFFu;
-        if (in) { rr = read_rec[s]; sp = slot_rec[s].x; }
-        const bool decide = in && rr.y > 64u && (int32_t)sp >= 0;
+        const RsLongSlot t = rs_long_slot(base, lane, n_slots, read_rec, slot_rec);
         unsigned long long cm = 0ull;
-        if (decide) {
-            const RsSpecies st = tab[sp];
-            if (st.m.route) cm = st.m.route == 1u ? rc_rank_bits(long_acc[s], st.m.bits) : long_acc[s];
+        if (t.decide) {
+            const RsSpecies st = tab[t.sp];
+            if (st.m.route) cm = st.m.route == 1u ? rc_rank_bits(long_acc[t.s], st.m.bits) : long_acc[t.s];
         }
-        rc_wave_reduce(lane, decide, sp, cm, rr.y, rc_span(rr), rc, out);
+        rc_wave_reduce(lane, t.decide, t.sp, cm, t.rr.y, rs_span(t.rr), rc, out);
     }
 }
 
@@ -266,7 +238,7 @@ int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const 
                    int32_t *converged_out, double *delta_out) {
     const uint32_t S = db->S;
     const uint64_t H = db->H, C = cand_off[S];
-    if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_read_em: %llu haplotypes + candidates exceed 32-bit positions", (unsigned long long)(H + C));
+    PTX_TRY(rs_check_bits(ctx, "strain_read_em", H, C));
     // the table of the pass: a skipped species (K_s > 64) is in it without candidates -- it is counted, and no mask of it is formed
     std::vector<uint64_t> t_off(S + 1, 0);
     std::vector<uint32_t> t_hap;
@@ -285,10 +257,9 @@ int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const 
     rs_table_build(ctx, db, t_off.data(), t_hap.data(), rt, [](uint64_t, uint64_t) {});
     std::vector<unsigned long long> h_sp((size_t)(S ? S : 1) * 6, 0ull);
     std::vector<std::vector<RcClass>> cls(S);
-    const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
-    const bool any_long = rd->n_long != 0;
     if (S) {
-        DevBuf<unsigned long long> d_sp, d_long, d_tabs, d_dmask, d_dq;
+        DevBuf<unsigned long long> d_sp, d_tabs, d_dmask, d_dq;
+        RsLongAcc lng;
         DevBuf<RsSpecies> d_tab;
         DevBuf<RcSpecies> d_rc;
         DevBuf<uint32_t> d_over, d_rank, d_tmp, d_tot, d_dslot;
@@ -299,9 +270,7 @@ int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const 
         PTX_HIP(ctx, d_tot.alloc(1));
         PTX_TRY(upload(ctx, d_tab, rt.tab.data(), rt.tab.size()));
         PTX_TRY(rt.wm.build(ctx, db));
-        PTX_HIP(ctx, d_long.alloc(any_long ? (size_t)n_slots : 1));
-        if (any_long) PTX_HIP(ctx, hipMemsetAsync(d_long.p, 0xFF, (size_t)n_slots * sizeof(unsigned long long), ctx->stream));   // (a rerun ANDs the same partials in again)
-        const unsigned long long *node_haps = rt.by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr;
+        PTX_TRY(lng.init(ctx, rd, 1u));   // (a rerun ANDs the same partials in again)
         std::vector<RcSpecies> rc(S);
         std::vector<uint64_t> slot_off(S + 1, 0);
         std::vector<uint32_t> h_over(S, 0), h_dslot;
@@ -323,16 +292,8 @@ int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const 
             PTX_TRY(zero_fill(ctx, d_over.p, (size_t)S * sizeof(uint32_t)));
             PTX_TRY(upload(ctx, d_rc, rc.data(), rc.size()));
             const RcOut out{d_tabs.p, d_tabs.p + (total ? total : 1), d_sp.p, d_over.p};
-            if (n_slots && n_groups) {
-                KTimer tm(ctx, "read_class_kernel");
-                hipLaunchKernelGGL(read_class_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->d_g_group_slot.p,
-                                   rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p, d_rc.p, node_haps, rt.wm.d_mask.p, d_long.p, out);
-            }
-            if (n_slots && any_long) {
-                KTimer tm(ctx, "read_class_long_kernel");
-                hipLaunchKernelGGL(read_class_long_kernel, dim3(grid_for(((uint64_t)n_slots + 63) / 64, 4, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, n_slots,
-                                   rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p, d_rc.p, d_long.p, out);
-            }
+            rs_launch_groups(ctx, rd, "read_class_kernel", read_class_kernel, d_tab.p, d_rc.p, rs_node_haps(rt, db), rt.wm.d_mask.p, lng.d_acc.p, out);
+            rs_launch_slots(ctx, rd, "read_class_long_kernel", read_class_long_kernel, d_tab.p, d_rc.p, lng.d_acc.p, out);
             PTX_HIP(ctx, hipGetLastError());
             uint32_t n_dense = 0;
             if (total) {

@@ -22,8 +22,7 @@
 #include <algorithm>
 #include <cmath>
 #include "common.hpp"
-#include "primitives.hpp"
-#include "read_strain_device.hpp"
+#include "read_pass_device.hpp"
 #include "wave.hpp"
 
 namespace ptx {
@@ -119,7 +118,7 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
                         int32_t *n_out, double *post_out) {
     const uint32_t S = db->S;
     const uint64_t H = db->H, C = cand_off[S];
-    if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "read_strains: %llu haplotypes + candidates exceed 32-bit positions", (unsigned long long)(H + C));
+    PTX_TRY(rs_check_bits(ctx, "read_strains", H, C));
     std::vector<double> bit_w(H + C + 1, 0.0);
     std::vector<uint32_t> bit_hap(H + C + 1, 0u);
     RsTable rt;
@@ -127,29 +126,17 @@ int read_strains_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
     DevBuf<RsSpecies> d_tab;
     DevBuf<double> d_bit_w;
     DevBuf<uint32_t> d_bit_hap;
-    DevBuf<unsigned long long> d_long;
     DevBuf<RsResult> d_res;
+    RsLongAcc lng;
     PTX_TRY(upload(ctx, d_tab, rt.tab.data(), rt.tab.size()));
     PTX_TRY(upload(ctx, d_bit_w, bit_w.data(), bit_w.size()));
     PTX_TRY(upload(ctx, d_bit_hap, bit_hap.data(), bit_hap.size()));
     PTX_TRY(rt.wm.build(ctx, db));
-    const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
-    PTX_HIP(ctx, d_res.alloc(n_slots ? n_slots : 1));
-    const bool any_long = rd->n_long != 0;
-    PTX_HIP(ctx, d_long.alloc(any_long ? (size_t)n_slots * rt.long_nw : 1));
-    if (any_long) PTX_HIP(ctx, hipMemsetAsync(d_long.p, 0xFF, (size_t)n_slots * rt.long_nw * sizeof(unsigned long long), ctx->stream));
-    if (n_slots && n_groups) {
-        KTimer tm(ctx, "read_strain_kernel");
-        hipLaunchKernelGGL(read_strain_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->d_g_group_slot.p,
-                           rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p,
-                           rt.by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr, rt.wm.d_mask.p, d_bit_w.p, d_bit_hap.p,
-                           d_long.p, rt.long_nw, d_res.p);
-    }
-    if (n_slots && any_long) {
-        KTimer tm(ctx, "read_strain_long_kernel");
-        hipLaunchKernelGGL(read_strain_long_kernel, dim3(grid_for(n_slots, 256, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, n_slots, rd->d_g_read_rec.p,
-                           rd->d_g_slot_rec.p, d_tab.p, d_long.p, rt.long_nw, d_bit_w.p, d_bit_hap.p, d_res.p);
-    }
+    PTX_HIP(ctx, d_res.alloc(rd->n_slots ? rd->n_slots : 1));
+    PTX_TRY(lng.init(ctx, rd, rt.long_nw));
+    rs_launch_groups(ctx, rd, "read_strain_kernel", read_strain_kernel, d_tab.p, rs_node_haps(rt, db), rt.wm.d_mask.p, d_bit_w.p, d_bit_hap.p, lng.d_acc.p, rt.long_nw,
+                     d_res.p);
+    rs_launch_slots(ctx, rd, "read_strain_long_kernel", read_strain_long_kernel, d_tab.p, lng.d_acc.p, rt.long_nw, d_bit_w.p, d_bit_hap.p, d_res.p);
     const uint64_t R = rd->R;
     if (R) {
         // the caller's arrays travel up first: entries of reads outside this db's species keep what the caller put there

@@ -7,9 +7,9 @@
 // (counted), over |C(r)| = 0 (unexplained), >= 2 (ambiguous), = K_s (uninformative); per pair of candidates of a species of K_s <= 64 the number of reads
 // with both in C(r).  Integers only: no order matters.
 //
-// read_support_kernel forms C(r) exactly as read_strain_kernel does (read_strain_device.hpp: a wave per 64-step group, a lane per step, the segmented AND on
+// read_support_kernel forms C(r) exactly as read_strain_kernel does (read_pass_device.hpp: a wave per 64-step group, a lane per step, the segmented AND on
 // the DPP path; the lane of a walk's last step decides), but writes nothing per read: the WAVE reduces.  It takes the species of its first deciding lane
-// and handles the deciding lanes of that species, then the next species, until none is left (the stream is grouped by locus: one or two rounds).  Per round:
+// and handles the deciding lanes of that species, then the next species, until none is left (rs_species_rounds: one or two rounds).  Per round:
 //   species sums    n_reads = popcount of a ballot, n_steps and span one DPP wave reduction each; a class no lane falls in is skipped after its ballot;
 //   candidate sums  per candidate bit of the species one ballot over the lanes that carry it (none: skipped), then the same for unique and assigned.  Not a
 //                   lane per set bit: the lanes of a round share a species and core reads set the same bits, so 64 lanes would queue on K_s counters;
@@ -25,15 +25,11 @@
 #include <algorithm>
 #include <cmath>
 #include "common.hpp"
-#include "primitives.hpp"
-#include "read_strain_device.hpp"
-#include "wave.hpp"
+#include "read_pass_device.hpp"
 
 namespace ptx {
 
 namespace {
-
-constexpr uint32_t SUP_NO_ENTRY = 0xFFFFFFFFu;
 
 struct SupSpecies {
     uint64_t pair_base;   // first entry of the species' K x K block in the pair counts (own_pair)
@@ -56,11 +52,6 @@ struct SupRead {
     double best;
 };
 
-__device__ __forceinline__ void sup_add3(unsigned long long *__restrict__ dst, unsigned long long n, unsigned long long steps, unsigned long long span) {
-    if (n) atomicAdd(dst, n);
-    if (steps) atomicAdd(dst + 1, steps);
-    if (span) atomicAdd(dst + 2, span);
-}
 // one mask word of C(r), ascending: count, argmax of the weight (the first of equal weights: the smallest haplotype index; a set whose weights are all
 // NaN or -inf keeps its lowest bit).  plain: a species of several words -- the lane files the read under every candidate it is compatible with itself.
 __device__ __forceinline__ void sup_take(unsigned long long m, uint32_t w, const RsSpecies &st, bool plain, const double *__restrict__ bit_w,
@@ -76,7 +67,7 @@ __device__ __forceinline__ void sup_take(unsigned long long m, uint32_t w, const
         if (x > r.best) { r.best = x; r.besti = idx; }
         if (plain) {
             const uint32_t e = bit_entry[st.bit_base + idx];
-            if (e != SUP_NO_ENTRY) sup_add3(hap_out + (uint64_t)e * 9u, 1ull, steps, span);
+            if (e != MEMBER_NO_ENTRY) rs_add3(hap_out + (uint64_t)e * 9u, 1ull, steps, span);
         }
     }
 }
@@ -86,43 +77,30 @@ __device__ __forceinline__ void sup_plain_finish(const RsSpecies &st, const uint
     if (r.n == 0u) return;
     if (r.n == 1u) {
         const uint32_t e = bit_entry[st.bit_base + r.first];
-        if (e != SUP_NO_ENTRY) sup_add3(hap_out + (uint64_t)e * 9u + 3u, 1ull, steps, span);
+        if (e != MEMBER_NO_ENTRY) rs_add3(hap_out + (uint64_t)e * 9u + 3u, 1ull, steps, span);
     }
     const uint32_t e = bit_entry[st.bit_base + r.besti];
-    if (e != SUP_NO_ENTRY) sup_add3(hap_out + (uint64_t)e * 9u + 6u, 1ull, steps, span);
-}
-
-// sum of Q over the lanes of `on` (its ballot is `b`, not empty) -> dst; all 64 lanes call it
-__device__ __forceinline__ void sup_reduce_add(int lane, bool on, unsigned long long b, uint32_t steps, uint32_t span, unsigned long long *__restrict__ dst) {
-    const auto add = [](unsigned long long x, unsigned long long y) { return x + y; };
-    const unsigned long long qs = wave_reduce(on ? (unsigned long long)steps : 0ull, add);
-    const unsigned long long qp = wave_reduce(on ? (unsigned long long)span : 0ull, add);
-    if (lane == 0) sup_add3(dst, (unsigned long long)__popcll(b), qs, qp);
+    if (e != MEMBER_NO_ENTRY) rs_add3(hap_out + (uint64_t)e * 9u + 6u, 1ull, steps, span);
 }
 
 // the deciding lanes of the wave -> the counters, species by species.  All 64 lanes call it with everything but the per-lane values uniform.
 __device__ __forceinline__ void sup_wave_reduce(int lane, bool decide, uint32_t sp, const SupRead &r, uint32_t steps, uint32_t span,
                                                 const RsSpecies *__restrict__ tab, const SupSpecies *__restrict__ sup, const uint32_t *__restrict__ bit_entry,
                                                 const SupOut &out) {
-    unsigned long long rem = __builtin_amdgcn_ballot_w64(decide);
-    while (rem) {
-        const uint32_t s0 = lane_get(sp, __builtin_ctzll(rem));              // the species of the first deciding lane left
-        const bool mine = decide && sp == s0;
-        const unsigned long long mb = __builtin_amdgcn_ballot_w64(mine);
-        rem &= ~mb;
+    rs_species_rounds(decide, sp, [&](uint32_t s0, bool mine, unsigned long long mb) {
         const RsSpecies st = tab[s0];
         const SupSpecies su = sup[s0];
         unsigned long long *const so = out.sp + (uint64_t)s0 * 12u;
-        sup_reduce_add(lane, mine, mb, steps, span, so);                     // counted
-        if (st.m.route == 0u) continue;
+        rs_reduce_add(lane, mine, mb, steps, span, so);                      // counted
+        if (st.m.route == 0u) return;
         {
             const bool un = mine && r.n == 0u, am = mine && r.n >= 2u, ui = mine && r.n == su.K;
             const unsigned long long b_un = __builtin_amdgcn_ballot_w64(un), b_am = __builtin_amdgcn_ballot_w64(am), b_ui = __builtin_amdgcn_ballot_w64(ui);
-            if (b_un) sup_reduce_add(lane, un, b_un, steps, span, so + 3);
-            if (b_am) sup_reduce_add(lane, am, b_am, steps, span, so + 6);
-            if (b_ui) sup_reduce_add(lane, ui, b_ui, steps, span, so + 9);
+            if (b_un) rs_reduce_add(lane, un, b_un, steps, span, so + 3);
+            if (b_am) rs_reduce_add(lane, am, b_am, steps, span, so + 6);
+            if (b_ui) rs_reduce_add(lane, ui, b_ui, steps, span, so + 9);
         }
-        if (st.m.nw > 1u) continue;                                            // plain path: the lanes have filed their candidates themselves
+        if (st.m.nw > 1u) return;                                              // plain path: the lanes have filed their candidates themselves
         const unsigned long long bits = st.m.route == 1u ? st.m.bits : (su.K >= 64u ? ~0ull : (1ull << su.K) - 1ull);
         const unsigned long long mm = mine ? r.m0 : 0ull;
         unsigned long long present = 0ull;
@@ -132,20 +110,20 @@ __device__ __forceinline__ void sup_wave_reduce(int lane, bool decide, uint32_t 
             const unsigned long long cb = __builtin_amdgcn_ballot_w64(has);
             if (cb == 0ull) continue;                                        // no read of the round is compatible with this candidate
             const uint32_t e = bit_entry[st.bit_base + (uint32_t)b];
-            if (e == SUP_NO_ENTRY) continue;
+            if (e == MEMBER_NO_ENTRY) continue;
             present |= 1ull << b;
             unsigned long long *const ho = out.hap + (uint64_t)e * 9u;
-            sup_reduce_add(lane, has, cb, steps, span, ho);
+            rs_reduce_add(lane, has, cb, steps, span, ho);
             const bool uq = has && r.n == 1u, as = has && r.besti == (uint32_t)b;
             const unsigned long long b_uq = __builtin_amdgcn_ballot_w64(uq), b_as = __builtin_amdgcn_ballot_w64(as);
-            if (b_uq) sup_reduce_add(lane, uq, b_uq, steps, span, ho + 3);
-            if (b_as) sup_reduce_add(lane, as, b_as, steps, span, ho + 6);
+            if (b_uq) rs_reduce_add(lane, uq, b_uq, steps, span, ho + 3);
+            if (b_as) rs_reduce_add(lane, as, b_as, steps, span, ho + 6);
             if (su.own_pair && lane == 0) {
                 const uint64_t pa = e - su.ent0;
                 atomicAdd(out.pair + su.pair_base + pa * su.K + pa, (unsigned long long)__popcll(cb));
             }
         }
-        if (!su.own_pair) continue;
+        if (!su.own_pair) return;
         for (unsigned long long qa = present; qa; qa &= qa - 1ull) {
             const int a = __builtin_ctzll(qa);
             for (unsigned long long qb = qa & (qa - 1ull); qb; qb &= qb - 1ull) {
@@ -157,10 +135,8 @@ __device__ __forceinline__ void sup_wave_reduce(int lane, bool decide, uint32_t 
                 }
             }
         }
-    }
+    });
 }
-
-__device__ __forceinline__ uint32_t sup_span(const uint4 &rr) { return rr.w >= rr.z ? rr.w - rr.z : 0u; }
 
 __global__ void __launch_bounds__(256) read_support_kernel(uint32_t n_groups, uint32_t n_slots, const uint32_t *__restrict__ group_slot,
                                                            const uint8_t *__restrict__ step_code, const uint32_t *__restrict__ g_node_id,
@@ -176,7 +152,7 @@ __global__ void __launch_bounds__(256) read_support_kernel(uint32_t n_groups, ui
         const RsLane L = rs_lane(g, gs, lane, n_slots, step_code, g_node_id, read_rec, slot_rec, tab);
         const uint32_t nw_max = wave_reduce(L.nw, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
         const bool decide = L.last && L.counted && !L.is_long;
-        const uint32_t steps = L.rr.y, span = sup_span(L.rr);
+        const uint32_t steps = L.rr.y, span = rs_span(L.rr);
         SupRead r{0ull, 0u, 0u, 0u, -INFINITY};
         for (uint32_t w = 0; w < nw_max; ++w) {                              // (wave-uniform trip count: seg_and wants every lane)
             const unsigned long long m = rs_lane_word(L, w, lane, node_haps, mask);
@@ -197,20 +173,15 @@ __global__ void __launch_bounds__(256) read_support_long_kernel(uint32_t n_slots
                                                                 const double *__restrict__ bit_w, const uint32_t *__restrict__ bit_entry, SupOut out) {
     const int lane = threadIdx.x & 63;
     for (uint64_t base = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64u; base < n_slots; base += (uint64_t)gridDim.x * 256u) {   // (wave-uniform)
-        const uint64_t s = base + (uint64_t)lane;
-        const bool in = s < n_slots;
-        uint4 rr = make_uint4(0u, 0u, 0u, 0u);
-        uint32_t sp = 0xFFFFFFFFu;
-        if (in) { rr = read_rec[s]; sp = slot_rec[s].x; }
-        const bool decide = in && rr.y > 64u && (int32_t)sp >= 0;
+        const RsLongSlot t = rs_long_slot(base, lane, n_slots, read_rec, slot_rec);
         RsSpecies st{};
-        if (decide) st = tab[sp];
+        if (t.decide) st = tab[t.sp];
         const uint32_t nw = st.m.route ? st.m.nw : 0u;
-        const uint32_t steps = rr.y, span = sup_span(rr);
+        const uint32_t steps = t.rr.y, span = rs_span(t.rr);
         SupRead r{0ull, 0u, 0u, 0u, -INFINITY};
-        for (uint32_t w = 0; w < nw; ++w) sup_take(long_acc[s * long_nw + w], w, st, nw > 1u, bit_w, bit_entry, out.hap, steps, span, r);
-        if (decide && nw > 1u) sup_plain_finish(st, bit_entry, out.hap, steps, span, r);
-        sup_wave_reduce(lane, decide, sp, r, steps, span, tab, sup, bit_entry, out);
+        for (uint32_t w = 0; w < nw; ++w) sup_take(long_acc[t.s * long_nw + w], w, st, nw > 1u, bit_w, bit_entry, out.hap, steps, span, r);
+        if (t.decide && nw > 1u) sup_plain_finish(st, bit_entry, out.hap, steps, span, r);
+        sup_wave_reduce(lane, t.decide, t.sp, r, steps, span, tab, sup, bit_entry, out);
     }
 }
 
@@ -222,9 +193,9 @@ int read_support_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
                         const uint64_t *pair_off, uint64_t *hap_out, uint64_t *species_out, uint64_t *pair_out) {
     const uint32_t S = db->S;
     const uint64_t H = db->H, C = cand_off[S], P = pair_off[S];
-    if (H + C >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_read_support: %llu haplotypes + candidates exceed 32-bit positions", (unsigned long long)(H + C));
+    PTX_TRY(rs_check_bits(ctx, "strain_read_support", H, C));
     std::vector<double> bit_w(H + C + 1, 0.0);
-    std::vector<uint32_t> bit_entry(H + C + 1, SUP_NO_ENTRY);
+    std::vector<uint32_t> bit_entry(H + C + 1, MEMBER_NO_ENTRY);
     RsTable rt;
     rs_table_build(ctx, db, cand_off, cand_hap, rt, [&](uint64_t at, uint64_t c) { bit_w[at] = cand_w[c]; bit_entry[at] = (uint32_t)entry_of[c]; });
     std::vector<SupSpecies> sup(S ? S : 1, SupSpecies{0ull, 0u, 0u, 0u, 0u});
@@ -234,39 +205,26 @@ int read_support_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, c
     }
     const size_t n_out = (size_t)C * 9 + (size_t)S * 12 + (size_t)P;
     if (n_out == 0) return 0;
-    // one device block, zero-filled once: [hap C x 9][species S x 12][pair P]
-    DevBuf<unsigned long long> d_out, d_long;
+    RsCounters cnt;
+    RsLongAcc lng;
     DevBuf<RsSpecies> d_tab;
     DevBuf<SupSpecies> d_sup;
     DevBuf<double> d_bit_w;
     DevBuf<uint32_t> d_bit_entry;
-    PTX_HIP(ctx, d_out.alloc(n_out));
-    PTX_TRY(zero_fill(ctx, d_out.p, n_out * sizeof(unsigned long long)));
+    PTX_TRY(cnt.init(ctx, n_out));
+    const SupOut out{cnt.take((size_t)C * 9), cnt.take((size_t)S * 12), cnt.take((size_t)P)};
     PTX_TRY(upload(ctx, d_tab, rt.tab.data(), rt.tab.size()));
     PTX_TRY(upload(ctx, d_sup, sup.data(), sup.size()));
     PTX_TRY(upload(ctx, d_bit_w, bit_w.data(), bit_w.size()));
     PTX_TRY(upload(ctx, d_bit_entry, bit_entry.data(), bit_entry.size()));
     PTX_TRY(rt.wm.build(ctx, db));
-    const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
-    const bool any_long = rd->n_long != 0;
-    PTX_HIP(ctx, d_long.alloc(any_long ? (size_t)n_slots * rt.long_nw : 1));
-    if (any_long) PTX_HIP(ctx, hipMemsetAsync(d_long.p, 0xFF, (size_t)n_slots * rt.long_nw * sizeof(unsigned long long), ctx->stream));
-    const SupOut out{d_out.p, d_out.p + (size_t)C * 9, d_out.p + (size_t)C * 9 + (size_t)S * 12};
-    const unsigned long long *node_haps = rt.by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr;
-    if (n_slots && n_groups) {
-        KTimer tm(ctx, "read_support_kernel");
-        hipLaunchKernelGGL(read_support_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->d_g_group_slot.p,
-                           rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p, d_sup.p, node_haps, rt.wm.d_mask.p, d_bit_w.p,
-                           d_bit_entry.p, d_long.p, rt.long_nw, out);
-    }
-    if (n_slots && any_long) {
-        KTimer tm(ctx, "read_support_long_kernel");
-        hipLaunchKernelGGL(read_support_long_kernel, dim3(grid_for(((uint64_t)n_slots + 63) / 64, 4, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, n_slots,
-                           rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p, d_sup.p, d_long.p, rt.long_nw, d_bit_w.p, d_bit_entry.p, out);
-    }
+    PTX_TRY(lng.init(ctx, rd, rt.long_nw));
+    rs_launch_groups(ctx, rd, "read_support_kernel", read_support_kernel, d_tab.p, d_sup.p, rs_node_haps(rt, db), rt.wm.d_mask.p, d_bit_w.p, d_bit_entry.p,
+                     lng.d_acc.p, rt.long_nw, out);
+    rs_launch_slots(ctx, rd, "read_support_long_kernel", read_support_long_kernel, d_tab.p, d_sup.p, lng.d_acc.p, rt.long_nw, d_bit_w.p, d_bit_entry.p, out);
     PTX_HIP(ctx, hipGetLastError());
     std::vector<unsigned long long> h_pair(P ? P : 1);
-    if (C) PTX_TRY(download(ctx, (unsigned long long *)hap_out, d_out.p, (size_t)C * 9));
+    if (C) PTX_TRY(download(ctx, (unsigned long long *)hap_out, out.hap, (size_t)C * 9));
     if (S) PTX_TRY(download(ctx, (unsigned long long *)species_out, out.sp, (size_t)S * 12));
     if (P) PTX_TRY(download(ctx, h_pair.data(), out.pair, (size_t)P));
     PTX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // host arrays are filled, the temporaries are released on return

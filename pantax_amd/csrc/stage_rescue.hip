@@ -6,14 +6,14 @@
 // LIST Sel ++ Cand (member_plan.hpp), so a node has ONE u64 on either route -- bit = haplotype index (route 1) or position in the list (route 2) -- and
 // the species carries the two masks sel_bits and cand_bits that split it.  Integers only: no order matters.
 //
-// rescue_kernel walks the locus-grouped step stream as the other read passes do (read_strain_device.hpp: a wave per 64-step group, a lane per step):
+// rescue_kernel walks the locus-grouped step stream as the other read passes do (read_pass_device.hpp: a wave per 64-step group, a lane per step):
 //   the word    one seg_and of the step words gives C(r) = a & sel_bits and D(r) = a & cand_bits at the lane of the walk's last step;
 //   foreign     one ballot of the lanes with word & sel_bits = 0, novel one of word & (sel_bits | cand_bits) = 0; a deciding lane ANDs each with the
 //               lanes [first lane of its walk, its own];
 //   steps       foreign_steps, claimed_steps, novel_steps and the candidates' steps are sums over steps, walks of any length alike: per species of the
 //               wave's foreign lanes one ballot and popcount each, the candidates through one ballot per candidate bit present on those lanes;
 //   counters    counted and compatible take nearly every read: per species of the wave one ballot, two DPP reductions and one 64-bit atomicAdd per
-//               non-zero sum from lane 0, as in read_support_kernel.  The rare classes add per lane.  The per-candidate sums go through one ballot per
+//               non-zero sum from lane 0 (rs_species_rounds, rs_reduce_add).  The rare classes add per lane.  The per-candidate sums go through one ballot per
 //               candidate bit present in the D(r) of the species' rescued lanes.
 // A walk of more than 64 steps ANDs its per-group partial into its slot's word (rs_long_partial, one word a slot) and ORs its two flags -- a step with
 // M empty, a step with M and N empty -- into a per-slot u32; both arrays exist only when the reads hold such walks.  rescue_long_kernel takes a lane per
@@ -23,10 +23,8 @@
 // words) + 16R' (read records) + 8R' (slot records); out: 80 J + 240 S bytes of counters.  Nothing R-sized is allocated but the long-walk partials.
 #include <algorithm>
 #include "common.hpp"
-#include "primitives.hpp"
-#include "read_strain_device.hpp"
+#include "read_pass_device.hpp"
 #include "rescue_plan.hpp"
-#include "wave.hpp"
 
 namespace ptx {
 
@@ -47,29 +45,8 @@ struct ResOut {
     unsigned long long *step;         // [S][3]     foreign_steps, claimed_steps, novel_steps
 };
 
-__device__ __forceinline__ unsigned long long res_lanes(int a, int b) { return (~0ull << a) & (~0ull >> (63 - b)); }   // lanes a .. b
-
-__device__ __forceinline__ void res_add3(unsigned long long *__restrict__ dst, unsigned long long n, unsigned long long steps, unsigned long long span) {
-    if (n) atomicAdd(dst, n);
-    if (steps) atomicAdd(dst + 1, steps);
-    if (span) atomicAdd(dst + 2, span);
-}
-// sum of Q over the lanes of `on` (its ballot is `b`, not empty) -> dst; all 64 lanes call it
-__device__ __forceinline__ void res_reduce_add(int lane, bool on, unsigned long long b, uint32_t steps, uint32_t span, unsigned long long *__restrict__ dst) {
-    const auto add = [](unsigned long long x, unsigned long long y) { return x + y; };
-    const unsigned long long qs = wave_reduce(on ? (unsigned long long)steps : 0ull, add);
-    const unsigned long long qp = wave_reduce(on ? (unsigned long long)span : 0ull, add);
-    if (lane == 0) res_add3(dst, (unsigned long long)__popcll(b), qs, qp);
-}
 __device__ __forceinline__ unsigned long long res_wave_or(unsigned long long x) {
     return wave_reduce(x, [](unsigned long long p, unsigned long long q) { return p | q; });
-}
-__device__ __forceinline__ uint32_t res_span(const uint4 &rr) { return rr.w >= rr.z ? rr.w - rr.z : 0u; }
-// the word of global node v over the species' list (an open species: at most one word; an empty list: nobody walks anything)
-__device__ __forceinline__ unsigned long long res_word(const RsSpecies &st, uint32_t v, const unsigned long long *__restrict__ node_haps,
-                                                       const unsigned long long *__restrict__ mask) {
-    if (st.m.route == 0u) return 0ull;
-    return st.m.route == 1u ? (node_haps[v] & st.m.bits) : mask[member_mask_row(st.m, v)];
 }
 
 // The deciding lanes of the wave -> the counters, species by species: a = the AND of the read's step words, has_f / has_n = the read has a step with M
@@ -81,20 +58,15 @@ __device__ __forceinline__ void res_wave_classes(int lane, bool decide, uint32_t
     const unsigned long long c = a & rs.sel_bits, d = a & rs.cand_bits;
     const bool compatible = open && c != 0ull, foreign = open && has_f, mosaic = open && !has_f && c == 0ull;
     const bool rescued = (foreign || mosaic) && d != 0ull;
-    unsigned long long rem = __builtin_amdgcn_ballot_w64(decide);
-    while (rem) {
-        const uint32_t s0 = lane_get(sp, __builtin_ctzll(rem));              // the species of the first deciding lane left
-        const bool mine = decide && sp == s0;
-        const unsigned long long mb = __builtin_amdgcn_ballot_w64(mine);
-        rem &= ~mb;
+    rs_species_rounds(decide, sp, [&](uint32_t s0, bool mine, unsigned long long mb) {
         unsigned long long *const so = out.sp + (uint64_t)s0 * (3u * RES_N_CLASSES);
-        res_reduce_add(lane, mine, mb, steps, span, so + 3u * RES_COUNTED);
+        rs_reduce_add(lane, mine, mb, steps, span, so + 3u * RES_COUNTED);
         const bool comp = mine && compatible;
         const unsigned long long cb = __builtin_amdgcn_ballot_w64(comp);
-        if (cb) res_reduce_add(lane, comp, cb, steps, span, so + 3u * RES_COMPATIBLE);
+        if (cb) rs_reduce_add(lane, comp, cb, steps, span, so + 3u * RES_COMPATIBLE);
         // the candidates of the species' rescued lanes: one round per candidate bit present
         const unsigned long long dm = (mine && rescued) ? d : 0ull;
-        if (__builtin_amdgcn_ballot_w64(dm != 0ull) == 0ull) continue;
+        if (__builtin_amdgcn_ballot_w64(dm != 0ull) == 0ull) return;
         const uint32_t bit_base = tab[s0].bit_base;
         for (unsigned long long q = res_wave_or(dm); q; q &= q - 1ull) {
             const int b = __builtin_ctzll(q);
@@ -103,23 +75,23 @@ __device__ __forceinline__ void res_wave_classes(int lane, bool decide, uint32_t
             const uint32_t e = bit_entry[bit_base + (uint32_t)b];
             if (e == MEMBER_NO_ENTRY) continue;
             unsigned long long *const co = out.cand + (uint64_t)e * (3u * RES_N_CAND);
-            res_reduce_add(lane, has, hb, steps, span, co + 3u * RES_RESCUED);
+            rs_reduce_add(lane, has, hb, steps, span, co + 3u * RES_RESCUED);
             const bool al = has && (dm & (dm - 1ull)) == 0ull, ff = has && foreign;
             const unsigned long long b_al = __builtin_amdgcn_ballot_w64(al), b_ff = __builtin_amdgcn_ballot_w64(ff);
-            if (b_al) res_reduce_add(lane, al, b_al, steps, span, co + 3u * RES_ALONE);
-            if (b_ff) res_reduce_add(lane, ff, b_ff, steps, span, co + 3u * RES_FROM_FOREIGN);
+            if (b_al) rs_reduce_add(lane, al, b_al, steps, span, co + 3u * RES_ALONE);
+            if (b_ff) rs_reduce_add(lane, ff, b_ff, steps, span, co + 3u * RES_FROM_FOREIGN);
         }
-    }
-    if (foreign || mosaic) {                                                 // the rare classes, per lane
+    });
+    if (foreign || mosaic) {                                                // the rare classes, per lane
         unsigned long long *const so = out.sp + (uint64_t)sp * (3u * RES_N_CLASSES);
         if (foreign) {
-            res_add3(so + 3u * RES_FOREIGN, 1ull, steps, span);
-            res_add3(so + 3u * (rescued ? RES_FOREIGN_RESCUED : has_n ? RES_FOREIGN_NOVEL : RES_FOREIGN_PATCHWORK), 1ull, steps, span);
+            rs_add3(so + 3u * RES_FOREIGN, 1ull, steps, span);
+            rs_add3(so + 3u * (rescued ? RES_FOREIGN_RESCUED : has_n ? RES_FOREIGN_NOVEL : RES_FOREIGN_PATCHWORK), 1ull, steps, span);
         } else {
-            res_add3(so + 3u * RES_MOSAIC, 1ull, steps, span);
-            if (rescued) res_add3(so + 3u * RES_MOSAIC_RESCUED, 1ull, steps, span);
+            rs_add3(so + 3u * RES_MOSAIC, 1ull, steps, span);
+            if (rescued) rs_add3(so + 3u * RES_MOSAIC_RESCUED, 1ull, steps, span);
         }
-        if (rescued && (d & (d - 1ull)) != 0ull) res_add3(so + 3u * RES_CONTESTED, 1ull, steps, span);
+        if (rescued && (d & (d - 1ull)) != 0ull) rs_add3(so + 3u * RES_CONTESTED, 1ull, steps, span);
     }
 }
 
@@ -137,18 +109,15 @@ __global__ void __launch_bounds__(256) rescue_kernel(uint32_t n_groups, uint32_t
         ResSpecies rs{0ull, 0ull, 0u, 0u};
         if (L.counted) rs = res[L.sr.x];
         const bool step = L.counted && rs.open != 0u;                        // a step of a counted read of an open species
-        const unsigned long long m = step ? res_word(L.st, L.v, node_haps, mask) : ~0ull;
+        const unsigned long long m = step ? rs_word1(L.st, L.v, node_haps, mask) : ~0ull;
         const bool f0 = step && (m & rs.sel_bits) == 0ull, nv = step && (m & (rs.sel_bits | rs.cand_bits)) == 0ull;
         const unsigned long long f_b = __builtin_amdgcn_ballot_w64(f0), n_b = __builtin_amdgcn_ballot_w64(nv);
         const unsigned long long a = seg_and(m, lane, L.seg);
-        const unsigned long long walk = res_lanes(L.seg, lane);              // my walk's lanes in this wave up to mine
+        const unsigned long long walk = rs_lanes(L.seg, lane);              // my walk's lanes in this wave up to mine
         const bool has_f = (f_b & walk) != 0ull, has_n = (n_b & walk) != 0ull;
         // the step counters: per species of the wave's foreign lanes
-        for (unsigned long long rem = f_b; rem;) {
-            const uint32_t s0 = lane_get(L.sr.x, __builtin_ctzll(rem));
-            const bool mine = f0 && L.sr.x == s0;
-            const unsigned long long mb = __builtin_amdgcn_ballot_w64(mine), nb = __builtin_amdgcn_ballot_w64(mine && nv);
-            rem &= ~mb;
+        rs_species_rounds(f0, L.sr.x, [&](uint32_t s0, bool mine, unsigned long long mb) {
+            const unsigned long long nb = __builtin_amdgcn_ballot_w64(mine && nv);
             if (lane == 0) {
                 unsigned long long *const xo = out.step + (uint64_t)s0 * 3u;
                 const unsigned long long nf = (unsigned long long)__popcll(mb), nn = (unsigned long long)__popcll(nb);
@@ -157,7 +126,7 @@ __global__ void __launch_bounds__(256) rescue_kernel(uint32_t n_groups, uint32_t
                 if (nn) atomicAdd(xo + 2, nn);
             }
             const unsigned long long cm = mine ? (m & rs.cand_bits) : 0ull;
-            if (mb == nb) continue;                                          // no candidate walks any of them
+            if (mb == nb) return;                                            // no candidate walks any of them
             const uint32_t bit_base = tab[s0].bit_base;
             for (unsigned long long q = res_wave_or(cm); q; q &= q - 1ull) {
                 const int b = __builtin_ctzll(q);
@@ -165,7 +134,7 @@ __global__ void __launch_bounds__(256) rescue_kernel(uint32_t n_groups, uint32_t
                 const uint32_t e = bit_entry[bit_base + (uint32_t)b];
                 if (lane == 0 && e != MEMBER_NO_ENTRY) atomicAdd(out.cand_steps + e, (unsigned long long)__popcll(hb));
             }
-        }
+        });
         // a walk of more than 64 steps: this group's part of its word and of its flags
         if (L.tail && L.is_long && step) {
             rs_long_partial(long_acc, 1u, L.slot, 0u, a);
@@ -173,7 +142,7 @@ __global__ void __launch_bounds__(256) rescue_kernel(uint32_t n_groups, uint32_t
             if (fl) atomicOr(&long_flag[L.slot], fl);
         }
         const bool decide = L.last && L.counted && !L.is_long;
-        res_wave_classes(lane, decide, L.sr.x, rs, a, has_f, has_n, L.rr.y, res_span(L.rr), tab, bit_entry, out);
+        res_wave_classes(lane, decide, L.sr.x, rs, a, has_f, has_n, L.rr.y, rs_span(L.rr), tab, bit_entry, out);
     }
 }
 
@@ -184,18 +153,13 @@ __global__ void __launch_bounds__(256) rescue_long_kernel(uint32_t n_slots, cons
                                                           const uint32_t *__restrict__ bit_entry, ResOut out) {
     const int lane = threadIdx.x & 63;
     for (uint64_t base = ((uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64u; base < n_slots; base += (uint64_t)gridDim.x * 256u) {   // (wave-uniform)
-        const uint64_t s = base + (uint64_t)lane;
-        const bool in = s < n_slots;
-        uint4 rr = make_uint4(0u, 0u, 0u, 0u);
-        uint32_t sp = 0xFFFFFFFFu;
-        if (in) { rr = read_rec[s]; sp = slot_rec[s].x; }
-        const bool decide = in && rr.y > 64u && (int32_t)sp >= 0;
+        const RsLongSlot t = rs_long_slot(base, lane, n_slots, read_rec, slot_rec);
         ResSpecies rs{0ull, 0ull, 0u, 0u};
-        if (decide) rs = res[sp];
+        if (t.decide) rs = res[t.sp];
         unsigned long long a = 0ull;
         uint32_t fl = 0u;
-        if (decide && rs.open) { a = long_acc[s]; fl = long_flag[s]; }
-        res_wave_classes(lane, decide, sp, rs, a, (fl & RES_LONG_FOREIGN) != 0u, (fl & RES_LONG_NOVEL) != 0u, rr.y, res_span(rr), tab, bit_entry, out);
+        if (t.decide && rs.open) { a = long_acc[t.s]; fl = long_flag[t.s]; }
+        res_wave_classes(lane, t.decide, t.sp, rs, a, (fl & RES_LONG_FOREIGN) != 0u, (fl & RES_LONG_NOVEL) != 0u, t.rr.y, rs_span(t.rr), tab, bit_entry, out);
     }
 }
 
@@ -240,41 +204,22 @@ int rescue_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *sel_off, const ui
             res[s].cand_bits = all & ~res[s].sel_bits;
         }
     }
-    // one device block, zero-filled once: [cand J x 9][cand steps J][species S x 27][step S x 3]
     const size_t n_sp = (size_t)S * 3 * RES_N_CLASSES, n_out = (size_t)J * 10 + n_sp + (size_t)S * 3;
     if (n_out == 0) return 0;
-    DevBuf<unsigned long long> d_out, d_long;
-    DevBuf<uint32_t> d_flag, d_bit_entry;
+    RsCounters cnt;
+    RsLongAcc lng;
+    DevBuf<uint32_t> d_bit_entry;
     DevBuf<RsSpecies> d_tab;
     DevBuf<ResSpecies> d_res;
-    PTX_HIP(ctx, d_out.alloc(n_out));
-    PTX_TRY(zero_fill(ctx, d_out.p, n_out * sizeof(unsigned long long)));
+    PTX_TRY(cnt.init(ctx, n_out));
+    const ResOut out{cnt.take((size_t)J * 9), cnt.take((size_t)J), cnt.take(n_sp), cnt.take((size_t)S * 3)};
     PTX_TRY(upload(ctx, d_tab, rt.tab.data(), rt.tab.size()));
     PTX_TRY(upload(ctx, d_res, res.data(), res.size()));
     PTX_TRY(upload(ctx, d_bit_entry, bit_entry.data(), bit_entry.size()));
     PTX_TRY(rt.wm.build(ctx, db));
-    const uint32_t n_slots = rd->n_slots, n_groups = (uint32_t)(rd->T_pad / 64);
-    const bool any_long = rd->n_long != 0 && n_slots != 0;
-    PTX_HIP(ctx, d_long.alloc(any_long ? (size_t)n_slots : 1));
-    PTX_HIP(ctx, d_flag.alloc(any_long ? (size_t)n_slots : 1));
-    if (any_long) {
-        PTX_HIP(ctx, hipMemsetAsync(d_long.p, 0xFF, (size_t)n_slots * sizeof(unsigned long long), ctx->stream));
-        PTX_HIP(ctx, hipMemsetAsync(d_flag.p, 0, (size_t)n_slots * sizeof(uint32_t), ctx->stream));
-    }
-    ResOut out;
-    out.cand = d_out.p; out.cand_steps = out.cand + (size_t)J * 9; out.sp = out.cand_steps + (size_t)J; out.step = out.sp + n_sp;
-    const unsigned long long *node_haps = rt.by_node ? (const unsigned long long *)db->d_node_haps.p : (const unsigned long long *)nullptr;
-    if (n_slots && n_groups) {
-        KTimer tm(ctx, "rescue_kernel");
-        hipLaunchKernelGGL(rescue_kernel, dim3(grid_for(n_groups, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_groups, n_slots, rd->d_g_group_slot.p,
-                           rd->d_g_step_dup.p, rd->d_g_node_id.p, rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p, d_res.p, node_haps, rt.wm.d_mask.p,
-                           d_bit_entry.p, d_long.p, d_flag.p, out);
-    }
-    if (any_long) {
-        KTimer tm(ctx, "rescue_long_kernel");
-        hipLaunchKernelGGL(rescue_long_kernel, dim3(grid_for(((uint64_t)n_slots + 63) / 64, 4, ctx->n_cu * 8)), dim3(256), 0, ctx->stream, n_slots,
-                           rd->d_g_read_rec.p, rd->d_g_slot_rec.p, d_tab.p, d_res.p, d_long.p, d_flag.p, d_bit_entry.p, out);
-    }
+    PTX_TRY(lng.init(ctx, rd, 1u, true));
+    rs_launch_groups(ctx, rd, "rescue_kernel", rescue_kernel, d_tab.p, d_res.p, rs_node_haps(rt, db), rt.wm.d_mask.p, d_bit_entry.p, lng.d_acc.p, lng.d_flag.p, out);
+    rs_launch_slots(ctx, rd, "rescue_long_kernel", rescue_long_kernel, d_tab.p, d_res.p, lng.d_acc.p, lng.d_flag.p, d_bit_entry.p, out);
     PTX_HIP(ctx, hipGetLastError());
     if (J) PTX_TRY(download(ctx, (unsigned long long *)cand_out, out.cand, (size_t)J * 9));
     if (J) PTX_TRY(download(ctx, (unsigned long long *)cand_steps_out, out.cand_steps, (size_t)J));
