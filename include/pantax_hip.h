@@ -646,6 +646,56 @@ int pantax_hip_rarefy_node_bases(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_
 /* host helper, no ctx and no GPU: depth(replicate, read) of the rule above */
 uint32_t pantax_hip_rarefy_depth(uint64_t seed, uint32_t replicate, uint64_t read);
 
+/* ---- fragment support (the --strain-fragments report; not a stage of the reference): read pairs as the unit of strain compatibility.  The read passes
+ * above take every alignment record as an island; a paired-end fragment of 300 to 600 bases reaches private nodes that neither 150-base mate reaches alone.
+ * Three calls: the fragment key of a read id (host only), the mates of every read from the keys (device: sort and one pass), and the fragment pass over
+ * the resident reads.
+ *
+ * Key.  An id of len >= 3 bytes whose last two bytes are "/1" or "/2" has the stem id[0 .. len - 2) and the tag 1 or 2; every other id is its own stem and
+ * has the tag 0.  key = the id hash of pantax_hip_gaf_ids (FNV-1a-64 and its avalanche) over the stem bytes: for tag 0 it is the tokenizers' id_hash.
+ * PANTAX_HIP_E_INVALID for a null argument.  No ctx and no GPU. */
+int pantax_hip_fragment_key(const char *id, uint64_t len, uint64_t *key_out, uint8_t *tag_out);
+/* Mates.  Reads i != j are mates iff key[i] == key[j], no third read has that key, and their tags are {1, 2} in either order or both 0.  For mates
+ * mate_out[i] = j and mate_out[j] = i; a key seen once gives PANTAX_HIP_MATE_NONE; every read of a key seen three times or more, or seen twice with any
+ * other tag pair, gives PANTAX_HIP_MATE_AMBIGUOUS.  counts_out [4] = { pairs, reads without a mate, ambiguous reads, keys seen three times or more }.
+ * n >= 2^32 - 2: PANTAX_HIP_E_LIMIT; a tag above 2 or a null argument: PANTAX_HIP_E_INVALID; n = 0 is fine.  Integers only: the result is a function of
+ * the inputs alone. */
+#define PANTAX_HIP_MATE_NONE      0xFFFFFFFFu
+#define PANTAX_HIP_MATE_AMBIGUOUS 0xFFFFFFFEu
+int pantax_hip_fragment_mates(pantax_hip_ctx *ctx, uint64_t n, const uint64_t *key /*[n] host*/, const uint8_t *tag /*[n] host*/,
+                              uint32_t *mate_out /*[n] host*/, uint64_t *counts_out /*[4]: pairs, none, ambiguous reads, keys seen >= 3 times*/);
+/* The fragment pass.  Inputs, a counted read, N(r), C(r), the weights, the assigned strain (argmax of w, ties to the smallest species-local haplotype
+ * index) and the state rule (reads binned against db, else PANTAX_HIP_E_STATE) are those of pantax_hip_read_strains; Q(r) = (1, n_steps, span) is that of
+ * pantax_hip_strain_read_support, and the numbers of a fragment {r, m} are (1, n_steps(r) + n_steps(m), span(r) + span(m)).  mate [R] names, in file
+ * order, the mate of every read or one of the two codes.  Every counted read r of species s falls into exactly one class:
+ *   mate[r] = NONE: single;   AMBIGUOUS: multi;   m counted and binned to s too: the fragment {r, m} is paired, accounted once;   m without a walk, dropped
+ *   by its flags, unbinned or of another species: mate_elsewhere (whichever species share the db).
+ * species_out [S][9][3], classes in the order { counted, paired, concordant, discordant, half, unexplained, single, multi, mate_elsewhere }, each
+ * { n, n_steps, span }: counted sums Q over every counted read of s; single, multi and mate_elsewhere sum Q over their reads; paired and the four classes
+ * behind it sum fragments.  For a species of 1 <= K_s <= 64 (served) every paired fragment has F = C(r) & C(m) and is exactly one of concordant (F not
+ * empty), discordant (both C non-empty, F empty), half (exactly one C empty), unexplained (both empty).
+ * hap_out [C][4][3] in the order of cand_hap, { compatible, unique, unique_by_pair, assigned }: the fragments with h in F; with F = {h}; with F = {h} while
+ * neither |C(r)| = 1 nor |C(m)| = 1 (what pairing alone resolves); whose argmax of w over F is h.
+ * pair_out: a discordant fragment is filed by the assigned strains of its two mates, at positions a and b of the species' candidate list, and adds one
+ * (fragments only) at pair_out[pair_off[s] + a * K_s + b] and at [b][a].  pair_off_out / pair_cap as for pantax_hip_strain_read_support: more than
+ * pair_cap entries is PANTAX_HIP_E_LIMIT with nothing but pair_off_out touched.
+ * status_out [S]: 0 served; 1 for K_s = 0; PANTAX_HIP_E_LIMIT for K_s > 64 -- in the last two cases counted, paired, single, multi and mate_elsewhere are
+ * still written and the other four classes are zeros.
+ * frag_n_out [R] or NULL: only the entries of reads binned to a species of db are written: |F| for a read of a paired fragment of a served species, else -1.
+ * Validation, before anything is written: a mate[r] that is neither code must be below R, differ from r, and mate[mate[r]] must be r; otherwise
+ * PANTAX_HIP_E_INVALID (counted on the device).  Other PANTAX_HIP_E_INVALID cases of pantax_hip_read_strains.
+ * Identities (all three numbers unless noted): counted = counted of pantax_hip_strain_read_support on the same candidates; counted = single + multi +
+ * mate_elsewhere + paired with the n of paired taken twice; for a served species paired = concordant + discordant + half + unexplained, the sum of
+ * assigned = concordant, unique_by_pair <= unique <= assigned <= compatible, the sum of its pair block = 2 x discordant.n; with every mate NONE single =
+ * counted and every other class is zero.  Integers only: the same bits whatever the order and the membership route. */
+#define PANTAX_HIP_FRAGMENT_CLASSES 9   /* counted, paired, concordant, discordant, half, unexplained, single, multi, mate_elsewhere */
+int pantax_hip_strain_fragments(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand,
+                                const uint32_t *mate /*[R] host, file order*/,
+                                uint64_t *hap_out /*[C][4][3]: compatible, unique, unique_by_pair, assigned*/,
+                                uint64_t *species_out /*[S][9][3]*/, int32_t *status_out /*[S]*/,
+                                uint64_t *pair_off_out /*[S+1]*/, uint64_t pair_cap, uint64_t *pair_out,
+                                int32_t *frag_n_out /*[R] or NULL*/);
+
 /* ---- pairwise strain distinguishability of a db (the --db-pairs mode; not a stage of the reference): the strain step's LP has one 0/1 column per haplotype
  * over the nodes of its species (profile.rs:1333-1342); two haplotypes with equal columns cannot be told apart by it, and two whose columns differ on 300
  * bases of nodes only where those 300 bases are covered.  This call says, before any sample, which selected haplotypes of the db can be separated and by how
@@ -1320,6 +1370,24 @@ typedef struct {
     uint64_t strain_rarefy_replicates;   /* replicates per level: 0 reads as 5, and so does a struct that does not hold the field */
     uint64_t strain_rarefy_seed;         /* a struct that does not hold the field reads as 42; 0 passed explicitly is 0 */
 } pantax_hip_profile_ext10;
+/* ... and once more: pantax_hip_profile_ext10 is closed at strain_rarefy_seed (a committed host check holds its 200 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the tenth version.  A caller fills v10.v9.v8.v7.v6.v5.v4.v3.v2.v1.struct_size =
+ * sizeof(pantax_hip_profile_ext11) and passes &ext11.v10.v9.v8.v7.v6.v5.v4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40-, 48-, 64-,
+ * 88-, 120-, 136-, 152-, 168- or 200-byte struct runs with the field below off.  A later output is a field appended here. */
+typedef struct {
+    pantax_hip_profile_ext10 v10;   /* v10.v9.v8.v7.v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext11) */
+    /* --strain-fragments: path of the fragment support report (NULL, "" or "None" = off).  Key and tag of every GAF record by the rule of
+     * pantax_hip_fragment_key, pantax_hip_fragment_mates once per run, and pantax_hip_strain_fragments over every group of species, right behind the
+     * group's strain step and beside the rarefaction call, with the candidates and weights of read_strain_file (the rows of strain_abundance.txt, their
+     * unrounded predicted_coverage).  TSV with a header: species_taxid, strain_taxid, genome_ID, class, n_fragments, n_reads, n_steps, span, fraction,
+     * other_strain_taxid, other_genome_ID; f64 in shortest round-trip digits, "-" where a column does not apply.  (1) per row of strain_abundance.txt, in
+     * its order: "compatible", "unique", "unique_by_pair", "assigned" with fraction over the species' paired fragments (n_reads = 2 n_fragments);
+     * (2) per species in shard order the nine classes, fraction = n_reads over the counted reads (the read classes have "-" in n_fragments, the fragment
+     * classes n_reads = 2 n_fragments; a species of more than 64 rows prints counted, paired, single, multi, mate_elsewhere and one "skipped" row);
+     * (3) per species one "discordant_pair" row per pair a < b of its rows (ascending haplotype index) with a non-zero count: strain a in the strain
+     * columns, strain b in other_*, fraction over the species' discordant fragments.  Same rules as strain_fit_file. */
+    const char *strain_fragments_file;
+} pantax_hip_profile_ext11;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

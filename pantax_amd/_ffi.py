@@ -33,6 +33,7 @@ SYMBOLS = [
     "pantax_hip_strain_read_rescue", "pantax_hip_rescue_walk", "pantax_hip_rescue_rank",
     "pantax_hip_strain_links", "pantax_hip_link_crossings", "pantax_hip_link_top",
     "pantax_hip_strain_rarefy", "pantax_hip_rarefy_node_bases", "pantax_hip_rarefy_depth",
+    "pantax_hip_fragment_key", "pantax_hip_fragment_mates", "pantax_hip_strain_fragments",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -46,6 +47,9 @@ MOSAIC_CLASSES = 6   # PANTAX_HIP_MOSAIC_CLASSES
 RESCUE_CLASSES = 9   # PANTAX_HIP_RESCUE_CLASSES
 LINK_SPECIES_N = 6   # PANTAX_HIP_LINK_SPECIES_N
 LINK_HAP_N = 8       # PANTAX_HIP_LINK_HAP_N
+MATE_NONE = 0xFFFFFFFF        # PANTAX_HIP_MATE_NONE
+MATE_AMBIGUOUS = 0xFFFFFFFE   # PANTAX_HIP_MATE_AMBIGUOUS
+FRAGMENT_CLASSES = 9   # PANTAX_HIP_FRAGMENT_CLASSES
 DEPTH_BINS = 96   # PANTAX_HIP_DEPTH_BINS
 DEPTH_NONE = 1    # PANTAX_HIP_DEPTH_NONE: pantax_hip_depth_quantile of a histogram without length
 
@@ -156,9 +160,9 @@ class FitSet(C.Structure):
 
 
 class ProfileExt(C.Structure):
-    """pantax_hip_profile_ext10 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
+    """pantax_hip_profile_ext11 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
     behind it (40 bytes), strain_dropout_file (48), the two fields of pantax_hip_profile_ext4 (64), the three of pantax_hip_profile_ext5 (88), the four
-    of pantax_hip_profile_ext6 (120), the two of pantax_hip_profile_ext7 (136), the two of pantax_hip_profile_ext8 (152), the two of pantax_hip_profile_ext9 (168) and the four of pantax_hip_profile_ext10 (200); struct_size = ctypes.sizeof(ProfileExt)"""
+    of pantax_hip_profile_ext6 (120), the two of pantax_hip_profile_ext7 (136), the two of pantax_hip_profile_ext8 (152), the two of pantax_hip_profile_ext9 (168), the four of pantax_hip_profile_ext10 (200) and the one of pantax_hip_profile_ext11 (208); struct_size = ctypes.sizeof(ProfileExt)"""
     _fields_ = [("struct_size", C.c_uint64), ("strain_fit_file", C.c_char_p), ("strain_bootstrap_file", C.c_char_p),
                 ("strain_bootstrap_replicates", C.c_uint64), ("strain_bootstrap_seed", C.c_uint64), ("strain_dropout_file", C.c_char_p),
                 ("strain_addin_file", C.c_char_p), ("strain_addin_top", C.c_uint64),
@@ -168,7 +172,7 @@ class ProfileExt(C.Structure):
                 ("strain_rescue_file", C.c_char_p), ("strain_rescue_top", C.c_uint64),
                 ("strain_links_file", C.c_char_p), ("strain_links_top", C.c_uint64),
                 ("strain_rarefy_file", C.c_char_p), ("strain_rarefy_levels", C.c_uint64), ("strain_rarefy_replicates", C.c_uint64),
-                ("strain_rarefy_seed", C.c_uint64)]
+                ("strain_rarefy_seed", C.c_uint64), ("strain_fragments_file", C.c_char_p)]
 
 
 class RarefySet(C.Structure):
@@ -288,6 +292,12 @@ def load():
         _lib.pantax_hip_rarefy_node_bases.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib.pantax_hip_rarefy_depth.restype = C.c_uint32
         _lib.pantax_hip_rarefy_depth.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
+        _lib.pantax_hip_fragment_key.restype = C.c_int
+        _lib.pantax_hip_fragment_key.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]
+        _lib.pantax_hip_fragment_mates.restype = C.c_int
+        _lib.pantax_hip_fragment_mates.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.pantax_hip_strain_fragments.restype = C.c_int
+        _lib.pantax_hip_strain_fragments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReadStrainSet)] + [C.c_void_p] * 5 + [C.c_uint64] + [C.c_void_p] * 2
         _lib.pantax_hip_profile_with_ext.restype = C.c_int
         _lib.pantax_hip_profile_with_ext.argtypes = [C.c_void_p, C.POINTER(ProfilingConfig), C.POINTER(ProfileExt)]
         _lib.pantax_hip_db_pairs.restype = C.c_int

@@ -104,6 +104,8 @@ void rs_skipped(const RunPlan &p) {
         if (p.rep.ext9_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.ext9_path[i].c_str());
     for (int i = 0; i < N_EXT10_REPORTS; ++i)
         if (p.rep.ext10_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.ext10_path[i].c_str());
+    for (int i = 0; i < N_EXT11_REPORTS; ++i)
+        if (p.rep.ext11_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.ext11_path[i].c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
 // ALL species ranges (ranges-only db), counters on the device
@@ -131,7 +133,8 @@ int ingest_local(Run &run, Ingest &in) {
     // (no locus-grouped copy yet: the species decision needs the counters only -- the plain columns are binned in file order --, and the copy is
     // built while the first graphs travel, on an otherwise idle device; round 5 built it here, 27 ms behind the last byte of the GAF at 1e8 reads)
     PTX_TRY(gaf_tokenize_device(run.ctx, in.mf.data + in.text_begin, text_end - in.text_begin, in.hr, in.reads.rd, in.mf.fd, in.text_begin, /*group=*/false,
-                                /*want_id_spans=*/run.p.want_report || run.p.rep.run[REP_READ_STRAINS], /*want_host_columns=*/false));
+                                /*want_id_spans=*/run.p.want_report || run.p.rep.run[REP_READ_STRAINS] || run.p.rep.ext11_run[X11REP_FRAGMENTS],
+                                /*want_host_columns=*/false));
     in.R = in.R_all = in.reads.rd->R;
     run.lap("ranges + GAF tokenise");
     in.rs.resize(S); in.re.resize(S);

@@ -563,6 +563,32 @@ int pantax_hip_strain_read_support(pantax_hip_ctx *ctx, pantax_hip_db *db, panta
     return read_support_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), ord.data(), pair_off_out, hap_out, species_out, pair_out);
 }
 
+int pantax_hip_fragment_mates(pantax_hip_ctx *ctx, uint64_t n, const uint64_t *key, const uint8_t *tag, uint32_t *mate_out, uint64_t *counts_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!counts_out || (n && (!key || !tag || !mate_out))) return fail(ctx, PANTAX_HIP_E_INVALID, "fragment_mates: null argument");
+    if (n >= PANTAX_HIP_MATE_AMBIGUOUS) return fail(ctx, PANTAX_HIP_E_LIMIT, "fragment_mates: %llu reads exceed the 32-bit mate indices", (unsigned long long)n);
+    for (uint64_t i = 0; i < n; ++i)
+        if (tag[i] > 2) return fail(ctx, PANTAX_HIP_E_INVALID, "fragment_mates: tag %u of read %llu (0, 1 or 2)", (unsigned)tag[i], (unsigned long long)i);
+    PTX_ENTER(ctx);
+    counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+    if (n == 0) return 0;
+    return fragment_mates_launch(ctx, n, key, tag, mate_out, counts_out);
+}
+
+int pantax_hip_strain_fragments(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand, const uint32_t *mate,
+                                uint64_t *hap_out, uint64_t *species_out, int32_t *status_out, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out,
+                                int32_t *frag_n_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !reads || !cand || !cand->cand_off || !pair_off_out || (reads->R && !mate)) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_fragments: null argument");
+    PTX_ENTER(ctx);
+    std::vector<uint32_t> hap;
+    std::vector<double> w;
+    std::vector<uint64_t> ord;
+    PTX_TRY(check_read_strain_set(ctx, db, reads, cand, "strain_fragments", hap, w, ord));
+    return fragments_launch(ctx, db, reads, cand->cand_off, hap.data(), w.data(), ord.data(), mate, hap_out, species_out, status_out, pair_off_out, pair_cap, pair_out,
+                            frag_n_out);
+}
+
 int pantax_hip_strain_mosaic(pantax_hip_ctx *ctx, pantax_hip_db *db, pantax_hip_reads *reads, const pantax_hip_read_strain_set *cand, uint64_t *species_out,
                              uint64_t *extra_out, uint64_t *hap_out, uint64_t *pair_off_out, uint64_t pair_cap, uint64_t *pair_out, uint64_t junction_cap,
                              uint32_t *junction_out, uint64_t *junction_count_out, uint64_t *n_junctions_out, uint64_t *n_breaks_total_out) {

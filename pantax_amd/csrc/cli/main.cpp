@@ -82,6 +82,10 @@ static void usage() {
             "  --strain-rarefy-levels N   thinned levels 1/2 .. 2^-N (default 5, at most 16)\n"
             "  --strain-rarefy-replicates N   replicates per level (default 5)\n"
             "  --strain-rarefy-seed N   seed of the thinning rule (default 42)\n"
+            "  --strain-fragments F   fragment support: read pairs (ids X/1 and X/2, or one id twice) as the unit of strain compatibility -- per row of\n"
+            "                     strain_abundance.txt the fragments it is compatible with, alone, alone only as a pair, and assigned; per species the fragments\n"
+            "                     concordant, discordant (each mate fits a reported strain, no common one), half and unexplained, the reads single, multi and\n"
+            "                     with their mate elsewhere, and which two strains the discordant fragments sit between (one rank only)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -107,8 +111,9 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
-    pantax_hip_profile_ext10 ext10;   // the outputs added behind the config's last field
-    memset(&ext10, 0, sizeof(ext10));
+    pantax_hip_profile_ext11 ext11;   // the outputs added behind the config's last field
+    memset(&ext11, 0, sizeof(ext11));
+    pantax_hip_profile_ext10 &ext10 = ext11.v10;
     pantax_hip_profile_ext9 &ext9 = ext10.v9;
     pantax_hip_profile_ext8 &ext8 = ext9.v8;
     pantax_hip_profile_ext7 &ext7 = ext8.v7;
@@ -117,7 +122,7 @@ int main(int argc, char **argv) {
     pantax_hip_profile_ext4 &ext4 = ext5.v4;
     pantax_hip_profile_ext3 &ext3 = ext4.v3;
     pantax_hip_profile_ext2 &ext = ext3.v2;
-    ext.v1.struct_size = sizeof(ext10);
+    ext.v1.struct_size = sizeof(ext11);
     ext.strain_bootstrap_seed = 42;
     ext10.strain_rarefy_seed = 42;
     pantax_hip_db_pairs_config pairs;
@@ -205,6 +210,7 @@ int main(int argc, char **argv) {
         else if (a == "--strain-rarefy-levels") ext10.strain_rarefy_levels = strtoull(next(), nullptr, 10);
         else if (a == "--strain-rarefy-replicates") ext10.strain_rarefy_replicates = strtoull(next(), nullptr, 10);
         else if (a == "--strain-rarefy-seed") ext10.strain_rarefy_seed = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-fragments") ext11.strain_fragments_file = next();
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

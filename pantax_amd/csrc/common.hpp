@@ -712,6 +712,14 @@ int rescue_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *sel_off, const ui
 int links_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t *species_out, uint64_t *link_out, uint64_t *hap_out,
                  uint64_t *brk_off_out, uint64_t cap, uint64_t *brk_step_out, uint64_t *brk_start_out, uint32_t *brk_node_a_out, uint32_t *brk_node_b_out,
                  uint64_t *brk_flank_out, uint64_t *brk_mask_out);
+// stage_fragments.hip (pantax_hip_fragment_mates): n > 0 keys and tags (<= 2) validated by the caller; mate_out [n], counts_out [4]
+int fragment_mates_launch(Ctx *ctx, uint64_t n, const uint64_t *key, const uint8_t *tag, uint32_t *mate_out, uint64_t *counts_out);
+// ... (pantax_hip_strain_fragments): the arguments of read_support_launch; mate [R] is validated here, on the device, before anything is written; then
+// pair_off_out [S+1] is written and the pair_cap rule of read support holds; hap_out [C][4][3] in the caller's order, species_out [S][9][3], status_out [S],
+// frag_n_out [R] or null
+int fragments_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const double *cand_w, const uint64_t *entry_of,
+                     const uint32_t *mate, uint64_t *hap_out, uint64_t *species_out, int32_t *status_out, uint64_t *pair_off_out, uint64_t pair_cap,
+                     uint64_t *pair_out, int32_t *frag_n_out);
 // stage_read_em.hip (pantax_hip_strain_read_em): candidates of every species in ascending haplotype order with their lengths, entry_of[c] = the caller's entry
 // of sorted candidate c; all validated by the caller.  Outputs as the stage call's; they are written only when the call succeeds (cls_off_out: also on E_LIMIT)
 int read_em_launch(Ctx *ctx, Db *db, Reads *rd, const uint64_t *cand_off, const uint32_t *cand_hap, const uint64_t *cand_len, const uint64_t *entry_of, uint32_t max_iter,

@@ -2,11 +2,13 @@
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
 // (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
-// report, the add-one report, the read class report, the segment report, the mosaic read report, the read rescue report, the link support report and the rarefaction report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT10_REPORTS).
+// report, the add-one report, the read class report, the segment report, the mosaic read report, the read rescue report, the link support report, the rarefaction report and the fragment support report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT11_REPORTS).
 #include <algorithm>
 #include <cmath>
 #include <fstream>
+#include <thread>
 #include <unordered_map>
+#include "fragments_plan.hpp"
 #include "hap_pairs_plan.hpp"
 #include "links_plan.hpp"
 #include "mosaic_plan.hpp"
@@ -481,6 +483,39 @@ int group_links(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint
                                            lk.node_b.data() + at, lk.flank.data() + at, lk.mask.data() + at));
     for (size_t e = 0; e < C; ++e) lk.brk_off.push_back(at + b_off[e + 1]);
     run.lap("  strain link support");
+    return 0;
+}
+// --strain-fragments, beside the rarefaction call and with the candidates and weights of group_read_strains.  Before the first group: key and tag of every
+// record from the mapped text and the id spans, on the host crew, and the mates of the whole file in one call
+int group_fragments(Run &run, const Ingest &in, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &fr = sh.rep.fr;
+    const uint32_t Sg = k1 - k0;
+    const uint64_t R = in.R;
+    if (!fr.have_mate) {
+        if (in.hr.id_span.size() != R) return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: the fragment support report needs the id spans of the GAF");
+        std::vector<uint64_t> key(R);
+        std::vector<uint8_t> tag(R);
+        const int n_thr = (int)std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
+        parallel_for(R, n_thr, [&](uint64_t i0, uint64_t i1) {
+            for (uint64_t r = i0; r < i1; ++r) fragment_key(in.mf.data + in.text_begin + in.hr.id_span[r].first, in.hr.id_span[r].second, key[r], tag[r]);
+        });
+        uint64_t counts[4];
+        fr.mate.assign(R, PANTAX_HIP_MATE_NONE);
+        PTX_TRY(pantax_hip_fragment_mates(run.ctx, R, key.data(), tag.data(), fr.mate.data(), counts));
+        fr.have_mate = true;
+        run.lap("  fragment mates");
+    }
+    std::vector<uint64_t> p_off(Sg + 1, 0);
+    const pantax_hip_read_strain_set cs{Sg, g.off.data(), g.hap.data(), g.w.data()};
+    fr.hap.resize(3 * FRG_N_HAP * (g.entry0 + g.hap.size()));
+    uint64_t n_pair = 0;
+    for (uint32_t k = 0; k < Sg; ++k) { const uint64_t K = g.off[k + 1] - g.off[k]; fr.K[k0 + k] = (uint32_t)K; n_pair += K <= FRAG_MAX_LIST ? K * K : 0; }
+    const size_t pair0 = fr.pair.size();
+    fr.pair.resize(pair0 + n_pair);
+    PTX_TRY(pantax_hip_strain_fragments(run.ctx, db, in.reads.rd, &cs, fr.mate.data(), fr.hap.data() + 3 * FRG_N_HAP * g.entry0,
+                                        fr.species.data() + 3 * FRG_N_CLASSES * (size_t)k0, fr.status.data() + k0, p_off.data(), n_pair, fr.pair.data() + pair0, nullptr));
+    for (uint32_t k = 0; k < Sg; ++k) fr.pair_off[k0 + k] = pair0 + p_off[k];
+    run.lap("  strain fragment support");
     return 0;
 }
 
@@ -1146,6 +1181,63 @@ struct Writer {
             return 0;
         });
     }
+    // --strain-fragments: {compatible, unique, unique_by_pair, assigned} of every row of strain_abundance.txt, in its order; the nine classes of every species
+    // of the shard in the order it went through the device (a species without rows or of more than 64: the five that need no candidate set); the discordant
+    // fragments between every two rows of a species
+    int fragments() const {
+        const auto &fr = rep.fr;
+        return file(run.p.rep.ext11_path[X11REP_FRAGMENTS],
+                    "species_taxid\tstrain_taxid\tgenome_ID\tclass\tn_fragments\tn_reads\tn_steps\tspan\tfraction\tother_strain_taxid\tother_genome_ID\n",
+                    "strain fragment support report", [&](std::ofstream &f) {
+            const auto frac = [](uint64_t n, uint64_t of) { return of ? fmt_f64((double)n / (double)of) : std::string("-"); };
+            const auto served = [&](uint32_t k) { return fr.K[k] >= 1 && fr.K[k] <= FRAG_MAX_LIST; };
+            const auto sp = [&](uint32_t k, int cls) { return fr.species.data() + 3 * FRG_N_CLASSES * (size_t)k + 3 * cls; };
+            const char *const of_row[FRG_N_HAP] = {"compatible", "unique", "unique_by_pair", "assigned"};
+            const char *const of_species[FRG_N_CLASSES] = {"counted", "paired", "concordant", "discordant", "half", "unexplained", "single", "multi", "mate_elsewhere"};
+            std::vector<const TrackRow *> row_of(fr.hap.size() / (3 * FRG_N_HAP), nullptr);   // entry -> its first row of the table
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "fragment support", &e));
+                if (!row_of[e]) row_of[e] = &r;
+                const std::string head = strain_head(r);
+                for (int c = 0; c < (int)FRG_N_HAP; ++c) {
+                    const uint64_t *q = fr.hap.data() + 3 * FRG_N_HAP * (size_t)e + 3 * c;
+                    f << head << '\t' << of_row[c];
+                    if (served(r.k)) f << '\t' << q[0] << '\t' << 2 * q[0] << '\t' << q[1] << '\t' << q[2] << '\t' << frac(q[0], sp(r.k, FRG_PAIRED)[0]);
+                    else f << "\t-\t-\t-\t-\t-";
+                    f << "\t-\t-\n";
+                }
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const std::string head = species_head(k);
+                const uint64_t counted = sp(k, FRG_COUNTED)[0];
+                for (int c = 0; c < (int)FRG_N_CLASSES; ++c) {
+                    const bool of_reads = c == FRG_COUNTED || c >= FRG_SINGLE, needs_set = c >= FRG_CONCORDANT && c <= FRG_UNEXPLAINED;
+                    if (needs_set && !served(k)) continue;
+                    const uint64_t *q = sp(k, c), n_reads = of_reads ? q[0] : 2 * q[0];
+                    f << head << '\t' << of_species[c] << '\t';
+                    if (of_reads) f << '-'; else f << q[0];
+                    f << '\t' << n_reads << '\t' << q[1] << '\t' << q[2] << '\t' << frac(n_reads, counted) << "\t-\t-\n";
+                }
+                if (fr.K[k] > FRAG_MAX_LIST) f << head << "\tskipped\t-\t-\t-\t-\t-\t-\t-\n";
+            }
+            for (uint32_t k = 0; k < Su; ++k) {
+                const uint64_t K = fr.K[k];
+                if (K < 2 || K > FRAG_MAX_LIST) continue;
+                int64_t e0 = -1;                                                        // the species' entries are consecutive, in ascending haplotype index
+                for (uint64_t h = sh.hap_off[k]; h < sh.hap_off[k + 1] && e0 < 0; ++h) e0 = rep.entry[h];
+                const uint64_t *pm = fr.pair.data() + fr.pair_off[k];
+                for (uint64_t a = 0; a < K; ++a)
+                    for (uint64_t b = a + 1; b < K; ++b) {
+                        const uint64_t n = pm[a * K + b];
+                        if (!n || e0 < 0 || !row_of[e0 + a] || !row_of[e0 + b]) continue;
+                        const TrackRow &ra = *row_of[e0 + a], &rb = *row_of[e0 + b];
+                        f << strain_head(ra) << "\tdiscordant_pair\t" << n << '\t' << 2 * n << "\t-\t-\t" << frac(n, sp(k, FRG_DISCORDANT)[0]) << '\t'
+                          << (rb.gr ? rb.gr->strain_taxid : std::string()) << '\t' << (rb.gr ? rb.gr->genome_id : std::string()) << '\n';
+                    }
+            }
+            return 0;
+        });
+    }
     // --strain-pair-evidence: per species of the shard, in the order it went through the device, for every two of its rows a < b (ascending haplotype index)
     // what both walk (shared) and what only a, only b walks, as {n_nodes, len, covered, bases} with depth and breadth
     int pair_evidence() const {
@@ -1223,6 +1315,9 @@ void begin(const ReportPlan &plan, uint32_t Su, uint64_t H, uint64_t R, ReportDa
     if (plan.ext9_run[X9REP_LINKS]) {
         rep.lk.species.assign(LNK_N_SPECIES * (size_t)Su, 0); rep.lk.link.assign(LNK_N_TABLE * (size_t)Su, 0); rep.lk.open.assign(Su, 0);
     }
+    if (plan.ext11_run[X11REP_FRAGMENTS]) {
+        rep.fr.species.assign(3 * FRG_N_CLASSES * (size_t)Su, 0); rep.fr.pair_off.assign(Su, 0); rep.fr.K.assign(Su, 0); rep.fr.status.assign(Su, 1);
+    }
     if (plan.ext7_run[X7REP_MOSAIC]) {
         rep.mo.species.assign(3 * MOS_N_CLASSES * (size_t)Su, 0); rep.mo.extra.assign(3 * (size_t)Su, 0); rep.mo.pair_off.assign(Su, 0); rep.mo.K.assign(Su, 0); rep.mo.jn_off.assign(Su + 1, 0);
     }
@@ -1248,6 +1343,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.ext8_run[X8REP_RESCUE]) PTX_TRY(group_rescue(run, in, db, k0, k1, g, sh, gc));
     if (plan.ext9_run[X9REP_LINKS]) PTX_TRY(group_links(run, in, db, k0, k1, g, sh));
     if (plan.ext10_run[X10REP_RAREFY]) PTX_TRY(group_rarefy(run, in, db, k0, k1, g, sh));
+    if (plan.ext11_run[X11REP_FRAGMENTS]) PTX_TRY(group_fragments(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_DEPTH]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_depth, 2 * DEPTH_N, 2 * DEPTH_N, sh.rep.dp, "  strain depth"));
     if (plan.run[REP_NEAR_MISS]) PTX_TRY(group_near_miss(run, db, k0, k1, g, sh, gc));
     return 0;
@@ -1275,6 +1371,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext8_run[X8REP_RESCUE]) PTX_TRY(w.rescue());
     if (plan.ext9_run[X9REP_LINKS]) PTX_TRY(w.links());
     if (plan.ext10_run[X10REP_RAREFY]) PTX_TRY(w.rarefy());
+    if (plan.ext11_run[X11REP_FRAGMENTS]) PTX_TRY(w.fragments());
     return 0;
 }
 }  // namespace reports

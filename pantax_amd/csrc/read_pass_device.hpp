@@ -1,4 +1,4 @@
-// read_pass_device.hpp -- what the seven passes over the locus-grouped step stream share: a wave per 64-step group, a lane per step.  Who takes what:
+// read_pass_device.hpp -- what the eight passes over the locus-grouped step stream share: a wave per 64-step group, a lane per step.  Who takes what:
 //   stage_read_strain.hip    (read_strains)         the species table, rs_lane / rs_lane_word / seg_and, the long-walk partials, the host skeleton;
 //   stage_read_support.hip   (strain_read_support)  the same, and Q(r) with its wave sums, the species rounds, the lane-per-slot prologue, the counter block;
 //   stage_read_em.hip        (strain_read_em)       as read support, less the counter block (its class tables grow between reruns and stay its own);
@@ -6,7 +6,9 @@
 //   stage_rescue.hip         (strain_read_rescue)   the same, and the long-walk partials with their flags and the lane-per-slot prologue;
 //   stage_links.hip          (strain_links)         rs_lane, rs_word1, the species rounds, the table, the group launch -- its read pass, and the species
 //                                                   rounds once more in links_count_kernel, a lane per distinct link: the loop is written in one place;
-//   stage_rarefy.hip         (strain_rarefy)        the species rounds and the group launch (it has no species table and no candidate masks).
+//   stage_rarefy.hip         (strain_rarefy)        the species rounds and the group launch (it has no species table and no candidate masks);
+//   stage_fragments.hip      (strain_fragments)     rs_lane, rs_lane_word / seg_and, the long-walk partials, the table and the group launch in its mask pass;
+//                                                   Q(r) with its wave sums, the species rounds and the counter block in its join, a lane per slot.
 // The step codes and the slot lookup are those of the coverage pass (cov_device.hpp).  Device code and the host code that feeds it; include from .hip
 // files only.  The kernels keep flat parameter lists with __restrict__ on every pointer: the helpers share code, not a kernarg layout.
 #pragma once

@@ -29,7 +29,7 @@ template <class Ext, class T> bool ext_value(const pantax_hip_profile_ext *ext, 
     std::memcpy(&value, reinterpret_cast<const char *>(ext) + at, sizeof(value));
     return true;
 }
-// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2 / _ext3 / _ext4 / _ext5 / _ext6 / _ext7 / _ext8 / _ext9 / _ext10, which begin with it)
+// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2 / _ext3 / _ext4 / _ext5 / _ext6 / _ext7 / _ext8 / _ext9 / _ext10 / _ext11, which begin with it)
 template <class Ext> const char *ext_field(const pantax_hip_profile_ext *ext, const char *Ext::*field) {
     const char *value = nullptr;
     return ext_value(ext, field, value) ? value : nullptr;
@@ -68,6 +68,7 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
     for (int i = 0; i < N_EXT8_REPORTS; ++i) { plan.ext8_path[i].clear(); plan.ext8_want[i] = plan.ext8_run[i] = false; }
     for (int i = 0; i < N_EXT9_REPORTS; ++i) { plan.ext9_path[i].clear(); plan.ext9_want[i] = plan.ext9_run[i] = false; }
     for (int i = 0; i < N_EXT10_REPORTS; ++i) { plan.ext10_path[i].clear(); plan.ext10_want[i] = plan.ext10_run[i] = false; }
+    for (int i = 0; i < N_EXT11_REPORTS; ++i) { plan.ext11_path[i].clear(); plan.ext11_want[i] = plan.ext11_run[i] = false; }
     if (ext && (ext->struct_size < 8 || ext->struct_size % 8 != 0)) {
         err = "profile: pantax_hip_profile_ext.struct_size " + std::to_string((unsigned long long)ext->struct_size) + " (a multiple of 8, at least 8)";
         return false;
@@ -92,6 +93,8 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
         if (!plan_path(EXT9_REPORTS[i], ext_field(ext, EXT9_REPORTS[i].field), W, sharded, plan.ext9_path[i], plan.ext9_want[i], err)) return false;
     for (int i = 0; i < N_EXT10_REPORTS; ++i)
         if (!plan_path(EXT10_REPORTS[i], ext_field(ext, EXT10_REPORTS[i].field), W, sharded, plan.ext10_path[i], plan.ext10_want[i], err)) return false;
+    for (int i = 0; i < N_EXT11_REPORTS; ++i)
+        if (!plan_path(EXT11_REPORTS[i], ext_field(ext, EXT11_REPORTS[i].field), W, sharded, plan.ext11_path[i], plan.ext11_want[i], err)) return false;
     plan.bs_replicates = 100; plan.bs_seed = 42; plan.ai_top = 5; plan.em_classes = 10; plan.em_iterations = 1000;
     plan.sg_min = 1000; plan.sg_bridge = 100; plan.sg_peak = 10; plan.mo_top = 10; plan.rs_top = 5; plan.lk_top = 10;
     plan.rf_levels = 5; plan.rf_replicates = 5; plan.rf_seed = 42;
@@ -161,6 +164,7 @@ void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_d
     for (int i = 0; i < N_EXT8_REPORTS; ++i) plan.ext8_run[i] = runs(plan.ext8_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT9_REPORTS; ++i) plan.ext9_run[i] = runs(plan.ext9_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT10_REPORTS; ++i) plan.ext10_run[i] = runs(plan.ext10_want[i], strain, full_path, strain_done);
+    for (int i = 0; i < N_EXT11_REPORTS; ++i) plan.ext11_run[i] = runs(plan.ext11_want[i], strain, full_path, strain_done);
 }
 
 }  // namespace ptx

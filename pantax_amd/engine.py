@@ -344,6 +344,50 @@ class Engine:
                                                             p(species) if self.S else None, p(pair_off), len(pair), p(pair) if len(pair) else None))
         return hap, species, pair_off, pair
 
+    def fragment_mates(self, key, tag):
+        """pantax_hip_fragment_mates: the mate of every read from its fragment key and tag (fragment_key) -> (mate uint32 [n]: the index of the mate,
+        MATE_NONE or MATE_AMBIGUOUS; counts uint64 [4]: pairs, reads without a mate, ambiguous reads, keys seen three times or more)."""
+        k = as_c(key, np.uint64)
+        t = as_c(tag, np.uint8)
+        if len(k) != len(t):
+            raise ValueError("fragment_mates: key and tag are of one length")
+        mate = np.full(len(k), _ffi.MATE_NONE, dtype=np.uint32)
+        counts = np.zeros(4, dtype=np.uint64)
+        q = lambda a: p(a) if a.size else None
+        self._check(self.lib.pantax_hip_fragment_mates(self.ctx, len(k), q(k), q(t), q(mate), p(counts)))
+        return mate, counts
+
+    def strain_fragments(self, cand_off, cand_hap, cand_w, mate, want_n=False, fill=None, pair_cap=None):
+        """Fragment support (pantax_hip_strain_fragments) of the resident reads, binned against the resident db: read pairs as the unit of strain
+        compatibility.  The candidate set of read_strains and mate uint32 [R] in file order (fragment_mates) -> (hap uint64 [C, 4, 3]: compatible /
+        unique / unique_by_pair / assigned of every candidate entry, species uint64 [S, 9, 3]: counted / paired / concordant / discordant / half /
+        unexplained / single / multi / mate_elsewhere, status int32 [S], pair_off uint64 [S+1], pair uint64 [pair_off[-1]]: the K_s x K_s discordant
+        fragment counts of every species of K_s <= 64, frag_n int32 [R] or None); the last axis of hap and species is {n, n_steps, span}.  want_n: |F| of
+        every read of a paired fragment of a served species, -1 for the other reads binned to the db; entries of other reads keep `fill` (default -2).
+        pair_cap None: sized inside; a number that is too small raises PantaxHipError with code E_LIMIT."""
+        co = as_c(cand_off, np.uint64)
+        ch = as_c(cand_hap, np.uint32)
+        cw = as_c(cand_w, np.float64)
+        mt = as_c(mate, np.uint32)
+        if len(co) != self.S + 1 or len(ch) != int(co[-1]) or len(cw) != len(ch):
+            raise ValueError("strain_fragments: cand_off needs S + 1 entries and cand_hap / cand_w cand_off[-1] each")
+        if self.R is None or len(mt) != self.R:
+            raise ValueError("strain_fragments: mate needs one entry per resident read")
+        cs = _ffi.ReadStrainSet(self.S, co.ctypes.data, ch.ctypes.data if len(ch) else None, cw.ctypes.data if len(cw) else None)
+        hap = np.zeros((len(ch), 4, 3), dtype=np.uint64)
+        species = np.zeros((self.S, _ffi.FRAGMENT_CLASSES, 3), dtype=np.uint64)
+        status = np.zeros(self.S, dtype=np.int32)
+        pair_off = np.zeros(self.S + 1, dtype=np.uint64)
+        k = np.diff(co.astype(np.int64))
+        pair = np.zeros(int((k[k <= 64] ** 2).sum()) if pair_cap is None else int(pair_cap), dtype=np.uint64)
+        n = None
+        if want_n:
+            n = np.full(self.R, -2, dtype=np.int32) if fill is None else as_c(fill, np.int32).copy()
+        q = lambda a: p(a) if a is not None and a.size else None
+        self._check(self.lib.pantax_hip_strain_fragments(self.ctx, self.db, self.reads, C.byref(cs), q(mt), q(hap), q(species), q(status), p(pair_off),
+                                                         len(pair), q(pair), q(n)))
+        return hap, species, status, pair_off, pair, n
+
     def strain_mosaic(self, cand_off, cand_hap, cand_w, junction_cap=None):
         """Mosaic reads (pantax_hip_strain_mosaic) of the resident reads, binned against the resident db: every counted read of a species of 1 .. 64
         candidates cut into the fewest stretches that each fit one candidate.  The candidate set of read_strains -> (species uint64 [S, 6, 3]: counted /
@@ -866,7 +910,7 @@ class Engine:
                 strain_segments_file=None, strain_segments_min=0, strain_segments_bridge=None, strain_segments_peak=0,
                 strain_mosaic_file=None, strain_mosaic_top=0, strain_rescue_file=None, strain_rescue_top=0,
                 strain_links_file=None, strain_links_top=0,
-                strain_rarefy_file=None, strain_rarefy_levels=0, strain_rarefy_replicates=0, strain_rarefy_seed=42):
+                strain_rarefy_file=None, strain_rarefy_levels=0, strain_rarefy_replicates=0, strain_rarefy_seed=42, strain_fragments_file=None):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -889,7 +933,8 @@ class Engine:
         strain_rescue_file: path of the read rescue report (--strain-rescue; one rank only), strain_rescue_top the candidates it prints per species (0: 5).
         strain_links_file: path of the link support report (--strain-links; one rank only), strain_links_top the breaks it prints per strain (0: 10).
         strain_rarefy_file: path of the rarefaction report (--strain-rarefy; one rank only), strain_rarefy_levels the thinned levels 1/2 .. 2^-N (0: 5; at
-        most 16), strain_rarefy_replicates the replicates per level (0: 5), strain_rarefy_seed the seed of the thinning rule."""
+        most 16), strain_rarefy_replicates the replicates per level (0: 5), strain_rarefy_seed the seed of the thinning rule.
+        strain_fragments_file: path of the fragment support report (--strain-fragments; one rank only)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -932,7 +977,7 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None and strain_links_file is None and strain_rarefy_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None and strain_links_file is None and strain_rarefy_file is None and strain_fragments_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
@@ -947,7 +992,8 @@ class Engine:
                                   strain_rescue_file=enc(strain_rescue_file), strain_rescue_top=int(strain_rescue_top),
                                   strain_links_file=enc(strain_links_file), strain_links_top=int(strain_links_top),
                                   strain_rarefy_file=enc(strain_rarefy_file), strain_rarefy_levels=int(strain_rarefy_levels),
-                                  strain_rarefy_replicates=int(strain_rarefy_replicates), strain_rarefy_seed=int(strain_rarefy_seed))
+                                  strain_rarefy_replicates=int(strain_rarefy_replicates), strain_rarefy_seed=int(strain_rarefy_seed),
+                                  strain_fragments_file=enc(strain_fragments_file))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -1291,6 +1337,18 @@ def rescue_rank(cand_hap, cand_out, top=0):
     if rc != 0:
         raise ValueError("rescue_rank: refused (%d)" % rc)
     return out[:n.value].copy()
+
+
+def fragment_key(id_bytes):
+    """pantax_hip_fragment_key: (key, tag) of a read id -- an id that ends in "/1" or "/2" behind a stem of at least one byte has the tag 1 or 2 and the
+    id hash of the stem as its key; every other id has the tag 0 and its own id hash.  Host only: no Engine is needed."""
+    b = bytes(id_bytes)
+    key = C.c_uint64(0)
+    tag = C.c_uint8(0)
+    rc = _ffi.load().pantax_hip_fragment_key(b, len(b), C.byref(key), C.byref(tag))
+    if rc != 0:
+        raise ValueError("fragment_key: refused (%d)" % rc)
+    return int(key.value), int(tag.value)
 
 
 def rarefy_depth(seed, replicate, read):
