@@ -361,6 +361,47 @@ int pantax_hip_strain_cov_track(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
                                 uint64_t *win_off_out /*[C+1]*/, uint64_t cap /* windows the four arrays hold */,
                                 uint32_t *n_nodes_out, uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out);
 
+/* ---- own-node windows and the replication index of a strain (the --strain-growth report; not a stage of the reference): the strain's OWN depth along
+ * its genome, and the slope of that depth between the deepest and the shallowest part of it (the order-free formulation of iRep: sort the windows by depth,
+ * trim, fit a line to log2 depth against rank).  Selection, walk, o_i, G_h, w_i = o_i / W and n_win(h) as for pantax_hip_strain_cov_track above.  Step i of
+ * selection entry c is OWN when, among the selected haplotypes of its species, only c's haplotype walks v_i (in a species with one selected haplotype every
+ * step is own; a node the haplotype alone walks twice is own at both visits).  Window w carries
+ *     n_own (u32)     = the number of its own steps,        len (u64)       = sum of node_len[v_i] over ALL its steps, as the track has it,
+ *     len_own (u64)   = sum of node_len[v_i] over own steps,  bases_own (u64) = sum of bases_per_node[v_i] over own steps.
+ * Integers only: results are exact and independent of any order.  win_off_out, `cap`, validation and state rules are those of pantax_hip_strain_cov_track
+ * (pantax_hip_cov_track_set is the selection).  The option growth_route=walk (pantax_hip_set_option) takes every species' membership from its selected
+ * walks, as evidence_route=walk does. */
+int pantax_hip_strain_growth(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_cov_track_set *sel,
+                             uint64_t *win_off_out /*[C+1]*/, uint64_t cap /* windows the four arrays hold */,
+                             uint32_t *n_own_out, uint64_t *len_out, uint64_t *len_own_out, uint64_t *bases_own_out);
+/* host helper, no ctx and no GPU: the fit over the n windows of ONE entry.
+ *   1. a window is kept if len_own >= min_own; n_zero = the kept windows with bases_own = 0, which take no further part;
+ *   2. the others are sorted ascending by depth bases_own / len_own as an exact rational (128-bit cross products), ties by window index;
+ *   3. median_depth = the lower median as f64 bases / len; windows outside [median / 8, median x 8] are dropped, n_f remain;
+ *   4. floor(n_f x trim_permille / 1000) windows are trimmed from each end, n_fit remain;
+ *   5. least squares of y_j = log2(bases_j / len_j) against x_j = (t_lo + j + 0.5) / n_f (t_lo = the windows trimmed from the low end), centred two-pass
+ *      sums in ascending j, in f64: slope, intercept, r2; index = 2^slope = the ratio of the fitted depth between the two ends of the sorted range.
+ * status: the first that applies of EMPTY (no window is left to fit: n_fit = 0), FEW_WINDOWS (n_fit < min_windows), LOW_DEPTH (median_depth < min_depth),
+ * FLAT (all y equal: slope 0, r2 0, index 1), else OK.  With EMPTY slope, intercept and r2 are 0 and index is 1; median_depth is 0 when no window
+ * carries bases.  The report's min_windows and min_depth are the two constants below: choices of this contract, not measurements.
+ * PANTAX_HIP_E_INVALID: a null array with n > 0, a null `out`, trim_permille >= 500, min_own = 0. */
+#define PANTAX_HIP_GROWTH_OK 0
+#define PANTAX_HIP_GROWTH_EMPTY 1
+#define PANTAX_HIP_GROWTH_FEW_WINDOWS 2
+#define PANTAX_HIP_GROWTH_LOW_DEPTH 3
+#define PANTAX_HIP_GROWTH_FLAT 4
+#define PANTAX_HIP_GROWTH_MIN_WINDOWS 20
+#define PANTAX_HIP_GROWTH_MIN_DEPTH 5.0
+typedef struct {
+    uint64_t n_kept, n_zero, n_f, n_fit, own_len;   /* own_len = sum of len_own over the kept windows */
+    double median_depth, slope, intercept, r2, index;
+    int32_t status;                                  /* PANTAX_HIP_GROWTH_* */
+    int32_t pad;
+} pantax_hip_growth_fit_result;
+int pantax_hip_growth_fit(uint64_t n, const uint64_t *len_own, const uint64_t *bases_own, uint64_t min_own, uint64_t trim_permille, uint64_t min_windows,
+                          double min_depth, pantax_hip_growth_fit_result *out);
+const char *pantax_hip_growth_status_name(int32_t status);   /* "ok", "empty", "few_windows", "low_depth", "flat"; "?" otherwise */
+
 /* ---- absent and amplified segments along a strain (the --strain-segments report; not a stage of the reference): the exact stretches of the genome of
  * selected haplotypes that the sample does not cover at all, and those far deeper than a given depth, from what pantax_hip_node_coverage leaves on the
  * device.  Walk, o_i and G_h as for the coverage track above.  With min_len >= 1 and one peak_depth[c] <= 2^31 per selection entry c (0: no peak class
@@ -1388,6 +1429,24 @@ typedef struct {
      * columns, strain b in other_*, fraction over the species' discordant fragments.  Same rules as strain_fit_file. */
     const char *strain_fragments_file;
 } pantax_hip_profile_ext11;
+/* ... and once more: pantax_hip_profile_ext11 is closed at strain_fragments_file (a committed host check holds its 208 bytes); the outputs behind it are the
+ * fields of the struct below, which begins with the eleventh version.  A caller fills v11.v10.v9.v8.v7.v6.v5.v4.v3.v2.v1.struct_size =
+ * sizeof(pantax_hip_profile_ext12) and passes &ext12.v11.v10.v9.v8.v7.v6.v5.v4.v3.v2.v1 to pantax_hip_profile_with_ext; a caller with a 16-, 40-, 48-, 64-,
+ * 88-, 120-, 136-, 152-, 168-, 200- or 208-byte struct runs with the fields below off.  A later output is a field appended here. */
+typedef struct {
+    pantax_hip_profile_ext11 v11;   /* v11.v10.v9.v8.v7.v6.v5.v4.v3.v2.v1.struct_size = sizeof(pantax_hip_profile_ext12) */
+    /* --strain-growth: path of the replication index report (pantax_hip_strain_growth over every group of species, right behind the group's strain step
+     * and beside the coverage track, then pantax_hip_growth_fit per row with min_own = max(1, W x strain_growth_min_own_permille / 1000), min_windows =
+     * PANTAX_HIP_GROWTH_MIN_WINDOWS and min_depth = PANTAX_HIP_GROWTH_MIN_DEPTH; NULL, "" or "None" = off).  The selection of a species is its rows of
+     * strain_abundance.txt.  TSV with a header, one row per row of strain_abundance.txt, in its order: species_taxid, strain_taxid, genome_ID, window,
+     * n_windows, n_kept, n_zero, n_fit, own_len, own_fraction (own_len / G_h), median_depth, slope, intercept, r2, index, status, predicted_coverage; f64 in
+     * shortest round-trip digits.  Same rules as strain_coverage_file: world_size > 1 or a sharded ingest with it is PANTAX_HIP_E_INVALID; a run without
+     * a strain step writes nothing and says so on stderr. */
+    const char *strain_growth_file;
+    uint64_t strain_growth_window;             /* W in bases: 0 reads as 5000, and so does a struct that does not hold the field */
+    uint64_t strain_growth_min_own_permille;   /* own bases a window needs, in thousandths of W (1 .. 1000): 0 reads as 500 */
+    uint64_t strain_growth_trim_permille;      /* windows trimmed from each end of the sorted range, in thousandths (below 500): 0 reads as 100 */
+} pantax_hip_profile_ext12;
 
 /* ---- the --db-pairs mode: pairwise strain distinguishability of a db as one table (pantax_hip_db_hap_pairs over every haplotype of the chosen species).
  * Files in, one file out: no GAF, no work directory, no strain step; one rank.  The species are those named in `species`, or by default every species of

@@ -34,6 +34,7 @@ SYMBOLS = [
     "pantax_hip_strain_links", "pantax_hip_link_crossings", "pantax_hip_link_top",
     "pantax_hip_strain_rarefy", "pantax_hip_rarefy_node_bases", "pantax_hip_rarefy_depth",
     "pantax_hip_fragment_key", "pantax_hip_fragment_mates", "pantax_hip_strain_fragments",
+    "pantax_hip_strain_growth", "pantax_hip_growth_fit", "pantax_hip_growth_status_name",
     "pantax_hip_reads_route_pack", "pantax_hip_route_buffer", "pantax_hip_route_free", "pantax_hip_reads_from_routed",
     "pantax_hip_timing_enable", "pantax_hip_timing_filter", "pantax_hip_timing_reset", "pantax_hip_timing_get", "pantax_hip_sync",
 ]
@@ -50,6 +51,8 @@ LINK_HAP_N = 8       # PANTAX_HIP_LINK_HAP_N
 MATE_NONE = 0xFFFFFFFF        # PANTAX_HIP_MATE_NONE
 MATE_AMBIGUOUS = 0xFFFFFFFE   # PANTAX_HIP_MATE_AMBIGUOUS
 FRAGMENT_CLASSES = 9   # PANTAX_HIP_FRAGMENT_CLASSES
+GROWTH_MIN_WINDOWS = 20   # PANTAX_HIP_GROWTH_MIN_WINDOWS
+GROWTH_MIN_DEPTH = 5.0    # PANTAX_HIP_GROWTH_MIN_DEPTH
 DEPTH_BINS = 96   # PANTAX_HIP_DEPTH_BINS
 DEPTH_NONE = 1    # PANTAX_HIP_DEPTH_NONE: pantax_hip_depth_quantile of a histogram without length
 
@@ -160,9 +163,9 @@ class FitSet(C.Structure):
 
 
 class ProfileExt(C.Structure):
-    """pantax_hip_profile_ext11 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
+    """pantax_hip_profile_ext12 laid out flat: the 16-byte pantax_hip_profile_ext (struct_size, strain_fit_file), the fields of pantax_hip_profile_ext2
     behind it (40 bytes), strain_dropout_file (48), the two fields of pantax_hip_profile_ext4 (64), the three of pantax_hip_profile_ext5 (88), the four
-    of pantax_hip_profile_ext6 (120), the two of pantax_hip_profile_ext7 (136), the two of pantax_hip_profile_ext8 (152), the two of pantax_hip_profile_ext9 (168), the four of pantax_hip_profile_ext10 (200) and the one of pantax_hip_profile_ext11 (208); struct_size = ctypes.sizeof(ProfileExt)"""
+    of pantax_hip_profile_ext6 (120), the two of pantax_hip_profile_ext7 (136), the two of pantax_hip_profile_ext8 (152), the two of pantax_hip_profile_ext9 (168), the four of pantax_hip_profile_ext10 (200), the one of pantax_hip_profile_ext11 (208) and the four of pantax_hip_profile_ext12 (240); struct_size = ctypes.sizeof(ProfileExt)"""
     _fields_ = [("struct_size", C.c_uint64), ("strain_fit_file", C.c_char_p), ("strain_bootstrap_file", C.c_char_p),
                 ("strain_bootstrap_replicates", C.c_uint64), ("strain_bootstrap_seed", C.c_uint64), ("strain_dropout_file", C.c_char_p),
                 ("strain_addin_file", C.c_char_p), ("strain_addin_top", C.c_uint64),
@@ -172,7 +175,16 @@ class ProfileExt(C.Structure):
                 ("strain_rescue_file", C.c_char_p), ("strain_rescue_top", C.c_uint64),
                 ("strain_links_file", C.c_char_p), ("strain_links_top", C.c_uint64),
                 ("strain_rarefy_file", C.c_char_p), ("strain_rarefy_levels", C.c_uint64), ("strain_rarefy_replicates", C.c_uint64),
-                ("strain_rarefy_seed", C.c_uint64), ("strain_fragments_file", C.c_char_p)]
+                ("strain_rarefy_seed", C.c_uint64), ("strain_fragments_file", C.c_char_p),
+                ("strain_growth_file", C.c_char_p), ("strain_growth_window", C.c_uint64), ("strain_growth_min_own_permille", C.c_uint64),
+                ("strain_growth_trim_permille", C.c_uint64)]
+
+
+class GrowthFitResult(C.Structure):
+    """pantax_hip_growth_fit_result"""
+    _fields_ = [("n_kept", C.c_uint64), ("n_zero", C.c_uint64), ("n_f", C.c_uint64), ("n_fit", C.c_uint64), ("own_len", C.c_uint64),
+                ("median_depth", C.c_double), ("slope", C.c_double), ("intercept", C.c_double), ("r2", C.c_double), ("index", C.c_double),
+                ("status", C.c_int32), ("pad", C.c_int32)]
 
 
 class RarefySet(C.Structure):
@@ -227,6 +239,13 @@ def load():
         _lib.pantax_hip_strain_cov_track.restype = C.c_int
         _lib.pantax_hip_strain_cov_track.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CovTrackSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]
+        _lib.pantax_hip_strain_growth.restype = C.c_int
+        _lib.pantax_hip_strain_growth.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CovTrackSet), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]
+        _lib.pantax_hip_growth_fit.restype = C.c_int
+        _lib.pantax_hip_growth_fit.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, C.POINTER(GrowthFitResult)]
+        _lib.pantax_hip_growth_status_name.restype = C.c_char_p
+        _lib.pantax_hip_growth_status_name.argtypes = [C.c_int32]
         _lib.pantax_hip_strain_read_support.restype = C.c_int
         _lib.pantax_hip_strain_read_support.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ReadStrainSet), C.c_void_p, C.c_void_p, C.c_void_p,
                                                         C.c_uint64, C.c_void_p]

@@ -106,6 +106,8 @@ void rs_skipped(const RunPlan &p) {
         if (p.rep.ext10_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.ext10_path[i].c_str());
     for (int i = 0; i < N_EXT11_REPORTS; ++i)
         if (p.rep.ext11_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.ext11_path[i].c_str());
+    for (int i = 0; i < N_EXT12_REPORTS; ++i)
+        if (p.rep.ext12_want[i]) std::fprintf(stderr, "[pantax_hip_profile] note: no strain step ran in this call; %s was not written\n", p.rep.ext12_path[i].c_str());
 }
 // ---- a1 + a2/a3, rank-local: ranges, GAF (this rank's byte range when sharded) -> packed reads in HBM, binned against
 // ALL species ranges (ranges-only db), counters on the device

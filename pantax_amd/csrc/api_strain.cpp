@@ -679,6 +679,18 @@ int pantax_hip_strain_cov_track(pantax_hip_ctx *ctx, pantax_hip_db *db, const pa
     return cov_track_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->window, win_off_out, cap, n_nodes_out, len_out, covered_out, bases_out);
 }
 
+int pantax_hip_strain_growth(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_cov_track_set *sel, uint64_t *win_off_out, uint64_t cap,
+                             uint32_t *n_own_out, uint64_t *len_out, uint64_t *len_own_out, uint64_t *bases_own_out) {
+    if (!ctx) return PANTAX_HIP_E_INVALID;
+    if (!db || !sel || !sel->sel_off || !win_off_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_growth: null argument");
+    PTX_ENTER(ctx);
+    PTX_TRY(check_species_count(ctx, db, "strain_growth", sel->n_species));
+    if (sel->window == 0) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_growth: window of 0 bases");
+    PTX_TRY(check_hap_selection(ctx, db, "strain_growth", sel->sel_off, sel->sel_hap));
+    PTX_TRY(check_stage_coverage(ctx, db, "strain_growth"));
+    return growth_launch(ctx, db, sel->sel_off, sel->sel_hap, sel->window, win_off_out, cap, n_own_out, len_out, len_own_out, bases_own_out);
+}
+
 int pantax_hip_strain_segments(pantax_hip_ctx *ctx, pantax_hip_db *db, const pantax_hip_segment_set *sel, uint64_t *seg_off_out, uint64_t cap, uint64_t *hap_len_out,
                                uint64_t *n_runs_out, uint64_t *run_len_out, uint64_t *run_max_out, uint8_t *seg_class_out, uint64_t *seg_step_out,
                                uint32_t *seg_n_steps_out, uint64_t *seg_start_out, uint64_t *seg_len_out, uint64_t *seg_bases_out) {

@@ -86,6 +86,11 @@ static void usage() {
             "                     strain_abundance.txt the fragments it is compatible with, alone, alone only as a pair, and assigned; per species the fragments\n"
             "                     concordant, discordant (each mate fits a reported strain, no common one), half and unexplained, the reads single, multi and\n"
             "                     with their mate elsewhere, and which two strains the discordant fragments sit between (one rank only)\n"
+            "  --strain-growth F   replication index: per row of strain_abundance.txt the slope of the strain's OWN depth (nodes only it walks among the reported\n"
+            "                     strains of its species) over its windows sorted by depth -- n_windows, n_kept, n_zero, n_fit, own_len, own_fraction, median_depth,\n"
+            "                     slope, intercept, r2, index = 2^slope and status (ok, few_windows, low_depth, flat, empty); no origin is located (one rank only)\n"
+            "  --strain-growth-window N   its window in bases (default 5000)     --strain-growth-min-own P   own bases a window needs, in thousandths of the\n"
+            "                     window (default 500)     --strain-growth-trim P   windows trimmed from each end of the sorted range, in thousandths (default 100)\n"
             "  --image-cache 0|1|2  device-ready graph images <db>/species_graph_info/<otu>.hipdb: 1 = use, 2 = use and write\n"
             "  --filter-gaf  first replace the GAF by its best alignment per read (long reads; alignment.rs:171-175, gaf_filter.rs)\n"
             "  --filter-only <in.gaf> [<out.gaf>]   just write <stem>_filtered.gaf (or <out.gaf>) and exit\n"
@@ -111,8 +116,9 @@ int main(int argc, char **argv) {
     c.zip = "serialize"; c.world_size = 1;
     bool long_read = false, filter_gaf = false;
     const char *filter_in = nullptr, *filter_out = nullptr;
-    pantax_hip_profile_ext11 ext11;   // the outputs added behind the config's last field
-    memset(&ext11, 0, sizeof(ext11));
+    pantax_hip_profile_ext12 ext12;   // the outputs added behind the config's last field
+    memset(&ext12, 0, sizeof(ext12));
+    pantax_hip_profile_ext11 &ext11 = ext12.v11;
     pantax_hip_profile_ext10 &ext10 = ext11.v10;
     pantax_hip_profile_ext9 &ext9 = ext10.v9;
     pantax_hip_profile_ext8 &ext8 = ext9.v8;
@@ -122,7 +128,7 @@ int main(int argc, char **argv) {
     pantax_hip_profile_ext4 &ext4 = ext5.v4;
     pantax_hip_profile_ext3 &ext3 = ext4.v3;
     pantax_hip_profile_ext2 &ext = ext3.v2;
-    ext.v1.struct_size = sizeof(ext11);
+    ext.v1.struct_size = sizeof(ext12);
     ext.strain_bootstrap_seed = 42;
     ext10.strain_rarefy_seed = 42;
     pantax_hip_db_pairs_config pairs;
@@ -211,6 +217,10 @@ int main(int argc, char **argv) {
         else if (a == "--strain-rarefy-replicates") ext10.strain_rarefy_replicates = strtoull(next(), nullptr, 10);
         else if (a == "--strain-rarefy-seed") ext10.strain_rarefy_seed = strtoull(next(), nullptr, 10);
         else if (a == "--strain-fragments") ext11.strain_fragments_file = next();
+        else if (a == "--strain-growth") ext12.strain_growth_file = next();
+        else if (a == "--strain-growth-window") ext12.strain_growth_window = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-growth-min-own") ext12.strain_growth_min_own_permille = strtoull(next(), nullptr, 10);
+        else if (a == "--strain-growth-trim") ext12.strain_growth_trim_permille = strtoull(next(), nullptr, 10);
         else if (a == "--gfa") c.zip = nullptr;
         else if (a == "--zip") c.zip = next();        // serialize | lz | zstd (main.rs: --zip)
         else if (a == "--round") c.full = 0;

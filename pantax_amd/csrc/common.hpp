@@ -147,7 +147,7 @@ struct CtxConfig {
     std::string row_sort;            // "radix" / "nodes"
     std::string objective;           // "nodes": the LP objective summed over the nodes
     // "walk": the strain report takes the membership of every species from the chosen walks (the compact masks, route 2 of member_plan.hpp), not from the node -> haplotype words
-    std::string read_strain_route, evidence_route, depth_route, near_miss_route, hap_pairs_route, fit_route, bootstrap_route, dropout_route, addin_route, rarefy_route;
+    std::string read_strain_route, evidence_route, depth_route, near_miss_route, hap_pairs_route, fit_route, bootstrap_route, dropout_route, addin_route, rarefy_route, growth_route;
     uint64_t rarefy_levels_max = 0;  // levels of a replicate one pass of pantax_hip_strain_rarefy over the reads serves (0: from the free device memory, rarefy_plan.hpp; tests lower it to cut a replicate into passes)
     uint64_t bootstrap_rows_max = 0; // expanded rows of the bootstrap replicates in flight on the device (0: from the free device memory, bootstrap_plan.hpp; tests lower it to cut the replicates into chunks)
     uint64_t dropout_patterns_max = 0; // replicated patterns of the leave-one-out rounds in flight on the device (0: from the free device memory, dropout_plan.hpp; tests lower it to cut the rounds into chunks)
@@ -759,6 +759,10 @@ int near_miss_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
 // windows fit `cap`
 int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, uint32_t *n_nodes_out,
                      uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out);
+// stage_growth.hip (pantax_hip_strain_growth): selection validated by the caller; win_off_out [C+1] is always written, the four arrays only when the
+// windows fit `cap`
+int growth_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, uint32_t *n_own_out,
+                  uint64_t *len_out, uint64_t *len_own_out, uint64_t *bases_own_out);
 // stage_segments.hip (pantax_hip_strain_segments): selection, peak depths and min_len validated by the caller; seg_off_out [C+1] and the four summaries are
 // always written, the six segment arrays only when the segments fit `cap`
 int segments_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, const uint64_t *peak_depth, uint64_t min_len, uint64_t *seg_off_out,

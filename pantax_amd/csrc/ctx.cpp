@@ -87,7 +87,7 @@ struct OptDesc { const char *name; OptKind kind; size_t off; };
 const OptDesc OPTIONS[] = {
     OPT("hip_trace", O_BOOL, trace), OPT("stage_threads", O_INT, stage_threads), OPT("stage_ch_mb", O_INT, stage_ch_mb), OPT("stream_prio", O_BOOL, stream_prio), OPT("numa_bind", O_BOOL, numa_bind), OPT("dev_cache_gb", O_INT, dev_cache_gb),
     OPT("gaf_piece_bytes", O_U64, gaf_piece_bytes), OPT("db_path_steps_max", O_U64, db_path_steps_max), OPT("db_groups", O_INT, db_groups), OPT("trio_path", O_STR, trio_path), OPT("trio_rows", O_STR, trio_rows), OPT("trio_two_pass", O_BOOL, trio_two_pass), OPT("uniq_hash", O_INT, uniq_hash),
-    OPT("mask", O_STR, mask), OPT("row_sort", O_STR, row_sort), OPT("objective", O_STR, objective), OPT("read_strain_route", O_STR, read_strain_route), OPT("evidence_route", O_STR, evidence_route), OPT("depth_route", O_STR, depth_route), OPT("depth_grid", O_INT, depth_grid), OPT("near_miss_route", O_STR, near_miss_route), OPT("near_miss_words", O_INT, near_miss_words), OPT("hap_pairs_route", O_STR, hap_pairs_route), OPT("fit_route", O_STR, fit_route), OPT("bootstrap_route", O_STR, bootstrap_route), OPT("bootstrap_rows_max", O_U64, bootstrap_rows_max), OPT("dropout_route", O_STR, dropout_route), OPT("dropout_patterns_max", O_U64, dropout_patterns_max), OPT("dropout_yardstick", O_BOOL, dropout_yardstick), OPT("addin_route", O_STR, addin_route), OPT("addin_patterns_max", O_U64, addin_patterns_max), OPT("addin_yardstick", O_BOOL, addin_yardstick), OPT("rarefy_route", O_STR, rarefy_route), OPT("rarefy_levels_max", O_U64, rarefy_levels_max), OPT("read_class_slots", O_U64, read_class_slots), OPT("read_em_lds_classes", O_INT, read_em_lds_classes), OPT("hap_pairs_chunk", O_INT, hap_pairs_chunk),
+    OPT("mask", O_STR, mask), OPT("row_sort", O_STR, row_sort), OPT("objective", O_STR, objective), OPT("read_strain_route", O_STR, read_strain_route), OPT("evidence_route", O_STR, evidence_route), OPT("depth_route", O_STR, depth_route), OPT("depth_grid", O_INT, depth_grid), OPT("near_miss_route", O_STR, near_miss_route), OPT("near_miss_words", O_INT, near_miss_words), OPT("hap_pairs_route", O_STR, hap_pairs_route), OPT("fit_route", O_STR, fit_route), OPT("bootstrap_route", O_STR, bootstrap_route), OPT("bootstrap_rows_max", O_U64, bootstrap_rows_max), OPT("dropout_route", O_STR, dropout_route), OPT("dropout_patterns_max", O_U64, dropout_patterns_max), OPT("dropout_yardstick", O_BOOL, dropout_yardstick), OPT("addin_route", O_STR, addin_route), OPT("addin_patterns_max", O_U64, addin_patterns_max), OPT("addin_yardstick", O_BOOL, addin_yardstick), OPT("rarefy_route", O_STR, rarefy_route), OPT("growth_route", O_STR, growth_route), OPT("rarefy_levels_max", O_U64, rarefy_levels_max), OPT("read_class_slots", O_U64, read_class_slots), OPT("read_em_lds_classes", O_INT, read_em_lds_classes), OPT("hap_pairs_chunk", O_INT, hap_pairs_chunk),
     OPT("cov_general", O_BOOL, cov_general), OPT("cov_long", O_STR, cov_long), OPT("covl_shape", O_INT, covl_shape), OPT("cov_count", O_BOOL, cov_count), OPT("cov_self_clean", O_BOOL, cov_readers_clean), OPT("cov_clean_async", O_INT, cov_clean_async), OPT("cov_arena_verify", O_BOOL, cov_arena_verify), OPT("ncs_no_prefix", O_BOOL, ncs_no_prefix), OPT("ncs_prefix_min", O_INT, ncs_prefix_min), OPT("walk_sum_in_bin", O_BOOL, walk_sum_in_bin), OPT("cov_item_groups", O_INT, cov_item_groups), OPT("tv_u", O_INT, tv_u), OPT("tv_rounds", O_INT, tv_rounds), OPT("tf_u", O_INT, tf_u), OPT("tf_rounds", O_INT, tf_rounds),
     OPT("rows_u", O_INT, rows_u), OPT("tb_slots", O_INT, tb_slots), OPT("trio_xcd", O_INT, trio_xcd), OPT("cov_shape", O_INT, cov_shape),
     OPT("covf_shape", O_INT, covf_shape), OPT("cov_spec", O_STR, cov_spec), OPT("cov_xcd", O_INT, cov_xcd), OPT("group_bucket_bits", O_INT, group_bucket_bits), OPT("tv_ablate", O_U32, tv_ablate),

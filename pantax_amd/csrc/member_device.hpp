@@ -9,8 +9,8 @@
 namespace ptx {
 
 // Route 2: node membership in chosen walks as a compact arena -- member_words(K) words per node of a species over its K chosen haplotypes only (bit k = the
-// k-th of them), filled by read_strain_mask_kernel (walk_masks.hip).  Its seven users: read_strains_launch and read_support_launch (through rs_table_build),
-// evidence_launch, depth_launch, near_miss_launch (over Sel ++ Cand), hap_pairs_launch, fit_launch.  The object owns the device buffers: it outlives the kernels that read d_mask.
+// k-th of them), filled by read_strain_mask_kernel (walk_masks.hip).  Its eight users: read_strains_launch and read_support_launch (through rs_table_build),
+// evidence_launch, depth_launch, near_miss_launch (over Sel ++ Cand), hap_pairs_launch, fit_launch, growth_launch.  The object owns the device buffers: it outlives the kernels that read d_mask.
 constexpr uint64_t WALK_MASK_TILE = 4096;   // walk positions per tile of the mask pass (one wave)
 struct WalkMaskTile { uint64_t p0, p1, word0; uint32_t nw, k; };   // walk positions [p0, p1) of chosen walk k; its words start at word0 (+ local node * nw)
 struct WalkMasks {

@@ -1,10 +1,10 @@
 // member_plan.hpp -- "which of the chosen haplotypes of this species walk node v?", the question of the six strain reports (read strains, read support,
-// node evidence, depth, near miss, model fit) and of the db's pair sums (hap pairs: seven users), decided once on the host as pure functions of plain values:
+// node evidence, depth, near miss, model fit), of the db's pair sums (hap pairs) and of the own-node windows of the replication index (growth: eight users), decided once on the host as pure functions of plain values:
 //   route 0 -- nothing chosen;
 //   route 1 -- a species of <= 64 haplotypes whose node -> haplotype words were built at upload (Db::d_node_haps), the call's *_route option not "walk":
 //              word(v) = node_haps[v] & bits, bit = haplotype index; no array of its own;
 //   route 2 -- every other species: ceil(K / 64) words per node over the K chosen haplotypes only, bit = position in the chosen list (WalkMasks, member_device.hpp).
-// The launchers of the seven users follow it; nothing else decodes a *_route option, spells the route predicate or sizes a node's words.  Standard
+// The launchers of the eight users follow it; nothing else decodes a *_route option, spells the route predicate or sizes a node's words.  Standard
 // headers only: tests/native/member_plan_check.cpp compiles this with the host compiler alone; MemberRow is also what the kernels read.
 #pragma once
 #include <cstdint>
@@ -24,7 +24,7 @@ struct MemberRow {
     uint32_t K;                // chosen haplotypes
 };
 template <class T> constexpr T member_words(T K) { return (K + 63) / 64; }   // words that hold K bits
-// route 1 is open: `route_opt` is the call's read_strain_route / evidence_route / depth_route / near_miss_route / hap_pairs_route / fit_route (any value but "walk":
+// route 1 is open: `route_opt` is the call's read_strain_route / evidence_route / depth_route / near_miss_route / hap_pairs_route / fit_route / growth_route (any value but "walk":
 // the default)
 bool member_by_node(bool nh_built, const std::string &route_opt);
 unsigned long long member_bits(const uint32_t *haps, uint64_t K);   // bit haps[k] for every k (haplotype indices < 64)

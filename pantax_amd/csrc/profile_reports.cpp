@@ -2,7 +2,7 @@
 // strain_abundance.txt are selected once (GroupSel) and every running report takes from the device what it needs; behind the tables every running report
 // writes its file.  begin, collect_group and write at the end are the three places that name the reports.  The pair evidence report
 // (PAIR_REPORTS of report_plan.hpp) is about pairs of rows and is collected and written the same way; so are the model fit report, the bootstrap report, the leave-one-out
-// report, the add-one report, the read class report, the segment report, the mosaic read report, the read rescue report, the link support report, the rarefaction report and the fragment support report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT11_REPORTS).
+// report, the add-one report, the read class report, the segment report, the mosaic read report, the read rescue report, the link support report, the rarefaction report, the fragment support report and the replication index report, whose files are named in the seam's sized extension (EXT_REPORTS .. EXT12_REPORTS).
 #include <algorithm>
 #include <cmath>
 #include <fstream>
@@ -75,6 +75,21 @@ int group_cov_track(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const
     if (n) PTX_TRY(pantax_hip_strain_cov_track(run.ctx, db, &set, w_off.data(), n, ct.n_nodes.data() + at, ct.len.data() + at, ct.covered.data() + at, ct.bases.data() + at));
     for (size_t e = 0; e < g.hap.size(); ++e) ct.win_off.push_back(at + w_off[e + 1]);
     run.lap("  strain coverage track");
+    return 0;
+}
+// --strain-growth, beside the coverage track and on the same rows: the own-node windows of the group's rows (the fit is the writer's)
+int group_growth(Run &run, pantax_hip_db *db, uint32_t k0, uint32_t k1, const GroupSel &g, ShardResult &sh) {
+    auto &gr = sh.rep.gr;
+    const pantax_hip_cov_track_set set{k1 - k0, g.off.data(), g.hap.data(), run.p.rep.gr_window};
+    std::vector<uint64_t> w_off(g.hap.size() + 1, 0);
+    const int rc_size = pantax_hip_strain_growth(run.ctx, db, &set, w_off.data(), 0, nullptr, nullptr, nullptr, nullptr);   // sizes: E_LIMIT unless there is no window
+    if (rc_size != 0 && rc_size != PANTAX_HIP_E_LIMIT) return rc_size;
+    const uint64_t n = w_off[g.hap.size()], at = gr.len.size();
+    std::vector<uint32_t> n_own(n);   // (the report prints no step counts)
+    gr.len.resize(at + n); gr.len_own.resize(at + n); gr.bases_own.resize(at + n);
+    if (n) PTX_TRY(pantax_hip_strain_growth(run.ctx, db, &set, w_off.data(), n, n_own.data(), gr.len.data() + at, gr.len_own.data() + at, gr.bases_own.data() + at));
+    for (size_t e = 0; e < g.hap.size(); ++e) gr.win_off.push_back(at + w_off[e + 1]);
+    run.lap("  strain growth");
     return 0;
 }
 // --strain-segments, beside the coverage track and on the same rows: peak_depth = max(2, ceil(F x second_sol)) clamped at 2^31 (0 with peaks off); the device
@@ -607,6 +622,30 @@ struct Writer {
                     f << head << '\t' << start << '\t' << end << '\t' << ct.n_nodes[i] << '\t' << ct.len[i] << '\t' << ct.covered[i] << '\t' << ct.bases[i] << '\t'
                       << fmt_f64((double)ct.bases[i] / (double)ct.len[i]) << '\t' << fmt_f64((double)ct.covered[i] / (double)ct.len[i]) << '\n';
                 }
+            }
+            return 0;
+        });
+    }
+    // --strain-growth: one row per row of strain_abundance.txt, in its order: pantax_hip_growth_fit over the row's own-node windows
+    int growth() const {
+        const auto &gr = rep.gr;
+        const ReportPlan &plan = run.p.rep;
+        const uint64_t W = plan.gr_window;
+        const uint64_t min_own = std::max<uint64_t>(1, (uint64_t)((unsigned __int128)W * plan.gr_min_own / 1000));
+        return file(plan.ext12_path[X12REP_GROWTH],
+                    "species_taxid\tstrain_taxid\tgenome_ID\twindow\tn_windows\tn_kept\tn_zero\tn_fit\town_len\town_fraction\tmedian_depth\tslope\tintercept\tr2\tindex\tstatus\tpredicted_coverage\n",
+                    "strain growth report", [&](std::ofstream &f) {
+            for (const TrackRow &r : rows) {
+                int64_t e; PTX_TRY(entry_of(r, "growth", &e));
+                const uint64_t w0 = gr.win_off[e], n = gr.win_off[e + 1] - w0;
+                uint64_t G = 0;
+                for (uint64_t i = w0; i < w0 + n; ++i) G += gr.len[i];
+                pantax_hip_growth_fit_result q;
+                if (pantax_hip_growth_fit(n, gr.len_own.data() + w0, gr.bases_own.data() + w0, min_own, plan.gr_trim, PANTAX_HIP_GROWTH_MIN_WINDOWS, PANTAX_HIP_GROWTH_MIN_DEPTH, &q) != 0)
+                    return fail(run.ctx, PANTAX_HIP_E_STATE, "profile: the growth fit refused its parameters");
+                f << strain_head(r) << '\t' << W << '\t' << n << '\t' << q.n_kept << '\t' << q.n_zero << '\t' << q.n_fit << '\t' << q.own_len << '\t'
+                  << (G ? fmt_f64((double)q.own_len / (double)G) : std::string("-")) << '\t' << fmt_f64(q.median_depth) << '\t' << fmt_f64(q.slope) << '\t' << fmt_f64(q.intercept) << '\t'
+                  << fmt_f64(q.r2) << '\t' << fmt_f64(q.index) << '\t' << pantax_hip_growth_status_name(q.status) << '\t' << fmt_f64(sh.met[r.hap].second_sol) << '\n';
             }
             return 0;
         });
@@ -1331,6 +1370,7 @@ int collect_group(Run &run, const Ingest &in, const Selection &sn, pantax_hip_db
     if (plan.run[REP_READ_STRAINS]) PTX_TRY(group_read_strains(run, in, db, k0, k1, g, sh));
     if (plan.run[REP_COVERAGE]) PTX_TRY(group_cov_track(run, db, k0, k1, g, sh));
     if (plan.ext6_run[X6REP_SEGMENTS]) PTX_TRY(group_segments(run, db, k0, k1, g, sh));
+    if (plan.ext12_run[X12REP_GROWTH]) PTX_TRY(group_growth(run, db, k0, k1, g, sh));
     if (plan.run[REP_EVIDENCE]) PTX_TRY(group_node_sums(run, db, k0, k1, g, pantax_hip_strain_evidence, 2 * EVIDENCE_N, 3 * EVIDENCE_N, sh.rep.ev, "  strain evidence"));
     if (plan.ext_run[XREP_FIT]) PTX_TRY(group_fit(run, db, k0, k1, g, sh));
     if (plan.ext2_run[X2REP_BOOTSTRAP]) PTX_TRY(group_bootstrap(run, in, sn, db, k0, k1, g, sh));
@@ -1372,6 +1412,7 @@ int write(Run &run, const Ingest &in, const Selection &sn, const ShardResult &sh
     if (plan.ext9_run[X9REP_LINKS]) PTX_TRY(w.links());
     if (plan.ext10_run[X10REP_RAREFY]) PTX_TRY(w.rarefy());
     if (plan.ext11_run[X11REP_FRAGMENTS]) PTX_TRY(w.fragments());
+    if (plan.ext12_run[X12REP_GROWTH]) PTX_TRY(w.growth());
     return 0;
 }
 }  // namespace reports

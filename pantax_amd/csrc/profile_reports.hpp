@@ -1,6 +1,6 @@
 // profile_reports.hpp -- what the per-strain reports (report_plan.hpp) do in the file seam besides being planned: the data they collect group by group
 // while a group's coverage result is resident (ReportData, a member of ShardResult) and the three places the seam calls them from.  A new report is a field
-// of pantax_hip_profile_ext11 with its row of EXT11_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS, EXT5_REPORTS, EXT6_REPORTS, EXT7_REPORTS, EXT8_REPORTS, EXT9_REPORTS and EXT10_REPORTS are closed: the structs they point into keep their size), a sub-struct
+// of pantax_hip_profile_ext12 with its row of EXT12_REPORTS (REPORTS, PAIR_REPORTS, EXT_REPORTS, EXT2_REPORTS, EXT3_REPORTS, EXT4_REPORTS, EXT5_REPORTS, EXT6_REPORTS, EXT7_REPORTS, EXT8_REPORTS, EXT9_REPORTS, EXT10_REPORTS and EXT11_REPORTS are closed: the structs they point into keep their size), a sub-struct
 // here, and a line in each of begin / collect_group / write (profile_reports.cpp).
 #pragma once
 #include <cstdint>
@@ -70,6 +70,8 @@ struct ReportData {
     // assigned}, species[27k ..) = the nine classes and status[k] as pantax_hip_strain_fragments writes them; a species of K[k] = 1..64 rows owns the K x K
     // block of discordant fragments pair[pair_off[k] ..) over its entries in ascending order
     struct { bool have_mate = false; std::vector<uint32_t> mate, K; std::vector<uint64_t> hap, species, pair, pair_off; std::vector<int32_t> status; } fr;
+    // --strain-growth: entry e owns the windows [win_off[e], win_off[e + 1]) of the three arrays (len: every step, for G_h; len_own and bases_own: own steps)
+    struct { std::vector<uint64_t> win_off{0}, len, len_own, bases_own; } gr;
     // --strain-near-miss: species[12k ..) = {orphan, claimed, contested}; the printed candidates rows[row_off[k] .. row_off[k + 1]) in rank order: the
     // haplotype ([hap_names]) and q = {novel, exclusive, all} x {n_nodes, len, covered, bases}
     struct NearMissRow { uint64_t hap; uint64_t q[12]; };

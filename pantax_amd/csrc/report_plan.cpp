@@ -29,7 +29,7 @@ template <class Ext, class T> bool ext_value(const pantax_hip_profile_ext *ext, 
     std::memcpy(&value, reinterpret_cast<const char *>(ext) + at, sizeof(value));
     return true;
 }
-// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2 / _ext3 / _ext4 / _ext5 / _ext6 / _ext7 / _ext8 / _ext9 / _ext10 / _ext11, which begin with it)
+// (Ext: pantax_hip_profile_ext, or pantax_hip_profile_ext2 / _ext3 / _ext4 / _ext5 / _ext6 / _ext7 / _ext8 / _ext9 / _ext10 / _ext11 / _ext12, which begin with it)
 template <class Ext> const char *ext_field(const pantax_hip_profile_ext *ext, const char *Ext::*field) {
     const char *value = nullptr;
     return ext_value(ext, field, value) ? value : nullptr;
@@ -69,6 +69,7 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
     for (int i = 0; i < N_EXT9_REPORTS; ++i) { plan.ext9_path[i].clear(); plan.ext9_want[i] = plan.ext9_run[i] = false; }
     for (int i = 0; i < N_EXT10_REPORTS; ++i) { plan.ext10_path[i].clear(); plan.ext10_want[i] = plan.ext10_run[i] = false; }
     for (int i = 0; i < N_EXT11_REPORTS; ++i) { plan.ext11_path[i].clear(); plan.ext11_want[i] = plan.ext11_run[i] = false; }
+    for (int i = 0; i < N_EXT12_REPORTS; ++i) { plan.ext12_path[i].clear(); plan.ext12_want[i] = plan.ext12_run[i] = false; }
     if (ext && (ext->struct_size < 8 || ext->struct_size % 8 != 0)) {
         err = "profile: pantax_hip_profile_ext.struct_size " + std::to_string((unsigned long long)ext->struct_size) + " (a multiple of 8, at least 8)";
         return false;
@@ -95,9 +96,12 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
         if (!plan_path(EXT10_REPORTS[i], ext_field(ext, EXT10_REPORTS[i].field), W, sharded, plan.ext10_path[i], plan.ext10_want[i], err)) return false;
     for (int i = 0; i < N_EXT11_REPORTS; ++i)
         if (!plan_path(EXT11_REPORTS[i], ext_field(ext, EXT11_REPORTS[i].field), W, sharded, plan.ext11_path[i], plan.ext11_want[i], err)) return false;
+    for (int i = 0; i < N_EXT12_REPORTS; ++i)
+        if (!plan_path(EXT12_REPORTS[i], ext_field(ext, EXT12_REPORTS[i].field), W, sharded, plan.ext12_path[i], plan.ext12_want[i], err)) return false;
     plan.bs_replicates = 100; plan.bs_seed = 42; plan.ai_top = 5; plan.em_classes = 10; plan.em_iterations = 1000;
     plan.sg_min = 1000; plan.sg_bridge = 100; plan.sg_peak = 10; plan.mo_top = 10; plan.rs_top = 5; plan.lk_top = 10;
     plan.rf_levels = 5; plan.rf_replicates = 5; plan.rf_seed = 42;
+    plan.gr_window = 5000; plan.gr_min_own = 500; plan.gr_trim = 100;
     if (plan.ext2_want[X2REP_BOOTSTRAP]) {
         uint64_t n = 0, seed = 42;
         if (ext_value(ext, &pantax_hip_profile_ext2::strain_bootstrap_replicates, n) && n > 0xFFFFFFFEull) {
@@ -148,6 +152,20 @@ bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, Re
         if (r) plan.rf_replicates = (uint32_t)r;
         if (ext_value(ext, &pantax_hip_profile_ext10::strain_rarefy_seed, seed)) plan.rf_seed = seed;
     }
+    if (plan.ext12_want[X12REP_GROWTH]) {
+        uint64_t w = 0, own = 0, trim = 0;
+        if (ext_value(ext, &pantax_hip_profile_ext12::strain_growth_window, w) && w) plan.gr_window = w;
+        if (ext_value(ext, &pantax_hip_profile_ext12::strain_growth_min_own_permille, own) && own > 1000) {
+            err = "profile: strain_growth_min_own_permille " + std::to_string((unsigned long long)own) + " (at most 1000)";
+            return false;
+        }
+        if (own) plan.gr_min_own = own;
+        if (ext_value(ext, &pantax_hip_profile_ext12::strain_growth_trim_permille, trim) && trim >= 500) {
+            err = "profile: strain_growth_trim_permille " + std::to_string((unsigned long long)trim) + " (below 500)";
+            return false;
+        }
+        if (trim) plan.gr_trim = trim;
+    }
     return true;
 }
 
@@ -165,6 +183,7 @@ void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_d
     for (int i = 0; i < N_EXT9_REPORTS; ++i) plan.ext9_run[i] = runs(plan.ext9_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT10_REPORTS; ++i) plan.ext10_run[i] = runs(plan.ext10_want[i], strain, full_path, strain_done);
     for (int i = 0; i < N_EXT11_REPORTS; ++i) plan.ext11_run[i] = runs(plan.ext11_want[i], strain, full_path, strain_done);
+    for (int i = 0; i < N_EXT12_REPORTS; ++i) plan.ext12_run[i] = runs(plan.ext12_want[i], strain, full_path, strain_done);
 }
 
 }  // namespace ptx

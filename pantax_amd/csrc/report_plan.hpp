@@ -1,7 +1,7 @@
 // report_plan.hpp -- the per-strain reports of the file seam (pantax_hip_profile) as one table: which config field switches a report on, what its refusal
 // calls it, whether it follows the rows of strain_abundance.txt.  plan_reports / resume_reports decide from plain values which reports this call wants
 // and runs; nothing else in the seam spells a report's field name or repeats the rule.  pantax_hip.h and standard headers only:
-// tests/native/report_plan_check.cpp, pair_report_plan_check.cpp, fit_report_plan_check.cpp, bootstrap_plan_check.cpp, dropout_plan_check.cpp, addin_plan_check.cpp, read_em_check.cpp, segments_check.cpp, mosaic_check.cpp, rescue_check.cpp, links_check.cpp, rarefy_check.cpp and fragments_plan_check.cpp compile this with the host compiler alone.
+// tests/native/report_plan_check.cpp, pair_report_plan_check.cpp, fit_report_plan_check.cpp, bootstrap_plan_check.cpp, dropout_plan_check.cpp, addin_plan_check.cpp, read_em_check.cpp, segments_check.cpp, mosaic_check.cpp, rescue_check.cpp, links_check.cpp, rarefy_check.cpp, fragments_plan_check.cpp and growth_plan_check.cpp compile this with the host compiler alone.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -175,8 +175,21 @@ struct Ext11ReportRow {
 constexpr Ext11ReportRow EXT11_REPORTS[N_EXT11_REPORTS] = {
     {&pantax_hip_profile_ext11::strain_fragments_file, "strain_fragments_file", "fragment support report", true},
 };
+// ... and once more: pantax_hip_profile_ext11 is closed at strain_fragments_file (a committed host check pins its 208 bytes and N_EXT11_REPORTS = 1); the reports
+// named behind it are fields of pantax_hip_profile_ext12, which begins with the eleventh version, and rows of this table, checked after EXT11_REPORTS.  A later
+// report is a field appended to pantax_hip_profile_ext12 and a row here.
+enum Ext12ReportId { X12REP_GROWTH, N_EXT12_REPORTS };
+struct Ext12ReportRow {
+    const char *pantax_hip_profile_ext12::*field;
+    const char *name;
+    const char *what;
+    bool rows;
+};
+constexpr Ext12ReportRow EXT12_REPORTS[N_EXT12_REPORTS] = {
+    {&pantax_hip_profile_ext12::strain_growth_file, "strain_growth_file", "replication index report", true},
+};
 struct ReportPlan {
-    std::string path[N_REPORTS], pair_path[N_PAIR_REPORTS], ext_path[N_EXT_REPORTS], ext2_path[N_EXT2_REPORTS], ext3_path[N_EXT3_REPORTS], ext4_path[N_EXT4_REPORTS], ext5_path[N_EXT5_REPORTS], ext6_path[N_EXT6_REPORTS], ext7_path[N_EXT7_REPORTS], ext8_path[N_EXT8_REPORTS], ext9_path[N_EXT9_REPORTS], ext10_path[N_EXT10_REPORTS], ext11_path[N_EXT11_REPORTS];
+    std::string path[N_REPORTS], pair_path[N_PAIR_REPORTS], ext_path[N_EXT_REPORTS], ext2_path[N_EXT2_REPORTS], ext3_path[N_EXT3_REPORTS], ext4_path[N_EXT4_REPORTS], ext5_path[N_EXT5_REPORTS], ext6_path[N_EXT6_REPORTS], ext7_path[N_EXT7_REPORTS], ext8_path[N_EXT8_REPORTS], ext9_path[N_EXT9_REPORTS], ext10_path[N_EXT10_REPORTS], ext11_path[N_EXT11_REPORTS], ext12_path[N_EXT12_REPORTS];
     bool want[N_REPORTS] = {}, run[N_REPORTS] = {};   // want: the caller named a file; run: this call runs a strain step and writes it
     bool pair_want[N_PAIR_REPORTS] = {}, pair_run[N_PAIR_REPORTS] = {};
     bool ext_want[N_EXT_REPORTS] = {}, ext_run[N_EXT_REPORTS] = {};
@@ -190,6 +203,7 @@ struct ReportPlan {
     bool ext9_want[N_EXT9_REPORTS] = {}, ext9_run[N_EXT9_REPORTS] = {};
     bool ext10_want[N_EXT10_REPORTS] = {}, ext10_run[N_EXT10_REPORTS] = {};
     bool ext11_want[N_EXT11_REPORTS] = {}, ext11_run[N_EXT11_REPORTS] = {};
+    bool ext12_want[N_EXT12_REPORTS] = {}, ext12_run[N_EXT12_REPORTS] = {};
     uint64_t ct_window = 10000;                       // window of the coverage track in bases
     uint32_t nm_top = 5;                              // candidates the near-miss report prints per species
     uint32_t bs_replicates = 100;                     // resamples of the bootstrap report
@@ -205,6 +219,8 @@ struct ReportPlan {
     uint64_t lk_top = 10;                             // breaks the link support report prints per strain
     uint32_t rf_levels = 5, rf_replicates = 5;        // thinned levels and replicates per level of the rarefaction report
     uint64_t rf_seed = 42;                            // ... and the seed of its thinning rule
+    uint64_t gr_window = 5000;                        // window of the replication index report in bases
+    uint64_t gr_min_own = 500, gr_trim = 100;         // own bases a window needs, in thousandths of the window; windows trimmed from each end, in thousandths
     bool any_run() const {
         for (const bool r : run) if (r) return true;
         for (const bool r : pair_run) if (r) return true;
@@ -219,6 +235,7 @@ struct ReportPlan {
         for (const bool r : ext9_run) if (r) return true;
         for (const bool r : ext10_run) if (r) return true;
         for (const bool r : ext11_run) if (r) return true;
+        for (const bool r : ext12_run) if (r) return true;
         return false;
     }
     bool rows_run() const {
@@ -235,6 +252,7 @@ struct ReportPlan {
         for (int i = 0; i < N_EXT9_REPORTS; ++i) if (ext9_run[i] && EXT9_REPORTS[i].rows) return true;
         for (int i = 0; i < N_EXT10_REPORTS; ++i) if (ext10_run[i] && EXT10_REPORTS[i].rows) return true;
         for (int i = 0; i < N_EXT11_REPORTS; ++i) if (ext11_run[i] && EXT11_REPORTS[i].rows) return true;
+        for (int i = 0; i < N_EXT12_REPORTS; ++i) if (ext12_run[i] && EXT12_REPORTS[i].rows) return true;
         return false;
     }
 };
@@ -242,9 +260,9 @@ struct ReportPlan {
 // rows of the GAF on the rank of their byte range -- not joined here.  false: the first failing check in table order (REPORTS, then
 // PAIR_REPORTS), its message in err (E_INVALID)
 bool plan_reports(const pantax_hip_profiling_config *cfg, int W, bool sharded, ReportPlan &plan, std::string &err);
-// behind plan_reports, on the same plan: ext -> ext_path and ext_want, then ext2_path and ext2_want (the fields of pantax_hip_profile_ext2 behind it), then ext3_path and ext3_want (pantax_hip_profile_ext3), then ext4_path and ext4_want (pantax_hip_profile_ext4), then ext5_path and ext5_want (pantax_hip_profile_ext5), then ext6_path and ext6_want (pantax_hip_profile_ext6), then ext7_path and ext7_want (pantax_hip_profile_ext7), then ext8_path and ext8_want (pantax_hip_profile_ext8), then ext9_path and ext9_want (pantax_hip_profile_ext9), then ext10_path and ext10_want (pantax_hip_profile_ext10), then ext11_path and ext11_want (pantax_hip_profile_ext11), by the same rule and with the same refusal wording.  ext == null: all off; a field
-// that does not lie wholly inside ext->struct_size reads as off (the bootstrap report's replicates: 100, its seed: 42; the add-one report's top: 5; the read class report's classes: 10, its iterations: 1000; the segment report's min: 1000, its bridge: 100, its peak factor: 10; the mosaic read report's top: 10; the read rescue report's top: 5; the link support report's top: 10; the rarefaction report's levels: 5, its replicates: 5, its seed: 42); false also for a struct_size below 8
-// or not a multiple of 8, for more than 2^32 - 2 replicates of a wanted bootstrap report, and for more than 16 levels or 2^28 - 1 replicates of a wanted rarefaction report
+// behind plan_reports, on the same plan: ext -> ext_path and ext_want, then ext2_path and ext2_want (the fields of pantax_hip_profile_ext2 behind it), then ext3_path and ext3_want (pantax_hip_profile_ext3), then ext4_path and ext4_want (pantax_hip_profile_ext4), then ext5_path and ext5_want (pantax_hip_profile_ext5), then ext6_path and ext6_want (pantax_hip_profile_ext6), then ext7_path and ext7_want (pantax_hip_profile_ext7), then ext8_path and ext8_want (pantax_hip_profile_ext8), then ext9_path and ext9_want (pantax_hip_profile_ext9), then ext10_path and ext10_want (pantax_hip_profile_ext10), then ext11_path and ext11_want (pantax_hip_profile_ext11), then ext12_path and ext12_want (pantax_hip_profile_ext12), by the same rule and with the same refusal wording.  ext == null: all off; a field
+// that does not lie wholly inside ext->struct_size reads as off (the bootstrap report's replicates: 100, its seed: 42; the add-one report's top: 5; the read class report's classes: 10, its iterations: 1000; the segment report's min: 1000, its bridge: 100, its peak factor: 10; the mosaic read report's top: 10; the read rescue report's top: 5; the link support report's top: 10; the rarefaction report's levels: 5, its replicates: 5, its seed: 42; the replication index report's window: 5000, its min_own: 500, its trim: 100); false also for a struct_size below 8
+// or not a multiple of 8, for more than 2^32 - 2 replicates of a wanted bootstrap report, and for more than 16 levels or 2^28 - 1 replicates of a wanted rarefaction report, and for a min_own above 1000 or a trim of 500 or more thousandths of a wanted replication index report
 bool plan_ext_reports(const pantax_hip_profile_ext *ext, int W, bool sharded, ReportPlan &plan, std::string &err);
 // run[] from want[]: a wanted report is written by a call that runs a strain step
 void resume_reports(ReportPlan &plan, bool strain, bool full_path, bool strain_done);

@@ -20,6 +20,7 @@
 //   28 n_win                                                 the four output arrays (zero fill, atomics, download)
 #include <algorithm>
 #include "common.hpp"
+#include "cov_track_plan.hpp"
 #include "cov_track_tile.hpp"
 #include "primitives.hpp"
 #include "wave.hpp"
@@ -28,8 +29,7 @@ namespace ptx {
 
 namespace {
 
-// (CT_TILE, CtTile, ct_load_ids and ct_incl_scan64: cov_track_tile.hpp, shared with stage_segments.hip)
-struct CtTileOut { uint64_t base, out0, n_win; };             // o of position p0; first output window of the haplotype; its number of windows
+// (CT_TILE, CtTile, CtTileOut, ct_load_ids and ct_incl_scan64: cov_track_tile.hpp, shared with stage_segments.hip and stage_growth.hip)
 
 __global__ void __launch_bounds__(256) cov_track_len_kernel(uint32_t n_tiles, const CtTile *__restrict__ tiles, const uint32_t *__restrict__ path_nodes,
                                                             const uint32_t *__restrict__ node_len, unsigned long long *__restrict__ tile_sum) {
@@ -46,42 +46,7 @@ __global__ void __launch_bounds__(256) cov_track_len_kernel(uint32_t n_tiles, co
     }
 }
 
-// the four sums of a run of steps of one window
-struct CtAcc { uint32_t n; unsigned long long len, cov, bases; };
-
-// inclusive sum over the lanes [seg, lane] (seg <= lane: the first lane of my segment); all 64 lanes active.  The steps of seg_and (stage_read_strain.hip):
-// a lane takes a value only from a source lane of its own segment; lanes a row operation does not reach read zero.
-__device__ __forceinline__ void ct_seg_scan(CtAcc &a, int lane, int seg) {
-#define CT_MOVE(x, CTRL, RM, BC) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(x), CTRL, RM, 0xF, BC))
-#define CT_STEP(CTRL, RM, BC, SRC)                                                                                                             \
-    {                                                                                                                                          \
-        const uint32_t tn = CT_MOVE(a.n, CTRL, RM, BC);                                                                                        \
-        const unsigned long long tlen = ((unsigned long long)CT_MOVE((uint32_t)(a.len >> 32), CTRL, RM, BC) << 32) | CT_MOVE((uint32_t)a.len, CTRL, RM, BC);       \
-        const unsigned long long tcov = ((unsigned long long)CT_MOVE((uint32_t)(a.cov >> 32), CTRL, RM, BC) << 32) | CT_MOVE((uint32_t)a.cov, CTRL, RM, BC);       \
-        const unsigned long long tbas = ((unsigned long long)CT_MOVE((uint32_t)(a.bases >> 32), CTRL, RM, BC) << 32) | CT_MOVE((uint32_t)a.bases, CTRL, RM, BC);   \
-        const bool take = (SRC) >= seg;                                                                                                        \
-        a.n += take ? tn : 0u; a.len += take ? tlen : 0ull; a.cov += take ? tcov : 0ull; a.bases += take ? tbas : 0ull;                        \
-    }
-    CT_STEP(0x111, 0xF, true, lane - 1)
-    CT_STEP(0x112, 0xF, true, lane - 2)
-    CT_STEP(0x114, 0xF, true, lane - 4)
-    CT_STEP(0x118, 0xF, true, lane - 8)
-    CT_STEP(0x142, 0xA, false, (lane & ~15) - 1)   // rows 1 and 3 <- lanes 15 and 47
-    CT_STEP(0x143, 0xC, false, 31)                 // rows 2 and 3 <- lane 31
-#undef CT_STEP
-#undef CT_MOVE
-}
-
-struct CtOut { uint32_t *n; unsigned long long *len, *cov, *bases; };
-
-// window w of the haplotype whose windows start at out0; guarded by the haplotype's window count (a live step always lies below it: node lengths are > 0)
-__device__ __forceinline__ void ct_add(const CtOut &o, uint64_t out0, uint64_t n_win, bool on, uint64_t w, const CtAcc &a) {
-    if (on & (w < n_win)) {
-        const uint64_t i = out0 + w;
-        atomicAdd(o.n + i, a.n); atomicAdd(o.len + i, a.len); atomicAdd(o.cov + i, a.cov); atomicAdd(o.bases + i, a.bases);
-    }
-}
-
+// (CtAcc, ct_seg_scan, CtOut and ct_add: cov_track_tile.hpp, shared with stage_growth.hip)
 __global__ void __launch_bounds__(256) cov_track_accum_kernel(uint32_t n_tiles, const CtTile *__restrict__ tiles, const CtTileOut *__restrict__ touts,
                                                               const uint32_t *__restrict__ path_nodes, const uint32_t *__restrict__ node_len,
                                                               const uint32_t *__restrict__ cov, const unsigned long long *__restrict__ bases, uint64_t W, CtOut out) {
@@ -136,10 +101,10 @@ __global__ void __launch_bounds__(256) cov_track_accum_kernel(uint32_t n_tiles, 
 
 }  // namespace
 
-// sel_off [S+1], sel_hap validated by the caller (in range, no repeats).  win_off_out [C+1] is always written; more than `cap` windows: PANTAX_HIP_E_LIMIT
-// and nothing else is touched.
-int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, uint32_t *n_nodes_out,
-                     uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out) {
+// The tiles of the selected walks, the length pass over them and the host scan of its sums per haplotype (base offset of every tile, G_h, n_win):
+// win_off_out [C+1] is written, the tiles and their output records are left on the device.  `who` names the caller in messages (cov_track_launch here,
+// growth_launch in stage_growth.hip).
+int cov_track_plan(Ctx *ctx, Db *db, const char *who, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, CtPlan &pl) {
     const uint32_t S = db->S;
     const uint64_t C = sel_off[S];
     std::vector<CtTile> tiles;
@@ -154,17 +119,16 @@ int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
             }
             tile_first[c + 1] = tiles.size();
         }
-    if (tiles.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_cov_track: %llu tiles of selected walks exceed 32-bit positions", (unsigned long long)tiles.size());
+    if (tiles.size() >= 0xFFFFFFFFull) return fail(ctx, PANTAX_HIP_E_LIMIT, "%s: %llu tiles of selected walks exceed 32-bit positions", who, (unsigned long long)tiles.size());
     const uint32_t n_tiles = (uint32_t)tiles.size();
-    DevBuf<CtTile> d_tiles;
     DevBuf<unsigned long long> d_sum;
     std::vector<unsigned long long> sums(n_tiles);
     if (n_tiles) {
-        PTX_TRY(upload(ctx, d_tiles, tiles.data(), tiles.size()));
+        PTX_TRY(upload(ctx, pl.d_tiles, tiles.data(), tiles.size()));
         PTX_HIP(ctx, d_sum.alloc(n_tiles));
         {
             KTimer tm(ctx, "cov_track_len_kernel");
-            hipLaunchKernelGGL(cov_track_len_kernel, dim3(grid_for(n_tiles, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_tiles, d_tiles.p, db->d_path_nodes.p,
+            hipLaunchKernelGGL(cov_track_len_kernel, dim3(grid_for(n_tiles, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_tiles, pl.d_tiles.p, db->d_path_nodes.p,
                                db->d_node_len.p, d_sum.p);
         }
         PTX_HIP(ctx, hipGetLastError());
@@ -181,23 +145,35 @@ int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *
         for (uint64_t t = tile_first[c]; t < tile_first[c + 1]; ++t) { touts[t].out0 = win_off_out[c]; touts[t].n_win = n_win; }
         win_off_out[c + 1] = win_off_out[c] + n_win;
     }
+    pl.n_tiles = n_tiles;
+    pl.tile_first = std::move(tile_first);
     const uint64_t N = win_off_out[C];
-    if (N > cap) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_cov_track: the selection has %llu windows, the output arrays hold %llu (win_off_out is filled: size the arrays by it)",
+    if (N > cap) return fail(ctx, PANTAX_HIP_E_LIMIT, "%s: the selection has %llu windows, the output arrays hold %llu (win_off_out is filled: size the arrays by it)", who,
                              (unsigned long long)N, (unsigned long long)cap);
+    if (N) PTX_TRY(upload(ctx, pl.d_touts, touts.data(), touts.size()));
+    return 0;
+}
+
+// sel_off [S+1], sel_hap validated by the caller (in range, no repeats).  win_off_out [C+1] is always written; more than `cap` windows: PANTAX_HIP_E_LIMIT
+// and nothing else is touched.
+int cov_track_launch(Ctx *ctx, Db *db, const uint64_t *sel_off, const uint32_t *sel_hap, uint64_t W, uint64_t *win_off_out, uint64_t cap, uint32_t *n_nodes_out,
+                     uint64_t *len_out, uint64_t *covered_out, uint64_t *bases_out) {
+    CtPlan pl;
+    PTX_TRY(cov_track_plan(ctx, db, "strain_cov_track", sel_off, sel_hap, W, win_off_out, cap, pl));
+    const uint64_t N = win_off_out[sel_off[db->S]];
+    const uint32_t n_tiles = pl.n_tiles;
     if (N == 0) return 0;
     if (!n_nodes_out || !len_out || !covered_out || !bases_out) return fail(ctx, PANTAX_HIP_E_INVALID, "strain_cov_track: null output array");
     if (N > (~(size_t)0) / 32) return fail(ctx, PANTAX_HIP_E_LIMIT, "strain_cov_track: %llu windows", (unsigned long long)N);
     // one device block, zero-filled once: [len N u64][covered N u64][bases N u64][n_nodes N u32]
     DevBuf<uint8_t> d_out;
-    DevBuf<CtTileOut> d_touts;
     PTX_HIP(ctx, d_out.alloc((size_t)N * 28));
     PTX_TRY(zero_fill(ctx, d_out.p, (size_t)N * 28));
-    PTX_TRY(upload(ctx, d_touts, touts.data(), touts.size()));
     unsigned long long *o64 = reinterpret_cast<unsigned long long *>(d_out.p);
     const CtOut out{reinterpret_cast<uint32_t *>(o64 + 3 * N), o64, o64 + N, o64 + 2 * N};
     {
         KTimer tm(ctx, "cov_track_accum_kernel");
-        hipLaunchKernelGGL(cov_track_accum_kernel, dim3(grid_for(n_tiles, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_tiles, d_tiles.p, d_touts.p,
+        hipLaunchKernelGGL(cov_track_accum_kernel, dim3(grid_for(n_tiles, 4, ctx->n_cu * 16)), dim3(256), 0, ctx->stream, n_tiles, pl.d_tiles.p, pl.d_touts.p,
                            db->d_path_nodes.p, db->d_node_len.p, db->d_cov.p, db->d_bases.p, W, out);
     }
     PTX_HIP(ctx, hipGetLastError());

@@ -477,6 +477,27 @@ class Engine:
             self._check(self.lib.pantax_hip_strain_cov_track(self.ctx, self.db, C.byref(cs), p(win_off), n, p(n_nodes), p(ln), p(covered), p(bases)))
         return win_off, n_nodes, ln, covered, bases
 
+    def strain_growth(self, sel_off, sel_hap, window):
+        """Own-node windows along selected haplotypes (pantax_hip_strain_growth) of the coverage result get_node_abundances left on the device: the input
+        of growth_fit.  sel_off [S+1], sel_hap (species-local haplotype indices, no repeats within a species), window W >= 1 in bases ->
+        (win_off uint64 [C+1], n_own uint32, len, len_own, bases_own uint64): the windows of selection entry c are [win_off[c], win_off[c+1]); a step is
+        own when no other selected haplotype of its species walks its node."""
+        so = as_c(sel_off, np.uint64)
+        sh = as_c(sel_hap, np.uint32)
+        if len(so) != self.S + 1 or len(sh) != int(so[-1]):
+            raise ValueError("strain_growth: sel_off needs S + 1 entries and sel_hap sel_off[-1]")
+        cs = _ffi.CovTrackSet(self.S, so.ctypes.data, sh.ctypes.data if len(sh) else None, int(window))
+        win_off = np.zeros(len(sh) + 1, dtype=np.uint64)
+        rc = self.lib.pantax_hip_strain_growth(self.ctx, self.db, C.byref(cs), p(win_off), 0, None, None, None, None)   # sizes the arrays
+        if rc != _ffi.E_LIMIT:
+            self._check(rc)
+        n = int(win_off[-1])
+        n_own = np.zeros(n, dtype=np.uint32)
+        ln, len_own, bases_own = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        if n:
+            self._check(self.lib.pantax_hip_strain_growth(self.ctx, self.db, C.byref(cs), p(win_off), n, p(n_own), p(ln), p(len_own), p(bases_own)))
+        return win_off, n_own, ln, len_own, bases_own
+
     def strain_segments(self, sel_off, sel_hap, peak_depth, min_len):
         """Absent and amplified segments along selected haplotypes (pantax_hip_strain_segments) of the coverage result get_node_abundances left on the
         device.  sel_off [S+1], sel_hap (species-local haplotype indices, no repeats within a species), peak_depth (one uint64 per entry, or one number
@@ -910,7 +931,8 @@ class Engine:
                 strain_segments_file=None, strain_segments_min=0, strain_segments_bridge=None, strain_segments_peak=0,
                 strain_mosaic_file=None, strain_mosaic_top=0, strain_rescue_file=None, strain_rescue_top=0,
                 strain_links_file=None, strain_links_top=0,
-                strain_rarefy_file=None, strain_rarefy_levels=0, strain_rarefy_replicates=0, strain_rarefy_seed=42, strain_fragments_file=None):
+                strain_rarefy_file=None, strain_rarefy_levels=0, strain_rarefy_replicates=0, strain_rarefy_seed=42, strain_fragments_file=None,
+                strain_growth_file=None, strain_growth_window=0, strain_growth_min_own=0, strain_growth_trim=0):
         """profile::profile(ProfilingConfig) (profile.rs:3325): files in, files out.  allreduce(float64 array) sums in place over
         the ranks; alltoallv(send uint8 array, send_off [W+1], recv uint8 array, recv_off [W+1]) moves bytes between the ranks
         (host buffers) and switches on the sharded ingest.  read_strain_file: path of the per-read strain report
@@ -934,7 +956,10 @@ class Engine:
         strain_links_file: path of the link support report (--strain-links; one rank only), strain_links_top the breaks it prints per strain (0: 10).
         strain_rarefy_file: path of the rarefaction report (--strain-rarefy; one rank only), strain_rarefy_levels the thinned levels 1/2 .. 2^-N (0: 5; at
         most 16), strain_rarefy_replicates the replicates per level (0: 5), strain_rarefy_seed the seed of the thinning rule.
-        strain_fragments_file: path of the fragment support report (--strain-fragments; one rank only)."""
+        strain_fragments_file: path of the fragment support report (--strain-fragments; one rank only).
+        strain_growth_file: path of the replication index report (--strain-growth; one rank only), strain_growth_window its window in bases (0: 5000),
+        strain_growth_min_own the own bases a window needs in thousandths of the window (0: 500), strain_growth_trim the windows trimmed from each end of
+        the sorted range in thousandths (0: 100; below 500)."""
         enc = lambda x: None if x is None else str(x).encode()
         cfg = _ffi.ProfilingConfig(
             db=enc(db), wd=enc(wd), output_dir=enc(output_dir or wd), genomes_metadata=None, range_file=enc(range_file),
@@ -977,7 +1002,7 @@ class Engine:
             cb2 = _ffi.ALLTOALLV_FN(_cb2)
             cfg.alltoallv = C.cast(cb2, C.c_void_p)
             cfg.comm_device_buffers = 0
-        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None and strain_links_file is None and strain_rarefy_file is None and strain_fragments_file is None:
+        if strain_fit_file is None and strain_bootstrap_file is None and strain_dropout_file is None and strain_addin_file is None and strain_em_file is None and strain_segments_file is None and strain_mosaic_file is None and strain_rescue_file is None and strain_links_file is None and strain_rarefy_file is None and strain_fragments_file is None and strain_growth_file is None:
             self._check(self.lib.pantax_hip_profile(self.ctx, C.byref(cfg)))
         else:   # the outputs behind the config's last field travel in the sized extension
             ext = _ffi.ProfileExt(struct_size=C.sizeof(_ffi.ProfileExt), strain_fit_file=enc(strain_fit_file), strain_bootstrap_file=enc(strain_bootstrap_file),
@@ -993,7 +1018,9 @@ class Engine:
                                   strain_links_file=enc(strain_links_file), strain_links_top=int(strain_links_top),
                                   strain_rarefy_file=enc(strain_rarefy_file), strain_rarefy_levels=int(strain_rarefy_levels),
                                   strain_rarefy_replicates=int(strain_rarefy_replicates), strain_rarefy_seed=int(strain_rarefy_seed),
-                                  strain_fragments_file=enc(strain_fragments_file))
+                                  strain_fragments_file=enc(strain_fragments_file), strain_growth_file=enc(strain_growth_file),
+                                  strain_growth_window=int(strain_growth_window), strain_growth_min_own_permille=int(strain_growth_min_own),
+                                  strain_growth_trim_permille=int(strain_growth_trim))
             self._check(self.lib.pantax_hip_profile_with_ext(self.ctx, C.byref(cfg), C.byref(ext)))
 
     def db_pairs(self, db, out_file, species=None, max_distance=None, zip="serialize", range_file=None):
@@ -1175,6 +1202,30 @@ def read_em(mask, b, length, max_iter=1000, tol=1e-6):
     if _ffi.load().pantax_hip_read_em(len(ln), len(m), p(m), p(bb), p(ln), int(max_iter), float(tol), p(x), C.byref(n_iter), C.byref(conv), C.byref(delta)) != 0:
         raise ValueError("read_em: refused")
     return x, int(n_iter.value), int(conv.value), float(delta.value)
+
+
+GROWTH_STATUS = ("ok", "empty", "few_windows", "low_depth", "flat")   # PANTAX_HIP_GROWTH_*: the names the report prints
+
+
+def growth_fit(len_own, bases_own, min_own, trim_permille=100, min_windows=_ffi.GROWTH_MIN_WINDOWS, min_depth=_ffi.GROWTH_MIN_DEPTH):
+    """pantax_hip_growth_fit: the replication index over the own-node windows of ONE selection entry (Engine.strain_growth) -- keep the windows with
+    len_own >= min_own, sort by depth as an exact rational, drop what lies outside [median / 8, median x 8], trim trim_permille thousandths from each
+    end, fit log2 depth against rank.  -> dict(n_kept, n_zero, n_f, n_fit, own_len, median_depth, slope, intercept, r2, index, status), status one of
+    GROWTH_STATUS.  ValueError where the library refuses (trim_permille >= 500, min_own = 0)."""
+    ln = as_c(len_own, np.uint64)
+    bs = as_c(bases_own, np.uint64)
+    if len(ln) != len(bs):
+        raise ValueError("growth_fit: the two arrays are of one length")
+    if int(min_own) < 0 or int(trim_permille) < 0 or int(min_windows) < 0:
+        raise ValueError("growth_fit: negative parameter")
+    out = _ffi.GrowthFitResult()
+    lib = _ffi.load()
+    if lib.pantax_hip_growth_fit(len(ln), ln.ctypes.data if len(ln) else None, bs.ctypes.data if len(bs) else None, int(min_own), int(trim_permille),
+                                 int(min_windows), float(min_depth), C.byref(out)) != 0:
+        raise ValueError("growth_fit: refused")
+    r = {k: getattr(out, k) for k in ("n_kept", "n_zero", "n_f", "n_fit", "own_len", "median_depth", "slope", "intercept", "r2", "index")}
+    r["status"] = lib.pantax_hip_growth_status_name(out.status).decode()
+    return r
 
 
 def segment_chain(seg_class, seg_start, seg_len, seg_n_steps, seg_bases, bridge, min_span):
